@@ -9,7 +9,12 @@ starts; a step is  [halo exchange (N>1 only)] -> GShiftNet.forward -> restored f
 N > 1: launched by torch.distributed.run, one rank per GPU; windows are independent (weak scaling), the only
 communication is the all-gather of the 2+2 halo frames (shiftnet_amd/clip_parallel.py).
 
-Prints ONE JSON line on rank 0 (see the repository prompt / DESIGN.md "Measurement" for the field definitions).
+Prints ONE JSON line on rank 0 (DESIGN.md "Measurement" for the field definitions).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the headline line (frames/s,
+ms_per_step and its per-step spread).  `--full` adds what takes work or runs of its own: host <-> device transfer times, one extra
+per-kernel profiling step with the roofline / PMC traffic figures, the parity sample against the CPU oracle and the CPU baseline.
+`--dump-outputs DIR` writes the restored frames of the last timed step to DIR as float32 .npy files (dump_outputs below).
 """
 import argparse
 import json
@@ -187,6 +192,31 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_BYTES = 48 << 20          # --dump-outputs: float32 bytes written per run, all files together
+
+
+def dump_outputs(d, outs, rank, world):
+    """--dump-outputs: the restored frames the last timed step returned, as float32 .npy files in `d` (exact: bf16 / fp16 / fp32 all fit).
+    One file per output tensor: restored_frames[_q<quadrant>][_rank<rank>].npy.  A tensor larger than its share of DUMP_BYTES is written
+    as a fixed sample: its elements at flat indices drawn by a generator of fixed seed (the same shape gives the same indices), in index
+    order, as a 1-D array.  Returns {file: (shape, elements written)}."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // 4 // (len(outs) * world)
+    done = {}
+    for i, o in enumerate(outs):
+        name = "restored_frames" + (f"_q{i}" if len(outs) > 1 else "") + (f"_rank{rank}" if world > 1 else "")
+        flat = o.detach().reshape(-1)
+        if flat.numel() > share:
+            idx = np.unique(np.random.default_rng(20240901).integers(0, flat.numel(), share, dtype=np.int64))
+            arr = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+        else:
+            arr = o.detach().float().cpu().numpy()
+        np.save(os.path.join(d, name + ".npy"), arr)
+        done[name + ".npy"] = (list(o.shape), int(arr.size))
+    return done
+
+
 def cpu_baseline_subprocess(timeout_s=240):
     """Run the CPU leg in a child with a hard timeout so that the bench line is always produced."""
     import subprocess
@@ -265,7 +295,14 @@ def main():
                     help="N > 1: form of the halo exchange -- point to point to the two neighbour ranks, the all-gather of every rank's edge frames, or "
                          "(default) point to point with an automatic, logged fall-back to the all-gather form if the first exchange fails")
     ap.add_argument("--lib", default=None, help="A/B measurements only: another build of libshiftnet_hip.so (the line then carries its path)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure host transfers, one per-kernel profiling step (roofline, PMC traffic), the parity "
+                         "sample and the CPU baseline (the last two unless --no-parity / --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the restored frames of the last timed step to DIR as float32 .npy (a fixed sample beyond 48 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.lib:
         from shiftnet_amd import lib as _L
         _L.LIB_PATH = os.path.abspath(args.lib)
@@ -414,8 +451,12 @@ def main():
         own_elapsed = time.perf_counter() - t0          # this rank alone, before it waits for the others
         barrier()
         elapsed = time.perf_counter() - t0
-    for o in (out if isinstance(out, list) else [out]):
+    outs_last = out if isinstance(out, list) else [out]
+    for o in outs_last:
         assert o.shape == (L, 3, hh, ww) and torch.isfinite(o.float()).all()
+    if args.dump_outputs:
+        for f, (shape, n) in dump_outputs(args.dump_outputs, outs_last, rank, world).items():
+            log(f"rank {rank}: wrote {os.path.join(args.dump_outputs, f)}: output {shape}, {n} float32 values")
     per_rank = None
     if world > 1:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -431,12 +472,41 @@ def main():
                                  "on the compute stream after decoding: its rate per window is this ms_per_step + halo_exchange_ms"}
 
     result = None
+    dlabel = {"bf16": "bf16", "fp16": "fp16", "fp32": "fp32"}[args.dtype]
     if rank == 0:
-        log(f"timed {args.steps} steps in {elapsed:.3f} s; profiling one extra step with stream events")
+        log(f"timed {args.steps} steps in {elapsed:.3f} s")
         ms = elapsed / args.steps * 1e3
         fps = world * L * args.steps / elapsed
         step_ms = sorted(a.elapsed_time(b) for a, b in step_ev)
         ms_median = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
+        result = {
+            "metric": f"restored frames/sec at {w}x{h} T={L} {dlabel}", "value": round(fps, 3), "unit": "frames/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "ms_per_step_median": round(ms_median, 3),
+            "ms_per_step_min_max": [round(step_ms[0], 3), round(step_ms[-1], 3)],
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "data": "synthetic",
+            # module dtype; fp16 / bf16 modules both compute with bf16 storage + fp32 accumulation (DESIGN.md section 6)
+            "dtype": {"bf16": "bf16", "fp16": "fp16 module on bf16 storage",
+                      "fp32": "f32 exact (fp32 products)" if args.fp32_exact else "f32 (bf16 hi+lo split products, fp32 accumulation)"}[args.dtype],
+            "config": {"workload": f"{'Shift-Net-s' if args.variant.endswith('2') else 'Shift-Net+'} ({args.variant}), {w}x{h}, one_len={L} (T_in={L + 4}), "
+                                   + ("as the denoise CLI's 4 quadrants of %dx%d, " % (ww, hh) if args.quadrants else "")
+                                   + (f"module dtype {args.dtype}, " if args.dtype != "bf16" else "")
+                                   + "one window per GPU, synthetic checkpoint", "parallelism": f"clip-parallel x{world}",
+                       "baseline_config": args.config if args.config is not None else (2 if (args.variant, h, w, L) == (VARIANT, H, W, ONE_LEN) else None),
+                       **({"ab_library": args.lib} if args.lib else {}),
+                       **({"one_quadrant_only": "profiling run: a quarter of the window's work per step"} if args.one_quadrant else {}),
+                       "gsts_schedule": {"unit": "unit-major, one stream", "frame": f"frame wavefront on one stream, groups of {net.prepare().frame_group}",
+                                         "streams": f"{net.prepare().stream_groups} frame groups on concurrent HIP streams"}[getattr(net.prepare(), "schedule", "unit")]},
+            # high-water mark of this rank's device allocations over warm-up and timed steps (PyTorch caching allocator: every activation of a
+            # window is a torch tensor): how much of the 288 GB a window of this configuration occupies
+            "peak_device_memory_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 2),
+        }
+        if per_rank is not None:
+            result["per_rank"] = per_rank
+        if world > 1 and os.environ.get("SN_BENCH_SHARED_DEVICE_TEST") == "1":
+            result["shared_device_test"] = True        # all ranks on one GPU: a rank-flow test, not a measurement
+
+    if rank == 0 and args.full:
+        log("--full: host transfers, then one extra step profiled with stream events")
         # Host <-> device transfers of a window as the CLIs ship it (uint8 frames in, uint8 restored frames out; pinned host buffers), measured here,
         # NOT part of `value` ("excluded but reported")
         hin = torch.empty((L + 4, h, w, 3), dtype=torch.uint8).pin_memory()
@@ -574,24 +644,8 @@ def main():
                        "gbps_algorithmic": round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1)} for k, v in agg.items()}
         sbytes = 4 if dt == torch.float32 else 2
         win_bytes = len(quads) * algorithmic_bytes_window(args.variant, hh, ww, L + 4, L, s=sbytes)
-        dlabel = {"bf16": "bf16", "fp16": "fp16", "fp32": "fp32"}[args.dtype]
-        result = {
-            "metric": f"restored frames/sec at {w}x{h} T={L} {dlabel}", "value": round(fps, 3), "unit": "frames/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "ms_per_step_median": round(ms_median, 3),
-            "ms_per_step_min_max": [round(step_ms[0], 3), round(step_ms[-1], 3)], "host_transfers": xfer,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "data": "synthetic",
-            # module dtype; fp16 / bf16 modules both compute with bf16 storage + fp32 accumulation (DESIGN.md section 6)
-            "dtype": {"bf16": "bf16", "fp16": "fp16 module on bf16 storage",
-                      "fp32": "f32 exact (fp32 products)" if args.fp32_exact else "f32 (bf16 hi+lo split products, fp32 accumulation)"}[args.dtype],
-            "config": {"workload": f"{'Shift-Net-s' if args.variant.endswith('2') else 'Shift-Net+'} ({args.variant}), {w}x{h}, one_len={L} (T_in={L + 4}), "
-                                   + ("as the denoise CLI's 4 quadrants of %dx%d, " % (ww, hh) if args.quadrants else "")
-                                   + (f"module dtype {args.dtype}, " if args.dtype != "bf16" else "")
-                                   + "one window per GPU, synthetic checkpoint", "parallelism": f"clip-parallel x{world}",
-                       "baseline_config": args.config if args.config is not None else (2 if (args.variant, h, w, L) == (VARIANT, H, W, ONE_LEN) else None),
-                       **({"ab_library": args.lib} if args.lib else {}),
-                       **({"one_quadrant_only": "profiling run: a quarter of the window's work per step"} if args.one_quadrant else {}),
-                       "gsts_schedule": {"unit": "unit-major, one stream", "frame": f"frame wavefront on one stream, groups of {net.prepare().frame_group}",
-                                         "streams": f"{net.prepare().stream_groups} frame groups on concurrent HIP streams"}[getattr(net.prepare(), "schedule", "unit")]},
+        result.update({
+            "host_transfers": xfer,
             # the roofline this path is graded on is the FUSED GSTS UNIT (channel_shift + CAB2 + CAB1: read x, write y per
             # CAB = 4 T C h w s bytes) over the time of every GSTS kernel; intermediates count zero bytes.
             "roofline": {"bound": "hbm", "scope": "fused GSTS unit (SURVEY.md 8d), all pyramid levels of one window", "achieved": round(ach_unit, 1),
@@ -621,14 +675,9 @@ def main():
                                    "traffic": (round(sum((2 * v["FETCH_SIZE_KB"] + v["WRITE_SIZE_KB"]) for v in pmc.values()) * 1024 / 1e9, 1) if pmc else None),
                                    "traffic_note": "GB per window, all of this library's kernels: " + pmc_note},
             "kernels": kernels,
-            # high-water mark of this rank's device allocations over warm-up, timed steps and the profiling step (PyTorch caching allocator: every
-            # activation of a window is a torch tensor): how much of the 288 GB a window of this configuration occupies
+            # now over warm-up, timed steps and the profiling step
             "peak_device_memory_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 2),
-        }
-        if per_rank is not None:
-            result["per_rank"] = per_rank
-        if world > 1 and os.environ.get("SN_BENCH_SHARED_DEVICE_TEST") == "1":
-            result["shared_device_test"] = True        # all ranks on one GPU: a rank-flow test, not a measurement
+        })
         if world == 1 and args.variant == VARIANT and args.dtype == "bf16" and not args.no_parity:
             # parity sample next to the throughput: the same module on a small clip vs the CPU oracle (checker only)
             from oracle import shiftnet_oracle as O

@@ -64,7 +64,7 @@ def test_rccl_halo_allgather_and_config5_window(rccl_world1):
 def test_bench_two_rank_flow_on_one_device():
     """`bench.py --gpus 2` end to end with both ranks on the box's single GPU (gloo transport, SN_BENCH_SHARED_DEVICE_TEST=1): the
     self-launch through torch.distributed.run, the halo all-gather in every step, the MAX-over-ranks timing, rank 0's local
-    profiling step (no collective the other rank is not in) and the final barrier must all complete; the line is marked as a
+    profiling step of --full (no collective the other rank is not in) and the final barrier must all complete; the line is marked as a
     shared-device test, never as a 2-GPU measurement."""
     import json
     import subprocess
@@ -73,8 +73,34 @@ def test_bench_two_rank_flow_on_one_device():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["SN_BENCH_SHARED_DEVICE_TEST"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--height", "144",
-                        "--width", "256", "--one-len", "4", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
+                        "--width", "256", "--one-len", "4", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
     assert d["n_gpus"] == 2 and d["shared_device_test"] is True and d["value"] > 0 and d["config"]["parallelism"] == "clip-parallel x2"
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run: the headline fields only (the --full extras absent), `steps` timed steps, and --dump-outputs
+    writing the last timed step's restored frames as float32 .npy -- the same values from two runs with the same arguments."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "SN_BENCH_SHARED_DEVICE_TEST")}
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--height", "144",
+                            "--width", "256", "--one-len", "4", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in line, k
+        assert line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "frames/s"
+        assert not {"roofline", "kernels", "host_transfers", "parity", "cpu_baseline"} & set(line)
+        a = np.load(d / "restored_frames.npy")
+        assert a.dtype == np.float32 and a.shape == (4, 3, 144, 256) and np.isfinite(a).all()
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1])

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Aggregate rocprofv3 --pmc counter CSVs (one directory per pass) of bench.py runs that contain ONLY full windows
-(bench.py --no-parity --no-cpu-baseline: the small parity clip of the default run would dilute every per-launch average).
+(bench.py --full --no-parity --no-cpu-baseline: the small parity clip of --full would dilute every per-launch average).
 
 usage: pmc_summary.py OUT.json WINDOWS NOTE DIR [DIR ...]
-    WINDOWS = windows in each traced run = warmup + steps + 1 (bench.py's extra per-kernel profiling step)
+    WINDOWS = windows in each traced run = warmup + steps + 1 (the extra per-kernel profiling step of bench.py --full; warmup + steps
+              without --full)
     each DIR holds the *counter_collection.csv of one --pmc pass (all passes must come from the same bench.py command line)
 
 Output: per kernel symbol the counter totals PER WINDOW (sum over the symbol's launches / WINDOWS) and the launches per window; the

@@ -8,7 +8,7 @@ mkdir -p scale_out
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 for N in 1 2 4 8; do
   if [ "$(python -c 'import torch; print(torch.cuda.device_count())')" -lt "$N" ]; then echo "only $(python -c 'import torch; print(torch.cuda.device_count())') device(s): stopping before N=$N"; break; fi
-  python bench.py --config 6 --gpus $N --steps $ST --warmup $WU --no-cpu-baseline > scale_out/cfg6_n$N.json 2> scale_out/cfg6_n$N.err
+  python bench.py --config 6 --gpus $N --steps $ST --warmup $WU --full --no-cpu-baseline > scale_out/cfg6_n$N.json 2> scale_out/cfg6_n$N.err
   python - "$N" <<'PY'
 import json, sys
 n = sys.argv[1]
