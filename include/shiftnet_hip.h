@@ -127,9 +127,12 @@ int sn_cab_ca(const float* partial, int nblk, int cpad, const void* mid, int cs,
  *      tile (csrc/sn_cabf.hip); 0 = the STREAMING form (csrc/sn_conv3p.hip: cabp_kernel -- persistent workgroups, a loader wave that moves the next
  *      (8 + 4) x 36 pixel regions HBM -> LDS with LDS-DMA, four compute waves: conv1 on the ring -> mid in LDS -> conv2 -> scale + x -> store;
  *      no res2; its statistics pass is sn_cab_stats on a descriptor WITHOUT SN_CONV_TILE_KERNEL, i.e. the streaming conv's own pool rows).
+ *      The streaming form also needs conv1->act == 1 with 0 <= conv1->prelu <= 1 (its PReLU is max(v, a v)): for any other slope
+ *      tile_rows = 0 returns SN_EINVAL -- after the caller has already run passes 1 and 2 -- while the tile forms (8 / 16) take every slope.
  * Both descriptors are those of the two-launch form (3x3, stride 1, pad 1, one input, cs_in == cs_out, NHWC); conv1->pool / conv1->out are only
- * read by sn_cab_stats.  Results are bit-identical to the two-launch form.  sn_cab_fused_supported: 1 when an instance for the pair exists
- * (16- and 24-channel storage), else 0 -- the caller then uses the two-launch form. */
+ * read by sn_cab_stats.  Results are bit-identical to the two-launch form.  sn_cab_fused_supported: 1 when an instance for the pair's GEOMETRY
+ * exists (16- and 24-channel storage), else 0 -- the caller then uses the two-launch form.  It does not look at the slope: a caller of the
+ * streaming form checks 0 <= conv1->prelu <= 1 itself before pass 1 (shiftnet_amd/engine.py: Engine._cab_fused). */
 int sn_cab_fused_supported(const sn_conv_desc* conv1, const sn_conv_desc* conv2);
 int sn_cab_stats(const sn_conv_desc* conv1, int lines_len, void* stream);
 int sn_cab_ca_lines(const float* partial, int nblk, int cpad, const void* lines, int lines_len, int cs, int c, int cr, int h, int w,

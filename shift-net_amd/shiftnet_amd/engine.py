@@ -400,10 +400,14 @@ class Engine:
         return d
 
     def _cab_fused(self, pre: str, x: Act, extra: Optional[Act], slope: float) -> Optional[Act]:
-        """CAB as sn_cab_stats -> sn_cab_ca_lines -> sn_cab_fused; None when the library has no fused instance for this width."""
+        """CAB as sn_cab_stats -> sn_cab_ca_lines -> sn_cab_fused; None when the library has no fused instance for this width or slope."""
         lib = self.lib
         T, h, w, cs = x.dims
         if h < 2 or w < 2:
+            return None
+        if self.cab_fused[0] == "p" and not 0.0 <= slope <= 1.0:
+            # the streaming form implements PReLU as max(v, a v), right for a slope in [0, 1] only (sn_cab_fused answers SN_EINVAL for any
+            # other), and sn_cab_fused_supported looks at geometry alone: decide before anything is launched -- the two-launch form is general
             return None
         d1 = self._conv_desc(pre + "body.0", x, prelu=slope)
         d2 = self._conv_desc(pre + "body.2", x)

@@ -169,6 +169,28 @@ def test_whole_net_fp32_vs_reference_fixture(name, golden_dir):
     assert isinstance(net.prepare(), Engine32)
 
 
+
+@pytest.mark.parametrize("name", ["gshift_deblur2", "gshift_denoise1"])
+def test_whole_net_fp32_prelu_edge_checkpoint(name):
+    """float32 module on the edge checkpoint (tests/prelu_edge.py: PReLU slopes -0.25 / 0 / 0.6 / 1 / 1.25) against a live fp32 O.forward.
+    csrc/sn_f32.hip has one PReLU form for every slope, so this pins the shared control flow on these weights independently of the bf16 paths."""
+    import importlib
+    from prelu_edge import edge_state_dict
+    mod = importlib.import_module(f"basicsr.models.archs.{name}")
+    V = O.VARIANTS[name]
+    sd = edge_state_dict(name)
+    blur, _ = synth.blurred_clip(7, 48, 64, seed=3)
+    x = O.frames_to_tensor(list(blur))
+    nm = torch.full((1, 7, 1, 48, 64), 30.0 / 255.0) if V.denoise else None
+    net = mod.GShiftNet(future_frames=2, past_frames=2)
+    net.load_state_dict(sd, strict=True)
+    net = net.to("cuda").eval()
+    with torch.no_grad():
+        out = net(x.cuda(), nm.cuda()) if V.denoise else net(x.cuda())
+        ref = O.forward(V, sd, x, nm, 2, 2)
+    assert torch.isfinite(ref).all()
+    close(f"net32_prelu_edge_{name}", out, ref)
+
 def test_config1_fp32(golden_dir):
     """BASELINE config 1 (Shift-Net-s, fp32, 1 clip of T=5 256x256): the reference's CPU-runnable case, here on the GPU in fp32."""
     from basicsr.models.archs.gshift_deblur2 import GShiftNet

@@ -30,6 +30,7 @@ from oracle import shiftnet_oracle as O
 from shiftnet_amd import prep, synth
 from shiftnet_amd.spec import VARIANTS, shift_table
 from shiftnet_amd.weights import synth_state_dict
+from prelu_edge import edge_state_dict, set_slope
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -1270,3 +1271,180 @@ def test_cab_phase1_fused_kernel_denoisers_two_passes(T, h, w, name, engines):
         torch.cuda.synchronize()
         assert torch.equal(g2_b.view(torch.int16), g2.view(torch.int16)), (name, mode, (g2_b.float() - g2.float()).abs().max().item())
         assert torch.equal(pool_b, pool), (name, mode)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# PReLU slopes outside [0, 1].  Every slope of the synthetic checkpoint is 0.25 +- 0.05, but the kernels branch on the VALUE: conv3_fast_kernel
+# (csrc/sn_conv.hip) and cab_fused_kernel (csrc/sn_cabf.hip) compute max(v, a v) for a slope in [0, 1] and fma(a, min(v, 0), max(v, 0)) for any
+# other; the streaming conv (csrc/sn_conv3p.hip) implements its PReLU + pool epilogue and the streaming fused CAB for [0, 1] only, and the
+# library / the engine must route other slopes elsewhere.  nn.PReLU does not constrain its weight: a trained checkpoint may hold any of these.
+PRELU_SLOPES = (-0.25, 0.0, 1.0, 1.25)          # both ends of the fast path's [0, 1] and one value outside on each side
+
+
+@pytest.mark.parametrize("case", list(CONV_CASES))
+@pytest.mark.parametrize("slope", PRELU_SLOPES)
+@pytest.mark.parametrize("tiles", [True, False])
+def test_conv_prelu_slopes(case, slope, tiles, engines):
+    """test_conv at the edges of [0, 1] and outside it, on the tile kernels (conv_tiles) and with the streaming kernel allowed: every conv
+    kernel's PReLU epilogue against F.prelu, ragged tiles, pad channels that must stay zero."""
+    name, key, wkey, cins, stride, pad = CONV_CASES[case]
+    eng, sd = engines(name)
+    e = _sibling_engine(eng, conv_tiles=tiles)
+    T, H, W = 2, 10, 36
+    xs = [bf(torch.from_numpy(synth.unit_noise((T, c, H, W), seed=151 + i))) for i, c in enumerate(cins)]
+    out = e.conv(key, [act(to_dev(x), c) for x, c in zip(xs, cins)], stride=stride, pad=pad, prelu=slope)
+    torch.cuda.synchronize()
+    ref = torch.nn.functional.conv2d(torch.cat(xs, 1), sd[wkey + "weight"], sd.get(wkey + "bias"), stride=stride, padding=pad)
+    ref = torch.nn.functional.prelu(ref, torch.tensor([slope]))
+    check(f"conv_prelu{slope}_{case}_{'tile' if tiles else 'stream'}_{H}x{W}", to_cpu(out.t, out.c), ref, 8e-3)
+    if out.t.shape[-1] > out.c:
+        assert out.t[..., out.c:].float().abs().max().item() == 0.0
+
+
+@pytest.mark.parametrize("name,pre,c", [("gshift_deblur2", "stage1.concat.", 14), ("gshift_deblur2", "orb1.encoder_level2.1.", 18),
+                                        ("gshift_deblur1", "orb1.encoder_level2.0.", 36), ("gshift_deblur2", "stage1.skip_attn1.", 64)])
+@pytest.mark.parametrize("slope", (0.2,) + PRELU_SLOPES)
+@pytest.mark.parametrize("T,hw", [(2, (37, 33)), (5, (72, 200))])
+def test_cab_first_conv_prelu_slopes_with_pool(name, pre, c, slope, T, hw, engines):
+    """The first conv of a CAB (3x3 + PReLU + channel sums of the activated map) on the streaming kernel -- for a slope outside [0, 1] the library
+    sends it to the tile kernel (c3p_mode) -- and on the tile kernel: the activations bit-identical to each other, and both the activations and
+    the pooled means within the kernel tolerance of the oracle (the pool rows must sum the ACTIVATED values)."""
+    eng, sd = engines(name)
+    new = _sibling_engine(eng, conv_tiles=False, conv_stream_all=True)
+    old = _sibling_engine(eng, conv_tiles=True)
+    x = act(to_dev(bf(torch.from_numpy(synth.unit_noise((T, c, hw[0], hw[1]), seed=152)))), c)
+    m_new, p_new, npix = new.conv(pre + "body.0", [x], prelu=slope, pool=True)
+    m_old, p_old, _ = old.conv(pre + "body.0", [x], prelu=slope, pool=True)
+    torch.cuda.synchronize()
+    assert torch.equal(m_new.t, m_old.t), (name, pre, slope, T, hw, (m_new.t.float() - m_old.t.float()).abs().max().item())
+    F = torch.nn.functional
+    ref = F.prelu(F.conv2d(to_cpu(x.t, c), bf(sd[pre + "body.0.weight"]), sd.get(pre + "body.0.bias"), padding=1), torch.tensor([slope]))
+    for tag, m, p in (("stream", m_new, p_new), ("tile", m_old, p_old)):
+        check(f"conv_pool_prelu{slope}_{tag}_{name}_{pre}_{T}x{hw[0]}x{hw[1]}", to_cpu(m.t, c), ref, 8e-3)
+        check(f"conv_pool_prelu{slope}_{tag}_{name}_{pre}_{T}x{hw[0]}x{hw[1]}_sums", p.sum(1)[:, :c] / npix, ref.mean((2, 3)), 8e-3)
+
+
+# gshift_deblur2 CABs with 16-channel storage (14 channels: fused instance key 1016) and 24-channel storage (18 channels: key 2024)
+CAB_EDGE = [("stage1.concat.", 14), ("orb1.encoder_level2.1.", 18)]
+CAB_FORMS = {"0_tile": dict(cab_fused="0", conv_tiles=True), "0_stream": dict(cab_fused="0", conv_tiles=False),
+             "8": dict(cab_fused="8", conv_tiles=False), "16": dict(cab_fused="16", conv_tiles=False),
+             "s8": dict(cab_fused="s8", conv_tiles=False), "p": dict(cab_fused="p", conv_tiles=False)}
+
+
+@pytest.fixture(scope="module")
+def edge_engines():
+    """(Engine, state dict) of gshift_deblur2's edge checkpoint (tests/prelu_edge.py) with the PReLU of both CAB_EDGE CABs set to `slope`."""
+    from shiftnet_amd.engine import Engine, Plan
+    cache = {}
+
+    def get(slope):
+        if slope not in cache:
+            sd = edge_state_dict("gshift_deblur2")
+            for pre, _ in CAB_EDGE:
+                set_slope(sd, "gshift_deblur2", pre + "body.1.weight", slope)
+            cache[slope] = (Engine(Plan(VARIANTS["gshift_deblur2"], sd, DEV)), sd)
+        return cache[slope]
+    return get
+
+
+def _traced(eng, **attrs):
+    """_sibling_engine that records the C-ABI functions it launches."""
+    e = _sibling_engine(eng, **attrs)
+    e.called = []
+    orig = e._call
+    e._call = lambda fn, *a: (e.called.append(fn), orig(fn, *a))[1]
+    return e
+
+
+@pytest.mark.parametrize("pre,c", CAB_EDGE)
+@pytest.mark.parametrize("slope", PRELU_SLOPES)
+@pytest.mark.parametrize("T,hw", [(3, (45, 150)), (3, (2, 3)), (1, (360, 640))])
+def test_cab_prelu_slopes_every_form(pre, c, slope, T, hw, edge_engines):
+    """A CAB on the edge checkpoint through every form -- two launches on the tile / streaming convs, the tile fused form with 8 and 16 rows, its
+    streaming-statistics variant, the streaming fused form -- with and without the second residual, ragged tiles, a map smaller than a tile and a
+    360 x 640 frame: each within the CAB tolerance of O.cab.  The tile fused forms stay bit-identical to the two-launch tile form.  "p" runs the
+    streaming fused form for a slope in [0, 1] and, decided before anything is launched, the two-launch form for any other slope; either way
+    its result is bit-identical to the two-launch form with the same switches."""
+    eng, sd = edge_engines(slope)
+    assert eng.P.scalar(pre + "body.1.weight") == torch.tensor(slope).item()
+    x = bf(torch.from_numpy(synth.unit_noise((T, c, hw[0], hw[1]), seed=153)))
+    e = bf(torch.from_numpy(synth.unit_noise((T, c, hw[0], hw[1]), seed=154)))
+    xa, ea = act(to_dev(x), c), act(to_dev(e), c)
+    ref = O.cab(sd, pre, x)
+    outs, called = {}, {}
+    for form, attrs in CAB_FORMS.items():
+        f = _traced(eng, **attrs)
+        outs[form] = (f.cab(pre, xa).t, f.cab(pre, xa, ea).t)
+        called[form] = f.called
+    torch.cuda.synchronize()
+    tag = f"{slope}_{pre}_{T}x{hw[0]}x{hw[1]}"
+    for form, (o0, o1) in outs.items():
+        check(f"cab_prelu{tag}_{form}", to_cpu(o0, c), ref, 8e-3)
+        check(f"cab_prelu{tag}_{form}_extra", to_cpu(o1, c), ref + e, 8e-3)
+        if o0.shape[-1] > c:
+            assert o0[..., c:].float().abs().max().item() == 0.0 and o1[..., c:].float().abs().max().item() == 0.0, form
+    for form in ("8", "16", "s8"):
+        assert called[form].count("sn_cab_fused") == 2 and "sn_conv2d" not in called[form], (form, called[form])
+    for form in ("8", "16"):
+        assert torch.equal(outs[form][0], outs["0_tile"][0]) and torch.equal(outs[form][1], outs["0_tile"][1]), (form, tag)
+    inside = 0.0 <= slope <= 1.0
+    assert called["p"].count("sn_cab_fused") == int(inside) and called["p"].count("sn_cab_stats") == int(inside), called["p"]
+    assert torch.equal(outs["p"][0], outs["0_stream"][0]) and torch.equal(outs["p"][1], outs["0_stream"][1]), tag
+
+
+@pytest.mark.parametrize("slope", [-0.25, 0.6])
+def test_default_cab_path_at_720p_prelu_slopes(slope, edge_engines):
+    """The product default (SN_CAB_FUSED=p16, streaming convs) on Shift-Net-s' 14-channel full-resolution CAB at T = 5, 720 x 1280: 4.6 M
+    pixel-frames, above CAB_FUSED_MIN_PX, where the engine picks the streaming fused form.  With a negative slope the engine used to launch the
+    statistics pass and the CALayer and then fail in sn_cab_fused(rows = 0) (ShiftNetLibError: the forward aborted); it must take the two-launch
+    form instead.  0.6 (in [0, 1]) shows that this geometry does reach the streaming fused form."""
+    eng, sd = edge_engines(slope)
+    pre, c = "stage1.concat.", 14
+    f = _traced(eng, cab_fused="p16", conv_tiles=False)
+    T, H, W = 5, 720, 1280
+    assert T * H * W >= f.CAB_FUSED_MIN_PX
+    x = bf(torch.from_numpy(synth.unit_noise((T, c, H, W), seed=155)))
+    out = f.cab(pre, act(to_dev(x), c)).t
+    torch.cuda.synchronize()
+    assert f.called.count("sn_cab_fused") == int(0.0 <= slope <= 1.0), f.called
+    check(f"cab_default_p16_prelu{slope}_{T}x{H}x{W}", to_cpu(out, c), O.cab(sd, pre, x), 8e-3)
+
+
+@pytest.mark.parametrize("name", ["gshift_deblur2", "gshift_denoise1"])
+def test_whole_net_prelu_edge_checkpoint(name):
+    """The drop-in class on the edge checkpoint (every PReLU of the network at -0.25 / 0 / 0.6 / 1 / 1.25), SN_CAB_FUSED=p so that this small clip
+    reaches the streaming fused CAB wherever the slope allows it, against a live fp32 O.forward with the bounds of test_whole_net_vs_golden.  The
+    denoiser adds the PReLU'd DownSample convs (stride 2) and the PReLU after rconcat.  The range guard must not have tripped: the result comes
+    from the fused phase 1, not the chain."""
+    import importlib
+    mod = importlib.import_module(f"basicsr.models.archs.{name}")
+    V = O.VARIANTS[name]
+    sd = edge_state_dict(name)
+    blur, sharp = synth.blurred_clip(7, 48, 64, seed=3)
+    x = O.frames_to_tensor(list(blur))
+    nm = torch.full((1, 7, 1, 48, 64), 30.0 / 255.0) if V.denoise else None
+    net = mod.GShiftNet(future_frames=2, past_frames=2)
+    net.load_state_dict(sd, strict=True)
+    net = net.to(torch.bfloat16).to("cuda").eval()
+    eng = net.prepare()
+    eng.cab_fused = "p"
+    called = []
+    orig = eng._call
+    eng._call = lambda fn, *a: (called.append(fn), orig(fn, *a))[1]
+    args = (x.bfloat16().cuda(), nm.bfloat16().cuda()) if V.denoise else (x.bfloat16().cuda(),)
+    with torch.no_grad():
+        out = net(*args).float().cpu()
+        out32 = net.forward_fp32_out(*args, shortcut=x.cuda()).cpu()
+        ref = O.forward(V, sd, x, nm, 2, 2)
+    assert eng.fallbacks == 0 and eng.phase1 != "0"
+    assert "sn_cab_fused" in called and "sn_cab_stats" in called                 # the streaming fused CAB ran where the slope is in [0, 1]
+    assert torch.isfinite(ref).all() and out.shape == ref.shape
+    gt = torch.from_numpy(sharp[2:5]).permute(0, 3, 1, 2).float() / 255
+    p_oo, p_32 = _psnr(out, ref), _psnr(out32, ref)
+    dpsnr = abs(_psnr(out32.clamp(0, 1), gt) - _psnr(ref.clamp(0, 1), gt))
+    xin = x[0, 2:5]
+    corr_err = ((out32 - xin) - (ref - xin)).pow(2).mean().sqrt().item() / (ref - xin).pow(2).mean().sqrt().item()
+    REPORT.append({"name": f"net_prelu_edge_{name}", "psnr_vs_ref": p_oo, "psnr_fp32_out_vs_ref": p_32, "delta_psnr_gt": dpsnr,
+                   "correction_rel_rms_err": corr_err, "max_abs": (out32 - ref).abs().max().item()})
+    assert p_oo >= 48.0 and p_32 >= 48.0 and dpsnr <= 0.01, (name, p_oo, p_32, dpsnr)
+    assert corr_err <= CORR_TOL, (name, corr_err)
