@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SN_ABI_VERSION 17     /* bump on ANY change of a struct, signature or operand encoding (shiftnet_amd/lib.py checks it) */
+#define SN_ABI_VERSION 18     /* bump on ANY change of a struct, signature or operand encoding (shiftnet_amd/lib.py checks it) */
 
 /* element types of NCHW tensors exchanged with the PyTorch side */
 #define SN_F32 0
@@ -328,6 +328,17 @@ typedef struct sn32_conv_desc {
 } sn32_conv_desc;
 int sn32_conv_csum_tiles(int h_out, int w_out);
 int sn32_conv2d(const sn32_conv_desc* d, void* stream);
+/* The kernel instance sn32_conv2d launches for d (host only, no device access: the pointers' alignment takes part, nothing is read), or SN_EINVAL
+ * where sn32_conv2d refuses d.  sn32_conv2d launches exactly what this returns.  SN32_ROUTE(kernel, a, b), a / b its template arguments: */
+#define SN32_K_1X1      1    /* conv32s_1x1_kernel<NCB = a, LOAD = b>: split 1x1 over the flat pixel list; a = ceil(cin / 32) in 1..4,
+                              * b 0 plain (iscale), 1 LayerNorm on load, 2 bilinear x2 on load (in_mode 1) */
+#define SN32_K_SPLIT    2    /* conv32s_kernel<MTC = a, KSZ = b, dense>: split tiles, a in {1, 3, 4}, b in {1, 3} */
+#define SN32_K_SPLIT_G8 3    /* conv32s_kernel<MTC = a, KSZ = b, grouped by 8>: split tiles, a in {3, 4}, b in {3, 5} */
+#define SN32_K_EXACT    4    /* conv32m_kernel<MTC = a, TH = b, TW = 4 b>: exact fp32 MFMA, (a, b) in {(1, 8), (3, 8), (5, 8)} stride 1, {(2, 4), (5, 4)} stride 2 */
+#define SN32_K_DW       5    /* dw32_kernel: depthwise, four channels per thread (a = b = 0) */
+#define SN32_K_DIRECT   6    /* conv32_kernel<NCO = a>: direct fp32 FMA, a in {1, 4} (b = 0) */
+#define SN32_ROUTE(kernel, a, b) (((kernel) << 16) | ((a) << 8) | (b))
+int sn32_conv2d_route(const sn32_conv_desc* d);
 /* channel_shift (gshift_deblur1.py:504-528) materialised in fp32: offs != NULL: u [T][h][w][3C/2] = cat(roll(x), shift(borrowed));
  * offs == NULL: the temporal roll alone, [T][h][w][C] (Shift_CAB, gshift_denoise1.py:167-179).  s->x is a float tensor.
  * u2: NULL, or (offs != NULL) a second [T][h][w][3C/2] tensor whose first C channels receive roll(x) too (CAB2's LayerNorm input is built in it). */

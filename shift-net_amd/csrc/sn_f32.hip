@@ -1062,40 +1062,24 @@ __global__ void ingest32_kernel(const void* src, int dt, const void* noise, floa
 
 int grid_for(size_t n) { size_t g = (n + 255) / 256; return (int)(g > 65535 * 16 ? 65535 * 16 : (g < 1 ? 1 : g)); }
 
-}  // namespace
-
-extern "C" {
-
-int sn32_conv2d(const sn32_conv_desc* d, void* stream) {
-    sn_clear_error();
+// The kernel instance sn32_conv2d launches for a descriptor, or SN_EINVAL: every check and every choice of the dispatch, host side (no device
+// access).  sn32_conv2d launches what this returns and sn32_conv2d_route reports it, so the two cannot disagree.
+int conv32_route(const sn32_conv_desc* d) {
     if (!d || d->n_in < 1 || d->n_in > 3 || !d->w || !d->out || d->k < 1 || d->k > 5 || (d->stride != 1 && d->stride != 2) ||
         d->groups < 1 || d->c_out < 1 || (d->c_out % d->groups) || d->T < 1) return SN_EINVAL;
     if (d->groups > 1 && d->n_in != 1) return SN_EINVAL;
     if (d->in_mode == 1 && (((d->h_in | d->w_in) & 1) || d->groups != 1)) return SN_EINVAL;
     if (d->out_mode == 2 && !d->sc) return SN_EINVAL;
-    Conv32K K;
-    K.in0 = d->in[0]; K.in1 = d->in[1]; K.in2 = d->in[2];
-    K.cin0 = d->c_in[0]; K.cin1 = d->c_in[1]; K.cin2 = d->c_in[2];
-    K.cs0 = d->cs_in[0]; K.cs1 = d->cs_in[1]; K.cs2 = d->cs_in[2];
-    K.n_in = d->n_in; K.T = d->T; K.hin = d->h_in; K.win = d->w_in; K.in_mode = d->in_mode;
-    K.k = d->k; K.stride = d->stride; K.pad = d->pad; K.groups = d->groups; K.hout = d->h_out; K.wout = d->w_out; K.cout = d->c_out;
-    K.cin_total = 0;
-    for (int i = 0; i < d->n_in; ++i) { if (!d->in[i] || d->c_in[i] < 1 || d->cs_in[i] < d->c_in[i]) return SN_EINVAL; K.cin_total += d->c_in[i]; }
-    if (K.cin_total % d->groups) return SN_EINVAL;
-    K.w = d->w; K.bias = d->bias; K.act = d->act; K.prelu = d->prelu; K.oscale = d->oscale; K.oscale_stride = d->oscale_stride;
-    K.res = d->res; K.cs_res = d->cs_res; K.out = d->out; K.cs_out = d->cs_out; K.out_mode = d->out_mode; K.nchw_dtype = d->nchw_dtype; K.sc = d->sc;
-    const size_t n = (size_t)d->T * d->h_out * d->w_out * d->c_out;
-    const int cin_g = K.cin_total / d->groups, cout_g = d->c_out / d->groups;
-    K.wsplit = (const uint4*)d->wsplit;
-    K.iscale = d->iscale; K.iscale_stride = d->iscale_stride;
-    K.rscale = d->rscale; K.rscale_stride = d->rscale_stride;
-    K.lnw = d->ln_w; K.lnb = d->ln_b; K.csum = d->csum; K.csum_cpad = d->csum_cpad;
+    int cin_total = 0;
+    for (int i = 0; i < d->n_in; ++i) { if (!d->in[i] || d->c_in[i] < 1 || d->cs_in[i] < d->c_in[i]) return SN_EINVAL; cin_total += d->c_in[i]; }
+    if (cin_total % d->groups) return SN_EINVAL;
+    const int cin_g = cin_total / d->groups, cout_g = d->c_out / d->groups;
     {
-        const bool split1 = d->wsplit && d->n_in == 1 && d->in_mode == 0 && d->stride == 1 && (d->cs_in[0] & 3) == 0 && (K.cin_total & 3) == 0 &&
+        const bool split1 = d->wsplit && d->n_in == 1 && d->in_mode == 0 && d->stride == 1 && (d->cs_in[0] & 3) == 0 && (cin_total & 3) == 0 &&
                             ((size_t)d->in[0] & 15) == 0 && ((size_t)d->wsplit & 15) == 0 && d->groups == 1 && d->out_mode == 0;
         const int mt0 = (d->c_out + 15) / 16;
         // LayerNorm on load: the flat-pixel split 1x1 kernel only (same conditions as its dispatch below)
-        if (d->ln_w && !(split1 && d->ln_b && !d->iscale && d->k == 1 && d->pad == 0 && (K.cin_total + 31) / 32 <= 4 && d->h_out * d->w_out >= SN_1X1_NPX &&
+        if (d->ln_w && !(split1 && d->ln_b && !d->iscale && d->k == 1 && d->pad == 0 && (cin_total + 31) / 32 <= 4 && d->h_out * d->w_out >= SN_1X1_NPX &&
                          (d->c_out & 3) == 0 && (d->cs_out & 3) == 0 && ((size_t)d->out & 15) == 0 && (!d->res || ((d->cs_res & 3) == 0 && ((size_t)d->res & 15) == 0)) &&
                          mt0 > 1 && (((size_t)d->ln_w | (size_t)d->ln_b) & 15) == 0)) return SN_EINVAL;
         // channel sums of the output: the split dense 3x3 kernel only
@@ -1108,68 +1092,110 @@ int sn32_conv2d(const sn32_conv_desc* d, void* stream) {
                        ((d->k == 5 && d->pad == 2) || (d->k == 3 && d->pad == 1)) && (d->rscale_stride & 3) == 0 && ((size_t)d->rscale & 15) == 0)) return SN_EINVAL;
     // the input scale is implemented by the matrix-core kernels' 16-byte staging path only
     if (d->iscale && !((d->groups == 1 || (cin_g == 8 && cout_g == 8 && d->c_out % 16 == 0)) && d->n_in == 1 && d->in_mode == 0 && (d->cs_in[0] & 3) == 0 &&
-                       (K.cin_total & 3) == 0 && ((size_t)d->in[0] & 15) == 0 && (d->iscale_stride & 3) == 0 && ((size_t)d->iscale & 15) == 0)) return SN_EINVAL;
+                       (cin_total & 3) == 0 && ((size_t)d->in[0] & 15) == 0 && (d->iscale_stride & 3) == 0 && ((size_t)d->iscale & 15) == 0)) return SN_EINVAL;
     if (d->groups == 1 || (cin_g == 8 && cout_g == 8 && d->c_out % 16 == 0)) {          // matrix cores: dense convs and the "+" RepConv
-        hipStream_t st = (hipStream_t)stream;
         const int mt = (d->c_out + 15) / 16;
         // split-precision path (bf16 hi + lo operands, three bf16 MFMAs per k-step): single float4-addressable input, stride 1, NHWC out
         bool quads = true;                    // every input addressable in aligned 16-byte quads that stay inside one input
         for (int i = 0; i < d->n_in; ++i) quads = quads && (d->c_in[i] & 3) == 0 && (d->cs_in[i] & 3) == 0 && ((size_t)d->in[i] & 15) == 0;
+        const int ncb1 = (cin_total + 31) / 32;
         // SkipUpSample: bilinear x2 on load + 1x1 (+ residual) on the flat-pixel split kernel; anything it does not cover keeps the exact kernel below
         if (d->wsplit && d->in_mode == 1 && d->n_in == 1 && quads && d->stride == 1 && ((size_t)d->wsplit & 15) == 0 && d->groups == 1 && d->k == 1 && d->pad == 0 &&
-            d->out_mode == 0 && !d->iscale && !d->ln_w && !d->csum && (K.cin_total + 31) / 32 <= 4 && d->h_out * d->w_out >= SN_1X1_NPX && (d->c_out & 3) == 0 &&
-            (d->cs_out & 3) == 0 && ((size_t)d->out & 15) == 0 && (!d->res || ((d->cs_res & 3) == 0 && ((size_t)d->res & 15) == 0)) && mt > 1) {
-            const int ncb1 = (K.cin_total + 31) / 32;
-            const long long npix = (long long)d->T * d->h_out * d->w_out;
-            const size_t lds = (size_t)SN_1X1_NPX * (ncb1 * 160 + ((ncb1 & 1) ? 0 : 32));
-            const dim3 grid((unsigned)((npix + SN_1X1_NPX - 1) / SN_1X1_NPX));
-#define SN_1X1_CASE(N) case N: \
-            if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)conv32s_1x1_kernel<N, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return SN_ELAUNCH; \
-            hipLaunchKernelGGL((conv32s_1x1_kernel<N, false, 2>), grid, dim3(256), lds, st, K, npix, (float*)nullptr, 0); break;
-            switch (ncb1) { SN_1X1_CASE(1) SN_1X1_CASE(2) SN_1X1_CASE(3) SN_1X1_CASE(4) }
-#undef SN_1X1_CASE
-            return sn_check_launch();
-        }
+            d->out_mode == 0 && !d->iscale && !d->ln_w && !d->csum && ncb1 <= 4 && d->h_out * d->w_out >= SN_1X1_NPX && (d->c_out & 3) == 0 &&
+            (d->cs_out & 3) == 0 && ((size_t)d->out & 15) == 0 && (!d->res || ((d->cs_res & 3) == 0 && ((size_t)d->res & 15) == 0)) && mt > 1)
+            return SN32_ROUTE(SN32_K_1X1, ncb1, 2);
         if (d->wsplit && (d->n_in == 1 || (d->groups == 1 && !d->iscale)) && quads && d->in_mode == 0 && d->stride == 1 && ((size_t)d->wsplit & 15) == 0) {
-            const int ncb1 = (K.cin_total + 31) / 32;
             if (d->n_in == 1 && d->groups == 1 && d->k == 1 && d->pad == 0 && d->out_mode == 0 && ncb1 <= 4 && d->h_out * d->w_out >= SN_1X1_NPX && (d->c_out & 3) == 0 && (d->cs_out & 3) == 0 &&
-                ((size_t)d->out & 15) == 0 && (!d->res || ((d->cs_res & 3) == 0 && ((size_t)d->res & 15) == 0)) && mt > 1) {
-                const long long npix = (long long)d->T * d->h_out * d->w_out;
-                const size_t lds = (size_t)SN_1X1_NPX * (ncb1 * 160 + ((ncb1 & 1) ? 0 : 32));
-                const dim3 grid((unsigned)((npix + SN_1X1_NPX - 1) / SN_1X1_NPX));
-#define SN_1X1_CASE(N) case N: \
-                    if (d->ln_w) { \
-                        if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)conv32s_1x1_kernel<N, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return SN_ELAUNCH; \
-                        hipLaunchKernelGGL((conv32s_1x1_kernel<N, false, 1>), grid, dim3(256), lds, st, K, npix, (float*)nullptr, 0); break; \
-                    } \
-                    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)conv32s_1x1_kernel<N, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return SN_ELAUNCH; \
-                    hipLaunchKernelGGL((conv32s_1x1_kernel<N, false, 0>), grid, dim3(256), lds, st, K, npix, (float*)nullptr, 0); break;
-                switch (ncb1) { SN_1X1_CASE(1) SN_1X1_CASE(2) SN_1X1_CASE(3) SN_1X1_CASE(4) }
-#undef SN_1X1_CASE
-                return sn_check_launch();
-            }
-            if (d->groups == 1 && d->k == 1 && d->pad == 0)
-                return mt == 1 ? launch_conv32s<1, 1, false>(K, st) : (mt <= 3 ? launch_conv32s<3, 1, false>(K, st) : launch_conv32s<4, 1, false>(K, st));
-            if (d->groups == 1 && d->k == 3 && d->pad == 1)
-                return mt == 1 ? launch_conv32s<1, 3, false>(K, st) : (mt <= 3 ? launch_conv32s<3, 3, false>(K, st) : launch_conv32s<4, 3, false>(K, st));
-            if (d->groups > 1 && d->k == 5 && d->pad == 2)
-                return mt <= 3 ? launch_conv32s<3, 5, true>(K, st) : launch_conv32s<4, 5, true>(K, st);
-            if (d->groups > 1 && d->k == 3 && d->pad == 1)
-                return mt <= 3 ? launch_conv32s<3, 3, true>(K, st) : launch_conv32s<4, 3, true>(K, st);
+                ((size_t)d->out & 15) == 0 && (!d->res || ((d->cs_res & 3) == 0 && ((size_t)d->res & 15) == 0)) && mt > 1)
+                return SN32_ROUTE(SN32_K_1X1, ncb1, d->ln_w ? 1 : 0);
+            if (d->groups == 1 && d->k == 1 && d->pad == 0) return SN32_ROUTE(SN32_K_SPLIT, mt == 1 ? 1 : (mt <= 3 ? 3 : 4), 1);
+            if (d->groups == 1 && d->k == 3 && d->pad == 1) return SN32_ROUTE(SN32_K_SPLIT, mt == 1 ? 1 : (mt <= 3 ? 3 : 4), 3);
+            if (d->groups > 1 && d->k == 5 && d->pad == 2) return SN32_ROUTE(SN32_K_SPLIT_G8, mt <= 3 ? 3 : 4, 5);
+            if (d->groups > 1 && d->k == 3 && d->pad == 1) return SN32_ROUTE(SN32_K_SPLIT_G8, mt <= 3 ? 3 : 4, 3);
         }
-        if (d->stride == 2) return mt <= 2 ? launch_conv32m<2, 4, 16>(K, st) : launch_conv32m<5, 4, 16>(K, st);
-        return mt == 1 ? launch_conv32m<1, 8, 32>(K, st) : (mt <= 3 ? launch_conv32m<3, 8, 32>(K, st) : launch_conv32m<5, 8, 32>(K, st));
+        if (d->stride == 2) return SN32_ROUTE(SN32_K_EXACT, mt <= 2 ? 2 : 5, 4);
+        return SN32_ROUTE(SN32_K_EXACT, mt == 1 ? 1 : (mt <= 3 ? 3 : 5), 8);
     }
     if (d->groups == d->c_out && cin_g == 1 && d->stride == 1 && d->in_mode == 0 && d->out_mode == 0 && (d->c_out & 3) == 0 && (d->cs_in[0] & 3) == 0 &&
-        (d->cs_out & 3) == 0 && (!d->res || (d->cs_res & 3) == 0) && (((size_t)d->in[0] | (size_t)d->out | (size_t)d->res | (size_t)d->w) & 15) == 0) {
-        hipLaunchKernelGGL(dw32_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, K);      // depthwise, 4 channels per thread
+        (d->cs_out & 3) == 0 && (!d->res || (d->cs_res & 3) == 0) && (((size_t)d->in[0] | (size_t)d->out | (size_t)d->res | (size_t)d->w) & 15) == 0)
+        return SN32_ROUTE(SN32_K_DW, 0, 0);                        // depthwise, 4 channels per thread
+    // a thread's four channels share a group (and the weight row is 16-byte aligned: c_out % 4 == 0)
+    return SN32_ROUTE(SN32_K_DIRECT, cout_g % 4 == 0 ? 4 : 1, 0);
+}
+
+template <int NCB, int LOAD>
+int launch_conv32s_1x1(const Conv32K& K, hipStream_t st) {
+    const long long npix = (long long)K.T * K.hout * K.wout;
+    const size_t lds = (size_t)SN_1X1_NPX * (NCB * 160 + ((NCB & 1) ? 0 : 32));
+    const dim3 grid((unsigned)((npix + SN_1X1_NPX - 1) / SN_1X1_NPX));
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)conv32s_1x1_kernel<NCB, false, LOAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return SN_ELAUNCH;
+    hipLaunchKernelGGL((conv32s_1x1_kernel<NCB, false, LOAD>), grid, dim3(256), lds, st, K, npix, (float*)nullptr, 0);
+    return sn_check_launch();
+}
+
+template <int LOAD>
+int launch_conv32s_1x1_ncb(int ncb, const Conv32K& K, hipStream_t st) {
+    switch (ncb) {
+    case 1: return launch_conv32s_1x1<1, LOAD>(K, st);
+    case 2: return launch_conv32s_1x1<2, LOAD>(K, st);
+    case 3: return launch_conv32s_1x1<3, LOAD>(K, st);
+    case 4: return launch_conv32s_1x1<4, LOAD>(K, st);
+    }
+    return SN_EINVAL;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sn32_conv2d_route(const sn32_conv_desc* d) {
+    sn_clear_error();
+    return conv32_route(d);
+}
+
+int sn32_conv2d(const sn32_conv_desc* d, void* stream) {
+    sn_clear_error();
+    const int route = conv32_route(d);
+    if (route < 0) return route;
+    Conv32K K;
+    K.in0 = d->in[0]; K.in1 = d->in[1]; K.in2 = d->in[2];
+    K.cin0 = d->c_in[0]; K.cin1 = d->c_in[1]; K.cin2 = d->c_in[2];
+    K.cs0 = d->cs_in[0]; K.cs1 = d->cs_in[1]; K.cs2 = d->cs_in[2];
+    K.n_in = d->n_in; K.T = d->T; K.hin = d->h_in; K.win = d->w_in; K.in_mode = d->in_mode;
+    K.k = d->k; K.stride = d->stride; K.pad = d->pad; K.groups = d->groups; K.hout = d->h_out; K.wout = d->w_out; K.cout = d->c_out;
+    K.cin_total = 0;
+    for (int i = 0; i < d->n_in; ++i) K.cin_total += d->c_in[i];
+    K.w = d->w; K.bias = d->bias; K.act = d->act; K.prelu = d->prelu; K.oscale = d->oscale; K.oscale_stride = d->oscale_stride;
+    K.res = d->res; K.cs_res = d->cs_res; K.out = d->out; K.cs_out = d->cs_out; K.out_mode = d->out_mode; K.nchw_dtype = d->nchw_dtype; K.sc = d->sc;
+    K.wsplit = (const uint4*)d->wsplit;
+    K.iscale = d->iscale; K.iscale_stride = d->iscale_stride;
+    K.rscale = d->rscale; K.rscale_stride = d->rscale_stride;
+    K.lnw = d->ln_w; K.lnb = d->ln_b; K.csum = d->csum; K.csum_cpad = d->csum_cpad;
+    const size_t n = (size_t)d->T * d->h_out * d->w_out * d->c_out;
+    hipStream_t st = (hipStream_t)stream;
+    const int a = (route >> 8) & 255, b = route & 255;
+    switch (route >> 16) {
+    case SN32_K_1X1:
+        return b == 2 ? launch_conv32s_1x1_ncb<2>(a, K, st) : (b == 1 ? launch_conv32s_1x1_ncb<1>(a, K, st) : launch_conv32s_1x1_ncb<0>(a, K, st));
+    case SN32_K_SPLIT:
+        if (b == 1) return a == 1 ? launch_conv32s<1, 1, false>(K, st) : (a == 3 ? launch_conv32s<3, 1, false>(K, st) : launch_conv32s<4, 1, false>(K, st));
+        return a == 1 ? launch_conv32s<1, 3, false>(K, st) : (a == 3 ? launch_conv32s<3, 3, false>(K, st) : launch_conv32s<4, 3, false>(K, st));
+    case SN32_K_SPLIT_G8:
+        if (b == 5) return a == 3 ? launch_conv32s<3, 5, true>(K, st) : launch_conv32s<4, 5, true>(K, st);
+        return a == 3 ? launch_conv32s<3, 3, true>(K, st) : launch_conv32s<4, 3, true>(K, st);
+    case SN32_K_EXACT:
+        if (b == 4) return a == 2 ? launch_conv32m<2, 4, 16>(K, st) : launch_conv32m<5, 4, 16>(K, st);
+        return a == 1 ? launch_conv32m<1, 8, 32>(K, st) : (a == 3 ? launch_conv32m<3, 8, 32>(K, st) : launch_conv32m<5, 8, 32>(K, st));
+    case SN32_K_DW:
+        hipLaunchKernelGGL(dw32_kernel, dim3(grid_for(n / 4)), dim3(256), 0, st, K);
+        return sn_check_launch();
+    case SN32_K_DIRECT:
+        if (a == 4) hipLaunchKernelGGL(conv32_kernel<4>, dim3(grid_for(n / 4)), dim3(256), 0, st, K);
+        else hipLaunchKernelGGL(conv32_kernel<1>, dim3(grid_for(n)), dim3(256), 0, st, K);
         return sn_check_launch();
     }
-    if ((d->c_out / d->groups) % 4 == 0)      // a thread's four channels share a group (and the weight row is 16-byte aligned: c_out % 4 == 0)
-        hipLaunchKernelGGL(conv32_kernel<4>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, K);
-    else
-        hipLaunchKernelGGL(conv32_kernel<1>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, K);
-    return sn_check_launch();
+    return SN_EINVAL;
 }
 
 int sn32_gsts_gather(const sn_unit_src* s, const int8_t* offs, float* u, float* u2, void* stream) {
