@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SN_ABI_VERSION 18     /* bump on ANY change of a struct, signature or operand encoding (shiftnet_amd/lib.py checks it) */
+#define SN_ABI_VERSION 19     /* bump on ANY change of a struct, signature or operand encoding (shiftnet_amd/lib.py checks it) */
 
 /* element types of NCHW tensors exchanged with the PyTorch side */
 #define SN_F32 0
@@ -86,6 +86,11 @@ typedef struct sn_conv_desc {
                             bits 12..14: MEASUREMENTS ONLY, WRONG RESULTS -- the streaming conv without its DMA (1), B reads / MFMAs (2), stores (4);
                             on conv2 of sn_cab_fused(rows = 0) bit 12 means "both weight sets in LDS" (results unchanged); bit 15: stride-2 convs on
                             4 x 16 tiles whatever their width (measurements; results unchanged) */
+    int clip_n, clip_T, clip_lo; /* per-clip frame remap (ABI 19; all 0 = off): output frame j reads frame (j / clip_n) * clip_T + clip_lo + j % clip_n
+                            of every in[] -- the kept frames [clip_lo, clip_lo + clip_n) of each clip of a batch, read in place (rconcat of
+                            Engine.forward_clips).  out, res, res2, pool and oscale stay indexed by j.  T % clip_n == 0, clip_lo + clip_n <= clip_T.
+                            Implemented by the generic MFMA kernel (n_in > 1, or any conv the specialised 3x3 / streaming kernels do not take);
+                            on any other route, and in sn_cab_stats / sn_cab_fused, nonzero fields are SN_EINVAL */
 } sn_conv_desc;
 #define SN_CONV_TILE_KERNEL 1
 int sn_conv2d(const sn_conv_desc* d, void* stream);   /* d is a HOST pointer, read during the call */
@@ -159,6 +164,10 @@ typedef struct sn_unit_src {
     int t0, nt;          /* frames [t0, t0 + nt) of x are processed (nt == 0: all T).  Outputs, pool rows and the neighbour rule are indexed
                             by the absolute frame, so a unit can be launched in pieces: the frames that need no halo while the exchange is
                             in flight, the boundary frame after it */
+    int clip;            /* frames per clip (ABI 19): x holds T / clip independent clips end to end and the neighbour rule applies inside each --
+                            a forward unit's first frame of a clip is kept (wrap 0) or borrows from the last frame of the SAME clip (wrap 1), a
+                            reverse unit mirrors it.  0 (or T): one clip.  T % clip != 0, or clip > 0 with wrap 2, is SN_EINVAL.  t0 / nt stay
+                            absolute frame indices */
 } sn_unit_src;
 
 /* validation op: materialise u = cat(y, spatial_shift2(hw)) : [T][h][w][3C/2] exactly as channel_shift returns it
@@ -325,6 +334,8 @@ typedef struct sn32_conv_desc {
                           * it is loaded; the split-precision 1x1 path only (wsplit, k 1, cin <= 128, h_out w_out >= 64), SN_EINVAL otherwise */
     float* csum; int csum_cpad;               /* NULL or [T][sn32_conv_csum_tiles(h_out, w_out)][csum_cpad] f32: channel sums of the stored output per workgroup
                           * (AdaptiveAvgPool2d(1) of the CALayer behind a conv, finished by sn_ca_mlp / sn32_cab_ca); split-precision dense 3x3 only */
+    int clip_n, clip_T, clip_lo;              /* per-clip frame remap of the inputs as in sn_conv_desc (ABI 19; all 0 = off): the split dense tiles
+                          * (SN32_K_SPLIT) and the exact kernels (SN32_K_EXACT) without iscale / rscale / ln_w / csum; SN_EINVAL on any other route */
 } sn32_conv_desc;
 int sn32_conv_csum_tiles(int h_out, int w_out);
 int sn32_conv2d(const sn32_conv_desc* d, void* stream);

@@ -311,7 +311,8 @@ int cabf_key(const sn_conv_desc* a, const sn_conv_desc* b) {
     const sn_conv_desc* ds[2] = {a, b};
     for (const sn_conv_desc* d : ds)
         if (!(d->k == 3 && d->stride == 1 && d->pad == 1 && d->in_mode == 0 && d->out_mode == 0 && d->n_in == 1 && d->cs_in == d->cs_out &&
-              d->ks == (9 * d->cs_in + 31) / 32 && d->h_in == d->h_out && d->w_in == d->w_out && d->wfrag)) return 0;
+              d->ks == (9 * d->cs_in + 31) / 32 && d->h_in == d->h_out && d->w_in == d->w_out && d->wfrag &&
+              !sn_remap_set(d->clip_n, d->clip_T, d->clip_lo))) return 0;
     if (a->mt != b->mt || a->cs_in != b->cs_in || a->T != b->T || a->h_in != b->h_in || a->w_in != b->w_in) return 0;
     const int key = a->mt * 1000 + a->cs_in;
     return (key == 1016 || key == 2024) ? key : 0;

@@ -102,12 +102,22 @@ __device__ __forceinline__ float sum_rows4(float x) {
 // mode 0: CAB1, u = x[t].  mode 1 / 2: forward / reverse unit.  wrap 0: the window's boundary frame is kept un-rolled; 1: circular roll
 // inside the tensor; 2: the boundary frame's neighbour belongs to the adjacent rank of a temporally split window
 // (shiftnet_amd/temporal_split.py) and only its borrowed half exists here, as the contiguous [h][w][C/2] buffer `halo` (pixel stride C/2).
-// frame sub-range of an sn_unit_src: (first frame, count); false when it does not lie inside [0, T)
+// clip: frames per clip of a batch of independent clips laid end to end in x (shiftnet_amd/engine.py: Engine.forward_clips), normalised by the
+// entry points to T for "one clip" (sn_unit_src.clip == 0).  The rule above applies inside [base, base + clip) of t's clip: its first / last frame is
+// the boundary frame (kept, or rolled inside the clip).  t itself stays an absolute frame index.  Called once per frame and workgroup.
+// frame sub-range of an sn_unit_src: (first frame, count); false when it does not lie inside [0, T) or the clip length is not valid
 #define SN_FRAME_RANGE(s, T0, NT) const int T0 = (s)->nt > 0 ? (s)->t0 : 0, NT = (s)->nt > 0 ? (s)->nt : (s)->T; \
-    if (T0 < 0 || NT < 1 || T0 + NT > (s)->T) return SN_EINVAL
+    if (T0 < 0 || NT < 1 || T0 + NT > (s)->T || !sn_clip_ok((s)->T, (s)->clip, (s)->wrap)) return SN_EINVAL
+// sn_unit_src.clip: 0 = one clip; otherwise it divides T, and a temporally split window (wrap 2) is never batched
+static inline bool sn_clip_ok(int T, int clip, int wrap) { return clip == 0 || (clip > 0 && T % clip == 0 && wrap != 2); }
+static inline int sn_clip_len(int T, int clip) { return clip > 0 ? clip : T; }
 template <typename E> struct SnSlabs { const E* p0; const E* p1; const E* pb; int s0, s1, sb; };
 template <typename E>
-__device__ __forceinline__ SnSlabs<E> sn_unit_slabs(const E* x, const E* halo, int T, int hw, int C, int mode, int wrap, int t) {
+__device__ __forceinline__ SnSlabs<E> sn_unit_slabs(const E* x, const E* halo, int T, int hw, int C, int mode, int wrap, int clip, int t) {
+    if (clip < T) {                                    // a batch of clips: the rule below on t's own clip (clip == T: no division)
+        const int base = t / clip * clip;
+        x += (ptrdiff_t)base * hw * C; t -= base; T = clip;
+    }
     const int Ch = C >> 1;
     const E* xt = x + (ptrdiff_t)t * hw * C;
     SnSlabs<E> s;
@@ -123,6 +133,16 @@ __device__ __forceinline__ SnSlabs<E> sn_unit_slabs(const E* x, const E* halo, i
     }
     return s;
 }
+
+// Per-clip frame remap of sn_conv_desc / sn32_conv_desc (clip_n, clip_T, clip_lo; all 0 = none): output frame t reads input frame
+// (t / clip_n) * clip_T + clip_lo + t % clip_n.  Computed once per workgroup.
+__host__ __device__ __forceinline__ int sn_remap_frame(int t, int n, int T, int lo) {
+    if (n == 0) return t;
+    const int q = t / n;
+    return q * T + lo + (t - q * n);
+}
+static inline bool sn_remap_set(int n, int T, int lo) { return n != 0 || T != 0 || lo != 0; }
+static inline bool sn_remap_ok(int Tout, int n, int T, int lo) { return !sn_remap_set(n, T, lo) || (n > 0 && lo >= 0 && lo + n <= T && Tout % n == 0); }
 
 // ---- squeeze-excite folded into its producer (shiftnet_hip.h: sn_se_fold) -------------------------------------------------------
 // CALayer2 needs the global average pool of g2: every workgroup of a frame stores its partial channel sums, and the LAST workgroup of

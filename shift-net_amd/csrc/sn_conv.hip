@@ -30,6 +30,7 @@ struct ConvK {
     const bf16_t* res; bf16_t* out; int cs_out, out_mode, c_out, nchw_dtype, sc_dtype;
     const void* sc; float* pool; const float* oscale; int oscale_stride; const bf16_t* res2;
     int rh, rw, ps;
+    int clip_n, clip_T, clip_lo;     // conv_mfma_kernel: per-clip frame remap of the inputs (sn_remap_frame; all 0 = none)
     int lines_len;                   // conv3_fast_kernel<.., STATS>: `out` is the border-line buffer [T][4][lines_len][cs_out] (sn_cab_stats)
     XcdTiles xg;                     // tile walk of conv_mfma_kernel / conv3_fast_kernel (sn_common.h)
     unsigned m_nblk8, m_rw, m_csb, m_cv, m_k;   // ceil(2^24/d) multipliers: integer division by runtime constants without v_div
@@ -91,6 +92,7 @@ __global__ __launch_bounds__(256, sn_conv_waves(MT, TH)) void conv_mfma_kernel(c
     const int g = lane >> 4, p = lane & 15;
     int t, tyi, txi;
     if (!sn_xcd_tile(P.xg, t, tyi, txi)) return;
+    const int ti = sn_remap_frame(t, P.clip_n, P.clip_T, P.clip_lo);      // the input frame of output frame t
     const int oy0 = tyi * TH, ox0 = txi * TW;
     const int tile_bytes = P.rh * P.rw * P.ps;
     int* tapoff = (int*)(smem + tile_bytes);
@@ -125,8 +127,8 @@ __global__ __launch_bounds__(256, sn_conv_waves(MT, TH)) void conv_mfma_kernel(c
                 const int gy = iy0 + ry, gx = ix0 + rx;
                 const bool in = gy >= 0 && gy < P.hin && gx >= 0 && gx < P.win;
                 dst[u] = idx < total ? (in ? pix * P.ps + blk * 16 : -(pix * P.ps + blk * 16) - 1) : 0x7fffffff;
-                if (P.in_mode == 0) v[u] = *(const uint4*)(src + (in ? (((size_t)t * P.hin + gy) * P.win + gx) * P.cs + cb * 8 : 0));
-                else v[u] = in ? ld_bilinear(src, t, P.hin >> 1, P.win >> 1, P.cs, cb, gy, gx) : make_uint4(0, 0, 0, 0);
+                if (P.in_mode == 0) v[u] = *(const uint4*)(src + (in ? (((size_t)ti * P.hin + gy) * P.win + gx) * P.cs + cb * 8 : 0));
+                else v[u] = in ? ld_bilinear(src, ti, P.hin >> 1, P.win >> 1, P.cs, cb, gy, gx) : make_uint4(0, 0, 0, 0);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -875,6 +877,9 @@ int sn_conv2d(const sn_conv_desc* d, void* stream) {
     if (d->oscale && d->oscale_stride < 16 * d->mt) return SN_EINVAL;
     if ((d->res || d->res2) && d->out_mode != 0) return SN_EINVAL;
     if (d->out_mode == 1 && d->cs_out != 4 * d->mt) return SN_EINVAL;      // rows ordered [sub-pixel][cs_out channels]: a lane group = one sub-pixel
+    const bool remap = sn_remap_set(d->clip_n, d->clip_T, d->clip_lo);      // only the generic kernel implements the frame remap
+    if (!sn_remap_ok(d->T, d->clip_n, d->clip_T, d->clip_lo) || (remap && (conv3_key(d) || (!(d->flags & SN_CONV_TILE_KERNEL) && sn_conv3p_key(d, false)))))
+        return SN_EINVAL;
     ConvK K;
     K.in0 = (const bf16_t*)d->in[0]; K.in1 = (const bf16_t*)d->in[1]; K.in2 = (const bf16_t*)d->in[2];
     K.n_in = d->n_in; K.cs = d->cs_in; K.cv = d->n_in * d->cs_in;
@@ -886,6 +891,7 @@ int sn_conv2d(const sn_conv_desc* d, void* stream) {
     const int blocks = K.cv >> 3;
     K.ps = d->stride == 1 ? 16 * sn_lds_slots(blocks) : ((blocks & 1) ? K.cv * 2 : K.cv * 2 + 16);     // stride 2: odd slot count (pixels 2 apart)
     K.rh = K.rw = 0; K.lines_len = 0;
+    K.clip_n = d->clip_n; K.clip_T = d->clip_T; K.clip_lo = d->clip_lo;
     if (!(d->flags & SN_CONV_TILE_KERNEL) && sn_conv3p_key(d, false)) {
         const int rc = sn_conv3p_launch(d, 0, stream);
         if (rc != SN_EINVAL) return rc;                      // (SN_EINVAL: no device to plan for -- fall through to the tile kernel's own checks)
@@ -945,7 +951,8 @@ int sn_cab_ca_lines(const float* partial, int nblk, int cpad, const void* lines,
 // pass 1 of the fused CAB (csrc/sn_cabf.hip): d = the CAB's FIRST conv as sn_conv2d would run it with `pool`, except that d->out is the line buffer
 int sn_cab_stats(const sn_conv_desc* d, int lines_len, void* stream) {
     sn_clear_error();
-    if (!d || !d->out || !d->pool || !d->wfrag || !d->in[0] || d->res || d->res2 || d->oscale || d->cs_in != d->cs_out) return SN_EINVAL;
+    if (!d || !d->out || !d->pool || !d->wfrag || !d->in[0] || d->res || d->res2 || d->oscale || d->cs_in != d->cs_out ||
+        sn_remap_set(d->clip_n, d->clip_T, d->clip_lo)) return SN_EINVAL;
     if (lines_len < (d->h_out > d->w_out ? d->h_out : d->w_out) || d->h_out < 2 || d->w_out < 2) return SN_EINVAL;
     if (!(d->flags & SN_CONV_TILE_KERNEL) && sn_conv3p_key(d, false)) {      // the streaming kernel's statistics mode (pool rows: sn_conv_pool_blocks(d))
         const int rc = sn_conv3p_launch(d, lines_len, stream);
@@ -960,7 +967,7 @@ int sn_cab_stats(const sn_conv_desc* d, int lines_len, void* stream) {
     K.wfrag = (const uint4*)d->wfrag; K.ks = d->ks; K.bias = d->bias; K.act = d->act; K.prelu = d->prelu;
     K.res = nullptr; K.out = (bf16_t*)d->out; K.cs_out = d->cs_out; K.out_mode = 0; K.c_out = d->c_out; K.nchw_dtype = 0; K.sc_dtype = 0; K.sc = nullptr;
     K.pool = d->pool; K.oscale = nullptr; K.oscale_stride = 0; K.res2 = nullptr;
-    K.ps = 16 * sn_lds_slots(K.cv >> 3); K.rh = K.rw = 0; K.lines_len = lines_len;
+    K.ps = 16 * sn_lds_slots(K.cv >> 3); K.rh = K.rw = 0; K.lines_len = lines_len; K.clip_n = K.clip_T = K.clip_lo = 0;
     hipStream_t st = (hipStream_t)stream;
     return key == 1016 ? launch_conv3_fast<1, 16, true>(K, d->T, st) : launch_conv3_fast<2, 24, true>(K, d->T, st);
 }

@@ -30,6 +30,7 @@ struct Conv32K {
     const float* rscale; int rscale_stride;      // NULL or [T][rscale_stride]: res is multiplied by rscale[t][co] before it is added
     const float* lnw; const float* lnb;          // NULL or [cin]: LayerNorm2d over the input channels of a pixel while it is staged (split 1x1 kernel)
     float* csum; int csum_cpad;                  // NULL or [T][tiles][csum_cpad]: per-workgroup channel sums of the stored output (split dense 3x3 kernel)
+    int clip_n, clip_T, clip_lo;                 // per-clip frame remap of the inputs (sn_remap_frame; all 0 = none): conv32m_kernel, dense conv32s_kernel
 };
 
 __device__ __forceinline__ float ld_bilinear32(const float* src, int hs, int ws, int cs, int c, int gy, int gx) {
@@ -202,6 +203,7 @@ __global__ __launch_bounds__(256) void conv32m_kernel(const Conv32K P) {
     const int tid = threadIdx.x, lane = tid & 63, wv = wave_id(), g4 = lane >> 4, p = lane & 15;
     const int tiles_y = (P.hout + TH - 1) / TH;
     const int t = blockIdx.y / tiles_y, ty = blockIdx.y - t * tiles_y, tx = blockIdx.x;
+    const int ti = sn_remap_frame(t, P.clip_n, P.clip_T, P.clip_lo);      // the input frame of output frame t
     const int oy0 = ty * TH, ox0 = tx * TW, co0 = blockIdx.z * MTC * 16;
     const int rh = (TH - 1) * P.stride + P.k, rw = (TW - 1) * P.stride + P.k, npatch = rh * rw;
     const int iy0 = oy0 * P.stride - P.pad, ix0 = ox0 * P.stride - P.pad;
@@ -240,7 +242,7 @@ __global__ __launch_bounds__(256) void conv32m_kernel(const Conv32K P) {
                 const int ry = pix / rw, rx = pix - ry * rw, gy = iy0 + ry, gx = ix0 + rx;
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (ci < P.cin_total && gy >= 0 && gy < P.hin && gx >= 0 && gx < P.win)
-                    v = *(const float4*)(P.in0 + (((size_t)t * hs + gy) * ws + gx) * P.cs0 + ci);
+                    v = *(const float4*)(P.in0 + (((size_t)ti * hs + gy) * ws + gx) * P.cs0 + ci);
                 if (P.iscale && ci < P.cin_total) {
                     const float4 sc4 = *(const float4*)(P.iscale + (size_t)t * P.iscale_stride + ci);
                     v.x *= sc4.x; v.y *= sc4.y; v.z *= sc4.z; v.w *= sc4.w;
@@ -255,7 +257,7 @@ __global__ __launch_bounds__(256) void conv32m_kernel(const Conv32K P) {
                 if (ci < P.cin_total && gy >= 0 && gy < P.hin && gx >= 0 && gx < P.win) {
                     const float* src = P.in0; int cc = ci, cs = P.cs0;                    // torch.cat of up to three inputs along channels
                     if (P.n_in > 1 && cc >= P.cin0) { cc -= P.cin0; src = P.in1; cs = P.cs1; if (P.n_in > 2 && cc >= P.cin1) { cc -= P.cin1; src = P.in2; cs = P.cs2; } }
-                    const float* fr = src + (size_t)t * hs * ws * cs;
+                    const float* fr = src + (size_t)ti * hs * ws * cs;
                     v = P.in_mode == 0 ? fr[((size_t)gy * ws + gx) * cs + cc] : ld_bilinear32(fr, hs, ws, cs, cc, gy, gx);
                 }
                 smem32[pix * C32_PSL + c] = v;
@@ -391,6 +393,7 @@ __global__ __launch_bounds__(256, 2) void conv32s_kernel(const Conv32K P) {
     const int tid = threadIdx.x, lane = tid & 63, wv = wave_id(), g4 = lane >> 4, p = lane & 15;
     const int tiles_y = (P.hout + TH - 1) / TH;
     const int t = blockIdx.y / tiles_y, ty = blockIdx.y - t * tiles_y, tx = blockIdx.x;
+    const int ti = sn_remap_frame(t, P.clip_n, P.clip_T, P.clip_lo);      // the input frame of output frame t
     const int oy0 = ty * TH, ox0 = tx * TW, co0 = blockIdx.z * MTC * 16;
     const int iy0 = oy0 - P.pad, ix0 = ox0 - P.pad;
     const int mt_all = (P.cout + 15) / 16;
@@ -429,7 +432,7 @@ __global__ __launch_bounds__(256, 2) void conv32s_kernel(const Conv32K P) {
             const float* src = P.in0; int cs = P.cs0, cl = ci;
             if (ci >= P.cin0) { src = P.in1; cs = P.cs1; cl = ci - P.cin0; }
             if (ci >= P.cin0 + P.cin1) { src = P.in2; cs = P.cs2; cl = ci - P.cin0 - P.cin1; }
-            v[it] = *(const float4*)(in ? src + (((size_t)t * P.hin + gy) * P.win + gx) * cs + cl : P.in0);
+            v[it] = *(const float4*)(in ? src + (((size_t)ti * P.hin + gy) * P.win + gx) * cs + cl : P.in0);
             if (!in) v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
@@ -886,14 +889,14 @@ __global__ __launch_bounds__(256) void dwgate32_kernel(const float* a, int cs, c
     }
 }
 
-struct Unit32 { const float* x; const float* halo; int T, h, w, C, mode, wrap, t0; };
+struct Unit32 { const float* x; const float* halo; int T, h, w, C, mode, wrap, t0, clip; };      // clip: T for one clip (sn_clip_len)
 
 // u = cat(roll(x), spatial_shift2(borrowed half)) (gshift_deblur1.py:504-528); CU = 3C/2, or C for the roll alone (Shift_CAB)
 // u2 (optional): a second [T][h][w][CU] tensor that receives the first C channels (the rolled tensor = CAB2's shortcut) as well: the LayerNorm
 // input cat(shortcut, conv1(shifted)) is assembled in it without a second gather pass.
 __global__ void gather32_kernel(const Unit32 U, const int8_t* offs, float* u, const int CU, float* u2) {
     const int t = U.t0 + blockIdx.y, Ch = U.C >> 1, hw = U.h * U.w;
-    const SnSlabs<float> s = sn_unit_slabs<float>(U.x, U.halo, U.T, hw, U.C, U.mode, U.wrap, t);      // SURVEY.md 8a-1 table (sn_common.h)
+    const SnSlabs<float> s = sn_unit_slabs<float>(U.x, U.halo, U.T, hw, U.C, U.mode, U.wrap, U.clip, t);      // SURVEY.md 8a-1 table (sn_common.h)
     const size_t n = (size_t)hw * CU;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
         const int i = (int)(e / CU), c = (int)(e - (size_t)i * CU);
@@ -920,7 +923,7 @@ __global__ void gather32_kernel(const Unit32 U, const int8_t* offs, float* u, co
 template <bool CONV>
 __global__ __launch_bounds__(256) void shiftconv32_kernel(const Unit32 U, const int8_t* offs, const float* w, float* vin, float* u) {
     const int t = U.t0 + blockIdx.y, Ch = U.C >> 1, hw = U.h * U.w, CU = U.C + Ch, c4n = U.C >> 2;
-    const SnSlabs<float> s = sn_unit_slabs<float>(U.x, U.halo, U.T, hw, U.C, U.mode, U.wrap, t);      // SURVEY.md 8a-1 table (sn_common.h)
+    const SnSlabs<float> s = sn_unit_slabs<float>(U.x, U.halo, U.T, hw, U.C, U.mode, U.wrap, U.clip, t);      // SURVEY.md 8a-1 table (sn_common.h)
     float* const vt = vin + (size_t)t * hw * CU;
     const size_t na = (size_t)hw * c4n;
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < na; e += (size_t)gridDim.x * 256) {
@@ -1074,6 +1077,13 @@ int conv32_route(const sn32_conv_desc* d) {
     for (int i = 0; i < d->n_in; ++i) { if (!d->in[i] || d->c_in[i] < 1 || d->cs_in[i] < d->c_in[i]) return SN_EINVAL; cin_total += d->c_in[i]; }
     if (cin_total % d->groups) return SN_EINVAL;
     const int cin_g = cin_total / d->groups, cout_g = d->c_out / d->groups;
+    if (sn_remap_set(d->clip_n, d->clip_T, d->clip_lo)) {          // per-clip frame remap: dense split tiles and the exact kernels only
+        if (!sn_remap_ok(d->T, d->clip_n, d->clip_T, d->clip_lo) || d->iscale || d->rscale || d->ln_w || d->csum) return SN_EINVAL;
+        sn32_conv_desc plain = *d;
+        plain.clip_n = plain.clip_T = plain.clip_lo = 0;
+        const int r = conv32_route(&plain);
+        return (r >= 0 && ((r >> 16) == SN32_K_EXACT || (r >> 16) == SN32_K_SPLIT)) ? r : SN_EINVAL;
+    }
     {
         const bool split1 = d->wsplit && d->n_in == 1 && d->in_mode == 0 && d->stride == 1 && (d->cs_in[0] & 3) == 0 && (cin_total & 3) == 0 &&
                             ((size_t)d->in[0] & 15) == 0 && ((size_t)d->wsplit & 15) == 0 && d->groups == 1 && d->out_mode == 0;
@@ -1172,6 +1182,7 @@ int sn32_conv2d(const sn32_conv_desc* d, void* stream) {
     K.iscale = d->iscale; K.iscale_stride = d->iscale_stride;
     K.rscale = d->rscale; K.rscale_stride = d->rscale_stride;
     K.lnw = d->ln_w; K.lnb = d->ln_b; K.csum = d->csum; K.csum_cpad = d->csum_cpad;
+    K.clip_n = d->clip_n; K.clip_T = d->clip_T; K.clip_lo = d->clip_lo;
     const size_t n = (size_t)d->T * d->h_out * d->w_out * d->c_out;
     hipStream_t st = (hipStream_t)stream;
     const int a = (route >> 8) & 255, b = route & 255;
@@ -1201,7 +1212,7 @@ int sn32_conv2d(const sn32_conv_desc* d, void* stream) {
 int sn32_gsts_gather(const sn_unit_src* s, const int8_t* offs, float* u, float* u2, void* stream) {
     sn_clear_error();
     if (!s || !s->x || !u || (u2 && !offs) || (s->C & 1) || s->T < 1 || s->mode < 1 || s->mode > 2 || s->wrap < 0 || s->wrap > 2 || (s->wrap == 2 && !s->halo)) return SN_EINVAL;
-    Unit32 U; U.x = (const float*)s->x; U.halo = (const float*)s->halo; U.T = s->T; U.h = s->h; U.w = s->w; U.C = s->C; U.mode = s->mode; U.wrap = s->wrap;
+    Unit32 U; U.x = (const float*)s->x; U.halo = (const float*)s->halo; U.T = s->T; U.h = s->h; U.w = s->w; U.C = s->C; U.mode = s->mode; U.wrap = s->wrap; U.clip = sn_clip_len(s->T, s->clip);
     SN_FRAME_RANGE(s, t0, nt);
     U.t0 = t0;
     hipLaunchKernelGGL(gather32_kernel, dim3(1024, nt), dim3(256), 0, (hipStream_t)stream, U, offs, u, offs ? s->C + s->C / 2 : s->C, u2);
@@ -1212,7 +1223,7 @@ int sn32_gsts_shiftconv(const sn_unit_src* s, const int8_t* offs, const float* w
     sn_clear_error();
     if (!s || !s->x || !offs || (!w == !u) || !vin || (s->C & 7) || s->T < 1 || s->mode < 1 || s->mode > 2 || s->wrap < 0 || s->wrap > 2 || (s->wrap == 2 && !s->halo) ||
         (((size_t)s->x | (size_t)s->halo | (size_t)vin) & 15)) return SN_EINVAL;
-    Unit32 U; U.x = (const float*)s->x; U.halo = (const float*)s->halo; U.T = s->T; U.h = s->h; U.w = s->w; U.C = s->C; U.mode = s->mode; U.wrap = s->wrap;
+    Unit32 U; U.x = (const float*)s->x; U.halo = (const float*)s->halo; U.T = s->T; U.h = s->h; U.w = s->w; U.C = s->C; U.mode = s->mode; U.wrap = s->wrap; U.clip = sn_clip_len(s->T, s->clip);
     SN_FRAME_RANGE(s, t0, nt);
     U.t0 = t0;
     if (w) hipLaunchKernelGGL(shiftconv32_kernel<true>, dim3(1024, nt), dim3(256), 0, (hipStream_t)stream, U, offs, w, vin, u);

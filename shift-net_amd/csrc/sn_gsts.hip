@@ -12,10 +12,10 @@ namespace {
 
 struct UnitK {
     const bf16_t* x; const bf16_t* halo;
-    int T, h, w, C, mode, wrap, t0;
+    int T, h, w, C, mode, wrap, t0, clip;      // clip: frames per clip, T for one clip (sn_clip_len)
 };
 __device__ __forceinline__ SnSlabs<bf16_t> unit_slabs(const UnitK& U, int t) {
-    return sn_unit_slabs<bf16_t>(U.x, U.halo, U.T, U.h * U.w, U.C, U.mode, U.wrap, t);
+    return sn_unit_slabs<bf16_t>(U.x, U.halo, U.T, U.h * U.w, U.C, U.mode, U.wrap, U.clip, t);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -565,7 +565,7 @@ void scale_gemm_res_kernel(const UnitK U, const bf16_t* __restrict__ g2, const f
 
 UnitK to_k(const sn_unit_src* s) {
     UnitK u; u.x = (const bf16_t*)s->x; u.halo = (const bf16_t*)s->halo; u.T = s->T; u.h = s->h; u.w = s->w; u.C = s->C; u.mode = s->mode; u.wrap = s->wrap;
-    u.t0 = s->nt > 0 ? s->t0 : 0;
+    u.t0 = s->nt > 0 ? s->t0 : 0; u.clip = sn_clip_len(s->T, s->clip);
     return u;
 }
 bool unit_ok(const sn_unit_src* s) {

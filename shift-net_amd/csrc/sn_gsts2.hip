@@ -13,7 +13,7 @@ namespace {
 
 struct UnitK2 {
     const bf16_t* x; const bf16_t* halo;
-    int T, h, w, C, mode, wrap, t0;
+    int T, h, w, C, mode, wrap, t0, clip;      // clip: frames per clip, T for one clip (sn_clip_len)
 };
 
 // ------------------------------------------------------------------------------------------------------------
@@ -36,7 +36,7 @@ __global__ __launch_bounds__(SN_K12_NWV * 64) void ln_gemm_gate_kernel(const Uni
     t += U.t0;
     const int oy0 = tyi * TH, ox0 = txi * TW;
     const int hw = U.h * U.w;
-    const SnSlabs<bf16_t> sl = sn_unit_slabs<bf16_t>(U.x, U.halo, U.T, hw, C, U.mode, U.wrap, t);
+    const SnSlabs<bf16_t> sl = sn_unit_slabs<bf16_t>(U.x, U.halo, U.T, hw, C, U.mode, U.wrap, U.clip, t);
 
     // weight fragments and bias of one chunk, fetched one chunk AHEAD (they come from L2: ~1 us when loaded at the point of use)
     bf16x8_t Wf[2][KS];
@@ -462,7 +462,7 @@ int sn_ln_gemm_gate(const sn_unit_src* s, const void* hw, const void* wfrag, con
     if (!s || !s->x || (s->C != 64 && s->C != 80) || s->mode < 0 || s->mode > 2 || !wfrag || !bias || !wdw || !g1 ||
         (s->mode != 0 && !hw) || (g1_blocked && s->C != 64) || (g1_blocked != 0 && g1_blocked != 2) || (s->wrap == 2 && s->mode != 0 && !s->halo))
         return SN_EINVAL;
-    UnitK2 u; u.x = (const bf16_t*)s->x; u.halo = (const bf16_t*)s->halo; u.T = s->T; u.h = s->h; u.w = s->w; u.C = s->C; u.mode = s->mode; u.wrap = s->wrap;
+    UnitK2 u; u.x = (const bf16_t*)s->x; u.halo = (const bf16_t*)s->halo; u.T = s->T; u.h = s->h; u.w = s->w; u.C = s->C; u.mode = s->mode; u.wrap = s->wrap; u.clip = sn_clip_len(s->T, s->clip);
     SN_FRAME_RANGE(s, t0, nt);
     u.t0 = t0;
     const XcdTiles G = sn_xcd_tiles((s->w + 31) / 32, (s->h + SN_K12_TH - 1) / SN_K12_TH, nt);

@@ -70,7 +70,7 @@ __host__ __device__ inline int p1r_strip_begin(int nsx, int sd, int sr, int s, i
 
 struct P1RArgs {
     const bf16_t* x; const bf16_t* halo; const bf16_t* hwb;
-    int T, h, w, mode, wrap, t0, nfr;
+    int T, h, w, mode, wrap, t0, nfr, clip;      // clip: frames per clip, T for one clip (sn_clip_len)
     const uint4* wfrag1; const uint4* w3; const uint4* wgrp; const uint4* wfrag2;
     bf16_t* g2; float* pool;
     P1RPlan P;
@@ -363,7 +363,7 @@ __global__ __launch_bounds__((p1r_threads<C, HW, ICA>())) void cab_phase1r_kerne
             if (!item(u, I)) continue;
             const int t = I.t, Y0 = I.Y0, Y1 = I.Y1, seg = Y1 - Y0;
             const int NS = (seg + (ICA == 1 ? 7 : SH::WARM) + 1) & ~1;        // even: the stagers rotate two register sets (a padding step only has the barrier)
-            const SnSlabs<bf16_t> sl = sn_unit_slabs<bf16_t>(A.x, A.halo, A.T, hw, C, A.mode, A.wrap, t);
+            const SnSlabs<bf16_t> sl = sn_unit_slabs<bf16_t>(A.x, A.halo, A.T, hw, C, A.mode, A.wrap, A.clip, t);
             const bf16_t* sp[NP0];
             int sst[NP0];
 #pragma unroll
@@ -865,7 +865,7 @@ int cab_phase1(const sn_unit_src* s, const void* hw, const sn_phase1_weights* wt
     const int ncu = p1r_ncu();
     if (ncu < 1) return SN_ELAUNCH;
     P1RArgs A;
-    A.x = (const bf16_t*)s->x; A.halo = (const bf16_t*)s->halo; A.hwb = (const bf16_t*)hw; A.T = s->T; A.h = s->h; A.w = s->w; A.mode = s->mode; A.wrap = s->wrap;
+    A.x = (const bf16_t*)s->x; A.halo = (const bf16_t*)s->halo; A.hwb = (const bf16_t*)hw; A.T = s->T; A.h = s->h; A.w = s->w; A.mode = s->mode; A.wrap = s->wrap; A.clip = sn_clip_len(s->T, s->clip);
     A.wfrag1 = (const uint4*)wt->wfrag1; A.w3 = (const uint4*)wt->w3; A.wgrp = (const uint4*)wt->wgrp; A.wfrag2 = (const uint4*)wt->wfrag2;
     A.g2 = (bf16_t*)g2; A.pool = pool;
     A.g1_scale = opt ? opt->g1_scale : nullptr; A.g1_sums = sums ? 1 : 0;

@@ -6,6 +6,7 @@ Contract mirrored:
   * ``forward(x[, noise_map], k1=None, k2=None, k3=None)``: ``x:[B,T,3,H,W]`` in the parameters' dtype, only
     ``x[0]`` is used, returns ``[T-P-F, 3, H, W]``; ``T <= P+F`` gives an empty tensor;
   * ``load_state_dict(torch.load(p)['params'])`` strict: keys/shapes/aliases come from ``spec.param_table``.
+Beyond the upstream API: ``forward_clips(x[, noise_map])`` / ``forward_clips_fp32_out`` restore all B clips of ``x`` in one set of launches.
 There is no CPU path: calling ``forward`` without a HIP device and the built library raises.
 """
 from __future__ import annotations
@@ -136,6 +137,32 @@ class GShiftNetBase(nn.Module):
     def forward(self, x, noise_map=None, k1=None, k2=None, k3=None):
         return self._run(x, noise_map, None, None)
 
+    def forward_clips(self, x, noise_map=None):
+        """Restore B independent clips of the same shape in ONE set of launches: ``x:[B,T,3,H,W]`` -> ``[B, T-P-F, 3, H, W]``, clip b
+        bit-identical to ``forward(x[b:b+1])`` (``noise_map[b:b+1]``) on this module.  ``noise_map``: ``[B,T,1,H,W]`` or broadcastable to it.
+        Not part of the upstream API (whose ``forward`` restores ``x[0]`` only).  Not available on a temporally split module."""
+        return self._run_clips(x, noise_map, None, None)
+
+    def forward_clips_fp32_out(self, x, noise_map=None, shortcut=None):
+        """``forward_clips`` with float32 frames as ``forward_fp32_out`` returns them; ``shortcut``: ``[B,T,3,H,W]`` float32 or None.
+        Not part of the upstream API."""
+        return self._run_clips(x, noise_map, torch.float32, shortcut)
+
+    def _run_clips(self, x, noise_map, out_dtype, shortcut):
+        if not isinstance(x, torch.Tensor) or x.dim() != 5:
+            raise ValueError(f"forward_clips expects x:[B,T,C,H,W], got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+        dt = next(self.parameters()).dtype
+        if x.dtype != dt:
+            raise RuntimeError(f"Input type ({x.dtype}) and weight type ({dt}) should be the same")
+        if self.V.denoise and noise_map is None:
+            raise TypeError("noise_map is required by the denoise variants")
+        if shortcut is not None and (shortcut.dim() != 5 or tuple(shortcut.shape[:2]) != tuple(x.shape[:2])):
+            raise ValueError(f"shortcut must be [B,T,3,H,W] like x, got {tuple(shortcut.shape)}")
+        if getattr(self, "_split", None) is not None:
+            raise ValueError("forward_clips cannot be combined with a temporal split (set_temporal_split)")
+        eng = self.prepare()
+        return eng.forward_clips(x, noise_map, self.num_fb, self.num_ff, out_dtype, shortcut)
+
     def _run(self, x, noise_map, out_dtype, shortcut):
         eng = self.prepare()
         dt = next(self.parameters()).dtype
@@ -160,6 +187,12 @@ def _make(variant: str):
 
             def forward_fp32_out(self, x, shortcut=None):
                 return self._run(x, None, torch.float32, shortcut)
+
+            def forward_clips(self, x):
+                return self._run_clips(x, None, None, None)
+
+            def forward_clips_fp32_out(self, x, shortcut=None):
+                return self._run_clips(x, None, torch.float32, shortcut)
 
     GShiftNet.variant = variant
     GShiftNet.__qualname__ = "GShiftNet"

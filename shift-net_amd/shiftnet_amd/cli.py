@@ -100,9 +100,11 @@ def denoise_windows(n_frames: int) -> List[Tuple[int, int, int]]:
     return [(kk * one_len, one_len + (k_res if kk == k_len - 1 else 0), k_res if kk == k_len - 1 else 0) for kk in range(k_len)]
 
 
-def quadrant_forward(net, x: torch.Tensor, sigma: float, on_device: bool = False, x32: Optional[torch.Tensor] = None) -> torch.Tensor:
+def quadrant_forward(net, x: torch.Tensor, sigma: float, on_device: bool = False, x32: Optional[torch.Tensor] = None,
+                     batch: bool = False) -> torch.Tensor:
     """The denoise CLI's 4 overlapping quadrants (test_denoise.py:153-173); x:[1,N,3,H,W] on device.  The stitched float32 frames are
-    returned on the host like upstream's, or stay on the device (on_device) for the device-side metrics."""
+    returned on the host like upstream's, or stay on the device (on_device) for the device-side metrics.  batch (--batch_quadrants): the four
+    same-shape crops go through ONE forward_clips_fp32_out call instead of four forwards; the stitched frames are bit-identical."""
     B, N, _, H, W = x.shape
     pad_h, pad = 32 - (H // 2 % 16), 32 - (W // 2 % 16)
     hh, ww = H // 2 + pad_h, W // 2 + pad
@@ -113,12 +115,17 @@ def quadrant_forward(net, x: torch.Tensor, sigma: float, on_device: bool = False
         sc = x32[:, :, :, ys, xs].contiguous() if x32 is not None and x32.dtype != x.dtype else None
         o = net.forward_fp32_out(x[:, :, :, ys, xs].contiguous(), std, shortcut=sc)
         return o if on_device else o.cpu()
+    quads = [(slice(0, hh), slice(0, ww)), (slice(0, hh), slice(W // 2 - pad, W)),
+             (slice(H // 2 - pad_h, H), slice(0, ww)), (slice(H // 2 - pad_h, H), slice(W // 2 - pad, W))]
+
+    def run_batched():
+        xb = torch.cat([x[:, :, :, ys, xs] for ys, xs in quads], 0)
+        sc = torch.cat([x32[:, :, :, ys, xs] for ys, xs in quads], 0) if x32 is not None and x32.dtype != x.dtype else None
+        o = net.forward_clips_fp32_out(xb, std.expand(4, N, 1, hh, ww), shortcut=sc)
+        return list(o if on_device else o.cpu())
     for _ in range(2):      # one range-guard check for the four quadrants (no device sync between them); a tripped guard moved the module to the
         with net.guard_scope() as gs:      # bf16 chain: run them once more
-            o1 = run(slice(0, hh), slice(0, ww))
-            o2 = run(slice(0, hh), slice(W // 2 - pad, W))
-            o3 = run(slice(H // 2 - pad_h, H), slice(0, ww))
-            o4 = run(slice(H // 2 - pad_h, H), slice(W // 2 - pad, W))
+            o1, o2, o3, o4 = run_batched() if batch else [run(ys, xs) for ys, xs in quads]
         if not gs.tripped:
             break
     out[..., 0:H // 2, 0:W // 2] = o1[..., 0:-pad_h, 0:-pad]
@@ -286,14 +293,14 @@ class Inference:
                     x32 = x32 + torch.empty_like(x32).normal_(mean=0, std=sigma)
                     x = x32.to(self.dtype)
                     t1 = time.time()
-                    output = quadrant_forward(self.net, x, sigma, on_device=True, x32=x32)
+                    output = quadrant_forward(self.net, x, sigma, on_device=True, x32=x32, batch=a.batch_quadrants)
                 elif self.denoise:              # upstream's host path (test_denoise.py:145-173)
                     x32 = numpy2tensor(inputs)
                     sigma = a.sigma / 255.0
                     x32 = (x32 + torch.empty_like(x32).normal_(mean=0, std=sigma)).to(self.device)
                     x = x32.to(self.dtype)
                     t1 = time.time()
-                    output = quadrant_forward(self.net, x, sigma, x32=x32)
+                    output = quadrant_forward(self.net, x, sigma, x32=x32, batch=a.batch_quadrants)
                 elif dev_io:
                     u8 = torch.from_numpy(np.stack(inputs)).to(self.device)
                     x = ingest_u8(u8, self.dtype)
@@ -340,7 +347,8 @@ class Inference:
         return self._summary(total_psnr, total_ssim)
 
 
-def main(variant: str, argv: Optional[Sequence[str]] = None) -> Tuple[float, float]:
+def make_parser(variant: str) -> argparse.ArgumentParser:
+    """The command line of the CLI of `variant` (inference/test_{deblur,denoise}{,_small}.py)."""
     denoise = "denoise" in variant
     small = variant.endswith("2")
     ap = argparse.ArgumentParser(description="Inference")
@@ -350,6 +358,8 @@ def main(variant: str, argv: Optional[Sequence[str]] = None) -> Tuple[float, flo
     if denoise:
         ap.add_argument("--sigma", type=int, default=10, help="sigma")
         ap.add_argument("--one", type=int, default=10, help="unused upstream")
+        ap.add_argument("--batch_quadrants", action="store_true",
+                        help="run the four quadrants of a window as ONE batched forward (forward_clips) instead of four; results are bit-identical")
     else:
         ap.add_argument("--one_len", type=int, default=96 if small else 48)
     ap.add_argument("--synthetic", type=int, nargs=3, metavar=("H", "W", "N"), default=None)
@@ -364,6 +374,13 @@ def main(variant: str, argv: Optional[Sequence[str]] = None) -> Tuple[float, flo
         ap.add_argument("--gpus", type=int, default=1, help="clip-parallel: one process per GPU, the windows of a clip N at a time")
         ap.add_argument("--halo", choices=["auto", "p2p", "allgather"], default="auto",
                         help="clip-parallel halo exchange: point to point, all-gather, or point to point with an automatic fall-back (default)")
+    return ap
+
+
+def main(variant: str, argv: Optional[Sequence[str]] = None) -> Tuple[float, float]:
+    denoise = "denoise" in variant
+    small = variant.endswith("2")
+    ap = make_parser(variant)
     a = ap.parse_args(argv)
     if a.fp32_exact:
         os.environ["SN_FP32_EXACT"] = "1"

@@ -216,6 +216,8 @@ class Engine:
         self.split = None                     # temporal_split.TemporalSplit: this engine holds a frame range of a longer window
         self._side = None                     # side stream of the halo exchanges (created on first use)
         self._tickets = None                  # sn_se_fold frame counters: zero between launches (the kernels re-arm them)
+        self._old_tickets: List[torch.Tensor] = []
+        self._clip = 0                        # frames per clip while a batch of clips is being issued (forward_clips); 0: one clip
         self._bad = None                      # the range guard's device flag (one u32), created on first use
         self.fallbacks = 0                    # how often the guard moved this engine from the fused phase 1 to the bf16 chain (0 or 1)
         if self.phase1 not in ("auto", "r", "0"):
@@ -264,10 +266,15 @@ class Engine:
 
     def conv(self, name: str, ins: Sequence[Act], *, stride: int = 1, pad: Optional[int] = None, prelu: Optional[float] = None,
              res: Optional[Act] = None, out_mode: int = 0, pool: bool = False, in_mode: int = 0, oscale: Optional[torch.Tensor] = None,
-             nchw_out: Optional[torch.Tensor] = None, nchw_sc: Optional[torch.Tensor] = None, res2: Optional[Act] = None):
+             nchw_out: Optional[torch.Tensor] = None, nchw_sc: Optional[torch.Tensor] = None, res2: Optional[Act] = None,
+             remap: Optional[Tuple[int, int, int]] = None):
+        """remap = (clip_n, clip_T, clip_lo): the inputs hold clips of clip_T frames and output frame j reads frame
+        (j / clip_n) * clip_T + clip_lo + j % clip_n of them (sn_conv_desc; the trim of a batch of clips read in place)."""
         p = self.P.convs[name]
         k, cout = int(p["k"]), int(p["cout"])
         T, hs, ws, cs_in = ins[0].dims
+        if remap is not None:
+            T = T // remap[1] * remap[0]
         assert cs_in == p["cs_in"] and len(ins) == p["n_in"], (name, cs_in, p["cs_in"])
         h_in, w_in = (2 * hs, 2 * ws) if in_mode == 1 else (hs, ws)
         if pad is None:
@@ -306,6 +313,8 @@ class Engine:
             d.res2 = res2.t.data_ptr()
         if oscale is not None:
             d.oscale, d.oscale_stride = oscale.data_ptr(), oscale.shape[1]
+        if remap is not None:
+            d.clip_n, d.clip_T, d.clip_lo = remap
         if pool:
             nblk = self.lib.sn_conv_pool_blocks(C.byref(d))
             pool_buf = torch.empty((T, nblk, 16 * d.mt), dtype=torch.float32, device=self.dev)
@@ -452,7 +461,7 @@ class Engine:
         T, h, w, cs = x.dims
         assert cs == x.c
         wrap = self._wrap_flag(mode, self.V.wrap) if wrap is None else wrap
-        return L.UnitSrc(x.t.data_ptr(), T, h, w, x.c, mode, wrap, halo.data_ptr() if halo is not None else None, t0, nt)
+        return L.UnitSrc(x.t.data_ptr(), T, h, w, x.c, mode, wrap, halo.data_ptr() if halo is not None else None, t0, nt, self._clip)
 
     def _split_pieces(self, x: Act, mode: int, circular: bool):
         """Launch plan of a shifted operator on a temporally split window (temporal_split.py): [(wrap, halo, t0, nt), ...].
@@ -506,12 +515,26 @@ class Engine:
             self._bad = torch.zeros((1,), dtype=torch.int32, device=self.dev)
         return self._bad.data_ptr()
 
+    def _fold_ok(self, T: int) -> bool:
+        """Can the squeeze-excite tail of phase 1 finish the CALayer2 of a tensor of T frames?  Decided on the CLIP length, so that a batch of
+        clips (forward_clips) takes the path each of its clips would take alone; the counters then cover the whole batch (_ticket_ptr)."""
+        return self.fold_se and (self._clip or T) <= self.MAX_TICKETS
+
+    def _ticket_ptr(self, T: int) -> int:
+        """sn_se_fold frame counters for T frames (zero between launches: the kernels re-arm them).  A buffer outgrown by a larger batch stays
+        referenced: a captured graph may still use it."""
+        if self._tickets is None or self._tickets.numel() < T:
+            if self._tickets is not None:
+                self._old_tickets.append(self._tickets)
+            self._tickets = torch.zeros((max(self.MAX_TICKETS, T),), dtype=torch.int32, device=self.dev)
+        return self._tickets.data_ptr()
+
     def _fused_phase1(self, T: int) -> bool:
         """Does phase 1 of this engine's CAB2 / CAB1 run as the fused kernel?  (The denoisers' two passes rely on the squeeze-excite tail for
-        the inner scale, whose frame counters cover MAX_TICKETS frames.)"""
+        the inner scale, whose frame counters cover MAX_TICKETS frames per clip.)"""
         if self.phase1 == "0":
             return False
-        return not (self.V.denoise and (not self.fold_se or T > self.MAX_TICKETS))
+        return not (self.V.denoise and not self._fold_ok(T))
 
     def naf(self, pre: str, x: Act, mode: int, *, frames: Optional[Tuple[int, int]] = None, bufs: Optional[Dict[str, torch.Tensor]] = None) -> Act:
         """CAB2 (mode 1/2, fed by the GSTS gather of x) or CAB1 (mode 0) (gshift_deblur1.py:183-255).
@@ -532,8 +555,7 @@ class Engine:
         B = bufs if bufs is not None else self.naf_buffers(T, h, w, c, mode)
         hwb, g2, y, pool2, ca2, ca1, g1, pool1, g1s = (B.get(k) for k in ("hwb", "g2", "y", "pool2", "ca2", "ca1", "g1", "pool1", "g1s"))
         nb2 = pool2.shape[1]
-        if self._tickets is None and fused and self.fold_se:
-            self._tickets = torch.zeros((self.MAX_TICKETS,), dtype=torch.int32, device=self.dev)
+        tickets = self._ticket_ptr(T) if fused and self._fold_ok(T) else None
         b_out = u["b_out"].data_ptr() if u["b_out"] is not None else None
         es = 2                                           # bytes per activation element
         bad = self._guard_ptr()
@@ -563,14 +585,14 @@ class Engine:
             if fused:
                 wt = C.byref(u["p1r"]["desc"])
                 sep = None
-                if self.fold_se and T <= self.MAX_TICKETS:
+                if tickets is not None:
                     q = P.cas[pre + "ca2"]
-                    se = L.SeFold(q["wa"].data_ptr(), q["wb"].data_ptr(), q["c"], q["cr"], self._tickets.data_ptr(), ca2.data_ptr(), bad)
+                    se = L.SeFold(q["wa"].data_ptr(), q["wb"].data_ptr(), q["c"], q["cr"], tickets, ca2.data_ptr(), bad)
                     sep = C.byref(se)
                 opt = None
                 if V.denoise:      # inner CALayer2 on g1 (gshift_denoise1.py:224,257): pass 1 = the channel sums of g1 and, by the tail, its scale ca1
                     q1 = P.cas[pre + "ca1"]
-                    se1 = L.SeFold(q1["wa"].data_ptr(), q1["wb"].data_ptr(), q1["c"], q1["cr"], self._tickets.data_ptr(), ca1.data_ptr(), bad)
+                    se1 = L.SeFold(q1["wa"].data_ptr(), q1["wb"].data_ptr(), q1["c"], q1["cr"], tickets, ca1.data_ptr(), bad)
                     g1s_ptr = g1s.data_ptr() if (g1s is not None and self.g1_store) else None
                     o1 = L.Phase1Opts(None, 1, 0, g1s_ptr)
                     fn1 = "sn_gsts_cab2_phase1" if mode else "sn_cab1_phase1"
@@ -677,11 +699,11 @@ class Engine:
 
     def _shift_chain(self, pres: Sequence[str], x: Act) -> Act:
         T = x.dims[0]
-        if self.schedule == "streams" and self.split is None and not torch.cuda.is_current_stream_capturing():
+        if self.schedule == "streams" and self.split is None and not self._clip and not torch.cuda.is_current_stream_capturing():
             ng = min(self.stream_groups, T // 2)
             if ng >= 2 and (T // ng) * x.dims[1] * x.dims[2] >= self.STREAMS_MIN_PXF:
                 return self._shift_chain_streams(pres, x, ng)
-        if self.schedule != "frame" or self.split is not None or T <= self.frame_group:
+        if self.schedule != "frame" or self.split is not None or self._clip or T <= self.frame_group:
             for pre in pres:
                 x = self.shift_block(pre, x)
             return x
@@ -715,8 +737,8 @@ class Engine:
         streams = self._gstreams[:ng]
         main = torch.cuda.current_stream(self.dev)
         sets = [(self.naf_buffers(T, h, w, c, 1), self.naf_buffers(T, h, w, c, 0)) for _ in range(R)]
-        if self._tickets is None and self._fused_phase1(T) and self.fold_se:      # allocated on the launching stream, not on a group's
-            self._tickets = torch.zeros((self.MAX_TICKETS,), dtype=torch.int32, device=self.dev)
+        if self._fused_phase1(T) and self._fold_ok(T):      # allocated on the launching stream, not on a group's
+            self._ticket_ptr(T)
         self._guard_ptr()
         ready = main.record_event()
         done: List[List[Optional[torch.cuda.Event]]] = [[None] * ng for _ in units]      # unit u's output frames of group g are written
@@ -854,6 +876,42 @@ class Engine:
                 out = self._recover(lambda: self._forward(x, noise_map, past, future, out_dtype, shortcut), out, x.shape[0])
             return out
 
+    @torch.no_grad()
+    def forward_clips(self, x: torch.Tensor, noise_map: Optional[torch.Tensor], past: int, future: int,
+                      out_dtype: Optional[torch.dtype] = None, shortcut: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """B independent clips of the same shape in one set of launches: x:[B,T,C,H,W] -> [B, T-past-future, 3, H, W], clip b bit-identical
+        to forward(x[b], ...).  The batch runs as B*T frames: the shift units apply their neighbour rule inside each clip (sn_unit_src.clip),
+        rconcat reads each clip's kept frames [past, T-future) in place (the conv remap), every other operator is per frame.
+        noise_map: [B,T,1,H,W] or broadcastable to it; shortcut: [B,T,3,H,W] as in forward.  One range-guard check (and at most one recovery)
+        covers the whole batch.  Not combinable with a temporal split (ValueError); SN_SCHEDULE=frame / streams run the plain unit schedule here."""
+        if self.split is not None:
+            raise ValueError("forward_clips cannot be combined with a temporal split (set_temporal_split)")
+        if x.dim() != 5:
+            raise ValueError(f"forward_clips expects x:[B,T,C,H,W], got {tuple(x.shape)}")
+        B, T, cin, H, W = x.shape
+        xf = x.reshape(B * T, cin, H, W)
+        nm = noise_map.expand(B, T, 1, H, W).reshape(B * T, 1, H, W) if noise_map is not None else None
+        sc = None
+        if shortcut is not None:
+            assert shortcut.dim() == 5 and tuple(shortcut.shape[:2]) == (B, T), tuple(shortcut.shape)
+            sc = shortcut.reshape(B * T, *shortcut.shape[2:])
+        n_out = max(T - past - future, 0)
+        with torch.cuda.device(self.dev):
+            graphed = self.use_graph or (self.graph_auto and B * T * H * W <= self.GRAPH_AUTO_PXF)
+            eager = (not graphed or self.prof is not None or out_dtype is not None or shortcut is not None
+                     or torch.cuda.is_current_stream_capturing())
+            if self.range_guard_async:
+                self.check_range_guard()
+            out = (self._forward(xf, nm, past, future, out_dtype, sc, clip=T) if eager
+                   else self._forward_graphed(xf, nm, past, future, clip=T))
+            if self._scope is not None:
+                self._scope.frames = max(self._scope.frames, T)
+            elif self.range_guard_async:
+                self._post_guard_copy()
+            elif self._guard_tripped():
+                out = self._recover(lambda: self._forward(xf, nm, past, future, out_dtype, sc, clip=T), out, T)
+            return out.reshape(B, n_out, *out.shape[1:])
+
     _scope = None
 
     class GuardScope:
@@ -950,16 +1008,20 @@ class Engine:
                       "not reliable -- run the module in float32 (net.float(): the fp32 engine has no half-precision intermediates).")
         return out
 
-    def _forward_graphed(self, x, noise_map, past, future):
-        key = (tuple(x.shape), x.dtype, None if noise_map is None else (tuple(noise_map.shape), noise_map.dtype), past, future)
+    def _forward_graphed(self, x, noise_map, past, future, clip: int = 0):
+        # clip: frames per clip of a batch (forward_clips; x holds B * clip frames), 0 for forward -- part of the key, so is B
+        key = (tuple(x.shape), x.dtype, None if noise_map is None else (tuple(noise_map.shape), noise_map.dtype), past, future, clip)
+
+        def run(xx, nn):
+            return self._forward(xx, nn, past, future, clip=clip) if clip else self._forward(xx, nn, past, future)
         ent = self._graphs.get(key)
         if ent is None:                         # first sight of this signature: eager (also the warm-up the capture needs)
             self._graphs[key] = "seen"
             self._evict_graphs()
-            return self._forward(x, noise_map, past, future)
+            return run(x, noise_map)
         self._graphs.move_to_end(key)
         if ent == "eager":
-            return self._forward(x, noise_map, past, future)
+            return run(x, noise_map)
         if ent == "seen":
             try:
                 sx = x.clone()
@@ -968,7 +1030,7 @@ class Engine:
                 # thread_local: an allocation or a sync on ANOTHER host thread (pin-memory workers, a second engine) must neither fail nor
                 # invalidate this capture; __exit__ ends the capture on an exception too: the stream is never left capturing
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    so = self._forward(sx, sn, past, future)
+                    so = run(sx, sn)
                 ent = self._graphs[key] = (g, sx, sn, so)
                 self._evict_graphs()
             except Exception as e:                                  # noqa: BLE001  (capture unsupported here: stay eager, say so once)
@@ -981,7 +1043,7 @@ class Engine:
                 warnings.warn(f"shiftnet_amd: hipGraph capture failed ({type(e).__name__}: {e}); running eagerly")
                 self._graphs[key] = "eager"
                 torch.cuda.synchronize(self.dev)
-                return self._forward(x, noise_map, past, future)
+                return run(x, noise_map)
         g, sx, sn, so = ent
         sx.copy_(x)
         if sn is not None:
@@ -1007,7 +1069,19 @@ class Engine:
                 v[0].reset()
 
     def _forward(self, x: torch.Tensor, noise_map: Optional[torch.Tensor], past: int, future: int,
-                 out_dtype: Optional[torch.dtype] = None, shortcut: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 out_dtype: Optional[torch.dtype] = None, shortcut: Optional[torch.Tensor] = None, clip: int = 0) -> torch.Tensor:
+        """clip > 0: x holds x.shape[0] / clip clips of `clip` frames (forward_clips); the result is their trimmed frames, clip after clip."""
+        if clip:
+            assert self.split is None and x.shape[0] % clip == 0
+            self._clip = clip
+            try:
+                return self._forward_frames(x, noise_map, past, future, out_dtype, shortcut)
+            finally:
+                self._clip = 0
+        return self._forward_frames(x, noise_map, past, future, out_dtype, shortcut)
+
+    def _forward_frames(self, x: torch.Tensor, noise_map: Optional[torch.Tensor], past: int, future: int,
+                        out_dtype: Optional[torch.dtype], shortcut: Optional[torch.Tensor]) -> torch.Tensor:
         V = self.V
         x = x.contiguous()
         T, cin, H, W = x.shape
@@ -1015,10 +1089,12 @@ class Engine:
         if H % div or W % div:
             raise ValueError(f"{V.name}: H and W must be multiples of {div} (got {H}x{W})")
         sp = self.split
+        Tc = self._clip or T                # frames per clip
+        B = T // Tc
         lo = past if (sp is None or sp.rank == 0) else 0                         # a split window trims on its outer ranks only
-        hi = T - (future if (sp is None or sp.rank == sp.world - 1) else 0)
+        hi = Tc - (future if (sp is None or sp.rank == sp.world - 1) else 0)
         n_out = max(hi - lo, 0)
-        out = torch.empty((n_out, 3, H, W), dtype=out_dtype or x.dtype, device=x.device)
+        out = torch.empty((B * n_out, 3, H, W), dtype=out_dtype or x.dtype, device=x.device)
         if sp is not None:
             sp.validate(n_out)              # collective: all ranks raise together, none is left waiting in an exchange
         if n_out == 0:
@@ -1034,13 +1110,21 @@ class Engine:
 
         def cut(a: Act) -> Act:
             return Act(a.t[lo:hi], a.c)
-        y = self.conv("rconcat", [cut(x0), cut(feats), cut(dec)], prelu=self.P.scalar("lrelu.weight") if V.denoise else None)
+        prelu = self.P.scalar("lrelu.weight") if V.denoise else None
+        if self._clip:                      # a batch of clips: every clip's [lo, hi) read in place by the conv's frame remap
+            y = self.conv("rconcat", [x0, feats, dec], prelu=prelu, remap=(n_out, Tc, lo))
+        else:
+            y = self.conv("rconcat", [cut(x0), cut(feats), cut(dec)], prelu=prelu)
         sc = y
         for i in range(1, V.n_orb + 1):     # deblur: "+ shortcut" after the last rorb (:779), same folding
             y = self.tfr_unet(f"rorb{i}.", y, sc if (i == V.n_orb and not V.denoise) else None)
         sc = x if shortcut is None else shortcut
         assert sc.shape[0] == T and tuple(sc.shape[2:]) == (H, W) and sc.shape[1] >= 3 and sc.device == x.device
-        self.conv("conv_last", [y], out_mode=2, nchw_out=out, nchw_sc=sc[lo:hi, :3].contiguous() if sc.shape[1] > 3 else sc[lo:hi].contiguous())
+        if self._clip:                      # the per-clip [lo, hi) frames of the 3-channel shortcut, gathered
+            sc_out = sc.reshape(B, Tc, *sc.shape[1:])[:, lo:hi, :3].reshape(B * n_out, 3, H, W).contiguous()
+        else:
+            sc_out = sc[lo:hi, :3].contiguous() if sc.shape[1] > 3 else sc[lo:hi].contiguous()
+        self.conv("conv_last", [y], out_mode=2, nchw_out=out, nchw_sc=sc_out)
         return out
 
 

@@ -22,7 +22,7 @@ from __future__ import annotations
 import os
 
 import ctypes as C
-from typing import Dict, Optional, Sequence
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
@@ -132,11 +132,14 @@ class Engine32(Engine):
                 rscale: Optional[torch.Tensor] = None, ln: Optional[Sequence[torch.Tensor]] = None, csum: Optional[torch.Tensor] = None,
                 out: Optional[torch.Tensor] = None, out_mode: int = 0,
                 in_mode: int = 0, c_out: Optional[int] = None, nchw_out: Optional[torch.Tensor] = None,
-                nchw_sc: Optional[torch.Tensor] = None, label: str = "") -> torch.Tensor:
-        """ins: NHWC fp32 tensors (possibly channel-slice views of wider tensors: the pixel stride is taken from .stride(2))."""
+                nchw_sc: Optional[torch.Tensor] = None, label: str = "", remap: Optional[Tuple[int, int, int]] = None) -> torch.Tensor:
+        """ins: NHWC fp32 tensors (possibly channel-slice views of wider tensors: the pixel stride is taken from .stride(2)).
+        remap: the per-clip frame remap of sn32_conv_desc (Engine.conv)."""
         P = self.P
         w = P.wt(wkey)
         T, hs, ws = ins[0].shape[:3]
+        if remap is not None:
+            T = T // remap[1] * remap[0]
         h_in, w_in = (2 * hs, 2 * ws) if in_mode == 1 else (hs, ws)
         if pad is None:
             pad = k // 2
@@ -188,20 +191,23 @@ class Engine32(Engine):
             d.out, d.cs_out = out.data_ptr(), out.stride(2)
             o = out
         d.out_mode = out_mode
+        if remap is not None:
+            d.clip_n, d.clip_T, d.clip_lo = remap
         self._meta = ("conv32", T, h_out, w_out, sum(cins), co, k, stride, in_mode, out_mode)
         self._call("sn32_conv2d", f"sn32_conv2d[{label or wkey}]", C.byref(d), self._stream())
         return o
 
     def conv(self, name: str, ins: Sequence[Act], *, stride: int = 1, pad: Optional[int] = None, prelu: Optional[float] = None,
              res: Optional[Act] = None, out_mode: int = 0, pool: bool = False, in_mode: int = 0, oscale: Optional[torch.Tensor] = None,
-             nchw_out: Optional[torch.Tensor] = None, nchw_sc: Optional[torch.Tensor] = None, res2: Optional[Act] = None):
+             nchw_out: Optional[torch.Tensor] = None, nchw_sc: Optional[torch.Tensor] = None, res2: Optional[Act] = None,
+             remap: Optional[Tuple[int, int, int]] = None):
         p = self.P.convs[name]
         key = p["key"]
         k = int(self.P.sd[key + "weight"].shape[-1])
         assert oscale is None and res2 is None
         o = self._conv32(key + "weight", key + "bias", [a.t for a in ins], [a.c for a in ins], k=k, stride=stride, pad=pad,
                          prelu=prelu, res=res.t if res is not None else None, out_mode=out_mode, in_mode=in_mode,
-                         nchw_out=nchw_out, nchw_sc=nchw_sc, label=name)
+                         nchw_out=nchw_out, nchw_sc=nchw_sc, label=name, remap=remap)
         if out_mode == 2:
             return None
         a = Act(o, o.shape[3])

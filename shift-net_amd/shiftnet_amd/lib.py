@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libshiftnet_hip.so")
 
 SN_F32, SN_F16, SN_BF16 = 0, 1, 2
 
-ABI_VERSION = 18     # == SN_ABI_VERSION of include/shiftnet_hip.h; a stale .so from before a struct / signature change fails the check in load()
+ABI_VERSION = 19     # == SN_ABI_VERSION of include/shiftnet_hip.h; a stale .so from before a struct / signature change fails the check in load()
 
 SYMBOLS = [          # include/shiftnet_hip.h, production ABI
     "sn_abi_version", "sn_selftest_mfma", "sn_ingest", "sn_conv2d", "sn_conv_pool_blocks", "sn_upsample2_add", "sn_ca_mlp",
@@ -61,7 +61,7 @@ class ConvDesc(C.Structure):
         ("act", C.c_int), ("prelu", C.c_float), ("res", C.c_void_p), ("out", C.c_void_p),
         ("cs_out", C.c_int), ("out_mode", C.c_int), ("c_out", C.c_int), ("nchw_dtype", C.c_int),
         ("sc", C.c_void_p), ("sc_dtype", C.c_int), ("pool", C.c_void_p), ("oscale", C.c_void_p), ("oscale_stride", C.c_int), ("res2", C.c_void_p),
-        ("flags", C.c_int),
+        ("flags", C.c_int), ("clip_n", C.c_int), ("clip_T", C.c_int), ("clip_lo", C.c_int),
     ]
 
 
@@ -79,12 +79,14 @@ class Conv32Desc(C.Structure):
         ("out", C.c_void_p), ("cs_out", C.c_int), ("out_mode", C.c_int), ("nchw_dtype", C.c_int), ("sc", C.c_void_p),
         ("wsplit", C.c_void_p), ("iscale", C.c_void_p), ("iscale_stride", C.c_int), ("rscale", C.c_void_p), ("rscale_stride", C.c_int),
         ("ln_w", C.c_void_p), ("ln_b", C.c_void_p), ("csum", C.c_void_p), ("csum_cpad", C.c_int),
+        ("clip_n", C.c_int), ("clip_T", C.c_int), ("clip_lo", C.c_int),
     ]
 
 
 class UnitSrc(C.Structure):
     _fields_ = [("x", C.c_void_p), ("T", C.c_int), ("h", C.c_int), ("w", C.c_int), ("C", C.c_int),
-                ("mode", C.c_int), ("wrap", C.c_int), ("halo", C.c_void_p), ("t0", C.c_int), ("nt", C.c_int)]
+                ("mode", C.c_int), ("wrap", C.c_int), ("halo", C.c_void_p), ("t0", C.c_int), ("nt", C.c_int),
+                ("clip", C.c_int)]
 
 
 class ShiftNetLibError(RuntimeError):
