@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SN_ABI_VERSION 19     /* bump on ANY change of a struct, signature or operand encoding (shiftnet_amd/lib.py checks it) */
+#define SN_ABI_VERSION 20    /* bump on ANY change of a struct, signature or operand encoding (shiftnet_amd/lib.py checks it) */
 
 /* element types of NCHW tensors exchanged with the PyTorch side */
 #define SN_F32 0
@@ -85,7 +85,8 @@ typedef struct sn_conv_desc {
                             prefetch depth code (1 / 2: three / four tiles ahead at 16 channels; 3: the streaming fused CAB with two region buffers);
                             bits 12..14: MEASUREMENTS ONLY, WRONG RESULTS -- the streaming conv without its DMA (1), B reads / MFMAs (2), stores (4);
                             on conv2 of sn_cab_fused(rows = 0) bit 12 means "both weight sets in LDS" (results unchanged); bit 15: stride-2 convs on
-                            4 x 16 tiles whatever their width (measurements; results unchanged) */
+                            4 x 16 tiles whatever their width (measurements; results unchanged).  Which instance a descriptor runs on, with these
+                            bits and without: sn_conv2d_route (below) */
     int clip_n, clip_T, clip_lo; /* per-clip frame remap (ABI 19; all 0 = off): output frame j reads frame (j / clip_n) * clip_T + clip_lo + j % clip_n
                             of every in[] -- the kept frames [clip_lo, clip_lo + clip_n) of each clip of a batch, read in place (rconcat of
                             Engine.forward_clips).  out, res, res2, pool and oscale stay indexed by j.  T % clip_n == 0, clip_lo + clip_n <= clip_T.
@@ -96,6 +97,22 @@ typedef struct sn_conv_desc {
 int sn_conv2d(const sn_conv_desc* d, void* stream);   /* d is a HOST pointer, read during the call */
 /* number of workgroups per frame sn_conv2d launches for this descriptor (= rows of `pool` per frame); host only */
 int sn_conv_pool_blocks(const sn_conv_desc* d);
+/* The kernel instance sn_conv2d (lines_len = 0) or sn_cab_stats(d, lines_len) (lines_len > 0) launches for d, or SN_EINVAL where that entry point
+ * refuses d (ABI 20).  Both entry points launch exactly what this returns.  Host only: the pointers are tested for NULL, never read.
+ * ncu: compute units the streaming kernel plans for; 0 = the current device (none: the tile kernel, as the entry points do), < 0 = no device.
+ * plan: NULL, or int[8] that receives the streaming kernel's work plan {ntx, nty, S, nseg, nsg, qs, grid, pool_rows} (streaming routes only):
+ * tile columns / rows of 8 x 32 pixels, tiles per segment of a column (the last one shorter when S does not divide nty), segments per column,
+ * segments in all, segments per workgroup, workgroups launched (a multiple of 8; the last ones may be idle), pool rows per frame.
+ * The route does not depend on ncu, on the plan bits 4..7 or on the measurement bits 12..14 of flags.
+ * SN_CONV_ROUTE(kernel, mt, a, d, mode, rl) names one template instance: */
+#define SN_CONV_K_GENERIC 1   /* conv_mfma_kernel<MT = mt, TH = a, TW = 4 a>: a = 8 (8 x 32 tiles) or 4 (4 x 16: stride 2 over more than 24 input channels,
+                               * or bit 15 of flags); d = mode = rl = 0 */
+#define SN_CONV_K_FAST    2   /* conv3_fast_kernel<MT = mt, CS = a, 8>: (mt, a) in {(1, 16), (2, 24), (3, 40), (3, 48), (4, 64), (5, 80)} */
+#define SN_CONV_K_STATS   3   /* conv3_fast_kernel<MT = mt, CS = a, 8, STATS>: sn_cab_stats on the tile kernel, (mt, a) in {(1, 16), (2, 24)} */
+#define SN_CONV_K_STREAM  4   /* conv3p_kernel<MT = mt, CS = a, 8, D = d, MODE = mode, RL = rl> (csrc/sn_conv3p.hip): (mt, a) in {(1, 16), (2, 24),
+                               * (3, 40), (3, 48), (4, 64)}, mode 0 bias, 1 PReLU + pool, 2 oscale + res, 3 sn_cab_stats; d: tiles of prefetch */
+#define SN_CONV_ROUTE(kernel, mt, a, d, mode, rl) (((kernel) << 24) | ((mt) << 20) | ((a) << 12) | ((d) << 8) | ((mode) << 4) | (rl))
+int sn_conv2d_route(const sn_conv_desc* d, int lines_len, int ncu, int* plan);
 
 /* SkipUpSample's tail (gshift_deblur1.py:341-350: x = up(x); x = x + y with up = bilinear x2 -> 1x1 conv).  The 1x1 is linear and the interpolation
  * weights sum to one, so conv(up(x)) = up(conv(x)): the caller runs the 1x1 at LOW resolution with sn_conv2d (in_mode 0) and this pass computes

@@ -17,7 +17,8 @@
 // the streaming form of the single-input 3x3 convs (sn_conv3p.hip); sn_conv2d routes to it unless the descriptor asks for the tile kernel
 int sn_conv3p_key(const sn_conv_desc* d, bool want_pool);   // want_pool: the caller is about to attach a pool buffer (sn_conv_pool_blocks)
 int sn_conv3p_pool_rows(const sn_conv_desc* d);
-int sn_conv3p_launch(const sn_conv_desc* d, int lines_len, void* stream);
+int sn_conv3p_route(const sn_conv_desc* d, int lines_len, int ncu, int* plan8);     // SN_EINVAL: the tile kernel runs d
+int sn_conv3p_launch(const sn_conv_desc* d, int lines_len, int route, const int* plan8, void* stream);
 
 namespace {
 
@@ -70,8 +71,8 @@ __device__ __forceinline__ uint4 ld_bilinear(const bf16_t* src, int t, int hs, i
 // load -> barrier -> MFMA -> store latency ONLY through co-resident workgroups, so every one states the occupancy it can reach
 // without spilling (probed per instantiation with -Rpass-analysis=kernel-resource-usage; accepting 2-6 spilled
 // registers for one more wave lost time everywhere it was tried).
-constexpr int sn_conv_waves(int mt, int th) {         // generic conv: 8x32 / 4x16 tiles; the 16x32 shape is left to the compiler
-    return th == 16 ? 1 : (mt == 1 ? 6 : mt == 2 ? 5 : mt == 3 ? 4 : mt == 4 ? 3 : 2);
+constexpr int sn_conv_waves(int mt) {                 // generic conv: 8x32 / 4x16 tiles
+    return mt == 1 ? 6 : mt == 2 ? 5 : mt == 3 ? 4 : mt == 4 ? 3 : 2;
 }
 // (feat_extract.0 -- 8 input channels -- and the concatenating 3x3 convs rconcat / conv_hr0 stay on the generic kernel: routing them
 // through conv3_fast_kernel measured neutral in round 2, 122.7 vs 122.0 ms and 673.7 vs 664.8 ms.)
@@ -84,7 +85,7 @@ constexpr int sn_conv3_waves(int mt, int cs) {
 }
 
 template <int MT, int TH, int TW>
-__global__ __launch_bounds__(256, sn_conv_waves(MT, TH)) void conv_mfma_kernel(const ConvK P) {
+__global__ __launch_bounds__(256, sn_conv_waves(MT)) void conv_mfma_kernel(const ConvK P) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NTW = (TH * TW) / 64;      // N-tiles (16 pixels) per wave
     constexpr int XB = TW / 16;
@@ -570,6 +571,11 @@ int launch_conv3_fast(const ConvK& K, int T, hipStream_t st) {
     return sn_check_launch();
 }
 
+// dynamic LDS of conv_mfma_kernel: the staged input region, the tap offsets, the channel-sum scratch (the route selector refuses more than 160 KB)
+size_t conv_generic_lds(int th, int tw, int stride, int k, int ps, int ks, int mt) {
+    return (size_t)((th - 1) * stride + k) * ((tw - 1) * stride + k) * ps + ((ks * 16 + 15) & ~15) + 4 * 16 * mt * sizeof(float);
+}
+
 template <int TH, int TW>
 int launch_conv(const ConvK& K, int mt, int T, hipStream_t st) {
     const int rh = (TH - 1) * K.stride + K.k, rw = (TW - 1) * K.stride + K.k;
@@ -578,8 +584,7 @@ int launch_conv(const ConvK& K, int mt, int T, hipStream_t st) {
     const dim3 grid = sn_xcd_grid(P.xg);
     auto magic = [](int d) { return (unsigned)(((1u << 24) + d - 1) / d); };
     P.m_nblk8 = magic(P.cv >> 3); P.m_rw = magic(rw); P.m_csb = magic(P.cs >> 3); P.m_cv = magic(P.cv); P.m_k = magic(P.k);
-    const size_t lds = (size_t)rh * rw * P.ps + ((P.ks * 16 + 15) & ~15) + 4 * 16 * mt * sizeof(float);
-    if (lds > 160 * 1024) return SN_EINVAL;
+    const size_t lds = conv_generic_lds(TH, TW, K.stride, K.k, P.ps, P.ks, mt);
 #define SN_CONV_CASE(M) case M: \
         if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)conv_mfma_kernel<M, TH, TW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return SN_ELAUNCH; \
         hipLaunchKernelGGL((conv_mfma_kernel<M, TH, TW>), grid, dim3(256), lds, st, P); break;
@@ -866,9 +871,31 @@ int sn_conv_pool_blocks(const sn_conv_desc* d) {
     return ((d->h_out + th - 1) / th) * ((d->w_out + tw - 1) / tw);
 }
 
-int sn_conv2d(const sn_conv_desc* d, void* stream) {
-    sn_clear_error();
-    if (!d || d->n_in < 1 || d->n_in > 3 || (d->cs_in & 7) || (d->cs_out & 7) || !d->wfrag) return SN_EINVAL;
+// LDS bytes per staged pixel of conv_mfma_kernel (all inputs interleaved); stride 2: an odd count of 16-byte slots (pixels 2 apart)
+static int conv_ps(const sn_conv_desc* d) {
+    const int blocks = d->n_in * d->cs_in >> 3;
+    return d->stride == 1 ? 16 * sn_lds_slots(blocks) : ((blocks & 1) ? blocks * 16 : blocks * 16 + 16);
+}
+
+// The kernel instance (SN_CONV_ROUTE) sn_conv2d (lines_len = 0) or sn_cab_stats (lines_len > 0) launches for d, or SN_EINVAL where it refuses d:
+// every check and every choice of the two entry points, host side.  They launch what this returns and sn_conv2d_route reports it, so the three
+// cannot disagree.  ncu / plan8: sn_conv3p_route.
+static int conv_route(const sn_conv_desc* d, int lines_len, int ncu, int* plan8) {
+    if (!d) return SN_EINVAL;
+    const bool stream_ok = !(d->flags & SN_CONV_TILE_KERNEL);
+    if (lines_len > 0) {                                     // sn_cab_stats: the streaming statistics mode, else the tile kernel's
+        if (!d->out || !d->pool || !d->wfrag || !d->in[0] || d->res || d->res2 || d->oscale || d->cs_in != d->cs_out ||
+            sn_remap_set(d->clip_n, d->clip_T, d->clip_lo)) return SN_EINVAL;
+        if (lines_len < (d->h_out > d->w_out ? d->h_out : d->w_out) || d->h_out < 2 || d->w_out < 2) return SN_EINVAL;
+        if (stream_ok) {
+            const int r = sn_conv3p_route(d, lines_len, ncu, plan8);
+            if (r >= 0) return r;
+        }
+        const int key = conv3_key(d);
+        if (key != 1016 && key != 2024) return SN_EINVAL;
+        return SN_CONV_ROUTE(SN_CONV_K_STATS, key / 1000, key % 1000, 0, 0, 0);
+    }
+    if (d->n_in < 1 || d->n_in > 3 || (d->cs_in & 7) || (d->cs_out & 7) || !d->wfrag) return SN_EINVAL;
     if (!d->out) return SN_EINVAL;
     if (d->k < 1 || d->k > 5 || (d->stride != 1 && d->stride != 2) || d->mt < 1 || d->mt > 6 || d->ks < 1) return SN_EINVAL;
     if (d->in_mode == 1 && ((d->h_in | d->w_in) & 1)) return SN_EINVAL;
@@ -878,8 +905,29 @@ int sn_conv2d(const sn_conv_desc* d, void* stream) {
     if ((d->res || d->res2) && d->out_mode != 0) return SN_EINVAL;
     if (d->out_mode == 1 && d->cs_out != 4 * d->mt) return SN_EINVAL;      // rows ordered [sub-pixel][cs_out channels]: a lane group = one sub-pixel
     const bool remap = sn_remap_set(d->clip_n, d->clip_T, d->clip_lo);      // only the generic kernel implements the frame remap
-    if (!sn_remap_ok(d->T, d->clip_n, d->clip_T, d->clip_lo) || (remap && (conv3_key(d) || (!(d->flags & SN_CONV_TILE_KERNEL) && sn_conv3p_key(d, false)))))
+    if (!sn_remap_ok(d->T, d->clip_n, d->clip_T, d->clip_lo) || (remap && (conv3_key(d) || (stream_ok && sn_conv3p_key(d, false)))))
         return SN_EINVAL;
+    if (stream_ok && sn_conv3p_key(d, false)) {               // SN_EINVAL: no device to plan for (or no instance fits): the tile kernel
+        const int r = sn_conv3p_route(d, 0, ncu, plan8);
+        if (r >= 0) return r;
+    }
+    const int key = conv3_key(d);                             // the specialised single-input 3x3 path; key = M-tiles, channels
+    if (key) return SN_CONV_ROUTE(SN_CONV_K_FAST, key / 1000, key % 1000, 0, 0, 0);
+    int th, tw; conv_tile(d, &th, &tw);                       // any other width: the generic kernel
+    if (conv_generic_lds(th, tw, d->stride, d->k, conv_ps(d), d->ks, d->mt) > 160 * 1024) return SN_EINVAL;
+    return SN_CONV_ROUTE(SN_CONV_K_GENERIC, d->mt, th, 0, 0, 0);
+}
+
+int sn_conv2d_route(const sn_conv_desc* d, int lines_len, int ncu, int* plan) {
+    sn_clear_error();
+    return conv_route(d, lines_len, ncu, plan);
+}
+
+int sn_conv2d(const sn_conv_desc* d, void* stream) {
+    sn_clear_error();
+    int plan8[8];
+    const int route = conv_route(d, 0, 0, plan8);
+    if (route < 0) return route;
     ConvK K;
     K.in0 = (const bf16_t*)d->in[0]; K.in1 = (const bf16_t*)d->in[1]; K.in2 = (const bf16_t*)d->in[2];
     K.n_in = d->n_in; K.cs = d->cs_in; K.cv = d->n_in * d->cs_in;
@@ -888,30 +936,26 @@ int sn_conv2d(const sn_conv_desc* d, void* stream) {
     K.wfrag = (const uint4*)d->wfrag; K.ks = d->ks; K.bias = d->bias; K.act = d->act; K.prelu = d->prelu;
     K.res = (const bf16_t*)d->res; K.out = (bf16_t*)d->out; K.cs_out = d->cs_out; K.out_mode = d->out_mode;
     K.c_out = d->c_out; K.nchw_dtype = d->nchw_dtype; K.sc_dtype = d->sc_dtype; K.sc = d->sc; K.pool = d->pool; K.oscale = d->oscale; K.oscale_stride = d->oscale_stride; K.res2 = (const bf16_t*)d->res2;
-    const int blocks = K.cv >> 3;
-    K.ps = d->stride == 1 ? 16 * sn_lds_slots(blocks) : ((blocks & 1) ? K.cv * 2 : K.cv * 2 + 16);     // stride 2: odd slot count (pixels 2 apart)
+    K.ps = conv_ps(d);
     K.rh = K.rw = 0; K.lines_len = 0;
     K.clip_n = d->clip_n; K.clip_T = d->clip_T; K.clip_lo = d->clip_lo;
-    if (!(d->flags & SN_CONV_TILE_KERNEL) && sn_conv3p_key(d, false)) {
-        const int rc = sn_conv3p_launch(d, 0, stream);
-        if (rc != SN_EINVAL) return rc;                      // (SN_EINVAL: no device to plan for -- fall through to the tile kernel's own checks)
+    hipStream_t st = (hipStream_t)stream;
+    const int mt = (route >> 20) & 15, a = (route >> 12) & 255;
+    switch (route >> 24) {
+        case SN_CONV_K_STREAM: return sn_conv3p_launch(d, 0, route, plan8, stream);
+        case SN_CONV_K_FAST:
+            switch (mt * 1000 + a) {
+                case 1016: return launch_conv3_fast<1, 16>(K, d->T, st);
+                case 2024: return launch_conv3_fast<2, 24>(K, d->T, st);
+                case 4064: return launch_conv3_fast<4, 64>(K, d->T, st);
+                case 3040: return launch_conv3_fast<3, 40>(K, d->T, st);
+                case 3048: return launch_conv3_fast<3, 48>(K, d->T, st);
+                case 5080: return launch_conv3_fast<5, 80>(K, d->T, st);
+                default: return SN_EINVAL;
+            }
+        case SN_CONV_K_GENERIC: return a == 8 ? launch_conv<8, 32>(K, mt, d->T, st) : launch_conv<4, 16>(K, mt, d->T, st);
+        default: return SN_EINVAL;
     }
-    int th, tw; conv_tile(d, &th, &tw);
-    {   // the specialised single-input 3x3 path; key = M-tiles, channels
-        hipStream_t st = (hipStream_t)stream;
-        switch (conv3_key(d)) {
-            case 1016: return launch_conv3_fast<1, 16>(K, d->T, st);
-            case 2024: return launch_conv3_fast<2, 24>(K, d->T, st);
-            case 4064: return launch_conv3_fast<4, 64>(K, d->T, st);
-            case 3040: return launch_conv3_fast<3, 40>(K, d->T, st);
-            case 3048: return launch_conv3_fast<3, 48>(K, d->T, st);
-            case 5080: return launch_conv3_fast<5, 80>(K, d->T, st);
-            default: break;                       // any other width: the generic kernel below
-        }
-    }
-    if (th == 16) return launch_conv<16, 32>(K, d->mt, d->T, (hipStream_t)stream);
-    if (th == 8) return launch_conv<8, 32>(K, d->mt, d->T, (hipStream_t)stream);
-    return launch_conv<4, 16>(K, d->mt, d->T, (hipStream_t)stream);
 }
 
 
@@ -951,15 +995,12 @@ int sn_cab_ca_lines(const float* partial, int nblk, int cpad, const void* lines,
 // pass 1 of the fused CAB (csrc/sn_cabf.hip): d = the CAB's FIRST conv as sn_conv2d would run it with `pool`, except that d->out is the line buffer
 int sn_cab_stats(const sn_conv_desc* d, int lines_len, void* stream) {
     sn_clear_error();
-    if (!d || !d->out || !d->pool || !d->wfrag || !d->in[0] || d->res || d->res2 || d->oscale || d->cs_in != d->cs_out ||
-        sn_remap_set(d->clip_n, d->clip_T, d->clip_lo)) return SN_EINVAL;
-    if (lines_len < (d->h_out > d->w_out ? d->h_out : d->w_out) || d->h_out < 2 || d->w_out < 2) return SN_EINVAL;
-    if (!(d->flags & SN_CONV_TILE_KERNEL) && sn_conv3p_key(d, false)) {      // the streaming kernel's statistics mode (pool rows: sn_conv_pool_blocks(d))
-        const int rc = sn_conv3p_launch(d, lines_len, stream);
-        if (rc != SN_EINVAL) return rc;
-    }
-    const int key = conv3_key(d);
-    if (key != 1016 && key != 2024) return SN_EINVAL;
+    if (lines_len < 1) return SN_EINVAL;
+    int plan8[8];
+    const int route = conv_route(d, lines_len, 0, plan8);
+    if (route < 0) return route;
+    if ((route >> 24) == SN_CONV_K_STREAM) return sn_conv3p_launch(d, lines_len, route, plan8, stream);   // pool rows: sn_conv_pool_blocks(d)
+    const int key = ((route >> 20) & 15) * 1000 + ((route >> 12) & 255);
     ConvK K;
     K.in0 = (const bf16_t*)d->in[0]; K.in1 = K.in2 = nullptr;
     K.n_in = 1; K.cs = d->cs_in; K.cv = d->cs_in;

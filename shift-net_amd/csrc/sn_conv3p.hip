@@ -896,30 +896,63 @@ int sn_conv3p_pool_rows(const sn_conv_desc* d) {
     return c3p_plan(d->T, d->h_out, d->w_out, 8, ncu, c3p_wgs(d, key, 1), c3p_segment(d->h_out, d->w_out, 8, c3p_wgs_default(key))).pool_rows;
 }
 
-// lines_len > 0: the statistics pass of the fused CAB (sn_cab_stats): d is a MODE-1 descriptor whose `out` is the border-line buffer
-int sn_conv3p_launch(const sn_conv_desc* d, int lines_len, void* stream) {
-    const int key = sn_conv3p_key(d, false), ncu = key ? c3p_ncu() : 0;
-    if (!key || !ncu) return SN_EINVAL;
+// The streaming instance sn_conv2d (lines_len = 0) / sn_cab_stats (lines_len > 0: MODE 3) runs d on -- SN_CONV_ROUTE(SN_CONV_K_STREAM, MT, CS, D, MODE,
+// RL) -- and its work plan {ntx, nty, S, nseg, nsg, qs, grid, pool_rows} into plan8 (may be NULL), for `ncu` CUs (0: the current device).  SN_EINVAL:
+// the caller stays on the tile kernel (no instance, no device to plan for, or more LDS than a workgroup may have).  Host only; no launch.
+int sn_conv3p_route(const sn_conv_desc* d, int lines_len, int ncu, int* plan8) {
+    const int key = sn_conv3p_key(d, false);
+    if (!key) return SN_EINVAL;
+    if (ncu == 0) ncu = c3p_ncu();
+    if (ncu < 1) return SN_EINVAL;
+    const int mode = lines_len > 0 ? 3 : c3p_mode(d);
+    if (mode < 0 || (lines_len > 0 && c3p_mode(d) != 1)) return SN_EINVAL;
+    // <M-tiles, channels, tile rows, prefetch depth, MODE, MODE 2 with the residual in LDS>; bits 10..11: deeper prefetch at 16 channels (measurements)
+    const int mt = key / 1000, cs = key % 1000, depth = (d->flags >> 10) & 3;
+    bool rl = c3p_rl(d, key, mode);
+    int D = 2;
+    if (key == 1016 && (depth == 1 || depth == 2)) { D = depth + 2; rl = false; }
+    else if (key == 2024 && rl) D = 1;                    // the residual tile costs LDS: one buffer fewer
+    else if (key == 4064) D = 1;                          // 72 KB of weights: two buffers of 43 KB
+    const int npb = cs / 8, ndma = (10 * 34 * npb + 63) / 64, ks = (9 * cs + 31) / 32, rdma = rl ? (8 * 32 * npb) / 64 : 0;
+    const size_t lds = (size_t)(D + 1) * (ndma + rdma) * 1024 + (mt * ks > 16 ? mt * ks * 1024 : 0);      // launch_conv3p_mode
+    if (lds > 160 * 1024) return SN_EINVAL;
+    if (plan8) {
+        // (the workgroups per CU follow c3p_rl even where a prefetch-depth code launches the register form: the plans of those measurement
+        // instances are what they always were)
+        const C3PPlan pl = c3p_plan(d->T, d->h_out, d->w_out, 8, ncu, c3p_wgs(d, key, mode), c3p_segment(d->h_out, d->w_out, 8, c3p_wgs_default(key)));
+        const int v[8] = {pl.ntx, pl.nty, pl.S, pl.nseg, pl.nsg, pl.qs, pl.grid, pl.pool_rows};
+        for (int i = 0; i < 8; ++i) plan8[i] = v[i];
+    }
+    return SN_CONV_ROUTE(SN_CONV_K_STREAM, mt, cs, D, mode, rl ? 1 : 0);
+}
+
+template <int MT, int CS, int D>
+int launch_conv3p_rf(const C3P& K, const C3PPlan& pl, int mode, hipStream_t st) {      // every MODE, residual operand through registers
+    return launch_conv3p<MT, CS, 8, D, D, false>(K, pl, mode, st);
+}
+
+// launches route (from sn_conv3p_route) with its plan8; lines_len > 0: the statistics pass of the fused CAB (sn_cab_stats), d a MODE-1 descriptor
+// whose `out` is the border-line buffer
+int sn_conv3p_launch(const sn_conv_desc* d, int lines_len, int route, const int* plan8, void* stream) {
+    if ((route >> 24) != SN_CONV_K_STREAM || !plan8) return SN_EINVAL;
     C3P K;
     K.in = (const bf16_t*)d->in[0]; K.res = (const bf16_t*)d->res; K.out = (bf16_t*)d->out;
     K.wfrag = (const uint4*)d->wfrag; K.bias = d->bias; K.oscale = d->oscale; K.oscale_stride = d->oscale_stride;
     K.pool = d->pool; K.pool_rows = 0; K.act = d->act; K.prelu = d->prelu;
     K.T = d->T; K.h = d->h_out; K.w = d->w_out; K.lines_len = lines_len; K.dbg = (d->flags >> 12) & 7;
-    const int mode = lines_len > 0 ? 3 : c3p_mode(d);
-    if (lines_len > 0 && c3p_mode(d) != 1) return SN_EINVAL;
-    const C3PPlan pl = c3p_plan(d->T, d->h_out, d->w_out, 8, ncu, c3p_wgs(d, key, mode), c3p_segment(d->h_out, d->w_out, 8, c3p_wgs_default(key)));
+    const C3PPlan pl = {plan8[0], plan8[1], plan8[2], plan8[3], plan8[4], plan8[5], plan8[6], plan8[7]};
     hipStream_t st = (hipStream_t)stream;
-    const bool rl = c3p_rl(d, key, mode);
-    // <M-tiles, channels, tile rows, prefetch depth, prefetch depth of MODE 2, MODE 2 with the residual in LDS>
-    switch (key) {
+    const int mt = (route >> 20) & 15, cs = (route >> 12) & 255, D = (route >> 8) & 15, mode = (route >> 4) & 15;
+    const bool rl = route & 1;
+    switch (mt * 1000 + cs) {
         case 1016:
-            if (((d->flags >> 10) & 3) == 1) return launch_conv3p<1, 16, 8, 3, 3, false>(K, pl, mode, st);      // bits 10..11: deeper prefetch (measurements)
-            if (((d->flags >> 10) & 3) == 2) return launch_conv3p<1, 16, 8, 4, 4, false>(K, pl, mode, st);
-            return rl ? launch_conv3p<1, 16, 8, 2, 2, true>(K, pl, mode, st) : launch_conv3p<1, 16, 8, 2, 2, false>(K, pl, mode, st);
-        case 2024: return rl ? launch_conv3p<2, 24, 8, 2, 1, true>(K, pl, mode, st) : launch_conv3p<2, 24, 8, 2, 2, false>(K, pl, mode, st);
-        case 3040: return launch_conv3p<3, 40, 8, 2, 2, false>(K, pl, mode, st);
-        case 3048: return launch_conv3p<3, 48, 8, 2, 2, false>(K, pl, mode, st);
-        case 4064: return launch_conv3p<4, 64, 8, 1, 1, false>(K, pl, mode, st);      // 72 KB of weights: two buffers of 43 KB
+            if (rl) return launch_conv3p_mode<1, 16, 8, 2, 2, true>(K, pl, st);
+            return D == 3 ? launch_conv3p_rf<1, 16, 3>(K, pl, mode, st) : (D == 4 ? launch_conv3p_rf<1, 16, 4>(K, pl, mode, st)
+                                                                                  : launch_conv3p_rf<1, 16, 2>(K, pl, mode, st));
+        case 2024: return rl ? launch_conv3p_mode<2, 24, 8, 1, 2, true>(K, pl, st) : launch_conv3p_rf<2, 24, 2>(K, pl, mode, st);
+        case 3040: return launch_conv3p_rf<3, 40, 2>(K, pl, mode, st);
+        case 3048: return launch_conv3p_rf<3, 48, 2>(K, pl, mode, st);
+        case 4064: return launch_conv3p_rf<4, 64, 1>(K, pl, mode, st);
         default: return SN_EINVAL;
     }
 }

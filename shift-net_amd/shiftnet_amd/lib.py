@@ -15,10 +15,10 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libshiftnet_hip.so")
 
 SN_F32, SN_F16, SN_BF16 = 0, 1, 2
 
-ABI_VERSION = 19     # == SN_ABI_VERSION of include/shiftnet_hip.h; a stale .so from before a struct / signature change fails the check in load()
+ABI_VERSION = 20    # == SN_ABI_VERSION of include/shiftnet_hip.h; a stale .so from before a struct / signature change fails the check in load()
 
 SYMBOLS = [          # include/shiftnet_hip.h, production ABI
-    "sn_abi_version", "sn_selftest_mfma", "sn_ingest", "sn_conv2d", "sn_conv_pool_blocks", "sn_upsample2_add", "sn_ca_mlp",
+    "sn_abi_version", "sn_selftest_mfma", "sn_ingest", "sn_conv2d", "sn_conv_pool_blocks", "sn_conv2d_route","sn_upsample2_add", "sn_ca_mlp",
     "sn_cab_ca", "sn_cab_ca_scratch_floats", "sn_cab_fused_supported", "sn_cab_stats", "sn_cab_ca_lines", "sn_cab_fused", "sn_planar_pitch", "sn_nhwc_to_planar", "sn_dw5m_blocks",
     "sn_dw5m_gemm_gate", "sn_gsts_gather", "sn_temporal_roll", "sn_gsts_shiftconv", "sn_gsts_shiftconv_mfma", "sn_gsts_cab2_phase2", "sn_cab1_phase2",
     "sn_ingest_u8", "sn_egress_blocks", "sn_egress_u8", "sn_ssim_blocks", "sn_ssim_u8",
@@ -66,6 +66,28 @@ class ConvDesc(C.Structure):
 
 
 SN_CONV_TILE_KERNEL = 1
+
+# sn_conv2d_route: SN_CONV_ROUTE(kernel, mt, a, d, mode, rl) of include/shiftnet_hip.h
+SN_CONV_K_GENERIC, SN_CONV_K_FAST, SN_CONV_K_STATS, SN_CONV_K_STREAM = 1, 2, 3, 4
+CONV_KERNEL_NAMES = {SN_CONV_K_GENERIC: "conv_mfma", SN_CONV_K_FAST: "conv3_fast", SN_CONV_K_STATS: "conv3_fast_stats", SN_CONV_K_STREAM: "conv3p"}
+CONV_PLAN_FIELDS = ("ntx", "nty", "S", "nseg", "nsg", "qs", "grid", "pool_rows")      # the plan argument of sn_conv2d_route
+
+
+def conv_route(kernel: int, mt: int, a: int, d: int = 0, mode: int = 0, rl: int = 0) -> int:
+    return (kernel << 24) | (mt << 20) | (a << 12) | (d << 8) | (mode << 4) | rl
+
+
+def conv_route_name(r: int) -> str:
+    """conv_mfma<MT,TH,TW> / conv3_fast<MT,CS> / conv3_fast_stats<MT,CS> / conv3p<MT,CS,D,MODE,RL>, or EINVAL(code)"""
+    if r < 0:
+        return f"EINVAL({r})"
+    k, mt, a, d, mode, rl = r >> 24, (r >> 20) & 15, (r >> 12) & 255, (r >> 8) & 15, (r >> 4) & 15, r & 15
+    name = CONV_KERNEL_NAMES.get(k, str(k))
+    if k == SN_CONV_K_GENERIC:
+        return f"{name}<{mt},{a},{4 * a}>"
+    if k == SN_CONV_K_STREAM:
+        return f"{name}<{mt},{a},D{d},MODE{mode},RL{rl}>"
+    return f"{name}<{mt},{a}>"
 
 
 class Conv32Desc(C.Structure):
@@ -118,6 +140,7 @@ def load() -> C.CDLL:
     lib.sn_ingest.argtypes = [vp, ci, vp, vp, ci, ci, ci, ci, vp]
     lib.sn_conv2d.argtypes = [C.POINTER(ConvDesc), vp]
     lib.sn_conv_pool_blocks.argtypes = [C.POINTER(ConvDesc)]
+    lib.sn_conv2d_route.argtypes = [C.POINTER(ConvDesc), ci, ci, C.POINTER(ci * 8)]
     lib.sn_upsample2_add.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
     lib.sn_ca_mlp.argtypes = [vp, ci, ci, ci, ci, cf, vp, vp, vp, ci, vp, vp]
     lib.sn_planar_pitch.argtypes = [ci]

@@ -105,8 +105,9 @@ def test_batch_quadrants_flag_only_on_denoise_clis(name):
             ap.parse_args(["--batch_quadrants"])
 
 
-def test_descriptors_carry_the_clip_fields_zeroed():
-    assert L.ABI_VERSION == 19
+def test_abi20_descriptors_carry_the_clip_fields_zeroed():
+    """The clip fields arrived with ABI 19; ABI 20 (sn_conv2d_route) kept both descriptors' layouts."""
+    assert L.ABI_VERSION == 20
     s = L.UnitSrc()
     assert s.clip == 0
     s = L.UnitSrc(None, 12, 8, 8, 64, 1, 0, None, 0, 0, 6)           # positional: clip comes last
