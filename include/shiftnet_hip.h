@@ -416,6 +416,52 @@ int sn_egress_u8(const void* out, int out_dtype, const uint8_t* gt, uint8_t* img
 int sn_ssim_blocks(void);
 int sn_ssim_u8(const void* out, int out_dtype, const uint8_t* gt, float* scratch, float* partial, int T, int H, int W, void* stream);
 
+/* ---- Y'CbCr edges of the video restorer (csrc/sn_yuv.hip) ----------------------------------------------------------------
+ * Added without an ABI bump: SN_ABI_VERSION stays 20, because these are new symbols and a new struct; no existing struct,
+ * signature or operand encoding changes, so a caller built against the earlier header keeps working.
+ *
+ * A frame payload is Y4M's: the Y plane [H][W], then the U and the V plane, each [H][W] (4:4:4) or [ceil(H/2)][ceil(W/2)] (4:2:0);
+ * one byte per sample at 8 bit, one 16-bit little-endian word with the value in the low 10 bits at 10 bit.  T payloads lie end to end.
+ *
+ * Constants (each a float64 expression rounded ONCE to float32).  Kr, Kb = 0.299, 0.114 (BT.601) or 0.2126, 0.0722 (BT.709),
+ * Kg = (1 - Kr) - Kb; s = 2^(bits - 8); limited range: yo = 16 s, ys = 219 s, cs = 224 s, legal codes Y 16 s..235 s, C 16 s..240 s;
+ * full range: yo = 0, ys = cs = 2^bits - 1, legal codes 0..2^bits - 1; co = 128 s in both.
+ *   ky = 1 / ys, crv = 2 (1 - Kr) / cs, cbu = 2 (1 - Kb) / cs, cgu = -2 Kb (1 - Kb) / Kg / cs, cgv = -2 Kr (1 - Kr) / Kg / cs,
+ *   cu = 1 / (2 (1 - Kb)), cv = 1 / (2 (1 - Kr)).
+ *
+ * sn_ingest_yuv, per pixel, every product and sum rounded separately to float32 (no FMA):
+ *   yd = float(Y - yo); ud = float(Un - D co) / D, vd = float(Vn - D co) / D with Un / D the upsampled chroma code (below; exact);
+ *   yy = ky * yd;  R = yy + crv * vd;  G = (yy + cgu * ud) + cgv * vd;  B = yy + cbu * ud;  each clamped to [0,1] and then rounded
+ *   to dst_dtype (nearest even).  dst:[T][3][Hp][Wp]; pixel (y, x) with y >= H or x >= W is pixel (min(y, H-1), min(x, W-1)).
+ *   Chroma upsampling, bilinear on the integer codes, (j, i) = (y >> 1, x >> 1), neighbours clamped to the chroma plane:
+ *     4:2:0 centre-sited (D = 16): jn = j + 1 for odd y, j - 1 for even y, in likewise from x:
+ *                                  Un = 3 (3 C[j][i] + C[jn][i]) + (3 C[j][in] + C[jn][in])                 (weights 9/3/3/1)
+ *     4:2:0 left-sited   (D = 8):  v(c) = 3 C[j][c] + C[jn][c];  even x: Un = 2 v(i);  odd x: Un = v(i) + v(i + 1)
+ *     4:4:4              (D = 1):  Un = C[y][x].
+ *
+ * sn_egress_yuv, out:[T][3][Hp][Wp] of out_dtype, the H x W top-left crop is written:
+ *   R, G, B clamped to [0,1];  Y' = (Kr R + Kg G) + Kb B;  Cb = (B - Y') * cu;  Cr = (R - Y') * cv   (float32, no FMA);
+ *   4:2:0 chroma of block (j, i), pixel coordinates clamped to the H x W frame:
+ *     centre-sited: 0.25 * ((c[2j][2i] + c[2j][2i+1]) + (c[2j+1][2i] + c[2j+1][2i+1]))
+ *     left-sited:   h(y) = (c[y][2i-1] + 2 c[y][2i]) + c[y][2i+1];  0.125 * (h(2j) + h(2j+1))
+ *   code = clamp(rint(yo + ys * Y'), legal Y codes), clamp(rint(co + cs * C), legal C codes), rint = nearest even.
+ *   Only the T payloads are written.  10-bit payloads must be 2-byte aligned. */
+#define SN_YUV_444 0
+#define SN_YUV_420_CENTER 1     /* Y4M C420jpeg */
+#define SN_YUV_420_LEFT 2       /* Y4M C420mpeg2, C420 (and C420paldv, whose vertical siting is not modelled) */
+#define SN_YUV_BT601 0
+#define SN_YUV_BT709 1
+#define SN_YUV_LIMITED 0
+#define SN_YUV_FULL 1
+typedef struct sn_yuv_fmt {
+    int bits;      /* 8 | 10 */
+    int chroma;    /* SN_YUV_444 | SN_YUV_420_CENTER | SN_YUV_420_LEFT */
+    int matrix;    /* SN_YUV_BT601 | SN_YUV_BT709 */
+    int range;     /* SN_YUV_LIMITED | SN_YUV_FULL */
+} sn_yuv_fmt;
+int sn_ingest_yuv(const uint8_t* src, const sn_yuv_fmt* fmt, void* dst, int dst_dtype, int T, int H, int W, int Hp, int Wp, void* stream);
+int sn_egress_yuv(const void* out, int out_dtype, const sn_yuv_fmt* fmt, uint8_t* dst, int T, int H, int W, int Hp, int Wp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,384 @@
+// Y'CbCr <-> RGB edges of the video restorer on the device (gfx950): planar YUV frames as a Y4M stream carries them in,
+// planar YUV frames out.  4:2:0 crosses PCIe at 1.5 B per pixel (8 bit) and no float frame touches the host.
+//
+//   sn_ingest_yuv : T payloads [Y plane][U plane][V plane] -> [T][3][Hp][Wp] RGB of the module dtype in [0,1]; pixels outside H x W
+//                   replicate the edge pixel, so one launch gives the network a legal size for any input size;
+//   sn_egress_yuv : [T][3][Hp][Wp] RGB (float32 or module dtype) -> T payloads of H x W (the crop of the padding).
+//
+// The arithmetic (order of operations, constants) is stated in include/shiftnet_hip.h and restated in float32 by tests/yuv_ref.py,
+// which these kernels equal bit for bit.  Every float product and sum is rounded separately (contraction is off for this file: no
+// FMA); the chroma upsampling is integer arithmetic and therefore exact.
+//
+// Both are bandwidth kernels.  A thread owns four horizontally adjacent 2x2 luma blocks (8 x 2 pixels), so that every chroma sample is
+// produced once and the 8 pixels of a row are one 8 / 16 B load and one 16 / 2 x 16 B store where the address is aligned; a thread
+// whose span is not aligned, or touches the frame edge or the padding, takes the element-wise path with the same arithmetic.
+#include "sn_common.h"
+#include "../../include/shiftnet_hip.h"
+#pragma clang fp contract(off)
+
+namespace {
+
+struct YuvK {
+    // ingest: R = ky*(Y - yoff) + crv*(V - coff), G = (ky*(Y - yoff) + cgu*(U - coff)) + cgv*(V - coff), B = ky*(Y - yoff) + cbu*(U - coff)
+    float ky, crv, cgu, cgv, cbu;
+    // egress: Y' = (kr*R + kg*G) + kb*B, Cb = (B - Y')*cu, Cr = (R - Y')*cv; code = rint(off + scale * value)
+    float kr, kg, kb, cu, cv, ys, yo, cs, co;
+    int yoff, coff, ylo, yhi, clo, chi;
+};
+
+__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
+__device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
+// separately rounded float32 product / sum / difference.  Written with the operators under the pragma above: the __fmul_rn / __fadd_rn
+// of the HIP headers are compiled with the default contraction mode, and their results fuse into v_fma_f32 after inlining.
+__device__ __forceinline__ float mulr(float a, float b) { return a * b; }
+__device__ __forceinline__ float addr(float a, float b) { return a + b; }
+__device__ __forceinline__ float subr(float a, float b) { return a - b; }
+__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
+
+template <int ESZ> __device__ __forceinline__ int ld1(const uint8_t* p, size_t i) {
+    return ESZ == 1 ? (int)p[i] : (int)((const uint16_t*)p)[i];
+}
+template <int ESZ> __device__ __forceinline__ void st1(uint8_t* p, size_t i, int v) {
+    if (ESZ == 1) p[i] = (uint8_t)v; else ((uint16_t*)p)[i] = (uint16_t)v;
+}
+// N consecutive samples starting at element i, all inside the plane: one N * ESZ byte load if the address allows it
+template <int ESZ, int N> __device__ __forceinline__ void ldn(const uint8_t* p, size_t i, int* v) {
+    const uint8_t* a = p + i * ESZ;
+    if (((uintptr_t)a & (N * ESZ - 1)) == 0) {
+        uint32_t w[N * ESZ / 4];
+        if (N * ESZ == 4) w[0] = *(const uint32_t*)a;
+        else if (N * ESZ == 8) { const uint2 q = *(const uint2*)a; w[0] = q.x; w[1] = q.y; }
+        else { const uint4 q = *(const uint4*)a; w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w; }
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] = ESZ == 1 ? (int)((w[k >> 2] >> (8 * (k & 3))) & 0xffu) : (int)((w[k >> 1] >> (16 * (k & 1))) & 0xffffu);
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] = ld1<ESZ>(p, i + k);
+    }
+}
+template <int ESZ, int N> __device__ __forceinline__ void stn(uint8_t* p, size_t i, const int* v) {
+    uint8_t* a = p + i * ESZ;
+    if (((uintptr_t)a & (N * ESZ - 1)) == 0) {
+        uint32_t w[N * ESZ / 4];
+#pragma unroll
+        for (int k = 0; k < N * ESZ / 4; ++k) w[k] = 0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            if (ESZ == 1) w[k >> 2] |= (uint32_t)v[k] << (8 * (k & 3)); else w[k >> 1] |= (uint32_t)v[k] << (16 * (k & 1));
+        }
+        if (N * ESZ == 4) *(uint32_t*)a = w[0];
+        else if (N * ESZ == 8) *(uint2*)a = make_uint2(w[0], w[1]);
+        else *(uint4*)a = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; ++k) st1<ESZ>(p, i + k, v[k]);
+    }
+}
+
+// ---- RGB tensor elements ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float ld_any(const void* p, int dt, size_t i) {
+    return dt == SN_F32 ? ((const float*)p)[i] : (dt == SN_F16 ? __half2float(((const __half*)p)[i]) : bf_to_f(((const bf16_t*)p)[i]));
+}
+__device__ __forceinline__ void st_any(void* p, int dt, size_t i, float v) {       // as st_any of sn_io.hip
+    if (dt == SN_F32) ((float*)p)[i] = v;
+    else if (dt == SN_F16) ((__half*)p)[i] = __float2half(v);
+    else ((bf16_t*)p)[i] = f_to_bf(v);
+}
+__device__ __forceinline__ float h_lo(uint32_t u) { return __half2float(__ushort_as_half((unsigned short)(u & 0xffffu))); }
+__device__ __forceinline__ float h_hi(uint32_t u) { return __half2float(__ushort_as_half((unsigned short)(u >> 16))); }
+// 8 consecutive elements starting at i (all inside the tensor); vec: the caller knows that element i is 16 B (32 B for f32) aligned
+__device__ __forceinline__ void ld8_any(const void* p, int dt, size_t i, bool vec, float* v) {
+    if (vec) {
+        if (dt == SN_F32) {
+            const float4 a = *(const float4*)((const float*)p + i), b = *(const float4*)((const float*)p + i + 4);
+            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+        } else {
+            const uint4 q = *(const uint4*)((const uint16_t*)p + i);
+            if (dt == SN_BF16) unpack8(q, v);
+            else { v[0] = h_lo(q.x); v[1] = h_hi(q.x); v[2] = h_lo(q.y); v[3] = h_hi(q.y); v[4] = h_lo(q.z); v[5] = h_hi(q.z); v[6] = h_lo(q.w); v[7] = h_hi(q.w); }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = ld_any(p, dt, i + k);
+    }
+}
+// 8 consecutive elements starting at i, of which the first n (1..8) exist
+__device__ __forceinline__ void st8_any(void* p, int dt, size_t i, bool vec, int n, const float* v) {
+    if (vec) {
+        if (dt == SN_F32) {
+            *(float4*)((float*)p + i) = make_float4(v[0], v[1], v[2], v[3]);
+            *(float4*)((float*)p + i + 4) = make_float4(v[4], v[5], v[6], v[7]);
+        } else if (dt == SN_BF16) {
+            *(uint4*)((uint16_t*)p + i) = pack8(v);
+        } else {
+            *(uint4*)((uint16_t*)p + i) = make_uint4(pack_h2(v[0], v[1]), pack_h2(v[2], v[3]), pack_h2(v[4], v[5]), pack_h2(v[6], v[7]));
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) if (k < n) st_any(p, dt, i + k, v[k]);
+    }
+}
+
+// ---- ingest -------------------------------------------------------------------------------------------------------------------
+// CH: SN_YUV_444 / SN_YUV_420_CENTER / SN_YUV_420_LEFT.  Chroma reaches the matrix as an integer numerator over DEN (1 / 16 / 8):
+//   centre: (3 * (3 * C[j][i] + C[jn][i]) + (3 * C[j][in] + C[jn][in])) / 16 with (j, i) = (y >> 1, x >> 1) and jn / in the neighbour
+//           on the side of the luma sample (odd: +1, even: -1), clamped to the plane;
+//   left:   v(c) = 3 * C[j][c] + C[jn][c]; even x: 2 * v(i) / 8, odd x: (v(i) + v(min(i + 1, cw - 1))) / 8.
+template <int CH> struct Den { static constexpr int value = CH == SN_YUV_444 ? 1 : (CH == SN_YUV_420_CENTER ? 16 : 8); };
+
+template <int CH> __device__ __forceinline__ void yuv_to_rgb(const YuvK& K, int y, int un, int vn, float* r, float* g, float* b) {
+    constexpr float inv = 1.0f / Den<CH>::value;
+    const float yd = (float)(y - K.yoff);
+    const float ud = mulr((float)(un - Den<CH>::value * K.coff), inv);        // exact: a power of two times an integer < 2^15
+    const float vd = mulr((float)(vn - Den<CH>::value * K.coff), inv);
+    const float yy = mulr(K.ky, yd);
+    *r = clamp01(addr(yy, mulr(K.crv, vd)));
+    *g = clamp01(addr(addr(yy, mulr(K.cgu, ud)), mulr(K.cgv, vd)));
+    *b = clamp01(addr(yy, mulr(K.cbu, ud)));
+}
+
+template <int ESZ, int CH> __device__ __forceinline__ int chroma_num(const uint8_t* p, int cw, int ch, int ye, int xe) {
+    const int j = ye >> 1, i = xe >> 1;
+    const int jn = imin(imax(j + ((ye & 1) ? 1 : -1), 0), ch - 1);
+    const size_t rj = (size_t)j * cw, rn = (size_t)jn * cw;
+    if (CH == SN_YUV_420_CENTER) {
+        const int in = imin(imax(i + ((xe & 1) ? 1 : -1), 0), cw - 1);
+        return 3 * (3 * ld1<ESZ>(p, rj + i) + ld1<ESZ>(p, rn + i)) + (3 * ld1<ESZ>(p, rj + in) + ld1<ESZ>(p, rn + in));
+    }
+    const int v0 = 3 * ld1<ESZ>(p, rj + i) + ld1<ESZ>(p, rn + i);
+    if (!(xe & 1)) return 2 * v0;
+    const int i1 = imin(i + 1, cw - 1);
+    return v0 + (3 * ld1<ESZ>(p, rj + i1) + ld1<ESZ>(p, rn + i1));
+}
+
+template <int ESZ, int CH>
+__global__ __launch_bounds__(256) void ingest_yuv_kernel(const uint8_t* __restrict__ src, void* __restrict__ dst, int dt, const YuvK K,
+                                                       int H, int W, int Hp, int Wp, size_t frame_bytes, int dst_vec) {
+    const int t = blockIdx.z;
+    const int x0 = (blockIdx.x * 32 + threadIdx.x) * 8, y0 = (blockIdx.y * 8 + threadIdx.y) * 2;
+    if (x0 >= Wp || y0 >= Hp) return;
+    const int cw = CH == SN_YUV_444 ? W : (W + 1) >> 1, ch = CH == SN_YUV_444 ? H : (H + 1) >> 1;
+    const uint8_t* yp = src + (size_t)t * frame_bytes;
+    const uint8_t* up = yp + (size_t)H * W * ESZ;
+    const uint8_t* vp = up + (size_t)cw * ch * ESZ;
+    float rgb[3][2][8];
+    if (x0 + 8 <= W && y0 + 2 <= H) {                      // interior: whole blocks, wide loads
+        int Y[2][8];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) ldn<ESZ, 8>(yp, (size_t)(y0 + r) * W + x0, Y[r]);
+        if (CH == SN_YUV_444) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                int U[8], V[8];
+                ldn<ESZ, 8>(up, (size_t)(y0 + r) * W + x0, U);
+                ldn<ESZ, 8>(vp, (size_t)(y0 + r) * W + x0, V);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) yuv_to_rgb<CH>(K, Y[r][k], U[k], V[k], &rgb[0][r][k], &rgb[1][r][k], &rgb[2][r][k]);
+            }
+        } else {
+            const int j = y0 >> 1, c0 = x0 >> 1;
+            const int jr[3] = {imax(j - 1, 0), j, imin(j + 1, ch - 1)};
+            int num[2][2][8];                               // [plane][row][pixel]
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl) {
+                const uint8_t* cp = pl ? vp : up;
+                int win[3][6];                              // chroma columns c0 - 1 .. c0 + 4 (clamped) of rows j - 1, j, j + 1 (clamped)
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const size_t row = (size_t)jr[q] * cw;
+                    ldn<ESZ, 4>(cp, row + c0, &win[q][1]);
+                    win[q][0] = CH == SN_YUV_420_CENTER ? ld1<ESZ>(cp, row + imax(c0 - 1, 0)) : 0;
+                    win[q][5] = ld1<ESZ>(cp, row + imin(c0 + 4, cw - 1));
+                }
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    int vr[6];
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) vr[k] = 3 * win[1][k] + win[r ? 2 : 0][k];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        const int i = k >> 1;
+                        if (CH == SN_YUV_420_CENTER) num[pl][r][k] = 3 * vr[i + 1] + vr[(k & 1) ? i + 2 : i];
+                        else num[pl][r][k] = (k & 1) ? vr[i + 1] + vr[i + 2] : 2 * vr[i + 1];
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int k = 0; k < 8; ++k) yuv_to_rgb<CH>(K, Y[r][k], num[0][r][k], num[1][r][k], &rgb[0][r][k], &rgb[1][r][k], &rgb[2][r][k]);
+        }
+    } else {                                               // frame edge and padding: pixel (y, x) is pixel (min(y, H-1), min(x, W-1))
+        for (int r = 0; r < 2; ++r) {
+            const int ye = imin(y0 + r, H - 1);
+            for (int k = 0; k < 8; ++k) {
+                const int xe = imin(x0 + k, W - 1);
+                const int y = ld1<ESZ>(yp, (size_t)ye * W + xe);
+                int un, vn;
+                if (CH == SN_YUV_444) { un = ld1<ESZ>(up, (size_t)ye * W + xe); vn = ld1<ESZ>(vp, (size_t)ye * W + xe); }
+                else { un = chroma_num<ESZ, CH>(up, cw, ch, ye, xe); vn = chroma_num<ESZ, CH>(vp, cw, ch, ye, xe); }
+                yuv_to_rgb<CH>(K, y, un, vn, &rgb[0][r][k], &rgb[1][r][k], &rgb[2][r][k]);
+            }
+        }
+    }
+    const int n = imin(8, Wp - x0);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+            if (y0 + r < Hp) st8_any(dst, dt, (((size_t)t * 3 + c) * Hp + (y0 + r)) * Wp + x0, dst_vec != 0, n, rgb[c][r]);
+}
+
+// ---- egress -------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int quant(float off, float scale, float v, int lo, int hi) {
+    return imin(imax(__float2int_rn(addr(off, mulr(scale, v))), lo), hi);
+}
+
+template <int ESZ, int CH>
+__global__ __launch_bounds__(256) void egress_yuv_kernel(const void* __restrict__ out, int dt, uint8_t* __restrict__ dstp, const YuvK K,
+                                                       int H, int W, int Hp, int Wp, size_t frame_bytes, int src_vec) {
+    const int t = blockIdx.z;
+    const int x0 = (blockIdx.x * 32 + threadIdx.x) * 8, y0 = (blockIdx.y * 8 + threadIdx.y) * 2;
+    if (x0 >= W || y0 >= H) return;
+    const int cw = CH == SN_YUV_444 ? W : (W + 1) >> 1, ch = CH == SN_YUV_444 ? H : (H + 1) >> 1;
+    uint8_t* yp = dstp + (size_t)t * frame_bytes;
+    uint8_t* up = yp + (size_t)H * W * ESZ;
+    uint8_t* vp = up + (size_t)cw * ch * ESZ;
+    const bool inner = x0 + 8 <= W;
+    // Y', Cb, Cr of pixels x0 - 1 .. x0 + 7 (index 0 .. 8) of rows y0, y0 + 1, coordinates clamped to the H x W frame
+    float yv[2][9], cb[2][9], cr[2][9];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int ye = imin(y0 + r, H - 1);
+        float c[3][9];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const size_t row = (((size_t)t * 3 + q) * Hp + ye) * Wp;
+            if (inner) ld8_any(out, dt, row + x0, src_vec != 0, &c[q][1]);
+            else for (int k = 0; k < 8; ++k) c[q][1 + k] = ld_any(out, dt, row + imin(x0 + k, W - 1));
+            c[q][0] = CH == SN_YUV_420_LEFT ? ld_any(out, dt, row + imax(x0 - 1, 0)) : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const float R = clamp01(c[0][k]), G = clamp01(c[1][k]), B = clamp01(c[2][k]);
+            const float y = addr(addr(mulr(K.kr, R), mulr(K.kg, G)), mulr(K.kb, B));
+            yv[r][k] = y;
+            cb[r][k] = mulr(subr(B, y), K.cu);
+            cr[r][k] = mulr(subr(R, y), K.cv);
+        }
+    }
+    const int n = imin(8, W - x0);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        if (y0 + r >= H) break;
+        int q[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) q[k] = quant(K.yo, K.ys, yv[r][1 + k], K.ylo, K.yhi);
+        const size_t o = (size_t)(y0 + r) * W + x0;
+        if (inner) stn<ESZ, 8>(yp, o, q); else for (int k = 0; k < n; ++k) st1<ESZ>(yp, o + k, q[k]);
+        if (CH == SN_YUV_444) {
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) q[k] = quant(K.co, K.cs, pl ? cr[r][1 + k] : cb[r][1 + k], K.clo, K.chi);
+                if (inner) stn<ESZ, 8>(pl ? vp : up, o, q); else for (int k = 0; k < n; ++k) st1<ESZ>(pl ? vp : up, o + k, q[k]);
+            }
+        }
+    }
+    if (CH != SN_YUV_444) {
+        const int c0 = x0 >> 1, nc = imin(4, cw - c0);
+        const size_t o = (size_t)(y0 >> 1) * cw + c0;
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) {
+            int q[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float* a = pl ? cr[0] : cb[0];
+                const float* b = pl ? cr[1] : cb[1];
+                float m;
+                if (CH == SN_YUV_420_CENTER)       // mean of the 2x2 block: ((a0 + a1) + (b0 + b1)) / 4
+                    m = mulr(0.25f, addr(addr(a[1 + 2 * i], a[2 + 2 * i]), addr(b[1 + 2 * i], b[2 + 2 * i])));
+                else                               // (1,2,1)/4 along x centred on the even pixel, (1,1)/2 along y: (((l + 2c) + r)_a + ((l + 2c) + r)_b) / 8
+                    m = mulr(0.125f, addr(addr(addr(a[2 * i], mulr(2.f, a[1 + 2 * i])), a[2 + 2 * i]),
+                                                    addr(addr(b[2 * i], mulr(2.f, b[1 + 2 * i])), b[2 + 2 * i])));
+                q[i] = quant(K.co, K.cs, m, K.clo, K.chi);
+            }
+            if (nc == 4) stn<ESZ, 4>(pl ? vp : up, o, q); else for (int i = 0; i < nc; ++i) st1<ESZ>(pl ? vp : up, o + i, q[i]);
+        }
+    }
+}
+
+// constants: float64 expressions rounded once to float32 (tests/yuv_ref.py: constants() evaluates the same expressions)
+bool make_consts(const sn_yuv_fmt* f, YuvK* K) {
+    if (!f || (f->bits != 8 && f->bits != 10) || f->chroma < 0 || f->chroma > 2 || f->matrix < 0 || f->matrix > 1 || f->range < 0 || f->range > 1) return false;
+    const double kr = f->matrix == SN_YUV_BT709 ? 0.2126 : 0.299, kb = f->matrix == SN_YUV_BT709 ? 0.0722 : 0.114;
+    const double kg = 1.0 - kr - kb;
+    const int s = 1 << (f->bits - 8), top = (1 << f->bits) - 1;
+    const bool full = f->range == SN_YUV_FULL;
+    const double yo = full ? 0.0 : 16.0 * s, ys = full ? (double)top : 219.0 * s, cs = full ? (double)top : 224.0 * s, co = 128.0 * s;
+    K->ky = (float)(1.0 / ys);
+    K->crv = (float)(2.0 * (1.0 - kr) / cs);
+    K->cgu = (float)(-2.0 * kb * (1.0 - kb) / kg / cs);
+    K->cgv = (float)(-2.0 * kr * (1.0 - kr) / kg / cs);
+    K->cbu = (float)(2.0 * (1.0 - kb) / cs);
+    K->kr = (float)kr; K->kg = (float)kg; K->kb = (float)kb;
+    K->cu = (float)(1.0 / (2.0 * (1.0 - kb)));
+    K->cv = (float)(1.0 / (2.0 * (1.0 - kr)));
+    K->ys = (float)ys; K->yo = (float)yo; K->cs = (float)cs; K->co = (float)co;
+    K->yoff = (int)yo; K->coff = (int)co;
+    K->ylo = full ? 0 : 16 * s; K->yhi = full ? top : 235 * s; K->clo = full ? 0 : 16 * s; K->chi = full ? top : 240 * s;
+    return true;
+}
+
+size_t frame_bytes_of(const sn_yuv_fmt* f, int H, int W) {
+    const size_t esz = f->bits == 8 ? 1 : 2;
+    const size_t c = f->chroma == SN_YUV_444 ? (size_t)H * W : (size_t)((H + 1) / 2) * ((W + 1) / 2);
+    return ((size_t)H * W + 2 * c) * esz;
+}
+
+}  // namespace
+
+extern "C" {
+
+#define SN_YUV_DISPATCH(KERNEL, ...)                                                                                       \
+    do {                                                                                                                   \
+        if (fmt->bits == 8) {                                                                                              \
+            if (fmt->chroma == SN_YUV_444) hipLaunchKernelGGL((KERNEL<1, SN_YUV_444>), grid, block, 0, s, __VA_ARGS__);      \
+            else if (fmt->chroma == SN_YUV_420_CENTER) hipLaunchKernelGGL((KERNEL<1, SN_YUV_420_CENTER>), grid, block, 0, s, __VA_ARGS__); \
+            else hipLaunchKernelGGL((KERNEL<1, SN_YUV_420_LEFT>), grid, block, 0, s, __VA_ARGS__);                           \
+        } else {                                                                                                           \
+            if (fmt->chroma == SN_YUV_444) hipLaunchKernelGGL((KERNEL<2, SN_YUV_444>), grid, block, 0, s, __VA_ARGS__);      \
+            else if (fmt->chroma == SN_YUV_420_CENTER) hipLaunchKernelGGL((KERNEL<2, SN_YUV_420_CENTER>), grid, block, 0, s, __VA_ARGS__); \
+            else hipLaunchKernelGGL((KERNEL<2, SN_YUV_420_LEFT>), grid, block, 0, s, __VA_ARGS__);                           \
+        }                                                                                                                  \
+    } while (0)
+
+int sn_ingest_yuv(const uint8_t* src, const sn_yuv_fmt* fmt, void* dst, int dst_dtype, int T, int H, int W, int Hp, int Wp, void* stream) {
+    sn_clear_error();
+    YuvK K;
+    if (!src || !dst || !make_consts(fmt, &K) || dst_dtype < 0 || dst_dtype > 2 || T < 1 || T > 65535 || H < 1 || W < 1 || Hp < H || Wp < W) return SN_EINVAL;
+    if (fmt->bits == 10 && ((uintptr_t)src & 1)) return SN_EINVAL;
+    const size_t fb = frame_bytes_of(fmt, H, W);
+    const int dst_vec = Wp % 8 == 0 && ((uintptr_t)dst & 15) == 0;       // every 8-pixel span of a row is 16 B (f32: 32 B) aligned
+    const dim3 block(32, 8), grid(((Wp + 7) / 8 + 31) / 32, ((Hp + 1) / 2 + 7) / 8, T);
+    if (grid.y > 65535) return SN_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    SN_YUV_DISPATCH(ingest_yuv_kernel, src, dst, dst_dtype, K, H, W, Hp, Wp, fb, dst_vec);
+    return sn_check_launch();
+}
+
+int sn_egress_yuv(const void* out, int out_dtype, const sn_yuv_fmt* fmt, uint8_t* dst, int T, int H, int W, int Hp, int Wp, void* stream) {
+    sn_clear_error();
+    YuvK K;
+    if (!out || !dst || !make_consts(fmt, &K) || out_dtype < 0 || out_dtype > 2 || T < 1 || T > 65535 || H < 1 || W < 1 || Hp < H || Wp < W) return SN_EINVAL;
+    if (fmt->bits == 10 && ((uintptr_t)dst & 1)) return SN_EINVAL;
+    const size_t fb = frame_bytes_of(fmt, H, W);
+    const int src_vec = Wp % 8 == 0 && ((uintptr_t)out & 15) == 0;
+    const dim3 block(32, 8), grid(((W + 7) / 8 + 31) / 32, ((H + 1) / 2 + 7) / 8, T);
+    if (grid.y > 65535) return SN_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    SN_YUV_DISPATCH(egress_yuv_kernel, out, out_dtype, dst, K, H, W, Hp, Wp, fb, src_vec);
+    return sn_check_launch();
+}
+
+}  // extern "C"

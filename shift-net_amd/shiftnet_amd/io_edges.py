@@ -2,6 +2,8 @@
 
 ``ingest_u8``  == ``numpy2tensor(frames).to(device).to(dtype)`` of inference/test_deblur.py:191-200,128,134, bit for bit,
                with 3 instead of 12 bytes per pixel crossing PCIe;
+``ingest_yuv`` / ``egress_yuv``: planar Y'CbCr payloads as a Y4M stream carries them (csrc/sn_yuv.hip) <-> RGB tensors, for the video
+               restorer (shiftnet_amd/restore.py); 1.5 bytes per pixel cross PCIe for 8-bit 4:2:0;
 ``egress_u8``  == the per-frame ``clamp(0,1) * 255`` -> skimage PSNR(data_range=255) against the uint8 ground truth
                (:139-143) and the rounded uint8 frame cv2.imwrite would store (:152).
 """
@@ -69,3 +71,39 @@ def ssim_u8(out: torch.Tensor, gt_u8: torch.Tensor) -> List[float]:
         L.check(lib.sn_ssim_u8(out.data_ptr(), _CODE[out.dtype], gt_u8.data_ptr(), scratch.data_ptr(), part.data_ptr(), T, H, W,
                                torch.cuda.current_stream(out.device).cuda_stream), "sn_ssim_u8")
     return (part.double().cpu().sum(1) / (3.0 * H * W)).tolist()
+
+
+def yuv_fmt(bits: int, chroma: int, matrix: int, range_: int) -> "L.YuvFmt":
+    """sn_yuv_fmt from the integer codes of lib.py (SN_YUV_*)."""
+    return L.YuvFmt(bits, chroma, matrix, range_)
+
+
+def ingest_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, Hp: int, Wp: int, dtype: torch.dtype,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """payload_u8: [T, frame_bytes] uint8 on a HIP device, T planar Y'CbCr frames of H x W -> [1,T,3,Hp,Wp] RGB of ``dtype`` in [0,1];
+    pixels outside H x W replicate the edge pixel.  ``out``: a [1,T,3,Hp,Wp] tensor to fill instead of a new one."""
+    fb = fmt.frame_bytes(H, W)
+    assert payload_u8.dtype == torch.uint8 and payload_u8.is_cuda and payload_u8.dim() == 2 and payload_u8.shape[1] == fb and payload_u8.is_contiguous()
+    assert Hp >= H and Wp >= W and dtype in _CODE
+    T = payload_u8.shape[0]
+    x = out if out is not None else torch.empty((1, T, 3, Hp, Wp), dtype=dtype, device=payload_u8.device)
+    assert tuple(x.shape) == (1, T, 3, Hp, Wp) and x.dtype == dtype and x.is_contiguous() and x.device == payload_u8.device
+    with torch.cuda.device(payload_u8.device):
+        L.check(L.load().sn_ingest_yuv(payload_u8.data_ptr(), fmt, x.data_ptr(), _CODE[dtype], T, H, W, Hp, Wp,
+                                       torch.cuda.current_stream(payload_u8.device).cuda_stream), "sn_ingest_yuv")
+    return x
+
+
+def egress_yuv(out: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, dst: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out: [T,3,Hp,Wp] network output (float32 or module dtype) on the device -> [T, frame_bytes] uint8 payloads of the H x W crop.
+    ``dst``: a [T, frame_bytes] uint8 tensor to fill instead of a new one."""
+    assert out.is_cuda and out.dim() == 4 and out.shape[1] == 3 and out.dtype in _CODE and out.is_contiguous()
+    T, _, Hp, Wp = out.shape
+    assert Hp >= H and Wp >= W
+    fb = fmt.frame_bytes(H, W)
+    y = dst if dst is not None else torch.empty((T, fb), dtype=torch.uint8, device=out.device)
+    assert tuple(y.shape) == (T, fb) and y.dtype == torch.uint8 and y.is_contiguous() and y.device == out.device
+    with torch.cuda.device(out.device):
+        L.check(L.load().sn_egress_yuv(out.data_ptr(), _CODE[out.dtype], fmt, y.data_ptr(), T, H, W, Hp, Wp,
+                                       torch.cuda.current_stream(out.device).cuda_stream), "sn_egress_yuv")
+    return y
