@@ -317,6 +317,17 @@ int sn_p1r_strip_begin(const int* plan7, int s, int w);
 int sn_gsts_cab2_phase2(const sn_unit_src* s, const void* g2, const float* ca, const void* wfrag, const float* bias, void* y, void* stream);
 int sn_cab1_phase2(const sn_unit_src* s, const void* g2, const float* ca, const void* wfrag, const float* bias, void* y, void* stream);
 
+/* sn_gsts_cab2_phase2 of a unit's CAB2 and sn_cab1_phase1 of its CAB1 in ONE launch (csrc/sn_phase1r.hip, the FK4 instance): the stager waves of
+ * phase 1 form y = shortcut + W3' . (ca * g2_in) + bias' for the rows they stage -- the operations of phase 2 in its order, y is bit-identical --
+ * store it once (the CAB1's phase 2 reads it as its shortcut) and feed the LayerNorm from the values they just rounded; g2 / pool / se as
+ * sn_cab1_phase1, also bit-identical.  s is the CAB2's source (mode 1 / 2), g2_in / ca / wfrag / bias / y the operands of sn_gsts_cab2_phase2, wt
+ * the CAB1's phase-1 weights; opt: NULL or the team size only.  g2_in, y, g2 and s->x are four distinct tensors.
+ * sn_cab2_phase2_cab1_phase1_supported: 1 where the fused launch exists -- C = 64, the whole tensor (nt = 0), wrap 0 / 1, one clip -- else 0, and the
+ * entry point returns SN_EINVAL (never a wrong result): the caller keeps the two launches. */
+int sn_cab2_phase2_cab1_phase1_supported(const sn_unit_src* s);
+int sn_cab2_phase2_cab1_phase1(const sn_unit_src* s, const void* g2_in, const float* ca, const void* wfrag, const float* bias, void* y,
+                               const sn_phase1_weights* wt, void* g2, float* pool, const sn_se_fold* se, const sn_phase1_opts* opt, void* stream);
+
 
 /* ---- fp32-storage path (csrc/sn_f32.hip) -----------------------------------------------------------------------
  * The arithmetic type upstream runs the "+" denoiser in (inference/test_denoise.py:83-85: the .half() is commented out)

@@ -79,6 +79,9 @@ struct P1RArgs {
     int g1_sums;                         // 1: only the channel sums of g1 (the A waves' SimpleGate output) are produced: pool / se describe g1, no g2
     char* g1_store;                      // denoisers, or NULL: the sums pass also writes every g1 row it computes ([frame][strip][image row][P1R g1 row], fp16, unscaled),
                                          // and the second pass (ICA 3) reads them back instead of running the stagers' LayerNorm and the A waves again
+    // FK4 instance (sn_cab2_phase2_cab1_phase1): the input of this CAB1 is formed here, y = shortcut + W3' . bf16(ca * g2 of the CAB2) + bias'.
+    // x / halo / mode / wrap / clip above then describe the CAB2's source (the shortcut is its rolled x); the LayerNorm runs over y's C channels.
+    const bf16_t* k4_g2; const float* k4_ca; const uint4* k4_w; const float* k4_bias; bf16_t* k4_y;
 };
 
 __device__ __forceinline__ f32x4_t mfma16h(const uint4 a, const uint4 b, const f32x4_t c) {
@@ -189,8 +192,12 @@ template <int C, bool HW, int ICA> constexpr int p1r_threads() { return (ICA == 
 // bytes of a stored g1 row of one strip: [wave][group][column mod 4][16 lanes] x 16 B -- the ring row without its pad columns
 template <int C> constexpr int p1r_g1_row_bytes() { return (C / 16) * 8 * 256; }
 
-template <int C, bool HW, int ICA>
+// FK4: the stagers run the previous CAB2's phase 2 (K4, scale_gemm_res_kernel of sn_gsts.hip) on the rows they stage, store its y and feed the
+// LayerNorm from the values they just rounded: K4's launch and the read of y disappear.  C = 64, CAB1 (no hw half), ICA 0 only -- C = 80 has two
+// stager waves with two lanes per pixel and 149 KB of LDS, the denoisers run phase 1 twice; both keep the two launches.
+template <int C, bool HW, int ICA, int FK4 = 0>
 __global__ __launch_bounds__((p1r_threads<C, HW, ICA>())) void cab_phase1r_kernel(const P1RArgs A_) {
+    static_assert(!FK4 || (C == 64 && !HW && ICA == 0 && P1RShape<C, HW>::NSW == 4), "the K4 fusion exists for C = 64, CAB1, four stager waves");
     using SH = P1RShape<C, HW>;
     // The arguments are read from the kernarg segment where they are needed, through a pointer the compiler cannot see through (p1r_args): as SSA
     // values of the by-value parameter everything the end of a walk needs (plan, pool, squeeze-excite operands) stayed live across the step
@@ -332,6 +339,173 @@ __global__ __launch_bounds__((p1r_threads<C, HW, ICA>())) void cab_phase1r_kerne
                 __builtin_amdgcn_sched_barrier(0);
                 if (j >= 10 && j <= seg + 9) store_row(j);
                 gslot = gslot == SH::GRING - 1 ? 0 : gslot + 1;
+                __syncthreads();
+            };
+#pragma unroll 1
+            for (int j = 0; j < NS; j += 2) {
+                step(j, XB);
+                step(j + 1, XA);
+            }
+            Ap = p1r_fresh(Ap);
+            finish(u);
+        }
+    } else if (FK4 && role == 2) {
+        // ============================== S, K4 fused: y = shortcut + W3' . bf16(ca * g2) + bias' of the CAB2, then LayerNorm(y) ==============================
+        // A stager wave is ONE N-tile of K4's GEMM: lane (g, p) holds pixel 16 q + p of the region; as the B operand the k-chunks g (k-step 0) and
+        // g + 4 (k-step 1) of the CAB2's g2, as the D operand channels 16 g .. 16 g + 15 of y (K4's c0) = the 16-byte pieces 2 g, 2 g + 1.  Same
+        // operations in the same order as scale_gemm_res_kernel: bit-identical y.  The LayerNorm below must also reproduce the plain stager's
+        // sums bit for bit, and those are per lane `sub` over pieces sub, sub + 4: one v_permlane32_swap per word turns (2 g, 2 g + 1) into
+        // (sub, sub + 4) with sub = 2 (g & 1) + (g >> 1), and the sums over a pixel's four lanes go over the wave halves first (sub ^ 1), then over
+        // neighbouring rows (sub ^ 2), the order of the two quad_perm steps of the plain stager (fp32 addition commutes, it does not associate).
+        __builtin_amdgcn_s_setprio(P1R_PRIO_S);
+        constexpr int NSTH = 64 * SH::NSW, MT = C / 16, KS = C / 32;
+        const int stid = q * 64 + lane, spx = 16 * q + p, sub = ((g & 1) << 1) | (g >> 1);
+        // x ring: 8 consecutive lanes of a ds_write_b128 are 8 consecutive pixels with the SAME piece: 4 distinct 16-byte bank groups, a two-way
+        // conflict on two of the row's stores (the piece index is tied to the lane group by the MFMA layout); 64 of a step's ~3700 cycles
+        const int xpix = (spx & 3) * XPL + (spx >> 2) * PSX;
+        bf16x8_t Wk[MT][KS];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int s = 0; s < KS; ++s) Wk[m][s] = as_frag(A.k4_w[(m * KS + s) * 64 + lane]);
+        float4 bs[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) bs[m] = A.k4_bias ? *(const float4*)(A.k4_bias + g * 4 * MT + m * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        constexpr int NPO = C / 8, NIT = (SH::VWMAX * NPO + NSTH - 1) / NSTH;
+#pragma unroll 1
+        for (int u = u0; u < u1; ++u) {
+            Ap = p1r_fresh(Ap);
+            P1RItem I;
+            if (!item(u, I)) continue;
+            const int t = I.t, Y0 = I.Y0, Y1 = I.Y1, seg = Y1 - Y0;
+            const int NS = (seg + SH::WARM + 1) & ~1;
+            const SnSlabs<bf16_t> sl = sn_unit_slabs<bf16_t>(A.x, A.halo, A.T, hw, C, A.mode, A.wrap, A.clip, t);
+            const int c0 = g * 4 * MT;                                        // K4's c0: this lane's channels of the shortcut and of y
+            const bf16_t* const sbase = c0 < CH ? sl.p0 + c0 : sl.p1 + c0 - CH;
+            const int sstr = c0 < CH ? sl.s0 : sl.s1;
+            const bf16_t* const gbase = A.k4_g2 + (size_t)t * hw * C + g * 8;
+            float cs[KS][8];
+#pragma unroll
+            for (int s = 0; s < KS; ++s)
+#pragma unroll
+                for (int k = 0; k < 8; ++k) cs[s][k] = A.k4_ca[(size_t)t * C + s * 32 + g * 8 + k];
+            const int sgx = I.xo + spx, sgxc = (sgx >= 0 && sgx < w) ? sgx : 0;
+            // y leaves as the pieces sub, sub + 4 the lane holds after the swap: the four lanes of a pixel write its 128 bytes.  Own columns and
+            // own rows only: halo columns and warm-up rows are recomputed by their owners, every element of y is written exactly once per launch.
+            const bool owncol = spx >= I.olo && spx < I.ohi && sgx >= 0 && sgx < w;
+            bf16_t* const ybase = A.k4_y + ((size_t)t * hw + sgxc) * C + sub * 8;
+            uint4 XA[4], XB[4];
+            auto issue_row = [&](int y, uint4* X) {
+                const int yc = (y >= 0 && y < h) ? y : 0;
+                const int ii = yc * w + sgxc;
+                X[0] = *(const uint4*)(gbase + (size_t)ii * C); X[1] = *(const uint4*)(gbase + (size_t)ii * C + 32);
+                X[2] = *(const uint4*)(sbase + (size_t)ii * sstr); X[3] = *(const uint4*)(sbase + (size_t)ii * sstr + 8);
+            };
+            auto stage_row = [&](int slot, const uint4* X, int y, uint4* yw) {
+                const bool inimg = y >= 0 && y < h && sgx >= 0 && sgx < w;
+                // ---- K4 on this wave's 16 pixels ----
+                bf16x8_t B[KS];
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    float v[8];
+                    unpack8(X[s], v);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) v[k] *= cs[s][k];
+                    B[s] = as_frag(pack8(v));
+                }
+                f32x4_t acc[MT];
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[m] = (f32x4_t){bs[m].x, bs[m].y, bs[m].z, bs[m].w};
+#pragma unroll
+                for (int s = 0; s < KS; ++s)
+#pragma unroll
+                    for (int m = 0; m < MT; ++m) acc[m] = mfma16(Wk[m][s], B[s], acc[m]);
+                const uint32_t sc[2 * MT] = {X[2].x, X[2].y, X[2].z, X[2].w, X[3].x, X[3].y, X[3].z, X[3].w};
+                uint32_t wd[2][4];                                            // [piece][word]: pieces 2 g, 2 g + 1 of y, rounded to bf16
+#pragma unroll
+                for (int m = 0; m < MT; ++m) {
+                    wd[m >> 1][2 * (m & 1)] = pack_bf2(bf_lo(sc[2 * m]) + acc[m][0], bf_hi(sc[2 * m]) + acc[m][1]);
+                    wd[m >> 1][2 * (m & 1) + 1] = pack_bf2(bf_lo(sc[2 * m + 1]) + acc[m][2], bf_hi(sc[2 * m + 1]) + acc[m][3]);
+                }
+                // rows 2, 3 of the first operand <-> rows 0, 1 of the second: (2 g, 2 g + 1) -> (sub, sub + 4)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(wd[0][k]), "+v"(wd[1][k]));
+                yw[0] = make_uint4(wd[0][0], wd[0][1], wd[0][2], wd[0][3]); yw[1] = make_uint4(wd[1][0], wd[1][1], wd[1][2], wd[1][3]);
+                // ---- two-pass LayerNorm over the rounded y, as the plain stager with four lanes per pixel ----
+                auto sum4 = [](float x) -> float {
+                    float a = x, b = x;
+                    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+                    const float s2 = a + b;                                   // lane sub + lane sub ^ 1
+                    float c = s2, d = s2;
+                    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(c), "+v"(d));
+                    return c + d;
+                };
+                float s1[2] = {0.f, 0.f};
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) s1[k & 1] = dot2bf(wd[i][k], 0x3f803f80u, s1[k & 1]);
+                const float mean = sum4(s1[0] + s1[1]) * (1.0f / K);
+                const f32x2_t mean2 = {mean, mean};
+                f32x2_t d[2][4];
+                f32x2_t sq2[2] = {{0.f, 0.f}, {0.f, 0.f}};
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const f32x2_t v = {bf_lo(wd[i][k]), bf_hi(wd[i][k])};
+                        d[i][k] = v - mean2;
+                        sq2[k & 1] = __builtin_elementwise_fma(d[i][k], d[i][k], sq2[k & 1]);
+                    }
+                const float sq = sum4((sq2[0][0] + sq2[0][1]) + (sq2[1][0] + sq2[1][1]));
+                const float rstd = inimg ? __builtin_amdgcn_rsqf(sq * (1.0f / K) + 1e-6f) : 0.f;
+                const f32x2_t rstd2 = {rstd, rstd};
+                char* xs = lds_x + slot * XSLOT + xpix + sub * 16;
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    uint4 o;
+                    f32x2_t e0 = d[i][0] * rstd2, e1 = d[i][1] * rstd2, e2 = d[i][2] * rstd2, e3 = d[i][3] * rstd2;
+                    o.x = pack_bf2(e0[0], e0[1]); o.y = pack_bf2(e1[0], e1[1]); o.z = pack_bf2(e2[0], e2[1]); o.w = pack_bf2(e3[0], e3[1]);
+                    *(uint4*)(xs + i * 64) = o;
+                }
+                if (sub == 3) *(uint32_t*)(lds_x + slot * XSLOT + xpix + K * 2) = inimg ? 0x3f803f80u : 0u;
+            };
+            int so_l[NIT], so_g[NIT];
+#pragma unroll
+            for (int k = 0; k < NIT; ++k) {
+                const int e = stid + NSTH * k, px = e / NPO, pc = e - px * NPO, rc = I.olo + px;
+                so_l[k] = ((rc & 3) * 16 + (rc >> 2)) * PSO + pc * 16;
+                so_g[k] = rc < I.ohi ? (I.xo + rc) * C + pc * 8 : -1;
+                if (so_g[k] < 0) so_l[k] = 0;
+            }
+            auto store_row = [&](int j) {
+                const int yo = Y0 - 10 + j;
+                const char* os = lds_o + ((j - 1) & 1) * OSLOT;
+                bf16_t* const g2row = A.g2 + ((size_t)t * h + yo) * w * C;
+#pragma unroll
+                for (int k = 0; k < NIT; ++k) {
+                    const uint4 v = *(const uint4*)(os + so_l[k]);
+                    if (so_g[k] >= 0) *(uint4*)(g2row + so_g[k]) = v;
+                }
+            };
+            uint4 yw[2] = {make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
+            issue_row(Y0 - 3, XA);
+            issue_row(Y0 - 2, XB);
+            stage_row(0, XA, Y0 - 3, yw);                                     // (a warm-up row: its y belongs to the walk above)
+            issue_row(Y0 - 1, XA);
+            __syncthreads();
+            const int ylast = Y1 + 2;
+            // step j as in the plain stager; the y row it formed (Y0 - 2 + j) is stored behind the refill loads
+            auto step = [&](const int j, uint4* X) {
+                const int yr = Y0 - 2 + j;
+                if (j <= seg + 4) stage_row((j + 1) & 1, X, yr, yw);
+                issue_row(Y0 + j < ylast ? Y0 + j : ylast, X);
+                __builtin_amdgcn_sched_barrier(0);
+                if (owncol && yr >= Y0 && yr < Y1) {
+                    bf16_t* const yp = ybase + (size_t)yr * w * C;
+                    *(uint4*)yp = yw[0]; *(uint4*)(yp + 32) = yw[1];
+                }
+                if (j >= 10 && j <= seg + 9) store_row(j);
                 __syncthreads();
             };
 #pragma unroll 1
@@ -839,14 +1013,14 @@ int p1r_plan(int nfr, int h, int w, int ncu, int team, P1RPlan& P) {
     return SN_OK;
 }
 
-template <int C, bool HW, int ICA>
+template <int C, bool HW, int ICA, int FK4 = 0>
 int p1r_launch1(P1RArgs& A, hipStream_t st) {
     using SH = P1RShape<C, HW>;
-    if (hipFuncSetAttribute((const void*)cab_phase1r_kernel<C, HW, ICA>, hipFuncAttributeMaxDynamicSharedMemorySize, SH::LDS) != hipSuccess) return SN_ELAUNCH;
+    if (hipFuncSetAttribute((const void*)cab_phase1r_kernel<C, HW, ICA, FK4>, hipFuncAttributeMaxDynamicSharedMemorySize, SH::LDS) != hipSuccess) return SN_ELAUNCH;
     sn_clear_error();
     int per = (A.P.F * A.P.nteam + 7) / 8;
     per = (per + A.P.F - 1) / A.P.F * A.P.F;                                 // whole teams per XCD
-    hipLaunchKernelGGL((cab_phase1r_kernel<C, HW, ICA>), dim3((unsigned)(8 * per)), dim3(p1r_threads<C, HW, ICA>()), SH::LDS, st, A);
+    hipLaunchKernelGGL((cab_phase1r_kernel<C, HW, ICA, FK4>), dim3((unsigned)(8 * per)), dim3(p1r_threads<C, HW, ICA>()), SH::LDS, st, A);
     return sn_check_launch();
 }
 template <int C, bool HW>
@@ -870,6 +1044,7 @@ int cab_phase1(const sn_unit_src* s, const void* hw, const sn_phase1_weights* wt
     A.g2 = (bf16_t*)g2; A.pool = pool;
     A.g1_scale = opt ? opt->g1_scale : nullptr; A.g1_sums = sums ? 1 : 0;
     A.g1_store = opt ? (char*)opt->g1_store : nullptr;
+    A.k4_g2 = nullptr; A.k4_ca = nullptr; A.k4_w = nullptr; A.k4_bias = nullptr; A.k4_y = nullptr;
     if (A.g1_store && !sums && !A.g1_scale) return SN_EINVAL;               // a g1 store belongs to the two passes of the denoisers
     A.se.ca = nullptr; A.se.bad = nullptr;
     if (se) {
@@ -915,6 +1090,39 @@ int sn_gsts_cab2_phase1(const sn_unit_src* s, const void* hw, const sn_phase1_we
 int sn_cab1_phase1(const sn_unit_src* s, const sn_phase1_weights* wt, void* g2, float* pool, const sn_se_fold* se, const sn_phase1_opts* opt, void* stream) {
     if (!s || s->mode != 0) return SN_EINVAL;
     return cab_phase1(s, nullptr, wt, g2, pool, se, opt, stream);
+}
+
+// Which sources the fused launch takes.  C = 64 only (C = 80: two stager waves, two lanes per pixel, 149 KB of LDS -- it keeps the two launches, and
+// so do the denoisers, whose phase 1 runs twice); whole tensors only: a frame range, a temporally split window (wrap 2: the shortcut's halo half has
+// another pixel stride) and a batch of clips keep the two launches too.
+int sn_cab2_phase2_cab1_phase1_supported(const sn_unit_src* s) {
+    return s && s->C == 64 && (s->mode == 1 || s->mode == 2) && (s->wrap == 0 || s->wrap == 1) && s->nt <= 0 && (s->clip == 0 || s->clip == s->T);
+}
+
+int sn_cab2_phase2_cab1_phase1(const sn_unit_src* s, const void* g2_in, const float* ca, const void* wfrag, const float* bias, void* y,
+                               const sn_phase1_weights* wt, void* g2, float* pool, const sn_se_fold* se, const sn_phase1_opts* opt, void* stream) {
+    sn_clear_error();
+    if (!sn_cab2_phase2_cab1_phase1_supported(s) || !s->x || s->T < 1 || s->h < 1 || s->w < 1 || !g2_in || !ca || !wfrag || !y || !g2 || y == s->x ||
+        y == g2_in || g2 == g2_in || g2 == y || g2 == s->x || !wt || !wt->wfrag1 || !wt->w3 || !wt->wgrp || !wt->wfrag2) return SN_EINVAL;
+    if (opt && (opt->g1_scale || opt->g1_sums || opt->g1_store)) return SN_EINVAL;      // (only the team size: the denoisers are not fused)
+    const int ncu = p1r_ncu();
+    if (ncu < 1) return SN_ELAUNCH;
+    P1RArgs A;
+    A.x = (const bf16_t*)s->x; A.halo = nullptr; A.hwb = nullptr; A.T = s->T; A.h = s->h; A.w = s->w; A.mode = s->mode; A.wrap = s->wrap; A.clip = s->T;
+    A.wfrag1 = (const uint4*)wt->wfrag1; A.w3 = (const uint4*)wt->w3; A.wgrp = (const uint4*)wt->wgrp; A.wfrag2 = (const uint4*)wt->wfrag2;
+    A.g2 = (bf16_t*)g2; A.pool = pool;
+    A.g1_scale = nullptr; A.g1_sums = 0; A.g1_store = nullptr;
+    A.k4_g2 = (const bf16_t*)g2_in; A.k4_ca = ca; A.k4_w = (const uint4*)wfrag; A.k4_bias = bias; A.k4_y = (bf16_t*)y;
+    A.se.ca = nullptr; A.se.bad = nullptr;
+    if (se) {
+        if (!pool || !se->wa || !se->wb || !se->ticket || !se->ca || se->c != s->C || se->cr < 1 || se->cr > 128) return SN_EINVAL;
+        A.se.wa = se->wa; A.se.wb = se->wb; A.se.ca = se->ca; A.se.ticket = se->ticket; A.se.bad = se->bad; A.se.inv_hw = 1.0f / ((float)s->h * (float)s->w);
+        A.se.c = se->c; A.se.cr = se->cr;
+    }
+    A.t0 = 0; A.nfr = s->T;
+    const int rc = p1r_plan(s->T, s->h, s->w, ncu, opt ? opt->team : 0, A.P);
+    if (rc != SN_OK) return rc;
+    return p1r_launch1<64, false, 0, 1>(A, (hipStream_t)stream);
 }
 
 }  // extern "C"

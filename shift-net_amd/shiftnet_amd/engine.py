@@ -213,6 +213,7 @@ class Engine:
         self.prof: Optional[list] = None      # bench.py attaches a list to collect (fn, label, meta, ev0, ev1)
         self._meta: Tuple = ()
         self._unit: Optional[Tuple] = None    # (T, h, w, c, mode) while the launches of a CAB2 / CAB1 of a GSTS unit are being issued
+        self._k4_meta: Tuple = ()             # profiler meta of the CAB2 whose phase 2 runs inside the CAB1's phase 1 (gsts_unit)
         self.split = None                     # temporal_split.TemporalSplit: this engine holds a frame range of a longer window
         self._side = None                     # side stream of the halo exchanges (created on first use)
         self._tickets = None                  # sn_se_fold frame counters: zero between launches (the kernels re-arm them)
@@ -222,6 +223,8 @@ class Engine:
         self.fallbacks = 0                    # how often the guard moved this engine from the fused phase 1 to the bf16 chain (0 or 1)
         if self.phase1 not in ("auto", "r", "0"):
             raise ValueError(f"SN_PHASE1={self.phase1!r}: expected auto, r (fused kernel) or 0 (two-kernel bf16 chain)")
+        if self.k4_fuse not in ("0", "1"):
+            raise ValueError(f"SN_K4_FUSE={self.k4_fuse!r}: expected 1 (CAB2's phase 2 inside CAB1's phase 1, four launches per unit) or 0 (five launches)")
         # hipGraph replay of the whole forward (~1400 launches per window): the first call with a given input signature runs eagerly, the second
         # one is captured, later ones replay, so the Python / ctypes / allocator work per launch disappears.  Measured on MI355X: neutral at
         # 1280x720 (126.4 vs 126.0 ms per window: the GPU is never starved there, kernels average 90 us), 1.39x on a 64x96 clip where the ~10 us
@@ -248,6 +251,12 @@ class Engine:
         meta = self._meta
         if self._unit is not None and not (meta and meta[0] == "naf"):       # a kernel of the unit with its own meta (the fp32 engine's operators)
             meta = tuple(meta) + ("unit",) + self._unit
+        if fn == "sn_cab2_phase2_cab1_phase1":
+            # The fused launch IS the CAB1's phase 1 (plus the CAB2's phase 2 inside its stagers): its time is recorded as sn_cab1_phase1.  The
+            # consumers of these records count a finished CAB -- and through it the window's units and their algorithmic bytes -- by its phase-2
+            # record, so the CAB2 gets one of zero length (the same event twice): the unit count stays what it is and no time is counted twice.
+            self.prof.append(("sn_gsts_cab2_phase2", "sn_gsts_cab2_phase2 [in sn_cab1_phase1]", self._k4_meta, e0, e0))
+            fn = "sn_cab1_phase1"
         self.prof.append((fn, label, meta, e0, e1))
 
     act_dtype = torch.bfloat16
@@ -346,6 +355,9 @@ class Engine:
     # cannot leave ITS range).  SN_PHASE1 picks one; "auto" starts fused and lets the range guard decide.
     # C = 64, 20 x 360 x 640, CAB1 / CAB2: "r" 565 / 696 us (round 4), chain 837 / 950 us
     phase1 = os.environ.get("SN_PHASE1", "auto")
+    # A GSTS unit is K0 -> phase 1 (CAB2) -> K4 (CAB2) -> phase 1 (CAB1) -> K4 (CAB1).  "1": the CAB2's K4 runs inside the stager waves of the CAB1's
+    # phase 1 (sn_cab2_phase2_cab1_phase1: one launch and one read of y per unit less, bit-identical); "0": five launches.  See k4_fused().
+    k4_fuse = os.environ.get("SN_K4_FUSE", "1")
     # Range guard of the half-precision intermediates: every squeeze-excite reduction of the GSTS path (the sn_se_fold tail, sn_ca_mlp)
     # raises a device flag when a channel sum is not finite -- what an overflowed fp16 `a`, g1 or r upstream turns into.  forward() reads the flag
     # once per call; a raised flag on the fused path switches THIS engine to the chain for good, warns, and recomputes the window.
@@ -536,7 +548,17 @@ class Engine:
             return False
         return not (self.V.denoise and not self._fold_ok(T))
 
-    def naf(self, pre: str, x: Act, mode: int, *, frames: Optional[Tuple[int, int]] = None, bufs: Optional[Dict[str, torch.Tensor]] = None) -> Act:
+    def k4_fused(self, T: int, c: int) -> bool:
+        """Does gsts_unit run the CAB2's phase 2 inside the CAB1's phase 1?  The fused launch exists for C = 64 without the denoisers' inner
+        CALayer2 (C = 80 -- two stager waves, two lanes per pixel, 149 KB of LDS -- and the denoisers' two passes keep the five launches), it needs
+        the CAB2's squeeze-excite scale on the device before it starts (the fold: the tail of the CAB2's phase 1 wrote it) and takes whole
+        tensors only: no temporal split, no batch of clips, and the unit schedule (frame / streams launch frame ranges through naf).  The range
+        guard's move to the bf16 chain (phase1 "0") switches it off with the fused phase 1."""
+        return (self.k4_fuse == "1" and self._fused_phase1(T) and self._fold_ok(T) and c == 64 and not self.V.denoise and self.split is None
+                and not self._clip and self.schedule == "unit")
+
+    def naf(self, pre: str, x: Act, mode: int, *, frames: Optional[Tuple[int, int]] = None, bufs: Optional[Dict[str, torch.Tensor]] = None,
+            defer_k4: bool = False, k4: Optional[Tuple] = None):
         """CAB2 (mode 1/2, fed by the GSTS gather of x) or CAB1 (mode 0) (gshift_deblur1.py:183-255).
 
         Phase 1: [K0 sn_gsts_shiftconv (CAB2 only)] -> sn_gsts_cab2_phase1 / sn_cab1_phase1 (ONE kernel up to g2; the denoisers run it twice, the first
@@ -545,7 +567,9 @@ class Engine:
         workgroup per frame, or sn_ca_mlp) and phase 2, K4 sn_gsts_cab2_phase2 / sn_cab1_phase2.  The global average pool of CALayer2 sits
         between the phases and forbids a single pass.  Every frame is independent inside a CAB (the pool is per frame), so
         on a temporally split window the chain runs in two pieces: all frames but the boundary one while the halo exchange is in flight, then
-        the boundary frame.  frames = (t0, nt) / bufs: one frame range of a block whose tensors the caller owns (the frame-wavefront schedule)."""
+        the boundary frame.  frames = (t0, nt) / bufs: one frame range of a block whose tensors the caller owns (the frame-wavefront schedule).
+        defer_k4 / k4 (gsts_unit only, see k4_fused): a CAB2 stops before its K4 and returns that launch's operands; the CAB1 given them runs
+        sn_cab2_phase2_cab1_phase1 in place of its phase 1, with x the CAB2's output tensor, written by that launch."""
         lib, V, P = self.lib, self.V, self.P
         u = P.units[pre]
         T, h, w, c = x.dims
@@ -602,6 +626,10 @@ class Engine:
                     opt = C.byref(L.Phase1Opts(ca1.data_ptr(), 0, 0, g1s_ptr))
                 if mode:
                     self._call("sn_gsts_cab2_phase1", "sn_gsts_cab2_phase1", C.byref(src), hw_ptr, wt, g2.data_ptr(), pool2.data_ptr(), sep, opt, st)
+                elif k4 is not None:
+                    src2, g2_2, ca2_2, w_out2, b_out2, self._k4_meta = k4[:6]
+                    self._call("sn_cab2_phase2_cab1_phase1", "sn_cab2_phase2_cab1_phase1", C.byref(src2), g2_2.data_ptr(), ca2_2.data_ptr(), w_out2.data_ptr(),
+                               b_out2, x.t.data_ptr(), wt, g2.data_ptr(), pool2.data_ptr(), sep, None, st)
                 else:
                     self._call("sn_cab1_phase1", "sn_cab1_phase1", C.byref(src), wt, g2.data_ptr(), pool2.data_ptr(), sep, opt, st)
                 folded = sep is not None
@@ -619,8 +647,10 @@ class Engine:
                            g2.data_ptr() + fr2, pool2.data_ptr() + f0 * nb2 * c * 4, n, h, w, c, st)
             if not folded:
                 ca_mlp(pre + "ca2", pool2, ca2, f0, n)
-            k4 = "sn_gsts_cab2_phase2" if mode else "sn_cab1_phase2"
-            self._call(k4, k4, C.byref(src), g2.data_ptr(), ca2.data_ptr(), u["w_out"].data_ptr(), b_out, y.data_ptr(), st)
+            if defer_k4:         # (one piece: no split.  B rides along: the tensors stay referenced until the fused launch is issued)
+                return Act(y, c), (src, g2, ca2, u["w_out"], b_out, self._meta, B)
+            fn4 = "sn_gsts_cab2_phase2" if mode else "sn_cab1_phase2"
+            self._call(fn4, fn4, C.byref(src), g2.data_ptr(), ca2.data_ptr(), u["w_out"].data_ptr(), b_out, y.data_ptr(), st)
         return Act(y, c)
 
     def naf_buffers(self, T: int, h: int, w: int, c: int, mode: int) -> Dict[str, torch.Tensor]:
@@ -657,6 +687,9 @@ class Engine:
         return B
 
     def gsts_unit(self, pre: str, x: Act, reverse: bool) -> Act:
+        if self.k4_fused(x.dims[0], x.c):           # four launches: K0, phase 1 (CAB2), [K4 (CAB2) + phase 1 (CAB1)], K4 (CAB1)
+            y2, k4 = self.naf(pre + "0.", x, 2 if reverse else 1, defer_k4=True)
+            return self.naf(pre + "1.", y2, 0, k4=k4)
         return self.naf(pre + "1.", self.naf(pre + "0.", x, 2 if reverse else 1), 0)
 
     def shift_block(self, pre: str, x: Act) -> Act:

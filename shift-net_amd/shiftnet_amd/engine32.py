@@ -111,6 +111,7 @@ class Engine32(Engine):
 
     act_dtype = torch.float32
     fused_cab_tail = False
+    k4_fuse = "0"                      # sn_cab2_phase2_cab1_phase1 is a bf16 kernel: the fp32 unit keeps its own launches
     skip_up_lowres = False             # SkipUpSample stays "bilinear x2 in the 1x1's loader" here (sn_upsample2_add is a bf16 pass)
     # Dense k = 1 / 3 and grouped-by-8 k = 5 convs with their operands split into bf16 hi + lo parts (three bf16 MFMAs per k-step instead of
     # eight fp32 ones; ~2^-16 per product, fp32 accumulation).  False: exact fp32 products everywhere (v_mfma_f32_16x16x4_f32), about half as

@@ -25,6 +25,7 @@ SYMBOLS = [          # include/shiftnet_hip.h, production ABI
     "sn_ingest_yuv", "sn_egress_yuv",
     "sn32_conv2d", "sn32_conv2d_route", "sn32_gsts_gather", "sn32_layernorm", "sn32_gate", "sn32_gate_sum", "sn32_chan_sum", "sn32_scale_residual", "sn32_ingest", "sn32_cab_ca", "sn32_dw_gate", "sn32_conv1x1_gate2", "sn32_gsts_shiftconv", "sn32_conv_csum_tiles",
     "sn_ln_gemm_gate", "sn_lngate_blocks", "sn_grp5_gemm_gate", "sn_grp5_blocks", "sn_gsts_cab2_phase1", "sn_cab1_phase1", "sn_phase1_pool_blocks", "sn_phase1_g1_store_bytes", "sn_p1r_plan", "sn_p1r_strip_begin",
+    "sn_cab2_phase2_cab1_phase1", "sn_cab2_phase2_cab1_phase1_supported",
 ]
 
 
@@ -186,6 +187,8 @@ def load() -> C.CDLL:
     lib.sn_cab1_phase1.argtypes = [C.POINTER(UnitSrc), C.POINTER(Phase1Weights), vp, vp, C.POINTER(SeFold), C.POINTER(Phase1Opts), vp]
     lib.sn_gsts_cab2_phase2.argtypes = [C.POINTER(UnitSrc), vp, vp, vp, vp, vp, vp]
     lib.sn_cab1_phase2.argtypes = [C.POINTER(UnitSrc), vp, vp, vp, vp, vp, vp]
+    lib.sn_cab2_phase2_cab1_phase1_supported.argtypes = [C.POINTER(UnitSrc)]
+    lib.sn_cab2_phase2_cab1_phase1.argtypes = [C.POINTER(UnitSrc), vp, vp, vp, vp, vp, C.POINTER(Phase1Weights), vp, vp, C.POINTER(SeFold), C.POINTER(Phase1Opts), vp]
     lib.sn_ingest_u8.argtypes = [vp, vp, ci, ci, ci, ci, vp]
     lib.sn_egress_blocks.argtypes = []
     lib.sn_egress_u8.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, vp]
