@@ -473,6 +473,16 @@ typedef struct sn_yuv_fmt {
 int sn_ingest_yuv(const uint8_t* src, const sn_yuv_fmt* fmt, void* dst, int dst_dtype, int T, int H, int W, int Hp, int Wp, void* stream);
 int sn_egress_yuv(const void* out, int out_dtype, const sn_yuv_fmt* fmt, uint8_t* dst, int T, int H, int W, int Hp, int Wp, void* stream);
 
+/* sn_yuv_thumb (added like the two above: a new symbol, SN_ABI_VERSION stays 20): luma thumbnails for the scene-cut detector of the video
+ * restorer (shiftnet_amd/scenes.py).  src: T payloads as sn_ingest_yuv takes them (frame_bytes(fmt, H, W) apart, luma plane first); only the
+ * luma plane is read, fmt->matrix and fmt->range are not looked at.  dst:[T][ceil(H/8)][ceil(W/8)] uint16,
+ *   dst[t][by][bx] = sum of the luma codes Y[y][x] of frame t over 8 by <= y < min(8 by + 8, H), 8 bx <= x < min(8 bx + 8, W):
+ * the integer sum of the 8 x 8 block; pixels outside H x W contribute nothing (edge blocks are partial sums, not replicated).
+ * 64 x 1023 = 65 472 fits uint16.  Integer arithmetic, no atomics: exact, and the same for every launch geometry.  Only dst is written.
+ * SN_EINVAL before anything is launched: null pointers, bits not 8 / 10, unknown chroma code, T, H or W < 1, dst at an odd address, src at
+ * an odd address at 10 bit. */
+int sn_yuv_thumb(const uint8_t* src, const sn_yuv_fmt* fmt, uint16_t* dst, int T, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,9 @@
 //
 //   sn_ingest_yuv : T payloads [Y plane][U plane][V plane] -> [T][3][Hp][Wp] RGB of the module dtype in [0,1]; pixels outside H x W
 //                   replicate the edge pixel, so one launch gives the network a legal size for any input size;
-//   sn_egress_yuv : [T][3][Hp][Wp] RGB (float32 or module dtype) -> T payloads of H x W (the crop of the padding).
+//   sn_egress_yuv : [T][3][Hp][Wp] RGB (float32 or module dtype) -> T payloads of H x W (the crop of the padding);
+//   sn_yuv_thumb  : T payloads -> [T][ceil(H/8)][ceil(W/8)] uint16 sums of the luma codes of every 8 x 8 block (the scene-cut measure of
+//                   shiftnet_amd/scenes.py is computed from these on the host); integer arithmetic, the chroma planes are not read.
 //
 // The arithmetic (order of operations, constants) is stated in include/shiftnet_hip.h and restated in float32 by tests/yuv_ref.py,
 // which these kernels equal bit for bit.  Every float product and sum is rounded separately (contraction is off for this file: no
@@ -308,6 +310,37 @@ __global__ __launch_bounds__(256) void egress_yuv_kernel(const void* __restrict_
     }
 }
 
+// ---- thumbnail ------------------------------------------------------------------------------------------------------------------
+// A lane owns one 8 x 8 luma block: 8 rows of one 8 B (10 bit: 16 B) load where the address allows it, element-wise on the right edge
+// (x0 + 8 > W: only the pixels inside the frame are read and summed) and where the row's address is not aligned.  Neighbouring lanes
+// own neighbouring blocks of a block row, so a wave's load covers 512 (1024) consecutive bytes of a luma row and its store 128 bytes.
+// No atomics and no cross-lane step: the sum is an exact integer, the same for every launch geometry (64 x 1023 = 65 472 < 2^16).
+template <int ESZ>
+__global__ __launch_bounds__(256) void yuv_thumb_kernel(const uint8_t* __restrict__ src, uint16_t* __restrict__ dst, int H, int W, int hb, int wb,
+                                                      size_t frame_bytes) {
+    const int t = blockIdx.z;
+    const int bx = blockIdx.x * 32 + threadIdx.x, by = blockIdx.y * 8 + threadIdx.y;
+    if (bx >= wb || by >= hb) return;
+    const uint8_t* yp = src + (size_t)t * frame_bytes;
+    const int x0 = bx * 8, y0 = by * 8;
+    const int rows = imin(8, H - y0), n = imin(8, W - x0);
+    int sum = 0;
+    if (n == 8) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            if (r < rows) {
+                int v[8];
+                ldn<ESZ, 8>(yp, (size_t)(y0 + r) * W + x0, v);
+                sum += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+            }
+        }
+    } else {
+        for (int r = 0; r < rows; ++r)
+            for (int k = 0; k < n; ++k) sum += ld1<ESZ>(yp, (size_t)(y0 + r) * W + x0 + k);
+    }
+    dst[((size_t)t * hb + by) * wb + bx] = (uint16_t)sum;
+}
+
 // constants: float64 expressions rounded once to float32 (tests/yuv_ref.py: constants() evaluates the same expressions)
 bool make_consts(const sn_yuv_fmt* f, YuvK* K) {
     if (!f || (f->bits != 8 && f->bits != 10) || f->chroma < 0 || f->chroma > 2 || f->matrix < 0 || f->matrix > 1 || f->range < 0 || f->range > 1) return false;
@@ -378,6 +411,20 @@ int sn_egress_yuv(const void* out, int out_dtype, const sn_yuv_fmt* fmt, uint8_t
     if (grid.y > 65535) return SN_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     SN_YUV_DISPATCH(egress_yuv_kernel, out, out_dtype, dst, K, H, W, Hp, Wp, fb, src_vec);
+    return sn_check_launch();
+}
+
+int sn_yuv_thumb(const uint8_t* src, const sn_yuv_fmt* fmt, uint16_t* dst, int T, int H, int W, void* stream) {
+    sn_clear_error();
+    if (!src || !dst || !fmt || (fmt->bits != 8 && fmt->bits != 10) || fmt->chroma < 0 || fmt->chroma > 2 || T < 1 || T > 65535 || H < 1 || W < 1) return SN_EINVAL;
+    if (((uintptr_t)dst & 1) || (fmt->bits == 10 && ((uintptr_t)src & 1))) return SN_EINVAL;
+    const size_t fb = frame_bytes_of(fmt, H, W);
+    const int hb = (H + 7) / 8, wb = (W + 7) / 8;
+    const dim3 block(32, 8), grid((wb + 31) / 32, (hb + 7) / 8, T);
+    if (grid.y > 65535) return SN_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (fmt->bits == 8) hipLaunchKernelGGL((yuv_thumb_kernel<1>), grid, block, 0, s, src, dst, H, W, hb, wb, fb);
+    else hipLaunchKernelGGL((yuv_thumb_kernel<2>), grid, block, 0, s, src, dst, H, W, hb, wb, fb);
     return sn_check_launch();
 }
 

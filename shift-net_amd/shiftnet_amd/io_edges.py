@@ -4,6 +4,7 @@
                with 3 instead of 12 bytes per pixel crossing PCIe;
 ``ingest_yuv`` / ``egress_yuv``: planar Y'CbCr payloads as a Y4M stream carries them (csrc/sn_yuv.hip) <-> RGB tensors, for the video
                restorer (shiftnet_amd/restore.py); 1.5 bytes per pixel cross PCIe for 8-bit 4:2:0;
+``thumb_yuv``  : the same payloads -> uint16 sums of the luma codes of every 8 x 8 block, for the scene-cut detector (shiftnet_amd/scenes.py);
 ``egress_u8``  == the per-frame ``clamp(0,1) * 255`` -> skimage PSNR(data_range=255) against the uint8 ground truth
                (:139-143) and the rounded uint8 frame cv2.imwrite would store (:152).
 """
@@ -106,4 +107,18 @@ def egress_yuv(out: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, dst: Optional
     with torch.cuda.device(out.device):
         L.check(L.load().sn_egress_yuv(out.data_ptr(), _CODE[out.dtype], fmt, y.data_ptr(), T, H, W, Hp, Wp,
                                        torch.cuda.current_stream(out.device).cuda_stream), "sn_egress_yuv")
+    return y
+
+
+def thumb_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """payload_u8: [T, frame_bytes] uint8 on a HIP device (only the luma plane of each payload is read) -> uint16 [T, ceil(H/8), ceil(W/8)]:
+    the integer sum of the luma codes of every 8 x 8 block, partial at the right and bottom edge.  ``out``: a tensor of that shape to fill."""
+    fb = fmt.frame_bytes(H, W)
+    assert payload_u8.dtype == torch.uint8 and payload_u8.is_cuda and payload_u8.dim() == 2 and payload_u8.shape[1] == fb and payload_u8.is_contiguous()
+    T, hb, wb = payload_u8.shape[0], (H + 7) // 8, (W + 7) // 8
+    y = out if out is not None else torch.empty((T, hb, wb), dtype=torch.uint16, device=payload_u8.device)
+    assert tuple(y.shape) == (T, hb, wb) and y.dtype == torch.uint16 and y.is_contiguous() and y.device == payload_u8.device
+    with torch.cuda.device(payload_u8.device):
+        L.check(L.load().sn_yuv_thumb(payload_u8.data_ptr(), fmt, y.data_ptr(), T, H, W,
+                                      torch.cuda.current_stream(payload_u8.device).cuda_stream), "sn_yuv_thumb")
     return y

@@ -7,6 +7,12 @@ colour conversion, the padding to a legal size and the crop run on the device (c
 
 Windows: window k restores frames [k L, min((k + 1) L, N)) and feeds the network those plus 2 frames before and 2 after; frames before
 0 and after N - 1 are reflected without repeating the edge (-1 -> 1, -2 -> 2, N -> N - 2), or clamped where N <= 2.
+
+Scenes (``scene_cuts``, off by default): every GSTS unit of the network borrows channels from the neighbouring frames, so across a cut the
+last frames of one shot would be restored with features of the next.  With scene cuts c_1 < c_2 < ... the scenes [0, c_1), [c_1, c_2), ...
+are clips of their own: windows restart at every scene start and reflect about the scene's first and last frame, and the bytes written are
+those of restoring every scene as a separate video.  The cuts are listed by the caller or found from luma thumbnails made on the device
+(``sn_yuv_thumb``, shiftnet_amd/scenes.py).
 """
 from __future__ import annotations
 
@@ -48,6 +54,19 @@ def plan_windows(n: int, one_len: int, past: int = PAST, future: int = FUTURE) -
     return [window_indices(k, one_len, n, past, future) for k in range((n + one_len - 1) // one_len)]
 
 
+def plan_scene_windows(n: int, one_len: int, cuts: Iterable[int], past: int = PAST, future: int = FUTURE) -> List[Tuple[int, int, List[int]]]:
+    """plan_windows of every scene [0, c_1), [c_1, c_2), ..., [c_k, n) on its own, indices shifted to the stream's.  Cuts at or beyond n are
+    ignored."""
+    from .scenes import check_cuts
+    if n < 1 or one_len < 1:
+        raise ValueError(f"plan_scene_windows: need n >= 1 and one_len >= 1, got {n}, {one_len}")
+    starts = [0] + [c for c in check_cuts(cuts) if c < n]
+    plan = []
+    for a, b in zip(starts, starts[1:] + [n]):
+        plan += [(a + lo, cnt, [a + i for i in idx]) for lo, cnt, idx in plan_windows(b - a, one_len, past, future)]
+    return plan
+
+
 def pad_multiple(topo: str) -> int:
     return 8 if topo == "plus" else 4
 
@@ -87,6 +106,69 @@ class _Frames:
             del self.buf[:drop]
             self.base += drop
         return lo, cnt, frames
+
+
+class _SceneFrames:
+    """_Frames for a stream with scene cuts: the windows of plan_scene_windows from an iterator of unknown length, with the cut decisions
+    arriving late.  ``decider`` (scenes.ListedCuts, scenes.CutDetector behind _DeviceThumbs, or anything shaped like them) is fed every frame
+    exactly once and in order, in chunks, and answers ``is_cut(t)`` for t < ``decided``; it needs ``lookahead`` frames beyond t to decide t.
+
+    The window that restores [lo, lo + L) of a scene that started at a reads frames lo - 2 .. lo + L + 1 unless the scene ends before: it
+    depends on the decisions for lo + 1 .. lo + L + 1, so it is handed out once frame lo + L + 1 + lookahead has been read or the stream has
+    ended.  Frames before max(a, lo - 2) of the next window are dropped: at most L + 4 + lookahead + 1 are held."""
+
+    def __init__(self, it: Iterable[np.ndarray], decider) -> None:
+        self.it = iter(it)
+        self.decider = decider
+        self.base = 0
+        self.buf: List[np.ndarray] = []
+        self.n: Optional[int] = None
+        self.fed = 0                      # frames handed to the decider
+        self.finished = False             # the decider has been told that the stream has ended
+        self.a = 0                        # first frame of the current scene
+        self.lo = 0                       # next frame to restore
+        self.k = 0
+        self.cuts: List[int] = []         # the scene starts used
+
+    def _fill(self, upto: int) -> None:
+        while self.n is None and self.base + len(self.buf) <= upto:
+            try:
+                self.buf.append(next(self.it))
+            except StopIteration:
+                self.n = self.base + len(self.buf)
+        have = self.base + len(self.buf)
+        if have > self.fed:
+            self.decider.feed(self.buf[self.fed - self.base:])
+            self.fed = have
+        if self.n is not None and not self.finished:
+            self.decider.finish()
+            self.finished = True
+
+    def window(self, k: int, one_len: int) -> Optional[Tuple[int, int, List[np.ndarray]]]:
+        """The frames of the k-th window of the stream (k counts up from 0 across the scenes), or None past the end."""
+        assert k == self.k, "windows are handed out in order"
+        lo, a = self.lo, self.a
+        last = lo + one_len + FUTURE - 1                                      # the last frame this window can read
+        self._fill(last + self.decider.lookahead)
+        n = self.n if self.n is not None else self.base + len(self.buf)      # not at the end: n > last
+        if lo >= n:
+            return None
+        cut = next((t for t in range(lo + 1, min(last, n - 1) + 1) if self.decider.is_cut(t)), None)
+        # the scene's end.  Without a cut in reach and before the end of the stream it is not known, only that it lies beyond `last`: then no
+        # index of this window reflects about it, and n (> last) stands in for it with the same result
+        b = cut if cut is not None else n
+        hi = min(lo + one_len, b)
+        frames = [self.buf[a + reflect_index(i - a, b - a) - self.base] for i in range(lo - PAST, hi + FUTURE)]
+        self.k += 1
+        self.lo = hi
+        if cut is not None and hi == cut:
+            self.a = cut
+            self.cuts.append(cut)
+        drop = max(self.a, self.lo - PAST) - self.base                        # the next window reaches back to here
+        if drop > 0:
+            del self.buf[:drop]
+            self.base += drop
+        return lo, hi - lo, frames
 
 
 class _Thread(threading.Thread):
@@ -133,6 +215,62 @@ class _Thread(threading.Thread):
             self.join(timeout=0.05)
 
 
+# ---- cut detection on the device ----------------------------------------------------------------------------------------------------
+class _DeviceThumbs:
+    """The decider of _SceneFrames for ``scene_cuts="auto"``: host payloads -> luma thumbnails on the device (sn_yuv_thumb) -> scenes.CutDetector.
+
+    The detector has an upload of its own, luma bytes only: which frames a window holds depends on the decisions, so the thumbnails must exist
+    before the window is assembled and uploaded, and the window's upload repeats reflected frames while the detector takes every frame once.
+    One chunk = the new frames of one window: their luma planes go through a pinned buffer into payload-shaped device slots (the chroma part
+    of a slot is never written and never read), one launch makes the thumbnails, one copy brings the uint16 sums back into pinned memory, and the
+    calling thread waits for the event recorded behind that copy on the detector's own stream -- never for the device, and never for the stream
+    the forward runs on."""
+
+    def __init__(self, torch, dev, fmt, h: int, w: int, chunk: int, threshold: float, ratio: float) -> None:
+        from .scenes import CutDetector
+        self.torch, self.dev, self.fmt, self.h, self.w, self.chunk = torch, dev, fmt, h, w, chunk
+        self.lb = h * w * (1 if fmt.bits == 8 else 2)                    # the luma plane leads the payload
+        hb, wb = (h + 7) // 8, (w + 7) // 8
+        self.pin_y = torch.empty((chunk, self.lb), dtype=torch.uint8).pin_memory()
+        self.dev_y = torch.empty((chunk, fmt.frame_bytes(h, w)), dtype=torch.uint8, device=dev)
+        self.dev_s = torch.empty((chunk, hb, wb), dtype=torch.uint16, device=dev)
+        self.pin_s = torch.empty((chunk, hb, wb), dtype=torch.uint16).pin_memory()
+        self.stream, self.event = torch.cuda.Stream(dev), torch.cuda.Event()
+        self.detector = CutDetector(h, w, fmt.bits, threshold, ratio)
+        self.lookahead = self.detector.lookahead
+        self.frames = self.launches = 0
+
+    def feed(self, frames: Sequence[np.ndarray]) -> None:
+        from .io_edges import thumb_yuv
+        torch = self.torch
+        for o in range(0, len(frames), self.chunk):
+            part = frames[o:o + self.chunk]
+            t = len(part)
+            pin = self.pin_y.numpy()
+            for i, f in enumerate(part):
+                pin[i] = f[:self.lb]
+            with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+                for i in range(t):
+                    self.dev_y[i, :self.lb].copy_(self.pin_y[i], non_blocking=True)
+                thumb_yuv(self.dev_y[:t], self.fmt, self.h, self.w, out=self.dev_s[:t])
+                self.pin_s[:t].copy_(self.dev_s[:t], non_blocking=True)
+                self.event.record(self.stream)
+            self.event.synchronize()
+            self.detector.feed(self.pin_s[:t].numpy())
+            self.frames += t
+            self.launches += 1
+
+    def finish(self) -> None:
+        self.detector.finish()
+
+    @property
+    def decided(self) -> int:
+        return self.detector.decided
+
+    def is_cut(self, t: int) -> bool:
+        return self.detector.is_cut(t)
+
+
 # ---- the restorer -----------------------------------------------------------------------------------------------------------------
 class VideoRestorer:
     """``VideoRestorer(net, one_len, sigma=None).restore(frames, fmt, height, width)`` -> iterator of restored payloads, one per input frame.
@@ -140,14 +278,28 @@ class VideoRestorer:
     net: a GShiftNet of shiftnet_amd.arch on a HIP device (eval mode, any dtype).  sigma: the noise level in 8-bit code values for the
     denoise variants (noise_map = sigma / 255 everywhere; no noise is added and the frame is not cut into quadrants).
     pipeline: read / copy / ingest window k + 1 on a side stream and copy back / hand out window k - 1 while window k runs; False runs
-    the same steps one after the other.  Both give identical bytes."""
+    the same steps one after the other.  Both give identical bytes.
+    scene_cuts: None -- the stream is one clip; ``"auto"`` -- find the cuts from luma thumbnails made on the device (scenes.py: frame t starts a
+    scene iff its measure m[t] >= cut_threshold and >= cut_ratio times the median of its six neighbours'; heuristic defaults); an iterable of
+    frame indices (each >= 1, strictly increasing) -- use these, run no detector.  Every scene is then restored as a clip of its own: the bytes
+    are those of restoring each scene as a separate video.  Once ``restore()`` has been exhausted ``stats["cuts"]`` lists the scene starts used,
+    ``stats["cut_measure"]`` the m[t] of every frame (auto only; m[0] = 0.0) and ``stats["cuts_ignored"]`` the listed cuts at or beyond the end."""
 
-    def __init__(self, net, one_len: int, sigma: Optional[float] = None, pipeline: bool = True) -> None:
+    def __init__(self, net, one_len: int, sigma: Optional[float] = None, pipeline: bool = True, scene_cuts=None,
+                 cut_threshold: float = 4.0, cut_ratio: float = 2.5) -> None:
         import torch
         self.torch = torch
         self.net, self.one_len, self.pipeline = net, int(one_len), bool(pipeline)
         if self.one_len < 1:
             raise ValueError("one_len must be >= 1")
+        if scene_cuts is None or (isinstance(scene_cuts, str) and scene_cuts == "auto"):
+            self.scene_cuts = scene_cuts
+        elif isinstance(scene_cuts, str):
+            raise ValueError(f"scene_cuts must be None, 'auto' or an iterable of frame indices, got {scene_cuts!r}")
+        else:
+            from .scenes import check_cuts
+            self.scene_cuts = check_cuts(scene_cuts)
+        self.cut_threshold, self.cut_ratio = float(cut_threshold), float(cut_ratio)
         self.V = net.V
         if self.V.denoise and sigma is None:
             raise ValueError("sigma is required by the denoise variants (the noise level of the footage, in 8-bit code values)")
@@ -245,6 +397,26 @@ class VideoRestorer:
         self.stats["window_forward_ms"] = ms
         self.stats["forward_s"] = sum(ms) / 1e3
         self.stats["windows"] = len(ms)
+        src = self._src
+        if isinstance(src, _SceneFrames):                        # its thread has ended: the stream has been read to its end
+            self.stats["cuts"] = list(src.cuts)
+            if isinstance(src.decider, _DeviceThumbs):
+                self.stats["cut_measure"] = list(src.decider.detector.m)
+                self.stats["thumb_frames"], self.stats["thumb_launches"] = src.decider.frames, src.decider.launches
+            else:
+                self.stats["cuts_ignored"] = [c for c in src.decider.all if c >= (src.n or 0)]
+
+    def _source(self, frames: Iterable[np.ndarray]):
+        """The frame source of one restore(): today's for scene_cuts=None, the scene-aware one otherwise."""
+        if self.scene_cuts is None:
+            self._src = _Frames(frames)
+        elif self.scene_cuts == "auto":
+            self._src = _SceneFrames(frames, _DeviceThumbs(self.torch, self.dev, self.fmt, self.h, self.w, self.one_len + PAST + FUTURE + 4,
+                                                           self.cut_threshold, self.cut_ratio))
+        else:
+            from .scenes import ListedCuts
+            self._src = _SceneFrames(frames, ListedCuts(self.scene_cuts))
+        return self._src
 
     # -- drivers -------------------------------------------------------------------------------------------------------------------
     def restore(self, frames: Iterable[np.ndarray], fmt, height: int, width: int) -> Iterator[np.ndarray]:
@@ -254,6 +426,7 @@ class VideoRestorer:
         self._timers: List = []
         self.used = [False, False]
         self.stats = {"frames": 0, "windows": 0, "forward_s": 0.0, "window_forward_ms": []}
+        self._src = None
         main = torch.cuda.current_stream(self.dev)
 
         def checked(it):
@@ -264,7 +437,7 @@ class VideoRestorer:
                 yield f
 
         if not self.pipeline:
-            src = _Frames(checked(frames))
+            src = self._source(checked(frames))
             k = 0
             with torch.cuda.device(self.dev):
                 while True:
@@ -295,7 +468,7 @@ class VideoRestorer:
             return False
 
         def stage_loop(put):
-            src = _Frames(checked(frames))
+            src = self._source(checked(frames))
             k = 0
             with torch.cuda.device(self.dev):
                 while True:
@@ -346,6 +519,12 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--matrix", choices=["bt601", "bt709"], default=None, help="default: bt709 when H >= 720, else bt601")
     ap.add_argument("--range", choices=["limited", "full"], default=None, help="default: the stream's XCOLORRANGE, else limited")
     ap.add_argument("--no_pipeline", action="store_true", help="run read / copy / forward / write one after the other")
+    ap.add_argument("--scene_cuts", default="off", metavar="{off,auto,FILE}",
+                    help="restore every scene as a clip of its own: 'auto' finds the cuts on the device (a heuristic, see --cut_threshold / --cut_ratio), "
+                         "FILE lists the first frame of every scene but the first, one index per line ('#' comments); default off: the stream is one clip")
+    ap.add_argument("--cut_threshold", type=float, default=4.0, help="auto: smallest mean absolute difference of 8x8 block means (8-bit code units) of a cut")
+    ap.add_argument("--cut_ratio", type=float, default=2.5, help="auto: ... and at least this many times the median of the six neighbouring frames' differences")
+    ap.add_argument("--cuts_out", default=None, metavar="FILE", help="write the scene starts that were used, in the format --scene_cuts FILE reads")
     ap.add_argument("input", metavar="IN", help="Y4M file, or - for stdin")
     ap.add_argument("output", metavar="OUT", help="Y4M file, or - for stdout")
     return ap
@@ -374,6 +553,17 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     if "denoise" in a.variant and a.sigma is None:
         ap.error("--sigma is required by the denoise variants")
     log = lambda s: (sys.stderr.write(s + "\n"), sys.stderr.flush())      # noqa: E731
+    if a.scene_cuts == "off":
+        cuts = None
+    elif a.scene_cuts == "auto":
+        cuts = "auto"
+    else:
+        from .scenes import parse_cuts
+        try:
+            with open(a.scene_cuts, "r") as fh:
+                cuts = parse_cuts(fh.read())
+        except (OSError, ValueError) as e:
+            ap.error(f"--scene_cuts {a.scene_cuts}: {e}")
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
     fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
     try:
@@ -386,7 +576,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         fmt = yuv_fmt(hd.bits, hd.chroma_code, L.SN_YUV_BT709 if matrix == "bt709" else L.SN_YUV_BT601,
                       L.SN_YUV_FULL if rng == "full" else L.SN_YUV_LIMITED)
         net = load_net(a.variant, a.checkpoint, a.dtype)
-        vr = VideoRestorer(net, a.one_len, sigma=a.sigma, pipeline=not a.no_pipeline)
+        vr = VideoRestorer(net, a.one_len, sigma=a.sigma, pipeline=not a.no_pipeline, scene_cuts=cuts, cut_threshold=a.cut_threshold,
+                           cut_ratio=a.cut_ratio)
         wr = Y4MWriter(fout, hd)
         t0 = time.perf_counter()
         n = 0
@@ -398,8 +589,16 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         fout.flush()
         dt = time.perf_counter() - t0
         fwd = vr.stats["forward_s"]
+        used = vr.stats.get("cuts", [])
+        if vr.stats.get("cuts_ignored"):
+            log(f"scene cuts at or beyond the end of the stream ({n} frames) ignored: {vr.stats['cuts_ignored']}")
+        if a.cuts_out is not None:
+            from .scenes import format_cuts
+            with open(a.cuts_out, "w") as fh:
+                fh.write(format_cuts(used))
         log(f"done: {n} frames in {dt:.2f} s, {n / dt if dt > 0 else 0.0:.2f} frames/s end to end, "
-            f"{n / fwd if fwd > 0 else 0.0:.2f} frames/s forward only")
+            f"{n / fwd if fwd > 0 else 0.0:.2f} frames/s forward only, {len(used) + 1} scene{'s' if used else ''}"
+            f"{'' if cuts is None else (' (cuts found)' if cuts == 'auto' else ' (cuts listed)')}")
     finally:
         if fin is not sys.stdin.buffer:
             fin.close()

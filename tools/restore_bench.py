@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""Measurements behind DESIGN.md 3.11 (run on the MI355X from the repository root).
+"""Measurements behind DESIGN.md 3.11 and 3.13 (run on the MI355X from the repository root).
 
   kernels : time per pixel of sn_ingest_yuv / sn_egress_yuv (4:2:0 8 bit, 720p x 20 frames) beside sn_ingest_u8 / sn_egress_u8 on the same
             frames, interleaved in one process: REPS repetitions, each timing INNER back-to-back launches of every kernel with device events;
             median and min..max over the repetitions.
   pipeline: steady-state wall time per 720p window of the pipelined restorer (Shift-Net-s, one_len 16, bf16, Y4M held in memory) beside the
             forward-only time of the same windows (device events in the same runs) and beside pipeline=False, the two alternating.
+            --scene_cuts auto: the same stream with the cut detector running (sn_yuv_thumb; 3.13).  --cut_every N: every second scene of N frames
+            is inverted, so that the stream has a cut every N frames; with --scene_cuts off / auto / listed.
 Prints one JSON object per part.
 """
 import argparse
@@ -25,7 +27,7 @@ import torch  # noqa: E402
 
 from shiftnet_amd import lib as L  # noqa: E402
 from shiftnet_amd import restore, synth, y4m  # noqa: E402
-from shiftnet_amd.io_edges import egress_u8, egress_yuv, ingest_u8, ingest_yuv, yuv_fmt  # noqa: E402
+from shiftnet_amd.io_edges import egress_u8, egress_yuv, ingest_u8, ingest_yuv, thumb_yuv, yuv_fmt  # noqa: E402
 
 
 def summary(v):
@@ -43,8 +45,10 @@ def kernels(a):
     out_bf, out_32 = rgb.to(torch.bfloat16), rgb
     x_bf = torch.empty((1, T, 3, H, W), dtype=torch.bfloat16, device="cuda")
     dst = torch.empty_like(pay)
+    thumbs = torch.empty((T, (H + 7) // 8, (W + 7) // 8), dtype=torch.uint16, device="cuda")
     cases = {
         "ingest_yuv_bf16": lambda: ingest_yuv(pay, fmt, H, W, H, W, torch.bfloat16, out=x_bf),
+        "thumb_yuv": lambda: thumb_yuv(pay, fmt, H, W, out=thumbs),
         "ingest_u8_bf16": lambda: ingest_u8(u8, torch.bfloat16),
         "egress_yuv_bf16": lambda: egress_yuv(out_bf, fmt, H, W, dst=dst),
         "egress_u8_bf16": lambda: egress_u8(out_bf),
@@ -80,12 +84,19 @@ def pipeline(a):
     buf = io.BytesIO()
     wr = y4m.Y4MWriter(buf, hd)
     for i in range(n):
-        wr.write(pay8[i % 8])
+        j = i % 14                                                                   # 0 .. 7, 6 .. 1: consecutive frames are always neighbours of
+        p = pay8[j if j < 8 else 14 - j]                                             # the clip (a jump back from 7 to 0 would look like a cut)
+        if a.cut_every and (i // a.cut_every) % 2:                                   # every second scene inverted (the luma plane: 235 + 16 - Y)
+            p = p.copy()
+            p[:H * W] = 251 - p[:H * W]
+        wr.write(p)
     data = buf.getvalue()
     net = restore.load_net("deblur_small", "synthetic", "bf16")
+    cuts = {"off": None, "auto": "auto", "listed": list(range(a.cut_every, n, a.cut_every)) if a.cut_every else []}[a.scene_cuts]
+    found = []
 
     def run(pipe):
-        vr = restore.VideoRestorer(net, one_len, pipeline=pipe)
+        vr = restore.VideoRestorer(net, one_len, pipeline=pipe, scene_cuts=cuts)
         sink = y4m.Y4MWriter(io.BytesIO(), hd)
         stamps = []
         t0 = time.perf_counter()
@@ -94,6 +105,7 @@ def pipeline(a):
             if (i + 1) % one_len == 0:
                 stamps.append(time.perf_counter())
         total = time.perf_counter() - t0
+        found.append(vr.stats.get("cuts"))
         gaps = [(b - c) * 1e3 for b, c in zip(stamps[1:], stamps[:-1])]
         return {"total_s": total, "window_wall_ms": gaps[1:], "window_forward_ms": vr.stats["window_forward_ms"][2:]}
 
@@ -112,7 +124,8 @@ def pipeline(a):
         fwd = [g for r in rs for g in r["window_forward_ms"]]
         res[k] = {"window_wall_ms": summary(wall), "window_forward_ms": summary(fwd), "total_s": [round(r["total_s"], 3) for r in rs],
                   "frames_per_s_end_to_end": [round(n / r["total_s"], 2) for r in rs]}
-    print(json.dumps({"part": "pipeline", "variant": "deblur_small", "dtype": "bf16", "one_len": one_len, "windows": nwin, "size": [H, W], "runs": a.runs, **res}))
+    print(json.dumps({"part": "pipeline", "variant": "deblur_small", "dtype": "bf16", "one_len": one_len, "windows": nwin, "size": [H, W], "runs": a.runs,
+                      "scene_cuts": a.scene_cuts, "cut_every": a.cut_every, "cuts_found": found[-1], **res}))
 
 
 if __name__ == "__main__":
@@ -123,6 +136,8 @@ if __name__ == "__main__":
     ap.add_argument("--windows", type=int, default=8)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--only", choices=["both", "pipelined", "serial"], default="both", help="pipeline part: one mode only (for a kernel trace of its own)")
+    ap.add_argument("--scene_cuts", choices=["off", "auto", "listed"], default="off", help="pipeline part: VideoRestorer(scene_cuts=...)")
+    ap.add_argument("--cut_every", type=int, default=0, help="pipeline part: a cut every N frames in the stream (0: none)")
     a = ap.parse_args()
     with torch.no_grad():
         {"kernels": kernels, "pipeline": pipeline}[a.part](a)
