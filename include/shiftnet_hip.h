@@ -483,6 +483,18 @@ int sn_egress_yuv(const void* out, int out_dtype, const sn_yuv_fmt* fmt, uint8_t
  * an odd address at 10 bit. */
 int sn_yuv_thumb(const uint8_t* src, const sn_yuv_fmt* fmt, uint16_t* dst, int T, int H, int W, void* stream);
 
+/* sn_yuv_noise_hist (a new symbol, SN_ABI_VERSION stays 20): histograms for the blind noise estimate of the video restorer
+ * (shiftnet_amd/noise.py).  src: T payloads as sn_yuv_thumb takes them; only the luma plane is read and of fmt only bits decides anything.
+ * For every non-overlapping 2 x 2 block i < H/2, j < W/2 (integer division: a last odd row or column belongs to no block) with
+ *   a = Y[2i][2j], b = Y[2i][2j+1], c = Y[2i+1][2j], d = Y[2i+1][2j+1]:
+ * the block counts iff all four codes lie strictly between lo and hi, and then adds one to bin v = |a - b - c + d| (twice the Haar HH
+ * coefficient, 0 <= v <= 2 (2^bits - 1)).  dst:[T][NB] uint32 with NB = 2 (2^bits - 1) + 1 (511 at 8 bit, 2047 at 10 bit) is OVERWRITTEN
+ * with the counts, never added to; nothing outside these T NB words is written.  Integer sums: exact, and the same for every launch
+ * geometry and schedule.  H < 2 or W < 2 is legal and gives all-zero histograms.
+ * SN_EINVAL before anything is launched: null pointers, bits not 8 / 10, unknown chroma code, T, H or W < 1, lo > hi, dst not 4-byte
+ * aligned, src at an odd address at 10 bit. */
+int sn_yuv_noise_hist(const uint8_t* src, const sn_yuv_fmt* fmt, uint32_t* dst, int lo, int hi, int T, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

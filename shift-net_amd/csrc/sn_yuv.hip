@@ -6,6 +6,9 @@
 //   sn_egress_yuv : [T][3][Hp][Wp] RGB (float32 or module dtype) -> T payloads of H x W (the crop of the padding);
 //   sn_yuv_thumb  : T payloads -> [T][ceil(H/8)][ceil(W/8)] uint16 sums of the luma codes of every 8 x 8 block (the scene-cut measure of
 //                   shiftnet_amd/scenes.py is computed from these on the host); integer arithmetic, the chroma planes are not read.
+//   sn_yuv_noise_hist : T payloads -> [T][2 (2^bits - 1) + 1] uint32 histograms of |a - b - c + d| over the 2 x 2 luma blocks whose four codes lie
+//                   strictly between lo and hi (the blind noise estimate of shiftnet_amd/noise.py is computed from these on the host); integer
+//                   arithmetic, the chroma planes are not read.
 //
 // The arithmetic (order of operations, constants) is stated in include/shiftnet_hip.h and restated in float32 by tests/yuv_ref.py,
 // which these kernels equal bit for bit.  Every float product and sum is rounded separately (contraction is off for this file: no
@@ -341,6 +344,71 @@ __global__ __launch_bounds__(256) void yuv_thumb_kernel(const uint8_t* __restric
     dst[((size_t)t * hb + by) * wb + bx] = (uint16_t)sum;
 }
 
+// ---- noise histogram ------------------------------------------------------------------------------------------------------------
+// v = |a - b - c + d| of every non-overlapping 2 x 2 luma block (twice its Haar HH coefficient), counted where all four codes lie strictly
+// between lo and hi.  A lane owns four horizontally adjacent blocks (8 x 2 pixels: one 8 B / 16 B load per row where the ADDRESS allows it,
+// element-wise otherwise and where fewer than four blocks are left on the right edge); a workgroup walks units gridDim.x * 256 apart of one
+// frame and keeps that frame's histogram in LDS: bins >= LOW in one array of NB words, bins < LOW -- where nearly all of the mass lies --
+// in 32 copies, copy (lane & 31) at word v * 32 + (lane & 31).  An LDS instruction is served in lane groups 0..31 and 32..63 and a b32
+// access banks by word mod 32, so the 32 lanes of a group hit 32 different banks whatever their v: a wave's add to the low bins never
+// meets a bank conflict or a second lane on its own address.  At the end the copies are summed and the non-zero bins added to dst with
+// one global atomic each.  Integer sums commute: the result is the same for every geometry and every schedule.
+template <int ESZ> struct NoiseK {
+    static constexpr int NB = 2 * ((ESZ == 1 ? 256 : 1024) - 1) + 1;      // 511 / 2047
+    static constexpr int LOW = ESZ == 1 ? 32 : 128;                       // the same range of noise levels at both depths
+};
+
+template <int ESZ>
+__global__ __launch_bounds__(256) void yuv_noise_hist_kernel(const uint8_t* __restrict__ src, uint32_t* __restrict__ dst, int lo, int hi, int W,
+                                                           int hb, int wb, int ux, size_t frame_bytes) {
+    constexpr int NB = NoiseK<ESZ>::NB, LOW = NoiseK<ESZ>::LOW;
+    __shared__ uint32_t low[LOW * 32];
+    __shared__ uint32_t hist[NB];
+    const int tid = threadIdx.x, t = blockIdx.y, cp = tid & 31;
+    for (int i = tid; i < LOW * 32; i += 256) low[i] = 0;
+    for (int i = tid; i < NB; i += 256) hist[i] = 0;
+    __syncthreads();
+    const uint8_t* yp = src + (size_t)t * frame_bytes;
+    const int units = ux * hb;                                            // hb, wb: whole 2 x 2 blocks; ux = ceil(wb / 4) units per block row
+    for (int u = blockIdx.x * 256 + tid; u < units; u += gridDim.x * 256) {
+        const int by = u / ux, bx0 = (u - by * ux) * 4;
+        const int nb = imin(4, wb - bx0);
+        const size_t r0 = (size_t)(2 * by) * W + 2 * bx0, r1 = r0 + W;
+        int a[8], b[8];
+        if (nb == 4) {
+            ldn<ESZ, 8>(yp, r0, a);
+            ldn<ESZ, 8>(yp, r1, b);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {                                 // pixels 2 bx0 .. 2 (bx0 + nb) - 1 < 2 wb <= W exist; the others are not read
+                const bool in = k < 2 * nb;
+                a[k] = in ? ld1<ESZ>(yp, r0 + k) : 0;
+                b[k] = in ? ld1<ESZ>(yp, r1 + k) : 0;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int p = a[2 * k], q = a[2 * k + 1], r = b[2 * k], s = b[2 * k + 1];
+            const int mn = imin(imin(p, q), imin(r, s)), mx = imax(imax(p, q), imax(r, s));
+            if (k < nb && mn > lo && mx < hi) {
+                const int d = p - q - r + s, v = d < 0 ? -d : d;          // 0 .. 2 (2^bits - 1) = NB - 1
+                if (v < LOW) atomicAdd(&low[v * 32 + cp], 1u);
+                else atomicAdd(&hist[v], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    uint32_t* out = dst + (size_t)t * NB;
+    for (int i = tid; i < NB; i += 256) {
+        uint32_t n = hist[i];
+        if (i < LOW) {
+#pragma unroll 8
+            for (int c = 0; c < 32; ++c) n += low[i * 32 + ((c + i) & 31)];   // rotated by the bin: the lanes of a group read 32 different banks
+        }
+        if (n) atomicAdd(&out[i], n);
+    }
+}
+
 // constants: float64 expressions rounded once to float32 (tests/yuv_ref.py: constants() evaluates the same expressions)
 bool make_consts(const sn_yuv_fmt* f, YuvK* K) {
     if (!f || (f->bits != 8 && f->bits != 10) || f->chroma < 0 || f->chroma > 2 || f->matrix < 0 || f->matrix > 1 || f->range < 0 || f->range > 1) return false;
@@ -425,6 +493,26 @@ int sn_yuv_thumb(const uint8_t* src, const sn_yuv_fmt* fmt, uint16_t* dst, int T
     hipStream_t s = (hipStream_t)stream;
     if (fmt->bits == 8) hipLaunchKernelGGL((yuv_thumb_kernel<1>), grid, block, 0, s, src, dst, H, W, hb, wb, fb);
     else hipLaunchKernelGGL((yuv_thumb_kernel<2>), grid, block, 0, s, src, dst, H, W, hb, wb, fb);
+    return sn_check_launch();
+}
+
+int sn_yuv_noise_hist(const uint8_t* src, const sn_yuv_fmt* fmt, uint32_t* dst, int lo, int hi, int T, int H, int W, void* stream) {
+    sn_clear_error();
+    if (!src || !dst || !fmt || (fmt->bits != 8 && fmt->bits != 10) || fmt->chroma < 0 || fmt->chroma > 2 || T < 1 || T > 65535 || H < 1 || W < 1 || lo > hi) return SN_EINVAL;
+    if (((uintptr_t)dst & 3) || (fmt->bits == 10 && ((uintptr_t)src & 1))) return SN_EINVAL;
+    const size_t fb = frame_bytes_of(fmt, H, W);
+    const int nbins = fmt->bits == 8 ? NoiseK<1>::NB : NoiseK<2>::NB;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(dst, 0, (size_t)T * nbins * sizeof(uint32_t), s) != hipSuccess) return sn_check_launch();      // dst is overwritten, not added to
+    const int hb = H / 2, wb = W / 2, ux = (wb + 3) / 4;
+    if (hb < 1 || wb < 1) return sn_check_launch();                        // no whole block: all-zero histograms
+    const long long units = (long long)ux * hb;
+    if (units > 0x7fffffffLL - 1024 * 256) return SN_EINVAL;
+    // about 8 units (32 blocks) per lane: the zeroing, the sum of the copies and the flush are paid once per 8192 blocks and a 720p frame is 29 workgroups
+    const int gx = (int)((units + 2047) / 2048 < 1024 ? (units + 2047) / 2048 : 1024);
+    const dim3 block(256), grid(gx, T);
+    if (fmt->bits == 8) hipLaunchKernelGGL((yuv_noise_hist_kernel<1>), grid, block, 0, s, src, dst, lo, hi, W, hb, wb, ux, fb);
+    else hipLaunchKernelGGL((yuv_noise_hist_kernel<2>), grid, block, 0, s, src, dst, lo, hi, W, hb, wb, ux, fb);
     return sn_check_launch();
 }
 

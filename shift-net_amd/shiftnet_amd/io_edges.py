@@ -5,6 +5,8 @@
 ``ingest_yuv`` / ``egress_yuv``: planar Y'CbCr payloads as a Y4M stream carries them (csrc/sn_yuv.hip) <-> RGB tensors, for the video
                restorer (shiftnet_amd/restore.py); 1.5 bytes per pixel cross PCIe for 8-bit 4:2:0;
 ``thumb_yuv``  : the same payloads -> uint16 sums of the luma codes of every 8 x 8 block, for the scene-cut detector (shiftnet_amd/scenes.py);
+``noise_hist_yuv``: the same payloads -> uint32 histograms of |a - b - c + d| over the 2 x 2 luma blocks, for the blind noise estimate
+               (shiftnet_amd/noise.py);
 ``egress_u8``  == the per-frame ``clamp(0,1) * 255`` -> skimage PSNR(data_range=255) against the uint8 ground truth
                (:139-143) and the rounded uint8 frame cv2.imwrite would store (:152).
 """
@@ -121,4 +123,23 @@ def thumb_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, out: Op
     with torch.cuda.device(payload_u8.device):
         L.check(L.load().sn_yuv_thumb(payload_u8.data_ptr(), fmt, y.data_ptr(), T, H, W,
                                       torch.cuda.current_stream(payload_u8.device).cuda_stream), "sn_yuv_thumb")
+    return y
+
+
+def noise_hist_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lo: Optional[int] = None, hi: Optional[int] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """payload_u8: [T, frame_bytes] uint8 on a HIP device (only the luma plane of each payload is read) -> uint32 [T, 2 (2^bits - 1) + 1]:
+    per frame the counts of v = |a - b - c + d| over the non-overlapping 2 x 2 luma blocks whose four codes lie strictly between ``lo`` and
+    ``hi`` (default: the format's black and white codes, noise.clip_codes).  ``out``: a tensor of that shape to overwrite."""
+    from .noise import clip_codes, nbins
+    fb = fmt.frame_bytes(H, W)
+    assert payload_u8.dtype == torch.uint8 and payload_u8.is_cuda and payload_u8.dim() == 2 and payload_u8.shape[1] == fb and payload_u8.is_contiguous()
+    T, nb = payload_u8.shape[0], nbins(fmt.bits)
+    dlo, dhi = clip_codes(fmt.bits, fmt.range)
+    lo, hi = dlo if lo is None else int(lo), dhi if hi is None else int(hi)
+    y = out if out is not None else torch.empty((T, nb), dtype=torch.uint32, device=payload_u8.device)
+    assert tuple(y.shape) == (T, nb) and y.dtype == torch.uint32 and y.is_contiguous() and y.device == payload_u8.device
+    with torch.cuda.device(payload_u8.device):
+        L.check(L.load().sn_yuv_noise_hist(payload_u8.data_ptr(), fmt, y.data_ptr(), lo, hi, T, H, W,
+                                           torch.cuda.current_stream(payload_u8.device).cuda_stream), "sn_yuv_noise_hist")
     return y

@@ -1,0 +1,134 @@
+"""Blind estimate of the noise level of footage, for the denoise variants of the video restorer (numpy only, no torch).
+
+The histograms are what ``sn_yuv_noise_hist`` (csrc/sn_yuv.hip) writes: per frame, over the luma plane, the counts of
+``v = |a - b - c + d|`` of every non-overlapping 2 x 2 block whose four codes lie strictly between the format's black and white codes
+(clipped pixels carry less noise than the footage has).  ``v`` is twice the Haar HH coefficient of the block: a smooth image contributes
+nothing to it, and white noise of standard deviation s on the codes gives it the variance ``4 s^2 + 1/3`` (the 1/3 is the rounding of four
+codes, 4 / 12).  The median of ``|v|`` is robust against the edges and texture that do reach HH:
+
+  med   = the median of v from the cumulative histogram, linear inside the bin (bin 0 covers [0, 0.5), bin k >= 1 [k - 0.5, k + 0.5));
+  var   = max((med / 0.6744897501960817)^2 - 1/3, 0);  sigma_Y = sqrt(var) / 2          (luma code units)
+  sigma = sigma_Y / (g s),  g = sqrt(Kr^2 + Kg^2 + Kb^2),  s = 219 2^(bits-8) / 255 (limited) or (2^bits - 1) / 255 (full):
+
+the standard deviation of i.i.d. noise on 8-bit R'G'B', which is what the networks were trained with (``noise_map = sigma / 255``).
+A window's sigma is the median of its input frames' (as fed: reflected duplicates count), clamped.  Everything here is float64 on exact
+integers, so the device's histograms and a host restatement of them give the same floats.
+
+A heuristic, checked on synthetic clips only.  It assumes white Gaussian noise: compression makes noise non-white and the estimate then reads
+low; pixel-scale texture adds to it in quadrature; at sigma >= 40 the clipping of R'G'B' to [0, 1] makes it read low by construction.
+"""
+from __future__ import annotations
+
+import math
+from typing import Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+MAD_TO_SIGMA = 0.6744897501960817          # the median of |x| for x ~ N(0, 1)
+CLAMP = (0.0, 50.0)                        # the range of noise levels upstream evaluates
+BT601, BT709 = 0, 1                        # the codes of sn_yuv_fmt.matrix
+LIMITED, FULL = 0, 1                       # ... and .range
+
+
+def nbins(bits: int) -> int:
+    """Bins per frame of sn_yuv_noise_hist: v = 0 .. 2 (2^bits - 1)."""
+    return 2 * ((1 << bits) - 1) + 1
+
+
+def clip_codes(bits: int, range_: int) -> Tuple[int, int]:
+    """(lo, hi) of sn_yuv_noise_hist: the format's black and white luma codes; a block counts iff its four codes lie strictly between."""
+    s = 1 << (bits - 8)
+    return (0, (1 << bits) - 1) if range_ == FULL else (16 * s, 235 * s)
+
+
+def luma_gain(matrix: int) -> float:
+    """sqrt(Kr^2 + Kg^2 + Kb^2): the standard deviation of Y' for unit i.i.d. noise on R', G', B'."""
+    kr, kb = (0.2126, 0.0722) if matrix == BT709 else (0.299, 0.114)
+    kg = 1.0 - kr - kb
+    return math.sqrt(kr * kr + kg * kg + kb * kb)
+
+
+def code_scale(bits: int, range_: int) -> float:
+    """Luma codes per 8-bit R'G'B' code."""
+    return ((1 << bits) - 1) / 255.0 if range_ == FULL else 219.0 * (1 << (bits - 8)) / 255.0
+
+
+def hist_median(hist) -> Optional[float]:
+    """The median of v of one histogram, or None if it is empty."""
+    h = np.asarray(hist).reshape(-1).astype(np.int64)
+    cum = np.cumsum(h)                                       # exact integers
+    n = int(cum[-1]) if len(cum) else 0
+    if n == 0:
+        return None
+    half = n / 2.0
+    k = int(np.searchsorted(cum, half, side="left"))         # the first bin whose cumulative count reaches N / 2 (hist[k] > 0 there: half > 0)
+    before = int(cum[k - 1]) if k else 0
+    left, width = (0.0, 0.5) if k == 0 else (k - 0.5, 1.0)
+    return left + width * (half - before) / int(h[k])
+
+
+def sigma_luma(hist) -> Optional[float]:
+    """sigma_Y of one frame in luma code units, or None if no block counted."""
+    med = hist_median(hist)
+    if med is None:
+        return None
+    q = med / MAD_TO_SIGMA
+    var = q * q - 1.0 / 3.0
+    return math.sqrt(var) / 2.0 if var > 0.0 else 0.0
+
+
+def frame_sigma(hist, bits: int, matrix: int, range_: int) -> Optional[float]:
+    """One histogram -> the sigma of i.i.d. noise on 8-bit R'G'B' that explains it, or None if no block counted."""
+    s = sigma_luma(hist)
+    return None if s is None else s / (luma_gain(matrix) * code_scale(bits, range_))
+
+
+def check_clamp(clamp: Sequence[float]) -> Tuple[float, float]:
+    lo, hi = (float(c) for c in clamp)
+    if not (0.0 <= lo <= hi):                                # refuses NaN as well
+        raise ValueError(f"sigma_clamp must be (lo, hi) with 0 <= lo <= hi, got {tuple(clamp)!r}")
+    return lo, hi
+
+
+def window_sigma(frame_sigmas: Iterable[Optional[float]], clamp: Sequence[float] = CLAMP) -> float:
+    """The median of the frames' sigmas (frames without an estimate left out; 0 if none has one), clamped."""
+    lo, hi = check_clamp(clamp)
+    v = [s for s in frame_sigmas if s is not None]
+    s = float(np.median(np.asarray(v, np.float64))) if v else 0.0
+    return min(max(s, lo), hi)
+
+
+def check_sigmas(sigmas: Iterable[float]) -> List[float]:
+    """A per-window list: finite numbers >= 0."""
+    out: List[float] = []
+    for s in sigmas:
+        if isinstance(s, (bool, str)) or not math.isfinite(float(s)) or float(s) < 0.0:
+            raise ValueError(f"a sigma must be a finite number >= 0, got {s!r}")
+        out.append(float(s))
+    return out
+
+
+def parse_sigmas(text: str) -> List[float]:
+    """One sigma per line, one per window in order; '#' starts a comment, blank lines are skipped.  Anything else raises ValueError naming
+    the line."""
+    out: List[float] = []
+    for no, line in enumerate(text.splitlines(), 1):
+        word = line.split("#", 1)[0].strip()
+        if not word:
+            continue
+        try:
+            try:
+                val = float(word)
+            except ValueError:
+                raise ValueError("not a number") from None
+            out += check_sigmas([val])
+        except ValueError as e:
+            raise ValueError(f"line {no}: {line.strip()!r}: {e}") from None
+    return out
+
+
+def format_sigmas(sigmas: Iterable[float], how: str = "") -> str:
+    """The text ``parse_sigmas`` reads back to the same floats (repr round-trips float64)."""
+    sigmas = [float(s) for s in sigmas]
+    head = f"# noise level per window (sigma of 8-bit R'G'B' codes), in the order the windows are restored; {len(sigmas)} window{'' if len(sigmas) == 1 else 's'}"
+    return head + (f"; {how}" if how else "") + "\n" + "".join(f"{s!r}\n" for s in sigmas)

@@ -13,6 +13,10 @@ last frames of one shot would be restored with features of the next.  With scene
 are clips of their own: windows restart at every scene start and reflect about the scene's first and last frame, and the bytes written are
 those of restoring every scene as a separate video.  The cuts are listed by the caller or found from luma thumbnails made on the device
 (``sn_yuv_thumb``, shiftnet_amd/scenes.py).
+
+Noise level (``sigma``, denoise variants): a number, a list with one number per window, or ``"auto"``: a blind estimate per window from
+histograms of the luma's 2 x 2 Haar HH coefficient, made on the device from the payloads the window has uploaded anyway
+(``sn_yuv_noise_hist``, shiftnet_amd/noise.py).
 """
 from __future__ import annotations
 
@@ -276,7 +280,12 @@ class VideoRestorer:
     """``VideoRestorer(net, one_len, sigma=None).restore(frames, fmt, height, width)`` -> iterator of restored payloads, one per input frame.
 
     net: a GShiftNet of shiftnet_amd.arch on a HIP device (eval mode, any dtype).  sigma: the noise level in 8-bit code values for the
-    denoise variants (noise_map = sigma / 255 everywhere; no noise is added and the frame is not cut into quadrants).
+    denoise variants (noise_map = sigma / 255 everywhere; no noise is added and the frame is not cut into quadrants): a number; a sequence of
+    numbers, one per window in the order the windows are restored (running out is a ValueError that names the window); or ``"auto"`` -- per window
+    the median over its input frames of a blind estimate from the luma plane (noise.py; a heuristic that assumes white Gaussian noise), clamped to
+    ``sigma_clamp``.  The deblur variants ignore a number and refuse the other two.  Once ``restore()`` has been exhausted
+    ``stats["window_sigma"]`` lists the sigma of every window (denoise variants), ``stats["window_frame_sigma"]`` the estimates of every window's
+    input frames (auto only; None where no block of a frame counted) and ``stats["noise_launches"]`` the ``sn_yuv_noise_hist`` launches.
     pipeline: read / copy / ingest window k + 1 on a side stream and copy back / hand out window k - 1 while window k runs; False runs
     the same steps one after the other.  Both give identical bytes.
     scene_cuts: None -- the stream is one clip; ``"auto"`` -- find the cuts from luma thumbnails made on the device (scenes.py: frame t starts a
@@ -285,8 +294,8 @@ class VideoRestorer:
     are those of restoring each scene as a separate video.  Once ``restore()`` has been exhausted ``stats["cuts"]`` lists the scene starts used,
     ``stats["cut_measure"]`` the m[t] of every frame (auto only; m[0] = 0.0) and ``stats["cuts_ignored"]`` the listed cuts at or beyond the end."""
 
-    def __init__(self, net, one_len: int, sigma: Optional[float] = None, pipeline: bool = True, scene_cuts=None,
-                 cut_threshold: float = 4.0, cut_ratio: float = 2.5) -> None:
+    def __init__(self, net, one_len: int, sigma=None, pipeline: bool = True, scene_cuts=None,
+                 cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0)) -> None:
         import torch
         self.torch = torch
         self.net, self.one_len, self.pipeline = net, int(one_len), bool(pipeline)
@@ -303,13 +312,28 @@ class VideoRestorer:
         self.V = net.V
         if self.V.denoise and sigma is None:
             raise ValueError("sigma is required by the denoise variants (the noise level of the footage, in 8-bit code values)")
-        self.sigma = None if sigma is None else float(sigma)
+        from .noise import check_clamp, check_sigmas
+        self.sigma_clamp = check_clamp(sigma_clamp)
+        # sigma_mode: "fixed" (a number: the code path without any of the rest), "auto", "list"
+        self.sigma, self.sigma_list, self.sigma_mode = None, None, "fixed"
+        if isinstance(sigma, str):
+            if sigma != "auto":
+                raise ValueError(f"sigma must be a number, 'auto' or a sequence of numbers, got {sigma!r}")
+            self.sigma_mode = "auto"
+        elif sigma is not None and hasattr(sigma, "__iter__"):
+            self.sigma_list, self.sigma_mode = check_sigmas(sigma), "list"
+        elif sigma is not None:
+            self.sigma = float(sigma)
+        if self.sigma_mode != "fixed" and not self.V.denoise:
+            raise ValueError(f"sigma={'auto' if self.sigma_mode == 'auto' else 'a per-window list'!r} is for the denoise variants; {type(net).__name__} "
+                             "of a deblur variant takes no noise level")
         p = next(net.parameters())
         self.dev, self.dtype = p.device, p.dtype
         if self.dev.type != "cuda":
             raise ValueError("VideoRestorer needs the module on a HIP device")
         self.stats = {"frames": 0, "windows": 0, "forward_s": 0.0, "window_forward_ms": []}
         self._shape = None
+        self._wsig, self._wfsig, self._noise_launches = [], [], 0
 
     # -- per-shape state: two slots of staging and device buffers, sized for the largest window -------------------------------------
     def _prepare(self, fmt, h: int, w: int) -> None:
@@ -334,11 +358,18 @@ class VideoRestorer:
         ev = lambda: [torch.cuda.Event() for _ in range(2)]      # noqa: E731
         self.ev_h2d, self.ev_ready, self.ev_done, self.ev_d2h = ev(), ev(), ev(), ev()
         self.used = [False, False]
+        if self.sigma_mode == "auto":                             # per slot: the window's histograms on the device and in pinned memory
+            from .noise import clip_codes, nbins
+            self.nb = nbins(fmt.bits)
+            self.noise_lo, self.noise_hi = clip_codes(fmt.bits, fmt.range)
+            self.dev_hist = [torch.empty((tin, self.nb), dtype=torch.uint32, device=dev) for _ in range(2)]
+            self.pin_hist = [torch.empty((tin, self.nb), dtype=torch.uint32).pin_memory() for _ in range(2)]
+            self.ev_noise = ev()
 
     # -- the steps of one window; slot = k % 2 -------------------------------------------------------------------------------------
     def _stage(self, slot: int, frames: Sequence[np.ndarray]) -> int:
         """Host frames -> pinned slot -> device -> RGB tensors, on the side stream."""
-        from .io_edges import ingest_yuv
+        from .io_edges import ingest_yuv, noise_hist_yuv
         torch = self.torch
         t = len(frames)
         if self.used[slot]:
@@ -351,17 +382,44 @@ class VideoRestorer:
                 self.s_in.wait_event(self.ev_done[slot])         # the forward that last read this slot's tensors has finished
             self.dev_in[slot][:t].copy_(self.pin_in[slot][:t], non_blocking=True)
             self.ev_h2d[slot].record(self.s_in)
+            if self.sigma_mode == "auto":
+                # the histograms of the payloads just uploaded, ahead of the ingest so that they are on the host long before _run asks.  The
+                # pinned slot is free: _run read it on the host before this slot was handed back to the stager
+                noise_hist_yuv(self.dev_in[slot][:t], self.fmt, self.h, self.w, self.noise_lo, self.noise_hi, out=self.dev_hist[slot][:t])
+                self.pin_hist[slot][:t].copy_(self.dev_hist[slot][:t], non_blocking=True)
+                self.ev_noise[slot].record(self.s_in)
+                self._noise_launches += 1
             ingest_yuv(self.dev_in[slot][:t], self.fmt, self.h, self.w, self.hp, self.wp, self.dtype, out=self.x[slot][:, :t])
             if self.x32[slot] is not None:
                 ingest_yuv(self.dev_in[slot][:t], self.fmt, self.h, self.w, self.hp, self.wp, torch.float32, out=self.x32[slot][:, :t])
             self.ev_ready[slot].record(self.s_in)
         return t
 
+    def _window_sigma(self, slot: int, t: int) -> float:
+        """The noise level of the window about to run (denoise variants); windows run in the order they are handed out."""
+        k = len(self._wsig)
+        if self.sigma_mode == "auto":
+            from .noise import frame_sigma, window_sigma
+            self.ev_noise[slot].synchronize()                    # the copy of this slot's histograms, on the side stream: not the device, not main
+            hist = self.pin_hist[slot][:t].numpy()
+            per = [frame_sigma(hist[i], self.fmt.bits, self.fmt.matrix, self.fmt.range) for i in range(t)]
+            self._wfsig.append(per)
+            sigma = window_sigma(per, self.sigma_clamp)
+        elif self.sigma_mode == "list":
+            if k >= len(self.sigma_list):
+                raise ValueError(f"sigma lists {len(self.sigma_list)} window{'' if len(self.sigma_list) == 1 else 's'}, window {k} has no entry")
+            sigma = self.sigma_list[k]
+        else:
+            sigma = self.sigma
+        self._wsig.append(sigma)
+        return sigma
+
     def _run(self, slot: int, t: int, main) -> int:
         """Forward + egress on the main stream, copy back on the output stream."""
         from .io_edges import egress_yuv
         torch = self.torch
         n = t - PAST - FUTURE
+        sigma = self._window_sigma(slot, t) if self.V.denoise else None
         with torch.cuda.stream(main), torch.no_grad():
             main.wait_event(self.ev_ready[slot])
             if self.used[slot]:
@@ -373,7 +431,7 @@ class VideoRestorer:
             if self.x32[slot] is not None:
                 kw["shortcut"] = self.x32[slot][:, :t]
             if self.V.denoise:
-                nm = torch.full((1, 1, 1, 1, 1), self.sigma / 255.0, dtype=self.dtype, device=self.dev).expand(1, t, 1, self.hp, self.wp)
+                nm = torch.full((1, 1, 1, 1, 1), sigma / 255.0, dtype=self.dtype, device=self.dev).expand(1, t, 1, self.hp, self.wp)
                 out = self.net.forward_fp32_out(x, nm, **kw)
             else:
                 out = self.net.forward_fp32_out(x, **kw)
@@ -397,6 +455,11 @@ class VideoRestorer:
         self.stats["window_forward_ms"] = ms
         self.stats["forward_s"] = sum(ms) / 1e3
         self.stats["windows"] = len(ms)
+        self.stats["noise_launches"] = self._noise_launches
+        if self.V.denoise:
+            self.stats["window_sigma"] = list(self._wsig)
+            if self.sigma_mode == "auto":
+                self.stats["window_frame_sigma"] = [list(p) for p in self._wfsig]
         src = self._src
         if isinstance(src, _SceneFrames):                        # its thread has ended: the stream has been read to its end
             self.stats["cuts"] = list(src.cuts)
@@ -427,6 +490,7 @@ class VideoRestorer:
         self.used = [False, False]
         self.stats = {"frames": 0, "windows": 0, "forward_s": 0.0, "window_forward_ms": []}
         self._src = None
+        self._wsig, self._wfsig, self._noise_launches = [], [], 0
         main = torch.cuda.current_stream(self.dev)
 
         def checked(it):
@@ -509,13 +573,25 @@ class VideoRestorer:
 
 
 # ---- command line -------------------------------------------------------------------------------------------------------------------
+def sigma_arg(word: str):
+    """--sigma: a number stays the float it always was; 'auto'; anything else names a file with one sigma per window."""
+    try:
+        return float(word)
+    except ValueError:
+        return word
+
+
 def make_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Restore a Y4M video with Shift-Net on the MI355X: same frames, size and pixel format out")
     ap.add_argument("--variant", choices=list(VARIANTS), required=True)
     ap.add_argument("--checkpoint", required=True, help="checkpoint path, or 'synthetic' for the deterministic synthetic weights")
     ap.add_argument("--dtype", choices=["fp32", "fp16", "bf16"], default="bf16")
     ap.add_argument("--one_len", type=int, default=16, help="frames restored per window")
-    ap.add_argument("--sigma", type=float, default=None, help="noise level (8-bit code values), required by the denoise variants")
+    ap.add_argument("--sigma", type=sigma_arg, default=None, metavar="{NUMBER,auto,FILE}",
+                    help="noise level (8-bit code values), required by the denoise variants: a number; 'auto' estimates it per window on the device "
+                         "(a heuristic that assumes white Gaussian noise); FILE lists one sigma per window, one per line ('#' comments)")
+    ap.add_argument("--sigma_clamp", type=float, nargs=2, default=(0.0, 50.0), metavar=("LO", "HI"), help="auto: the estimate is clamped to this range")
+    ap.add_argument("--sigma_out", default=None, metavar="FILE", help="write the sigma that every window was restored with, in the format --sigma FILE reads")
     ap.add_argument("--matrix", choices=["bt601", "bt709"], default=None, help="default: bt709 when H >= 720, else bt601")
     ap.add_argument("--range", choices=["limited", "full"], default=None, help="default: the stream's XCOLORRANGE, else limited")
     ap.add_argument("--no_pipeline", action="store_true", help="run read / copy / forward / write one after the other")
@@ -553,6 +629,24 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     if "denoise" in a.variant and a.sigma is None:
         ap.error("--sigma is required by the denoise variants")
     log = lambda s: (sys.stderr.write(s + "\n"), sys.stderr.flush())      # noqa: E731
+    sigma, sigma_how = a.sigma, "fixed"
+    if isinstance(sigma, str):
+        if "denoise" not in a.variant:
+            ap.error(f"--sigma {sigma} is for the denoise variants")
+        if sigma == "auto":
+            sigma_how = "auto"
+        else:
+            from .noise import parse_sigmas
+            try:
+                with open(sigma, "r") as fh:
+                    sigma, sigma_how = parse_sigmas(fh.read()), "listed"
+            except (OSError, ValueError) as e:
+                ap.error(f"--sigma {a.sigma}: {e}")
+    try:
+        from .noise import check_clamp
+        check_clamp(a.sigma_clamp)
+    except ValueError as e:
+        ap.error(f"--sigma_clamp: {e}")
     if a.scene_cuts == "off":
         cuts = None
     elif a.scene_cuts == "auto":
@@ -576,8 +670,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         fmt = yuv_fmt(hd.bits, hd.chroma_code, L.SN_YUV_BT709 if matrix == "bt709" else L.SN_YUV_BT601,
                       L.SN_YUV_FULL if rng == "full" else L.SN_YUV_LIMITED)
         net = load_net(a.variant, a.checkpoint, a.dtype)
-        vr = VideoRestorer(net, a.one_len, sigma=a.sigma, pipeline=not a.no_pipeline, scene_cuts=cuts, cut_threshold=a.cut_threshold,
-                           cut_ratio=a.cut_ratio)
+        vr = VideoRestorer(net, a.one_len, sigma=sigma, pipeline=not a.no_pipeline, scene_cuts=cuts, cut_threshold=a.cut_threshold,
+                           cut_ratio=a.cut_ratio, sigma_clamp=a.sigma_clamp)
         wr = Y4MWriter(fout, hd)
         t0 = time.perf_counter()
         n = 0
@@ -599,6 +693,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         log(f"done: {n} frames in {dt:.2f} s, {n / dt if dt > 0 else 0.0:.2f} frames/s end to end, "
             f"{n / fwd if fwd > 0 else 0.0:.2f} frames/s forward only, {len(used) + 1} scene{'s' if used else ''}"
             f"{'' if cuts is None else (' (cuts found)' if cuts == 'auto' else ' (cuts listed)')}")
+        ws = vr.stats.get("window_sigma")
+        if a.sigma_out is not None:
+            from .noise import format_sigmas
+            with open(a.sigma_out, "w") as fh:
+                fh.write(format_sigmas(ws or [], sigma_how))
+        if ws:
+            log(f"sigma ({sigma_how}{', clamped to [%g, %g]' % tuple(a.sigma_clamp) if sigma_how == 'auto' else ''}): "
+                f"min {min(ws):.2f} / median {float(np.median(ws)):.2f} / max {max(ws):.2f} over {len(ws)} window{'' if len(ws) == 1 else 's'}")
     finally:
         if fin is not sys.stdin.buffer:
             fin.close()
