@@ -495,6 +495,40 @@ int sn_yuv_thumb(const uint8_t* src, const sn_yuv_fmt* fmt, uint16_t* dst, int T
  * aligned, src at an odd address at 10 bit. */
 int sn_yuv_noise_hist(const uint8_t* src, const sn_yuv_fmt* fmt, uint32_t* dst, int lo, int hi, int T, int H, int W, void* stream);
 
+/* ---- the active picture of a letterboxed / pillarboxed stream (new symbols and one new struct, SN_ABI_VERSION stays 20) ------------------
+ * A picture rectangle is (x0, y0, w, h) in luma samples of the H x W stream: 0 <= x0, 1 <= w, x0 + w <= W, and the same for y.  At 4:2:0
+ * x0 and y0 are even, w is even unless x0 + w == W and h is even unless y0 + h == H, so that no chroma sample is shared between the inside
+ * and the outside; at 4:4:4 any integers are legal.  "The cropped stream" is the video whose planes are the rectangle cut out of every plane:
+ * luma rows y0 .. y0 + h - 1, columns x0 .. x0 + w - 1; 4:2:0 chroma rows y0/2 .. y0/2 + ceil(h/2) - 1, columns x0/2 .. x0/2 + ceil(w/2) - 1.
+ * The three _rect entry points launch the kernels of the entry points above with the rectangle's origin and the stream's row pitches (H, W
+ * give the pitches and frame_bytes, payload to payload); SN_EINVAL as theirs, and for a null or illegal rectangle.
+ *
+ * sn_ingest_yuv_rect: dst:[T][3][Hp][Wp], Hp >= rect.h, Wp >= rect.w, is bit for bit what sn_ingest_yuv writes for the cropped stream (H = rect.h,
+ *   W = rect.w): the chroma neighbours clamp to the rectangle's chroma planes, never to the stream's -- no bar sample reaches the picture --
+ *   and the padding repeats the rectangle's last row and column.
+ * sn_egress_yuv_rect: out:[T][3][Hp][Wp]; the samples of the rectangle, luma and chroma, of the T payloads of the STREAM's size at dst are written
+ *   with what sn_egress_yuv writes for the cropped stream (the 4:2:0 filters clamp to the rect.h x rect.w crop of out), and nothing else is.
+ * sn_yuv_noise_hist_rect: the histograms of sn_yuv_noise_hist over the rectangle's luma, the 2 x 2 block grid anchored at (x0, y0): block
+ *   (i, j), i < rect.h / 2, j < rect.w / 2, is Y[y0 + 2i .. y0 + 2i + 1][x0 + 2j .. x0 + 2j + 1].
+ * The wide loads and stores test the address itself: a rectangle with x0 % 16 == 0 in a stream with W % 16 == 0 keeps them, any other takes the
+ * element-wise path with the same arithmetic. */
+typedef struct sn_yuv_rect { int x0, y0, w, h; } sn_yuv_rect;
+int sn_ingest_yuv_rect(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, void* dst, int dst_dtype, int T, int H, int W, int Hp, int Wp,
+                       void* stream);
+int sn_egress_yuv_rect(const void* out, int out_dtype, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint8_t* dst, int T, int H, int W, int Hp, int Wp,
+                       void* stream);
+int sn_yuv_noise_hist_rect(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint32_t* dst, int lo, int hi, int T, int H, int W,
+                           void* stream);
+
+/* sn_yuv_rowcol_sums: what the letterbox rule of the video restorer (shiftnet_amd/picture.py) looks at.  src: T payloads as sn_yuv_thumb takes
+ * them; only the luma plane is read and of fmt only bits decides anything.
+ *   rows[t][y] = sum over x < W of Y[y][x],  cols[t][x] = sum over y < H of Y[y][x]      (uint32 [T][H] and [T][W])
+ * exact integer sums (65535 x 1023 < 2^32).  Both arrays are OVERWRITTEN, never added to, and nothing else is written.  Integer atomics: the
+ * result is the same for every launch geometry and schedule.
+ * SN_EINVAL before anything is launched: null pointers, bits not 8 / 10, unknown chroma code, T, H or W < 1, H or W > 65535, rows or cols not
+ * 4-byte aligned, src at an odd address at 10 bit. */
+int sn_yuv_rowcol_sums(const uint8_t* src, const sn_yuv_fmt* fmt, uint32_t* rows, uint32_t* cols, int T, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,11 @@
 //   sn_yuv_noise_hist : T payloads -> [T][2 (2^bits - 1) + 1] uint32 histograms of |a - b - c + d| over the 2 x 2 luma blocks whose four codes lie
 //                   strictly between lo and hi (the blind noise estimate of shiftnet_amd/noise.py is computed from these on the host); integer
 //                   arithmetic, the chroma planes are not read.
+//   sn_yuv_rowcol_sums : T payloads -> [T][H] and [T][W] uint32 sums of the luma codes of every row and every column (the letterbox rule of
+//                   shiftnet_amd/picture.py is evaluated on these on the host); integer arithmetic, the chroma planes are not read.
+//   sn_ingest_yuv_rect / sn_egress_yuv_rect / sn_yuv_noise_hist_rect : the first, second and fourth restricted to a picture rectangle of the
+//                   stream.  They are the same kernels: every kernel sees "its frame" as h x w samples whose planes have a row pitch and a
+//                   first sample of their own (YuvGeo); the entry points without _rect pass the whole frame.
 //
 // The arithmetic (order of operations, constants) is stated in include/shiftnet_hip.h and restated in float32 by tests/yuv_ref.py,
 // which these kernels equal bit for bit.  Every float product and sum is rounded separately (contraction is off for this file: no
@@ -29,6 +34,17 @@ struct YuvK {
     // egress: Y' = (kr*R + kg*G) + kb*B, Cb = (B - Y')*cu, Cr = (R - Y')*cv; code = rint(off + scale * value)
     float kr, kg, kb, cu, cv, ys, yo, cs, co;
     int yoff, coff, ylo, yhi, clo, chi;
+};
+
+// The picture a launch works on, inside payloads of a larger (or the same) stream: h x w luma samples, planes with the stream's row pitches.
+// Everything that clamps (chroma neighbours, edge replication, the egress filters) clamps to h x w and its chroma planes: the kernels compute
+// what they would on the cropped stream.  The wide loads and stores test the address itself, so a picture whose rows are not aligned takes
+// the element-wise path on its own.
+struct YuvGeo {
+    int h, w;                   // the picture, in luma samples
+    int py, pc;                 // row pitch of the luma and of the chroma planes, in samples
+    size_t oy, ou, ov;          // byte offset of the picture's first Y / U / V sample from the start of a payload
+    size_t frame_bytes;         // payload to payload
 };
 
 __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
@@ -142,10 +158,10 @@ template <int CH> __device__ __forceinline__ void yuv_to_rgb(const YuvK& K, int 
     *b = clamp01(addr(yy, mulr(K.cbu, ud)));
 }
 
-template <int ESZ, int CH> __device__ __forceinline__ int chroma_num(const uint8_t* p, int cw, int ch, int ye, int xe) {
+template <int ESZ, int CH> __device__ __forceinline__ int chroma_num(const uint8_t* p, int pc, int cw, int ch, int ye, int xe) {
     const int j = ye >> 1, i = xe >> 1;
     const int jn = imin(imax(j + ((ye & 1) ? 1 : -1), 0), ch - 1);
-    const size_t rj = (size_t)j * cw, rn = (size_t)jn * cw;
+    const size_t rj = (size_t)j * pc, rn = (size_t)jn * pc;
     if (CH == SN_YUV_420_CENTER) {
         const int in = imin(imax(i + ((xe & 1) ? 1 : -1), 0), cw - 1);
         return 3 * (3 * ld1<ESZ>(p, rj + i) + ld1<ESZ>(p, rn + i)) + (3 * ld1<ESZ>(p, rj + in) + ld1<ESZ>(p, rn + in));
@@ -158,25 +174,27 @@ template <int ESZ, int CH> __device__ __forceinline__ int chroma_num(const uint8
 
 template <int ESZ, int CH>
 __global__ __launch_bounds__(256) void ingest_yuv_kernel(const uint8_t* __restrict__ src, void* __restrict__ dst, int dt, const YuvK K,
-                                                       int H, int W, int Hp, int Wp, size_t frame_bytes, int dst_vec) {
+                                                       const YuvGeo G, int Hp, int Wp, int dst_vec) {
     const int t = blockIdx.z;
     const int x0 = (blockIdx.x * 32 + threadIdx.x) * 8, y0 = (blockIdx.y * 8 + threadIdx.y) * 2;
     if (x0 >= Wp || y0 >= Hp) return;
+    const int H = G.h, W = G.w, py = G.py, pc = G.pc;
     const int cw = CH == SN_YUV_444 ? W : (W + 1) >> 1, ch = CH == SN_YUV_444 ? H : (H + 1) >> 1;
-    const uint8_t* yp = src + (size_t)t * frame_bytes;
-    const uint8_t* up = yp + (size_t)H * W * ESZ;
-    const uint8_t* vp = up + (size_t)cw * ch * ESZ;
+    const uint8_t* base = src + (size_t)t * G.frame_bytes;
+    const uint8_t* yp = base + G.oy;
+    const uint8_t* up = base + G.ou;
+    const uint8_t* vp = base + G.ov;
     float rgb[3][2][8];
     if (x0 + 8 <= W && y0 + 2 <= H) {                      // interior: whole blocks, wide loads
         int Y[2][8];
 #pragma unroll
-        for (int r = 0; r < 2; ++r) ldn<ESZ, 8>(yp, (size_t)(y0 + r) * W + x0, Y[r]);
+        for (int r = 0; r < 2; ++r) ldn<ESZ, 8>(yp, (size_t)(y0 + r) * py + x0, Y[r]);
         if (CH == SN_YUV_444) {
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
                 int U[8], V[8];
-                ldn<ESZ, 8>(up, (size_t)(y0 + r) * W + x0, U);
-                ldn<ESZ, 8>(vp, (size_t)(y0 + r) * W + x0, V);
+                ldn<ESZ, 8>(up, (size_t)(y0 + r) * pc + x0, U);
+                ldn<ESZ, 8>(vp, (size_t)(y0 + r) * pc + x0, V);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) yuv_to_rgb<CH>(K, Y[r][k], U[k], V[k], &rgb[0][r][k], &rgb[1][r][k], &rgb[2][r][k]);
             }
@@ -190,7 +208,7 @@ __global__ __launch_bounds__(256) void ingest_yuv_kernel(const uint8_t* __restri
                 int win[3][6];                              // chroma columns c0 - 1 .. c0 + 4 (clamped) of rows j - 1, j, j + 1 (clamped)
 #pragma unroll
                 for (int q = 0; q < 3; ++q) {
-                    const size_t row = (size_t)jr[q] * cw;
+                    const size_t row = (size_t)jr[q] * pc;
                     ldn<ESZ, 4>(cp, row + c0, &win[q][1]);
                     win[q][0] = CH == SN_YUV_420_CENTER ? ld1<ESZ>(cp, row + imax(c0 - 1, 0)) : 0;
                     win[q][5] = ld1<ESZ>(cp, row + imin(c0 + 4, cw - 1));
@@ -218,10 +236,10 @@ __global__ __launch_bounds__(256) void ingest_yuv_kernel(const uint8_t* __restri
             const int ye = imin(y0 + r, H - 1);
             for (int k = 0; k < 8; ++k) {
                 const int xe = imin(x0 + k, W - 1);
-                const int y = ld1<ESZ>(yp, (size_t)ye * W + xe);
+                const int y = ld1<ESZ>(yp, (size_t)ye * py + xe);
                 int un, vn;
-                if (CH == SN_YUV_444) { un = ld1<ESZ>(up, (size_t)ye * W + xe); vn = ld1<ESZ>(vp, (size_t)ye * W + xe); }
-                else { un = chroma_num<ESZ, CH>(up, cw, ch, ye, xe); vn = chroma_num<ESZ, CH>(vp, cw, ch, ye, xe); }
+                if (CH == SN_YUV_444) { un = ld1<ESZ>(up, (size_t)ye * pc + xe); vn = ld1<ESZ>(vp, (size_t)ye * pc + xe); }
+                else { un = chroma_num<ESZ, CH>(up, pc, cw, ch, ye, xe); vn = chroma_num<ESZ, CH>(vp, pc, cw, ch, ye, xe); }
                 yuv_to_rgb<CH>(K, y, un, vn, &rgb[0][r][k], &rgb[1][r][k], &rgb[2][r][k]);
             }
         }
@@ -241,14 +259,16 @@ __device__ __forceinline__ int quant(float off, float scale, float v, int lo, in
 
 template <int ESZ, int CH>
 __global__ __launch_bounds__(256) void egress_yuv_kernel(const void* __restrict__ out, int dt, uint8_t* __restrict__ dstp, const YuvK K,
-                                                       int H, int W, int Hp, int Wp, size_t frame_bytes, int src_vec) {
+                                                       const YuvGeo G, int Hp, int Wp, int src_vec) {
     const int t = blockIdx.z;
     const int x0 = (blockIdx.x * 32 + threadIdx.x) * 8, y0 = (blockIdx.y * 8 + threadIdx.y) * 2;
+    const int H = G.h, W = G.w, py = G.py, pc = G.pc;
     if (x0 >= W || y0 >= H) return;
-    const int cw = CH == SN_YUV_444 ? W : (W + 1) >> 1, ch = CH == SN_YUV_444 ? H : (H + 1) >> 1;
-    uint8_t* yp = dstp + (size_t)t * frame_bytes;
-    uint8_t* up = yp + (size_t)H * W * ESZ;
-    uint8_t* vp = up + (size_t)cw * ch * ESZ;
+    const int cw = CH == SN_YUV_444 ? W : (W + 1) >> 1;
+    uint8_t* base = dstp + (size_t)t * G.frame_bytes;
+    uint8_t* yp = base + G.oy;
+    uint8_t* up = base + G.ou;
+    uint8_t* vp = base + G.ov;
     const bool inner = x0 + 8 <= W;
     // Y', Cb, Cr of pixels x0 - 1 .. x0 + 7 (index 0 .. 8) of rows y0, y0 + 1, coordinates clamped to the H x W frame
     float yv[2][9], cb[2][9], cr[2][9];
@@ -279,20 +299,20 @@ __global__ __launch_bounds__(256) void egress_yuv_kernel(const void* __restrict_
         int q[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) q[k] = quant(K.yo, K.ys, yv[r][1 + k], K.ylo, K.yhi);
-        const size_t o = (size_t)(y0 + r) * W + x0;
+        const size_t o = (size_t)(y0 + r) * py + x0, oc = (size_t)(y0 + r) * pc + x0;
         if (inner) stn<ESZ, 8>(yp, o, q); else for (int k = 0; k < n; ++k) st1<ESZ>(yp, o + k, q[k]);
         if (CH == SN_YUV_444) {
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) q[k] = quant(K.co, K.cs, pl ? cr[r][1 + k] : cb[r][1 + k], K.clo, K.chi);
-                if (inner) stn<ESZ, 8>(pl ? vp : up, o, q); else for (int k = 0; k < n; ++k) st1<ESZ>(pl ? vp : up, o + k, q[k]);
+                if (inner) stn<ESZ, 8>(pl ? vp : up, oc, q); else for (int k = 0; k < n; ++k) st1<ESZ>(pl ? vp : up, oc + k, q[k]);
             }
         }
     }
     if (CH != SN_YUV_444) {
         const int c0 = x0 >> 1, nc = imin(4, cw - c0);
-        const size_t o = (size_t)(y0 >> 1) * cw + c0;
+        const size_t o = (size_t)(y0 >> 1) * pc + c0;
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
             int q[4];
@@ -360,7 +380,7 @@ template <int ESZ> struct NoiseK {
 
 template <int ESZ>
 __global__ __launch_bounds__(256) void yuv_noise_hist_kernel(const uint8_t* __restrict__ src, uint32_t* __restrict__ dst, int lo, int hi, int W,
-                                                           int hb, int wb, int ux, size_t frame_bytes) {
+                                                           int hb, int wb, int ux, size_t origin, size_t frame_bytes) {
     constexpr int NB = NoiseK<ESZ>::NB, LOW = NoiseK<ESZ>::LOW;
     __shared__ uint32_t low[LOW * 32];
     __shared__ uint32_t hist[NB];
@@ -368,7 +388,7 @@ __global__ __launch_bounds__(256) void yuv_noise_hist_kernel(const uint8_t* __re
     for (int i = tid; i < LOW * 32; i += 256) low[i] = 0;
     for (int i = tid; i < NB; i += 256) hist[i] = 0;
     __syncthreads();
-    const uint8_t* yp = src + (size_t)t * frame_bytes;
+    const uint8_t* yp = src + (size_t)t * frame_bytes + origin;           // W: the luma row pitch; origin: the byte offset of block (0, 0)
     const int units = ux * hb;                                            // hb, wb: whole 2 x 2 blocks; ux = ceil(wb / 4) units per block row
     for (int u = blockIdx.x * 256 + tid; u < units; u += gridDim.x * 256) {
         const int by = u / ux, bx0 = (u - by * ux) * 4;
@@ -409,6 +429,54 @@ __global__ __launch_bounds__(256) void yuv_noise_hist_kernel(const uint8_t* __re
     }
 }
 
+// ---- row and column sums ------------------------------------------------------------------------------------------------------------
+// A lane owns 8 consecutive pixels of a row (one 8 B / 16 B load where the ADDRESS allows it, element-wise otherwise and on the right edge, where
+// only the pixels inside the frame are read); a wave (blockDim.x = 64: threadIdx.y is the wave) covers 512 consecutive pixels and walks down a strip
+// of ROWCOL_STRIP rows.  Per row the lanes' sums are added across the wave and lane 0 adds the wave's sum to rows[t][y]: one integer atomic per
+// wave and row.  Each lane keeps 8 column accumulators over the strip and adds them to cols[t][x] at the end: one integer atomic per lane and
+// column.  Integer sums commute: the result is the same for every geometry and every schedule.  (16 x 1023 and 512 x 1023 fit an int.)
+constexpr int ROWCOL_STRIP = 16;
+
+__device__ __forceinline__ int wave_sum_i(int x) {                         // the sum over the 64 lanes, in every lane
+    x += dpp_movi<0xB1>(x);      // quad_perm [1,0,3,2]
+    x += dpp_movi<0x4E>(x);      // quad_perm [2,3,0,1]
+    x += dpp_movi<0x141>(x);     // row_half_mirror
+    x += dpp_movi<0x140>(x);     // row_mirror: the sum of the DPP row of 16
+    x += __shfl_xor(x, 16, 64);
+    x += __shfl_xor(x, 32, 64);
+    return x;
+}
+
+template <int ESZ>
+__global__ __launch_bounds__(256) void yuv_rowcol_kernel(const uint8_t* __restrict__ src, uint32_t* __restrict__ rows, uint32_t* __restrict__ cols,
+                                                       int H, int W, size_t frame_bytes) {
+    const int t = blockIdx.z, lane = threadIdx.x;
+    const int x0 = (blockIdx.x * 64 + lane) * 8, y0 = (blockIdx.y * 4 + threadIdx.y) * ROWCOL_STRIP;
+    if (y0 >= H) return;                                                  // the whole wave: every lane of a wave that stays takes part in the sums
+    const uint8_t* yp = src + (size_t)t * frame_bytes;
+    const int n = imin(8, W - x0);                                        // <= 0: a lane beyond the right edge reads nothing and adds zeros
+    const int y1 = imin(y0 + ROWCOL_STRIP, H);
+    int acc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[k] = 0;
+    for (int y = y0; y < y1; ++y) {
+        int v[8];
+        if (n == 8) {
+            ldn<ESZ, 8>(yp, (size_t)y * W + x0, v);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = k < n ? ld1<ESZ>(yp, (size_t)y * W + x0 + k) : 0;
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] += v[k];
+        const int s = wave_sum_i(((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7])));
+        if (lane == 0) atomicAdd(&rows[(size_t)t * H + y], (uint32_t)s);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if (k < n) atomicAdd(&cols[(size_t)t * W + x0 + k], (uint32_t)acc[k]);
+}
+
 // constants: float64 expressions rounded once to float32 (tests/yuv_ref.py: constants() evaluates the same expressions)
 bool make_consts(const sn_yuv_fmt* f, YuvK* K) {
     if (!f || (f->bits != 8 && f->bits != 10) || f->chroma < 0 || f->chroma > 2 || f->matrix < 0 || f->matrix > 1 || f->range < 0 || f->range > 1) return false;
@@ -437,6 +505,27 @@ size_t frame_bytes_of(const sn_yuv_fmt* f, int H, int W) {
     return ((size_t)H * W + 2 * c) * esz;
 }
 
+// The picture of a launch: the whole H x W frame (rect == nullptr) or rect inside it.  false: rect does not lie inside the frame, or at
+// 4:2:0 it would share a chroma sample with its surroundings (x0, y0 odd; w or h odd without reaching the frame's far edge).
+bool make_geo(const sn_yuv_fmt* f, int H, int W, const sn_yuv_rect* rect, YuvGeo* G) {
+    const size_t esz = f->bits == 8 ? 1 : 2;
+    const bool sub = f->chroma != SN_YUV_444;
+    const int cw = sub ? (W + 1) / 2 : W, ch = sub ? (H + 1) / 2 : H;
+    int x0 = 0, y0 = 0, w = W, h = H;
+    if (rect) {
+        x0 = rect->x0; y0 = rect->y0; w = rect->w; h = rect->h;
+        if (x0 < 0 || y0 < 0 || w < 1 || h < 1 || x0 > W - w || y0 > H - h) return false;
+        if (sub && ((x0 & 1) || (y0 & 1) || ((w & 1) && x0 + w != W) || ((h & 1) && y0 + h != H))) return false;
+    }
+    G->h = h; G->w = w; G->py = W; G->pc = cw;
+    G->frame_bytes = frame_bytes_of(f, H, W);
+    const size_t oc = sub ? (size_t)(y0 >> 1) * cw + (x0 >> 1) : (size_t)y0 * W + x0;
+    G->oy = ((size_t)y0 * W + x0) * esz;
+    G->ou = ((size_t)H * W + oc) * esz;
+    G->ov = G->ou + (size_t)cw * ch * esz;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -454,32 +543,56 @@ extern "C" {
         }                                                                                                                  \
     } while (0)
 
-int sn_ingest_yuv(const uint8_t* src, const sn_yuv_fmt* fmt, void* dst, int dst_dtype, int T, int H, int W, int Hp, int Wp, void* stream) {
+static int ingest_yuv(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, void* dst, int dst_dtype, int T, int H, int W, int Hp, int Wp,
+                      void* stream) {
     sn_clear_error();
     YuvK K;
-    if (!src || !dst || !make_consts(fmt, &K) || dst_dtype < 0 || dst_dtype > 2 || T < 1 || T > 65535 || H < 1 || W < 1 || Hp < H || Wp < W) return SN_EINVAL;
+    YuvGeo G;
+    if (!src || !dst || !make_consts(fmt, &K) || dst_dtype < 0 || dst_dtype > 2 || T < 1 || T > 65535 || H < 1 || W < 1) return SN_EINVAL;
+    if (!make_geo(fmt, H, W, rect, &G) || Hp < G.h || Wp < G.w) return SN_EINVAL;
     if (fmt->bits == 10 && ((uintptr_t)src & 1)) return SN_EINVAL;
-    const size_t fb = frame_bytes_of(fmt, H, W);
     const int dst_vec = Wp % 8 == 0 && ((uintptr_t)dst & 15) == 0;       // every 8-pixel span of a row is 16 B (f32: 32 B) aligned
     const dim3 block(32, 8), grid(((Wp + 7) / 8 + 31) / 32, ((Hp + 1) / 2 + 7) / 8, T);
     if (grid.y > 65535) return SN_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    SN_YUV_DISPATCH(ingest_yuv_kernel, src, dst, dst_dtype, K, H, W, Hp, Wp, fb, dst_vec);
+    SN_YUV_DISPATCH(ingest_yuv_kernel, src, dst, dst_dtype, K, G, Hp, Wp, dst_vec);
+    return sn_check_launch();
+}
+
+int sn_ingest_yuv(const uint8_t* src, const sn_yuv_fmt* fmt, void* dst, int dst_dtype, int T, int H, int W, int Hp, int Wp, void* stream) {
+    return ingest_yuv(src, fmt, nullptr, dst, dst_dtype, T, H, W, Hp, Wp, stream);
+}
+
+int sn_ingest_yuv_rect(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, void* dst, int dst_dtype, int T, int H, int W, int Hp, int Wp,
+                       void* stream) {
+    if (!rect) { sn_clear_error(); return SN_EINVAL; }
+    return ingest_yuv(src, fmt, rect, dst, dst_dtype, T, H, W, Hp, Wp, stream);
+}
+
+static int egress_yuv(const void* out, int out_dtype, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint8_t* dst, int T, int H, int W, int Hp, int Wp,
+                      void* stream) {
+    sn_clear_error();
+    YuvK K;
+    YuvGeo G;
+    if (!out || !dst || !make_consts(fmt, &K) || out_dtype < 0 || out_dtype > 2 || T < 1 || T > 65535 || H < 1 || W < 1) return SN_EINVAL;
+    if (!make_geo(fmt, H, W, rect, &G) || Hp < G.h || Wp < G.w) return SN_EINVAL;
+    if (fmt->bits == 10 && ((uintptr_t)dst & 1)) return SN_EINVAL;
+    const int src_vec = Wp % 8 == 0 && ((uintptr_t)out & 15) == 0;
+    const dim3 block(32, 8), grid(((G.w + 7) / 8 + 31) / 32, ((G.h + 1) / 2 + 7) / 8, T);
+    if (grid.y > 65535) return SN_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    SN_YUV_DISPATCH(egress_yuv_kernel, out, out_dtype, dst, K, G, Hp, Wp, src_vec);
     return sn_check_launch();
 }
 
 int sn_egress_yuv(const void* out, int out_dtype, const sn_yuv_fmt* fmt, uint8_t* dst, int T, int H, int W, int Hp, int Wp, void* stream) {
-    sn_clear_error();
-    YuvK K;
-    if (!out || !dst || !make_consts(fmt, &K) || out_dtype < 0 || out_dtype > 2 || T < 1 || T > 65535 || H < 1 || W < 1 || Hp < H || Wp < W) return SN_EINVAL;
-    if (fmt->bits == 10 && ((uintptr_t)dst & 1)) return SN_EINVAL;
-    const size_t fb = frame_bytes_of(fmt, H, W);
-    const int src_vec = Wp % 8 == 0 && ((uintptr_t)out & 15) == 0;
-    const dim3 block(32, 8), grid(((W + 7) / 8 + 31) / 32, ((H + 1) / 2 + 7) / 8, T);
-    if (grid.y > 65535) return SN_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    SN_YUV_DISPATCH(egress_yuv_kernel, out, out_dtype, dst, K, H, W, Hp, Wp, fb, src_vec);
-    return sn_check_launch();
+    return egress_yuv(out, out_dtype, fmt, nullptr, dst, T, H, W, Hp, Wp, stream);
+}
+
+int sn_egress_yuv_rect(const void* out, int out_dtype, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint8_t* dst, int T, int H, int W, int Hp, int Wp,
+                       void* stream) {
+    if (!rect) { sn_clear_error(); return SN_EINVAL; }
+    return egress_yuv(out, out_dtype, fmt, rect, dst, T, H, W, Hp, Wp, stream);
 }
 
 int sn_yuv_thumb(const uint8_t* src, const sn_yuv_fmt* fmt, uint16_t* dst, int T, int H, int W, void* stream) {
@@ -496,23 +609,50 @@ int sn_yuv_thumb(const uint8_t* src, const sn_yuv_fmt* fmt, uint16_t* dst, int T
     return sn_check_launch();
 }
 
-int sn_yuv_noise_hist(const uint8_t* src, const sn_yuv_fmt* fmt, uint32_t* dst, int lo, int hi, int T, int H, int W, void* stream) {
+static int noise_hist(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint32_t* dst, int lo, int hi, int T, int H, int W, void* stream) {
     sn_clear_error();
     if (!src || !dst || !fmt || (fmt->bits != 8 && fmt->bits != 10) || fmt->chroma < 0 || fmt->chroma > 2 || T < 1 || T > 65535 || H < 1 || W < 1 || lo > hi) return SN_EINVAL;
     if (((uintptr_t)dst & 3) || (fmt->bits == 10 && ((uintptr_t)src & 1))) return SN_EINVAL;
-    const size_t fb = frame_bytes_of(fmt, H, W);
+    YuvGeo G;
+    if (!make_geo(fmt, H, W, rect, &G)) return SN_EINVAL;
+    const size_t fb = G.frame_bytes;
     const int nbins = fmt->bits == 8 ? NoiseK<1>::NB : NoiseK<2>::NB;
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(dst, 0, (size_t)T * nbins * sizeof(uint32_t), s) != hipSuccess) return sn_check_launch();      // dst is overwritten, not added to
-    const int hb = H / 2, wb = W / 2, ux = (wb + 3) / 4;
+    const int hb = G.h / 2, wb = G.w / 2, ux = (wb + 3) / 4;               // the block grid is anchored at the picture's first sample
     if (hb < 1 || wb < 1) return sn_check_launch();                        // no whole block: all-zero histograms
     const long long units = (long long)ux * hb;
     if (units > 0x7fffffffLL - 1024 * 256) return SN_EINVAL;
     // about 8 units (32 blocks) per lane: the zeroing, the sum of the copies and the flush are paid once per 8192 blocks and a 720p frame is 29 workgroups
     const int gx = (int)((units + 2047) / 2048 < 1024 ? (units + 2047) / 2048 : 1024);
     const dim3 block(256), grid(gx, T);
-    if (fmt->bits == 8) hipLaunchKernelGGL((yuv_noise_hist_kernel<1>), grid, block, 0, s, src, dst, lo, hi, W, hb, wb, ux, fb);
-    else hipLaunchKernelGGL((yuv_noise_hist_kernel<2>), grid, block, 0, s, src, dst, lo, hi, W, hb, wb, ux, fb);
+    if (fmt->bits == 8) hipLaunchKernelGGL((yuv_noise_hist_kernel<1>), grid, block, 0, s, src, dst, lo, hi, W, hb, wb, ux, G.oy, fb);
+    else hipLaunchKernelGGL((yuv_noise_hist_kernel<2>), grid, block, 0, s, src, dst, lo, hi, W, hb, wb, ux, G.oy, fb);
+    return sn_check_launch();
+}
+
+int sn_yuv_noise_hist(const uint8_t* src, const sn_yuv_fmt* fmt, uint32_t* dst, int lo, int hi, int T, int H, int W, void* stream) {
+    return noise_hist(src, fmt, nullptr, dst, lo, hi, T, H, W, stream);
+}
+
+int sn_yuv_noise_hist_rect(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint32_t* dst, int lo, int hi, int T, int H, int W,
+                           void* stream) {
+    if (!rect) { sn_clear_error(); return SN_EINVAL; }
+    return noise_hist(src, fmt, rect, dst, lo, hi, T, H, W, stream);
+}
+
+int sn_yuv_rowcol_sums(const uint8_t* src, const sn_yuv_fmt* fmt, uint32_t* rows, uint32_t* cols, int T, int H, int W, void* stream) {
+    sn_clear_error();
+    if (!src || !rows || !cols || !fmt || (fmt->bits != 8 && fmt->bits != 10) || fmt->chroma < 0 || fmt->chroma > 2 || T < 1 || T > 65535 || H < 1 || W < 1 ||
+        H > 65535 || W > 65535) return SN_EINVAL;
+    if (((uintptr_t)rows & 3) || ((uintptr_t)cols & 3) || (fmt->bits == 10 && ((uintptr_t)src & 1))) return SN_EINVAL;
+    const size_t fb = frame_bytes_of(fmt, H, W);
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(rows, 0, (size_t)T * H * sizeof(uint32_t), s) != hipSuccess) return sn_check_launch();       // both are overwritten, not added to
+    if (hipMemsetAsync(cols, 0, (size_t)T * W * sizeof(uint32_t), s) != hipSuccess) return sn_check_launch();
+    const dim3 block(64, 4), grid((W + 511) / 512, (H + 4 * ROWCOL_STRIP - 1) / (4 * ROWCOL_STRIP), T);
+    if (fmt->bits == 8) hipLaunchKernelGGL((yuv_rowcol_kernel<1>), grid, block, 0, s, src, rows, cols, H, W, fb);
+    else hipLaunchKernelGGL((yuv_rowcol_kernel<2>), grid, block, 0, s, src, rows, cols, H, W, fb);
     return sn_check_launch();
 }
 

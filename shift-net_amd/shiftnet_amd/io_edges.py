@@ -7,6 +7,9 @@
 ``thumb_yuv``  : the same payloads -> uint16 sums of the luma codes of every 8 x 8 block, for the scene-cut detector (shiftnet_amd/scenes.py);
 ``noise_hist_yuv``: the same payloads -> uint32 histograms of |a - b - c + d| over the 2 x 2 luma blocks, for the blind noise estimate
                (shiftnet_amd/noise.py);
+``rowcol_sums_yuv``: the same payloads -> uint32 sums of the luma codes of every row and of every column, for the letterbox rule
+               (shiftnet_amd/picture.py); ``ingest_yuv`` / ``egress_yuv`` / ``noise_hist_yuv`` take ``rect=(x0, y0, w, h)`` to work on that
+               picture of the stream alone, as on the cropped stream;
 ``egress_u8``  == the per-frame ``clamp(0,1) * 255`` -> skimage PSNR(data_range=255) against the uint8 ground truth
                (:139-143) and the rounded uint8 frame cv2.imwrite would store (:152).
 """
@@ -81,34 +84,51 @@ def yuv_fmt(bits: int, chroma: int, matrix: int, range_: int) -> "L.YuvFmt":
     return L.YuvFmt(bits, chroma, matrix, range_)
 
 
+def _rect(rect, fmt: "L.YuvFmt", H: int, W: int) -> "L.YuvRect":
+    from .picture import check_rect
+    return L.YuvRect(*check_rect(rect, fmt, H, W, smallest=1))      # the kernels take any rectangle; the restorer has a limit of its own
+
+
 def ingest_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, Hp: int, Wp: int, dtype: torch.dtype,
-               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+               out: Optional[torch.Tensor] = None, rect=None) -> torch.Tensor:
     """payload_u8: [T, frame_bytes] uint8 on a HIP device, T planar Y'CbCr frames of H x W -> [1,T,3,Hp,Wp] RGB of ``dtype`` in [0,1];
-    pixels outside H x W replicate the edge pixel.  ``out``: a [1,T,3,Hp,Wp] tensor to fill instead of a new one."""
+    pixels outside H x W replicate the edge pixel.  ``out``: a [1,T,3,Hp,Wp] tensor to fill instead of a new one.
+    ``rect=(x0, y0, w, h)``: the picture of the stream to ingest, bit for bit as the cropped stream would be: Hp >= h, Wp >= w, the chroma
+    neighbours clamp to the picture's chroma planes and the padding repeats its last row and column."""
     fb = fmt.frame_bytes(H, W)
     assert payload_u8.dtype == torch.uint8 and payload_u8.is_cuda and payload_u8.dim() == 2 and payload_u8.shape[1] == fb and payload_u8.is_contiguous()
-    assert Hp >= H and Wp >= W and dtype in _CODE
+    r = None if rect is None else _rect(rect, fmt, H, W)
+    assert Hp >= (H if r is None else r.h) and Wp >= (W if r is None else r.w) and dtype in _CODE
     T = payload_u8.shape[0]
     x = out if out is not None else torch.empty((1, T, 3, Hp, Wp), dtype=dtype, device=payload_u8.device)
     assert tuple(x.shape) == (1, T, 3, Hp, Wp) and x.dtype == dtype and x.is_contiguous() and x.device == payload_u8.device
     with torch.cuda.device(payload_u8.device):
-        L.check(L.load().sn_ingest_yuv(payload_u8.data_ptr(), fmt, x.data_ptr(), _CODE[dtype], T, H, W, Hp, Wp,
-                                       torch.cuda.current_stream(payload_u8.device).cuda_stream), "sn_ingest_yuv")
+        st = torch.cuda.current_stream(payload_u8.device).cuda_stream
+        if r is None:
+            L.check(L.load().sn_ingest_yuv(payload_u8.data_ptr(), fmt, x.data_ptr(), _CODE[dtype], T, H, W, Hp, Wp, st), "sn_ingest_yuv")
+        else:
+            L.check(L.load().sn_ingest_yuv_rect(payload_u8.data_ptr(), fmt, r, x.data_ptr(), _CODE[dtype], T, H, W, Hp, Wp, st), "sn_ingest_yuv_rect")
     return x
 
 
-def egress_yuv(out: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, dst: Optional[torch.Tensor] = None) -> torch.Tensor:
+def egress_yuv(out: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, dst: Optional[torch.Tensor] = None, rect=None) -> torch.Tensor:
     """out: [T,3,Hp,Wp] network output (float32 or module dtype) on the device -> [T, frame_bytes] uint8 payloads of the H x W crop.
-    ``dst``: a [T, frame_bytes] uint8 tensor to fill instead of a new one."""
+    ``dst``: a [T, frame_bytes] uint8 tensor to fill instead of a new one.
+    ``rect=(x0, y0, w, h)``: out holds that picture of the H x W stream (Hp >= h, Wp >= w); only the picture's samples of the payloads, luma and
+    chroma, are written, with what the cropped stream's egress writes -- every other byte of ``dst`` stays (a new tensor starts as zeros)."""
     assert out.is_cuda and out.dim() == 4 and out.shape[1] == 3 and out.dtype in _CODE and out.is_contiguous()
     T, _, Hp, Wp = out.shape
-    assert Hp >= H and Wp >= W
+    r = None if rect is None else _rect(rect, fmt, H, W)
+    assert Hp >= (H if r is None else r.h) and Wp >= (W if r is None else r.w)
     fb = fmt.frame_bytes(H, W)
-    y = dst if dst is not None else torch.empty((T, fb), dtype=torch.uint8, device=out.device)
+    y = dst if dst is not None else (torch.empty if r is None else torch.zeros)((T, fb), dtype=torch.uint8, device=out.device)
     assert tuple(y.shape) == (T, fb) and y.dtype == torch.uint8 and y.is_contiguous() and y.device == out.device
     with torch.cuda.device(out.device):
-        L.check(L.load().sn_egress_yuv(out.data_ptr(), _CODE[out.dtype], fmt, y.data_ptr(), T, H, W, Hp, Wp,
-                                       torch.cuda.current_stream(out.device).cuda_stream), "sn_egress_yuv")
+        st = torch.cuda.current_stream(out.device).cuda_stream
+        if r is None:
+            L.check(L.load().sn_egress_yuv(out.data_ptr(), _CODE[out.dtype], fmt, y.data_ptr(), T, H, W, Hp, Wp, st), "sn_egress_yuv")
+        else:
+            L.check(L.load().sn_egress_yuv_rect(out.data_ptr(), _CODE[out.dtype], fmt, r, y.data_ptr(), T, H, W, Hp, Wp, st), "sn_egress_yuv_rect")
     return y
 
 
@@ -127,10 +147,11 @@ def thumb_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, out: Op
 
 
 def noise_hist_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lo: Optional[int] = None, hi: Optional[int] = None,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, rect=None) -> torch.Tensor:
     """payload_u8: [T, frame_bytes] uint8 on a HIP device (only the luma plane of each payload is read) -> uint32 [T, 2 (2^bits - 1) + 1]:
     per frame the counts of v = |a - b - c + d| over the non-overlapping 2 x 2 luma blocks whose four codes lie strictly between ``lo`` and
-    ``hi`` (default: the format's black and white codes, noise.clip_codes).  ``out``: a tensor of that shape to overwrite."""
+    ``hi`` (default: the format's black and white codes, noise.clip_codes).  ``out``: a tensor of that shape to overwrite.
+    ``rect=(x0, y0, w, h)``: the blocks of that picture of the stream alone, the block grid anchored at (x0, y0): the cropped stream's histograms."""
     from .noise import clip_codes, nbins
     fb = fmt.frame_bytes(H, W)
     assert payload_u8.dtype == torch.uint8 and payload_u8.is_cuda and payload_u8.dim() == 2 and payload_u8.shape[1] == fb and payload_u8.is_contiguous()
@@ -139,7 +160,28 @@ def noise_hist_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lo
     lo, hi = dlo if lo is None else int(lo), dhi if hi is None else int(hi)
     y = out if out is not None else torch.empty((T, nb), dtype=torch.uint32, device=payload_u8.device)
     assert tuple(y.shape) == (T, nb) and y.dtype == torch.uint32 and y.is_contiguous() and y.device == payload_u8.device
+    r = None if rect is None else _rect(rect, fmt, H, W)
     with torch.cuda.device(payload_u8.device):
-        L.check(L.load().sn_yuv_noise_hist(payload_u8.data_ptr(), fmt, y.data_ptr(), lo, hi, T, H, W,
-                                           torch.cuda.current_stream(payload_u8.device).cuda_stream), "sn_yuv_noise_hist")
+        st = torch.cuda.current_stream(payload_u8.device).cuda_stream
+        if r is None:
+            L.check(L.load().sn_yuv_noise_hist(payload_u8.data_ptr(), fmt, y.data_ptr(), lo, hi, T, H, W, st), "sn_yuv_noise_hist")
+        else:
+            L.check(L.load().sn_yuv_noise_hist_rect(payload_u8.data_ptr(), fmt, r, y.data_ptr(), lo, hi, T, H, W, st), "sn_yuv_noise_hist_rect")
     return y
+
+
+def rowcol_sums_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, out_rows: Optional[torch.Tensor] = None,
+                    out_cols: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """payload_u8: [T, frame_bytes] uint8 on a HIP device (only the luma plane of each payload is read) -> (uint32 [T, H], uint32 [T, W]): the exact
+    sums of the luma codes of every row and of every column of every frame.  ``out_rows`` / ``out_cols``: tensors of those shapes to overwrite."""
+    fb = fmt.frame_bytes(H, W)
+    assert payload_u8.dtype == torch.uint8 and payload_u8.is_cuda and payload_u8.dim() == 2 and payload_u8.shape[1] == fb and payload_u8.is_contiguous()
+    T, dev = payload_u8.shape[0], payload_u8.device
+    rows = out_rows if out_rows is not None else torch.empty((T, H), dtype=torch.uint32, device=dev)
+    cols = out_cols if out_cols is not None else torch.empty((T, W), dtype=torch.uint32, device=dev)
+    for a, n in ((rows, H), (cols, W)):
+        assert tuple(a.shape) == (T, n) and a.dtype == torch.uint32 and a.is_contiguous() and a.device == dev
+    with torch.cuda.device(dev):
+        L.check(L.load().sn_yuv_rowcol_sums(payload_u8.data_ptr(), fmt, rows.data_ptr(), cols.data_ptr(), T, H, W,
+                                            torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_rowcol_sums")
+    return rows, cols

@@ -17,6 +17,11 @@ those of restoring every scene as a separate video.  The cuts are listed by the 
 Noise level (``sigma``, denoise variants): a number, a list with one number per window, or ``"auto"``: a blind estimate per window from
 histograms of the luma's 2 x 2 Haar HH coefficient, made on the device from the payloads the window has uploaded anyway
 (``sn_yuv_noise_hist``, shiftnet_amd/noise.py).
+
+Active picture (``picture``, off by default): a letterboxed or pillarboxed stream is restored inside its picture rectangle only -- there the bytes
+are those of restoring the cropped stream, and the bars leave as they came in.  The rectangle is given by the caller, for the stream or per window,
+or found per window from the sums of the luma's rows and columns, made on the device from the payloads the window has uploaded anyway
+(``sn_yuv_rowcol_sums``, shiftnet_amd/picture.py).
 """
 from __future__ import annotations
 
@@ -292,10 +297,27 @@ class VideoRestorer:
     scene iff its measure m[t] >= cut_threshold and >= cut_ratio times the median of its six neighbours'; heuristic defaults); an iterable of
     frame indices (each >= 1, strictly increasing) -- use these, run no detector.  Every scene is then restored as a clip of its own: the bytes
     are those of restoring each scene as a separate video.  Once ``restore()`` has been exhausted ``stats["cuts"]`` lists the scene starts used,
-    ``stats["cut_measure"]`` the m[t] of every frame (auto only; m[0] = 0.0) and ``stats["cuts_ignored"]`` the listed cuts at or beyond the end."""
+    ``stats["cut_measure"]`` the m[t] of every frame (auto only; m[0] = 0.0) and ``stats["cuts_ignored"]`` the listed cuts at or beyond the end.
+    picture: None -- the whole frame, today's code path and bytes; ``(x0, y0, w, h)`` in luma samples -- restore that rectangle of every frame; a
+    list with one rectangle (or None) per window in the order the windows are restored (running out is a ValueError that names the window).  The
+    two are told apart by their elements: four numbers are one rectangle, anything whose elements are sequences or None is a list, of four windows
+    too.  Every entry is judged against the stream's size and format when restore() starts (a ValueError before the first window); how many
+    windows a stream has is known only at its end, so a list that is too short is found when the stager reaches the window without an entry;
+    ``"auto"`` -- per window the rectangle left by the black bars of its input frames as fed (picture.py: rows and columns whose mean luma stays
+    within ``bar_level`` 8-bit codes of black in every frame of the window; a heuristic; None where it finds no bars, or nothing but bars).  At
+    4:2:0 x0 and y0 are even, and w and h unless the rectangle reaches the frame's far edge; a rectangle is at least as large as the smallest
+    frame the network takes, 5 x 5 ("small" topology) or 9 x 9 ("plus") (picture.check_rect, picture.smallest_picture).  Inside the rectangle, luma and
+    chroma, the output equals that of this restorer with the same other arguments on the cropped stream -- the network, the chroma filters of both
+    edges and the ``sigma="auto"`` estimate see the rectangle as the whole frame -- and every sample outside equals the input's.
+    ``scene_cuts="auto"`` keeps looking at the whole frame: the bars add nothing to the difference measure but dilute its mean, so the cuts found
+    may differ from those of the cropped stream.  A window whose rectangle differs from the previous window's has a new input signature for the
+    engine: a new plan, and a new captured graph where graphs are on.  Once ``restore()`` has been exhausted ``stats["window_picture"]`` lists the
+    rectangle of every window (None: the full frame), ``stats["picture_launches"]`` counts the ``sn_yuv_rowcol_sums`` launches and
+    ``stats["picture_wait_ms"]`` (auto only) lists how long the stager waited for every window's sums (upload, kernel and copy back included)."""
 
     def __init__(self, net, one_len: int, sigma=None, pipeline: bool = True, scene_cuts=None,
-                 cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0)) -> None:
+                 cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0),
+                 picture=None, bar_level: float = 1.0) -> None:
         import torch
         self.torch = torch
         self.net, self.one_len, self.pipeline = net, int(one_len), bool(pipeline)
@@ -327,6 +349,20 @@ class VideoRestorer:
         if self.sigma_mode != "fixed" and not self.V.denoise:
             raise ValueError(f"sigma={'auto' if self.sigma_mode == 'auto' else 'a per-window list'!r} is for the denoise variants; {type(net).__name__} "
                              "of a deblur variant takes no noise level")
+        # picture_mode: "full" (None: the code path without any of the rest), "auto", "fixed" (one rectangle), "list"
+        self.picture, self.picture_mode, self.bar_level = None, "full", float(bar_level)
+        if isinstance(picture, str):
+            if picture != "auto":
+                raise ValueError(f"picture must be None, 'auto', (x0, y0, w, h) or a list of rectangles, got {picture!r}")
+            self.picture_mode = "auto"
+        elif picture is not None:
+            picture = list(picture)
+            if len(picture) == 4 and not any(r is None or hasattr(r, "__iter__") for r in picture):
+                self.picture, self.picture_mode = tuple(picture), "fixed"
+            else:
+                self.picture, self.picture_mode = picture, "list"
+        if not (self.bar_level >= 0.0):                            # refuses NaN as well
+            raise ValueError(f"bar_level must be >= 0, got {bar_level!r}")
         p = next(net.parameters())
         self.dev, self.dtype = p.device, p.dtype
         if self.dev.type != "cuda":
@@ -334,11 +370,15 @@ class VideoRestorer:
         self.stats = {"frames": 0, "windows": 0, "forward_s": 0.0, "window_forward_ms": []}
         self._shape = None
         self._wsig, self._wfsig, self._noise_launches = [], [], 0
+        self._wpic, self._picture_launches, self._staged, self._picture_wait = [], 0, 0, []
 
     # -- per-shape state: two slots of staging and device buffers, sized for the largest window -------------------------------------
     def _prepare(self, fmt, h: int, w: int) -> None:
         torch = self.torch
         key = (fmt.bits, fmt.chroma, fmt.matrix, fmt.range, h, w)
+        if self.picture_mode in ("fixed", "list"):                # the rectangles are judged against this stream
+            from .picture import check_pictures, smallest_picture
+            self._pics = check_pictures([self.picture] if self.picture_mode == "fixed" else self.picture, fmt, h, w, smallest_picture(self.V.topo))
         if self._shape == key:
             return
         self._shape = key
@@ -351,9 +391,11 @@ class VideoRestorer:
         self.pin_out = [torch.empty((tout, self.fb), dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.dev_in = [torch.empty((tin, self.fb), dtype=torch.uint8, device=dev) for _ in range(2)]
         self.dev_out = [torch.empty((tout, self.fb), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.x = [torch.empty((1, tin, 3, self.hp, self.wp), dtype=self.dtype, device=dev) for _ in range(2)]
+        # flat, sized for the full frame: a window's tensors are views of the leading elements at the padded size of its picture
+        self.x = [torch.empty(tin * 3 * self.hp * self.wp, dtype=self.dtype, device=dev) for _ in range(2)]
         half = self.dtype != torch.float32
-        self.x32 = [torch.empty((1, tin, 3, self.hp, self.wp), dtype=torch.float32, device=dev) if half else None for _ in range(2)]
+        self.x32 = [torch.empty(tin * 3 * self.hp * self.wp, dtype=torch.float32, device=dev) if half else None for _ in range(2)]
+        self.rect = [None, None]                                  # the picture of the window a slot holds (None: the full frame)
         self.s_in, self.s_out = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
         ev = lambda: [torch.cuda.Event() for _ in range(2)]      # noqa: E731
         self.ev_h2d, self.ev_ready, self.ev_done, self.ev_d2h = ev(), ev(), ev(), ev()
@@ -365,13 +407,42 @@ class VideoRestorer:
             self.dev_hist = [torch.empty((tin, self.nb), dtype=torch.uint32, device=dev) for _ in range(2)]
             self.pin_hist = [torch.empty((tin, self.nb), dtype=torch.uint32).pin_memory() for _ in range(2)]
             self.ev_noise = ev()
+        if self.picture_mode == "auto":                           # per slot: the window's row and column sums on the device and in pinned memory
+            self.dev_rows = [torch.empty((tin, h), dtype=torch.uint32, device=dev) for _ in range(2)]
+            self.dev_cols = [torch.empty((tin, w), dtype=torch.uint32, device=dev) for _ in range(2)]
+            self.pin_rows = [torch.empty((tin, h), dtype=torch.uint32).pin_memory() for _ in range(2)]
+            self.pin_cols = [torch.empty((tin, w), dtype=torch.uint32).pin_memory() for _ in range(2)]
+            self.ev_sums = ev()
+
+    def _size(self, rect) -> Tuple[int, int, int, int]:
+        """(h, w, padded h, padded w) of what a window with picture ``rect`` feeds the network."""
+        h, w = (self.h, self.w) if rect is None else (rect[3], rect[2])
+        return (h, w) + padded_size(h, w, self.V.topo)
+
+    def _views(self, slot: int, t: int, rect):
+        """The window's input tensors [1, t, 3, hp, wp]: views of the slot's flat buffers."""
+        _, _, hp, wp = self._size(rect)
+        n = t * 3 * hp * wp
+        x32 = self.x32[slot]
+        return self.x[slot][:n].view(1, t, 3, hp, wp), (x32[:n].view(1, t, 3, hp, wp) if x32 is not None else None)
+
+    def _listed_picture(self, k: int):
+        if self.picture_mode == "fixed":
+            return self._pics[0]
+        if k >= len(self._pics):
+            raise ValueError(f"picture lists {len(self._pics)} window{'' if len(self._pics) == 1 else 's'}, window {k} has no entry")
+        return self._pics[k]
 
     # -- the steps of one window; slot = k % 2 -------------------------------------------------------------------------------------
     def _stage(self, slot: int, frames: Sequence[np.ndarray]) -> int:
-        """Host frames -> pinned slot -> device -> RGB tensors, on the side stream."""
-        from .io_edges import ingest_yuv, noise_hist_yuv
+        """Host frames -> pinned slot -> device -> RGB tensors, on the side stream.  Windows are staged in the order they are restored."""
+        from .io_edges import ingest_yuv, noise_hist_yuv, rowcol_sums_yuv
         torch = self.torch
         t = len(frames)
+        rect = None
+        if self.picture_mode in ("fixed", "list"):
+            rect = self._listed_picture(self._staged)
+        self._staged += 1
         if self.used[slot]:
             self.ev_h2d[slot].synchronize()                      # the copy that last read this pinned slot has finished
         pin = self.pin_in[slot].numpy()
@@ -382,16 +453,33 @@ class VideoRestorer:
                 self.s_in.wait_event(self.ev_done[slot])         # the forward that last read this slot's tensors has finished
             self.dev_in[slot][:t].copy_(self.pin_in[slot][:t], non_blocking=True)
             self.ev_h2d[slot].record(self.s_in)
+            if self.picture_mode == "auto":
+                # the sums of the payloads just uploaded; this thread waits for the event behind their copy to the host -- the side stream's own
+                # work, never the device and never the stream the forward runs on -- because the rectangle shapes everything staged from here on
+                from .picture import decide_picture, smallest_picture
+                rowcol_sums_yuv(self.dev_in[slot][:t], self.fmt, self.h, self.w, out_rows=self.dev_rows[slot][:t], out_cols=self.dev_cols[slot][:t])
+                self.pin_rows[slot][:t].copy_(self.dev_rows[slot][:t], non_blocking=True)
+                self.pin_cols[slot][:t].copy_(self.dev_cols[slot][:t], non_blocking=True)
+                self.ev_sums[slot].record(self.s_in)
+                self._picture_launches += 1
+                t0 = time.perf_counter()
+                self.ev_sums[slot].synchronize()
+                self._picture_wait.append((time.perf_counter() - t0) * 1e3)
+                rect = decide_picture(self.pin_rows[slot][:t].numpy(), self.pin_cols[slot][:t].numpy(), self.fmt, self.h, self.w, self.bar_level,
+                                      smallest_picture(self.V.topo))
+            self.rect[slot] = rect
+            x, x32 = self._views(slot, t, rect)
+            hp, wp = x.shape[3], x.shape[4]
             if self.sigma_mode == "auto":
                 # the histograms of the payloads just uploaded, ahead of the ingest so that they are on the host long before _run asks.  The
                 # pinned slot is free: _run read it on the host before this slot was handed back to the stager
-                noise_hist_yuv(self.dev_in[slot][:t], self.fmt, self.h, self.w, self.noise_lo, self.noise_hi, out=self.dev_hist[slot][:t])
+                noise_hist_yuv(self.dev_in[slot][:t], self.fmt, self.h, self.w, self.noise_lo, self.noise_hi, out=self.dev_hist[slot][:t], rect=rect)
                 self.pin_hist[slot][:t].copy_(self.dev_hist[slot][:t], non_blocking=True)
                 self.ev_noise[slot].record(self.s_in)
                 self._noise_launches += 1
-            ingest_yuv(self.dev_in[slot][:t], self.fmt, self.h, self.w, self.hp, self.wp, self.dtype, out=self.x[slot][:, :t])
-            if self.x32[slot] is not None:
-                ingest_yuv(self.dev_in[slot][:t], self.fmt, self.h, self.w, self.hp, self.wp, torch.float32, out=self.x32[slot][:, :t])
+            ingest_yuv(self.dev_in[slot][:t], self.fmt, self.h, self.w, hp, wp, self.dtype, out=x, rect=rect)
+            if x32 is not None:
+                ingest_yuv(self.dev_in[slot][:t], self.fmt, self.h, self.w, hp, wp, torch.float32, out=x32, rect=rect)
             self.ev_ready[slot].record(self.s_in)
         return t
 
@@ -420,24 +508,29 @@ class VideoRestorer:
         torch = self.torch
         n = t - PAST - FUTURE
         sigma = self._window_sigma(slot, t) if self.V.denoise else None
+        rect = self.rect[slot]
+        self._wpic.append(rect)
         with torch.cuda.stream(main), torch.no_grad():
             main.wait_event(self.ev_ready[slot])
             if self.used[slot]:
                 main.wait_event(self.ev_d2h[slot])               # the copy that last read this slot's device payloads has finished
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(main)
-            x = self.x[slot][:, :t]
+            x, x32 = self._views(slot, t, rect)
             kw = {}
-            if self.x32[slot] is not None:
-                kw["shortcut"] = self.x32[slot][:, :t]
+            if x32 is not None:
+                kw["shortcut"] = x32
             if self.V.denoise:
-                nm = torch.full((1, 1, 1, 1, 1), sigma / 255.0, dtype=self.dtype, device=self.dev).expand(1, t, 1, self.hp, self.wp)
+                nm = torch.full((1, 1, 1, 1, 1), sigma / 255.0, dtype=self.dtype, device=self.dev).expand(1, t, 1, x.shape[3], x.shape[4])
                 out = self.net.forward_fp32_out(x, nm, **kw)
             else:
                 out = self.net.forward_fp32_out(x, **kw)
             e1.record(main)
             self._timers.append((e0, e1))
-            egress_yuv(out, self.fmt, self.h, self.w, dst=self.dev_out[slot][:n])
+            if rect is not None:
+                # everything outside the picture leaves as it came in: the window's own n frames (not the reflected ones around them) first
+                self.dev_out[slot][:n].copy_(self.dev_in[slot][PAST:PAST + n], non_blocking=True)
+            egress_yuv(out, self.fmt, self.h, self.w, dst=self.dev_out[slot][:n], rect=rect)
             self.ev_done[slot].record(main)
         with torch.cuda.stream(self.s_out):
             self.s_out.wait_event(self.ev_done[slot])
@@ -456,6 +549,10 @@ class VideoRestorer:
         self.stats["forward_s"] = sum(ms) / 1e3
         self.stats["windows"] = len(ms)
         self.stats["noise_launches"] = self._noise_launches
+        self.stats["window_picture"] = list(self._wpic)
+        self.stats["picture_launches"] = self._picture_launches
+        if self.picture_mode == "auto":
+            self.stats["picture_wait_ms"] = list(self._picture_wait)
         if self.V.denoise:
             self.stats["window_sigma"] = list(self._wsig)
             if self.sigma_mode == "auto":
@@ -491,6 +588,7 @@ class VideoRestorer:
         self.stats = {"frames": 0, "windows": 0, "forward_s": 0.0, "window_forward_ms": []}
         self._src = None
         self._wsig, self._wfsig, self._noise_launches = [], [], 0
+        self._wpic, self._picture_launches, self._staged, self._picture_wait = [], 0, 0, []
         main = torch.cuda.current_stream(self.dev)
 
         def checked(it):
@@ -581,6 +679,16 @@ def sigma_arg(word: str):
         return word
 
 
+def picture_arg(word: str):
+    """--picture: 'full' -> None; 'auto'; X:Y:W:H -> the rectangle; anything else names a file with one rectangle per window."""
+    if word == "full":
+        return None
+    parts = word.split(":")
+    if len(parts) == 4 and all(p.isdigit() for p in parts):
+        return tuple(int(p) for p in parts)
+    return word
+
+
 def make_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Restore a Y4M video with Shift-Net on the MI355X: same frames, size and pixel format out")
     ap.add_argument("--variant", choices=list(VARIANTS), required=True)
@@ -600,6 +708,12 @@ def make_parser() -> argparse.ArgumentParser:
                          "FILE lists the first frame of every scene but the first, one index per line ('#' comments); default off: the stream is one clip")
     ap.add_argument("--cut_threshold", type=float, default=4.0, help="auto: smallest mean absolute difference of 8x8 block means (8-bit code units) of a cut")
     ap.add_argument("--cut_ratio", type=float, default=2.5, help="auto: ... and at least this many times the median of the six neighbouring frames' differences")
+    ap.add_argument("--picture", default="full", metavar="{full,auto,X:Y:W:H,FILE}",
+                    help="restore the active picture of a letterboxed / pillarboxed stream only and leave the bars as they are: X:Y:W:H in luma samples; "
+                         "'auto' finds the bars per window on the device (a heuristic, see --bar_level); FILE lists 'x0 y0 w h' (or 'full') per window, one "
+                         "per line ('#' comments); default full: the whole frame")
+    ap.add_argument("--bar_level", type=float, default=1.0, help="auto: a row or column is bar if its mean luma stays within this many 8-bit codes of black")
+    ap.add_argument("--picture_out", default=None, metavar="FILE", help="write the picture every window was restored with, in the format --picture FILE reads")
     ap.add_argument("--cuts_out", default=None, metavar="FILE", help="write the scene starts that were used, in the format --scene_cuts FILE reads")
     ap.add_argument("input", metavar="IN", help="Y4M file, or - for stdin")
     ap.add_argument("output", metavar="OUT", help="Y4M file, or - for stdout")
@@ -658,6 +772,15 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 cuts = parse_cuts(fh.read())
         except (OSError, ValueError) as e:
             ap.error(f"--scene_cuts {a.scene_cuts}: {e}")
+    picture, picture_how = picture_arg(a.picture), "fixed"
+    if picture == "auto":
+        picture_how = "auto"
+    elif isinstance(picture, str):
+        from .picture import read_pictures
+        try:
+            picture, picture_how = read_pictures(picture), "listed"
+        except (OSError, ValueError) as e:
+            ap.error(f"--picture {a.picture}: {e}")
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
     fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
     try:
@@ -671,7 +794,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                       L.SN_YUV_FULL if rng == "full" else L.SN_YUV_LIMITED)
         net = load_net(a.variant, a.checkpoint, a.dtype)
         vr = VideoRestorer(net, a.one_len, sigma=sigma, pipeline=not a.no_pipeline, scene_cuts=cuts, cut_threshold=a.cut_threshold,
-                           cut_ratio=a.cut_ratio, sigma_clamp=a.sigma_clamp)
+                           cut_ratio=a.cut_ratio, sigma_clamp=a.sigma_clamp, picture=picture, bar_level=a.bar_level)
         wr = Y4MWriter(fout, hd)
         t0 = time.perf_counter()
         n = 0
@@ -693,6 +816,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         log(f"done: {n} frames in {dt:.2f} s, {n / dt if dt > 0 else 0.0:.2f} frames/s end to end, "
             f"{n / fwd if fwd > 0 else 0.0:.2f} frames/s forward only, {len(used) + 1} scene{'s' if used else ''}"
             f"{'' if cuts is None else (' (cuts found)' if cuts == 'auto' else ' (cuts listed)')}")
+        wp = vr.stats.get("window_picture", [])
+        if a.picture_out is not None:
+            from .picture import write_pictures
+            write_pictures(a.picture_out, wp, picture_how)
+        if picture is not None:
+            kinds = sorted({r for r in wp if r is not None})
+            log(f"picture ({picture_how}): {sum(r is not None for r in wp)} of {len(wp)} window{'' if len(wp) == 1 else 's'} restored inside a rectangle"
+                f"{': ' + ', '.join('%d:%d:%d:%d' % r for r in kinds[:4]) + (' ...' if len(kinds) > 4 else '') if kinds else ''}")
         ws = vr.stats.get("window_sigma")
         if a.sigma_out is not None:
             from .noise import format_sigmas

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measurements behind DESIGN.md 3.11, 3.13 and 3.14 (run on the MI355X from the repository root).
+"""Measurements behind DESIGN.md 3.11, 3.13, 3.14 and 3.15 (run on the MI355X from the repository root).
 
   kernels : time per pixel of sn_ingest_yuv / sn_egress_yuv / sn_yuv_thumb / sn_yuv_noise_hist (4:2:0 8 bit, 720p x 20 frames; the noise
             histogram on the same frames with noise of sigma 10 as well) beside sn_ingest_u8 / sn_egress_u8 on the same
@@ -11,6 +11,12 @@
             is inverted, so that the stream has a cut every N frames; with --scene_cuts off / auto / listed.
   sigma   : steady-state wall time per 720p window of the pipelined denoiser (Shift-Net-s denoise, one_len 16, bf16) with sigma=10.0 and with
             sigma="auto" (sn_yuv_noise_hist per window; 3.14), runs of the two alternating in one process, the first two windows left out.
+  picture : the active picture (3.15) on a 1920 x 1080 stream whose picture is (0, 138, 1920, 804), bars at black.  --mode forward: steady-state
+            forward time per window of the pipelined restorer (Shift-Net-s, one_len 16, bf16, Y4M held in memory) with picture=None and with
+            picture="auto" (or --picture fixed), runs of the two alternating in one process, the first two windows left out, beside the wall time
+            per window and the time the stager waits for the sums.  --mode kernels: time per pixel of sn_ingest_yuv / sn_egress_yuv on a 1080p and
+            on an 804-row stream beside the _rect entry points with the whole-frame rectangle and with the picture's, and sn_yuv_rowcol_sums beside
+            sn_yuv_thumb on the same payloads, interleaved as in the kernels part; --parent_lib SO adds the two entry points of another build.
 Prints one JSON object per part.
 """
 import argparse
@@ -30,7 +36,7 @@ import torch  # noqa: E402
 
 from shiftnet_amd import lib as L  # noqa: E402
 from shiftnet_amd import restore, synth, y4m  # noqa: E402
-from shiftnet_amd.io_edges import egress_u8, egress_yuv, ingest_u8, ingest_yuv, noise_hist_yuv, thumb_yuv, yuv_fmt  # noqa: E402
+from shiftnet_amd.io_edges import egress_u8, egress_yuv, ingest_u8, ingest_yuv, noise_hist_yuv, rowcol_sums_yuv, thumb_yuv, yuv_fmt  # noqa: E402
 
 
 def summary(v):
@@ -177,9 +183,146 @@ def sigma(a):
                       "window_sigma_auto": [round(s, 3) for s in seen["auto"]], **res}))
 
 
+PICTURE = dict(H=1080, W=1920, rect=(0, 138, 1920, 804))
+
+
+def boxed_1080p(fmt, n_src=8):
+    """n_src payloads of a 1920 x 1080 stream on the device: the blurred synthetic clip at 804 rows inside PICTURE['rect'], bars at black (16 / 128)."""
+    H, W, (x0, y0, w, h) = PICTURE["H"], PICTURE["W"], PICTURE["rect"]
+    blur, _ = synth.blurred_clip(n_src, h, w, seed=2)
+    full = torch.empty((n_src, fmt.frame_bytes(H, W)), dtype=torch.uint8, device="cuda")
+    full[:, :H * W] = 16
+    full[:, H * W:] = 128
+    inner = ingest_u8(torch.from_numpy(blur).cuda(), torch.float32)[0]
+    return egress_yuv(inner, fmt, H, W, dst=full, rect=PICTURE["rect"]), inner
+
+
+def parent_cases(path, fmt, T, H, W, h, w, pay, crop, out_full, out_crop, x_full, x_crop, dst_full, dst_crop):
+    """sn_ingest_yuv / sn_egress_yuv of ANOTHER build of csrc/sn_yuv.hip (--parent_lib: the parent commit's, compiled on its own into a shared
+    library), called through ctypes on the same tensors, so that the two builds are timed interleaved in one process."""
+    if not path:
+        return {}
+    import ctypes as C
+    lib = C.CDLL(os.path.abspath(path))
+    vp, ci = C.c_void_p, C.c_int
+    lib.sn_ingest_yuv.argtypes = [vp, C.POINTER(L.YuvFmt), vp, ci, ci, ci, ci, ci, ci, vp]
+    lib.sn_egress_yuv.argtypes = [vp, ci, C.POINTER(L.YuvFmt), vp, ci, ci, ci, ci, ci, vp]
+    st = lambda: torch.cuda.current_stream().cuda_stream      # noqa: E731
+
+    def ing(p, x, hh, ww):
+        return lambda: L.check(lib.sn_ingest_yuv(p.data_ptr(), fmt, x.data_ptr(), L.SN_BF16, T, hh, ww, hh, ww, st()), "parent sn_ingest_yuv")
+
+    def egr(o, d, hh, ww):
+        return lambda: L.check(lib.sn_egress_yuv(o.data_ptr(), L.SN_BF16, fmt, d.data_ptr(), T, hh, ww, hh, ww, st()), "parent sn_egress_yuv")
+    return {"parent_ingest_yuv_1080": (T * H * W, ing(pay, x_full, H, W)), "parent_ingest_yuv_804": (T * h * w, ing(crop, x_crop, h, w)),
+            "parent_egress_yuv_1080": (T * H * W, egr(out_full, dst_full, H, W)), "parent_egress_yuv_804": (T * h * w, egr(out_crop, dst_crop, h, w))}
+
+
+def picture_kernels(a):
+    T, H, W, rect = 8, PICTURE["H"], PICTURE["W"], PICTURE["rect"]
+    h, w = rect[3], rect[2]
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    pay, inner = boxed_1080p(fmt, T)
+    whole = (0, 0, W, H)
+    crop = egress_yuv(inner, fmt, h, w)                                              # the cropped stream: 804 rows, the same pixel count as the rectangle
+    rgb_full = ingest_yuv(pay, fmt, H, W, H, W, torch.float32)[0]
+    out_full, out_crop = rgb_full.to(torch.bfloat16), inner.to(torch.bfloat16)
+    x_full = torch.empty((1, T, 3, H, W), dtype=torch.bfloat16, device="cuda")
+    x_crop = torch.empty((1, T, 3, h, w), dtype=torch.bfloat16, device="cuda")
+    dst_full, dst_crop = torch.empty_like(pay), torch.empty_like(crop)
+    thumbs = torch.empty((T, (H + 7) // 8, (W + 7) // 8), dtype=torch.uint16, device="cuda")
+    rows, cols = torch.empty((T, H), dtype=torch.uint32, device="cuda"), torch.empty((T, W), dtype=torch.uint32, device="cuda")
+    cases = {                                                                        # name: (pixels per launch, the launch)
+        "ingest_yuv_1080": (T * H * W, lambda: ingest_yuv(pay, fmt, H, W, H, W, torch.bfloat16, out=x_full)),
+        "ingest_yuv_rect_whole_1080": (T * H * W, lambda: ingest_yuv(pay, fmt, H, W, H, W, torch.bfloat16, out=x_full, rect=whole)),
+        "ingest_yuv_804": (T * h * w, lambda: ingest_yuv(crop, fmt, h, w, h, w, torch.bfloat16, out=x_crop)),
+        "ingest_yuv_rect_804_of_1080": (T * h * w, lambda: ingest_yuv(pay, fmt, H, W, h, w, torch.bfloat16, out=x_crop, rect=rect)),
+        "egress_yuv_1080": (T * H * W, lambda: egress_yuv(out_full, fmt, H, W, dst=dst_full)),
+        "egress_yuv_rect_whole_1080": (T * H * W, lambda: egress_yuv(out_full, fmt, H, W, dst=dst_full, rect=whole)),
+        "egress_yuv_804": (T * h * w, lambda: egress_yuv(out_crop, fmt, h, w, dst=dst_crop)),
+        "egress_yuv_rect_804_of_1080": (T * h * w, lambda: egress_yuv(out_crop, fmt, H, W, dst=dst_full, rect=rect)),
+        **parent_cases(a.parent_lib, fmt, T, H, W, h, w, pay, crop, out_full, out_crop, x_full, x_crop, dst_full, dst_crop),
+        "d2d_copy_payloads_1080": (T * H * W, lambda: dst_full.copy_(pay, non_blocking=True)),       # what _run adds per restored frame of a rectangle
+        "thumb_yuv_1080": (T * H * W, lambda: thumb_yuv(pay, fmt, H, W, out=thumbs)),
+        "rowcol_sums_yuv_1080": (T * H * W, lambda: rowcol_sums_yuv(pay, fmt, H, W, out_rows=rows, out_cols=cols)),
+    }
+    for _, f in cases.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in cases}
+    for _ in range(a.reps):
+        for k, (_, f) in cases.items():                                              # interleaved: every repetition times every kernel
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.inner):
+                f()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.inner)
+    res = {k: {"us_per_frame": summary([m * 1e3 / T for m in v]), "ps_per_pixel": summary([m * 1e9 / cases[k][0] for m in v])} for k, v in ms.items()}
+    print(json.dumps({"part": "picture", "mode": "kernels", "frames": T, "size": [H, W], "rect": list(rect), "reps": a.reps, "inner": a.inner,
+                      "note": "rowcol_sums includes its two memsets", **res}))
+
+
+def picture_forward(a):
+    H, W, rect, one_len, nwin = PICTURE["H"], PICTURE["W"], PICTURE["rect"], 16, a.windows
+    n = one_len * nwin
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    pay8 = boxed_1080p(fmt, 8)[0].cpu().numpy()
+    hd = y4m.Y4MHeader(width=W, height=H, chroma="420jpeg")
+    buf = io.BytesIO()
+    wr = y4m.Y4MWriter(buf, hd)
+    for i in range(n):
+        j = i % 14
+        wr.write(pay8[j if j < 8 else 14 - j])
+    data = buf.getvalue()
+    net = restore.load_net("deblur_small", "synthetic", "bf16")
+    pic = "auto" if a.picture == "auto" else rect
+    seen = {}
+
+    def run(picture):
+        vr = restore.VideoRestorer(net, one_len, pipeline=True, picture=picture)
+        stamps = []
+        t0 = time.perf_counter()
+        for i, _ in enumerate(vr.restore(y4m.Y4MReader(io.BytesIO(data)), fmt, H, W)):
+            if (i + 1) % one_len == 0:
+                stamps.append(time.perf_counter())
+        total = time.perf_counter() - t0
+        seen[str(picture)] = vr.stats["window_picture"]
+        gaps = [(b - c) * 1e3 for b, c in zip(stamps[1:], stamps[:-1])]
+        return {"total_s": total, "window_wall_ms": gaps[1:], "window_forward_ms": vr.stats["window_forward_ms"][2:],
+                "stager_wait_ms": vr.stats.get("picture_wait_ms", [])[2:]}
+
+    run(None)                                                                        # warm-up: code objects, engine buffers and plans of both sizes
+    run(pic)
+    runs = {"full": [], "picture": []}
+    for _ in range(a.runs):
+        runs["full"].append(run(None))
+        runs["picture"].append(run(pic))
+    res = {}
+    for k, rs in runs.items():
+        res[k] = {"window_forward_ms": summary([g for r in rs for g in r["window_forward_ms"]]),
+                  "window_forward_ms_per_run": [round(statistics.median(r["window_forward_ms"]), 2) for r in rs],
+                  "window_wall_ms": summary([g for r in rs for g in r["window_wall_ms"]]),
+                  "window_wall_ms_per_run": [round(statistics.median(r["window_wall_ms"]), 2) for r in rs],
+                  "total_s": [round(r["total_s"], 3) for r in rs]}
+        w = [g for r in rs for g in r["stager_wait_ms"]]
+        if w:
+            res[k]["stager_wait_ms"] = summary(w)
+    ratio = res["picture"]["window_forward_ms"]["median"] / res["full"]["window_forward_ms"]["median"]
+    print(json.dumps({"part": "picture", "mode": "forward", "variant": "deblur_small", "dtype": "bf16", "one_len": one_len, "windows": nwin, "size": [H, W],
+                      "rect": list(rect), "picture": a.picture, "runs": a.runs, "pixel_ratio": rect[2] * rect[3] / (H * W), "forward_ratio": ratio,
+                      "window_picture": [None if r is None else list(r) for r in seen[str(pic)][:3]], **res}))
+
+
+def picture_part(a):
+    {"forward": picture_forward, "kernels": picture_kernels}[a.mode](a)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=["kernels", "pipeline", "sigma"])
+    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture"])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--inner", type=int, default=200)
     ap.add_argument("--windows", type=int, default=8)
@@ -187,6 +330,10 @@ if __name__ == "__main__":
     ap.add_argument("--only", choices=["both", "pipelined", "serial"], default="both", help="pipeline part: one mode only (for a kernel trace of its own)")
     ap.add_argument("--scene_cuts", choices=["off", "auto", "listed"], default="off", help="pipeline part: VideoRestorer(scene_cuts=...)")
     ap.add_argument("--cut_every", type=int, default=0, help="pipeline part: a cut every N frames in the stream (0: none)")
+    ap.add_argument("--parent_lib", default=None, metavar="SO", help="picture part, kernels mode: a shared library built from another commit's csrc/sn_yuv.hip "
+                    "alone; its sn_ingest_yuv / sn_egress_yuv are timed beside this build's")
+    ap.add_argument("--mode", choices=["forward", "kernels"], default="forward", help="picture part: which measurement")
+    ap.add_argument("--picture", choices=["auto", "fixed"], default="auto", help="picture part, forward mode: VideoRestorer(picture='auto') or the rectangle itself")
     a = ap.parse_args()
     with torch.no_grad():
-        {"kernels": kernels, "pipeline": pipeline, "sigma": sigma}[a.part](a)
+        {"kernels": kernels, "pipeline": pipeline, "sigma": sigma, "picture": picture_part}[a.part](a)
