@@ -14,7 +14,7 @@ import ctypes as C
 import os
 from collections import OrderedDict
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -32,6 +32,15 @@ class Act:
     @property
     def dims(self) -> Tuple[int, int, int, int]:
         return tuple(self.t.shape)  # type: ignore[return-value]
+
+
+class Route(NamedTuple):
+    """How the GSTS units of a tensor run (Engine.route): decided once per unit, read by naf_buffers and by every step that issues a launch."""
+    fused: bool       # phase 1 is ONE kernel (sn_gsts_cab2_phase1 / sn_cab1_phase1), not the two-kernel bf16 chain
+    fold: bool        # ... and its squeeze-excite tail finishes CALayer2: no sn_ca_mlp launch
+    k4: bool          # the CAB2's phase 2 runs inside the CAB1's phase 1: four launches per unit (k4_fused)
+    mstencil: bool    # chain: the depthwise RepConv (C = 64) as a Toeplitz-MFMA 5x5 on a channel-planar g1
+    g1_store: bool    # fused denoisers: the sums pass stores its g1 rows and the main pass reads them back
 
 
 def _dtype_code(dt: torch.dtype) -> int:
@@ -213,7 +222,6 @@ class Engine:
         self.prof: Optional[list] = None      # bench.py attaches a list to collect (fn, label, meta, ev0, ev1)
         self._meta: Tuple = ()
         self._unit: Optional[Tuple] = None    # (T, h, w, c, mode) while the launches of a CAB2 / CAB1 of a GSTS unit are being issued
-        self._k4_meta: Tuple = ()             # profiler meta of the CAB2 whose phase 2 runs inside the CAB1's phase 1 (gsts_unit)
         self.split = None                     # temporal_split.TemporalSplit: this engine holds a frame range of a longer window
         self._side = None                     # side stream of the halo exchanges (created on first use)
         self._tickets = None                  # sn_se_fold frame counters: zero between launches (the kernels re-arm them)
@@ -251,12 +259,6 @@ class Engine:
         meta = self._meta
         if self._unit is not None and not (meta and meta[0] == "naf"):       # a kernel of the unit with its own meta (the fp32 engine's operators)
             meta = tuple(meta) + ("unit",) + self._unit
-        if fn == "sn_cab2_phase2_cab1_phase1":
-            # The fused launch IS the CAB1's phase 1 (plus the CAB2's phase 2 inside its stagers): its time is recorded as sn_cab1_phase1.  The
-            # consumers of these records count a finished CAB -- and through it the window's units and their algorithmic bytes -- by its phase-2
-            # record, so the CAB2 gets one of zero length (the same event twice): the unit count stays what it is and no time is counted twice.
-            self.prof.append(("sn_gsts_cab2_phase2", "sn_gsts_cab2_phase2 [in sn_cab1_phase1]", self._k4_meta, e0, e0))
-            fn = "sn_cab1_phase1"
         self.prof.append((fn, label, meta, e0, e1))
 
     act_dtype = torch.bfloat16
@@ -334,12 +336,14 @@ class Engine:
             return out_act, pool_buf, h_out * w_out
         return out_act
 
-    def ca_mlp(self, name: str, pool: torch.Tensor, npix: int) -> torch.Tensor:
+    def ca_mlp(self, name: str, pool: torch.Tensor, npix: int, *, out: Optional[torch.Tensor] = None, frames: Optional[Tuple[int, int]] = None, guard: Optional[int] = None) -> torch.Tensor:
+        """Squeeze-excite MLP: partial channel sums pool [T][nblk][cpad] -> scales [T][cpad] in `out` (or a new tensor), of `frames` = (f0, n) only if given."""
         p = self.P.cas[name]
         T, nblk, cpad = pool.shape
-        ca = torch.empty((T, cpad), dtype=torch.float32, device=self.dev)
-        self._call("sn_ca_mlp", f"sn_ca_mlp[{name}]", pool.data_ptr(), nblk, cpad, p["c"], p["cr"], 1.0 / npix, p["wa"].data_ptr(),
-                                   p["wb"].data_ptr(), ca.data_ptr(), T, None, self._stream())
+        ca = out if out is not None else torch.empty((T, cpad), dtype=torch.float32, device=self.dev)
+        f0, n = frames if frames is not None else (0, T)
+        self._call("sn_ca_mlp", f"sn_ca_mlp[{name}]", pool.data_ptr() + f0 * nblk * cpad * 4, nblk, cpad, p["c"], p["cr"], 1.0 / npix, p["wa"].data_ptr(),
+                   p["wb"].data_ptr(), ca.data_ptr() + f0 * cpad * 4, n, guard, self._stream())
         return ca
 
     # ---- blocks (oracle/shiftnet_oracle.py has the same names) ----------------------------------------------
@@ -549,109 +553,97 @@ class Engine:
         return not (self.V.denoise and not self._fold_ok(T))
 
     def k4_fused(self, T: int, c: int) -> bool:
-        """Does gsts_unit run the CAB2's phase 2 inside the CAB1's phase 1?  The fused launch exists for C = 64 without the denoisers' inner
-        CALayer2 (C = 80 -- two stager waves, two lanes per pixel, 149 KB of LDS -- and the denoisers' two passes keep the five launches), it needs
-        the CAB2's squeeze-excite scale on the device before it starts (the fold: the tail of the CAB2's phase 1 wrote it) and takes whole
-        tensors only: no temporal split, no batch of clips, and the unit schedule (frame / streams launch frame ranges through naf).  The range
-        guard's move to the bf16 chain (phase1 "0") switches it off with the fused phase 1."""
+        """Route.k4: does gsts_unit run the CAB2's phase 2 inside the CAB1's phase 1?  The fused launch exists for C = 64 without the denoisers'
+        inner CALayer2 (C = 80 and the denoisers' two passes keep the five launches), it needs the CAB2's squeeze-excite scale on the device before
+        it starts (the fold: the tail of the CAB2's phase 1 wrote it) and takes whole tensors only: no temporal split, no batch of clips, and the unit
+        schedule (frame / streams launch frame ranges through naf).  The range guard's move to the bf16 chain (phase1 "0") switches it off too."""
         return (self.k4_fuse == "1" and self._fused_phase1(T) and self._fold_ok(T) and c == 64 and not self.V.denoise and self.split is None
                 and not self._clip and self.schedule == "unit")
 
-    def naf(self, pre: str, x: Act, mode: int, *, frames: Optional[Tuple[int, int]] = None, bufs: Optional[Dict[str, torch.Tensor]] = None,
-            defer_k4: bool = False, k4: Optional[Tuple] = None):
+    def route(self, T: int, c: int) -> Route:
+        """The route of the GSTS units of a [T, h, w, c] tensor under this engine's switches and state: the one place that decides it."""
+        fused = self._fused_phase1(T)                    # phase 1 in ONE kernel: neither a, g1 nor r leave the CU
+        return Route(fused, fused and self._fold_ok(T), self.k4_fused(T, c), not self.V.grouped_rep, fused and self.V.denoise and self.g1_store)
+
+    # ---- one stage of a CAB2 / CAB1 each, for one piece (src; f0, n: its frames for the operators that take plain pointers) on the tensors B of naf_buffers
+    def _k0(self, pre: str, src: L.UnitSrc, B: Dict[str, torch.Tensor], st: int) -> None:
+        """K0 (CAB2): conv1 of the spatially shifted borrowed half -> hwb."""
+        fn = "sn_gsts_shiftconv_mfma" if self.k0_mfma and self.P.k0_mfma_ok else "sn_gsts_shiftconv"
+        self._call(fn, "sn_gsts_shiftconv", C.byref(src), self.P.offs.data_ptr(), self.P.units[pre]["w1"].data_ptr(), B["hwb"].data_ptr(), st)
+
+    def _se_fold(self, name: str, T: int, ca: torch.Tensor):
+        """sn_se_fold operand: the last workgroup of each frame of a fused phase 1 finishes the squeeze-excite MLP `name` into ca."""
+        q = self.P.cas[name]
+        return C.byref(L.SeFold(q["wa"].data_ptr(), q["wb"].data_ptr(), q["c"], q["cr"], self._ticket_ptr(T), ca.data_ptr(), self._guard_ptr()))
+
+    def _phase1(self, pre: str, r: Route, src: L.UnitSrc, f0: int, n: int, B: Dict[str, torch.Tensor], st: int) -> bool:
+        """Phase 1: g2 and the partial channel sums of CALayer2 (pool2).  True if the fold has also finished its scale ca2."""
+        V, u = self.V, self.P.units[pre]
+        if r.fused:
+            fn = "sn_gsts_cab2_phase1" if src.mode else "sn_cab1_phase1"
+            def args(g2_ptr, se, opt):     # the two entry points differ by K0's output, which only the CAB2 reads
+                return (C.byref(src),) + ((B["hwb"].data_ptr(),) if src.mode else ()) + (C.byref(u["p1r"]["desc"]), g2_ptr, B["pool2"].data_ptr(), se, opt, st)
+            opt = None
+            if V.denoise:      # inner CALayer2 on g1 (gshift_denoise1.py:224,257): pass 1 = the channel sums of g1 and, by the tail, its scale ca1
+                g1s = B["g1s"].data_ptr() if r.g1_store else None
+                self._call(fn, fn + "[g1 sums]", *args(None, self._se_fold(pre + "ca1", src.T, B["ca1"]), C.byref(L.Phase1Opts(None, 1, 0, g1s))))
+                opt = C.byref(L.Phase1Opts(B["ca1"].data_ptr(), 0, 0, g1s))
+            self._call(fn, fn, *args(B["g2"].data_ptr(), self._se_fold(pre + "ca2", src.T, B["ca2"]) if r.fold else None, opt))
+            return r.fold
+        g1, g2, pool1, pool2, h, w, c, es = B["g1"], B["g2"], B.get("pool1"), B["pool2"], src.h, src.w, src.C, 2      # es: bytes per activation element
+        self._call("sn_ln_gemm_gate", "sn_ln_gemm_gate", C.byref(src), B["hwb"].data_ptr() if src.mode else None, u["w_ln"].data_ptr(), u["b_ln"].data_ptr(),
+                   u["w_dw3_h2"].data_ptr(), g1.data_ptr(), pool1.data_ptr() if pool1 is not None else None, 2 if r.mstencil else 0, st)
+        ca1_ptr = self.ca_mlp(pre + "ca1", pool1, h * w, out=B["ca1"], frames=(f0, n), guard=self._guard_ptr()).data_ptr() + f0 * c * 4 if V.denoise else None
+        k3 = "sn_dw5m_gemm_gate" if r.mstencil else "sn_grp5_gemm_gate"
+        self._call(k3, k3, g1.data_ptr() + g1.stride(0) * es * f0, ca1_ptr, u["w_toep5" if r.mstencil else "w_grp"].data_ptr(), u["w_gate"].data_ptr(),
+                   g2.data_ptr() + g2.stride(0) * es * f0, pool2.data_ptr() + f0 * pool2.stride(0) * 4, n, h, w, c, st)
+        return False
+
+    def _phase2_args(self, pre: str, src: L.UnitSrc, B: Dict[str, torch.Tensor]) -> Tuple:
+        u = self.P.units[pre]
+        return C.byref(src), B["g2"].data_ptr(), B["ca2"].data_ptr(), u["w_out"].data_ptr(), u["b_out"].data_ptr() if u["b_out"] is not None else None, B["y"].data_ptr()
+
+    def _phase2(self, pre: str, src: L.UnitSrc, B: Dict[str, torch.Tensor], st: int) -> None:
+        """Phase 2 (K4): y = shortcut + beta * (1x1 of ca2 * g2)."""
+        fn = "sn_gsts_cab2_phase2" if src.mode else "sn_cab1_phase2"
+        self._call(fn, fn, *self._phase2_args(pre, src, B), st)
+
+    def _cab2_phase2_cab1_phase1(self, pre2: str, src2: L.UnitSrc, B2: Dict[str, torch.Tensor], meta2: Tuple, pre1: str, B1: Dict[str, torch.Tensor], st: int) -> None:
+        """The CAB2's phase 2 inside the stager waves of the CAB1's phase 1 (Route.k4): writes the CAB2's y and the CAB1's g2, pool2 and ca2."""
+        fn = "sn_cab2_phase2_cab1_phase1"
+        self._call(fn, fn, *self._phase2_args(pre2, src2, B2), C.byref(self.P.units[pre1]["p1r"]["desc"]), B1["g2"].data_ptr(), B1["pool2"].data_ptr(),
+                   self._se_fold(pre1 + "ca2", src2.T, B1["ca2"]), None, st)
+        if self.prof is not None:
+            # The fused launch IS the CAB1's phase 1 (plus the CAB2's phase 2 in its stagers): its time is recorded as sn_cab1_phase1.  The consumers of these
+            # records count a finished CAB -- and so the window's units and their bytes -- by its phase-2 record: the CAB2 gets one of zero length (one event twice).
+            _, label, meta, e0, e1 = self.prof.pop()
+            self.prof += [("sn_gsts_cab2_phase2", "sn_gsts_cab2_phase2 [in sn_cab1_phase1]", meta2, e0, e0), ("sn_cab1_phase1", label, meta, e0, e1)]
+
+    def naf(self, pre: str, x: Act, mode: int, *, frames: Optional[Tuple[int, int]] = None, bufs: Optional[Dict[str, torch.Tensor]] = None) -> Act:
         """CAB2 (mode 1/2, fed by the GSTS gather of x) or CAB1 (mode 0) (gshift_deblur1.py:183-255).
 
-        Phase 1: [K0 sn_gsts_shiftconv (CAB2 only)] -> sn_gsts_cab2_phase1 / sn_cab1_phase1 (ONE kernel up to g2; the denoisers run it twice, the first
-        pass for the channel sums of g1 behind their inner CALayer2), or -- phase1 "0" -- K12 sn_ln_gemm_gate -> K3 (sn_dw5m_gemm_gate depthwise,
-        sn_grp5_gemm_gate for the grouped "+" RepConv) with g1 in bf16 through HBM; then the squeeze-excite MLP (folded into phase 1's last
-        workgroup per frame, or sn_ca_mlp) and phase 2, K4 sn_gsts_cab2_phase2 / sn_cab1_phase2.  The global average pool of CALayer2 sits
-        between the phases and forbids a single pass.  Every frame is independent inside a CAB (the pool is per frame), so
-        on a temporally split window the chain runs in two pieces: all frames but the boundary one while the halo exchange is in flight, then
-        the boundary frame.  frames = (t0, nt) / bufs: one frame range of a block whose tensors the caller owns (the frame-wavefront schedule).
-        defer_k4 / k4 (gsts_unit only, see k4_fused): a CAB2 stops before its K4 and returns that launch's operands; the CAB1 given them runs
-        sn_cab2_phase2_cab1_phase1 in place of its phase 1, with x the CAB2's output tensor, written by that launch."""
-        lib, V, P = self.lib, self.V, self.P
-        u = P.units[pre]
+        [K0 (CAB2 only)] -> phase 1 up to g2 (ONE kernel, which the denoisers run twice, or -- phase1 "0" -- the bf16 chain K12 -> K3) -> the squeeze-excite
+        MLP (folded into phase 1's last workgroup per frame, or sn_ca_mlp) -> phase 2, K4.  The global average pool of CALayer2 sits between the phases
+        and forbids a single pass.  Every frame is independent inside a CAB (the pool is per frame), so a temporally split window runs
+        the steps for two pieces: all frames but the boundary one while the halo exchange is in flight, then the boundary frame.  frames = (t0, nt) /
+        bufs: one frame range of a block whose tensors the caller owns (the frame-wavefront and streams schedules)."""
         T, h, w, c = x.dims
+        r = self.route(T, c)
         self._meta = ("naf", frames[1] if frames is not None else T, h, w, c, mode, T)      # (frames of this launch group, ..., frames of the tensor)
-        fused = self._fused_phase1(T)                    # phase 1 in ONE kernel: neither a, g1 nor r leave the CU
-        mstencil = not V.grouped_rep                     # chain: depthwise RepConv (C = 64) as a Toeplitz-MFMA 5x5 on a channel-planar g1
         B = bufs if bufs is not None else self.naf_buffers(T, h, w, c, mode)
-        hwb, g2, y, pool2, ca2, ca1, g1, pool1, g1s = (B.get(k) for k in ("hwb", "g2", "y", "pool2", "ca2", "ca1", "g1", "pool1", "g1s"))
-        nb2 = pool2.shape[1]
-        tickets = self._ticket_ptr(T) if fused and self._fold_ok(T) else None
-        b_out = u["b_out"].data_ptr() if u["b_out"] is not None else None
-        es = 2                                           # bytes per activation element
-        bad = self._guard_ptr()
-
-        def ca_mlp(name: str, pool: torch.Tensor, ca: torch.Tensor, f0: int, n: int) -> None:
-            q = P.cas[name]
-            nblk = pool.shape[1]
-            self._call("sn_ca_mlp", f"sn_ca_mlp[{name}]", pool.data_ptr() + f0 * nblk * c * 4, nblk, c, q["c"], q["cr"], 1.0 / (h * w),
-                       q["wa"].data_ptr(), q["wb"].data_ptr(), ca.data_ptr() + f0 * c * 4, n, bad, self._stream())
-
-        if frames is not None:
-            assert self.split is None
-            pieces = [(self._wrap_flag(mode, V.wrap) if mode else 0, None, frames[0], frames[1])]
-        else:
-            pieces = self._split_pieces(x, mode, V.wrap) if mode else [(0, None, 0, 0)]
+        assert frames is None or self.split is None
+        pieces = ([(self._wrap_flag(mode, self.V.wrap) if mode else 0, None, frames[0], frames[1])] if frames is not None
+                  else self._split_pieces(x, mode, self.V.wrap) if mode else [(0, None, 0, 0)])
         for wrap, halo, t0, nt in pieces:
             st = self._stream()
             src = self._unit_src(x, mode, wrap=wrap, halo=halo, t0=t0, nt=nt)
-            f0, n = (t0, nt) if nt else (0, T)           # frame range of this piece for the operators that take plain pointers
+            f0, n = (t0, nt) if nt else (0, T)
             if mode:
-                if self.k0_mfma and P.k0_mfma_ok:
-                    self._call("sn_gsts_shiftconv_mfma", "sn_gsts_shiftconv", C.byref(src), P.offs.data_ptr(), u["w1"].data_ptr(), hwb.data_ptr(), st)
-                else:
-                    self._call("sn_gsts_shiftconv", "sn_gsts_shiftconv", C.byref(src), P.offs.data_ptr(), u["w1"].data_ptr(), hwb.data_ptr(), st)
-            hw_ptr = hwb.data_ptr() if mode else None
-            folded = False
-            if fused:
-                wt = C.byref(u["p1r"]["desc"])
-                sep = None
-                if tickets is not None:
-                    q = P.cas[pre + "ca2"]
-                    se = L.SeFold(q["wa"].data_ptr(), q["wb"].data_ptr(), q["c"], q["cr"], tickets, ca2.data_ptr(), bad)
-                    sep = C.byref(se)
-                opt = None
-                if V.denoise:      # inner CALayer2 on g1 (gshift_denoise1.py:224,257): pass 1 = the channel sums of g1 and, by the tail, its scale ca1
-                    q1 = P.cas[pre + "ca1"]
-                    se1 = L.SeFold(q1["wa"].data_ptr(), q1["wb"].data_ptr(), q1["c"], q1["cr"], tickets, ca1.data_ptr(), bad)
-                    g1s_ptr = g1s.data_ptr() if (g1s is not None and self.g1_store) else None
-                    o1 = L.Phase1Opts(None, 1, 0, g1s_ptr)
-                    fn1 = "sn_gsts_cab2_phase1" if mode else "sn_cab1_phase1"
-                    a1 = (C.byref(src), hw_ptr, wt, None, pool2.data_ptr(), C.byref(se1), C.byref(o1), st) if mode else \
-                         (C.byref(src), wt, None, pool2.data_ptr(), C.byref(se1), C.byref(o1), st)
-                    self._call(fn1, fn1 + "[g1 sums]", *a1)
-                    opt = C.byref(L.Phase1Opts(ca1.data_ptr(), 0, 0, g1s_ptr))
-                if mode:
-                    self._call("sn_gsts_cab2_phase1", "sn_gsts_cab2_phase1", C.byref(src), hw_ptr, wt, g2.data_ptr(), pool2.data_ptr(), sep, opt, st)
-                elif k4 is not None:
-                    src2, g2_2, ca2_2, w_out2, b_out2, self._k4_meta = k4[:6]
-                    self._call("sn_cab2_phase2_cab1_phase1", "sn_cab2_phase2_cab1_phase1", C.byref(src2), g2_2.data_ptr(), ca2_2.data_ptr(), w_out2.data_ptr(),
-                               b_out2, x.t.data_ptr(), wt, g2.data_ptr(), pool2.data_ptr(), sep, None, st)
-                else:
-                    self._call("sn_cab1_phase1", "sn_cab1_phase1", C.byref(src), wt, g2.data_ptr(), pool2.data_ptr(), sep, opt, st)
-                folded = sep is not None
-            else:
-                self._call("sn_ln_gemm_gate", "sn_ln_gemm_gate", C.byref(src), hw_ptr, u["w_ln"].data_ptr(), u["b_ln"].data_ptr(),
-                           u["w_dw3_h2"].data_ptr(), g1.data_ptr(), pool1.data_ptr() if pool1 is not None else None, 2 if mstencil else 0, st)
-                ca1_ptr = None
-                if V.denoise:
-                    ca_mlp(pre + "ca1", pool1, ca1, f0, n)
-                    ca1_ptr = ca1.data_ptr() + f0 * c * 4
-                fr1 = g1.stride(0) * es * f0
-                fr2 = g2.stride(0) * es * f0
-                k3 = "sn_dw5m_gemm_gate" if mstencil else "sn_grp5_gemm_gate"
-                self._call(k3, k3, g1.data_ptr() + fr1, ca1_ptr, u["w_toep5" if mstencil else "w_grp"].data_ptr(), u["w_gate"].data_ptr(),
-                           g2.data_ptr() + fr2, pool2.data_ptr() + f0 * nb2 * c * 4, n, h, w, c, st)
-            if not folded:
-                ca_mlp(pre + "ca2", pool2, ca2, f0, n)
-            if defer_k4:         # (one piece: no split.  B rides along: the tensors stay referenced until the fused launch is issued)
-                return Act(y, c), (src, g2, ca2, u["w_out"], b_out, self._meta, B)
-            fn4 = "sn_gsts_cab2_phase2" if mode else "sn_cab1_phase2"
-            self._call(fn4, fn4, C.byref(src), g2.data_ptr(), ca2.data_ptr(), u["w_out"].data_ptr(), b_out, y.data_ptr(), st)
-        return Act(y, c)
+                self._k0(pre, src, B, st)
+            if not self._phase1(pre, r, src, f0, n, B, st):
+                self.ca_mlp(pre + "ca2", B["pool2"], h * w, out=B["ca2"], frames=(f0, n), guard=self._guard_ptr())
+            self._phase2(pre, src, B, st)
+        return Act(B["y"], c)
 
     def naf_buffers(self, T: int, h: int, w: int, c: int, mode: int) -> Dict[str, torch.Tensor]:
         """The tensors one CAB2 / CAB1 writes: hwb (conv1 of the shifted half, CAB2), g2, y, the partial channel sums and the squeeze-excite
@@ -659,25 +651,23 @@ class Engine:
         referenced by the caller until the block's launches are issued: a temporary would go back to the caching allocator at once and a
         tensor K3 WRITES could be carved out of the block K3 still READS its scale from (intermittent wrong frames at the small pyramid
         levels; found by the full-size determinism check of config 4)."""
-        lib, V = self.lib, self.V
-        fused = self._fused_phase1(T)
-        mstencil = not V.grouped_rep
+        lib, V, r = self.lib, self.V, self.route(T, c)
         B: Dict[str, torch.Tensor] = {}
         if mode:
             B["hwb"] = self._new(T, h, w, c // 2)
         B["g2"] = self._new(T, h, w, c)
         B["y"] = self._new(T, h, w, c)
-        if fused:
+        if r.fused:
             nb2 = lib.sn_phase1_pool_blocks(T, h, w)
             if nb2 < 1:
                 raise L.ShiftNetLibError(f"sn_phase1_pool_blocks failed with code {nb2}")
-            if V.denoise and self.g1_store:
+            if r.g1_store:
                 nbytes = C.c_longlong(0)
                 L.check(lib.sn_phase1_g1_store_bytes(T, h, w, c, C.byref(nbytes)), "sn_phase1_g1_store_bytes")
                 B["g1s"] = torch.empty((nbytes.value,), dtype=torch.uint8, device=self.dev)
         else:
-            B["g1"] = (torch.empty((T, h, c, lib.sn_planar_pitch(w)), dtype=torch.bfloat16, device=self.dev) if mstencil else self._new(T, h, w, c))
-            nb2 = lib.sn_dw5m_blocks(h, w) if mstencil else lib.sn_grp5_blocks(h, w)
+            B["g1"] = (torch.empty((T, h, c, lib.sn_planar_pitch(w)), dtype=torch.bfloat16, device=self.dev) if r.mstencil else self._new(T, h, w, c))
+            nb2 = lib.sn_dw5m_blocks(h, w) if r.mstencil else lib.sn_grp5_blocks(h, w)
             if V.denoise:
                 B["pool1"] = torch.empty((T, lib.sn_lngate_blocks(h, w), c), dtype=torch.float32, device=self.dev)
         if V.denoise:
@@ -687,10 +677,20 @@ class Engine:
         return B
 
     def gsts_unit(self, pre: str, x: Act, reverse: bool) -> Act:
-        if self.k4_fused(x.dims[0], x.c):           # four launches: K0, phase 1 (CAB2), [K4 (CAB2) + phase 1 (CAB1)], K4 (CAB1)
-            y2, k4 = self.naf(pre + "0.", x, 2 if reverse else 1, defer_k4=True)
-            return self.naf(pre + "1.", y2, 0, k4=k4)
-        return self.naf(pre + "1.", self.naf(pre + "0.", x, 2 if reverse else 1), 0)
+        """CAB2 (pre + "0.", on the GSTS gather of x) then CAB1 (pre + "1.").  Both CABs' tensors are locals here until the last launch is issued."""
+        mode, (T, h, w, c) = 2 if reverse else 1, x.dims
+        r = self.route(T, c)
+        if not r.k4:
+            return self.naf(pre + "1.", self.naf(pre + "0.", x, mode), 0)
+        B2, B1 = self.naf_buffers(T, h, w, c, mode), self.naf_buffers(T, h, w, c, 0)
+        src2, src1, st = self._unit_src(x, mode), self._unit_src(Act(B2["y"], c), 0, wrap=0), self._stream()
+        self._meta = meta2 = ("naf", T, h, w, c, mode, T)
+        self._k0(pre + "0.", src2, B2, st)
+        self._phase1(pre + "0.", r, src2, 0, T, B2, st)          # (r.k4 implies r.fold: the CAB2's ca2 is on the device)
+        self._meta = ("naf", T, h, w, c, 0, T)
+        self._cab2_phase2_cab1_phase1(pre + "0.", src2, B2, meta2, pre + "1.", B1, st)
+        self._phase2(pre + "1.", src1, B1, st)
+        return Act(B1["y"], c)
 
     def shift_block(self, pre: str, x: Act) -> Act:
         """Encoder_shift_block.forward (gshift_deblur1.py:530-547 / gshift_deblur2.py:521-530)."""
@@ -770,7 +770,7 @@ class Engine:
         streams = self._gstreams[:ng]
         main = torch.cuda.current_stream(self.dev)
         sets = [(self.naf_buffers(T, h, w, c, 1), self.naf_buffers(T, h, w, c, 0)) for _ in range(R)]
-        if self._fused_phase1(T) and self._fold_ok(T):      # allocated on the launching stream, not on a group's
+        if self.route(T, c).fold:                           # allocated on the launching stream, not on a group's
             self._ticket_ptr(T)
         self._guard_ptr()
         ready = main.record_event()
