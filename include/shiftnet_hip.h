@@ -529,6 +529,30 @@ int sn_yuv_noise_hist_rect(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_y
  * 4-byte aligned, src at an odd address at 10 bit. */
 int sn_yuv_rowcol_sums(const uint8_t* src, const sn_yuv_fmt* fmt, uint32_t* rows, uint32_t* cols, int T, int H, int W, void* stream);
 
+/* ---- dithered egress (a new symbol and one new struct, SN_ABI_VERSION stays 20) ------------------------------------------------------------
+ * sn_egress_yuv_dither is sn_egress_yuv (rect == NULL: the whole frame) or sn_egress_yuv_rect (rect != NULL) with one change in the last line
+ * of sn_egress_yuv above.  With mode SN_DITHER_TPDF the code of a sample is
+ *   clamp(rint((off + scale * v) + d), legal codes)        (off, scale) = (yo, ys) for Y, (co, cs) for C; every float32 sum rounded separately
+ * where d is triangular noise of +-1 code (mean 0, variance 1/6), an integer hash of where the sample is:
+ *   f = dither->t0 + t                       the frame number: t counts the payloads of the launch
+ *   p = 0 (Y), 1 (Cb), 2 (Cr)
+ *   (y, x) = the sample's row and column in ITS plane (at 4:2:0 the chroma planes count chroma samples), counted from the picture's first
+ *            sample: the rectangle's origin with rect, so that the rectangle still holds what the cropped stream's egress writes
+ *   k = (y * 0x9E3779B1) ^ (x * 0x85EBCA77) ^ (f * 0xC2B2AE3D) ^ (p * 0x27D4EB2F) ^ seed                  (uint32, products wrap)
+ *   k ^= k >> 16;  k *= 0x85EBCA6B;  k ^= k >> 13;  k *= 0xC2B2AE35;  k ^= k >> 16
+ *   d = float((k & 0xFFF) + ((k >> 12) & 0xFFF) - 4095) / 4096                                            (exact in float32, |d| < 1)
+ * (tests/dither_ref.py restates it in numpy; the kernel equals it bit for bit.)  A launch of T payloads at t0 therefore equals launches of its
+ * parts at their own t0.  With mode SN_DITHER_NONE the launch, the kernel instantiation and the bytes are those of the entry points without
+ * _dither, which launch the instantiations without a dither as before.  The per-thread layout is theirs: 8 x 2 pixels, wide stores where the
+ * address allows, the element-wise path elsewhere; both paths dither.
+ * SN_EINVAL before anything is launched: as sn_egress_yuv / sn_egress_yuv_rect (an illegal rectangle included), and a null dither, a mode
+ * that is neither of the two, or t0 < 0. */
+#define SN_DITHER_NONE 0
+#define SN_DITHER_TPDF 1
+typedef struct sn_yuv_dither { int mode; uint32_t seed; int t0; } sn_yuv_dither;
+int sn_egress_yuv_dither(const void* out, int out_dtype, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */,
+                         const sn_yuv_dither* dither, uint8_t* dst, int T, int H, int W, int Hp, int Wp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

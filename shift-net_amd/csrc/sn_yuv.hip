@@ -4,6 +4,8 @@
 //   sn_ingest_yuv : T payloads [Y plane][U plane][V plane] -> [T][3][Hp][Wp] RGB of the module dtype in [0,1]; pixels outside H x W
 //                   replicate the edge pixel, so one launch gives the network a legal size for any input size;
 //   sn_egress_yuv : [T][3][Hp][Wp] RGB (float32 or module dtype) -> T payloads of H x W (the crop of the padding);
+//   sn_egress_yuv_dither : the same with triangular noise of +-1 code added before the rounding (SN_DITHER_TPDF), an integer hash of the
+//                   sample's position: instantiations of their own of the same kernel, the entry points without _dither launch the others;
 //   sn_yuv_thumb  : T payloads -> [T][ceil(H/8)][ceil(W/8)] uint16 sums of the luma codes of every 8 x 8 block (the scene-cut measure of
 //                   shiftnet_amd/scenes.py is computed from these on the host); integer arithmetic, the chroma planes are not read.
 //   sn_yuv_noise_hist : T payloads -> [T][2 (2^bits - 1) + 1] uint32 histograms of |a - b - c + d| over the 2 x 2 luma blocks whose four codes lie
@@ -257,9 +259,31 @@ __device__ __forceinline__ int quant(float off, float scale, float v, int lo, in
     return imin(imax(__float2int_rn(addr(off, mulr(scale, v))), lo), hi);
 }
 
-template <int ESZ, int CH>
+// The dither of a launch.  DITHER is a template parameter of the kernel: SN_DITHER_NONE carries nothing and every line below that touches a
+// key is dead in it, so the instantiations the entry points without _dither launch are the ones they launched before there was a dither.
+template <int DITHER> struct DitherK {};
+template <> struct DitherK<SN_DITHER_TPDF> { uint32_t seed; uint32_t t0; };
+template <int DITHER> __device__ __forceinline__ uint32_t dither_frame_key(const DitherK<DITHER>&, int) { return 0u; }
+template <> __device__ __forceinline__ uint32_t dither_frame_key<SN_DITHER_TPDF>(const DitherK<SN_DITHER_TPDF>& D, int t) {
+    return ((D.t0 + (uint32_t)t) * 0xC2B2AE3Du) ^ D.seed;
+}
+// plane p, row y of the plane: the part of the key that a row of samples shares (uint32 arithmetic wraps)
+__device__ __forceinline__ uint32_t dither_row_key(uint32_t fk, int p, int y) { return fk ^ ((uint32_t)p * 0x27D4EB2Fu) ^ ((uint32_t)y * 0x9E3779B1u); }
+// the sample at column x of that row: the murmur3 finaliser of the key, two 12-bit fields of it summed to a triangle on (-1, 1); exact in float32
+__device__ __forceinline__ float dither_tpdf(uint32_t rk, int x) {
+    uint32_t k = rk ^ ((uint32_t)x * 0x85EBCA77u);
+    k ^= k >> 16; k *= 0x85EBCA6Bu; k ^= k >> 13; k *= 0xC2B2AE35u; k ^= k >> 16;
+    return mulr((float)((int)(k & 0xFFFu) + (int)((k >> 12) & 0xFFFu) - 4095), 1.0f / 4096.0f);
+}
+// code = clamp(rint((off + scale * v) + d)); without dither the line above
+template <int DITHER> __device__ __forceinline__ int quantd(float off, float scale, float v, int lo, int hi, uint32_t rk, int x) {
+    if (DITHER == SN_DITHER_NONE) return quant(off, scale, v, lo, hi);
+    return imin(imax(__float2int_rn(addr(addr(off, mulr(scale, v)), dither_tpdf(rk, x))), lo), hi);
+}
+
+template <int ESZ, int CH, int DITHER = SN_DITHER_NONE>
 __global__ __launch_bounds__(256) void egress_yuv_kernel(const void* __restrict__ out, int dt, uint8_t* __restrict__ dstp, const YuvK K,
-                                                       const YuvGeo G, int Hp, int Wp, int src_vec) {
+                                                       const YuvGeo G, int Hp, int Wp, int src_vec, const DitherK<DITHER> D) {
     const int t = blockIdx.z;
     const int x0 = (blockIdx.x * 32 + threadIdx.x) * 8, y0 = (blockIdx.y * 8 + threadIdx.y) * 2;
     const int H = G.h, W = G.w, py = G.py, pc = G.pc;
@@ -293,19 +317,21 @@ __global__ __launch_bounds__(256) void egress_yuv_kernel(const void* __restrict_
         }
     }
     const int n = imin(8, W - x0);
+    const uint32_t fk = dither_frame_key<DITHER>(D, t);    // the sample positions count from the picture's first sample: x0, y0 do
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         if (y0 + r >= H) break;
         int q[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) q[k] = quant(K.yo, K.ys, yv[r][1 + k], K.ylo, K.yhi);
+        for (int k = 0; k < 8; ++k) q[k] = quantd<DITHER>(K.yo, K.ys, yv[r][1 + k], K.ylo, K.yhi, dither_row_key(fk, 0, y0 + r), x0 + k);
         const size_t o = (size_t)(y0 + r) * py + x0, oc = (size_t)(y0 + r) * pc + x0;
         if (inner) stn<ESZ, 8>(yp, o, q); else for (int k = 0; k < n; ++k) st1<ESZ>(yp, o + k, q[k]);
         if (CH == SN_YUV_444) {
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) {
 #pragma unroll
-                for (int k = 0; k < 8; ++k) q[k] = quant(K.co, K.cs, pl ? cr[r][1 + k] : cb[r][1 + k], K.clo, K.chi);
+                for (int k = 0; k < 8; ++k)
+                    q[k] = quantd<DITHER>(K.co, K.cs, pl ? cr[r][1 + k] : cb[r][1 + k], K.clo, K.chi, dither_row_key(fk, 1 + pl, y0 + r), x0 + k);
                 if (inner) stn<ESZ, 8>(pl ? vp : up, oc, q); else for (int k = 0; k < n; ++k) st1<ESZ>(pl ? vp : up, oc + k, q[k]);
             }
         }
@@ -326,7 +352,7 @@ __global__ __launch_bounds__(256) void egress_yuv_kernel(const void* __restrict_
                 else                               // (1,2,1)/4 along x centred on the even pixel, (1,1)/2 along y: (((l + 2c) + r)_a + ((l + 2c) + r)_b) / 8
                     m = mulr(0.125f, addr(addr(addr(a[2 * i], mulr(2.f, a[1 + 2 * i])), a[2 + 2 * i]),
                                                     addr(addr(b[2 * i], mulr(2.f, b[1 + 2 * i])), b[2 + 2 * i])));
-                q[i] = quant(K.co, K.cs, m, K.clo, K.chi);
+                q[i] = quantd<DITHER>(K.co, K.cs, m, K.clo, K.chi, dither_row_key(fk, 1 + pl, y0 >> 1), c0 + i);
             }
             if (nc == 4) stn<ESZ, 4>(pl ? vp : up, o, q); else for (int i = 0; i < nc; ++i) st1<ESZ>(pl ? vp : up, o + i, q[i]);
         }
@@ -530,18 +556,21 @@ bool make_geo(const sn_yuv_fmt* f, int H, int W, const sn_yuv_rect* rect, YuvGeo
 
 extern "C" {
 
-#define SN_YUV_DISPATCH(KERNEL, ...)                                                                                       \
+// TAIL: further template arguments after <ESZ, CH>, with their leading comma (empty for the kernels that have none)
+#define SN_YUV_DISPATCH_T(KERNEL, TAIL, ...)                                                                                \
     do {                                                                                                                   \
         if (fmt->bits == 8) {                                                                                              \
-            if (fmt->chroma == SN_YUV_444) hipLaunchKernelGGL((KERNEL<1, SN_YUV_444>), grid, block, 0, s, __VA_ARGS__);      \
-            else if (fmt->chroma == SN_YUV_420_CENTER) hipLaunchKernelGGL((KERNEL<1, SN_YUV_420_CENTER>), grid, block, 0, s, __VA_ARGS__); \
-            else hipLaunchKernelGGL((KERNEL<1, SN_YUV_420_LEFT>), grid, block, 0, s, __VA_ARGS__);                           \
+            if (fmt->chroma == SN_YUV_444) hipLaunchKernelGGL((KERNEL<1, SN_YUV_444 TAIL>), grid, block, 0, s, __VA_ARGS__); \
+            else if (fmt->chroma == SN_YUV_420_CENTER) hipLaunchKernelGGL((KERNEL<1, SN_YUV_420_CENTER TAIL>), grid, block, 0, s, __VA_ARGS__); \
+            else hipLaunchKernelGGL((KERNEL<1, SN_YUV_420_LEFT TAIL>), grid, block, 0, s, __VA_ARGS__);                      \
         } else {                                                                                                           \
-            if (fmt->chroma == SN_YUV_444) hipLaunchKernelGGL((KERNEL<2, SN_YUV_444>), grid, block, 0, s, __VA_ARGS__);      \
-            else if (fmt->chroma == SN_YUV_420_CENTER) hipLaunchKernelGGL((KERNEL<2, SN_YUV_420_CENTER>), grid, block, 0, s, __VA_ARGS__); \
-            else hipLaunchKernelGGL((KERNEL<2, SN_YUV_420_LEFT>), grid, block, 0, s, __VA_ARGS__);                           \
+            if (fmt->chroma == SN_YUV_444) hipLaunchKernelGGL((KERNEL<2, SN_YUV_444 TAIL>), grid, block, 0, s, __VA_ARGS__); \
+            else if (fmt->chroma == SN_YUV_420_CENTER) hipLaunchKernelGGL((KERNEL<2, SN_YUV_420_CENTER TAIL>), grid, block, 0, s, __VA_ARGS__); \
+            else hipLaunchKernelGGL((KERNEL<2, SN_YUV_420_LEFT TAIL>), grid, block, 0, s, __VA_ARGS__);                      \
         }                                                                                                                  \
     } while (0)
+#define SN_YUV_DISPATCH(KERNEL, ...) SN_YUV_DISPATCH_T(KERNEL, , __VA_ARGS__)
+#define SN_YUV_TAIL_TPDF , SN_DITHER_TPDF
 
 static int ingest_yuv(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, void* dst, int dst_dtype, int T, int H, int W, int Hp, int Wp,
                       void* stream) {
@@ -569,8 +598,8 @@ int sn_ingest_yuv_rect(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_r
     return ingest_yuv(src, fmt, rect, dst, dst_dtype, T, H, W, Hp, Wp, stream);
 }
 
-static int egress_yuv(const void* out, int out_dtype, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint8_t* dst, int T, int H, int W, int Hp, int Wp,
-                      void* stream) {
+static int egress_yuv(const void* out, int out_dtype, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const sn_yuv_dither* dither, uint8_t* dst, int T, int H,
+                      int W, int Hp, int Wp, void* stream) {
     sn_clear_error();
     YuvK K;
     YuvGeo G;
@@ -581,18 +610,29 @@ static int egress_yuv(const void* out, int out_dtype, const sn_yuv_fmt* fmt, con
     const dim3 block(32, 8), grid(((G.w + 7) / 8 + 31) / 32, ((G.h + 1) / 2 + 7) / 8, T);
     if (grid.y > 65535) return SN_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    SN_YUV_DISPATCH(egress_yuv_kernel, out, out_dtype, dst, K, G, Hp, Wp, src_vec);
+    if (dither && dither->mode == SN_DITHER_TPDF) {
+        const DitherK<SN_DITHER_TPDF> D{dither->seed, (uint32_t)dither->t0};
+        SN_YUV_DISPATCH_T(egress_yuv_kernel, SN_YUV_TAIL_TPDF, out, out_dtype, dst, K, G, Hp, Wp, src_vec, D);
+    } else {
+        SN_YUV_DISPATCH(egress_yuv_kernel, out, out_dtype, dst, K, G, Hp, Wp, src_vec, DitherK<SN_DITHER_NONE>{});
+    }
     return sn_check_launch();
 }
 
 int sn_egress_yuv(const void* out, int out_dtype, const sn_yuv_fmt* fmt, uint8_t* dst, int T, int H, int W, int Hp, int Wp, void* stream) {
-    return egress_yuv(out, out_dtype, fmt, nullptr, dst, T, H, W, Hp, Wp, stream);
+    return egress_yuv(out, out_dtype, fmt, nullptr, nullptr, dst, T, H, W, Hp, Wp, stream);
 }
 
 int sn_egress_yuv_rect(const void* out, int out_dtype, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint8_t* dst, int T, int H, int W, int Hp, int Wp,
                        void* stream) {
     if (!rect) { sn_clear_error(); return SN_EINVAL; }
-    return egress_yuv(out, out_dtype, fmt, rect, dst, T, H, W, Hp, Wp, stream);
+    return egress_yuv(out, out_dtype, fmt, rect, nullptr, dst, T, H, W, Hp, Wp, stream);
+}
+
+int sn_egress_yuv_dither(const void* out, int out_dtype, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const sn_yuv_dither* dither, uint8_t* dst, int T,
+                         int H, int W, int Hp, int Wp, void* stream) {
+    if (!dither || (dither->mode != SN_DITHER_NONE && dither->mode != SN_DITHER_TPDF) || dither->t0 < 0) { sn_clear_error(); return SN_EINVAL; }
+    return egress_yuv(out, out_dtype, fmt, rect, dither, dst, T, H, W, Hp, Wp, stream);
 }
 
 int sn_yuv_thumb(const uint8_t* src, const sn_yuv_fmt* fmt, uint16_t* dst, int T, int H, int W, void* stream) {

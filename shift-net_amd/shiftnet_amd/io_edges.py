@@ -9,7 +9,8 @@
                (shiftnet_amd/noise.py);
 ``rowcol_sums_yuv``: the same payloads -> uint32 sums of the luma codes of every row and of every column, for the letterbox rule
                (shiftnet_amd/picture.py); ``ingest_yuv`` / ``egress_yuv`` / ``noise_hist_yuv`` take ``rect=(x0, y0, w, h)`` to work on that
-               picture of the stream alone, as on the cropped stream;
+               picture of the stream alone, as on the cropped stream; ``egress_yuv`` takes ``dither=(seed, t0)`` to add triangular noise of
+               +-1 code before the rounding (``sn_egress_yuv_dither``);
 ``egress_u8``  == the per-frame ``clamp(0,1) * 255`` -> skimage PSNR(data_range=255) against the uint8 ground truth
                (:139-143) and the rounded uint8 frame cv2.imwrite would store (:152).
 """
@@ -111,11 +112,13 @@ def ingest_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, Hp: in
     return x
 
 
-def egress_yuv(out: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, dst: Optional[torch.Tensor] = None, rect=None) -> torch.Tensor:
+def egress_yuv(out: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, dst: Optional[torch.Tensor] = None, rect=None, dither=None) -> torch.Tensor:
     """out: [T,3,Hp,Wp] network output (float32 or module dtype) on the device -> [T, frame_bytes] uint8 payloads of the H x W crop.
     ``dst``: a [T, frame_bytes] uint8 tensor to fill instead of a new one.
     ``rect=(x0, y0, w, h)``: out holds that picture of the H x W stream (Hp >= h, Wp >= w); only the picture's samples of the payloads, luma and
-    chroma, are written, with what the cropped stream's egress writes -- every other byte of ``dst`` stays (a new tensor starts as zeros)."""
+    chroma, are written, with what the cropped stream's egress writes -- every other byte of ``dst`` stays (a new tensor starts as zeros).
+    ``dither=(seed, t0)``: triangular noise of +-1 code is added before the rounding (include/shiftnet_hip.h: sn_egress_yuv_dither), a hash of
+    the seed (0 .. 2^32 - 1), the frame number t0 + t and the sample's plane, row and column; None is today's call and today's bytes."""
     assert out.is_cuda and out.dim() == 4 and out.shape[1] == 3 and out.dtype in _CODE and out.is_contiguous()
     T, _, Hp, Wp = out.shape
     r = None if rect is None else _rect(rect, fmt, H, W)
@@ -123,9 +126,17 @@ def egress_yuv(out: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, dst: Optional
     fb = fmt.frame_bytes(H, W)
     y = dst if dst is not None else (torch.empty if r is None else torch.zeros)((T, fb), dtype=torch.uint8, device=out.device)
     assert tuple(y.shape) == (T, fb) and y.dtype == torch.uint8 and y.is_contiguous() and y.device == out.device
+    d = None
+    if dither is not None:
+        seed, t0 = (int(v) for v in dither)
+        if not (0 <= seed < 2 ** 32) or not (0 <= t0 <= 2 ** 31 - 1 - T):
+            raise ValueError(f"dither=(seed, t0): need 0 <= seed < 2^32 and 0 <= t0 <= 2^31 - 1 - T, got {dither!r}")
+        d = L.YuvDither(L.SN_DITHER_TPDF, seed, t0)
     with torch.cuda.device(out.device):
         st = torch.cuda.current_stream(out.device).cuda_stream
-        if r is None:
+        if d is not None:
+            L.check(L.load().sn_egress_yuv_dither(out.data_ptr(), _CODE[out.dtype], fmt, r, d, y.data_ptr(), T, H, W, Hp, Wp, st), "sn_egress_yuv_dither")
+        elif r is None:
             L.check(L.load().sn_egress_yuv(out.data_ptr(), _CODE[out.dtype], fmt, y.data_ptr(), T, H, W, Hp, Wp, st), "sn_egress_yuv")
         else:
             L.check(L.load().sn_egress_yuv_rect(out.data_ptr(), _CODE[out.dtype], fmt, r, y.data_ptr(), T, H, W, Hp, Wp, st), "sn_egress_yuv_rect")

@@ -17,6 +17,9 @@ integer sum of the luma codes of every row and of every column.  With ``black`` 
 
 The comparison is made on integers and one float64 product, the same on every host.
 
+Where the restorer writes another format than it reads (``out_format``) the rectangle must be legal in both: ``out_fmt`` below.  If either is 4:2:0
+the even-alignment rule applies, to a listed rectangle and to the one ``decide_picture`` finds.
+
 A heuristic, checked on synthetic clips only.  Noisy analogue bars need a higher level; a part of the picture that stays at black for a whole
 window is taken for bar and left as it is; a logo or a subtitle inside a bar ends the bar where it is.
 """
@@ -46,9 +49,15 @@ def black_code(bits: int, range_: int) -> int:
     return 0 if range_ == FULL else 16 << (bits - 8)
 
 
-def check_rect(rect, fmt, h: int, w: int, smallest: int = MIN_SIDE) -> Rect:
+def subsampled(fmt, out_fmt=None) -> bool:
+    """Does the even-alignment rule of 4:2:0 apply: to ``fmt``, or to the format written where that is another (``out_fmt``)."""
+    return fmt.chroma != C444 or (out_fmt is not None and out_fmt.chroma != C444)
+
+
+def check_rect(rect, fmt, h: int, w: int, smallest: int = MIN_SIDE, out_fmt=None) -> Rect:
     """``rect`` as a tuple of four ints if it is a legal picture of an ``h x w`` stream of ``fmt`` (anything with ``.chroma``), else ValueError.
-    ``smallest``: the least width and height (``smallest_picture(topo)`` where the network is known; 1 for the kernels alone)."""
+    ``smallest``: the least width and height (``smallest_picture(topo)`` where the network is known; 1 for the kernels alone).  ``out_fmt``: the
+    format the stream is written in where it is not ``fmt``; the rectangle is then legal in both."""
     try:
         vals = tuple(rect)
         if len(vals) != 4 or any(isinstance(v, (bool, float, str)) or int(v) != v for v in vals):
@@ -60,7 +69,7 @@ def check_rect(rect, fmt, h: int, w: int, smallest: int = MIN_SIDE) -> Rect:
         raise ValueError(f"picture {(x0, y0, rw, rh)}: the smallest picture the restorer takes is {smallest} x {smallest}, as the smallest frame")
     if x0 < 0 or y0 < 0 or x0 + rw > w or y0 + rh > h:
         raise ValueError(f"picture {(x0, y0, rw, rh)} does not lie inside the {w} x {h} frame")
-    if fmt.chroma != C444:
+    if subsampled(fmt, out_fmt):
         if x0 % 2 or y0 % 2:
             raise ValueError(f"picture {(x0, y0, rw, rh)}: x0 and y0 must be even at 4:2:0 (a chroma sample covers 2 x 2 luma samples)")
         if rw % 2 and x0 + rw != w:
@@ -77,9 +86,9 @@ def _runs(bar: np.ndarray) -> Tuple[int, int]:
     return (n, n) if len(nz) == 0 else (int(nz[0]), n - 1 - int(nz[-1]))
 
 
-def decide_picture(rows, cols, fmt, h: int, w: int, level: float = LEVEL, smallest: int = MIN_SIDE) -> Optional[Rect]:
+def decide_picture(rows, cols, fmt, h: int, w: int, level: float = LEVEL, smallest: int = MIN_SIDE, out_fmt=None) -> Optional[Rect]:
     """rows: integers [T, h], cols: [T, w] -- the sums of the luma codes of every row and column of the T input frames of a window -> the picture
-    of the window, or None for the full frame (the rule of the module text)."""
+    of the window, or None for the full frame (the rule of the module text).  ``out_fmt``: as for check_rect; bits and range are ``fmt``'s, the sums'."""
     rows = np.asarray(rows).astype(np.int64).reshape(-1, h)
     cols = np.asarray(cols).astype(np.int64).reshape(-1, w)
     if len(rows) < 1 or len(rows) != len(cols):
@@ -91,7 +100,7 @@ def decide_picture(rows, cols, fmt, h: int, w: int, level: float = LEVEL, smalle
     if top == h or left == w:                              # everything is bar
         return None
     x0, y0, x1, y1 = left, top, w - right, h - bottom
-    if fmt.chroma != C444:
+    if subsampled(fmt, out_fmt):
         x0, y0 = x0 + (x0 & 1), y0 + (y0 & 1)
         x1 -= (x1 & 1) if x1 != w else 0
         y1 -= (y1 & 1) if y1 != h else 0
@@ -102,9 +111,9 @@ def decide_picture(rows, cols, fmt, h: int, w: int, level: float = LEVEL, smalle
     return x0, y0, x1 - x0, y1 - y0
 
 
-def check_pictures(rects: Iterable, fmt, h: int, w: int, smallest: int = MIN_SIDE) -> List[Optional[Rect]]:
+def check_pictures(rects: Iterable, fmt, h: int, w: int, smallest: int = MIN_SIDE, out_fmt=None) -> List[Optional[Rect]]:
     """A per-window list: every entry a legal rectangle, or None for the full frame."""
-    return [None if r is None else check_rect(r, fmt, h, w, smallest) for r in rects]
+    return [None if r is None else check_rect(r, fmt, h, w, smallest, out_fmt) for r in rects]
 
 
 def parse_pictures(text: str) -> List[Optional[Rect]]:

@@ -1,4 +1,4 @@
-"""Restore a whole video: N frames in, N restored frames of the same size and pixel format out (single GPU).
+"""Restore a whole video: N frames in, N restored frames of the same size out, in the same pixel format unless another is asked for (single GPU).
 
 Not part of the upstream API.  The programs under ``inference/test_*.py`` are upstream's evaluation harnesses (ground truth, dropped border
 frames, crops); this is the path for footage.  Frames are planar Y'CbCr payloads as a Y4M stream carries them (shiftnet_amd/y4m.py); the
@@ -22,6 +22,12 @@ Active picture (``picture``, off by default): a letterboxed or pillarboxed strea
 are those of restoring the cropped stream, and the bars leave as they came in.  The rectangle is given by the caller, for the stream or per window,
 or found per window from the sums of the luma's rows and columns, made on the device from the payloads the window has uploaded anyway
 (``sn_yuv_rowcol_sums``, shiftnet_amd/picture.py).
+
+Output format (``out_format``, ``dither``; both off by default): the network's result is float32, and rounding it to the 8-bit codes it came from
+puts back the steps that the noise just removed was hiding.  ``out_format`` writes another bit depth and chroma layout than was read (10 bit
+from 8 bit footage keeps the precision); ``dither="tpdf"`` adds triangular noise of +-1 code before the rounding, which makes the mean of the codes
+follow the value at the price of about 0.5 code rms of noise (``sn_egress_yuv_dither``, csrc/sn_yuv.hip).  The noise is a hash of the seed, the
+sample's position and the number of the frame in its clip -- the stream, or the scene -- so the bytes do not depend on how the windows are run.
 """
 from __future__ import annotations
 
@@ -76,6 +82,29 @@ def plan_scene_windows(n: int, one_len: int, cuts: Iterable[int], past: int = PA
     return plan
 
 
+DITHERS = ("tpdf",)
+
+
+def plan_output(fmt, out_format=None, dither=None, dither_seed=0):
+    """(the format written, the dither word or None, the seed) for a stream read as ``fmt`` (anything with bits, chroma, matrix, range that is built
+    from the four): ``out_format`` is a C tag of y4m.MODES and changes bit depth and chroma layout only, matrix and range stay the input's; None,
+    or a tag that says what ``fmt`` says, returns ``fmt`` itself.  ValueError for an unknown tag, a dither word other than None / "tpdf", and a seed
+    outside 0 .. 2^32 - 1."""
+    from .y4m import MODES
+    out = fmt
+    if out_format is not None:
+        if not isinstance(out_format, str) or out_format not in MODES:
+            raise ValueError(f"out_format must be None or one of {', '.join(MODES)}, got {out_format!r}")
+        bits, chroma = MODES[out_format]
+        if (bits, chroma) != (fmt.bits, fmt.chroma):
+            out = type(fmt)(bits, chroma, fmt.matrix, fmt.range)
+    if dither is not None and not (isinstance(dither, str) and dither in DITHERS):
+        raise ValueError(f"dither must be None or 'tpdf', got {dither!r}")
+    if isinstance(dither_seed, (bool, float, str)) or int(dither_seed) != dither_seed or not (0 <= int(dither_seed) < 2 ** 32):
+        raise ValueError(f"dither_seed must be an integer in 0 .. 2^32 - 1, got {dither_seed!r}")
+    return out, dither, int(dither_seed)
+
+
 def pad_multiple(topo: str) -> int:
     return 8 if topo == "plus" else 4
 
@@ -92,6 +121,7 @@ class _Frames:
         self.base = 0                     # index of buf[0]
         self.buf: List[np.ndarray] = []
         self.n: Optional[int] = None      # known once the iterator ends
+        self.clip_lo = 0                  # the first restored frame of the window handed out last, counted from the first frame of its clip
 
     def _fill(self, upto: int) -> None:
         while self.n is None and self.base + len(self.buf) <= upto:
@@ -109,6 +139,7 @@ class _Frames:
         if k * one_len >= n:
             return None
         lo, cnt, idx = window_indices(k, one_len, n)
+        self.clip_lo = lo
         frames = [self.buf[i - self.base] for i in idx]
         drop = max(0, (k + 1) * one_len - PAST - self.base)                  # the next window reaches back to (k + 1) L - PAST
         if drop > 0:
@@ -138,6 +169,7 @@ class _SceneFrames:
         self.lo = 0                       # next frame to restore
         self.k = 0
         self.cuts: List[int] = []         # the scene starts used
+        self.clip_lo = 0                  # as _Frames.clip_lo: the clip is the scene
 
     def _fill(self, upto: int) -> None:
         while self.n is None and self.base + len(self.buf) <= upto:
@@ -170,6 +202,7 @@ class _SceneFrames:
         frames = [self.buf[a + reflect_index(i - a, b - a) - self.base] for i in range(lo - PAST, hi + FUTURE)]
         self.k += 1
         self.lo = hi
+        self.clip_lo = lo - a
         if cut is not None and hi == cut:
             self.a = cut
             self.cuts.append(cut)
@@ -313,13 +346,28 @@ class VideoRestorer:
     may differ from those of the cropped stream.  A window whose rectangle differs from the previous window's has a new input signature for the
     engine: a new plan, and a new captured graph where graphs are on.  Once ``restore()`` has been exhausted ``stats["window_picture"]`` lists the
     rectangle of every window (None: the full frame), ``stats["picture_launches"]`` counts the ``sn_yuv_rowcol_sums`` launches and
-    ``stats["picture_wait_ms"]`` (auto only) lists how long the stager waited for every window's sums (upload, kernel and copy back included)."""
+    ``stats["picture_wait_ms"]`` (auto only) lists how long the stager waited for every window's sums (upload, kernel and copy back included).
+    out_format: None -- the payloads yielded have the format of those read, today's code path and bytes; a C tag of y4m.MODES -- they have that bit
+    depth and chroma layout (``plan_output(fmt, tag)[0].frame_bytes(h, w)`` bytes each), matrix and range stay the input's.  A tag that says what the
+    input's says is None.  With ``picture`` a rectangle must then be legal in both formats (the even-alignment rule applies if either is 4:2:0, to
+    ``"auto"`` as well), and the samples outside it cannot be copied: they are the whole input frame converted, ``egress(out format,
+    ingest_float32(in format, frame))``, undithered -- a bar at 8-bit code 16 leaves at 10-bit code 64.
+    dither: None -- codes are rounded to nearest, today's bytes; ``"tpdf"`` -- triangular noise of +-1 code is added before the rounding
+    (``sn_egress_yuv_dither``): the mean of the codes of a flat area follows its value instead of sitting on a step, at the price of noise of about
+    0.5 code rms.  ``dither_seed`` (0 .. 2^32 - 1) picks the noise.  The noise of a sample is a hash of the seed, its plane, row and column -- counted
+    from the picture's origin under ``picture`` -- and the number of its frame counted from the first frame of its clip: the stream, or the scene under
+    ``scene_cuts``.  So the bytes are the same with ``pipeline`` on and off, those of restoring every scene as a separate video, and inside a picture
+    those of restoring the cropped stream.  ``stats["out_format"]`` and ``stats["dither"]`` record the two arguments as used (None: the input's
+    format / no dither), ``stats["dither_seed"]`` the seed."""
 
     def __init__(self, net, one_len: int, sigma=None, pipeline: bool = True, scene_cuts=None,
                  cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0),
-                 picture=None, bar_level: float = 1.0) -> None:
+                 picture=None, bar_level: float = 1.0, out_format=None, dither=None, dither_seed: int = 0) -> None:
         import torch
+        from .lib import YuvFmt
         self.torch = torch
+        _, self.dither, self.dither_seed = plan_output(YuvFmt(8, 0, 0, 0), out_format, dither, dither_seed)      # the argument errors, before anything else
+        self.out_format = out_format
         self.net, self.one_len, self.pipeline = net, int(one_len), bool(pipeline)
         if self.one_len < 1:
             raise ValueError("one_len must be >= 1")
@@ -376,21 +424,27 @@ class VideoRestorer:
     def _prepare(self, fmt, h: int, w: int) -> None:
         torch = self.torch
         key = (fmt.bits, fmt.chroma, fmt.matrix, fmt.range, h, w)
-        if self.picture_mode in ("fixed", "list"):                # the rectangles are judged against this stream
+        ofmt = plan_output(fmt, self.out_format)[0]               # fmt itself unless another bit depth or chroma layout is written
+        if self.picture_mode in ("fixed", "list"):                # the rectangles are judged against this stream, as read and as written
             from .picture import check_pictures, smallest_picture
-            self._pics = check_pictures([self.picture] if self.picture_mode == "fixed" else self.picture, fmt, h, w, smallest_picture(self.V.topo))
+            self._pics = check_pictures([self.picture] if self.picture_mode == "fixed" else self.picture, fmt, h, w, smallest_picture(self.V.topo),
+                                        out_fmt=ofmt)
         if self._shape == key:
             return
         self._shape = key
         self.fmt, self.h, self.w = fmt, h, w
+        self.ofmt, self.convert = ofmt, ofmt is not fmt
         self.hp, self.wp = padded_size(h, w, self.V.topo)
-        self.fb = fmt.frame_bytes(h, w)
+        self.fb, self.ofb = fmt.frame_bytes(h, w), ofmt.frame_bytes(h, w)
         tin, tout = self.one_len + PAST + FUTURE, self.one_len
         dev = self.dev
         self.pin_in = [torch.empty((tin, self.fb), dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self.pin_out = [torch.empty((tout, self.fb), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.pin_out = [torch.empty((tout, self.ofb), dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.dev_in = [torch.empty((tin, self.fb), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.dev_out = [torch.empty((tout, self.fb), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.dev_out = [torch.empty((tout, self.ofb), dtype=torch.uint8, device=dev) for _ in range(2)]
+        # a picture in another format than was read: the window's whole frames as float32 on their way from one format to the other (main stream only)
+        self.conv32 = torch.empty(tout * 3 * h * w, dtype=torch.float32, device=dev) if self.convert and self.picture_mode != "full" else None
+        self.t0 = [0, 0]                                          # the frame number, in its clip, of the first frame the window of a slot restores
         # flat, sized for the full frame: a window's tensors are views of the leading elements at the padded size of its picture
         self.x = [torch.empty(tin * 3 * self.hp * self.wp, dtype=self.dtype, device=dev) for _ in range(2)]
         half = self.dtype != torch.float32
@@ -434,8 +488,9 @@ class VideoRestorer:
         return self._pics[k]
 
     # -- the steps of one window; slot = k % 2 -------------------------------------------------------------------------------------
-    def _stage(self, slot: int, frames: Sequence[np.ndarray]) -> int:
-        """Host frames -> pinned slot -> device -> RGB tensors, on the side stream.  Windows are staged in the order they are restored."""
+    def _stage(self, slot: int, frames: Sequence[np.ndarray], t0: int = 0) -> int:
+        """Host frames -> pinned slot -> device -> RGB tensors, on the side stream.  Windows are staged in the order they are restored.
+        t0: the number of the window's first restored frame in its clip (the dither's frame number)."""
         from .io_edges import ingest_yuv, noise_hist_yuv, rowcol_sums_yuv
         torch = self.torch
         t = len(frames)
@@ -443,6 +498,7 @@ class VideoRestorer:
         if self.picture_mode in ("fixed", "list"):
             rect = self._listed_picture(self._staged)
         self._staged += 1
+        self.t0[slot] = t0
         if self.used[slot]:
             self.ev_h2d[slot].synchronize()                      # the copy that last read this pinned slot has finished
         pin = self.pin_in[slot].numpy()
@@ -466,7 +522,7 @@ class VideoRestorer:
                 self.ev_sums[slot].synchronize()
                 self._picture_wait.append((time.perf_counter() - t0) * 1e3)
                 rect = decide_picture(self.pin_rows[slot][:t].numpy(), self.pin_cols[slot][:t].numpy(), self.fmt, self.h, self.w, self.bar_level,
-                                      smallest_picture(self.V.topo))
+                                      smallest_picture(self.V.topo), out_fmt=self.ofmt)
             self.rect[slot] = rect
             x, x32 = self._views(slot, t, rect)
             hp, wp = x.shape[3], x.shape[4]
@@ -504,7 +560,7 @@ class VideoRestorer:
 
     def _run(self, slot: int, t: int, main) -> int:
         """Forward + egress on the main stream, copy back on the output stream."""
-        from .io_edges import egress_yuv
+        from .io_edges import egress_yuv, ingest_yuv
         torch = self.torch
         n = t - PAST - FUTURE
         sigma = self._window_sigma(slot, t) if self.V.denoise else None
@@ -527,10 +583,16 @@ class VideoRestorer:
                 out = self.net.forward_fp32_out(x, **kw)
             e1.record(main)
             self._timers.append((e0, e1))
-            if rect is not None:
+            if rect is not None and not self.convert:
                 # everything outside the picture leaves as it came in: the window's own n frames (not the reflected ones around them) first
                 self.dev_out[slot][:n].copy_(self.dev_in[slot][PAST:PAST + n], non_blocking=True)
-            egress_yuv(out, self.fmt, self.h, self.w, dst=self.dev_out[slot][:n], rect=rect)
+            elif rect is not None:
+                # ... in the format written: the whole frames converted by the two edges, float32 between them, rounded to nearest
+                full = self.conv32[:n * 3 * self.h * self.w].view(1, n, 3, self.h, self.w)
+                ingest_yuv(self.dev_in[slot][PAST:PAST + n], self.fmt, self.h, self.w, self.h, self.w, torch.float32, out=full)
+                egress_yuv(full[0], self.ofmt, self.h, self.w, dst=self.dev_out[slot][:n])
+            dither = None if self.dither is None else (self.dither_seed, self.t0[slot])
+            egress_yuv(out, self.ofmt, self.h, self.w, dst=self.dev_out[slot][:n], rect=rect, dither=dither)
             self.ev_done[slot].record(main)
         with torch.cuda.stream(self.s_out):
             self.s_out.wait_event(self.ev_done[slot])
@@ -586,6 +648,7 @@ class VideoRestorer:
         self._timers: List = []
         self.used = [False, False]
         self.stats = {"frames": 0, "windows": 0, "forward_s": 0.0, "window_forward_ms": []}
+        self.stats["out_format"], self.stats["dither"], self.stats["dither_seed"] = (self.out_format if self.convert else None), self.dither, self.dither_seed
         self._src = None
         self._wsig, self._wfsig, self._noise_launches = [], [], 0
         self._wpic, self._picture_launches, self._staged, self._picture_wait = [], 0, 0, []
@@ -606,7 +669,7 @@ class VideoRestorer:
                     win = src.window(k, self.one_len)
                     if win is None:
                         break
-                    t = self._stage(k % 2, win[2])
+                    t = self._stage(k % 2, win[2], src.clip_lo)
                     n = self._run(k % 2, t, main)
                     for p in self._collect(k % 2, n):
                         self.stats["frames"] += 1
@@ -637,7 +700,7 @@ class VideoRestorer:
                     win = src.window(k, self.one_len)
                     if win is None or not acquire(in_free[k % 2]):
                         return
-                    if not put((k % 2, self._stage(k % 2, win[2]))):
+                    if not put((k % 2, self._stage(k % 2, win[2], src.clip_lo))):
                         return
                     k += 1
 
@@ -689,8 +752,14 @@ def picture_arg(word: str):
     return word
 
 
+def _modes():
+    from .y4m import MODES
+    return MODES
+
+
 def make_parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser(description="Restore a Y4M video with Shift-Net on the MI355X: same frames, size and pixel format out")
+    ap = argparse.ArgumentParser(description="Restore a Y4M video with Shift-Net on the MI355X: same frames and size out, same pixel format unless "
+                                             "--out_format names another")
     ap.add_argument("--variant", choices=list(VARIANTS), required=True)
     ap.add_argument("--checkpoint", required=True, help="checkpoint path, or 'synthetic' for the deterministic synthetic weights")
     ap.add_argument("--dtype", choices=["fp32", "fp16", "bf16"], default="bf16")
@@ -714,6 +783,13 @@ def make_parser() -> argparse.ArgumentParser:
                          "per line ('#' comments); default full: the whole frame")
     ap.add_argument("--bar_level", type=float, default=1.0, help="auto: a row or column is bar if its mean luma stays within this many 8-bit codes of black")
     ap.add_argument("--picture_out", default=None, metavar="FILE", help="write the picture every window was restored with, in the format --picture FILE reads")
+    ap.add_argument("--out_format", choices=list(_modes()), default=None, metavar="TAG",
+                    help="write this Y4M C tag instead of the input's (%(choices)s): another bit depth and chroma layout, e.g. 444p10 or 420p10 to keep the "
+                         "precision of the result when 8 bit came in; matrix and range stay the input's; default: the input's format")
+    ap.add_argument("--dither", choices=["none", "tpdf"], default="none",
+                    help="tpdf: add triangular noise of +-1 code before rounding to the output's codes: no banding, about 0.5 code rms of noise instead; "
+                         "default none: round to nearest")
+    ap.add_argument("--dither_seed", type=int, default=0, metavar="N", help="tpdf: which noise (0 .. 2^32 - 1); the same seed gives the same bytes")
     ap.add_argument("--cuts_out", default=None, metavar="FILE", help="write the scene starts that were used, in the format --scene_cuts FILE reads")
     ap.add_argument("input", metavar="IN", help="Y4M file, or - for stdin")
     ap.add_argument("output", metavar="OUT", help="Y4M file, or - for stdout")
@@ -737,9 +813,11 @@ def load_net(variant: str, checkpoint: str, dtype: str, device="cuda"):
 def main(argv: Optional[Sequence[str]] = None) -> int:
     from . import lib as L
     from .io_edges import yuv_fmt
-    from .y4m import Y4MReader, Y4MWriter
+    from .y4m import Y4MReader, Y4MWriter, output_header
     ap = make_parser()
     a = ap.parse_args(argv)
+    if not (0 <= a.dither_seed < 2 ** 32):
+        ap.error("--dither_seed: an integer in 0 .. 2^32 - 1")
     if "denoise" in a.variant and a.sigma is None:
         ap.error("--sigma is required by the denoise variants")
     log = lambda s: (sys.stderr.write(s + "\n"), sys.stderr.flush())      # noqa: E731
@@ -794,8 +872,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                       L.SN_YUV_FULL if rng == "full" else L.SN_YUV_LIMITED)
         net = load_net(a.variant, a.checkpoint, a.dtype)
         vr = VideoRestorer(net, a.one_len, sigma=sigma, pipeline=not a.no_pipeline, scene_cuts=cuts, cut_threshold=a.cut_threshold,
-                           cut_ratio=a.cut_ratio, sigma_clamp=a.sigma_clamp, picture=picture, bar_level=a.bar_level)
-        wr = Y4MWriter(fout, hd)
+                           cut_ratio=a.cut_ratio, sigma_clamp=a.sigma_clamp, picture=picture, bar_level=a.bar_level, out_format=a.out_format,
+                           dither=None if a.dither == "none" else a.dither, dither_seed=a.dither_seed)
+        if a.out_format is not None or a.dither != "none":
+            log(f"output: C{a.out_format or hd.chroma}{'' if a.out_format else ' (as the input)'}, dither {a.dither}"
+                f"{' seed %d' % a.dither_seed if a.dither != 'none' else ''}")
+        wr = Y4MWriter(fout, output_header(hd, a.out_format))
         t0 = time.perf_counter()
         n = 0
         for p in vr.restore(rd, fmt, hd.height, hd.width):

@@ -14,7 +14,7 @@ Interlaced streams and every other mode are refused.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import BinaryIO, Iterator, List, Optional
 
 import numpy as np
@@ -64,6 +64,16 @@ class Y4MHeader:
         tags = [f"W{self.width}", f"H{self.height}", f"F{self.fps}", f"I{self.interlace}", f"A{self.aspect}", f"C{self.chroma}"]
         tags += ["X" + x for x in self.extensions]
         return MAGIC + b" " + " ".join(tags).encode("ascii") + b"\n"
+
+
+def output_header(header: Y4MHeader, out_format: Optional[str] = None) -> Y4MHeader:
+    """The header of the stream the restorer writes for ``header``'s: the new C tag (``out_format``, a key of MODES; None keeps the input's), every
+    other tag and every X extension the input's."""
+    if out_format is None:
+        return header
+    if out_format not in MODES:
+        raise Y4MError(f"Y4M: output format C{out_format} is not supported (supported: {', '.join('C' + m for m in MODES)})")
+    return replace(header, chroma=out_format, extensions=list(header.extensions))
 
 
 def _read_exact(f: BinaryIO, n: int) -> bytes:

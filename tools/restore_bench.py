@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Measurements behind DESIGN.md 3.11, 3.13, 3.14 and 3.15 (run on the MI355X from the repository root).
+"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15 and 3.16 (run on the MI355X from the repository root).
 
   kernels : time per pixel of sn_ingest_yuv / sn_egress_yuv / sn_yuv_thumb / sn_yuv_noise_hist (4:2:0 8 bit, 720p x 20 frames; the noise
             histogram on the same frames with noise of sigma 10 as well) beside sn_ingest_u8 / sn_egress_u8 on the same
             frames, interleaved in one process: REPS repetitions, each timing INNER back-to-back launches of every kernel with device events;
-            median and min..max over the repetitions.
+            median and min..max over the repetitions.  Since 3.16 also the dithered egress (sn_egress_yuv_dither) from float32 at 8 bit 4:2:0,
+            10 bit 4:2:0 and 10 bit 4:4:4 beside the undithered egress of the same formats, and with --parent_lib SO the undithered sn_egress_yuv
+            of another build on the same tensors.
   pipeline: steady-state wall time per 720p window of the pipelined restorer (Shift-Net-s, one_len 16, bf16, Y4M held in memory) beside the
             forward-only time of the same windows (device events in the same runs) and beside pipeline=False, the two alternating.
             --scene_cuts auto: the same stream with the cut detector running (sn_yuv_thumb; 3.13).  --cut_every N: every second scene of N frames
@@ -57,6 +59,19 @@ def kernels(a):
     thumbs = torch.empty((T, (H + 7) // 8, (W + 7) // 8), dtype=torch.uint16, device="cuda")
     hists = torch.empty((T, 511), dtype=torch.uint32, device="cuda")
     pay_noisy = egress_yuv((rgb + torch.randn(rgb.shape, device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * (10.0 / 255)).clamp(0, 1), fmt, H, W)
+    fmt10, fmt444 = yuv_fmt(10, L.SN_YUV_420_LEFT, L.SN_YUV_BT709, L.SN_YUV_LIMITED), yuv_fmt(10, L.SN_YUV_444, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    dst10 = torch.empty((T, fmt10.frame_bytes(H, W)), dtype=torch.uint8, device="cuda")
+    dst444 = torch.empty((T, fmt444.frame_bytes(H, W)), dtype=torch.uint8, device="cuda")
+    parent = {}
+    if a.parent_lib:                                                                 # another build's undithered egress, interleaved with this one's
+        import ctypes as C
+        plib = C.CDLL(os.path.abspath(a.parent_lib))
+        plib.sn_egress_yuv.argtypes = [C.c_void_p, C.c_int, C.POINTER(L.YuvFmt), C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]
+
+        def pegr(o, code, f, d):
+            return lambda: L.check(plib.sn_egress_yuv(o.data_ptr(), code, f, d.data_ptr(), T, H, W, H, W, torch.cuda.current_stream().cuda_stream), "parent sn_egress_yuv")
+        parent = {"parent_egress_yuv_bf16": pegr(out_bf, L.SN_BF16, fmt, dst), "parent_egress_yuv_fp32": pegr(out_32, L.SN_F32, fmt, dst),
+                  "parent_egress_yuv_420p10_fp32": pegr(out_32, L.SN_F32, fmt10, dst10), "parent_egress_yuv_444p10_fp32": pegr(out_32, L.SN_F32, fmt444, dst444)}
     cases = {
         "ingest_yuv_bf16": lambda: ingest_yuv(pay, fmt, H, W, H, W, torch.bfloat16, out=x_bf),
         "thumb_yuv": lambda: thumb_yuv(pay, fmt, H, W, out=thumbs),
@@ -67,6 +82,12 @@ def kernels(a):
         "egress_u8_bf16": lambda: egress_u8(out_bf),
         "egress_yuv_fp32": lambda: egress_yuv(out_32, fmt, H, W, dst=dst),
         "egress_u8_fp32": lambda: egress_u8(out_32),
+        "egress_yuv_fp32_tpdf": lambda: egress_yuv(out_32, fmt, H, W, dst=dst, dither=(1, 0)),
+        "egress_yuv_420p10_fp32": lambda: egress_yuv(out_32, fmt10, H, W, dst=dst10),
+        "egress_yuv_420p10_fp32_tpdf": lambda: egress_yuv(out_32, fmt10, H, W, dst=dst10, dither=(1, 0)),
+        "egress_yuv_444p10_fp32": lambda: egress_yuv(out_32, fmt444, H, W, dst=dst444),
+        "egress_yuv_444p10_fp32_tpdf": lambda: egress_yuv(out_32, fmt444, H, W, dst=dst444, dither=(1, 0)),
+        **parent,
     }
     for f in cases.values():
         for _ in range(3):
@@ -330,8 +351,8 @@ if __name__ == "__main__":
     ap.add_argument("--only", choices=["both", "pipelined", "serial"], default="both", help="pipeline part: one mode only (for a kernel trace of its own)")
     ap.add_argument("--scene_cuts", choices=["off", "auto", "listed"], default="off", help="pipeline part: VideoRestorer(scene_cuts=...)")
     ap.add_argument("--cut_every", type=int, default=0, help="pipeline part: a cut every N frames in the stream (0: none)")
-    ap.add_argument("--parent_lib", default=None, metavar="SO", help="picture part, kernels mode: a shared library built from another commit's csrc/sn_yuv.hip "
-                    "alone; its sn_ingest_yuv / sn_egress_yuv are timed beside this build's")
+    ap.add_argument("--parent_lib", default=None, metavar="SO", help="kernels part and picture part in kernels mode: a shared library built from another commit's "
+                    "csrc/sn_yuv.hip alone; its sn_ingest_yuv / sn_egress_yuv are timed beside this build's")
     ap.add_argument("--mode", choices=["forward", "kernels"], default="forward", help="picture part: which measurement")
     ap.add_argument("--picture", choices=["auto", "fixed"], default="auto", help="picture part, forward mode: VideoRestorer(picture='auto') or the rectangle itself")
     a = ap.parse_args()
