@@ -553,6 +553,41 @@ typedef struct sn_yuv_dither { int mode; uint32_t seed; int t0; } sn_yuv_dither;
 int sn_egress_yuv_dither(const void* out, int out_dtype, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */,
                          const sn_yuv_dither* dither, uint8_t* dst, int T, int H, int W, int Hp, int Wp, void* stream);
 
+/* ---- a noise-level function for the denoisers (new symbols, SN_ABI_VERSION stays 20) -----------------------------------------------------------
+ * The curve: the sigma of the noise as a function of the luma code, SN_NLF_BANDS = 16 knots; knot b sits at luma code lo + (b + 0.5) (hi - lo) / 16
+ * (shiftnet_amd/noise.py estimates it on the host from the histograms of the first entry point; the second turns it into the network's noise plane).
+ *
+ * sn_yuv_noise_hist_bands: the statistic of sn_yuv_noise_hist split by brightness.  src, fmt, lo, hi, T, H, W as sn_yuv_noise_hist_rect; rect == NULL is
+ * the whole frame, otherwise the block grid is anchored at the rectangle's origin (the cropped stream's histograms).  For every non-overlapping 2 x 2 luma
+ * block (a, b / c, d) whose four codes lie strictly between lo and hi, with S = a + b + c + d:
+ *   band = (16 (S - 4 lo)) / (4 (hi - lo))      integer division; 4 <= S - 4 lo <= 4 (hi - lo) - 4, so 0 <= band <= 15
+ *   v    = min(|a - b - c + d|, NBV - 1)         NBV = 128 at 8 bit, 512 at 10 bit: the last bin means "at least NBV - 1"
+ * and one is added to dst[t][band][v].  dst:[T][16][NBV] uint32 is OVERWRITTEN with the counts, never added to; nothing else is written.  Integer
+ * arithmetic: exact, and the same for every launch geometry and schedule.  Summed over the bands, bins < NBV - 1 are those of sn_yuv_noise_hist and the
+ * last bin is the sum of its bins from NBV - 1 up.  A picture without a whole block is legal and gives zeros.
+ * SN_EINVAL before anything is launched: as sn_yuv_noise_hist_rect (rect may be NULL here), and lo < -2^24 or hi > 2^24 (the band is 32-bit arithmetic).
+ *
+ * sn_noise_map_level: dst:[T][1][Hp][Wp] of dst_dtype, Hp >= h, Wp >= w, with h x w the picture (rect, or H x W for rect == NULL; all coordinates below
+ * count from the picture's first sample and nothing outside the picture is read).  knots: 16 finite float32 in HOST memory, read before the call returns:
+ * the curve already divided by 255.  lo < hi.  Every float32 product, sum, difference and quotient below is rounded separately (no FMA):
+ *   block means   M[j][i] = float(sum of the luma codes of block (j, i)) / float(count), block (j, i) = rows 8j .. min(8j + 8, h) - 1, columns
+ *                 8i .. min(8i + 8, w) - 1: partial blocks at the far edges divide by their own count; nby = ceil(h / 8), nbx = ceil(w / 8)
+ *   pixel (y, x): ye = min(y, h - 1), xe = min(x, w - 1)      (the padding replicates the edge pixel, as sn_ingest_yuv pads)
+ *                 nx = 2 xe - 7;  i0 = floor(nx / 16);  ax = float(nx - 16 i0) * 0.0625      ((xe - 3.5) / 8 = i0 + ax: the block centres lie at 8 i + 3.5; exact)
+ *                 ny, j0, ay likewise from ye;  i1 = i0 + 1, j1 = j0 + 1;  all four indices clamped to 0 .. nbx - 1 / 0 .. nby - 1 after that
+ *                 top = M[j0][i0] + ax * (M[j0][i1] - M[j0][i0]);  bot = M[j1][i0] + ax * (M[j1][i1] - M[j1][i0]);  m = top + ay * (bot - top)
+ *                 u = min(max((m - float(lo)) * s - 0.5, 0), 15)   with s = 16 / (hi - lo), a float64 expression rounded ONCE to float32
+ *                 i = min(int(floor(u)), 14);  f = u - float(i);  value = k[i] + f * (k[i + 1] - k[i])
+ *   and value is rounded to dst_dtype (nearest even).  A flat curve therefore gives exactly k[0] at every pixel.  (tests/nlf_ref.py restates both entry
+ * points in numpy; the kernels equal it bit for bit.)  Only dst is written.
+ * SN_EINVAL before anything is launched: null pointers, bits not 8 / 10, unknown chroma code or dtype, T, H or W < 1, an illegal rectangle, Hp or Wp
+ * smaller than the picture, lo >= hi, lo < -2^24 or hi > 2^24, a knot that is not finite, src at an odd address at 10 bit. */
+#define SN_NLF_BANDS 16
+int sn_yuv_noise_hist_bands(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */, uint32_t* dst, int lo, int hi,
+                            int T, int H, int W, void* stream);
+int sn_noise_map_level(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */, const float* knots, int lo, int hi,
+                       void* dst, int dst_dtype, int T, int H, int W, int Hp, int Wp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

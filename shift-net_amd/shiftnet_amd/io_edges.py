@@ -7,6 +7,9 @@
 ``thumb_yuv``  : the same payloads -> uint16 sums of the luma codes of every 8 x 8 block, for the scene-cut detector (shiftnet_amd/scenes.py);
 ``noise_hist_yuv``: the same payloads -> uint32 histograms of |a - b - c + d| over the 2 x 2 luma blocks, for the blind noise estimate
                (shiftnet_amd/noise.py);
+``noise_hist_bands_yuv`` / ``noise_map_level``: the same payloads -> that statistic split into 16 bands of brightness, from which noise.py estimates a
+               noise-level function (sigma against the luma code), and payloads + the 16 knots of one -> the denoisers' noise plane
+               (``sn_yuv_noise_hist_bands``, ``sn_noise_map_level``); both take ``rect``;
 ``rowcol_sums_yuv``: the same payloads -> uint32 sums of the luma codes of every row and of every column, for the letterbox rule
                (shiftnet_amd/picture.py); ``ingest_yuv`` / ``egress_yuv`` / ``noise_hist_yuv`` take ``rect=(x0, y0, w, h)`` to work on that
                picture of the stream alone, as on the cropped stream; ``egress_yuv`` takes ``dither=(seed, t0)`` to add triangular noise of
@@ -178,6 +181,54 @@ def noise_hist_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lo
             L.check(L.load().sn_yuv_noise_hist(payload_u8.data_ptr(), fmt, y.data_ptr(), lo, hi, T, H, W, st), "sn_yuv_noise_hist")
         else:
             L.check(L.load().sn_yuv_noise_hist_rect(payload_u8.data_ptr(), fmt, r, y.data_ptr(), lo, hi, T, H, W, st), "sn_yuv_noise_hist_rect")
+    return y
+
+
+def noise_hist_bands_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lo: Optional[int] = None, hi: Optional[int] = None,
+                         out: Optional[torch.Tensor] = None, rect=None) -> torch.Tensor:
+    """payload_u8: [T, frame_bytes] uint8 on a HIP device (only the luma plane of each payload is read) -> uint32 [T, 16, NBV], NBV = 128 / 512:
+    ``noise_hist_yuv``'s counts split by the block's brightness, band = (16 (S - 4 lo)) / (4 (hi - lo)) for the block's sum S, and v saturated to
+    NBV - 1 (the last bin means "at least NBV - 1").  ``lo``, ``hi``, ``out``, ``rect`` as there."""
+    from .noise import NLF_BANDS, clip_codes, nlf_bins
+    fb = fmt.frame_bytes(H, W)
+    assert payload_u8.dtype == torch.uint8 and payload_u8.is_cuda and payload_u8.dim() == 2 and payload_u8.shape[1] == fb and payload_u8.is_contiguous()
+    T, nbv = payload_u8.shape[0], nlf_bins(fmt.bits)
+    dlo, dhi = clip_codes(fmt.bits, fmt.range)
+    lo, hi = dlo if lo is None else int(lo), dhi if hi is None else int(hi)
+    y = out if out is not None else torch.empty((T, NLF_BANDS, nbv), dtype=torch.uint32, device=payload_u8.device)
+    assert tuple(y.shape) == (T, NLF_BANDS, nbv) and y.dtype == torch.uint32 and y.is_contiguous() and y.device == payload_u8.device
+    r = None if rect is None else _rect(rect, fmt, H, W)
+    with torch.cuda.device(payload_u8.device):
+        L.check(L.load().sn_yuv_noise_hist_bands(payload_u8.data_ptr(), fmt, r, y.data_ptr(), lo, hi, T, H, W,
+                                                 torch.cuda.current_stream(payload_u8.device).cuda_stream), "sn_yuv_noise_hist_bands")
+    return y
+
+
+def noise_map_level(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, Hp: int, Wp: int, knots, dtype: torch.dtype,
+                    lo: Optional[int] = None, hi: Optional[int] = None, out: Optional[torch.Tensor] = None, rect=None) -> torch.Tensor:
+    """payload_u8: [T, frame_bytes] uint8 on a HIP device (only the luma plane of each payload is read) -> [1, T, 1, Hp, Wp] of ``dtype``: the noise
+    plane of the denoisers for a noise-level function.  ``knots``: its 16 values as the network takes them (sigma / 255), rounded to float32 here; knot
+    b sits at luma code lo + (b + 0.5) (hi - lo) / 16 (default ``lo``, ``hi``: noise.clip_codes).  The value at a pixel is the function, linear between
+    the knots and constant beyond the outer ones, at the bilinear interpolation of the means of the 8 x 8 luma blocks -- not at the noisy pixel itself;
+    pixels outside H x W replicate the edge pixel.  ``rect=(x0, y0, w, h)``: the plane of that picture of the stream (Hp >= h, Wp >= w), bit for bit the
+    cropped stream's.  ``out``: a [1, T, 1, Hp, Wp] tensor to fill.  The knots travel as a kernel argument: no upload, nothing to wait for."""
+    import ctypes as C
+    from .noise import NLF_BANDS, clip_codes
+    fb = fmt.frame_bytes(H, W)
+    assert payload_u8.dtype == torch.uint8 and payload_u8.is_cuda and payload_u8.dim() == 2 and payload_u8.shape[1] == fb and payload_u8.is_contiguous()
+    r = None if rect is None else _rect(rect, fmt, H, W)
+    assert Hp >= (H if r is None else r.h) and Wp >= (W if r is None else r.w) and dtype in _CODE
+    kn = [float(k) for k in knots]
+    if len(kn) != NLF_BANDS or not all(math.isfinite(k) for k in kn):
+        raise ValueError(f"knots: need {NLF_BANDS} finite numbers, got {knots!r}")
+    dlo, dhi = clip_codes(fmt.bits, fmt.range)
+    lo, hi = dlo if lo is None else int(lo), dhi if hi is None else int(hi)
+    T = payload_u8.shape[0]
+    y = out if out is not None else torch.empty((1, T, 1, Hp, Wp), dtype=dtype, device=payload_u8.device)
+    assert tuple(y.shape) == (1, T, 1, Hp, Wp) and y.dtype == dtype and y.is_contiguous() and y.device == payload_u8.device
+    with torch.cuda.device(payload_u8.device):
+        L.check(L.load().sn_noise_map_level(payload_u8.data_ptr(), fmt, r, (C.c_float * NLF_BANDS)(*kn), lo, hi, y.data_ptr(), _CODE[dtype], T, H, W, Hp, Wp,
+                                            torch.cuda.current_stream(payload_u8.device).cuda_stream), "sn_noise_map_level")
     return y
 
 

@@ -14,6 +14,14 @@ the standard deviation of i.i.d. noise on 8-bit R'G'B', which is what the networ
 A window's sigma is the median of its input frames' (as fed: reflected duplicates count), clamped.  Everything here is float64 on exact
 integers, so the device's histograms and a host restatement of them give the same floats.
 
+Noise-level function (``noise_model="level"`` of the restorer): real sensor noise is signal dependent, and after the camera's transfer curve the
+shadows carry several times the noise of the highlights.  ``sn_yuv_noise_hist_bands`` splits the same statistic into ``NLF_BANDS`` = 16 bands of the
+block's brightness (``band = (16 (S - 4 lo)) / (4 (hi - lo))`` for the sum S of the block's four codes; v saturated to ``nlf_bins(bits)`` - 1, the last
+bin meaning "at least that").  ``window_curve`` turns a window's summed band histograms into 16 knots, sigma of 8-bit R'G'B' at luma code
+``lo + (b + 0.5) (hi - lo) / 16``: the estimate above per band; a band with fewer than ``NLF_MIN_BLOCKS`` blocks or whose median falls in the saturating
+bin has none and is filled linearly between the nearest bands that have (constant beyond the outermost; all 0 if none has); then every knot is
+clamped.  ``sn_noise_map_level`` evaluates the curve per pixel.  ``parse_curves`` / ``format_curves`` are the file of one curve per window.
+
 A heuristic, checked on synthetic clips only.  It assumes white Gaussian noise: compression makes noise non-white and the estimate then reads
 low; pixel-scale texture adds to it in quadrature; at sigma >= 40 the clipping of R'G'B' to [0, 1] makes it read low by construction.
 """
@@ -28,6 +36,8 @@ MAD_TO_SIGMA = 0.6744897501960817          # the median of |x| for x ~ N(0, 1)
 CLAMP = (0.0, 50.0)                        # the range of noise levels upstream evaluates
 BT601, BT709 = 0, 1                        # the codes of sn_yuv_fmt.matrix
 LIMITED, FULL = 0, 1                       # ... and .range
+NLF_BANDS = 16                             # SN_NLF_BANDS: knots of a noise-level function
+NLF_MIN_BLOCKS = 1024                      # a band with fewer counted blocks in the window has no estimate of its own
 
 
 def nbins(bits: int) -> int:
@@ -132,3 +142,100 @@ def format_sigmas(sigmas: Iterable[float], how: str = "") -> str:
     sigmas = [float(s) for s in sigmas]
     head = f"# noise level per window (sigma of 8-bit R'G'B' codes), in the order the windows are restored; {len(sigmas)} window{'' if len(sigmas) == 1 else 's'}"
     return head + (f"; {how}" if how else "") + "\n" + "".join(f"{s!r}\n" for s in sigmas)
+
+
+# ---- the noise-level function: sigma against the luma code ---------------------------------------------------------------------------------
+def nlf_bins(bits: int) -> int:
+    """NBV: bins per band of sn_yuv_noise_hist_bands; the last one means "at least NBV - 1"."""
+    return 128 << (bits - 8)
+
+
+def knot_codes(lo: int, hi: int) -> List[float]:
+    """The luma codes the 16 knots sit at."""
+    return [lo + (b + 0.5) * (hi - lo) / NLF_BANDS for b in range(NLF_BANDS)]
+
+
+def band_sigma(hist, bits: int, matrix: int, range_: int, min_blocks: int = NLF_MIN_BLOCKS) -> Optional[float]:
+    """One band's histogram (the window's sum) -> ``frame_sigma`` of it, or None: fewer than ``min_blocks`` blocks, or the median in the last bin."""
+    h = np.asarray(hist).reshape(-1).astype(np.int64)
+    cum = np.cumsum(h)
+    n = int(cum[-1])
+    if n < max(min_blocks, 1):
+        return None
+    if int(np.searchsorted(cum, n / 2.0, side="left")) == len(h) - 1:        # hist_median's bin: "at least NBV - 1" has no width to interpolate in
+        return None
+    return frame_sigma(h, bits, matrix, range_)
+
+
+def fill_curve(knots: Sequence[Optional[float]]) -> List[float]:
+    """None entries filled: linear in the band index between the nearest entries that have a value, a + (c - a) (b - i) / (j - i) for i < b < j;
+    constant beyond the outermost; all 0.0 if there is none."""
+    have = [b for b, k in enumerate(knots) if k is not None]
+    if not have:
+        return [0.0] * len(knots)
+    out: List[float] = []
+    for b, k in enumerate(knots):
+        if k is not None:
+            out.append(float(k))
+        elif b < have[0]:
+            out.append(float(knots[have[0]]))
+        elif b > have[-1]:
+            out.append(float(knots[have[-1]]))
+        else:
+            i = max(x for x in have if x < b)
+            j = min(x for x in have if x > b)
+            out.append(float(knots[i]) + (float(knots[j]) - float(knots[i])) * (b - i) / (j - i))
+    return out
+
+
+def window_curve(band_hists, bits: int, matrix: int, range_: int, clamp: Sequence[float] = CLAMP, min_blocks: int = NLF_MIN_BLOCKS) -> List[float]:
+    """band_hists: [T, 16, NBV] (or [16, NBV]) counts of a window's input frames as fed -> its 16 knots: summed over the frames, estimated per band,
+    holes filled, clamped."""
+    lo, hi = check_clamp(clamp)
+    h = np.asarray(band_hists).astype(np.int64)
+    h = h.reshape(-1, NLF_BANDS, h.shape[-1]).sum(axis=0)
+    knots = fill_curve([band_sigma(h[b], bits, matrix, range_, min_blocks) for b in range(NLF_BANDS)])
+    return [min(max(k, lo), hi) for k in knots]
+
+
+def check_curves(curves: Iterable[Sequence[float]]) -> List[List[float]]:
+    """A per-window list of curves: each 16 finite numbers >= 0."""
+    out: List[List[float]] = []
+    for c in curves:
+        if isinstance(c, (str, bytes)) or not hasattr(c, "__iter__"):
+            raise ValueError(f"a noise curve must be a sequence of {NLF_BANDS} numbers, got {c!r}")
+        c = list(c)
+        if len(c) != NLF_BANDS:
+            raise ValueError(f"a noise curve has {NLF_BANDS} knots, got {len(c)}")
+        try:
+            out.append(check_sigmas(c))
+        except ValueError as e:
+            raise ValueError(f"a knot of a noise curve: {e}") from None
+    return out
+
+
+def parse_curves(text: str) -> List[List[float]]:
+    """One curve per line, 16 numbers separated by blanks, one line per window in order; '#' starts a comment, blank lines are skipped.  Anything
+    else raises ValueError naming the line."""
+    out: List[List[float]] = []
+    for no, line in enumerate(text.splitlines(), 1):
+        words = line.split("#", 1)[0].split()
+        if not words:
+            continue
+        try:
+            try:
+                vals = [float(w) for w in words]
+            except ValueError:
+                raise ValueError("not a number") from None
+            out += check_curves([vals])
+        except ValueError as e:
+            raise ValueError(f"line {no}: {line.strip()!r}: {e}") from None
+    return out
+
+
+def format_curves(curves: Iterable[Sequence[float]], how: str = "") -> str:
+    """The text ``parse_curves`` reads back to the same floats (repr round-trips float64)."""
+    curves = [[float(k) for k in c] for c in curves]
+    head = (f"# noise-level function per window: sigma of 8-bit R'G'B' codes at {NLF_BANDS} luma levels from black to white, in the order the windows are "
+            f"restored; {len(curves)} window{'' if len(curves) == 1 else 's'}")
+    return head + (f"; {how}" if how else "") + "\n" + "".join(" ".join(repr(k) for k in c) + "\n" for c in curves)

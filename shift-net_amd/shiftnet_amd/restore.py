@@ -18,6 +18,10 @@ Noise level (``sigma``, denoise variants): a number, a list with one number per 
 histograms of the luma's 2 x 2 Haar HH coefficient, made on the device from the payloads the window has uploaded anyway
 (``sn_yuv_noise_hist``, shiftnet_amd/noise.py).
 
+Noise model (``noise_model``, denoise variants, off by default): sensor noise is signal dependent, the shadows of R'G'B' carry more of it than the
+highlights.  ``"level"`` estimates per window a noise-level function -- sigma against the luma code, 16 knots -- from the same histograms split by
+brightness (``sn_yuv_noise_hist_bands``) and writes the network's noise plane per pixel from it (``sn_noise_map_level``), in place of one level everywhere.
+
 Active picture (``picture``, off by default): a letterboxed or pillarboxed stream is restored inside its picture rectangle only -- there the bytes
 are those of restoring the cropped stream, and the bars leave as they came in.  The rectangle is given by the caller, for the stream or per window,
 or found per window from the sums of the luma's rows and columns, made on the device from the payloads the window has uploaded anyway
@@ -331,6 +335,16 @@ class VideoRestorer:
     frame indices (each >= 1, strictly increasing) -- use these, run no detector.  Every scene is then restored as a clip of its own: the bytes
     are those of restoring each scene as a separate video.  Once ``restore()`` has been exhausted ``stats["cuts"]`` lists the scene starts used,
     ``stats["cut_measure"]`` the m[t] of every frame (auto only; m[0] = 0.0) and ``stats["cuts_ignored"]`` the listed cuts at or beyond the end.
+    noise_model: None -- ``noise_map = sigma / 255`` at every pixel, today's code path and bytes; ``"level"`` (needs ``sigma="auto"``) -- per window a
+    noise-level function is estimated from band histograms of the payloads the window has uploaded anyway (``sn_yuv_noise_hist_bands``; noise.window_curve
+    on the host: sigma of 8-bit R'G'B' at 16 luma levels, holes filled, clamped to ``sigma_clamp``) and ``sn_noise_map_level`` writes the window's noise
+    plane from it: the curve at the low-passed luma of every pixel, which replaces the broadcast number.  The flat estimate still runs and is still
+    reported.  A list of curves (16 numbers each), one per window in the order the windows are restored, is used as given: no estimate of the curve
+    runs, and running out is a ValueError that names the window.  Any ``noise_model`` with a deblur variant is a ValueError.  **A heuristic, checked on
+    synthetic clips only**: the networks were trained with uniform maps and nobody has judged their output for a varying one; the curve is a function
+    of the luma alone; texture adds to a band's estimate as it does to the flat one.  With ``picture`` both kernels see the rectangle as the whole
+    frame.  ``stats["window_nlf"]`` lists the 16 knots of every window, ``stats["nlf_launches"]`` counts the ``sn_yuv_noise_hist_bands`` launches and
+    ``stats["nlf_map_launches"]`` the ``sn_noise_map_level`` launches.
     picture: None -- the whole frame, today's code path and bytes; ``(x0, y0, w, h)`` in luma samples -- restore that rectangle of every frame; a
     list with one rectangle (or None) per window in the order the windows are restored (running out is a ValueError that names the window).  The
     two are told apart by their elements: four numbers are one rectangle, anything whose elements are sequences or None is a list, of four windows
@@ -362,7 +376,7 @@ class VideoRestorer:
 
     def __init__(self, net, one_len: int, sigma=None, pipeline: bool = True, scene_cuts=None,
                  cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0),
-                 picture=None, bar_level: float = 1.0, out_format=None, dither=None, dither_seed: int = 0) -> None:
+                 picture=None, bar_level: float = 1.0, out_format=None, dither=None, dither_seed: int = 0, noise_model=None) -> None:
         import torch
         from .lib import YuvFmt
         self.torch = torch
@@ -397,6 +411,22 @@ class VideoRestorer:
         if self.sigma_mode != "fixed" and not self.V.denoise:
             raise ValueError(f"sigma={'auto' if self.sigma_mode == 'auto' else 'a per-window list'!r} is for the denoise variants; {type(net).__name__} "
                              "of a deblur variant takes no noise level")
+        # nlf_mode: None (the code path without any of the rest), "level", "list"
+        self.nlf_mode, self.nlf_list = None, None
+        if noise_model is not None:
+            if not self.V.denoise:
+                raise ValueError(f"noise_model is for the denoise variants; {type(net).__name__} of a deblur variant takes no noise level")
+            if isinstance(noise_model, str):
+                if noise_model != "level":
+                    raise ValueError(f"noise_model must be None, 'level' or a list of curves, got {noise_model!r}")
+                if self.sigma_mode != "auto":
+                    raise ValueError("noise_model='level' estimates the curve beside the flat estimate: it needs sigma='auto'")
+                self.nlf_mode = "level"
+            elif hasattr(noise_model, "__iter__"):
+                from .noise import check_curves
+                self.nlf_list, self.nlf_mode = check_curves(noise_model), "list"
+            else:
+                raise ValueError(f"noise_model must be None, 'level' or a list of curves, got {noise_model!r}")
         # picture_mode: "full" (None: the code path without any of the rest), "auto", "fixed" (one rectangle), "list"
         self.picture, self.picture_mode, self.bar_level = None, "full", float(bar_level)
         if isinstance(picture, str):
@@ -419,6 +449,7 @@ class VideoRestorer:
         self._shape = None
         self._wsig, self._wfsig, self._noise_launches = [], [], 0
         self._wpic, self._picture_launches, self._staged, self._picture_wait = [], 0, 0, []
+        self._wnlf, self._nlf_launches, self._nlf_map_launches = [], 0, 0
 
     # -- per-shape state: two slots of staging and device buffers, sized for the largest window -------------------------------------
     def _prepare(self, fmt, h: int, w: int) -> None:
@@ -461,6 +492,15 @@ class VideoRestorer:
             self.dev_hist = [torch.empty((tin, self.nb), dtype=torch.uint32, device=dev) for _ in range(2)]
             self.pin_hist = [torch.empty((tin, self.nb), dtype=torch.uint32).pin_memory() for _ in range(2)]
             self.ev_noise = ev()
+        if self.nlf_mode is not None:
+            from .noise import clip_codes
+            self.noise_lo, self.noise_hi = clip_codes(fmt.bits, fmt.range)
+        if self.nlf_mode == "level":                              # per slot: the window's band histograms on the device and in pinned memory
+            from .noise import NLF_BANDS, nlf_bins
+            nbv = nlf_bins(fmt.bits)
+            self.dev_bands = [torch.empty((tin, NLF_BANDS, nbv), dtype=torch.uint32, device=dev) for _ in range(2)]
+            self.pin_bands = [torch.empty((tin, NLF_BANDS, nbv), dtype=torch.uint32).pin_memory() for _ in range(2)]
+            self.ev_bands = ev()
         if self.picture_mode == "auto":                           # per slot: the window's row and column sums on the device and in pinned memory
             self.dev_rows = [torch.empty((tin, h), dtype=torch.uint32, device=dev) for _ in range(2)]
             self.dev_cols = [torch.empty((tin, w), dtype=torch.uint32, device=dev) for _ in range(2)]
@@ -491,7 +531,7 @@ class VideoRestorer:
     def _stage(self, slot: int, frames: Sequence[np.ndarray], t0: int = 0) -> int:
         """Host frames -> pinned slot -> device -> RGB tensors, on the side stream.  Windows are staged in the order they are restored.
         t0: the number of the window's first restored frame in its clip (the dither's frame number)."""
-        from .io_edges import ingest_yuv, noise_hist_yuv, rowcol_sums_yuv
+        from .io_edges import ingest_yuv, noise_hist_bands_yuv, noise_hist_yuv, rowcol_sums_yuv
         torch = self.torch
         t = len(frames)
         rect = None
@@ -533,6 +573,11 @@ class VideoRestorer:
                 self.pin_hist[slot][:t].copy_(self.dev_hist[slot][:t], non_blocking=True)
                 self.ev_noise[slot].record(self.s_in)
                 self._noise_launches += 1
+            if self.nlf_mode == "level":                         # the same statistic by brightness band, from the same payloads, behind it
+                noise_hist_bands_yuv(self.dev_in[slot][:t], self.fmt, self.h, self.w, self.noise_lo, self.noise_hi, out=self.dev_bands[slot][:t], rect=rect)
+                self.pin_bands[slot][:t].copy_(self.dev_bands[slot][:t], non_blocking=True)
+                self.ev_bands[slot].record(self.s_in)
+                self._nlf_launches += 1
             ingest_yuv(self.dev_in[slot][:t], self.fmt, self.h, self.w, hp, wp, self.dtype, out=x, rect=rect)
             if x32 is not None:
                 ingest_yuv(self.dev_in[slot][:t], self.fmt, self.h, self.w, hp, wp, torch.float32, out=x32, rect=rect)
@@ -558,12 +603,27 @@ class VideoRestorer:
         self._wsig.append(sigma)
         return sigma
 
+    def _window_curve(self, slot: int, t: int) -> List[float]:
+        """The noise-level function of the window about to run (noise_model): 16 knots, sigma of 8-bit R'G'B'."""
+        k = len(self._wnlf)
+        if self.nlf_mode == "level":
+            from .noise import window_curve
+            self.ev_bands[slot].synchronize()                    # the copy of this slot's band histograms, on the side stream: not the device, not main
+            curve = window_curve(self.pin_bands[slot][:t].numpy(), self.fmt.bits, self.fmt.matrix, self.fmt.range, self.sigma_clamp)
+        else:
+            if k >= len(self.nlf_list):
+                raise ValueError(f"noise_model lists {len(self.nlf_list)} window{'' if len(self.nlf_list) == 1 else 's'}, window {k} has no entry")
+            curve = list(self.nlf_list[k])
+        self._wnlf.append(curve)
+        return curve
+
     def _run(self, slot: int, t: int, main) -> int:
         """Forward + egress on the main stream, copy back on the output stream."""
-        from .io_edges import egress_yuv, ingest_yuv
+        from .io_edges import egress_yuv, ingest_yuv, noise_map_level
         torch = self.torch
         n = t - PAST - FUTURE
         sigma = self._window_sigma(slot, t) if self.V.denoise else None
+        curve = self._window_curve(slot, t) if self.nlf_mode is not None else None
         rect = self.rect[slot]
         self._wpic.append(rect)
         with torch.cuda.stream(main), torch.no_grad():
@@ -576,7 +636,13 @@ class VideoRestorer:
             kw = {}
             if x32 is not None:
                 kw["shortcut"] = x32
-            if self.V.denoise:
+            if curve is not None:
+                # the plane from the payloads the ingest read (ev_ready lies behind their upload; they stay until ev_done); the knots are a kernel argument
+                nm = noise_map_level(self.dev_in[slot][:t], self.fmt, self.h, self.w, x.shape[3], x.shape[4], [c / 255.0 for c in curve], self.dtype,
+                                     self.noise_lo, self.noise_hi, rect=rect)
+                self._nlf_map_launches += 1
+                out = self.net.forward_fp32_out(x, nm, **kw)
+            elif self.V.denoise:
                 nm = torch.full((1, 1, 1, 1, 1), sigma / 255.0, dtype=self.dtype, device=self.dev).expand(1, t, 1, x.shape[3], x.shape[4])
                 out = self.net.forward_fp32_out(x, nm, **kw)
             else:
@@ -611,6 +677,9 @@ class VideoRestorer:
         self.stats["forward_s"] = sum(ms) / 1e3
         self.stats["windows"] = len(ms)
         self.stats["noise_launches"] = self._noise_launches
+        if self.nlf_mode is not None:
+            self.stats["window_nlf"] = [list(c) for c in self._wnlf]
+            self.stats["nlf_launches"], self.stats["nlf_map_launches"] = self._nlf_launches, self._nlf_map_launches
         self.stats["window_picture"] = list(self._wpic)
         self.stats["picture_launches"] = self._picture_launches
         if self.picture_mode == "auto":
@@ -652,6 +721,7 @@ class VideoRestorer:
         self._src = None
         self._wsig, self._wfsig, self._noise_launches = [], [], 0
         self._wpic, self._picture_launches, self._staged, self._picture_wait = [], 0, 0, []
+        self._wnlf, self._nlf_launches, self._nlf_map_launches = [], 0, 0
         main = torch.cuda.current_stream(self.dev)
 
         def checked(it):
@@ -769,6 +839,12 @@ def make_parser() -> argparse.ArgumentParser:
                          "(a heuristic that assumes white Gaussian noise); FILE lists one sigma per window, one per line ('#' comments)")
     ap.add_argument("--sigma_clamp", type=float, nargs=2, default=(0.0, 50.0), metavar=("LO", "HI"), help="auto: the estimate is clamped to this range")
     ap.add_argument("--sigma_out", default=None, metavar="FILE", help="write the sigma that every window was restored with, in the format --sigma FILE reads")
+    ap.add_argument("--noise_model", default="flat", metavar="{flat,level,FILE}",
+                    help="denoise variants: 'level' (needs --sigma auto) estimates per window the noise level as a function of brightness on the device and "
+                         "gives the network a noise plane that follows it (a heuristic, checked on synthetic clips only); FILE lists one curve per window, "
+                         "16 sigmas per line from black to white ('#' comments); default flat: one level per window")
+    ap.add_argument("--noise_model_out", default=None, metavar="FILE",
+                    help="write the curve every window was restored with, in the format --noise_model FILE reads")
     ap.add_argument("--matrix", choices=["bt601", "bt709"], default=None, help="default: bt709 when H >= 720, else bt601")
     ap.add_argument("--range", choices=["limited", "full"], default=None, help="default: the stream's XCOLORRANGE, else limited")
     ap.add_argument("--no_pipeline", action="store_true", help="run read / copy / forward / write one after the other")
@@ -834,6 +910,21 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                     sigma, sigma_how = parse_sigmas(fh.read()), "listed"
             except (OSError, ValueError) as e:
                 ap.error(f"--sigma {a.sigma}: {e}")
+    noise_model, nlf_how = None, "flat"
+    if a.noise_model != "flat":
+        if "denoise" not in a.variant:
+            ap.error(f"--noise_model {a.noise_model} is for the denoise variants")
+        if a.noise_model == "level":
+            if sigma_how != "auto":
+                ap.error("--noise_model level needs --sigma auto")
+            noise_model, nlf_how = "level", "level"
+        else:
+            from .noise import parse_curves
+            try:
+                with open(a.noise_model, "r") as fh:
+                    noise_model, nlf_how = parse_curves(fh.read()), "listed"
+            except (OSError, ValueError) as e:
+                ap.error(f"--noise_model {a.noise_model}: {e}")
     try:
         from .noise import check_clamp
         check_clamp(a.sigma_clamp)
@@ -873,7 +964,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         net = load_net(a.variant, a.checkpoint, a.dtype)
         vr = VideoRestorer(net, a.one_len, sigma=sigma, pipeline=not a.no_pipeline, scene_cuts=cuts, cut_threshold=a.cut_threshold,
                            cut_ratio=a.cut_ratio, sigma_clamp=a.sigma_clamp, picture=picture, bar_level=a.bar_level, out_format=a.out_format,
-                           dither=None if a.dither == "none" else a.dither, dither_seed=a.dither_seed)
+                           dither=None if a.dither == "none" else a.dither, dither_seed=a.dither_seed, noise_model=noise_model)
         if a.out_format is not None or a.dither != "none":
             log(f"output: C{a.out_format or hd.chroma}{'' if a.out_format else ' (as the input)'}, dither {a.dither}"
                 f"{' seed %d' % a.dither_seed if a.dither != 'none' else ''}")
@@ -911,6 +1002,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             from .noise import format_sigmas
             with open(a.sigma_out, "w") as fh:
                 fh.write(format_sigmas(ws or [], sigma_how))
+        wn = vr.stats.get("window_nlf")
+        if a.noise_model_out is not None:
+            from .noise import format_curves
+            with open(a.noise_model_out, "w") as fh:
+                fh.write(format_curves(wn or [], nlf_how))
+        if wn:
+            log(f"noise model ({nlf_how}): knots min {min(min(c) for c in wn):.2f} / max {max(max(c) for c in wn):.2f} over {len(wn)} "
+                f"window{'' if len(wn) == 1 else 's'}")
         if ws:
             log(f"sigma ({sigma_how}{', clamped to [%g, %g]' % tuple(a.sigma_clamp) if sigma_how == 'auto' else ''}): "
                 f"min {min(ws):.2f} / median {float(np.median(ws)):.2f} / max {max(ws):.2f} over {len(ws)} window{'' if len(ws) == 1 else 's'}")

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15 and 3.16 (run on the MI355X from the repository root).
+"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15, 3.16 and 3.17 (run on the MI355X from the repository root).
 
   kernels : time per pixel of sn_ingest_yuv / sn_egress_yuv / sn_yuv_thumb / sn_yuv_noise_hist (4:2:0 8 bit, 720p x 20 frames; the noise
             histogram on the same frames with noise of sigma 10 as well) beside sn_ingest_u8 / sn_egress_u8 on the same
@@ -19,6 +19,10 @@
             per window and the time the stager waits for the sums.  --mode kernels: time per pixel of sn_ingest_yuv / sn_egress_yuv on a 1080p and
             on an 804-row stream beside the _rect entry points with the whole-frame rectangle and with the picture's, and sn_yuv_rowcol_sums beside
             sn_yuv_thumb on the same payloads, interleaved as in the kernels part; --parent_lib SO adds the two entry points of another build.
+  nlf     : the noise-level function (3.17).  --mode kernels: time per launch of sn_yuv_noise_hist_bands and sn_noise_map_level (-> bf16) beside
+            sn_yuv_noise_hist and sn_ingest_yuv on the same payloads (4:2:0 8 bit, 720p x 20 frames, a blurred clip and the same with noise of sigma 10),
+            interleaved as in the kernels part.  --mode forward: steady-state wall time per 720p window of the pipelined denoiser (as the sigma part)
+            with sigma="auto" alone and with noise_model="level" on top, runs of the two alternating in one process, the first two windows left out.
 Prints one JSON object per part.
 """
 import argparse
@@ -38,7 +42,8 @@ import torch  # noqa: E402
 
 from shiftnet_amd import lib as L  # noqa: E402
 from shiftnet_amd import restore, synth, y4m  # noqa: E402
-from shiftnet_amd.io_edges import egress_u8, egress_yuv, ingest_u8, ingest_yuv, noise_hist_yuv, rowcol_sums_yuv, thumb_yuv, yuv_fmt  # noqa: E402
+from shiftnet_amd.io_edges import (egress_u8, egress_yuv, ingest_u8, ingest_yuv, noise_hist_bands_yuv, noise_hist_yuv, noise_map_level,  # noqa: E402
+                                   rowcol_sums_yuv, thumb_yuv, yuv_fmt)
 
 
 def summary(v):
@@ -204,6 +209,89 @@ def sigma(a):
                       "window_sigma_auto": [round(s, 3) for s in seen["auto"]], **res}))
 
 
+def nlf_kernels(a):
+    T, H, W = 20, 720, 1280
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    blur, _ = synth.blurred_clip(4, H, W, seed=1)
+    rgb = ingest_u8(torch.from_numpy(np.concatenate([blur] * 5)).cuda(), torch.float32)[0]
+    pay = egress_yuv(rgb, fmt, H, W)
+    pay_noisy = egress_yuv((rgb + torch.randn(rgb.shape, device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * (10.0 / 255)).clamp(0, 1), fmt, H, W)
+    x_bf = torch.empty((1, T, 3, H, W), dtype=torch.bfloat16, device="cuda")
+    nm = torch.empty((1, T, 1, H, W), dtype=torch.bfloat16, device="cuda")
+    hists = torch.empty((T, 511), dtype=torch.uint32, device="cuda")
+    bands = torch.empty((T, 16, 128), dtype=torch.uint32, device="cuda")
+    knots = [(9.0 - 0.4 * b) / 255.0 for b in range(16)]
+    cases = {
+        "ingest_yuv_bf16": lambda: ingest_yuv(pay, fmt, H, W, H, W, torch.bfloat16, out=x_bf),
+        "noise_hist_yuv": lambda: noise_hist_yuv(pay, fmt, H, W, out=hists),
+        "noise_hist_yuv_sigma10": lambda: noise_hist_yuv(pay_noisy, fmt, H, W, out=hists),
+        "noise_hist_bands_yuv": lambda: noise_hist_bands_yuv(pay, fmt, H, W, out=bands),
+        "noise_hist_bands_yuv_sigma10": lambda: noise_hist_bands_yuv(pay_noisy, fmt, H, W, out=bands),
+        "noise_map_level_bf16": lambda: noise_map_level(pay, fmt, H, W, H, W, knots, torch.bfloat16, out=nm),
+        "noise_map_level_bf16_sigma10": lambda: noise_map_level(pay_noisy, fmt, H, W, H, W, knots, torch.bfloat16, out=nm),
+    }
+    for f in cases.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in cases}
+    for _ in range(a.reps):
+        for k, f in cases.items():                                                   # interleaved: every repetition times every kernel
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.inner):
+                f()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.inner)
+    px = T * H * W
+    res = {k: {"us_per_launch": summary([m * 1e3 for m in v]), "ps_per_pixel": summary([m * 1e9 / px for m in v])} for k, v in ms.items()}
+    print(json.dumps({"part": "nlf", "mode": "kernels", "frames": T, "size": [H, W], "reps": a.reps, "inner": a.inner, **res}))
+
+
+def nlf_forward(a):
+    H, W, one_len, nwin = 720, 1280, 16, a.windows
+    n = one_len * nwin
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    blur, _ = synth.blurred_clip(8, H, W, seed=2)
+    rgb = ingest_u8(torch.from_numpy(blur).cuda(), torch.float32)[0]
+    g = torch.Generator("cuda").manual_seed(1)
+    frames = []
+    for i in range(n):                                                               # fresh noise of sigma 10 on every frame, as the sigma part
+        j = i % 14
+        x = rgb[j if j < 8 else 14 - j][None]
+        frames.append(egress_yuv((x + torch.randn(x.shape, device="cuda", generator=g) * (10.0 / 255)).clamp(0, 1), fmt, H, W)[0].cpu().numpy())
+    net = restore.load_net("denoise_small", "synthetic", "bf16")
+    seen = {}
+
+    def run(model):
+        vr = restore.VideoRestorer(net, one_len, sigma="auto", pipeline=True, noise_model=model)
+        stamps = []
+        t0 = time.perf_counter()
+        for i, p in enumerate(vr.restore(iter(frames), fmt, H, W)):
+            if (i + 1) % one_len == 0:
+                stamps.append(time.perf_counter())
+        total = time.perf_counter() - t0
+        seen[str(model)] = vr.stats.get("window_nlf")
+        gaps = [(b - c) * 1e3 for b, c in zip(stamps[1:], stamps[:-1])]
+        return {"total_s": total, "window_wall_ms": gaps[1:], "window_forward_ms": vr.stats["window_forward_ms"][2:]}
+
+    run(None)                                                                        # warm-up: code objects, engine buffers
+    run("level")
+    runs = {"auto": [], "level": []}
+    for _ in range(a.runs):
+        runs["auto"].append(run(None))
+        runs["level"].append(run("level"))
+    res = {}
+    for k, rs in runs.items():
+        res[k] = {"window_wall_ms": summary([g for r in rs for g in r["window_wall_ms"]]),
+                  "window_wall_ms_per_run": [round(statistics.median(r["window_wall_ms"]), 2) for r in rs],
+                  "window_forward_ms": summary([g for r in rs for g in r["window_forward_ms"]]), "total_s": [round(r["total_s"], 3) for r in rs],
+                  "frames_per_s_end_to_end": [round(n / r["total_s"], 2) for r in rs]}
+    print(json.dumps({"part": "nlf", "mode": "forward", "variant": "denoise_small", "dtype": "bf16", "one_len": one_len, "windows": nwin, "size": [H, W],
+                      "runs": a.runs, "window_nlf_first": [round(k, 3) for k in seen["level"][0]], **res}))
+
+
 PICTURE = dict(H=1080, W=1920, rect=(0, 138, 1920, 804))
 
 
@@ -343,7 +431,7 @@ def picture_part(a):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture"])
+    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf"])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--inner", type=int, default=200)
     ap.add_argument("--windows", type=int, default=8)
@@ -353,8 +441,9 @@ if __name__ == "__main__":
     ap.add_argument("--cut_every", type=int, default=0, help="pipeline part: a cut every N frames in the stream (0: none)")
     ap.add_argument("--parent_lib", default=None, metavar="SO", help="kernels part and picture part in kernels mode: a shared library built from another commit's "
                     "csrc/sn_yuv.hip alone; its sn_ingest_yuv / sn_egress_yuv are timed beside this build's")
-    ap.add_argument("--mode", choices=["forward", "kernels"], default="forward", help="picture part: which measurement")
+    ap.add_argument("--mode", choices=["forward", "kernels"], default="forward", help="picture and nlf parts: which measurement")
     ap.add_argument("--picture", choices=["auto", "fixed"], default="auto", help="picture part, forward mode: VideoRestorer(picture='auto') or the rectangle itself")
     a = ap.parse_args()
     with torch.no_grad():
-        {"kernels": kernels, "pipeline": pipeline, "sigma": sigma, "picture": picture_part}[a.part](a)
+        {"kernels": kernels, "pipeline": pipeline, "sigma": sigma, "picture": picture_part,
+         "nlf": nlf_kernels if a.mode == "kernels" else nlf_forward}[a.part](a)
