@@ -1,0 +1,212 @@
+"""The command line of the video restorer (inference/restore_video.py): Y4M in, Y4M out.  The restorer itself is shiftnet_amd/restore.py, which
+hands these names on; nothing here touches the device before the arguments have been judged."""
+from __future__ import annotations
+
+import argparse
+import sys
+import time
+from typing import Optional, Sequence
+
+import numpy as np
+
+
+def sigma_arg(word: str):
+    """--sigma: a number stays the float it always was; 'auto'; anything else names a file with one sigma per window."""
+    try:
+        return float(word)
+    except ValueError:
+        return word
+
+
+def picture_arg(word: str):
+    """--picture: 'full' -> None; 'auto'; X:Y:W:H -> the rectangle; anything else names a file with one rectangle per window."""
+    if word == "full":
+        return None
+    parts = word.split(":")
+    if len(parts) == 4 and all(p.isdigit() for p in parts):
+        return tuple(int(p) for p in parts)
+    return word
+
+
+def _modes():
+    from .y4m import MODES
+    return MODES
+
+
+def make_parser() -> argparse.ArgumentParser:
+    from .restore import VARIANTS
+    ap = argparse.ArgumentParser(description="Restore a Y4M video with Shift-Net on the MI355X: same frames and size out, same pixel format unless "
+                                             "--out_format names another")
+    ap.add_argument("--variant", choices=list(VARIANTS), required=True)
+    ap.add_argument("--checkpoint", required=True, help="checkpoint path, or 'synthetic' for the deterministic synthetic weights")
+    ap.add_argument("--dtype", choices=["fp32", "fp16", "bf16"], default="bf16")
+    ap.add_argument("--one_len", type=int, default=16, help="frames restored per window")
+    ap.add_argument("--sigma", type=sigma_arg, default=None, metavar="{NUMBER,auto,FILE}",
+                    help="noise level (8-bit code values), required by the denoise variants: a number; 'auto' estimates it per window on the device "
+                         "(a heuristic that assumes white Gaussian noise); FILE lists one sigma per window, one per line ('#' comments)")
+    ap.add_argument("--sigma_clamp", type=float, nargs=2, default=(0.0, 50.0), metavar=("LO", "HI"), help="auto: the estimate is clamped to this range")
+    ap.add_argument("--sigma_out", default=None, metavar="FILE", help="write the sigma that every window was restored with, in the format --sigma FILE reads")
+    ap.add_argument("--noise_model", default="flat", metavar="{flat,level,FILE}",
+                    help="denoise variants: 'level' (needs --sigma auto) estimates per window the noise level as a function of brightness on the device and "
+                         "gives the network a noise plane that follows it (a heuristic, checked on synthetic clips only); FILE lists one curve per window, "
+                         "16 sigmas per line from black to white ('#' comments); default flat: one level per window")
+    ap.add_argument("--noise_model_out", default=None, metavar="FILE",
+                    help="write the curve every window was restored with, in the format --noise_model FILE reads")
+    ap.add_argument("--matrix", choices=["bt601", "bt709"], default=None, help="default: bt709 when H >= 720, else bt601")
+    ap.add_argument("--range", choices=["limited", "full"], default=None, help="default: the stream's XCOLORRANGE, else limited")
+    ap.add_argument("--no_pipeline", action="store_true", help="run read / copy / forward / write one after the other")
+    ap.add_argument("--scene_cuts", default="off", metavar="{off,auto,FILE}",
+                    help="restore every scene as a clip of its own: 'auto' finds the cuts on the device (a heuristic, see --cut_threshold / --cut_ratio), "
+                         "FILE lists the first frame of every scene but the first, one index per line ('#' comments); default off: the stream is one clip")
+    ap.add_argument("--cut_threshold", type=float, default=4.0, help="auto: smallest mean absolute difference of 8x8 block means (8-bit code units) of a cut")
+    ap.add_argument("--cut_ratio", type=float, default=2.5, help="auto: ... and at least this many times the median of the six neighbouring frames' differences")
+    ap.add_argument("--picture", default="full", metavar="{full,auto,X:Y:W:H,FILE}",
+                    help="restore the active picture of a letterboxed / pillarboxed stream only and leave the bars as they are: X:Y:W:H in luma samples; "
+                         "'auto' finds the bars per window on the device (a heuristic, see --bar_level); FILE lists 'x0 y0 w h' (or 'full') per window, one "
+                         "per line ('#' comments); default full: the whole frame")
+    ap.add_argument("--bar_level", type=float, default=1.0, help="auto: a row or column is bar if its mean luma stays within this many 8-bit codes of black")
+    ap.add_argument("--picture_out", default=None, metavar="FILE", help="write the picture every window was restored with, in the format --picture FILE reads")
+    ap.add_argument("--out_format", choices=list(_modes()), default=None, metavar="TAG",
+                    help="write this Y4M C tag instead of the input's (%(choices)s): another bit depth and chroma layout, e.g. 444p10 or 420p10 to keep the "
+                         "precision of the result when 8 bit came in; matrix and range stay the input's; default: the input's format")
+    ap.add_argument("--dither", choices=["none", "tpdf"], default="none",
+                    help="tpdf: add triangular noise of +-1 code before rounding to the output's codes: no banding, about 0.5 code rms of noise instead; "
+                         "default none: round to nearest")
+    ap.add_argument("--dither_seed", type=int, default=0, metavar="N", help="tpdf: which noise (0 .. 2^32 - 1); the same seed gives the same bytes")
+    ap.add_argument("--cuts_out", default=None, metavar="FILE", help="write the scene starts that were used, in the format --scene_cuts FILE reads")
+    ap.add_argument("input", metavar="IN", help="Y4M file, or - for stdin")
+    ap.add_argument("output", metavar="OUT", help="Y4M file, or - for stdout")
+    return ap
+
+
+def _text_reader(parse):
+    """parse(text) as a reader by path."""
+    def read(path):
+        with open(path, "r") as fh:
+            return parse(fh.read())
+    return read
+
+
+def _text_writer(fmt):
+    """fmt(*args) -> text as a writer by path."""
+    def write(path, *args):
+        with open(path, "w") as fh:
+            fh.write(fmt(*args))
+    return write
+
+
+def _listed(ap: argparse.ArgumentParser, flag: str, word: str, read):
+    """The FILE form of a {keyword,FILE} option: what ``read(word)`` makes of the file, or the parser's error naming the option and the word."""
+    try:
+        return read(word)
+    except (OSError, ValueError) as e:
+        ap.error(f"{flag} {word}: {e}")
+
+
+def _write_out(path: Optional[str], write, *args) -> None:
+    """A --*_out option: ``write(path, *args)`` where a path was given."""
+    if path is not None:
+        write(path, *args)
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    from . import lib as L
+    from . import noise, picture as pic, scenes
+    from .io_edges import yuv_fmt
+    from .restore import VideoRestorer, load_net
+    from .y4m import Y4MReader, Y4MWriter, output_header
+    ap = make_parser()
+    a = ap.parse_args(argv)
+    if not (0 <= a.dither_seed < 2 ** 32):
+        ap.error("--dither_seed: an integer in 0 .. 2^32 - 1")
+    if "denoise" in a.variant and a.sigma is None:
+        ap.error("--sigma is required by the denoise variants")
+    log = lambda s: (sys.stderr.write(s + "\n"), sys.stderr.flush())      # noqa: E731
+    sigma, sigma_how = a.sigma, "fixed"
+    if isinstance(sigma, str):
+        if "denoise" not in a.variant:
+            ap.error(f"--sigma {sigma} is for the denoise variants")
+        if sigma == "auto":
+            sigma_how = "auto"
+        else:
+            sigma, sigma_how = _listed(ap, "--sigma", sigma, _text_reader(noise.parse_sigmas)), "listed"
+    noise_model, nlf_how = None, "flat"
+    if a.noise_model != "flat":
+        if "denoise" not in a.variant:
+            ap.error(f"--noise_model {a.noise_model} is for the denoise variants")
+        if a.noise_model == "level":
+            if sigma_how != "auto":
+                ap.error("--noise_model level needs --sigma auto")
+            noise_model, nlf_how = "level", "level"
+        else:
+            noise_model, nlf_how = _listed(ap, "--noise_model", a.noise_model, _text_reader(noise.parse_curves)), "listed"
+    try:
+        noise.check_clamp(a.sigma_clamp)
+    except ValueError as e:
+        ap.error(f"--sigma_clamp: {e}")
+    cuts = None if a.scene_cuts == "off" else a.scene_cuts
+    if cuts not in (None, "auto"):
+        cuts = _listed(ap, "--scene_cuts", cuts, _text_reader(scenes.parse_cuts))
+    picture, picture_how = picture_arg(a.picture), "fixed"
+    if picture == "auto":
+        picture_how = "auto"
+    elif isinstance(picture, str):
+        picture, picture_how = _listed(ap, "--picture", picture, pic.read_pictures), "listed"
+    fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
+    fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
+    try:
+        rd = Y4MReader(fin)
+        hd = rd.header
+        matrix = a.matrix or ("bt709" if hd.height >= 720 else "bt601")
+        rng = a.range or (hd.color_range if hd.color_range in ("full", "limited") else "limited")
+        log(f"input: {hd.width}x{hd.height} C{hd.chroma} F{hd.fps}; matrix {matrix}{'' if a.matrix else ' (default)'}, range {rng}"
+            f"{'' if a.range else (' (stream)' if hd.color_range else ' (default)')}")
+        fmt = yuv_fmt(hd.bits, hd.chroma_code, L.SN_YUV_BT709 if matrix == "bt709" else L.SN_YUV_BT601,
+                      L.SN_YUV_FULL if rng == "full" else L.SN_YUV_LIMITED)
+        net = load_net(a.variant, a.checkpoint, a.dtype)
+        vr = VideoRestorer(net, a.one_len, sigma=sigma, pipeline=not a.no_pipeline, scene_cuts=cuts, cut_threshold=a.cut_threshold,
+                           cut_ratio=a.cut_ratio, sigma_clamp=a.sigma_clamp, picture=picture, bar_level=a.bar_level, out_format=a.out_format,
+                           dither=None if a.dither == "none" else a.dither, dither_seed=a.dither_seed, noise_model=noise_model)
+        if a.out_format is not None or a.dither != "none":
+            log(f"output: C{a.out_format or hd.chroma}{'' if a.out_format else ' (as the input)'}, dither {a.dither}"
+                f"{' seed %d' % a.dither_seed if a.dither != 'none' else ''}")
+        wr = Y4MWriter(fout, output_header(hd, a.out_format))
+        t0 = time.perf_counter()
+        n = 0
+        for p in vr.restore(rd, fmt, hd.height, hd.width):
+            wr.write(p)
+            n += 1
+            if n % max(a.one_len, 1) == 0:
+                log(f"  {n} frames, {time.perf_counter() - t0:.1f} s")
+        fout.flush()
+        dt = time.perf_counter() - t0
+        fwd = vr.stats["forward_s"]
+        used = vr.stats.get("cuts", [])
+        if vr.stats.get("cuts_ignored"):
+            log(f"scene cuts at or beyond the end of the stream ({n} frames) ignored: {vr.stats['cuts_ignored']}")
+        _write_out(a.cuts_out, _text_writer(scenes.format_cuts), used)
+        log(f"done: {n} frames in {dt:.2f} s, {n / dt if dt > 0 else 0.0:.2f} frames/s end to end, "
+            f"{n / fwd if fwd > 0 else 0.0:.2f} frames/s forward only, {len(used) + 1} scene{'s' if used else ''}"
+            f"{'' if cuts is None else (' (cuts found)' if cuts == 'auto' else ' (cuts listed)')}")
+        wp = vr.stats.get("window_picture", [])
+        _write_out(a.picture_out, pic.write_pictures, wp, picture_how)
+        if picture is not None:
+            kinds = sorted({r for r in wp if r is not None})
+            log(f"picture ({picture_how}): {sum(r is not None for r in wp)} of {len(wp)} window{'' if len(wp) == 1 else 's'} restored inside a rectangle"
+                f"{': ' + ', '.join('%d:%d:%d:%d' % r for r in kinds[:4]) + (' ...' if len(kinds) > 4 else '') if kinds else ''}")
+        ws = vr.stats.get("window_sigma")
+        _write_out(a.sigma_out, _text_writer(noise.format_sigmas), ws or [], sigma_how)
+        wn = vr.stats.get("window_nlf")
+        _write_out(a.noise_model_out, _text_writer(noise.format_curves), wn or [], nlf_how)
+        if wn:
+            log(f"noise model ({nlf_how}): knots min {min(min(c) for c in wn):.2f} / max {max(max(c) for c in wn):.2f} over {len(wn)} "
+                f"window{'' if len(wn) == 1 else 's'}")
+        if ws:
+            log(f"sigma ({sigma_how}{', clamped to [%g, %g]' % tuple(a.sigma_clamp) if sigma_how == 'auto' else ''}): "
+                f"min {min(ws):.2f} / median {float(np.median(ws)):.2f} / max {max(ws):.2f} over {len(ws)} window{'' if len(ws) == 1 else 's'}")
+    finally:
+        if fin is not sys.stdin.buffer:
+            fin.close()
+        if fout is not sys.stdout.buffer:
+            fout.close()
+    return 0

@@ -1,0 +1,281 @@
+"""The pure part of the video restorer (shiftnet_amd/restore.py): which frames a window reads, the format a stream is written in, the
+per-window options, and the frame source that turns an iterator of unknown length into windows.
+
+No torch here: the module is used by the CPU tests and by the command line before a device exists.
+"""
+from __future__ import annotations
+
+import queue
+import threading
+from typing import Iterable, Iterator, List, Optional, Tuple
+
+import numpy as np
+
+from .scenes import ListedCuts, check_cuts
+
+PAST, FUTURE = 2, 2
+
+
+# ---- the window planner -----------------------------------------------------------------------------------------------------------
+def reflect_index(i: int, n: int) -> int:
+    """Frame index i of a clip of n frames: reflection about the first / last frame without repeating it; clamped where n <= 2."""
+    if n <= 2:
+        return min(max(i, 0), n - 1)
+    if i < 0:
+        i = -i
+    if i >= n:
+        i = 2 * (n - 1) - i
+    return min(max(i, 0), n - 1)
+
+
+def window_indices(k: int, one_len: int, n: int, past: int = PAST, future: int = FUTURE) -> Tuple[int, int, List[int]]:
+    """(first restored frame, number restored, the past + number + future input frame indices) of window k of a clip of n frames."""
+    lo = k * one_len
+    hi = min(lo + one_len, n)
+    return lo, hi - lo, [reflect_index(i, n) for i in range(lo - past, hi + future)]
+
+
+def plan_windows(n: int, one_len: int, past: int = PAST, future: int = FUTURE) -> List[Tuple[int, int, List[int]]]:
+    if n < 1 or one_len < 1:
+        raise ValueError(f"plan_windows: need n >= 1 and one_len >= 1, got {n}, {one_len}")
+    return [window_indices(k, one_len, n, past, future) for k in range((n + one_len - 1) // one_len)]
+
+
+def plan_scene_windows(n: int, one_len: int, cuts: Iterable[int], past: int = PAST, future: int = FUTURE) -> List[Tuple[int, int, List[int]]]:
+    """plan_windows of every scene [0, c_1), [c_1, c_2), ..., [c_k, n) on its own, indices shifted to the stream's.  Cuts at or beyond n are
+    ignored."""
+    if n < 1 or one_len < 1:
+        raise ValueError(f"plan_scene_windows: need n >= 1 and one_len >= 1, got {n}, {one_len}")
+    starts = [0] + [c for c in check_cuts(cuts) if c < n]
+    plan = []
+    for a, b in zip(starts, starts[1:] + [n]):
+        plan += [(a + lo, cnt, [a + i for i in idx]) for lo, cnt, idx in plan_windows(b - a, one_len, past, future)]
+    return plan
+
+
+DITHERS = ("tpdf",)
+
+
+def plan_output(fmt, out_format=None, dither=None, dither_seed=0):
+    """(the format written, the dither word or None, the seed) for a stream read as ``fmt`` (anything with bits, chroma, matrix, range that is built
+    from the four): ``out_format`` is a C tag of y4m.MODES and changes bit depth and chroma layout only, matrix and range stay the input's; None,
+    or a tag that says what ``fmt`` says, returns ``fmt`` itself.  ValueError for an unknown tag, a dither word other than None / "tpdf", and a seed
+    outside 0 .. 2^32 - 1."""
+    from .y4m import MODES
+    out = fmt
+    if out_format is not None:
+        if not isinstance(out_format, str) or out_format not in MODES:
+            raise ValueError(f"out_format must be None or one of {', '.join(MODES)}, got {out_format!r}")
+        bits, chroma = MODES[out_format]
+        if (bits, chroma) != (fmt.bits, fmt.chroma):
+            out = type(fmt)(bits, chroma, fmt.matrix, fmt.range)
+    if dither is not None and not (isinstance(dither, str) and dither in DITHERS):
+        raise ValueError(f"dither must be None or 'tpdf', got {dither!r}")
+    if isinstance(dither_seed, (bool, float, str)) or int(dither_seed) != dither_seed or not (0 <= int(dither_seed) < 2 ** 32):
+        raise ValueError(f"dither_seed must be an integer in 0 .. 2^32 - 1, got {dither_seed!r}")
+    return out, dither, int(dither_seed)
+
+
+def pad_multiple(topo: str) -> int:
+    return 8 if topo == "plus" else 4
+
+
+def padded_size(h: int, w: int, topo: str) -> Tuple[int, int]:
+    m = pad_multiple(topo)
+    return (h + m - 1) // m * m, (w + m - 1) // m * m
+
+
+# ---- per-window options: one value for the stream, or a list with one entry per window ---------------------------------------------
+class PerWindow:
+    """An option of the restorer that is one value for the stream (``listed=False``) or a list with one entry per window in the order the
+    windows are restored.  How many windows a stream has is known only at its end, so a list that is too short is found at the window
+    without an entry."""
+
+    def __init__(self, name: str, value, listed: bool) -> None:
+        self.name, self.value, self.listed = name, value, listed
+
+    def at(self, k: int):
+        if not self.listed:
+            return self.value
+        n = len(self.value)
+        if k >= n:
+            raise ValueError(f"{self.name} lists {n} window{'' if n == 1 else 's'}, window {k} has no entry")
+        return self.value[k]
+
+
+# The accepted forms of the four options, each -> (mode, value).  What depends on the network (deblur or denoise) is judged by the caller.
+def scene_cuts_form(scene_cuts):
+    """None -> ("off", None); "auto" -> ("auto", "auto"); an iterable of frame indices -> ("list", the checked list)."""
+    if scene_cuts is None:
+        return "off", None
+    if isinstance(scene_cuts, str):
+        if scene_cuts != "auto":
+            raise ValueError(f"scene_cuts must be None, 'auto' or an iterable of frame indices, got {scene_cuts!r}")
+        return "auto", "auto"
+    return "list", check_cuts(scene_cuts)
+
+
+def sigma_form(sigma):
+    """None or a number -> ("fixed", PerWindow of None or the float); "auto" -> ("auto", None); a sequence -> ("list", PerWindow of the checked list)."""
+    if isinstance(sigma, str):
+        if sigma != "auto":
+            raise ValueError(f"sigma must be a number, 'auto' or a sequence of numbers, got {sigma!r}")
+        return "auto", None
+    if sigma is not None and hasattr(sigma, "__iter__"):
+        from .noise import check_sigmas
+        return "list", PerWindow("sigma", check_sigmas(sigma), True)
+    return "fixed", PerWindow("sigma", None if sigma is None else float(sigma), False)
+
+
+def noise_model_form(noise_model):
+    """None -> (None, None); "level" -> ("level", None); a list of curves -> ("list", PerWindow of the checked list)."""
+    if noise_model is None:
+        return None, None
+    if isinstance(noise_model, str) and noise_model == "level":
+        return "level", None
+    if isinstance(noise_model, str) or not hasattr(noise_model, "__iter__"):
+        raise ValueError(f"noise_model must be None, 'level' or a list of curves, got {noise_model!r}")
+    from .noise import check_curves
+    return "list", PerWindow("noise_model", check_curves(noise_model), True)
+
+
+def picture_form(picture):
+    """None -> ("full", None); "auto" -> ("auto", None); four numbers -> ("fixed", the tuple); anything whose elements are sequences or None ->
+    ("list", the list).  The rectangles are judged where the stream is known (picture.check_pictures)."""
+    if picture is None:
+        return "full", None
+    if isinstance(picture, str):
+        if picture != "auto":
+            raise ValueError(f"picture must be None, 'auto', (x0, y0, w, h) or a list of rectangles, got {picture!r}")
+        return "auto", None
+    picture = list(picture)
+    if len(picture) == 4 and not any(r is None or hasattr(r, "__iter__") for r in picture):
+        return "fixed", tuple(picture)
+    return "list", picture
+
+
+# ---- frame source: look-ahead over an iterator whose length is unknown until it ends ----------------------------------------------
+class _SceneFrames:
+    """The windows of plan_scene_windows from an iterator of unknown length, with the cut decisions arriving late.  ``decider``
+    (scenes.ListedCuts, scenes.CutDetector behind the restorer's _DeviceThumbs, or anything shaped like them) is fed every frame exactly once
+    and in order, in chunks, and answers ``is_cut(t)`` for t < ``decided``; it needs ``lookahead`` frames beyond t to decide t.
+
+    The window that restores [lo, lo + L) of a scene that started at a reads frames lo - 2 .. lo + L + 1 unless the scene ends before: it
+    depends on the decisions for lo + 1 .. lo + L + 1, so it is handed out once frame lo + L + 1 + lookahead has been read or the stream has
+    ended.  Frames before max(a, lo - 2) of the next window are dropped: at most L + 4 + lookahead + 1 are held."""
+
+    def __init__(self, it: Iterable[np.ndarray], decider) -> None:
+        self.it = iter(it)
+        self.decider = decider
+        self.base = 0                     # index of buf[0]
+        self.buf: List[np.ndarray] = []
+        self.n: Optional[int] = None      # known once the iterator ends
+        self.fed = 0                      # frames handed to the decider
+        self.finished = False             # the decider has been told that the stream has ended
+        self.a = 0                        # first frame of the current scene
+        self.lo = 0                       # next frame to restore
+        self.k = 0
+        self.cuts: List[int] = []         # the scene starts used
+        self.clip_lo = 0                  # the first restored frame of the window handed out last, counted from the first frame of its clip: the scene
+
+    def _fill(self, upto: int) -> None:
+        while self.n is None and self.base + len(self.buf) <= upto:
+            try:
+                self.buf.append(next(self.it))
+            except StopIteration:
+                self.n = self.base + len(self.buf)
+        have = self.base + len(self.buf)
+        if have > self.fed:
+            self.decider.feed(self.buf[self.fed - self.base:])
+            self.fed = have
+        if self.n is not None and not self.finished:
+            self.decider.finish()
+            self.finished = True
+
+    def window(self, k: int, one_len: int) -> Optional[Tuple[int, int, List[np.ndarray]]]:
+        """The frames of the k-th window of the stream (k counts up from 0 across the scenes), or None past the end."""
+        assert k == self.k, "windows are handed out in order"
+        lo, a = self.lo, self.a
+        last = lo + one_len + FUTURE - 1                                      # the last frame this window can read
+        self._fill(last + self.decider.lookahead)
+        n = self.n if self.n is not None else self.base + len(self.buf)      # not at the end: n > last
+        if lo >= n:
+            return None
+        cut = next((t for t in range(lo + 1, min(last, n - 1) + 1) if self.decider.is_cut(t)), None)
+        # the scene's end.  Without a cut in reach and before the end of the stream it is not known, only that it lies beyond `last`: then no
+        # index of this window reflects about it, and n (> last) stands in for it with the same result
+        b = cut if cut is not None else n
+        hi = min(lo + one_len, b)
+        frames = [self.buf[a + reflect_index(i - a, b - a) - self.base] for i in range(lo - PAST, hi + FUTURE)]
+        self.k += 1
+        self.lo = hi
+        self.clip_lo = lo - a
+        if cut is not None and hi == cut:
+            self.a = cut
+            self.cuts.append(cut)
+        drop = max(self.a, self.lo - PAST) - self.base                        # the next window reaches back to here
+        if drop > 0:
+            del self.buf[:drop]
+            self.base += drop
+        return lo, hi - lo, frames
+
+    def windows(self, one_len: int) -> Iterator[Tuple[int, List[np.ndarray], int]]:
+        """(k, the frames of window k, its clip_lo) of every window of the stream, in order."""
+        k = 0
+        while True:
+            win = self.window(k, one_len)
+            if win is None:
+                return
+            yield k, win[2], self.clip_lo
+            k += 1
+
+
+class _Frames(_SceneFrames):
+    """The source of a stream that is one clip: no frame starts a scene, so the windows are plan_windows'."""
+
+    def __init__(self, it: Iterable[np.ndarray]) -> None:
+        super().__init__(it, ListedCuts(()))
+
+
+class _Thread(threading.Thread):
+    """A producer thread: runs fn(put) and forwards its exception to the consumer of the queue."""
+    END = object()
+
+    def __init__(self, fn, depth: int) -> None:
+        super().__init__(daemon=True)
+        self.q: "queue.Queue" = queue.Queue(maxsize=depth)
+        self.fn, self.stop = fn, threading.Event()
+
+    def put(self, item) -> bool:
+        while not self.stop.is_set():
+            try:
+                self.q.put(item, timeout=0.1)
+                return True
+            except queue.Full:
+                pass
+        return False
+
+    def run(self) -> None:
+        try:
+            self.fn(self.put)
+            self.put(self.END)
+        except BaseException as e:      # noqa: BLE001 -- handed to the consumer, which raises it
+            self.put(e)
+
+    def __iter__(self):
+        while True:
+            item = self.q.get()
+            if item is self.END:
+                return
+            if isinstance(item, BaseException):
+                raise item
+            yield item
+
+    def close(self) -> None:
+        self.stop.set()
+        while self.is_alive():
+            try:
+                self.q.get_nowait()
+            except queue.Empty:
+                pass
+            self.join(timeout=0.05)

@@ -179,13 +179,17 @@ def test_restorer_noise_model_forms():
 
 
 def test_per_window_list_of_curves_running_short_names_the_window():
-    vr = restore.VideoRestorer.__new__(restore.VideoRestorer)
     a, b = [1.0] * 16, [float(i) for i in range(16)]
-    vr.nlf_mode, vr.nlf_list, vr._wnlf = "list", [a, b], []
-    assert vr._window_curve(0, 9) == a and vr._window_curve(1, 9) == b
+    mode, nlf = restore.noise_model_form([a, b])
+    assert mode == "list" and isinstance(nlf, restore.PerWindow) and nlf.at(0) == a and nlf.at(1) == b
+    with pytest.raises(ValueError, match="noise_model lists 2 windows, window 2 has no entry"):
+        nlf.at(2)
+    vr = restore.VideoRestorer.__new__(restore.VideoRestorer)                               # the restorer's record of what every window used
+    vr.nlf_mode, vr.nlf, vr.run = mode, nlf, restore._Run()
+    assert vr._window_curve(None, 9) == a and vr._window_curve(None, 9) == b
     with pytest.raises(ValueError, match="window 2"):
-        vr._window_curve(0, 9)
-    assert vr._wnlf == [a, b]
+        vr._window_curve(None, 9)
+    assert vr.run.window_nlf == [a, b]
 
 
 def test_parser_takes_flat_level_or_a_file():

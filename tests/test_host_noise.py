@@ -137,12 +137,17 @@ def test_restorer_sigma_forms():
 
 
 def test_per_window_list_running_short_names_the_window():
-    vr = restore.VideoRestorer.__new__(restore.VideoRestorer)
-    vr.sigma_mode, vr.sigma_list, vr.sigma, vr._wsig, vr._wfsig = "list", [10.0, 12.5], None, [], []
-    assert vr._window_sigma(0, 9) == 10.0 and vr._window_sigma(1, 9) == 12.5
+    mode, sigma = restore.sigma_form([10.0, 12.5])
+    assert mode == "list" and isinstance(sigma, restore.PerWindow) and sigma.at(0) == 10.0 and sigma.at(1) == 12.5
+    with pytest.raises(ValueError, match="sigma lists 2 windows, window 2 has no entry"):
+        sigma.at(2)
+    assert restore.sigma_form(10)[1].at(0) == restore.sigma_form(10)[1].at(99) == 10.0            # one value for the stream never runs out
+    vr = restore.VideoRestorer.__new__(restore.VideoRestorer)                                     # the restorer's record of what every window used
+    vr.sigma_mode, vr.sigma, vr.run = mode, sigma, restore._Run()
+    assert vr._window_sigma(None, 9) == 10.0 and vr._window_sigma(None, 9) == 12.5
     with pytest.raises(ValueError, match="window 2"):
-        vr._window_sigma(0, 9)
-    assert vr._wsig == [10.0, 12.5]
+        vr._window_sigma(None, 9)
+    assert vr.run.window_sigma == [10.0, 12.5]
 
 
 def test_sigma_list_format_round_trip_and_refusals():

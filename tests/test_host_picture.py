@@ -180,3 +180,24 @@ def test_the_command_line_words():
     assert restore.picture_arg("bars.txt") == "bars.txt" and restore.picture_arg("1:2:3") == "1:2:3"
     a = restore.make_parser().parse_args(["--variant", "deblur", "--checkpoint", "synthetic", "in.y4m", "out.y4m"])
     assert a.picture == "full" and a.bar_level == 1.0 and a.picture_out is None
+
+
+def test_per_window_list_of_pictures_running_short_names_the_window():
+    from shiftnet_amd import restore
+    rects = [(0, 12, 128, 72), None]
+    mode, listed = restore.picture_form(rects)
+    assert mode == "list" and listed == rects
+    assert restore.picture_form((0, 12, 128, 72)) == ("fixed", (0, 12, 128, 72)) and restore.picture_form([rects[0]] * 4)[0] == "list"
+    pics = restore.PerWindow("picture", picture.check_pictures(listed, F420, 96, 128), True)
+    assert pics.at(0) == rects[0] and pics.at(1) is None
+    with pytest.raises(ValueError, match="picture lists 2 windows, window 2 has no entry"):
+        pics.at(2)
+    one = restore.PerWindow("picture", [rects[0]], True)
+    with pytest.raises(ValueError, match="picture lists 1 window, window 1 has no entry"):
+        one.at(1)
+    vr = restore.VideoRestorer.__new__(restore.VideoRestorer)                                   # the stager's count of the windows it has taken on
+    vr.picture_mode, vr._pics, vr.run = mode, pics, restore._Run()
+    assert vr._window_picture() == rects[0] and vr._window_picture() is None
+    with pytest.raises(ValueError, match="window 2"):
+        vr._window_picture()
+    assert vr.run.staged == 2 and vr.run.window_picture == []
