@@ -553,6 +553,34 @@ typedef struct sn_yuv_dither { int mode; uint32_t seed; int t0; } sn_yuv_dither;
 int sn_egress_yuv_dither(const void* out, int out_dtype, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */,
                          const sn_yuv_dither* dither, uint8_t* dst, int T, int H, int W, int Hp, int Wp, void* stream);
 
+/* ---- restoration amount and the view of what was removed (a new symbol and one new struct, SN_ABI_VERSION stays 20) ----------------------------
+ * sn_egress_yuv_mix is sn_egress_yuv_dither (dither == NULL is legal here and means no dither; rect == NULL: the whole frame) that also reads the code
+ * every sample had on the way in.  in: T payloads of the same fmt, H and W as dst; the sample of `in` that belongs to a sample of dst sits at the same
+ * byte offset -- with a rectangle it is the STREAM's sample, not the crop's.  Everything up to the value
+ *   v = off + scale * value                  (off, scale) = (yo, ys) for Y, (co, cs) for C
+ * is sn_egress_yuv_dither's, unchanged: the clamp of R, G, B, Y', Cb, Cr, the 4:2:0 filters, their clamping to the crop with rect, every float32
+ * operation rounded separately (no FMA).  Then, with e = float(code_in), a = mix->ay for Y and mix->ac for Cb and Cr, d the dither of that sample as
+ * sn_egress_yuv_dither defines it (0 without one), lo..hi the plane's legal codes, every float32 product, sum and difference rounded separately:
+ *   SN_MIX_AMOUNT   a == 0.0f:  code = code_in, whatever the dither is
+ *                   otherwise:  m = e + a * (v - e);  code = clamp(rint(m + d), min(lo, code_in), max(hi, code_in))
+ *                   The result never leaves the legal range unless the input sample already had; amount 0 is the identity on illegal codes too.
+ *                   Amount 1 is e + (v - e) in float32, which may differ from v in the last bit: callers who want sn_egress_yuv's bytes call it.
+ *   SN_MIX_REMOVED  m = co + a * (e - v);  code = clamp(rint(m + d), lo, hi)      co = 128 s for all three planes: input minus result around mid-grey,
+ *                   a the gain
+ * The blend is linear in the code domain: not perceptual, and at 4:2:0 not a blend of the R'G'B' pictures.  (tests/mix_ref.py restates it in numpy; the
+ * kernel equals it bit for bit.)  The per-thread layout is sn_egress_yuv's: 8 x 2 pixels; `in` is read with one 8 / 16 B load (chroma at 4:2:0:
+ * 4 / 8 B) where dst is stored wide and the address of `in` allows it, element-wise elsewhere; both paths use the same arithmetic.  Only the samples
+ * sn_egress_yuv_dither writes are written.  The entry points without _mix launch the instantiations they launched before.
+ * SN_EINVAL before anything is launched: everything sn_egress_yuv_dither refuses except a null dither; a null mix or in; a mode that is neither of the
+ * two; ay or ac that is not finite, or outside [0, 1] in SN_MIX_AMOUNT; in at an odd address at 10 bit; byte ranges [in, in + T frame_bytes) and
+ * [dst, dst + T frame_bytes) that overlap. */
+#define SN_MIX_AMOUNT  0
+#define SN_MIX_REMOVED 1
+typedef struct sn_yuv_mix { int mode; float ay, ac; } sn_yuv_mix;   /* AMOUNT: the amounts of Y and of Cb/Cr; REMOVED: the gains */
+int sn_egress_yuv_mix(const void* out, int out_dtype, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */,
+                      const sn_yuv_dither* dither /* NULL: none */, const sn_yuv_mix* mix, const uint8_t* in, uint8_t* dst,
+                      int T, int H, int W, int Hp, int Wp, void* stream);
+
 /* ---- a noise-level function for the denoisers (new symbols, SN_ABI_VERSION stays 20) -----------------------------------------------------------
  * The curve: the sigma of the noise as a function of the luma code, SN_NLF_BANDS = 16 knots; knot b sits at luma code lo + (b + 0.5) (hi - lo) / 16
  * (shiftnet_amd/noise.py estimates it on the host from the histograms of the first entry point; the second turns it into the network's noise plane).

@@ -6,6 +6,9 @@
 //   sn_egress_yuv : [T][3][Hp][Wp] RGB (float32 or module dtype) -> T payloads of H x W (the crop of the padding);
 //   sn_egress_yuv_dither : the same with triangular noise of +-1 code added before the rounding (SN_DITHER_TPDF), an integer hash of the
 //                   sample's position: instantiations of their own of the same kernel, the entry points without _dither launch the others;
+//   sn_egress_yuv_mix : the same, dithered or not, blended in the code domain with the code every sample had on the way in (SN_MIX_AMOUNT: "70 % of the
+//                   correction", separately for luma and chroma; amount 0 is the input byte for byte) or the difference input minus result around
+//                   mid-grey (SN_MIX_REMOVED): a further template parameter of the same kernel, which then reads the T input payloads beside dst;
 //   sn_yuv_thumb  : T payloads -> [T][ceil(H/8)][ceil(W/8)] uint16 sums of the luma codes of every 8 x 8 block (the scene-cut measure of
 //                   shiftnet_amd/scenes.py is computed from these on the host); integer arithmetic, the chroma planes are not read.
 //   sn_yuv_noise_hist : T payloads -> [T][2 (2^bits - 1) + 1] uint32 histograms of |a - b - c + d| over the 2 x 2 luma blocks whose four codes lie
@@ -285,9 +288,39 @@ template <int DITHER> __device__ __forceinline__ int quantd(float off, float sca
     return imin(imax(__float2int_rn(addr(addr(off, mulr(scale, v)), dither_tpdf(rk, x))), lo), hi);
 }
 
-template <int ESZ, int CH, int DITHER = SN_DITHER_NONE>
+// The mix of a launch (sn_egress_yuv_mix): the code the same sample had on the way in is read beside the value on the way out.  MIX is a template
+// parameter of the kernel as DITHER is: SN_MIX_OFF carries nothing, reads nothing and every line below that touches `in` is dead in it, so the
+// instantiations of the entry points without _mix are the ones they launched before there was a mix.
+constexpr int SN_MIX_OFF = -1;
+template <int MIX> struct MixK { const uint8_t* in; float ay, ac; };       // in: T payloads laid out as dst; AMOUNT: the amounts, REMOVED: the gains
+template <> struct MixK<SN_MIX_OFF> {};
+template <int MIX> __device__ __forceinline__ const uint8_t* mix_in(const MixK<MIX>& M) { return M.in; }
+template <> __device__ __forceinline__ const uint8_t* mix_in<SN_MIX_OFF>(const MixK<SN_MIX_OFF>&) { return nullptr; }
+template <int MIX> __device__ __forceinline__ float mix_a(const MixK<MIX>& M, bool chroma) { return chroma ? M.ac : M.ay; }
+template <> __device__ __forceinline__ float mix_a<SN_MIX_OFF>(const MixK<SN_MIX_OFF>&, bool) { return 0.f; }
+// v = off + scale * value as quantd forms it, e = float(code_in), d the sample's dither (0 without one):
+//   AMOUNT : a == 0: code_in;  otherwise clamp(rint((e + a * (v - e)) + d), min(lo, code_in), max(hi, code_in))
+//   REMOVED: clamp(rint((co + a * (e - v)) + d), lo, hi)
+template <int DITHER, int MIX>
+__device__ __forceinline__ int quantm(float off, float scale, float v, int lo, int hi, uint32_t rk, int x, int cin, float a, float co) {
+    if (MIX == SN_MIX_OFF) return quantd<DITHER>(off, scale, v, lo, hi, rk, x);
+    const float val = addr(off, mulr(scale, v)), e = (float)cin;
+    float m = MIX == SN_MIX_AMOUNT ? addr(e, mulr(a, subr(val, e))) : addr(co, mulr(a, subr(e, val)));
+    if (DITHER != SN_DITHER_NONE) m = addr(m, dither_tpdf(rk, x));
+    if (MIX == SN_MIX_AMOUNT) { lo = imin(lo, cin); hi = imax(hi, cin); }
+    const int c = imin(imax(__float2int_rn(m), lo), hi);
+    return MIX == SN_MIX_AMOUNT && a == 0.f ? cin : c;
+}
+// the N codes of `in` beside a store of N samples at element i: the wide load where all N exist, the first n element-wise otherwise (the others are not stored)
+template <int ESZ, int N, int MIX> __device__ __forceinline__ void mix_ld(const uint8_t* p, size_t i, bool all, int n, int* e) {
+    if (MIX != SN_MIX_OFF && all) { ldn<ESZ, N>(p, i, e); return; }
+#pragma unroll
+    for (int k = 0; k < N; ++k) e[k] = MIX != SN_MIX_OFF && k < n ? ld1<ESZ>(p, i + k) : 0;
+}
+
+template <int ESZ, int CH, int DITHER = SN_DITHER_NONE, int MIX = SN_MIX_OFF>
 __global__ __launch_bounds__(256) void egress_yuv_kernel(const void* __restrict__ out, int dt, uint8_t* __restrict__ dstp, const YuvK K,
-                                                       const YuvGeo G, int Hp, int Wp, int src_vec, const DitherK<DITHER> D) {
+                                                       const YuvGeo G, int Hp, int Wp, int src_vec, const DitherK<DITHER> D, const MixK<MIX> M) {
     const int t = blockIdx.z;
     const int x0 = (blockIdx.x * 32 + threadIdx.x) * 8, y0 = (blockIdx.y * 8 + threadIdx.y) * 2;
     const int H = G.h, W = G.w, py = G.py, pc = G.pc;
@@ -297,6 +330,12 @@ __global__ __launch_bounds__(256) void egress_yuv_kernel(const void* __restrict_
     uint8_t* yp = base + G.oy;
     uint8_t* up = base + G.ou;
     uint8_t* vp = base + G.ov;
+    // the payloads that came in: the sample that belongs to a sample of dst sits at the same byte offset
+    const uint8_t* ibase = MIX == SN_MIX_OFF ? nullptr : mix_in<MIX>(M) + (size_t)t * G.frame_bytes;
+    const uint8_t* iyp = ibase + (MIX == SN_MIX_OFF ? 0 : G.oy);
+    const uint8_t* iup = ibase + (MIX == SN_MIX_OFF ? 0 : G.ou);
+    const uint8_t* ivp = ibase + (MIX == SN_MIX_OFF ? 0 : G.ov);
+    const float ay = mix_a<MIX>(M, false), ac = mix_a<MIX>(M, true);
     const bool inner = x0 + 8 <= W;
     // Y', Cb, Cr of pixels x0 - 1 .. x0 + 7 (index 0 .. 8) of rows y0, y0 + 1, coordinates clamped to the H x W frame
     float yv[2][9], cb[2][9], cr[2][9];
@@ -325,17 +364,21 @@ __global__ __launch_bounds__(256) void egress_yuv_kernel(const void* __restrict_
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         if (y0 + r >= H) break;
-        int q[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) q[k] = quantd<DITHER>(K.yo, K.ys, yv[r][1 + k], K.ylo, K.yhi, dither_row_key(fk, 0, y0 + r), x0 + k);
+        int q[8], e[8];
         const size_t o = (size_t)(y0 + r) * py + x0, oc = (size_t)(y0 + r) * pc + x0;
+        mix_ld<ESZ, 8, MIX>(iyp, o, inner, n, e);
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            q[k] = quantm<DITHER, MIX>(K.yo, K.ys, yv[r][1 + k], K.ylo, K.yhi, dither_row_key(fk, 0, y0 + r), x0 + k, e[k], ay, K.co);
         if (inner) stn<ESZ, 8>(yp, o, q); else for (int k = 0; k < n; ++k) st1<ESZ>(yp, o + k, q[k]);
         if (CH == SN_YUV_444) {
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) {
+                mix_ld<ESZ, 8, MIX>(pl ? ivp : iup, oc, inner, n, e);
 #pragma unroll
                 for (int k = 0; k < 8; ++k)
-                    q[k] = quantd<DITHER>(K.co, K.cs, pl ? cr[r][1 + k] : cb[r][1 + k], K.clo, K.chi, dither_row_key(fk, 1 + pl, y0 + r), x0 + k);
+                    q[k] = quantm<DITHER, MIX>(K.co, K.cs, pl ? cr[r][1 + k] : cb[r][1 + k], K.clo, K.chi, dither_row_key(fk, 1 + pl, y0 + r), x0 + k, e[k],
+                                               ac, K.co);
                 if (inner) stn<ESZ, 8>(pl ? vp : up, oc, q); else for (int k = 0; k < n; ++k) st1<ESZ>(pl ? vp : up, oc + k, q[k]);
             }
         }
@@ -345,7 +388,8 @@ __global__ __launch_bounds__(256) void egress_yuv_kernel(const void* __restrict_
         const size_t o = (size_t)(y0 >> 1) * pc + c0;
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
-            int q[4];
+            int q[4], e[4];
+            if constexpr (MIX != SN_MIX_OFF) mix_ld<ESZ, 4, MIX>(pl ? ivp : iup, o, nc == 4, nc, e);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const float* a = pl ? cr[0] : cb[0];
@@ -356,7 +400,9 @@ __global__ __launch_bounds__(256) void egress_yuv_kernel(const void* __restrict_
                 else                               // (1,2,1)/4 along x centred on the even pixel, (1,1)/2 along y: (((l + 2c) + r)_a + ((l + 2c) + r)_b) / 8
                     m = mulr(0.125f, addr(addr(addr(a[2 * i], mulr(2.f, a[1 + 2 * i])), a[2 + 2 * i]),
                                                     addr(addr(b[2 * i], mulr(2.f, b[1 + 2 * i])), b[2 + 2 * i])));
-                q[i] = quantd<DITHER>(K.co, K.cs, m, K.clo, K.chi, dither_row_key(fk, 1 + pl, y0 >> 1), c0 + i);
+                // (constexpr: with the call below alone the dithered 4:2:0 instantiations without a mix come out with one s_mov scheduled elsewhere)
+                if constexpr (MIX == SN_MIX_OFF) q[i] = quantd<DITHER>(K.co, K.cs, m, K.clo, K.chi, dither_row_key(fk, 1 + pl, y0 >> 1), c0 + i);
+                else q[i] = quantm<DITHER, MIX>(K.co, K.cs, m, K.clo, K.chi, dither_row_key(fk, 1 + pl, y0 >> 1), c0 + i, e[i], ac, K.co);
             }
             if (nc == 4) stn<ESZ, 4>(pl ? vp : up, o, q); else for (int i = 0; i < nc; ++i) st1<ESZ>(pl ? vp : up, o + i, q[i]);
         }
@@ -732,6 +778,10 @@ extern "C" {
     } while (0)
 #define SN_YUV_DISPATCH(KERNEL, ...) SN_YUV_DISPATCH_T(KERNEL, , __VA_ARGS__)
 #define SN_YUV_TAIL_TPDF , SN_DITHER_TPDF
+#define SN_YUV_TAIL_AMOUNT , SN_DITHER_NONE, SN_MIX_AMOUNT
+#define SN_YUV_TAIL_AMOUNT_TPDF , SN_DITHER_TPDF, SN_MIX_AMOUNT
+#define SN_YUV_TAIL_REMOVED , SN_DITHER_NONE, SN_MIX_REMOVED
+#define SN_YUV_TAIL_REMOVED_TPDF , SN_DITHER_TPDF, SN_MIX_REMOVED
 
 static int ingest_yuv(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, void* dst, int dst_dtype, int T, int H, int W, int Hp, int Wp,
                       void* stream) {
@@ -759,41 +809,70 @@ int sn_ingest_yuv_rect(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_r
     return ingest_yuv(src, fmt, rect, dst, dst_dtype, T, H, W, Hp, Wp, stream);
 }
 
-static int egress_yuv(const void* out, int out_dtype, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const sn_yuv_dither* dither, uint8_t* dst, int T, int H,
-                      int W, int Hp, int Wp, void* stream) {
+// mix == nullptr: the entry points without _mix, `in` is not looked at
+static int egress_yuv(const void* out, int out_dtype, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const sn_yuv_dither* dither, const sn_yuv_mix* mix,
+                      const uint8_t* in, uint8_t* dst, int T, int H, int W, int Hp, int Wp, void* stream) {
     sn_clear_error();
     YuvK K;
     YuvGeo G;
     if (!out || !dst || !make_consts(fmt, &K) || out_dtype < 0 || out_dtype > 2 || T < 1 || T > 65535 || H < 1 || W < 1) return SN_EINVAL;
     if (!make_geo(fmt, H, W, rect, &G) || Hp < G.h || Wp < G.w) return SN_EINVAL;
     if (fmt->bits == 10 && ((uintptr_t)dst & 1)) return SN_EINVAL;
+    if (mix) {
+        if (!in || (fmt->bits == 10 && ((uintptr_t)in & 1))) return SN_EINVAL;
+        const uintptr_t a = (uintptr_t)in, b = (uintptr_t)dst;
+        const size_t bytes = (size_t)T * G.frame_bytes;
+        if (a < b + bytes && b < a + bytes) return SN_EINVAL;             // the kernel reads `in` while other lanes write dst
+    }
     const int src_vec = Wp % 8 == 0 && ((uintptr_t)out & 15) == 0;
     const dim3 block(32, 8), grid(((G.w + 7) / 8 + 31) / 32, ((G.h + 1) / 2 + 7) / 8, T);
     if (grid.y > 65535) return SN_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    if (dither && dither->mode == SN_DITHER_TPDF) {
-        const DitherK<SN_DITHER_TPDF> D{dither->seed, (uint32_t)dither->t0};
-        SN_YUV_DISPATCH_T(egress_yuv_kernel, SN_YUV_TAIL_TPDF, out, out_dtype, dst, K, G, Hp, Wp, src_vec, D);
+    const bool tpdf = dither && dither->mode == SN_DITHER_TPDF;
+    const DitherK<SN_DITHER_TPDF> D{tpdf ? dither->seed : 0u, tpdf ? (uint32_t)dither->t0 : 0u};
+    const DitherK<SN_DITHER_NONE> D0{};
+    if (mix && mix->mode == SN_MIX_AMOUNT) {
+        const MixK<SN_MIX_AMOUNT> M{in, mix->ay, mix->ac};
+        if (tpdf) SN_YUV_DISPATCH_T(egress_yuv_kernel, SN_YUV_TAIL_AMOUNT_TPDF, out, out_dtype, dst, K, G, Hp, Wp, src_vec, D, M);
+        else SN_YUV_DISPATCH_T(egress_yuv_kernel, SN_YUV_TAIL_AMOUNT, out, out_dtype, dst, K, G, Hp, Wp, src_vec, D0, M);
+    } else if (mix) {
+        const MixK<SN_MIX_REMOVED> M{in, mix->ay, mix->ac};
+        if (tpdf) SN_YUV_DISPATCH_T(egress_yuv_kernel, SN_YUV_TAIL_REMOVED_TPDF, out, out_dtype, dst, K, G, Hp, Wp, src_vec, D, M);
+        else SN_YUV_DISPATCH_T(egress_yuv_kernel, SN_YUV_TAIL_REMOVED, out, out_dtype, dst, K, G, Hp, Wp, src_vec, D0, M);
+    } else if (tpdf) {
+        SN_YUV_DISPATCH_T(egress_yuv_kernel, SN_YUV_TAIL_TPDF, out, out_dtype, dst, K, G, Hp, Wp, src_vec, D, MixK<SN_MIX_OFF>{});
     } else {
-        SN_YUV_DISPATCH(egress_yuv_kernel, out, out_dtype, dst, K, G, Hp, Wp, src_vec, DitherK<SN_DITHER_NONE>{});
+        SN_YUV_DISPATCH(egress_yuv_kernel, out, out_dtype, dst, K, G, Hp, Wp, src_vec, D0, MixK<SN_MIX_OFF>{});
     }
     return sn_check_launch();
 }
 
 int sn_egress_yuv(const void* out, int out_dtype, const sn_yuv_fmt* fmt, uint8_t* dst, int T, int H, int W, int Hp, int Wp, void* stream) {
-    return egress_yuv(out, out_dtype, fmt, nullptr, nullptr, dst, T, H, W, Hp, Wp, stream);
+    return egress_yuv(out, out_dtype, fmt, nullptr, nullptr, nullptr, nullptr, dst, T, H, W, Hp, Wp, stream);
 }
 
 int sn_egress_yuv_rect(const void* out, int out_dtype, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint8_t* dst, int T, int H, int W, int Hp, int Wp,
                        void* stream) {
     if (!rect) { sn_clear_error(); return SN_EINVAL; }
-    return egress_yuv(out, out_dtype, fmt, rect, nullptr, dst, T, H, W, Hp, Wp, stream);
+    return egress_yuv(out, out_dtype, fmt, rect, nullptr, nullptr, nullptr, dst, T, H, W, Hp, Wp, stream);
+}
+
+static bool bad_dither(const sn_yuv_dither* dither) {
+    return (dither->mode != SN_DITHER_NONE && dither->mode != SN_DITHER_TPDF) || dither->t0 < 0;
 }
 
 int sn_egress_yuv_dither(const void* out, int out_dtype, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const sn_yuv_dither* dither, uint8_t* dst, int T,
                          int H, int W, int Hp, int Wp, void* stream) {
-    if (!dither || (dither->mode != SN_DITHER_NONE && dither->mode != SN_DITHER_TPDF) || dither->t0 < 0) { sn_clear_error(); return SN_EINVAL; }
-    return egress_yuv(out, out_dtype, fmt, rect, dither, dst, T, H, W, Hp, Wp, stream);
+    if (!dither || bad_dither(dither)) { sn_clear_error(); return SN_EINVAL; }
+    return egress_yuv(out, out_dtype, fmt, rect, dither, nullptr, nullptr, dst, T, H, W, Hp, Wp, stream);
+}
+
+int sn_egress_yuv_mix(const void* out, int out_dtype, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const sn_yuv_dither* dither, const sn_yuv_mix* mix,
+                      const uint8_t* in, uint8_t* dst, int T, int H, int W, int Hp, int Wp, void* stream) {
+    const auto finite = [](float v) { return v - v == 0.f; };             // false for NaN and for the infinities
+    if ((dither && bad_dither(dither)) || !mix || !in || (mix->mode != SN_MIX_AMOUNT && mix->mode != SN_MIX_REMOVED) || !finite(mix->ay) || !finite(mix->ac) ||
+        (mix->mode == SN_MIX_AMOUNT && (mix->ay < 0.f || mix->ay > 1.f || mix->ac < 0.f || mix->ac > 1.f))) { sn_clear_error(); return SN_EINVAL; }
+    return egress_yuv(out, out_dtype, fmt, rect, dither, mix, in, dst, T, H, W, Hp, Wp, stream);
 }
 
 int sn_yuv_thumb(const uint8_t* src, const sn_yuv_fmt* fmt, uint16_t* dst, int T, int H, int W, void* stream) {

@@ -13,7 +13,8 @@
 ``rowcol_sums_yuv``: the same payloads -> uint32 sums of the luma codes of every row and of every column, for the letterbox rule
                (shiftnet_amd/picture.py); ``ingest_yuv`` / ``egress_yuv`` / ``noise_hist_yuv`` take ``rect=(x0, y0, w, h)`` to work on that
                picture of the stream alone, as on the cropped stream; ``egress_yuv`` takes ``dither=(seed, t0)`` to add triangular noise of
-               +-1 code before the rounding (``sn_egress_yuv_dither``);
+               +-1 code before the rounding (``sn_egress_yuv_dither``), and ``mix=`` with ``ref=`` to blend the result with the payloads that came
+               in, or to show their difference (``sn_egress_yuv_mix``);
 ``egress_u8``  == the per-frame ``clamp(0,1) * 255`` -> skimage PSNR(data_range=255) against the uint8 ground truth
                (:139-143) and the rounded uint8 frame cv2.imwrite would store (:152).
 """
@@ -115,13 +116,35 @@ def ingest_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, Hp: in
     return x
 
 
-def egress_yuv(out: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, dst: Optional[torch.Tensor] = None, rect=None, dither=None) -> torch.Tensor:
+MIXES = {"amount": L.SN_MIX_AMOUNT, "removed": L.SN_MIX_REMOVED}
+
+
+def _mix(mix) -> "L.YuvMix":
+    """("amount", ay, ac) or ("removed", gy, gc) -> sn_yuv_mix; ValueError for anything sn_egress_yuv_mix would refuse."""
+    try:
+        word, y, c = mix
+        y, c = float(y), float(c)
+    except (TypeError, ValueError):
+        raise ValueError(f"mix must be ('amount', ay, ac) or ('removed', gy, gc), got {mix!r}") from None
+    if not isinstance(word, str) or word not in MIXES or not (math.isfinite(y) and math.isfinite(c)):
+        raise ValueError(f"mix must be ('amount', ay, ac) or ('removed', gy, gc) with finite numbers, got {mix!r}")
+    if word == "amount" and not (0.0 <= y <= 1.0 and 0.0 <= c <= 1.0):
+        raise ValueError(f"mix=('amount', ay, ac): the amounts lie in [0, 1], got {mix!r}")
+    return L.YuvMix(MIXES[word], y, c)
+
+
+def egress_yuv(out: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, dst: Optional[torch.Tensor] = None, rect=None, dither=None, mix=None,
+               ref: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out: [T,3,Hp,Wp] network output (float32 or module dtype) on the device -> [T, frame_bytes] uint8 payloads of the H x W crop.
     ``dst``: a [T, frame_bytes] uint8 tensor to fill instead of a new one.
     ``rect=(x0, y0, w, h)``: out holds that picture of the H x W stream (Hp >= h, Wp >= w); only the picture's samples of the payloads, luma and
     chroma, are written, with what the cropped stream's egress writes -- every other byte of ``dst`` stays (a new tensor starts as zeros).
     ``dither=(seed, t0)``: triangular noise of +-1 code is added before the rounding (include/shiftnet_hip.h: sn_egress_yuv_dither), a hash of
-    the seed (0 .. 2^32 - 1), the frame number t0 + t and the sample's plane, row and column; None is today's call and today's bytes."""
+    the seed (0 .. 2^32 - 1), the frame number t0 + t and the sample's plane, row and column; None is today's call and today's bytes.
+    ``mix=("amount", ay, ac)`` with ``ref``, the [T, frame_bytes] payloads that came in (same format and size as the result, another tensor than
+    ``dst``): every code is the input's code moved by that share of the way to the result's, separately for luma and chroma, linear in the code
+    domain; amount 0 is ``ref`` byte for byte.  ``mix=("removed", gy, gc)``: input minus result around mid-grey, times the gain
+    (include/shiftnet_hip.h: sn_egress_yuv_mix).  ``mix=None`` calls exactly what it called before."""
     assert out.is_cuda and out.dim() == 4 and out.shape[1] == 3 and out.dtype in _CODE and out.is_contiguous()
     T, _, Hp, Wp = out.shape
     r = None if rect is None else _rect(rect, fmt, H, W)
@@ -135,9 +158,17 @@ def egress_yuv(out: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, dst: Optional
         if not (0 <= seed < 2 ** 32) or not (0 <= t0 <= 2 ** 31 - 1 - T):
             raise ValueError(f"dither=(seed, t0): need 0 <= seed < 2^32 and 0 <= t0 <= 2^31 - 1 - T, got {dither!r}")
         d = L.YuvDither(L.SN_DITHER_TPDF, seed, t0)
+    if (mix is None) != (ref is None):
+        raise ValueError("mix and ref go together: the mix reads the payloads that came in")
+    m = None if mix is None else _mix(mix)
+    if m is not None:
+        assert tuple(ref.shape) == (T, fb) and ref.dtype == torch.uint8 and ref.is_contiguous() and ref.device == out.device
     with torch.cuda.device(out.device):
         st = torch.cuda.current_stream(out.device).cuda_stream
-        if d is not None:
+        if m is not None:
+            L.check(L.load().sn_egress_yuv_mix(out.data_ptr(), _CODE[out.dtype], fmt, r, d, m, ref.data_ptr(), y.data_ptr(), T, H, W, Hp, Wp, st),
+                    "sn_egress_yuv_mix")
+        elif d is not None:
             L.check(L.load().sn_egress_yuv_dither(out.data_ptr(), _CODE[out.dtype], fmt, r, d, y.data_ptr(), T, H, W, Hp, Wp, st), "sn_egress_yuv_dither")
         elif r is None:
             L.check(L.load().sn_egress_yuv(out.data_ptr(), _CODE[out.dtype], fmt, y.data_ptr(), T, H, W, Hp, Wp, st), "sn_egress_yuv")

@@ -32,6 +32,11 @@ puts back the steps that the noise just removed was hiding.  ``out_format`` writ
 from 8 bit footage keeps the precision); ``dither="tpdf"`` adds triangular noise of +-1 code before the rounding, which makes the mean of the codes
 follow the value at the price of about 0.5 code rms of noise (``sn_egress_yuv_dither``, csrc/sn_yuv.hip).  The noise is a hash of the seed, the
 sample's position and the number of the frame in its clip -- the stream, or the scene -- so the bytes do not depend on how the windows are run.
+
+Amount and the removed view (``amount``, ``view``; both off by default): ``amount`` writes the input's codes moved by that share of the way to the
+result's, separately for luma and chroma -- the fallback when the restoration is too strong; ``view="removed"`` writes input minus result around
+mid-grey, to see whether detail leaves with the noise.  Both happen in the egress, in the code domain, from the payloads the window has uploaded
+anyway (``sn_egress_yuv_mix``): amount 0 is the input byte for byte.  The blend is linear in the codes, not perceptual.
 """
 from __future__ import annotations
 
@@ -42,9 +47,9 @@ from typing import Iterable, Iterator, List, Sequence, Tuple
 
 import numpy as np
 
-from .restore_cli import main, make_parser, picture_arg, sigma_arg  # noqa: F401 -- the command line (restore_cli.py), reached through this module
-from .windows import (DITHERS, FUTURE, PAST, PerWindow, _Frames, _SceneFrames, _Thread, noise_model_form, pad_multiple, padded_size,  # noqa: F401
-                      picture_form, plan_output, plan_scene_windows, plan_windows, reflect_index, scene_cuts_form, sigma_form, window_indices)
+from .restore_cli import amount_arg, main, make_parser, picture_arg, sigma_arg  # noqa: F401 -- the command line (restore_cli.py), reached through this module
+from .windows import (DITHERS, FUTURE, PAST, PerWindow, _Frames, _SceneFrames, _Thread, amount_form, noise_model_form, pad_multiple,  # noqa: F401
+                      padded_size, picture_form, plan_output, plan_scene_windows, plan_windows, reflect_index, scene_cuts_form, sigma_form, window_indices)
 
 VARIANTS = {"deblur": "gshift_deblur1", "deblur_small": "gshift_deblur2", "denoise": "gshift_denoise1", "denoise_small": "gshift_denoise2"}
 
@@ -92,6 +97,7 @@ class _Slot:
         self.t0 = 0                                               # the frame number, in its clip, of the first frame that window restores
         self.used = False                                         # in this restore(): a window has gone through the slot
         self.noise = self.bands = self.sums = None                # _Stat: the window's histograms, band histograms, row and column sums
+        self.dev_ref = None                                       # a mix with another format out: the window's input payloads in the format written
 
 
 class _Run:
@@ -214,17 +220,31 @@ class VideoRestorer:
     from the picture's origin under ``picture`` -- and the number of its frame counted from the first frame of its clip: the stream, or the scene under
     ``scene_cuts``.  So the bytes are the same with ``pipeline`` on and off, those of restoring every scene as a separate video, and inside a picture
     those of restoring the cropped stream.  ``stats["out_format"]`` and ``stats["dither"]`` record the two arguments as used (None: the input's
-    format / no dither), ``stats["dither_seed"]`` the seed."""
+    format / no dither), ``stats["dither_seed"]`` the seed.
+    amount: None -- the network's result is written, today's code path and bytes, and so are 1.0 and (1.0, 1.0); a number in [0, 1] -- every code
+    written is ``code_in + amount * (code_out - code_in)`` rounded (dithered where ``dither`` says so): that share of the correction; ``(luma, chroma)``
+    -- the two kinds of plane separately ("denoise chroma fully, luma at half" is ``(0.5, 1.0)``, "leave chroma alone" ``(1.0, 0.0)``).  The blend is
+    made by the egress in the code domain (``sn_egress_yuv_mix``) against the payloads the window has uploaded anyway: amount 0 returns every input
+    frame byte for byte, illegal codes included, and no float frame is made.  **Linear in the code domain, not perceptual**, and at 4:2:0 not the blend
+    of the two R'G'B' pictures; nobody has judged it on real footage.  With ``out_format`` the input side of the blend is the input converted as the
+    frames outside a picture are (``egress(out format, ingest_float32(in format, frame))``, undithered), kept in one more device buffer per slot.
+    view: None -- the restored frames; ``"removed"`` (with ``amount`` None or 1) -- what the restoration took out: ``mid-grey + removed_gain * (code_in
+    - code_out)`` per sample, clamped to the legal codes, 128 (512 at 10 bit) in all three planes where nothing changed.  ``removed_gain`` (finite, >= 0)
+    makes small differences visible.  With ``picture`` the samples outside the rectangle stay what they are without a view.
+    ``stats["amount"]`` is the pair of amounts used (None: none given) and ``stats["view"]`` the view."""
 
     def __init__(self, net, one_len: int, sigma=None, pipeline: bool = True, scene_cuts=None,
                  cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0),
-                 picture=None, bar_level: float = 1.0, out_format=None, dither=None, dither_seed: int = 0, noise_model=None) -> None:
+                 picture=None, bar_level: float = 1.0, out_format=None, dither=None, dither_seed: int = 0, noise_model=None,
+                 amount=None, view=None, removed_gain: float = 1.0) -> None:
         import torch
         from .lib import YuvFmt
         from .noise import check_clamp
         self.torch = torch
         _, self.dither, self.dither_seed = plan_output(YuvFmt(8, 0, 0, 0), out_format, dither, dither_seed)      # the argument errors, before anything else
         self.out_format = out_format
+        # the mix of the last egress (None: the code path without any of it), the amounts and the view as stats reports them
+        self.mix, self.amount, self.view = amount_form(amount, view, removed_gain)
         self.net, self.one_len, self.pipeline = net, int(one_len), bool(pipeline)
         if self.one_len < 1:
             raise ValueError("one_len must be >= 1")
@@ -283,7 +303,11 @@ class VideoRestorer:
         dev = self.dev
         self.slots = [_Slot(torch, dev, self.dtype, tin, tout, self.fb, self.ofb, self.hp * self.wp) for _ in range(2)]
         # a picture in another format than was read: the window's whole frames as float32 on their way from one format to the other (main stream only)
-        self.conv32 = torch.empty(tout * 3 * h * w, dtype=torch.float32, device=dev) if self.convert and self.picture_mode != "full" else None
+        # ... and a mix in another format than was read: the same conversion gives the input side of the mix, one buffer of payloads per slot
+        ref = self.convert and self.mix is not None
+        self.conv32 = torch.empty(tout * 3 * h * w, dtype=torch.float32, device=dev) if self.convert and (self.picture_mode != "full" or ref) else None
+        for s in self.slots:
+            s.dev_ref = torch.empty((tout, self.ofb), dtype=torch.uint8, device=dev) if ref else None
         self.s_in, self.s_out = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
         if self.sigma_mode == "auto" or self.nlf_mode is not None:
             from .noise import clip_codes
@@ -419,16 +443,23 @@ class VideoRestorer:
                 out = self.net.forward_fp32_out(x, **kw)
             e1.record(main)
             run.timers.append((e0, e1))
-            if rect is not None and not self.convert:
-                # everything outside the picture leaves as it came in: the window's own n frames (not the reflected ones around them) first
-                slot.dev_out[:n].copy_(slot.dev_in[PAST:PAST + n], non_blocking=True)
-            elif rect is not None:
-                # ... in the format written: the whole frames converted by the two edges, float32 between them, rounded to nearest
+            own = slot.dev_in[PAST:PAST + n]                     # the window's own n frames (not the reflected ones around them), still on the device
+            outside = rect is not None                           # the samples outside the picture have to be put into dev_out first
+            if self.convert and (outside or self.mix is not None):
+                # ... in the format written: the whole frames converted by the two edges, float32 between them, rounded to nearest.  Straight into
+                # dev_out without a mix; with one into the slot's reference buffer, because the mix reads one while it writes the other
                 full = self.conv32[:n * 3 * self.h * self.w].view(1, n, 3, self.h, self.w)
-                ingest_yuv(slot.dev_in[PAST:PAST + n], self.fmt, self.h, self.w, self.h, self.w, torch.float32, out=full)
-                egress_yuv(full[0], self.ofmt, self.h, self.w, dst=slot.dev_out[:n])
+                ingest_yuv(own, self.fmt, self.h, self.w, self.h, self.w, torch.float32, out=full)
+                own = egress_yuv(full[0], self.ofmt, self.h, self.w, dst=(slot.dev_out if self.mix is None else slot.dev_ref)[:n])
+                outside = outside and self.mix is not None
+            if outside:
+                # everything outside the picture leaves as it came in (as converted, in another format): the egress below writes the inside only
+                slot.dev_out[:n].copy_(own, non_blocking=True)
             dither = None if self.dither is None else (self.dither_seed, slot.t0)
-            egress_yuv(out, self.ofmt, self.h, self.w, dst=slot.dev_out[:n], rect=rect, dither=dither)
+            if self.mix is None:
+                egress_yuv(out, self.ofmt, self.h, self.w, dst=slot.dev_out[:n], rect=rect, dither=dither)
+            else:
+                egress_yuv(out, self.ofmt, self.h, self.w, dst=slot.dev_out[:n], rect=rect, dither=dither, mix=self.mix, ref=own)
             slot.ev_done.record(main)
         with torch.cuda.stream(self.s_out):
             self.s_out.wait_event(slot.ev_done)
@@ -488,6 +519,7 @@ class VideoRestorer:
         for slot in self.slots:
             slot.used = False
         self.stats["out_format"], self.stats["dither"], self.stats["dither_seed"] = (self.out_format if self.convert else None), self.dither, self.dither_seed
+        self.stats["amount"], self.stats["view"] = self.amount, self.view
         main = torch.cuda.current_stream(self.dev)
 
         def checked(it):

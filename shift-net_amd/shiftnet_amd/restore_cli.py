@@ -28,6 +28,18 @@ def picture_arg(word: str):
     return word
 
 
+def amount_arg(word: str):
+    """--amount: A -> the float; AY,AC -> the pair (luma, chroma)."""
+    parts = word.split(",")
+    if len(parts) not in (1, 2):
+        raise argparse.ArgumentTypeError(f"A or AY,AC, got {word!r}")
+    try:
+        vals = tuple(float(p) for p in parts)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"A or AY,AC with numbers in [0, 1], got {word!r}") from None
+    return vals[0] if len(vals) == 1 else vals
+
+
 def _modes():
     from .y4m import MODES
     return MODES
@@ -73,6 +85,14 @@ def make_parser() -> argparse.ArgumentParser:
                     help="tpdf: add triangular noise of +-1 code before rounding to the output's codes: no banding, about 0.5 code rms of noise instead; "
                          "default none: round to nearest")
     ap.add_argument("--dither_seed", type=int, default=0, metavar="N", help="tpdf: which noise (0 .. 2^32 - 1); the same seed gives the same bytes")
+    ap.add_argument("--amount", type=amount_arg, default=None, metavar="{A,AY,AC}",
+                    help="how much of the restoration to apply, 0 .. 1: every code written is the input's moved by that share of the way to the result's "
+                         "(linear in the code domain, not perceptual; 0 writes the input byte for byte); AY,AC sets luma and chroma separately, e.g. 0.5,1 "
+                         "denoises chroma fully and luma at half; default: the full result")
+    ap.add_argument("--view", choices=["restored", "removed"], default="restored",
+                    help="removed: write what the restoration took out instead of the result, input minus result around mid-grey (see --removed_gain); "
+                         "not together with an --amount other than 1; default restored")
+    ap.add_argument("--removed_gain", type=float, default=1.0, metavar="G", help="removed: the difference is multiplied by G (finite, >= 0) to make it visible")
     ap.add_argument("--cuts_out", default=None, metavar="FILE", help="write the scene starts that were used, in the format --scene_cuts FILE reads")
     ap.add_argument("input", metavar="IN", help="Y4M file, or - for stdin")
     ap.add_argument("output", metavar="OUT", help="Y4M file, or - for stdout")
@@ -114,11 +134,17 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     from . import noise, picture as pic, scenes
     from .io_edges import yuv_fmt
     from .restore import VideoRestorer, load_net
+    from .windows import amount_form
     from .y4m import Y4MReader, Y4MWriter, output_header
     ap = make_parser()
     a = ap.parse_args(argv)
     if not (0 <= a.dither_seed < 2 ** 32):
         ap.error("--dither_seed: an integer in 0 .. 2^32 - 1")
+    view = None if a.view == "restored" else a.view
+    try:
+        amount_form(a.amount, view, a.removed_gain)
+    except ValueError as e:
+        ap.error(f"--amount / --view / --removed_gain: {e}")
     if "denoise" in a.variant and a.sigma is None:
         ap.error("--sigma is required by the denoise variants")
     log = lambda s: (sys.stderr.write(s + "\n"), sys.stderr.flush())      # noqa: E731
@@ -166,10 +192,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         net = load_net(a.variant, a.checkpoint, a.dtype)
         vr = VideoRestorer(net, a.one_len, sigma=sigma, pipeline=not a.no_pipeline, scene_cuts=cuts, cut_threshold=a.cut_threshold,
                            cut_ratio=a.cut_ratio, sigma_clamp=a.sigma_clamp, picture=picture, bar_level=a.bar_level, out_format=a.out_format,
-                           dither=None if a.dither == "none" else a.dither, dither_seed=a.dither_seed, noise_model=noise_model)
+                           dither=None if a.dither == "none" else a.dither, dither_seed=a.dither_seed, noise_model=noise_model,
+                           amount=a.amount, view=view, removed_gain=a.removed_gain)
         if a.out_format is not None or a.dither != "none":
             log(f"output: C{a.out_format or hd.chroma}{'' if a.out_format else ' (as the input)'}, dither {a.dither}"
                 f"{' seed %d' % a.dither_seed if a.dither != 'none' else ''}")
+        if vr.mix is not None:
+            log("amount: luma %g, chroma %g of the correction (linear in the code domain)" % vr.amount if view is None else
+                f"view: removed (input minus result around mid-grey, gain {a.removed_gain:g})")
         wr = Y4MWriter(fout, output_header(hd, a.out_format))
         t0 = time.perf_counter()
         n = 0

@@ -139,6 +139,39 @@ def noise_model_form(noise_model):
     return "list", PerWindow("noise_model", check_curves(noise_model), True)
 
 
+VIEWS = ("removed",)
+
+
+def amount_form(amount, view=None, removed_gain=1.0):
+    """-> (the mix ``egress_yuv`` takes or None, the amounts (ay, ac) or None, the view or None).  ``amount``: None, a number (both planes) or
+    (luma, chroma), each in [0, 1]; ``view``: None or "removed", which shows input minus result around mid-grey times ``removed_gain`` (finite,
+    >= 0) and goes with no amount other than None or 1.  None, 1 or (1, 1) without a view is no mix: the code path without any of this."""
+    import math
+    if amount is None:
+        pair = None
+    else:
+        try:
+            pair = () if isinstance(amount, str) else (tuple(float(v) for v in amount) if hasattr(amount, "__iter__") else (float(amount),) * 2)
+        except (TypeError, ValueError):
+            pair = ()
+        if len(pair) != 2 or not all(0.0 <= v <= 1.0 for v in pair):                # refuses NaN as well
+            raise ValueError(f"amount must be None, a number in [0, 1] or (luma, chroma) with both in [0, 1], got {amount!r}")
+    if view is not None and not (isinstance(view, str) and view in VIEWS):
+        raise ValueError(f"view must be None or 'removed', got {view!r}")
+    full = pair is None or pair == (1.0, 1.0)
+    if view is None:
+        return (None if full else ("amount",) + pair), pair, None
+    if not full:
+        raise ValueError(f"view='removed' shows what the full restoration took out: it goes with amount None or 1, got {amount!r}")
+    try:
+        gain = math.nan if isinstance(removed_gain, (bool, str)) else float(removed_gain)
+    except (TypeError, ValueError):
+        gain = math.nan
+    if not (math.isfinite(gain) and gain >= 0.0):
+        raise ValueError(f"removed_gain must be a finite number >= 0, got {removed_gain!r}")
+    return ("removed", gain, gain), pair, view
+
+
 def picture_form(picture):
     """None -> ("full", None); "auto" -> ("auto", None); four numbers -> ("fixed", the tuple); anything whose elements are sequences or None ->
     ("list", the list).  The rectangles are judged where the stream is known (picture.check_pictures)."""

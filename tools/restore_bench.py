@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15, 3.16 and 3.17 (run on the MI355X from the repository root).
+"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15, 3.16, 3.17 and 3.19 (run on the MI355X from the repository root).
 
   kernels : time per pixel of sn_ingest_yuv / sn_egress_yuv / sn_yuv_thumb / sn_yuv_noise_hist (4:2:0 8 bit, 720p x 20 frames; the noise
             histogram on the same frames with noise of sigma 10 as well) beside sn_ingest_u8 / sn_egress_u8 on the same
             frames, interleaved in one process: REPS repetitions, each timing INNER back-to-back launches of every kernel with device events;
             median and min..max over the repetitions.  Since 3.16 also the dithered egress (sn_egress_yuv_dither) from float32 at 8 bit 4:2:0,
             10 bit 4:2:0 and 10 bit 4:4:4 beside the undithered egress of the same formats, and with --parent_lib SO the undithered sn_egress_yuv
-            of another build on the same tensors.
+            of another build on the same tensors.  Since 3.19 also the mixed egress (sn_egress_yuv_mix, amount (0.5, 0.5)) from float32 at 8 bit
+            4:2:0 and 10 bit 4:4:4, dithered and not, and the removed view at 8 bit 4:2:0, beside the plain egress of the same formats.
   pipeline: steady-state wall time per 720p window of the pipelined restorer (Shift-Net-s, one_len 16, bf16, Y4M held in memory) beside the
             forward-only time of the same windows (device events in the same runs) and beside pipeline=False, the two alternating.
             --scene_cuts auto: the same stream with the cut detector running (sn_yuv_thumb; 3.13).  --cut_every N: every second scene of N frames
@@ -67,6 +68,8 @@ def kernels(a):
     fmt10, fmt444 = yuv_fmt(10, L.SN_YUV_420_LEFT, L.SN_YUV_BT709, L.SN_YUV_LIMITED), yuv_fmt(10, L.SN_YUV_444, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
     dst10 = torch.empty((T, fmt10.frame_bytes(H, W)), dtype=torch.uint8, device="cuda")
     dst444 = torch.empty((T, fmt444.frame_bytes(H, W)), dtype=torch.uint8, device="cuda")
+    pay444 = egress_yuv(rgb, fmt444, H, W)                                           # the input side of the mix at 10 bit 4:4:4
+    half, removed = ("amount", 0.5, 0.5), ("removed", 1.0, 1.0)
     parent = {}
     if a.parent_lib:                                                                 # another build's undithered egress, interleaved with this one's
         import ctypes as C
@@ -92,8 +95,15 @@ def kernels(a):
         "egress_yuv_420p10_fp32_tpdf": lambda: egress_yuv(out_32, fmt10, H, W, dst=dst10, dither=(1, 0)),
         "egress_yuv_444p10_fp32": lambda: egress_yuv(out_32, fmt444, H, W, dst=dst444),
         "egress_yuv_444p10_fp32_tpdf": lambda: egress_yuv(out_32, fmt444, H, W, dst=dst444, dither=(1, 0)),
+        "egress_yuv_mix_fp32": lambda: egress_yuv(out_32, fmt, H, W, dst=dst, mix=half, ref=pay),
+        "egress_yuv_mix_fp32_tpdf": lambda: egress_yuv(out_32, fmt, H, W, dst=dst, dither=(1, 0), mix=half, ref=pay),
+        "egress_yuv_removed_fp32": lambda: egress_yuv(out_32, fmt, H, W, dst=dst, mix=removed, ref=pay),
+        "egress_yuv_mix_444p10_fp32": lambda: egress_yuv(out_32, fmt444, H, W, dst=dst444, mix=half, ref=pay444),
+        "egress_yuv_mix_444p10_fp32_tpdf": lambda: egress_yuv(out_32, fmt444, H, W, dst=dst444, dither=(1, 0), mix=half, ref=pay444),
         **parent,
     }
+    if a.only_cases:
+        cases = {k: f for k, f in cases.items() if any(w in k for w in a.only_cases.split(","))}
     for f in cases.values():
         for _ in range(3):
             f()
@@ -441,6 +451,7 @@ if __name__ == "__main__":
     ap.add_argument("--cut_every", type=int, default=0, help="pipeline part: a cut every N frames in the stream (0: none)")
     ap.add_argument("--parent_lib", default=None, metavar="SO", help="kernels part and picture part in kernels mode: a shared library built from another commit's "
                     "csrc/sn_yuv.hip alone; its sn_ingest_yuv / sn_egress_yuv are timed beside this build's")
+    ap.add_argument("--only_cases", default=None, metavar="WORDS", help="kernels part: time only the cases whose name contains one of these comma-separated words")
     ap.add_argument("--mode", choices=["forward", "kernels"], default="forward", help="picture and nlf parts: which measurement")
     ap.add_argument("--picture", choices=["auto", "fixed"], default="auto", help="picture part, forward mode: VideoRestorer(picture='auto') or the rectangle itself")
     a = ap.parse_args()
