@@ -427,7 +427,7 @@ int sn_egress_u8(const void* out, int out_dtype, const uint8_t* gt, uint8_t* img
 int sn_ssim_blocks(void);
 int sn_ssim_u8(const void* out, int out_dtype, const uint8_t* gt, float* scratch, float* partial, int T, int H, int W, void* stream);
 
-/* ---- Y'CbCr edges of the video restorer (csrc/sn_yuv.hip) ----------------------------------------------------------------
+/* ---- Y'CbCr edges of the video restorer (csrc/sn_yuv.hip, csrc/sn_yuv_stats.hip) -----------------------------------------
  * Added without an ABI bump: SN_ABI_VERSION stays 20, because these are new symbols and a new struct; no existing struct,
  * signature or operand encoding changes, so a caller built against the earlier header keeps working.
  *

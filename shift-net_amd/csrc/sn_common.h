@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include "../../include/shiftnet_hip.h"      // SN_F32 / SN_F16 / SN_BF16 of ld_any / st_any
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
@@ -43,6 +44,17 @@ __device__ __forceinline__ uint32_t pack_h2(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, h);
 }
 __device__ __forceinline__ bf16_t f_to_bf(float f) { return (bf16_t)(pack_bf2(f, 0.f) & 0xffffu); }
+
+// element i of a tensor of dtype dt (SN_F32 / SN_F16 / SN_BF16) as float32, and back with the dtype's rounding to nearest even: the image
+// edges (sn_io.hip, sn_yuv.hip, sn_yuv_stats.hip) take and give tensors of any of the three
+__device__ __forceinline__ float ld_any(const void* p, int dt, size_t i) {
+    return dt == SN_F32 ? ((const float*)p)[i] : (dt == SN_F16 ? __half2float(((const __half*)p)[i]) : bf_to_f(((const bf16_t*)p)[i]));
+}
+__device__ __forceinline__ void st_any(void* p, int dt, size_t i, float v) {
+    if (dt == SN_F32) ((float*)p)[i] = v;
+    else if (dt == SN_F16) ((__half*)p)[i] = __float2half(v);
+    else ((bf16_t*)p)[i] = f_to_bf(v);
+}
 
 __device__ __forceinline__ void unpack8(const uint4 q, float* v) {
     v[0] = bf_lo(q.x); v[1] = bf_hi(q.x); v[2] = bf_lo(q.y); v[3] = bf_hi(q.y);

@@ -16,15 +16,6 @@
 
 namespace {
 
-__device__ __forceinline__ float ld_any(const void* p, int dt, size_t i) {
-    return dt == SN_F32 ? ((const float*)p)[i] : (dt == SN_F16 ? __half2float(((const __half*)p)[i]) : bf_to_f(((const bf16_t*)p)[i]));
-}
-__device__ __forceinline__ void st_any(void* p, int dt, size_t i, float v) {
-    if (dt == SN_F32) ((float*)p)[i] = v;
-    else if (dt == SN_F16) ((__half*)p)[i] = __float2half(v);
-    else ((bf16_t*)p)[i] = f_to_bf(v);
-}
-
 __global__ __launch_bounds__(256) void ingest_u8_kernel(const uint8_t* __restrict__ src, void* dst, int dt, int HW) {
     const int t = blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;

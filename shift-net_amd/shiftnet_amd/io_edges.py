@@ -3,18 +3,18 @@
 ``ingest_u8``  == ``numpy2tensor(frames).to(device).to(dtype)`` of inference/test_deblur.py:191-200,128,134, bit for bit,
                with 3 instead of 12 bytes per pixel crossing PCIe;
 ``ingest_yuv`` / ``egress_yuv``: planar Y'CbCr payloads as a Y4M stream carries them (csrc/sn_yuv.hip) <-> RGB tensors, for the video
-               restorer (shiftnet_amd/restore.py); 1.5 bytes per pixel cross PCIe for 8-bit 4:2:0;
-``thumb_yuv``  : the same payloads -> uint16 sums of the luma codes of every 8 x 8 block, for the scene-cut detector (shiftnet_amd/scenes.py);
-``noise_hist_yuv``: the same payloads -> uint32 histograms of |a - b - c + d| over the 2 x 2 luma blocks, for the blind noise estimate
-               (shiftnet_amd/noise.py);
-``noise_hist_bands_yuv`` / ``noise_map_level``: the same payloads -> that statistic split into 16 bands of brightness, from which noise.py estimates a
-               noise-level function (sigma against the luma code), and payloads + the 16 knots of one -> the denoisers' noise plane
-               (``sn_yuv_noise_hist_bands``, ``sn_noise_map_level``); both take ``rect``;
-``rowcol_sums_yuv``: the same payloads -> uint32 sums of the luma codes of every row and of every column, for the letterbox rule
-               (shiftnet_amd/picture.py); ``ingest_yuv`` / ``egress_yuv`` / ``noise_hist_yuv`` take ``rect=(x0, y0, w, h)`` to work on that
-               picture of the stream alone, as on the cropped stream; ``egress_yuv`` takes ``dither=(seed, t0)`` to add triangular noise of
-               +-1 code before the rounding (``sn_egress_yuv_dither``), and ``mix=`` with ``ref=`` to blend the result with the payloads that came
-               in, or to show their difference (``sn_egress_yuv_mix``);
+               restorer (shiftnet_amd/restore.py); 1.5 bytes per pixel cross PCIe for 8-bit 4:2:0.  ``egress_yuv`` takes ``dither=(seed, t0)`` to add
+               triangular noise of +-1 code before the rounding, and ``mix=`` with ``ref=`` to blend the result with the payloads that came in, or to
+               show their difference;
+the statistics of the same payloads' luma (csrc/sn_yuv_stats.hip), each for one decision the restorer makes on the host:
+``thumb_yuv``  : uint16 sums of the luma codes of every 8 x 8 block, for the scene-cut detector (shiftnet_amd/scenes.py);
+``noise_hist_yuv``: uint32 histograms of |a - b - c + d| over the 2 x 2 luma blocks, for the blind noise estimate (shiftnet_amd/noise.py);
+``noise_hist_bands_yuv``: that statistic split into 16 bands of brightness, from which noise.py estimates a noise-level function (sigma against the
+               luma code);
+``noise_map_level``: payloads + the 16 knots of such a function -> the denoisers' noise plane;
+``rowcol_sums_yuv``: uint32 sums of the luma codes of every row and of every column, for the letterbox rule (shiftnet_amd/picture.py);
+``rect=(x0, y0, w, h)``, where a function takes it (all but ``thumb_yuv`` and ``rowcol_sums_yuv``), restricts it to that picture of the stream, with
+               the result of the cropped stream;
 ``egress_u8``  == the per-frame ``clamp(0,1) * 255`` -> skimage PSNR(data_range=255) against the uint8 ground truth
                (:139-143) and the rounded uint8 frame cv2.imwrite would store (:152).
 """
@@ -94,17 +94,29 @@ def _rect(rect, fmt: "L.YuvFmt", H: int, W: int) -> "L.YuvRect":
     return L.YuvRect(*check_rect(rect, fmt, H, W, smallest=1))      # the kernels take any rectangle; the restorer has a limit of its own
 
 
+def _payload(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int) -> Tuple[int, torch.device]:
+    """The check every function below makes of its payloads, [T, frame_bytes] uint8 on a HIP device -> (T, the device)."""
+    fb = fmt.frame_bytes(H, W)
+    assert payload_u8.dtype == torch.uint8 and payload_u8.is_cuda and payload_u8.dim() == 2 and payload_u8.shape[1] == fb and payload_u8.is_contiguous()
+    return payload_u8.shape[0], payload_u8.device
+
+
+def _clip(fmt: "L.YuvFmt", lo: Optional[int], hi: Optional[int]) -> Tuple[int, int]:
+    """``lo``, ``hi`` of the noise statistics; None is the format's black / white code (noise.clip_codes)."""
+    from .noise import clip_codes
+    dlo, dhi = clip_codes(fmt.bits, fmt.range)
+    return dlo if lo is None else int(lo), dhi if hi is None else int(hi)
+
+
 def ingest_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, Hp: int, Wp: int, dtype: torch.dtype,
                out: Optional[torch.Tensor] = None, rect=None) -> torch.Tensor:
     """payload_u8: [T, frame_bytes] uint8 on a HIP device, T planar Y'CbCr frames of H x W -> [1,T,3,Hp,Wp] RGB of ``dtype`` in [0,1];
     pixels outside H x W replicate the edge pixel.  ``out``: a [1,T,3,Hp,Wp] tensor to fill instead of a new one.
     ``rect=(x0, y0, w, h)``: the picture of the stream to ingest, bit for bit as the cropped stream would be: Hp >= h, Wp >= w, the chroma
     neighbours clamp to the picture's chroma planes and the padding repeats its last row and column."""
-    fb = fmt.frame_bytes(H, W)
-    assert payload_u8.dtype == torch.uint8 and payload_u8.is_cuda and payload_u8.dim() == 2 and payload_u8.shape[1] == fb and payload_u8.is_contiguous()
+    T, _ = _payload(payload_u8, fmt, H, W)
     r = None if rect is None else _rect(rect, fmt, H, W)
     assert Hp >= (H if r is None else r.h) and Wp >= (W if r is None else r.w) and dtype in _CODE
-    T = payload_u8.shape[0]
     x = out if out is not None else torch.empty((1, T, 3, Hp, Wp), dtype=dtype, device=payload_u8.device)
     assert tuple(x.shape) == (1, T, 3, Hp, Wp) and x.dtype == dtype and x.is_contiguous() and x.device == payload_u8.device
     with torch.cuda.device(payload_u8.device):
@@ -180,9 +192,7 @@ def egress_yuv(out: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, dst: Optional
 def thumb_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """payload_u8: [T, frame_bytes] uint8 on a HIP device (only the luma plane of each payload is read) -> uint16 [T, ceil(H/8), ceil(W/8)]:
     the integer sum of the luma codes of every 8 x 8 block, partial at the right and bottom edge.  ``out``: a tensor of that shape to fill."""
-    fb = fmt.frame_bytes(H, W)
-    assert payload_u8.dtype == torch.uint8 and payload_u8.is_cuda and payload_u8.dim() == 2 and payload_u8.shape[1] == fb and payload_u8.is_contiguous()
-    T, hb, wb = payload_u8.shape[0], (H + 7) // 8, (W + 7) // 8
+    T, hb, wb = _payload(payload_u8, fmt, H, W)[0], (H + 7) // 8, (W + 7) // 8
     y = out if out is not None else torch.empty((T, hb, wb), dtype=torch.uint16, device=payload_u8.device)
     assert tuple(y.shape) == (T, hb, wb) and y.dtype == torch.uint16 and y.is_contiguous() and y.device == payload_u8.device
     with torch.cuda.device(payload_u8.device):
@@ -197,12 +207,9 @@ def noise_hist_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lo
     per frame the counts of v = |a - b - c + d| over the non-overlapping 2 x 2 luma blocks whose four codes lie strictly between ``lo`` and
     ``hi`` (default: the format's black and white codes, noise.clip_codes).  ``out``: a tensor of that shape to overwrite.
     ``rect=(x0, y0, w, h)``: the blocks of that picture of the stream alone, the block grid anchored at (x0, y0): the cropped stream's histograms."""
-    from .noise import clip_codes, nbins
-    fb = fmt.frame_bytes(H, W)
-    assert payload_u8.dtype == torch.uint8 and payload_u8.is_cuda and payload_u8.dim() == 2 and payload_u8.shape[1] == fb and payload_u8.is_contiguous()
-    T, nb = payload_u8.shape[0], nbins(fmt.bits)
-    dlo, dhi = clip_codes(fmt.bits, fmt.range)
-    lo, hi = dlo if lo is None else int(lo), dhi if hi is None else int(hi)
+    from .noise import nbins
+    T, nb = _payload(payload_u8, fmt, H, W)[0], nbins(fmt.bits)
+    lo, hi = _clip(fmt, lo, hi)
     y = out if out is not None else torch.empty((T, nb), dtype=torch.uint32, device=payload_u8.device)
     assert tuple(y.shape) == (T, nb) and y.dtype == torch.uint32 and y.is_contiguous() and y.device == payload_u8.device
     r = None if rect is None else _rect(rect, fmt, H, W)
@@ -220,12 +227,9 @@ def noise_hist_bands_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: i
     """payload_u8: [T, frame_bytes] uint8 on a HIP device (only the luma plane of each payload is read) -> uint32 [T, 16, NBV], NBV = 128 / 512:
     ``noise_hist_yuv``'s counts split by the block's brightness, band = (16 (S - 4 lo)) / (4 (hi - lo)) for the block's sum S, and v saturated to
     NBV - 1 (the last bin means "at least NBV - 1").  ``lo``, ``hi``, ``out``, ``rect`` as there."""
-    from .noise import NLF_BANDS, clip_codes, nlf_bins
-    fb = fmt.frame_bytes(H, W)
-    assert payload_u8.dtype == torch.uint8 and payload_u8.is_cuda and payload_u8.dim() == 2 and payload_u8.shape[1] == fb and payload_u8.is_contiguous()
-    T, nbv = payload_u8.shape[0], nlf_bins(fmt.bits)
-    dlo, dhi = clip_codes(fmt.bits, fmt.range)
-    lo, hi = dlo if lo is None else int(lo), dhi if hi is None else int(hi)
+    from .noise import NLF_BANDS, nlf_bins
+    T, nbv = _payload(payload_u8, fmt, H, W)[0], nlf_bins(fmt.bits)
+    lo, hi = _clip(fmt, lo, hi)
     y = out if out is not None else torch.empty((T, NLF_BANDS, nbv), dtype=torch.uint32, device=payload_u8.device)
     assert tuple(y.shape) == (T, NLF_BANDS, nbv) and y.dtype == torch.uint32 and y.is_contiguous() and y.device == payload_u8.device
     r = None if rect is None else _rect(rect, fmt, H, W)
@@ -244,17 +248,14 @@ def noise_map_level(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, H
     pixels outside H x W replicate the edge pixel.  ``rect=(x0, y0, w, h)``: the plane of that picture of the stream (Hp >= h, Wp >= w), bit for bit the
     cropped stream's.  ``out``: a [1, T, 1, Hp, Wp] tensor to fill.  The knots travel as a kernel argument: no upload, nothing to wait for."""
     import ctypes as C
-    from .noise import NLF_BANDS, clip_codes
-    fb = fmt.frame_bytes(H, W)
-    assert payload_u8.dtype == torch.uint8 and payload_u8.is_cuda and payload_u8.dim() == 2 and payload_u8.shape[1] == fb and payload_u8.is_contiguous()
+    from .noise import NLF_BANDS
+    T, _ = _payload(payload_u8, fmt, H, W)
     r = None if rect is None else _rect(rect, fmt, H, W)
     assert Hp >= (H if r is None else r.h) and Wp >= (W if r is None else r.w) and dtype in _CODE
     kn = [float(k) for k in knots]
     if len(kn) != NLF_BANDS or not all(math.isfinite(k) for k in kn):
         raise ValueError(f"knots: need {NLF_BANDS} finite numbers, got {knots!r}")
-    dlo, dhi = clip_codes(fmt.bits, fmt.range)
-    lo, hi = dlo if lo is None else int(lo), dhi if hi is None else int(hi)
-    T = payload_u8.shape[0]
+    lo, hi = _clip(fmt, lo, hi)
     y = out if out is not None else torch.empty((1, T, 1, Hp, Wp), dtype=dtype, device=payload_u8.device)
     assert tuple(y.shape) == (1, T, 1, Hp, Wp) and y.dtype == dtype and y.is_contiguous() and y.device == payload_u8.device
     with torch.cuda.device(payload_u8.device):
@@ -267,9 +268,7 @@ def rowcol_sums_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, o
                     out_cols: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """payload_u8: [T, frame_bytes] uint8 on a HIP device (only the luma plane of each payload is read) -> (uint32 [T, H], uint32 [T, W]): the exact
     sums of the luma codes of every row and of every column of every frame.  ``out_rows`` / ``out_cols``: tensors of those shapes to overwrite."""
-    fb = fmt.frame_bytes(H, W)
-    assert payload_u8.dtype == torch.uint8 and payload_u8.is_cuda and payload_u8.dim() == 2 and payload_u8.shape[1] == fb and payload_u8.is_contiguous()
-    T, dev = payload_u8.shape[0], payload_u8.device
+    T, dev = _payload(payload_u8, fmt, H, W)
     rows = out_rows if out_rows is not None else torch.empty((T, H), dtype=torch.uint32, device=dev)
     cols = out_cols if out_cols is not None else torch.empty((T, W), dtype=torch.uint32, device=dev)
     for a, n in ((rows, H), (cols, W)):

@@ -115,7 +115,7 @@ class UnitSrc(C.Structure):
                 ("clip", C.c_int)]
 
 
-# sn_yuv_fmt (csrc/sn_yuv.hip)
+# sn_yuv_fmt (csrc/sn_yuv.hip, csrc/sn_yuv_stats.hip)
 SN_YUV_444, SN_YUV_420_CENTER, SN_YUV_420_LEFT = 0, 1, 2
 SN_YUV_BT601, SN_YUV_BT709 = 0, 1
 SN_YUV_LIMITED, SN_YUV_FULL = 0, 1

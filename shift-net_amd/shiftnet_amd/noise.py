@@ -1,6 +1,6 @@
 """Blind estimate of the noise level of footage, for the denoise variants of the video restorer (numpy only, no torch).
 
-The histograms are what ``sn_yuv_noise_hist`` (csrc/sn_yuv.hip) writes: per frame, over the luma plane, the counts of
+The histograms are what ``sn_yuv_noise_hist`` (csrc/sn_yuv_stats.hip) writes: per frame, over the luma plane, the counts of
 ``v = |a - b - c + d|`` of every non-overlapping 2 x 2 block whose four codes lie strictly between the format's black and white codes
 (clipped pixels carry less noise than the footage has).  ``v`` is twice the Haar HH coefficient of the block: a smooth image contributes
 nothing to it, and white noise of standard deviation s on the codes gives it the variance ``4 s^2 + 1/3`` (the 1/3 is the rounding of four

@@ -5,7 +5,7 @@ whole video -- inside it the bytes are those of restoring the cropped stream -- 
 ``x0`` and ``y0`` are even, ``w`` is even unless the rectangle reaches the frame's right edge and ``h`` unless it reaches the bottom edge, so that
 no chroma sample is shared between the inside and the outside.
 
-``decide_picture`` is the rule of ``picture="auto"``.  It looks at the sums ``sn_yuv_rowcol_sums`` (csrc/sn_yuv.hip) writes: per frame the exact
+``decide_picture`` is the rule of ``picture="auto"``.  It looks at the sums ``sn_yuv_rowcol_sums`` (csrc/sn_yuv_stats.hip) writes: per frame the exact
 integer sum of the luma codes of every row and of every column.  With ``black`` the format's black luma code (16 s limited, 0 full) and
 ``s = 2^(bits - 8)``:
 

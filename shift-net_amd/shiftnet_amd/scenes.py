@@ -1,6 +1,6 @@
 """Scene cuts of a video from luma thumbnails: the rule the video restorer uses to treat every scene as a clip of its own.
 
-The thumbnails ``S_t`` are what ``sn_yuv_thumb`` (csrc/sn_yuv.hip) writes: the integer sum of the luma codes of every 8 x 8 block of frame t,
+The thumbnails ``S_t`` are what ``sn_yuv_thumb`` (csrc/sn_yuv_stats.hip) writes: the integer sum of the luma codes of every 8 x 8 block of frame t,
 ``uint16 [ceil(H/8), ceil(W/8)]``.  From them, on the host and in exact integers:
 
   ``m[t]   = sum |S_t - S_(t-1)| / (H W 2^(bits-8))`` for t >= 1: the mean absolute difference of the 8 x 8 block means of two consecutive frames

@@ -1,4 +1,4 @@
-"""-m gpu: the active picture.  The three ``_rect`` entry points of csrc/sn_yuv.hip against the restatements of tests/yuv_ref.py and
+"""-m gpu: the active picture.  The three ``_rect`` entry points of csrc/sn_yuv.hip and csrc/sn_yuv_stats.hip against the restatements of tests/yuv_ref.py and
 tests/noise_ref.py on the CROPPED stream (tests/picture_ref.py), bit for bit; ``sn_yuv_rowcol_sums`` against numpy exactly; and the video
 restorer with ``picture=`` against itself on the cropped stream, byte for byte inside the rectangle, and against its input outside."""
 import os

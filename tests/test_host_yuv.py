@@ -242,6 +242,8 @@ def test_library_exports_the_yuv_entry_points_and_keeps_the_abi_version():
     spec = importlib.util.spec_from_file_location("sn_build", os.path.join(ROOT, "shift-net_amd", "build.py"))
     mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod)
     assert "sn_yuv.hip" in mod.SOURCES
+    csrc = os.path.join(ROOT, "shift-net_amd", "csrc")           # a unit left out of the build would only show as a missing symbol on the GPU
+    assert len(mod.SOURCES) == len(set(mod.SOURCES)) and set(mod.SOURCES) == {f for f in os.listdir(csrc) if f.endswith(".hip")}
     mod.build()                                              # hipcc cross-compiles gfx950 without a GPU
     from shiftnet_amd import lib as L
     lib = L.load()
