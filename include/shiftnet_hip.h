@@ -207,6 +207,31 @@ int sn_gsts_shiftconv(const sn_unit_src* s, const int8_t* offs, const uint32_t* 
  * word).  Every displacement in offs must be a multiple of 4 pixels (spec.shift_table: they are).  Same products, another accumulation order:
  * within rounding of sn_gsts_shiftconv, not bit-identical to it. */
 int sn_gsts_shiftconv_mfma(const sn_unit_src* s, const int8_t* offs, const uint32_t* w1, void* hw, void* stream);
+/* The kernel has two forms with bit-identical results: SN_K0_TILE, one 34 x 34 window per 16 x 16 tile (persistent workgroups walk an XCD's tile
+ * list), and SN_K0_WALK, a workgroup takes a segment of S vertically adjacent tiles and keeps the window as a ring of 34 rows (16 new rows per
+ * tile after a segment's first).  sn_gsts_shiftconv_mfma_plan tells which one a launch of s takes on a device with ncu compute units (host only,
+ * nothing is launched, no device access; the launch calls the same function with the device's own count): plan[SN_K0_PLAN_LEN] =
+ *   {form, S, nseg, wgs, per_x, per_tile, ntx, nty, nt, grid}
+ * form: SN_K0_TILE / SN_K0_WALK; S, nseg: segment length in tiles and segments per tile column (tile form: the candidate that was too short to
+ * walk); wgs: workgroups per XCD (grid = 8 wgs); per_x: rows of the item list per XCD -- (frame, segment) rows for the walking form, (frame, tile
+ * row) rows for the tile form, XCD k owns rows [k per_x, (k + 1) per_x) and a workgroup takes every wgs-th (row, tile column) item of them;
+ * per_tile: the tile form with one workgroup per tile; ntx, nty: tiles per row / column; nt: frames.  SN_EINVAL: what the launch refuses, ncu < 8.
+ * sn_gsts_shiftconv_mfma_opt: the same launch with the form named (tests and measurements; results do not depend on it).  form 0: the plan's;
+ * seg: segment length 1..8 of SN_K0_WALK (clipped to nty), 0: the plan's; wgs: workgroups per XCD, clipped to the XCD's items, 0: the plan's.
+ * Anything else -- a seg without form SN_K0_WALK included -- is SN_EINVAL and launches nothing.  opt == NULL: sn_gsts_shiftconv_mfma.
+ * sn_gsts_shiftconv_mfma_plan_opt: the plan of that launch (opt == NULL: sn_gsts_shiftconv_mfma_plan).
+ * (Three new symbols and one new struct, no existing struct or signature changes: SN_ABI_VERSION stays 20.) */
+#define SN_K0_TILE 1
+#define SN_K0_WALK 2
+#define SN_K0_PLAN_LEN 10
+typedef struct sn_k0_opts {
+    int form;
+    int seg;
+    int wgs;
+} sn_k0_opts;
+int sn_gsts_shiftconv_mfma_plan(const sn_unit_src* s, int ncu, int* plan);
+int sn_gsts_shiftconv_mfma_plan_opt(const sn_unit_src* s, int ncu, const sn_k0_opts* opt, int* plan);
+int sn_gsts_shiftconv_mfma_opt(const sn_unit_src* s, const int8_t* offs, const uint32_t* w1, void* hw, const sn_k0_opts* opt, void* stream);
 
 /* g1 = SimpleGate(RepConv2(body[0](norm(cat(shortcut, hw))))): LayerNorm2d over 3C/2 (CAB2) or C (CAB1) channels (eps 1e-6,
  * affine folded into the 1x1 weights), the 1x1 conv to 2C on MFMA, depthwise 3x3 + identity and the gate, with the 2C-channel

@@ -617,6 +617,59 @@ int sn_gsts_shiftconv(const sn_unit_src* s, const int8_t* offs, const uint32_t* 
 }  // extern "C"
 
 namespace {
+// The form and the grid of a K0 launch on the matrix cores: the one copy of the decision, used by the launcher and by sn_gsts_shiftconv_mfma_plan.
+// opt == NULL (or all zeros): the library's choice.
+#ifndef K0M_WALK         // 1: segments of tile columns with the window as a ring of rows (shiftconv_mfma_walk_kernel); 0: one window per tile
+#define K0M_WALK 1
+#endif
+#ifndef K0M_PERSIST      // measurement builds: 0 = one workgroup per tile (the dispatcher hands out an XCD's tiles in order)
+#define K0M_PERSIST 1
+#endif
+struct K0Plan { int form, S, nseg, wgs, per_x, per_tile, ntx, nty, nt; };
+int k0_plan(const sn_unit_src* s, int ncu, const sn_k0_opts* opt, K0Plan& P) {
+    if (!unit_ok(s) || s->mode == 0 || ncu < 8) return SN_EINVAL;
+    SN_FRAME_RANGE(s, t0, nt);
+    (void)t0;
+    const int form = opt ? opt->form : 0, seg = opt ? opt->seg : 0, wgs_o = opt ? opt->wgs : 0;
+    if (form < 0 || form > 2 || seg < 0 || seg > 8 || wgs_o < 0 || (seg && form != SN_K0_WALK)) return SN_EINVAL;
+    const int ntx = (s->w + 15) / 16, nty = (s->h + 15) / 16;
+    const int wgs_cu = s->C == 64 ? 2 : 1;                                   // workgroups per CU (LDS: 78 / 98 KB each)
+    const long slots = (long)wgs_cu * ncu;
+    // segment length: the longest of 8, 6, 4, 3, 2 tiles (a segment's first tile stages 34 rows, the others 16) whose item count keeps the
+    // workgroup slots busy: at least 4 items per slot, or whatever the launch has
+    int S = 2;
+    const int cand[5] = {8, 6, 4, 3, 2};
+    for (int k = 0; k < 5; ++k) {
+        const int Sk = cand[k] < nty ? cand[k] : nty, nsk = (nty + Sk - 1) / Sk;
+        if ((long)nsk * ntx * nt >= 4 * slots || k == 4) { S = Sk; break; }
+    }
+    // short segments mostly pay first tiles: measured 67 vs 62 us at 20 x 180 x 320 (S = 2) -- those launches take the tile form
+    const bool walk = form == SN_K0_WALK || (form == 0 && K0M_WALK && S >= 4);
+    if (seg) S = seg < nty ? seg : nty;
+    if (S < 1) S = 1;
+    P.S = S; P.nseg = (nty + S - 1) / S; P.ntx = ntx; P.nty = nty; P.nt = nt;
+    if (walk) {
+        const int rows = nt * P.nseg, per_x = (rows + 7) / 8;
+        long wg = wgs_o ? wgs_o : slots / 8;
+        if (wg > (long)per_x * ntx) wg = (long)per_x * ntx;
+        if (wg < 1) wg = 1;
+        P.form = SN_K0_WALK; P.wgs = (int)wg; P.per_x = per_x; P.per_tile = 0;
+        return SN_OK;
+    }
+    const int per_xcd = (nty * nt + 7) / 8;
+    long wgs = wgs_o ? wgs_o : slots / 8;                                    // persistent workgroups per XCD
+    const long tiles_x = (long)per_xcd * ntx;
+    // C = 64 on large maps: one workgroup per tile after all -- the dispatcher hands out an XCD's tiles in order, a compact frontier that keeps more
+    // of the windows' overlap in L2 than 64 persistent workgroups drifting apart (read requests to the fabric 301 vs ~570 MB per launch at
+    // 20 x 360 x 640; 284 vs 296 us).  Smaller maps and C = 80 (the per-workgroup tables rebuilt per tile cost more than the locality buys:
+    // 70 vs 62 us at 20 x 180 x 320, 1320 vs 1121 us at C = 80) stay persistent.  Same results either way.
+    const bool per_tile = !wgs_o && (!K0M_PERSIST || (s->C == 64 && tiles_x >= 1500));
+    if (wgs > tiles_x || per_tile) wgs = tiles_x;
+    if (wgs < 1) wgs = 1;
+    P.form = SN_K0_TILE; P.wgs = (int)wgs; P.per_x = per_xcd; P.per_tile = wgs == tiles_x ? 1 : 0;
+    return SN_OK;
+}
+
 int cab_phase2(const sn_unit_src* s, const void* g2, const float* ca, const void* wfrag, const float* bias, void* y, void* stream) {
     sn_clear_error();
     if (!unit_ok(s) || !g2 || !ca || !wfrag || !y || y == s->x) return SN_EINVAL;
@@ -633,75 +686,56 @@ int cab_phase2(const sn_unit_src* s, const void* g2, const float* ca, const void
 
 extern "C" {
 
-// K0 on the matrix cores (shiftconv_mfma_kernel); operands as sn_gsts_shiftconv
-int sn_gsts_shiftconv_mfma(const sn_unit_src* s, const int8_t* offs, const uint32_t* w1, void* hw, void* stream) {
+// K0 on the matrix cores (shiftconv_mfma_kernel / shiftconv_mfma_walk_kernel); operands as sn_gsts_shiftconv.  k0_plan (above) decides the form
+// and the grid, for the launch and for sn_gsts_shiftconv_mfma_plan alike.
+int sn_gsts_shiftconv_mfma_plan_opt(const sn_unit_src* s, int ncu, const sn_k0_opts* opt, int* plan) {
+    K0Plan P;
+    if (!plan) return SN_EINVAL;
+    const int rc = k0_plan(s, ncu, opt, P);
+    if (rc != SN_OK) return rc;
+    plan[0] = P.form; plan[1] = P.S; plan[2] = P.nseg; plan[3] = P.wgs; plan[4] = P.per_x; plan[5] = P.per_tile;
+    plan[6] = P.ntx; plan[7] = P.nty; plan[8] = P.nt; plan[9] = 8 * P.wgs;
+    return SN_OK;
+}
+int sn_gsts_shiftconv_mfma_plan(const sn_unit_src* s, int ncu, int* plan) { return sn_gsts_shiftconv_mfma_plan_opt(s, ncu, nullptr, plan); }
+
+int sn_gsts_shiftconv_mfma_opt(const sn_unit_src* s, const int8_t* offs, const uint32_t* w1, void* hw, const sn_k0_opts* opt, void* stream) {
     sn_clear_error();
-    if (!unit_ok(s) || !offs || !w1 || !hw || s->mode == 0) return SN_EINVAL;
-    SN_FRAME_RANGE(s, t0, nt);
+    if (!offs || !w1 || !hw) return SN_EINVAL;                 // the descriptor and the options: k0_plan's refusals, stated there alone
     int dev = 0, ncu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 8) {
         (void)hipGetLastError();
         return SN_ELAUNCH;
     }
-#ifndef K0M_WALK         // 1: segments of tile columns with the window as a ring of rows (shiftconv_mfma_walk_kernel); 0: one window per tile
-#define K0M_WALK 1
-#endif
-    if (K0M_WALK) {
-        const int ntx = (s->w + 15) / 16, nty = (s->h + 15) / 16, CHw = s->C / 2;
-        const int wgs_cu = s->C == 64 ? 2 : 1;
-        const long slots = (long)wgs_cu * ncu;
-        // segment length: the longest of 8, 6, 4, 3, 2 tiles (a segment's first tile stages 34 rows, the others 16) whose item count keeps the
-        // workgroup slots busy: at least 4 items per slot, or whatever the launch has
-        int S = 2;
-        const int cand[5] = {8, 6, 4, 3, 2};
-        for (int k = 0; k < 5; ++k) {
-            const int Sk = cand[k] < nty ? cand[k] : nty, nsk = (nty + Sk - 1) / Sk;
-            if ((long)nsk * ntx * nt >= 4 * slots || k == 4) { S = Sk; break; }
-        }
-        // short segments mostly pay first tiles: measured 67 vs 62 us at 20 x 180 x 320 (S = 2) -- those launches take the tile form below
-        const bool walk = S >= 4;
-        const int nseg = (nty + (S < 1 ? 1 : S) - 1) / (S < 1 ? 1 : S);
-        const int rows = nt * nseg, per_x = (rows + 7) / 8;
-        long wg = slots / 8;
-        if (wg > (long)per_x * ntx) wg = (long)per_x * ntx;
-        if (wg < 1) wg = 1;
-        const size_t ldsw = (size_t)CHw * 34 * 72 + (CHw / 8) * 32 + 64;
-        const dim3 gridw(8u * (unsigned)wg);
-        if (!walk) {
-        } else if (s->C == 64) {
-            if (hipFuncSetAttribute((const void*)shiftconv_mfma_walk_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw) != hipSuccess) return SN_ELAUNCH;
-            hipLaunchKernelGGL((shiftconv_mfma_walk_kernel<32>), gridw, dim3(256), ldsw, (hipStream_t)stream, to_k(s), ntx, nty, S, nseg, nt, per_x, offs, w1, (bf16_t*)hw);
-        } else {
-            if (hipFuncSetAttribute((const void*)shiftconv_mfma_walk_kernel<40>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw) != hipSuccess) return SN_ELAUNCH;
-            hipLaunchKernelGGL((shiftconv_mfma_walk_kernel<40>), gridw, dim3(320), ldsw, (hipStream_t)stream, to_k(s), ntx, nty, S, nseg, nt, per_x, offs, w1, (bf16_t*)hw);
-        }
-        if (walk) return sn_check_launch();
-    }
-    XcdTiles G = sn_xcd_tiles((s->w + 15) / 16, (s->h + 15) / 16, nt);
-    const int per_xcd = (G.nrf + 7) / 8;
+    K0Plan P;
+    const int rc = k0_plan(s, ncu, opt, P);
+    if (rc != SN_OK) return rc;
     const int CH = s->C / 2;
     const size_t lds = (size_t)CH * 34 * 72 + (CH / 8) * 32 + 64;
-#ifndef K0M_PERSIST      // measurement builds: 0 = one workgroup per tile (the dispatcher hands out an XCD's tiles in order)
-#define K0M_PERSIST 1
-#endif
-    int wgs = (s->C == 64 ? 2 : 1) * ncu / 8;                                // persistent workgroups per XCD (LDS: 78 / 98 KB each)
-    const long tiles_x = (long)per_xcd * G.ntx;
-    // C = 64 on large maps: one workgroup per tile after all -- the dispatcher hands out an XCD's tiles in order, a compact frontier that keeps more
-    // of the windows' overlap in L2 than 64 persistent workgroups drifting apart (read requests to the fabric 301 vs ~570 MB per launch at
-    // 20 x 360 x 640; 284 vs 296 us).  Smaller maps and C = 80 (the per-workgroup tables rebuilt per tile cost more than the locality buys:
-    // 70 vs 62 us at 20 x 180 x 320, 1320 vs 1121 us at C = 80) stay persistent.  Same results either way.
-    const bool per_tile = s->C == 64 && tiles_x >= 1500;
-    if (wgs > tiles_x || !K0M_PERSIST || per_tile) wgs = (int)tiles_x;
-    if (wgs < 1) wgs = 1;
-    const dim3 grid(8u * (unsigned)wgs);
+    const dim3 grid(8u * (unsigned)P.wgs);
+    if (P.form == SN_K0_WALK) {
+        if (s->C == 64) {
+            if (hipFuncSetAttribute((const void*)shiftconv_mfma_walk_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return SN_ELAUNCH;
+            hipLaunchKernelGGL((shiftconv_mfma_walk_kernel<32>), grid, dim3(256), lds, (hipStream_t)stream, to_k(s), P.ntx, P.nty, P.S, P.nseg, P.nt, P.per_x, offs, w1, (bf16_t*)hw);
+        } else {
+            if (hipFuncSetAttribute((const void*)shiftconv_mfma_walk_kernel<40>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return SN_ELAUNCH;
+            hipLaunchKernelGGL((shiftconv_mfma_walk_kernel<40>), grid, dim3(320), lds, (hipStream_t)stream, to_k(s), P.ntx, P.nty, P.S, P.nseg, P.nt, P.per_x, offs, w1, (bf16_t*)hw);
+        }
+        return sn_check_launch();
+    }
+    const XcdTiles G = sn_xcd_tiles(P.ntx, P.nty, P.nt);
     if (s->C == 64) {
         if (hipFuncSetAttribute((const void*)shiftconv_mfma_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return SN_ELAUNCH;
-        hipLaunchKernelGGL((shiftconv_mfma_kernel<32>), grid, dim3(256), lds, (hipStream_t)stream, to_k(s), G, nt, per_xcd, offs, w1, (bf16_t*)hw);
+        hipLaunchKernelGGL((shiftconv_mfma_kernel<32>), grid, dim3(256), lds, (hipStream_t)stream, to_k(s), G, P.nt, P.per_x, offs, w1, (bf16_t*)hw);
     } else {
         if (hipFuncSetAttribute((const void*)shiftconv_mfma_kernel<40>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return SN_ELAUNCH;
-        hipLaunchKernelGGL((shiftconv_mfma_kernel<40>), grid, dim3(320), lds, (hipStream_t)stream, to_k(s), G, nt, per_xcd, offs, w1, (bf16_t*)hw);
+        hipLaunchKernelGGL((shiftconv_mfma_kernel<40>), grid, dim3(320), lds, (hipStream_t)stream, to_k(s), G, P.nt, P.per_x, offs, w1, (bf16_t*)hw);
     }
     return sn_check_launch();
+}
+
+int sn_gsts_shiftconv_mfma(const sn_unit_src* s, const int8_t* offs, const uint32_t* w1, void* hw, void* stream) {
+    return sn_gsts_shiftconv_mfma_opt(s, offs, w1, hw, nullptr, stream);
 }
 
 int sn_gsts_cab2_phase2(const sn_unit_src* s, const void* g2, const float* ca, const void* wfrag, const float* bias, void* y, void* stream) {

@@ -20,7 +20,7 @@ ABI_VERSION = 20    # == SN_ABI_VERSION of include/shiftnet_hip.h; a stale .so f
 SYMBOLS = [          # include/shiftnet_hip.h, production ABI
     "sn_abi_version", "sn_selftest_mfma", "sn_ingest", "sn_conv2d", "sn_conv_pool_blocks", "sn_conv2d_route","sn_upsample2_add", "sn_ca_mlp",
     "sn_cab_ca", "sn_cab_ca_scratch_floats", "sn_cab_fused_supported", "sn_cab_stats", "sn_cab_ca_lines", "sn_cab_fused", "sn_planar_pitch", "sn_nhwc_to_planar", "sn_dw5m_blocks",
-    "sn_dw5m_gemm_gate", "sn_gsts_gather", "sn_temporal_roll", "sn_gsts_shiftconv", "sn_gsts_shiftconv_mfma", "sn_gsts_cab2_phase2", "sn_cab1_phase2",
+    "sn_dw5m_gemm_gate", "sn_gsts_gather", "sn_temporal_roll", "sn_gsts_shiftconv", "sn_gsts_shiftconv_mfma", "sn_gsts_shiftconv_mfma_plan", "sn_gsts_shiftconv_mfma_plan_opt", "sn_gsts_shiftconv_mfma_opt", "sn_gsts_cab2_phase2", "sn_cab1_phase2",
     "sn_ingest_u8", "sn_egress_blocks", "sn_egress_u8", "sn_ssim_blocks", "sn_ssim_u8",
     "sn_ingest_yuv", "sn_egress_yuv", "sn_yuv_thumb", "sn_yuv_noise_hist",
     "sn_ingest_yuv_rect", "sn_egress_yuv_rect", "sn_yuv_noise_hist_rect", "sn_yuv_rowcol_sums", "sn_egress_yuv_dither",
@@ -115,6 +115,26 @@ class UnitSrc(C.Structure):
                 ("clip", C.c_int)]
 
 
+# sn_gsts_shiftconv_mfma_plan / sn_gsts_shiftconv_mfma_opt: the two forms of K0 on the matrix cores
+SN_K0_TILE, SN_K0_WALK = 1, 2
+K0_PLAN_FIELDS = ("form", "S", "nseg", "wgs", "per_x", "per_tile", "ntx", "nty", "nt", "grid")      # the plan argument of sn_gsts_shiftconv_mfma_plan
+
+
+class K0Opts(C.Structure):
+    """sn_k0_opts: form 0 = the plan's, SN_K0_TILE, SN_K0_WALK; seg: segment length 1..8 of the walking form; wgs: workgroups per XCD; 0 = the plan's."""
+    _fields_ = [("form", C.c_int), ("seg", C.c_int), ("wgs", C.c_int)]
+
+
+def k0_plan(lib, src: "UnitSrc", ncu: int, opt: "K0Opts" = None) -> dict:
+    """sn_gsts_shiftconv_mfma_plan (opt: sn_gsts_shiftconv_mfma_plan_opt) as a dict of K0_PLAN_FIELDS; raises on SN_EINVAL."""
+    plan = (C.c_int * len(K0_PLAN_FIELDS))()
+    if opt is None:
+        check(lib.sn_gsts_shiftconv_mfma_plan(C.byref(src), ncu, plan), "sn_gsts_shiftconv_mfma_plan")
+    else:
+        check(lib.sn_gsts_shiftconv_mfma_plan_opt(C.byref(src), ncu, C.byref(opt), plan), "sn_gsts_shiftconv_mfma_plan_opt")
+    return dict(zip(K0_PLAN_FIELDS, plan))
+
+
 # sn_yuv_fmt (csrc/sn_yuv.hip, csrc/sn_yuv_stats.hip)
 SN_YUV_444, SN_YUV_420_CENTER, SN_YUV_420_LEFT = 0, 1, 2
 SN_YUV_BT601, SN_YUV_BT709 = 0, 1
@@ -199,6 +219,9 @@ def load() -> C.CDLL:
     lib.sn_temporal_roll.argtypes = [C.POINTER(UnitSrc), vp, vp]
     lib.sn_gsts_shiftconv.argtypes = [C.POINTER(UnitSrc), vp, vp, vp, vp]
     lib.sn_gsts_shiftconv_mfma.argtypes = [C.POINTER(UnitSrc), vp, vp, vp, vp]
+    lib.sn_gsts_shiftconv_mfma_plan.argtypes = [C.POINTER(UnitSrc), ci, C.POINTER(ci * len(K0_PLAN_FIELDS))]
+    lib.sn_gsts_shiftconv_mfma_plan_opt.argtypes = [C.POINTER(UnitSrc), ci, C.POINTER(K0Opts), C.POINTER(ci * len(K0_PLAN_FIELDS))]
+    lib.sn_gsts_shiftconv_mfma_opt.argtypes = [C.POINTER(UnitSrc), vp, vp, vp, C.POINTER(K0Opts), vp]
     lib.sn_ln_gemm_gate.argtypes = [C.POINTER(UnitSrc), vp, vp, vp, vp, vp, vp, ci, vp]
     lib.sn_lngate_blocks.argtypes = [ci, ci]
     lib.sn_grp5_gemm_gate.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
