@@ -641,6 +641,26 @@ int sn_yuv_noise_hist_bands(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_
 int sn_noise_map_level(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */, const float* knots, int lo, int hi,
                        void* dst, int dst_dtype, int T, int H, int W, int Hp, int Wp, void* stream);
 
+/* ---- the noise statistics of frame pairs (new symbols, SN_ABI_VERSION stays 20) -----------------------------------------------------------------
+ * The temporal noise estimate of the video restorer (shiftnet_amd/noise.py): texture that does not move is the same in the next frame and noise is
+ * not, so the Haar HH coefficient of the DIFFERENCE of two consecutive frames keeps the noise and drops the picture.  src, fmt, rect (NULL: the
+ * whole frame), lo, hi, H, W exactly as sn_yuv_noise_hist_rect / sn_yuv_noise_hist_bands take them: only the luma plane is read, of fmt only bits
+ * decides anything, the 2 x 2 block grid is anchored at the rectangle's origin, a last odd row or column belongs to no block.  T >= 2 payloads are
+ * T - 1 pairs; pair p is payloads p and p + 1.  For block (i, j) with the codes a0 b0 / c0 d0 in payload p and a1 b1 / c1 d1 in payload p + 1:
+ * the block counts iff all EIGHT codes lie strictly between lo and hi, and then
+ *   v = |(a1 - b1 - c1 + d1) - (a0 - b0 - c0 + d0)|          0 <= v <= 4 (2^bits - 1)
+ * sn_yuv_noise_hist_pairs: one is added to dst[p][v]; dst:[T - 1][NBP] uint32, NBP = 4 (2^bits - 1) + 1 (1021 at 8 bit, 4093 at 10 bit).
+ * sn_yuv_noise_hist_pairs_bands: one is added to dst[p][band][min(v, NBV - 1)]; dst:[T - 1][16][NBV] uint32 with the NBV of sn_yuv_noise_hist_bands and
+ *   band = (2 (S - 8 lo)) / (hi - lo)      unsigned integer division, S the sum of the eight codes; 8 <= S - 8 lo <= 8 (hi - lo) - 8, so 0 <= band <= 15
+ * Both: dst is OVERWRITTEN with the counts, never added to; nothing outside those words is written.  Integer sums: exact, and the same for every launch
+ * geometry and schedule.  A picture without a whole block (h < 2 or w < 2) is legal and gives zeros.
+ * SN_EINVAL before anything is launched: everything sn_yuv_noise_hist_bands refuses (an illegal rectangle and lo < -2^24 or hi > 2^24 included, for both
+ * entry points), and T < 2 (T - 1 > 65535 is refused with T > 65535). */
+int sn_yuv_noise_hist_pairs(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */, uint32_t* dst, int lo, int hi,
+                            int T, int H, int W, void* stream);
+int sn_yuv_noise_hist_pairs_bands(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */, uint32_t* dst, int lo, int hi,
+                                  int T, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,8 @@
 //                   sn_yuv_noise_hist_rect: the same kernel on a picture rectangle of the stream (YuvGeo, sn_yuv.h);
 //   sn_yuv_noise_hist_bands : the same statistic split into 16 bands of the block's brightness, v saturated to NBV = 128 / 512 bins: [T][16][NBV]
 //                   uint32 (the noise-level function of shiftnet_amd/noise.py is estimated from these on the host); rect or the whole frame;
+//   sn_yuv_noise_hist_pairs, sn_yuv_noise_hist_pairs_bands : the same two statistics of the DIFFERENCE of consecutive payloads, T - 1 pairs:
+//                   [T - 1][4 (2^bits - 1) + 1] and [T - 1][16][NBV] uint32 (the temporal noise estimate of shiftnet_amd/noise.py); rect or the whole frame;
 //   sn_noise_map_level : T payloads and the 16 knots of a noise-level function -> [T][1][Hp][Wp] of the module dtype or float32: the function at the
 //                   low-passed luma of every pixel (bilinear between the means of the 8 x 8 blocks): the denoisers' noise plane; rect or the whole frame;
 //   sn_yuv_rowcol_sums : T payloads -> [T][H] and [T][W] uint32 sums of the luma codes of every row and every column (the letterbox rule of
@@ -189,6 +191,156 @@ __global__ __launch_bounds__(256) void yuv_noise_hist_bands_kernel(const uint8_t
             const uint32_t* c = low + (band * LOW + v) * COPIES;
             const int rot = (i * COPIES) >> 5;                            // consecutive bins start on different copies: the lanes of a group read 32 different banks
 #pragma unroll 8
+            for (int k = 0; k < COPIES; ++k) n += c[(k + rot) & (COPIES - 1)];
+        }
+        if (n) atomicAdd(&out[i], n);
+    }
+}
+
+// ---- noise histograms of frame pairs ----------------------------------------------------------------------------------------------------
+// The temporal siblings of the two kernels above: v = |HH(payload p + 1) - HH(payload p)| with HH = a - b - c + d of the same 2 x 2 block in both
+// payloads, counted where all EIGHT codes lie strictly between lo and hi; blockIdx.y is the pair.  Content that does not move cancels in v and
+// the noise of both frames stays: v has the variance 8 s^2 + 2/3 where the spatial statistic has 4 s^2 + 1/3.  The same units and the same walk
+// (copied, not shared: see the note at the top of this namespace), with four loads per lane instead of two -- the same two rows of both payloads.  The
+// second payload lies frame_bytes further on, which need not be a multiple of 16: every load tests its own address and takes the element-wise path
+// on its own.  The histogram lives in LDS as above.  v is sqrt(2) times as wide as the spatial statistic at the same noise level and reaches twice
+// as far, so NB doubles and LOW is 1.5 times the spatial kernel's (48 / 192 bins: 6 / 24 KB of copies beside the 4 / 16 KB of the plain array): the
+// copies cover the noise levels they cover there.  Integer sums commute: the result is the same for every geometry and every schedule.
+template <int ESZ> struct PairK {
+    static constexpr int NB = 4 * ((ESZ == 1 ? 256 : 1024) - 1) + 1;      // 1021 / 4093
+    static constexpr int LOW = ESZ == 1 ? 48 : 192;                       // 1.5 x NoiseK::LOW >= sqrt(2) x: the same range of noise levels
+};
+
+template <int ESZ>
+__global__ __launch_bounds__(256) void yuv_noise_hist_pairs_kernel(const uint8_t* __restrict__ src, uint32_t* __restrict__ dst, int lo, int hi, int W,
+                                                                 int hb, int wb, int ux, size_t origin, size_t frame_bytes) {
+    constexpr int NB = PairK<ESZ>::NB, LOW = PairK<ESZ>::LOW;
+    __shared__ uint32_t low[LOW * 32];
+    __shared__ uint32_t hist[NB];
+    const int tid = threadIdx.x, pr = blockIdx.y, cp = tid & 31;
+    for (int i = tid; i < LOW * 32; i += 256) low[i] = 0;
+    for (int i = tid; i < NB; i += 256) hist[i] = 0;
+    __syncthreads();
+    const uint8_t* y0 = src + (size_t)pr * frame_bytes + origin;          // payload pr; W: the luma row pitch; origin: the byte offset of block (0, 0)
+    const uint8_t* y1 = y0 + frame_bytes;                                 // payload pr + 1 <= T - 1
+    const int units = ux * hb;                                            // hb, wb: whole 2 x 2 blocks; ux = ceil(wb / 4) units per block row
+    for (int u = blockIdx.x * 256 + tid; u < units; u += gridDim.x * 256) {
+        const int by = u / ux, bx0 = (u - by * ux) * 4;
+        const int nb = imin(4, wb - bx0);
+        const size_t r0 = (size_t)(2 * by) * W + 2 * bx0, r1 = r0 + W;
+        int a0[8], b0[8], a1[8], b1[8];
+        if (nb == 4) {
+            ldn<ESZ, 8>(y0, r0, a0);
+            ldn<ESZ, 8>(y0, r1, b0);
+            ldn<ESZ, 8>(y1, r0, a1);
+            ldn<ESZ, 8>(y1, r1, b1);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {                                 // pixels 2 bx0 .. 2 (bx0 + nb) - 1 < 2 wb <= W exist; the others are not read
+                const bool in = k < 2 * nb;
+                a0[k] = in ? ld1<ESZ>(y0, r0 + k) : 0;
+                b0[k] = in ? ld1<ESZ>(y0, r1 + k) : 0;
+                a1[k] = in ? ld1<ESZ>(y1, r0 + k) : 0;
+                b1[k] = in ? ld1<ESZ>(y1, r1 + k) : 0;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int p0 = a0[2 * k], q0 = a0[2 * k + 1], r0c = b0[2 * k], s0 = b0[2 * k + 1];
+            const int p1 = a1[2 * k], q1 = a1[2 * k + 1], r1c = b1[2 * k], s1 = b1[2 * k + 1];
+            const int mn = imin(imin(imin(p0, q0), imin(r0c, s0)), imin(imin(p1, q1), imin(r1c, s1)));
+            const int mx = imax(imax(imax(p0, q0), imax(r0c, s0)), imax(imax(p1, q1), imax(r1c, s1)));
+            if (k < nb && mn > lo && mx < hi) {
+                const int d = (p1 - q1 - r1c + s1) - (p0 - q0 - r0c + s0), v = d < 0 ? -d : d;      // 0 .. 4 (2^bits - 1) = NB - 1
+                if (v < LOW) atomicAdd(&low[v * 32 + cp], 1u);
+                else atomicAdd(&hist[v], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    uint32_t* out = dst + (size_t)pr * NB;
+    for (int i = tid; i < NB; i += 256) {
+        uint32_t n = hist[i];
+        if (i < LOW) {
+#pragma unroll 8
+            for (int c = 0; c < 32; ++c) n += low[i * 32 + ((c + i) & 31)];   // rotated by the bin: the lanes of a group read 32 different banks
+        }
+        if (n) atomicAdd(&out[i], n);
+    }
+}
+
+// The pair statistic by brightness band: band = (2 (S - 8 lo)) / (hi - lo) with S the sum of the eight codes, 0 .. 15 for every block that counts
+// (8 <= S - 8 lo <= 8 (hi - lo) - 8), v saturated to NBV - 1 with the NBV of the spatial band kernel.  [16][NBV] words of LDS and copies of the bins
+// v < LOW of every band, as there.  LOW is again 1.5 times the spatial kernel's: 24 bins at 8 bit with 32 copies (48 KB + 8 KB); at 10 bit 96 bins
+// cover the same noise levels and leave room for 4 copies (24 KB + 32 KB; 8 copies of 96 bins would need 48 KB + 32 KB), neighbouring lanes on
+// different copies, lanes 4 apart share one -- at 10 bit v spreads over four times as many bins, so lanes meet on a word less often to begin with.
+template <int ESZ> struct PairBandK {
+    static constexpr int NBV = BandK<ESZ>::NBV;                          // 128 / 512
+    static constexpr int LOW = ESZ == 1 ? 24 : 96;
+    static constexpr int COPIES = ESZ == 1 ? 32 : 4;
+    static constexpr int LOWW = SN_NLF_BANDS * LOW * COPIES;             // 12288 / 6144 words
+    static constexpr int HISTW = SN_NLF_BANDS * NBV;                     // 2048 / 8192 words
+};
+
+template <int ESZ>
+__global__ __launch_bounds__(256) void yuv_noise_hist_pairs_bands_kernel(const uint8_t* __restrict__ src, uint32_t* __restrict__ dst, int lo, int hi,
+                                                                       int W, int hb, int wb, int ux, size_t origin, size_t frame_bytes) {
+    constexpr int NBV = PairBandK<ESZ>::NBV, LOW = PairBandK<ESZ>::LOW, COPIES = PairBandK<ESZ>::COPIES, LOWW = PairBandK<ESZ>::LOWW,
+                  HISTW = PairBandK<ESZ>::HISTW;
+    __shared__ __attribute__((aligned(16))) uint32_t low[LOWW];
+    __shared__ __attribute__((aligned(16))) uint32_t hist[HISTW];
+    const int tid = threadIdx.x, pr = blockIdx.y, cp = tid & (COPIES - 1);
+    for (int i = tid; i < LOWW / 4; i += 256) ((uint4*)low)[i] = make_uint4(0u, 0u, 0u, 0u);
+    for (int i = tid; i < HISTW / 4; i += 256) ((uint4*)hist)[i] = make_uint4(0u, 0u, 0u, 0u);
+    __syncthreads();
+    const uint8_t* y0 = src + (size_t)pr * frame_bytes + origin;          // as yuv_noise_hist_pairs_kernel
+    const uint8_t* y1 = y0 + frame_bytes;
+    const int units = ux * hb;
+    const uint32_t span = (uint32_t)(hi - lo);
+    for (int u = blockIdx.x * 256 + tid; u < units; u += gridDim.x * 256) {
+        const int by = u / ux, bx0 = (u - by * ux) * 4;
+        const int nb = imin(4, wb - bx0);
+        const size_t r0 = (size_t)(2 * by) * W + 2 * bx0, r1 = r0 + W;
+        int a0[8], b0[8], a1[8], b1[8];
+        if (nb == 4) {
+            ldn<ESZ, 8>(y0, r0, a0);
+            ldn<ESZ, 8>(y0, r1, b0);
+            ldn<ESZ, 8>(y1, r0, a1);
+            ldn<ESZ, 8>(y1, r1, b1);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {                                 // pixels 2 bx0 .. 2 (bx0 + nb) - 1 < 2 wb <= W exist; the others are not read
+                const bool in = k < 2 * nb;
+                a0[k] = in ? ld1<ESZ>(y0, r0 + k) : 0;
+                b0[k] = in ? ld1<ESZ>(y0, r1 + k) : 0;
+                a1[k] = in ? ld1<ESZ>(y1, r0 + k) : 0;
+                b1[k] = in ? ld1<ESZ>(y1, r1 + k) : 0;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int p0 = a0[2 * k], q0 = a0[2 * k + 1], r0c = b0[2 * k], s0 = b0[2 * k + 1];
+            const int p1 = a1[2 * k], q1 = a1[2 * k + 1], r1c = b1[2 * k], s1 = b1[2 * k + 1];
+            const int mn = imin(imin(imin(p0, q0), imin(r0c, s0)), imin(imin(p1, q1), imin(r1c, s1)));
+            const int mx = imax(imax(imax(p0, q0), imax(r0c, s0)), imax(imax(p1, q1), imax(r1c, s1)));
+            if (k < nb && mn > lo && mx < hi) {
+                const int d = (p1 - q1 - r1c + s1) - (p0 - q0 - r0c + s0), v = imin(d < 0 ? -d : d, NBV - 1);
+                const int S = ((p0 + q0) + (r0c + s0)) + ((p1 + q1) + (r1c + s1));
+                const int band = (int)((uint32_t)(2 * (S - 8 * lo)) / span);                         // 0 .. 15 (above)
+                if (v < LOW) atomicAdd(&low[(band * LOW + v) * COPIES + cp], 1u);
+                else atomicAdd(&hist[band * NBV + v], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    uint32_t* out = dst + (size_t)pr * HISTW;
+    for (int i = tid; i < HISTW; i += 256) {
+        uint32_t n = hist[i];
+        const int band = i / NBV, v = i - band * NBV;
+        if (v < LOW) {
+            const uint32_t* c = low + (band * LOW + v) * COPIES;
+            const int rot = (i * COPIES) >> 5;                            // as yuv_noise_hist_bands_kernel: lanes whose copies start on one bank begin at different copies
+#pragma unroll 4
             for (int k = 0; k < COPIES; ++k) n += c[(k + rot) & (COPIES - 1)];
         }
         if (n) atomicAdd(&out[i], n);
@@ -383,6 +535,41 @@ int sn_yuv_noise_hist_rect(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_y
 int sn_yuv_noise_hist_bands(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint32_t* dst, int lo, int hi, int T, int H, int W,
                             void* stream) {
     return noise_hist(true, src, fmt, rect, dst, lo, hi, T, H, W, stream);
+}
+
+// The pair histograms: T payloads are T - 1 pairs, blockIdx.y is the pair; the rest is noise_hist's
+static int noise_hist_pairs(bool bands, const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint32_t* dst, int lo, int hi, int T, int H,
+                            int W, void* stream) {
+    sn_clear_error();
+    if (!valid_payloads(src, fmt, T, H, W) || T < 2 || !dst || ((uintptr_t)dst & 3) || lo > hi) return SN_EINVAL;     // T - 1 <= 65534 pairs: a grid dimension
+    if (lo < -(1 << 24) || hi > (1 << 24)) return SN_EINVAL;               // the band is 32-bit arithmetic: 2 (S - 8 lo) must fit
+    YuvGeo G;
+    if (!make_geo(fmt, H, W, rect, &G)) return SN_EINVAL;
+    int words = 0;
+    with_esz(fmt, [&](auto esz) { words = bands ? PairBandK<esz()>::HISTW : PairK<esz()>::NB; });
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(dst, 0, (size_t)(T - 1) * words * sizeof(uint32_t), s) != hipSuccess) return sn_check_launch();      // dst is overwritten, not added to
+    const int hb = G.h / 2, wb = G.w / 2, ux = (wb + 3) / 4;               // the block grid is anchored at the picture's first sample
+    if (hb < 1 || wb < 1) return sn_check_launch();                        // no whole block: all-zero histograms
+    const long long units = (long long)ux * hb;
+    if (units > 0x7fffffffLL - 1024 * 256) return SN_EINVAL;
+    const long long per = bands ? 4096 : 2048, wgs = (units + per - 1) / per;      // units per workgroup as noise_hist
+    const dim3 block(256), grid(wgs < 1024 ? (int)wgs : 1024, T - 1);
+    with_esz(fmt, [&](auto esz) {
+        if (bands) hipLaunchKernelGGL((yuv_noise_hist_pairs_bands_kernel<esz()>), grid, block, 0, s, src, dst, lo, hi, W, hb, wb, ux, G.oy, G.frame_bytes);
+        else hipLaunchKernelGGL((yuv_noise_hist_pairs_kernel<esz()>), grid, block, 0, s, src, dst, lo, hi, W, hb, wb, ux, G.oy, G.frame_bytes);
+    });
+    return sn_check_launch();
+}
+
+int sn_yuv_noise_hist_pairs(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint32_t* dst, int lo, int hi, int T, int H, int W,
+                            void* stream) {
+    return noise_hist_pairs(false, src, fmt, rect, dst, lo, hi, T, H, W, stream);
+}
+
+int sn_yuv_noise_hist_pairs_bands(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint32_t* dst, int lo, int hi, int T, int H, int W,
+                                  void* stream) {
+    return noise_hist_pairs(true, src, fmt, rect, dst, lo, hi, T, H, W, stream);
 }
 
 int sn_noise_map_level(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const float* knots, int lo, int hi, void* dst, int dst_dtype,

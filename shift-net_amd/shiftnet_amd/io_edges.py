@@ -11,6 +11,8 @@ the statistics of the same payloads' luma (csrc/sn_yuv_stats.hip), each for one 
 ``noise_hist_yuv``: uint32 histograms of |a - b - c + d| over the 2 x 2 luma blocks, for the blind noise estimate (shiftnet_amd/noise.py);
 ``noise_hist_bands_yuv``: that statistic split into 16 bands of brightness, from which noise.py estimates a noise-level function (sigma against the
                luma code);
+``noise_hist_pairs_yuv`` / ``noise_hist_pairs_bands_yuv``: the same two statistics of the difference of consecutive payloads, T - 1 pairs, for the
+               temporal noise estimate (shiftnet_amd/noise.py);
 ``noise_map_level``: payloads + the 16 knots of such a function -> the denoisers' noise plane;
 ``rowcol_sums_yuv``: uint32 sums of the luma codes of every row and of every column, for the letterbox rule (shiftnet_amd/picture.py);
 ``rect=(x0, y0, w, h)``, where a function takes it (all but ``thumb_yuv`` and ``rowcol_sums_yuv``), restricts it to that picture of the stream, with
@@ -237,6 +239,39 @@ def noise_hist_bands_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: i
         L.check(L.load().sn_yuv_noise_hist_bands(payload_u8.data_ptr(), fmt, r, y.data_ptr(), lo, hi, T, H, W,
                                                  torch.cuda.current_stream(payload_u8.device).cuda_stream), "sn_yuv_noise_hist_bands")
     return y
+
+
+def _hist_pairs(symbol: str, shape, payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lo, hi, out, rect) -> torch.Tensor:
+    """What the two pair histograms share: T >= 2 payloads -> uint32 [T - 1, *shape] from ``symbol``."""
+    T = _payload(payload_u8, fmt, H, W)[0]
+    if T < 2:
+        raise ValueError(f"{symbol}: a pair needs two payloads, got {T}")
+    lo, hi = _clip(fmt, lo, hi)
+    y = out if out is not None else torch.empty((T - 1,) + shape, dtype=torch.uint32, device=payload_u8.device)
+    assert tuple(y.shape) == (T - 1,) + shape and y.dtype == torch.uint32 and y.is_contiguous() and y.device == payload_u8.device
+    r = None if rect is None else _rect(rect, fmt, H, W)
+    with torch.cuda.device(payload_u8.device):
+        L.check(getattr(L.load(), symbol)(payload_u8.data_ptr(), fmt, r, y.data_ptr(), lo, hi, T, H, W,
+                                          torch.cuda.current_stream(payload_u8.device).cuda_stream), symbol)
+    return y
+
+
+def noise_hist_pairs_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lo: Optional[int] = None, hi: Optional[int] = None,
+                         out: Optional[torch.Tensor] = None, rect=None) -> torch.Tensor:
+    """payload_u8: [T, frame_bytes] uint8 on a HIP device, T >= 2 (only the luma plane of each payload is read) -> uint32 [T - 1, 4 (2^bits - 1) + 1]:
+    per pair of consecutive payloads the counts of v = |HH(p + 1) - HH(p)|, HH = a - b - c + d of the same 2 x 2 luma block in both, over the blocks
+    whose eight codes lie strictly between ``lo`` and ``hi``.  ``lo``, ``hi``, ``out``, ``rect`` as ``noise_hist_yuv``."""
+    from .noise import pair_bins
+    return _hist_pairs("sn_yuv_noise_hist_pairs", (pair_bins(fmt.bits),), payload_u8, fmt, H, W, lo, hi, out, rect)
+
+
+def noise_hist_pairs_bands_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lo: Optional[int] = None, hi: Optional[int] = None,
+                               out: Optional[torch.Tensor] = None, rect=None) -> torch.Tensor:
+    """payload_u8: [T, frame_bytes] uint8 on a HIP device, T >= 2 -> uint32 [T - 1, 16, NBV], NBV = 128 / 512: ``noise_hist_pairs_yuv``'s counts split by
+    the brightness of the block in both payloads, band = (2 (S - 8 lo)) / (hi - lo) for the sum S of the eight codes, and v saturated to NBV - 1.
+    ``lo``, ``hi``, ``out``, ``rect`` as ``noise_hist_yuv``."""
+    from .noise import NLF_BANDS, nlf_bins
+    return _hist_pairs("sn_yuv_noise_hist_pairs_bands", (NLF_BANDS, nlf_bins(fmt.bits)), payload_u8, fmt, H, W, lo, hi, out, rect)
 
 
 def noise_map_level(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, Hp: int, Wp: int, knots, dtype: torch.dtype,

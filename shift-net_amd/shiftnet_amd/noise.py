@@ -24,6 +24,24 @@ clamped.  ``sn_noise_map_level`` evaluates the curve per pixel.  ``parse_curves`
 
 A heuristic, checked on synthetic clips only.  It assumes white Gaussian noise: compression makes noise non-white and the estimate then reads
 low; pixel-scale texture adds to it in quadrature; at sigma >= 40 the clipping of R'G'B' to [0, 1] makes it read low by construction.
+
+Temporal estimate (``sigma_estimator="temporal"`` / ``"min"`` of the restorer): texture that does not move is the same in the next frame and noise is not.
+``sn_yuv_noise_hist_pairs`` counts ``v = |HH(frame p + 1) - HH(frame p)|`` with ``HH = a - b - c + d`` of the same 2 x 2 block in both frames, over the
+blocks whose eight codes are unclipped.  Static content cancels exactly; HH rather than the plain frame difference also cancels smooth change (flicker,
+fades, exposure drift, motion along gradients).  White noise of standard deviation s gives v the variance ``8 s^2 + 2/3`` (eight rounded codes):
+
+  var = max((med / 0.6744897501960817)^2 - 2/3, 0);  sigma_Y = sqrt(var / 8);  sigma = sigma_Y / (g s)            (``pair_sigma``)
+
+with ``med`` from ``hist_median`` (the same bin geometry).  A pair with no block outside bin 0 is the same frame twice -- the planner's clamped
+reflection in clips of one or two frames, duplicated frames in the footage -- and has no estimate: it says nothing about noise.  A window's temporal
+sigma is the median over its pairs that have one (a cut inside a window is one outlier pair).  Both estimators can only be pushed UP by picture
+content -- texture raises the spatial one, moving fine detail the temporal one -- so the lower of the two is nearer the truth: ``"min"``
+(``combine_sigma``), a rule without a threshold.  The curve follows suit band by band (``window_curve_pairs``): the band histograms of the pairs
+(``sn_yuv_noise_hist_pairs_bands``) summed over the pairs that are not repeats, estimated per band with the rules above, combined per band with the
+spatial knot, then filled and clamped.
+Caveats, stated plainly: also a heuristic, checked on synthetic clips only.  Temporally correlated noise reads LOW -- inter-coded footage, where the
+encoder predicts the noise, and temporally denoised footage -- and that is the one direction in which ``"min"`` can hurt.  Moving fine texture still
+raises both estimates.  A noise-free static clip gives identical frames, every pair is a repeat, and the spatial estimate is what is left.
 """
 from __future__ import annotations
 
@@ -103,9 +121,76 @@ def check_clamp(clamp: Sequence[float]) -> Tuple[float, float]:
 def window_sigma(frame_sigmas: Iterable[Optional[float]], clamp: Sequence[float] = CLAMP) -> float:
     """The median of the frames' sigmas (frames without an estimate left out; 0 if none has one), clamped."""
     lo, hi = check_clamp(clamp)
+    return min(max(frames_median(frame_sigmas), lo), hi)
+
+
+# ---- the temporal estimate: frame pairs ---------------------------------------------------------------------------------------------------
+ESTIMATORS = ("spatial", "temporal", "min")
+
+
+def pair_bins(bits: int) -> int:
+    """Bins per pair of sn_yuv_noise_hist_pairs: v = 0 .. 4 (2^bits - 1)."""
+    return 4 * ((1 << bits) - 1) + 1
+
+
+def pair_is_repeat(hist) -> bool:
+    """No block outside bin 0 (an empty histogram included): the same frame twice as far as the statistic can tell, or nothing counted."""
+    h = np.asarray(hist)
+    return not bool(h.reshape(-1, h.shape[-1])[:, 1:].any())
+
+
+def pair_sigma_luma(hist) -> Optional[float]:
+    """sigma_Y of one pair histogram in luma code units (no repeat rule here), or None if no block counted."""
+    med = hist_median(hist)
+    if med is None:
+        return None
+    q = med / MAD_TO_SIGMA
+    var = q * q - 2.0 / 3.0
+    return math.sqrt(var / 8.0) if var > 0.0 else 0.0
+
+
+def pair_sigma(hist, bits: int, matrix: int, range_: int) -> Optional[float]:
+    """One pair histogram -> the sigma of i.i.d. noise on 8-bit R'G'B' that explains it, or None: no block counted, or none fell outside bin 0."""
+    if pair_is_repeat(hist):
+        return None
+    return pair_sigma_luma(hist) / (luma_gain(matrix) * code_scale(bits, range_))
+
+
+def window_sigma_temporal(pair_sigmas: Iterable[Optional[float]]) -> Optional[float]:
+    """The median over the pairs that have an estimate, or None if none has."""
+    v = [s for s in pair_sigmas if s is not None]
+    return float(np.median(np.asarray(v, np.float64))) if v else None
+
+
+def frames_median(frame_sigmas: Iterable[Optional[float]]) -> float:
+    """The spatial estimate of a window before the clamp: the median of the frames' sigmas (frames without one left out; 0 if none has one)."""
     v = [s for s in frame_sigmas if s is not None]
-    s = float(np.median(np.asarray(v, np.float64))) if v else 0.0
-    return min(max(s, lo), hi)
+    return float(np.median(np.asarray(v, np.float64))) if v else 0.0
+
+
+def check_estimator(estimator) -> str:
+    if not (isinstance(estimator, str) and estimator in ESTIMATORS):
+        raise ValueError(f"sigma_estimator must be one of {', '.join(repr(e) for e in ESTIMATORS)}, got {estimator!r}")
+    return estimator
+
+
+def _combine(spatial: Optional[float], temporal: Optional[float], estimator: str) -> Optional[float]:
+    """The rule, on estimates that may be missing: "spatial" -> the spatial one; "temporal" -> the temporal one, the spatial one where there is none;
+    "min" -> the lower of the two, the one that exists where one is missing."""
+    check_estimator(estimator)
+    if estimator == "spatial" or temporal is None:
+        return spatial
+    if estimator == "temporal" or spatial is None:
+        return temporal
+    return min(spatial, temporal)
+
+
+def combine_sigma(spatial: float, temporal: Optional[float], estimator: str = "spatial", clamp: Sequence[float] = CLAMP) -> float:
+    """A window's sigma from its spatial estimate (``frames_median``, unclamped) and its temporal one (``window_sigma_temporal``, None: none):
+    "spatial" -> the spatial one; "temporal" -> the temporal one, or the spatial one where it is None; "min" -> the lower of the two, or the spatial
+    one where the temporal is None.  The clamp is applied last, once."""
+    lo, hi = check_clamp(clamp)
+    return min(max(float(_combine(float(spatial), temporal, estimator)), lo), hi)
 
 
 def check_sigmas(sigmas: Iterable[float]) -> List[float]:
@@ -196,6 +281,46 @@ def window_curve(band_hists, bits: int, matrix: int, range_: int, clamp: Sequenc
     h = h.reshape(-1, NLF_BANDS, h.shape[-1]).sum(axis=0)
     knots = fill_curve([band_sigma(h[b], bits, matrix, range_, min_blocks) for b in range(NLF_BANDS)])
     return [min(max(k, lo), hi) for k in knots]
+
+
+def pair_band_sigma(hist, bits: int, matrix: int, range_: int, min_blocks: int = NLF_MIN_BLOCKS) -> Optional[float]:
+    """One band's pair histogram (the window's sum over its pairs) -> ``pair_sigma``'s arithmetic on it, with ``band_sigma``'s rules: None for fewer than
+    ``min_blocks`` blocks or the median in the last bin."""
+    h = np.asarray(hist).reshape(-1).astype(np.int64)
+    cum = np.cumsum(h)
+    n = int(cum[-1])
+    if n < max(min_blocks, 1):
+        return None
+    if int(np.searchsorted(cum, n / 2.0, side="left")) == len(h) - 1:
+        return None
+    return pair_sigma_luma(h) / (luma_gain(matrix) * code_scale(bits, range_))
+
+
+def sum_pair_bands(pair_band_hists) -> np.ndarray:
+    """[P, 16, NBV] (or [16, NBV]) band histograms of a window's pairs -> their int64 sum [16, NBV] over the pairs that are not repeats
+    (``pair_is_repeat``: nothing outside bin 0 in any band); the bin-0 mass of a repeat would drag every band down."""
+    h = np.asarray(pair_band_hists).astype(np.int64)
+    h = h.reshape(-1, NLF_BANDS, h.shape[-1])
+    keep = [p for p in range(len(h)) if not pair_is_repeat(h[p])]
+    return h[keep].sum(axis=0) if keep else np.zeros(h.shape[1:], np.int64)
+
+
+def window_curve_pairs(band_hists, pair_band_hists, bits: int, matrix: int, range_: int, estimator: str = "min", clamp: Sequence[float] = CLAMP,
+                       min_blocks: int = NLF_MIN_BLOCKS) -> List[float]:
+    """``window_curve`` with the temporal estimate: band_hists [T, 16, NBV] of the window's frames and pair_band_hists [T - 1, 16, NBV] of its pairs ->
+    16 knots.  Per band the spatial estimate (``band_sigma`` of the frames' sum) and the temporal one (``pair_band_sigma`` of ``sum_pair_bands``) are
+    combined as ``combine_sigma`` combines (None where neither exists); then the holes are filled, then every knot is clamped."""
+    lo, hi = check_clamp(clamp)
+    check_estimator(estimator)
+    h = np.asarray(band_hists).astype(np.int64)
+    h = h.reshape(-1, NLF_BANDS, h.shape[-1]).sum(axis=0)
+    ph = sum_pair_bands(pair_band_hists)
+    knots = []
+    for b in range(NLF_BANDS):
+        spatial = band_sigma(h[b], bits, matrix, range_, min_blocks)
+        temporal = pair_band_sigma(ph[b], bits, matrix, range_, min_blocks) if estimator != "spatial" else None
+        knots.append(_combine(spatial, temporal, estimator))
+    return [min(max(k, lo), hi) for k in fill_curve(knots)]
 
 
 def check_curves(curves: Iterable[Sequence[float]]) -> List[List[float]]:

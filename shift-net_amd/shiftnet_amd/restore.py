@@ -16,7 +16,8 @@ those of restoring every scene as a separate video.  The cuts are listed by the 
 
 Noise level (``sigma``, denoise variants): a number, a list with one number per window, or ``"auto"``: a blind estimate per window from
 histograms of the luma's 2 x 2 Haar HH coefficient, made on the device from the payloads the window has uploaded anyway
-(``sn_yuv_noise_hist``, shiftnet_amd/noise.py).
+(``sn_yuv_noise_hist``, shiftnet_amd/noise.py).  ``sigma_estimator="temporal"`` / ``"min"`` adds the same statistic of the difference of consecutive
+input frames (``sn_yuv_noise_hist_pairs``), in which texture that does not move cancels, and uses it alone or the lower of the two.
 
 Noise model (``noise_model``, denoise variants, off by default): sensor noise is signal dependent, the shadows of R'G'B' carry more of it than the
 highlights.  ``"level"`` estimates per window a noise-level function -- sigma against the luma code, 16 knots -- from the same histograms split by
@@ -49,7 +50,8 @@ import numpy as np
 
 from .restore_cli import amount_arg, main, make_parser, picture_arg, sigma_arg  # noqa: F401 -- the command line (restore_cli.py), reached through this module
 from .windows import (DITHERS, FUTURE, PAST, PerWindow, _Frames, _SceneFrames, _Thread, amount_form, noise_model_form, pad_multiple,  # noqa: F401
-                      padded_size, picture_form, plan_output, plan_scene_windows, plan_windows, reflect_index, scene_cuts_form, sigma_form, window_indices)
+                      padded_size, picture_form, plan_output, plan_scene_windows, plan_windows, reflect_index, scene_cuts_form, sigma_estimator_form,
+                      sigma_form, window_indices)
 
 VARIANTS = {"deblur": "gshift_deblur1", "deblur_small": "gshift_deblur2", "denoise": "gshift_denoise1", "denoise_small": "gshift_denoise2"}
 
@@ -97,6 +99,7 @@ class _Slot:
         self.t0 = 0                                               # the frame number, in its clip, of the first frame that window restores
         self.used = False                                         # in this restore(): a window has gone through the slot
         self.noise = self.bands = self.sums = None                # _Stat: the window's histograms, band histograms, row and column sums
+        self.pairs = self.pair_bands = None                       # _Stat: the histograms and band histograms of the window's frame pairs
         self.dev_ref = None                                       # a mix with another format out: the window's input payloads in the format written
 
 
@@ -111,7 +114,10 @@ class _Run:
         self.window_nlf: List = []
         self.window_picture: List = []
         self.picture_wait_ms: List[float] = []
-        self.launches = {"noise": 0, "nlf": 0, "nlf_map": 0, "picture": 0, "thumb": 0}
+        self.window_sigma_spatial: List = []                      # sigma_estimator other than "spatial": the two estimates before the rule and the clamp
+        self.window_sigma_temporal: List = []
+        self.window_pair_sigma: List = []
+        self.launches = {"noise": 0, "nlf": 0, "nlf_map": 0, "picture": 0, "thumb": 0, "noise_pairs": 0, "nlf_pairs": 0}
         self.src = None                                           # the frame source
 
 
@@ -231,12 +237,26 @@ class VideoRestorer:
     view: None -- the restored frames; ``"removed"`` (with ``amount`` None or 1) -- what the restoration took out: ``mid-grey + removed_gain * (code_in
     - code_out)`` per sample, clamped to the legal codes, 128 (512 at 10 bit) in all three planes where nothing changed.  ``removed_gain`` (finite, >= 0)
     makes small differences visible.  With ``picture`` the samples outside the rectangle stay what they are without a view.
-    ``stats["amount"]`` is the pair of amounts used (None: none given) and ``stats["view"]`` the view."""
+    ``stats["amount"]`` is the pair of amounts used (None: none given) and ``stats["view"]`` the view.
+    sigma_estimator: ``"spatial"`` -- the estimate of ``sigma="auto"`` as described above, today's launches, bytes and stats keys; ``"temporal"`` or ``"min"``
+    (both need ``sigma="auto"``) -- the window's input frames as fed are also taken in consecutive pairs, and the same 2 x 2 statistic of the DIFFERENCE
+    of the two frames is counted (``sn_yuv_noise_hist_pairs``, one more launch on the side stream): content that does not move cancels in it, so
+    pixel-scale texture, which the spatial estimate reads as noise, does not reach it.  A pair of identical frames (a reflected duplicate in a clip of
+    one or two frames, a repeated frame) has no estimate; the window's temporal sigma is the median over the pairs that have one.  ``"temporal"`` uses
+    it, or the spatial estimate where no pair has one; ``"min"`` uses the lower of the two -- picture content can only push either one up.  The clamp
+    comes last.  With ``noise_model="level"`` the curve is combined band by band in the same way (``sn_yuv_noise_hist_pairs_bands``,
+    noise.window_curve_pairs).  **A heuristic, checked on synthetic clips only**: temporally correlated noise (inter-coded or temporally denoised footage)
+    reads LOW, the one direction in which ``"min"`` can hurt; moving fine texture still raises both estimates.  With ``picture`` the pair statistic sees
+    the window's rectangle, as the spatial one does; windows never cross a cut under ``scene_cuts``, and without it a cut inside a window is one outlier
+    pair, which the median over the pairs takes.  ``stats`` then also has ``sigma_estimator``, ``window_sigma_spatial`` and ``window_sigma_temporal`` (the
+    two estimates of every window before the rule and the clamp; None where no pair has one), ``window_pair_sigma`` (per window, one entry per pair, None
+    allowed), ``noise_pairs_launches`` and, with ``"level"``, ``nlf_pairs_launches``; ``window_sigma``, ``window_frame_sigma`` and ``window_nlf`` keep their
+    meaning: what the window was restored with, the per-frame spatial values, the curve used."""
 
     def __init__(self, net, one_len: int, sigma=None, pipeline: bool = True, scene_cuts=None,
                  cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0),
                  picture=None, bar_level: float = 1.0, out_format=None, dither=None, dither_seed: int = 0, noise_model=None,
-                 amount=None, view=None, removed_gain: float = 1.0) -> None:
+                 amount=None, view=None, removed_gain: float = 1.0, sigma_estimator: str = "spatial") -> None:
         import torch
         from .lib import YuvFmt
         from .noise import check_clamp
@@ -259,6 +279,7 @@ class VideoRestorer:
         if self.sigma_mode != "fixed" and not self.V.denoise:
             raise ValueError(f"sigma={'auto' if self.sigma_mode == 'auto' else 'a per-window list'!r} is for the denoise variants; {type(net).__name__} "
                              "of a deblur variant takes no noise level")
+        self.sigma_estimator = sigma_estimator_form(sigma_estimator, self.sigma_mode)      # "spatial": the code path without any of the rest
         if noise_model is not None and not self.V.denoise:
             raise ValueError(f"noise_model is for the denoise variants; {type(net).__name__} of a deblur variant takes no noise level")
         # None (the code path without any of the rest), "level", "list" (a PerWindow)
@@ -319,6 +340,11 @@ class VideoRestorer:
             if self.nlf_mode == "level":
                 from .noise import NLF_BANDS, nlf_bins
                 s.bands = _Stat(torch, dev, "nlf", tin, [(NLF_BANDS, nlf_bins(fmt.bits))])
+            if self.sigma_estimator != "spatial":                 # tin frames are tin - 1 pairs
+                from .noise import NLF_BANDS, nlf_bins, pair_bins
+                s.pairs = _Stat(torch, dev, "noise_pairs", tin - 1, [(pair_bins(fmt.bits),)])
+                if self.nlf_mode == "level":
+                    s.pair_bands = _Stat(torch, dev, "nlf_pairs", tin - 1, [(NLF_BANDS, nlf_bins(fmt.bits))])
             if self.picture_mode == "auto":
                 s.sums = _Stat(torch, dev, "picture", tin, [(h,), (w,)])
 
@@ -344,7 +370,7 @@ class VideoRestorer:
     def _stage(self, slot: _Slot, frames: Sequence[np.ndarray], t0: int = 0) -> int:
         """Host frames -> pinned slot -> device -> RGB tensors, on the side stream.  Windows are staged in the order they are restored.
         t0: the number of the window's first restored frame in its clip (the dither's frame number)."""
-        from .io_edges import ingest_yuv, noise_hist_bands_yuv, noise_hist_yuv, rowcol_sums_yuv
+        from .io_edges import ingest_yuv, noise_hist_bands_yuv, noise_hist_pairs_bands_yuv, noise_hist_pairs_yuv, noise_hist_yuv, rowcol_sums_yuv
         torch, run = self.torch, self.run
         t = len(frames)
         rect = self._window_picture()
@@ -376,9 +402,15 @@ class VideoRestorer:
                 # the histograms of the payloads just uploaded, ahead of the ingest so that they are on the host long before _run asks.  The
                 # pinned twin is free: _run read it on the host before this slot was handed back to the stager
                 slot.noise.launch(t, run, lambda out: noise_hist_yuv(payloads, self.fmt, self.h, self.w, self.noise_lo, self.noise_hi, out=out, rect=rect))
+            if slot.pairs is not None:                           # the statistic of the t - 1 pairs of consecutive payloads (t >= 5: a window has 4 neighbours)
+                slot.pairs.launch(t - 1, run, lambda out: noise_hist_pairs_yuv(payloads, self.fmt, self.h, self.w, self.noise_lo, self.noise_hi, out=out,
+                                                                               rect=rect))
             if self.nlf_mode == "level":                         # the same statistic by brightness band, from the same payloads, behind it
                 slot.bands.launch(t, run, lambda out: noise_hist_bands_yuv(payloads, self.fmt, self.h, self.w, self.noise_lo, self.noise_hi, out=out,
                                                                            rect=rect))
+            if slot.pair_bands is not None:
+                slot.pair_bands.launch(t - 1, run, lambda out: noise_hist_pairs_bands_yuv(payloads, self.fmt, self.h, self.w, self.noise_lo,
+                                                                                          self.noise_hi, out=out, rect=rect))
             ingest_yuv(payloads, self.fmt, self.h, self.w, hp, wp, self.dtype, out=x, rect=rect)
             if x32 is not None:
                 ingest_yuv(payloads, self.fmt, self.h, self.w, hp, wp, torch.float32, out=x32, rect=rect)
@@ -393,7 +425,17 @@ class VideoRestorer:
             hist, = slot.noise.wait(t)
             per = [frame_sigma(hist[i], self.fmt.bits, self.fmt.matrix, self.fmt.range) for i in range(t)]
             run.window_frame_sigma.append(per)
-            sigma = window_sigma(per, self.sigma_clamp)
+            if self.sigma_estimator == "spatial":
+                sigma = window_sigma(per, self.sigma_clamp)
+            else:
+                from .noise import combine_sigma, frames_median, pair_sigma, window_sigma_temporal
+                pairs, = slot.pairs.wait(t - 1)
+                ps = [pair_sigma(pairs[i], self.fmt.bits, self.fmt.matrix, self.fmt.range) for i in range(t - 1)]
+                spatial, temporal = frames_median(per), window_sigma_temporal(ps)
+                run.window_pair_sigma.append(ps)
+                run.window_sigma_spatial.append(spatial)
+                run.window_sigma_temporal.append(temporal)
+                sigma = combine_sigma(spatial, temporal, self.sigma_estimator, self.sigma_clamp)
         else:
             sigma = self.sigma.at(len(run.window_sigma))
         run.window_sigma.append(sigma)
@@ -403,9 +445,13 @@ class VideoRestorer:
         """The noise-level function of the window about to run (noise_model): 16 knots, sigma of 8-bit R'G'B'."""
         run = self.run
         if self.nlf_mode == "level":
-            from .noise import window_curve
+            from .noise import window_curve, window_curve_pairs
             bands, = slot.bands.wait(t)
-            curve = window_curve(bands, self.fmt.bits, self.fmt.matrix, self.fmt.range, self.sigma_clamp)
+            if self.sigma_estimator == "spatial":
+                curve = window_curve(bands, self.fmt.bits, self.fmt.matrix, self.fmt.range, self.sigma_clamp)
+            else:
+                pair_bands, = slot.pair_bands.wait(t - 1)
+                curve = window_curve_pairs(bands, pair_bands, self.fmt.bits, self.fmt.matrix, self.fmt.range, self.sigma_estimator, self.sigma_clamp)
         else:
             curve = list(self.nlf.at(len(run.window_nlf)))
         run.window_nlf.append(curve)
@@ -490,6 +536,13 @@ class VideoRestorer:
             stats["window_sigma"] = list(run.window_sigma)
             if self.sigma_mode == "auto":
                 stats["window_frame_sigma"] = [list(p) for p in run.window_frame_sigma]
+            if self.sigma_estimator != "spatial":
+                stats["sigma_estimator"] = self.sigma_estimator
+                stats["window_sigma_spatial"], stats["window_sigma_temporal"] = list(run.window_sigma_spatial), list(run.window_sigma_temporal)
+                stats["window_pair_sigma"] = [list(p) for p in run.window_pair_sigma]
+                stats["noise_pairs_launches"] = run.launches["noise_pairs"]
+                if self.nlf_mode == "level":
+                    stats["nlf_pairs_launches"] = run.launches["nlf_pairs"]
         src = run.src
         if self.scene_cuts is not None:                          # its thread has ended: the stream has been read to its end
             stats["cuts"] = list(src.cuts)

@@ -57,6 +57,10 @@ def make_parser() -> argparse.ArgumentParser:
                     help="noise level (8-bit code values), required by the denoise variants: a number; 'auto' estimates it per window on the device "
                          "(a heuristic that assumes white Gaussian noise); FILE lists one sigma per window, one per line ('#' comments)")
     ap.add_argument("--sigma_clamp", type=float, nargs=2, default=(0.0, 50.0), metavar=("LO", "HI"), help="auto: the estimate is clamped to this range")
+    ap.add_argument("--sigma_estimator", choices=["spatial", "temporal", "min"], default="spatial",
+                    help="--sigma auto only: 'temporal' estimates the noise from the difference of consecutive frames, in which texture that does not move "
+                         "cancels (temporally correlated noise -- inter-coded or temporally denoised footage -- reads low); 'min' takes the lower of that and "
+                         "the spatial estimate; with --noise_model level the curve follows band by band; default spatial: each frame on its own")
     ap.add_argument("--sigma_out", default=None, metavar="FILE", help="write the sigma that every window was restored with, in the format --sigma FILE reads")
     ap.add_argument("--noise_model", default="flat", metavar="{flat,level,FILE}",
                     help="denoise variants: 'level' (needs --sigma auto) estimates per window the noise level as a function of brightness on the device and "
@@ -147,6 +151,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error(f"--amount / --view / --removed_gain: {e}")
     if "denoise" in a.variant and a.sigma is None:
         ap.error("--sigma is required by the denoise variants")
+    if a.sigma_estimator != "spatial" and a.sigma != "auto":      # before the file of a --sigma FILE is opened
+        ap.error(f"--sigma_estimator {a.sigma_estimator} needs --sigma auto")
     log = lambda s: (sys.stderr.write(s + "\n"), sys.stderr.flush())      # noqa: E731
     sigma, sigma_how = a.sigma, "fixed"
     if isinstance(sigma, str):
@@ -193,7 +199,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         vr = VideoRestorer(net, a.one_len, sigma=sigma, pipeline=not a.no_pipeline, scene_cuts=cuts, cut_threshold=a.cut_threshold,
                            cut_ratio=a.cut_ratio, sigma_clamp=a.sigma_clamp, picture=picture, bar_level=a.bar_level, out_format=a.out_format,
                            dither=None if a.dither == "none" else a.dither, dither_seed=a.dither_seed, noise_model=noise_model,
-                           amount=a.amount, view=view, removed_gain=a.removed_gain)
+                           amount=a.amount, view=view, removed_gain=a.removed_gain, sigma_estimator=a.sigma_estimator)
         if a.out_format is not None or a.dither != "none":
             log(f"output: C{a.out_format or hd.chroma}{'' if a.out_format else ' (as the input)'}, dither {a.dither}"
                 f"{' seed %d' % a.dither_seed if a.dither != 'none' else ''}")
@@ -232,7 +238,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             log(f"noise model ({nlf_how}): knots min {min(min(c) for c in wn):.2f} / max {max(max(c) for c in wn):.2f} over {len(wn)} "
                 f"window{'' if len(wn) == 1 else 's'}")
         if ws:
-            log(f"sigma ({sigma_how}{', clamped to [%g, %g]' % tuple(a.sigma_clamp) if sigma_how == 'auto' else ''}): "
+            log(f"sigma ({sigma_how}{', ' + a.sigma_estimator if a.sigma_estimator != 'spatial' else ''}{', clamped to [%g, %g]' % tuple(a.sigma_clamp) if sigma_how == 'auto' else ''}): "
                 f"min {min(ws):.2f} / median {float(np.median(ws)):.2f} / max {max(ws):.2f} over {len(ws)} window{'' if len(ws) == 1 else 's'}")
     finally:
         if fin is not sys.stdin.buffer:

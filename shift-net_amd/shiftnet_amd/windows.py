@@ -103,7 +103,7 @@ class PerWindow:
         return self.value[k]
 
 
-# The accepted forms of the four options, each -> (mode, value).  What depends on the network (deblur or denoise) is judged by the caller.
+# The accepted forms of the options, each -> (mode, value).  What depends on the network (deblur or denoise) is judged by the caller.
 def scene_cuts_form(scene_cuts):
     """None -> ("off", None); "auto" -> ("auto", "auto"); an iterable of frame indices -> ("list", the checked list)."""
     if scene_cuts is None:
@@ -137,6 +137,16 @@ def noise_model_form(noise_model):
         raise ValueError(f"noise_model must be None, 'level' or a list of curves, got {noise_model!r}")
     from .noise import check_curves
     return "list", PerWindow("noise_model", check_curves(noise_model), True)
+
+
+def sigma_estimator_form(sigma_estimator, sigma_mode: str = "auto") -> str:
+    """"spatial" | "temporal" | "min" -> the word; ValueError for any other, and for one that is not "spatial" unless the sigma is estimated
+    (``sigma_mode`` of ``sigma_form``): only sigma="auto" has an estimate to choose."""
+    from .noise import check_estimator
+    word = check_estimator(sigma_estimator)
+    if word != "spatial" and sigma_mode != "auto":
+        raise ValueError(f"sigma_estimator={word!r} chooses how sigma='auto' estimates the noise level: it needs sigma='auto'")
+    return word
 
 
 VIEWS = ("removed",)

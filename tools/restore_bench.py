@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15, 3.16, 3.17 and 3.19 (run on the MI355X from the repository root).
+"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15, 3.16, 3.17, 3.19 and 3.20 (run on the MI355X from the repository root).
 
   kernels : time per pixel of sn_ingest_yuv / sn_egress_yuv / sn_yuv_thumb / sn_yuv_noise_hist (4:2:0 8 bit, 720p x 20 frames; the noise
             histogram on the same frames with noise of sigma 10 as well) beside sn_ingest_u8 / sn_egress_u8 on the same
@@ -7,13 +7,15 @@
             median and min..max over the repetitions.  Since 3.16 also the dithered egress (sn_egress_yuv_dither) from float32 at 8 bit 4:2:0,
             10 bit 4:2:0 and 10 bit 4:4:4 beside the undithered egress of the same formats, and with --parent_lib SO the undithered sn_egress_yuv
             of another build on the same tensors.  Since 3.19 also the mixed egress (sn_egress_yuv_mix, amount (0.5, 0.5)) from float32 at 8 bit
-            4:2:0 and 10 bit 4:4:4, dithered and not, and the removed view at 8 bit 4:2:0, beside the plain egress of the same formats.
+            4:2:0 and 10 bit 4:4:4, dithered and not, and the removed view at 8 bit 4:2:0, beside the plain egress of the same formats.  Since 3.20
+            also sn_yuv_noise_hist_pairs on the payloads of the noise histogram (20 frames are 19 pairs).
   pipeline: steady-state wall time per 720p window of the pipelined restorer (Shift-Net-s, one_len 16, bf16, Y4M held in memory) beside the
             forward-only time of the same windows (device events in the same runs) and beside pipeline=False, the two alternating.
             --scene_cuts auto: the same stream with the cut detector running (sn_yuv_thumb; 3.13).  --cut_every N: every second scene of N frames
             is inverted, so that the stream has a cut every N frames; with --scene_cuts off / auto / listed.
   sigma   : steady-state wall time per 720p window of the pipelined denoiser (Shift-Net-s denoise, one_len 16, bf16) with sigma=10.0 and with
-            sigma="auto" (sn_yuv_noise_hist per window; 3.14), runs of the two alternating in one process, the first two windows left out.
+            sigma="auto" (sn_yuv_noise_hist per window; 3.14), and since 3.20 with sigma="auto", sigma_estimator="min" (sn_yuv_noise_hist_pairs on
+            top), runs of the three alternating in one process, the first two windows left out.
   picture : the active picture (3.15) on a 1920 x 1080 stream whose picture is (0, 138, 1920, 804), bars at black.  --mode forward: steady-state
             forward time per window of the pipelined restorer (Shift-Net-s, one_len 16, bf16, Y4M held in memory) with picture=None and with
             picture="auto" (or --picture fixed), runs of the two alternating in one process, the first two windows left out, beside the wall time
@@ -22,7 +24,7 @@
             sn_yuv_thumb on the same payloads, interleaved as in the kernels part; --parent_lib SO adds the two entry points of another build.
   nlf     : the noise-level function (3.17).  --mode kernels: time per launch of sn_yuv_noise_hist_bands and sn_noise_map_level (-> bf16) beside
             sn_yuv_noise_hist and sn_ingest_yuv on the same payloads (4:2:0 8 bit, 720p x 20 frames, a blurred clip and the same with noise of sigma 10),
-            interleaved as in the kernels part.  --mode forward: steady-state wall time per 720p window of the pipelined denoiser (as the sigma part)
+            interleaved as in the kernels part; since 3.20 also sn_yuv_noise_hist_pairs and sn_yuv_noise_hist_pairs_bands.  --mode forward: steady-state wall time per 720p window of the pipelined denoiser (as the sigma part)
             with sigma="auto" alone and with noise_model="level" on top, runs of the two alternating in one process, the first two windows left out.
 Prints one JSON object per part.
 """
@@ -43,8 +45,8 @@ import torch  # noqa: E402
 
 from shiftnet_amd import lib as L  # noqa: E402
 from shiftnet_amd import restore, synth, y4m  # noqa: E402
-from shiftnet_amd.io_edges import (egress_u8, egress_yuv, ingest_u8, ingest_yuv, noise_hist_bands_yuv, noise_hist_yuv, noise_map_level,  # noqa: E402
-                                   rowcol_sums_yuv, thumb_yuv, yuv_fmt)
+from shiftnet_amd.io_edges import (egress_u8, egress_yuv, ingest_u8, ingest_yuv, noise_hist_bands_yuv, noise_hist_pairs_bands_yuv, noise_hist_pairs_yuv,  # noqa: E402
+                                   noise_hist_yuv, noise_map_level, rowcol_sums_yuv, thumb_yuv, yuv_fmt)
 
 
 def summary(v):
@@ -64,6 +66,7 @@ def kernels(a):
     dst = torch.empty_like(pay)
     thumbs = torch.empty((T, (H + 7) // 8, (W + 7) // 8), dtype=torch.uint16, device="cuda")
     hists = torch.empty((T, 511), dtype=torch.uint32, device="cuda")
+    pairs = torch.empty((T - 1, 1021), dtype=torch.uint32, device="cuda")
     pay_noisy = egress_yuv((rgb + torch.randn(rgb.shape, device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * (10.0 / 255)).clamp(0, 1), fmt, H, W)
     fmt10, fmt444 = yuv_fmt(10, L.SN_YUV_420_LEFT, L.SN_YUV_BT709, L.SN_YUV_LIMITED), yuv_fmt(10, L.SN_YUV_444, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
     dst10 = torch.empty((T, fmt10.frame_bytes(H, W)), dtype=torch.uint8, device="cuda")
@@ -85,6 +88,8 @@ def kernels(a):
         "thumb_yuv": lambda: thumb_yuv(pay, fmt, H, W, out=thumbs),
         "noise_hist_yuv": lambda: noise_hist_yuv(pay, fmt, H, W, out=hists),                 # a blurred clip: the mass sits in bins 0 .. 2
         "noise_hist_yuv_sigma10": lambda: noise_hist_yuv(pay_noisy, fmt, H, W, out=hists),   # spread over the first few dozen bins
+        "noise_hist_pairs_yuv": lambda: noise_hist_pairs_yuv(pay, fmt, H, W, out=pairs),     # the same payloads: 20 frames, 19 pairs
+        "noise_hist_pairs_yuv_sigma10": lambda: noise_hist_pairs_yuv(pay_noisy, fmt, H, W, out=pairs),
         "ingest_u8_bf16": lambda: ingest_u8(u8, torch.bfloat16),
         "egress_yuv_bf16": lambda: egress_yuv(out_bf, fmt, H, W, dst=dst),
         "egress_u8_bf16": lambda: egress_u8(out_bf),
@@ -192,31 +197,33 @@ def sigma(a):
     net = restore.load_net("denoise_small", "synthetic", "bf16")
     seen = {}
 
-    def run(sig):
-        vr = restore.VideoRestorer(net, one_len, sigma=sig, pipeline=True)
+    def run(sig, estimator="spatial"):
+        vr = restore.VideoRestorer(net, one_len, sigma=sig, pipeline=True, sigma_estimator=estimator)
         stamps = []
         t0 = time.perf_counter()
         for i, p in enumerate(vr.restore(iter(frames), fmt, H, W)):
             if (i + 1) % one_len == 0:
                 stamps.append(time.perf_counter())
         total = time.perf_counter() - t0
-        seen[str(sig)] = vr.stats["window_sigma"]
+        seen[str(sig) if estimator == "spatial" else estimator] = vr.stats["window_sigma"]
         gaps = [(b - c) * 1e3 for b, c in zip(stamps[1:], stamps[:-1])]
         return {"total_s": total, "window_wall_ms": gaps[1:], "window_forward_ms": vr.stats["window_forward_ms"][2:]}
 
     run(10.0)                                                                        # warm-up: code objects, engine buffers
     run("auto")
-    runs = {"fixed": [], "auto": []}
+    run("auto", "min")
+    runs = {"fixed": [], "auto": [], "auto_min": []}
     for _ in range(a.runs):
         runs["fixed"].append(run(10.0))
         runs["auto"].append(run("auto"))
+        runs["auto_min"].append(run("auto", "min"))
     res = {}
     for k, rs in runs.items():
         res[k] = {"window_wall_ms": summary([g for r in rs for g in r["window_wall_ms"]]),
                   "window_wall_ms_per_run": [round(statistics.median(r["window_wall_ms"]), 2) for r in rs],
                   "window_forward_ms": summary([g for r in rs for g in r["window_forward_ms"]]), "total_s": [round(r["total_s"], 3) for r in rs]}
     print(json.dumps({"part": "sigma", "variant": "denoise_small", "dtype": "bf16", "one_len": one_len, "windows": nwin, "size": [H, W], "runs": a.runs,
-                      "window_sigma_auto": [round(s, 3) for s in seen["auto"]], **res}))
+                      "window_sigma_auto": [round(s, 3) for s in seen["auto"]], "window_sigma_auto_min": [round(s, 3) for s in seen["min"]], **res}))
 
 
 def nlf_kernels(a):
@@ -230,6 +237,8 @@ def nlf_kernels(a):
     nm = torch.empty((1, T, 1, H, W), dtype=torch.bfloat16, device="cuda")
     hists = torch.empty((T, 511), dtype=torch.uint32, device="cuda")
     bands = torch.empty((T, 16, 128), dtype=torch.uint32, device="cuda")
+    pairs = torch.empty((T - 1, 1021), dtype=torch.uint32, device="cuda")
+    pair_bands = torch.empty((T - 1, 16, 128), dtype=torch.uint32, device="cuda")
     knots = [(9.0 - 0.4 * b) / 255.0 for b in range(16)]
     cases = {
         "ingest_yuv_bf16": lambda: ingest_yuv(pay, fmt, H, W, H, W, torch.bfloat16, out=x_bf),
@@ -237,6 +246,10 @@ def nlf_kernels(a):
         "noise_hist_yuv_sigma10": lambda: noise_hist_yuv(pay_noisy, fmt, H, W, out=hists),
         "noise_hist_bands_yuv": lambda: noise_hist_bands_yuv(pay, fmt, H, W, out=bands),
         "noise_hist_bands_yuv_sigma10": lambda: noise_hist_bands_yuv(pay_noisy, fmt, H, W, out=bands),
+        "noise_hist_pairs_yuv": lambda: noise_hist_pairs_yuv(pay, fmt, H, W, out=pairs),     # the same payloads: 20 frames, 19 pairs
+        "noise_hist_pairs_yuv_sigma10": lambda: noise_hist_pairs_yuv(pay_noisy, fmt, H, W, out=pairs),
+        "noise_hist_pairs_bands_yuv": lambda: noise_hist_pairs_bands_yuv(pay, fmt, H, W, out=pair_bands),
+        "noise_hist_pairs_bands_yuv_sigma10": lambda: noise_hist_pairs_bands_yuv(pay_noisy, fmt, H, W, out=pair_bands),
         "noise_map_level_bf16": lambda: noise_map_level(pay, fmt, H, W, H, W, knots, torch.bfloat16, out=nm),
         "noise_map_level_bf16_sigma10": lambda: noise_map_level(pay_noisy, fmt, H, W, H, W, knots, torch.bfloat16, out=nm),
     }
