@@ -661,6 +661,34 @@ int sn_yuv_noise_hist_pairs(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_
 int sn_yuv_noise_hist_pairs_bands(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */, uint32_t* dst, int lo, int hi,
                                   int T, int H, int W, void* stream);
 
+/* ---- method noise: the statistics of what a run changed (a new symbol, SN_ABI_VERSION stays 20) ---------------------------------------------------
+ * The report of the video restorer (shiftnet_amd/report.py): if only noise left the picture, input minus output is white in space, independent from
+ * frame to frame, no stronger on edges than on flat areas, and as strong as the noise was.  sn_yuv_diff_stats makes the integer sums those four
+ * measures are computed from on the host.  a (what came in) and b (what was written): T payloads each, of fmt and H x W, laid out as
+ * sn_egress_yuv_mix takes `in` and `dst`; rect == NULL is the whole frame, otherwise the h x w picture of every payload (the rules of
+ * sn_ingest_yuv_rect say which rectangles are legal).  Samples are taken as stored, not masked to the legal codes (a 10-bit payload's words may hold
+ * anything up to 65535).  On the picture's h x w luma samples d(y, x) = b_Y(y, x) - a_Y(y, x); on its chroma planes -- ceil(h / 2) x ceil(w / 2) at
+ * 4:2:0, h x w at 4:4:4 -- du and dv likewise.  A pixel is an EDGE pixel iff e(y, x) >= edge with
+ *   e(y, x) = |b_Y(y, min(x + 1, w - 1)) - b_Y(y, x)| + |b_Y(min(y + 1, h - 1), x) - b_Y(y, x)|
+ * (the written picture, which is the clean one, classifies).  dst[t] holds SN_DIFF_STATS = 16 signed 64-bit integers:
+ *   0, 1, 2     N = h w, sum d, sum d^2
+ *   3, 4        Nx = h (w - 1), sum d(y, x) d(y, x + 1) over x < w - 1
+ *   5, 6        Ny = (h - 1) w, sum d(y, x) d(y + 1, x) over y < h - 1
+ *   7           sum d_t(y, x) d_{t+1}(y, x) with payload t + 1 of the same launch; 0 for the launch's last payload
+ *   8, 9        Ne = the number of edge pixels, sum d^2 over them
+ *   10          Nc = the samples of one chroma plane
+ *   11, 12      sum du, sum du^2
+ *   13, 14      sum dv, sum dv^2
+ *   15          0
+ * dst:[T][16] int64 is OVERWRITTEN, never added to; nothing outside those words is written.  Integer sums accumulated in 64 bit (one product reaches
+ * 65535^2): exact, and the same for every launch geometry and schedule.  a == b is legal and gives zeros beside the counts.
+ * (tests/diff_stats_ref.py restates it in numpy; the kernel equals it word for word.)
+ * SN_EINVAL before anything is launched: a null a, b, dst or fmt; bits not 8 / 10 or an unknown chroma code; a or b at an odd address at 10 bit; dst
+ * not 8-byte aligned; an illegal rectangle; edge < 0; T outside 1 .. 65535; H or W < 1. */
+#define SN_DIFF_STATS 16
+int sn_yuv_diff_stats(const uint8_t* a, const uint8_t* b, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */,
+                      int edge, int64_t* dst /* [T][SN_DIFF_STATS] */, int T, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 // Statistics of the luma plane of planar Y'CbCr payloads, for the decisions the video restorer makes on the host (gfx950).  The payloads are those
-// of csrc/sn_yuv.hip; the chroma planes are not read and of the format only the bit depth decides anything.
+// of csrc/sn_yuv.hip; all but sn_yuv_diff_stats leave the chroma planes unread, and of the format only the bit depth decides anything there.
 //
 //   sn_yuv_thumb  : T payloads -> [T][ceil(H/8)][ceil(W/8)] uint16 sums of the luma codes of every 8 x 8 block (the scene-cut measure of
 //                   shiftnet_amd/scenes.py is computed from these on the host);
@@ -13,7 +13,10 @@
 //   sn_noise_map_level : T payloads and the 16 knots of a noise-level function -> [T][1][Hp][Wp] of the module dtype or float32: the function at the
 //                   low-passed luma of every pixel (bilinear between the means of the 8 x 8 blocks): the denoisers' noise plane; rect or the whole frame;
 //   sn_yuv_rowcol_sums : T payloads -> [T][H] and [T][W] uint32 sums of the luma codes of every row and every column (the letterbox rule of
-//                   shiftnet_amd/picture.py is evaluated on these on the host).
+//                   shiftnet_amd/picture.py is evaluated on these on the host);
+//   sn_yuv_diff_stats : two sets of T payloads, what came in and what was written -> [T][16] int64 sums of their difference in all three planes: its
+//                   moments, its products with the right, lower and next-frame neighbour, its energy on the edges of the written picture (the method-noise
+//                   report of shiftnet_amd/report.py is computed from these on the host); rect or the whole frame.
 //
 // All but the noise map are integer reductions: sums commute, so the results are the same for every launch geometry and every schedule, and the numpy
 // restatements of tests/ equal them exactly.  The noise map is float32 arithmetic with every product and sum rounded separately (contraction is
@@ -479,6 +482,153 @@ __global__ __launch_bounds__(256) void yuv_rowcol_kernel(const uint8_t* __restri
     for (int k = 0; k < 8; ++k)
         if (k < n) atomicAdd(&cols[(size_t)t * W + x0 + k], (uint32_t)acc[k]);
 }
+// ---- method noise: sums of the difference of two sets of payloads ---------------------------------------------------------------------------
+// d = b - a of the luma and of both chroma planes, and the sums include/shiftnet_hip.h lists (sn_yuv_diff_stats): of d, of d^2, of the products of d with its
+// right, lower and next-frame neighbour, and of d^2 over the pixels that b calls an edge.  blockIdx.y is the payload; payload t + 1 is read by the
+// workgroups of t (for the temporal product) and by its own.  A lane owns a unit of 8 x DS_STRIP luma samples: per row one 8 B / 16 B load of a and of
+// b where the ADDRESS allows it, element-wise otherwise and on the right edge, plus the one sample right of the unit; it walks down the strip and keeps
+// the row below in registers, so that a row is loaded once per unit (and the first row of the next strip twice).  Neighbouring lanes own neighbouring
+// units of a strip; a workgroup walks units gridDim.x * 256 apart.  The chroma planes follow in units of the same shape, U and V together.  Every lane
+// accumulates in 64 bit -- one product reaches 65535^2 when a 10-bit payload holds arbitrary words, so a 32-bit partial sum is wrong after two
+// pixels -- then the 11 sums are added across the wave (cross-lane moves, no LDS), across the four waves through 4 x 16 words of LDS, and the
+// workgroup adds each non-zero sum to dst with ONE 64-bit vector atomic.  The first workgroup of a payload adds the four counts the same way.  Integer
+// sums commute (a negative sum is added modulo 2^64): the result is the same for every geometry and every schedule.
+constexpr int DS_STRIP = 8;
+
+__device__ __forceinline__ long long wave_sum_ll(long long x) {             // the sum over the 64 lanes, in every lane
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
+    return x;
+}
+
+// n (1..8) samples of one row of a and of b from element o on: d[k] = b - a and bb[k] = b, both 0 for k >= n; right: the sample at o + 8 exists, then
+// dR and bR are its difference and its b, otherwise 0
+template <int ESZ>
+__device__ __forceinline__ void diff_row(const uint8_t* ap, const uint8_t* bp, size_t o, int n, bool right, int* d, int* bb, int& dR, int& bR) {
+    int av[8];
+    if (n == 8) {
+        ldn<ESZ, 8>(ap, o, av);
+        ldn<ESZ, 8>(bp, o, bb);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {                                     // samples o .. o + n - 1 exist; the others are not read
+            const bool in = k < n;
+            av[k] = in ? ld1<ESZ>(ap, o + k) : 0;
+            bb[k] = in ? ld1<ESZ>(bp, o + k) : 0;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) d[k] = bb[k] - av[k];
+    bR = right ? ld1<ESZ>(bp, o + 8) : 0;
+    dR = right ? bR - ld1<ESZ>(ap, o + 8) : 0;
+}
+
+template <int ESZ>
+__global__ __launch_bounds__(256) void yuv_diff_stats_kernel(const uint8_t* a, const uint8_t* b, unsigned long long* dst, const YuvGeo G, int ch, int cw,
+                                                           int edge, int T) {
+    __shared__ long long part[4][SN_DIFF_STATS];
+    const int tid = threadIdx.x, t = blockIdx.y;
+    const int h = G.h, w = G.w;
+    const uint8_t* af = a + (size_t)t * G.frame_bytes;
+    const uint8_t* bf = b + (size_t)t * G.frame_bytes;
+    const bool next = t + 1 < T;                                          // payload t + 1 exists: only then is anything beyond payload t read
+    long long s1 = 0, s2 = 0, sx = 0, sy = 0, st = 0, ne = 0, s2e = 0, su = 0, su2 = 0, sv = 0, sv2 = 0;
+    {
+        const uint8_t* ay = af + G.oy;
+        const uint8_t* by = bf + G.oy;
+        const int ux = (w + 7) >> 3, units = ux * ((h + DS_STRIP - 1) / DS_STRIP);
+        for (int u = blockIdx.x * 256 + tid; u < units; u += gridDim.x * 256) {
+            const int sr = u / ux, x0 = (u - sr * ux) * 8, y0 = sr * DS_STRIP, y1 = imin(y0 + DS_STRIP, h);
+            const int n = imin(8, w - x0);                                // >= 1
+            const bool right = x0 + 8 < w;                                // n < 8 is the picture's right edge: no sample right of the unit
+            int d[8], bb[8], dR, bR;
+            diff_row<ESZ>(ay, by, (size_t)y0 * G.py + x0, n, right, d, bb, dR, bR);
+#pragma unroll 1
+            for (int y = y0; y < y1; ++y) {
+                const size_t o = (size_t)y * G.py + x0;
+                int dn[8], bn[8], dRn = 0, bRn = 0, dt[8];
+                if (y + 1 < h) {
+                    diff_row<ESZ>(ay, by, o + G.py, n, right, dn, bn, dRn, bRn);
+                } else {                                                  // the last row: no product, and the row below is the row itself
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) { dn[k] = 0; bn[k] = bb[k]; }
+                }
+                if (next) {
+                    int bt[8], dRt, bRt;
+                    diff_row<ESZ>(ay + G.frame_bytes, by + G.frame_bytes, o, n, false, dt, bt, dRt, bRt);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) dt[k] = 0;
+                }
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const int dk = d[k];                                  // 0 beyond the picture, and so is every product with it
+                    const int dr = k < 7 ? d[k + 1] : dR;
+                    const int br = k < 7 ? (k + 1 < n ? bb[k + 1] : bb[k]) : (right ? bR : bb[k]);       // min(x + 1, w - 1)
+                    const int eh = br - bb[k], ev = bn[k] - bb[k];
+                    const int e = (eh < 0 ? -eh : eh) + (ev < 0 ? -ev : ev);
+                    const long long q = (long long)dk * dk;
+                    s1 += dk;
+                    s2 += q;
+                    sx += (long long)dk * dr;
+                    sy += (long long)dk * dn[k];
+                    st += (long long)dk * dt[k];
+                    if (k < n && e >= edge) { ne += 1; s2e += q; }
+                }
+#pragma unroll
+                for (int k = 0; k < 8; ++k) { d[k] = dn[k]; bb[k] = bn[k]; }
+                dR = dRn; bR = bRn;
+            }
+        }
+    }
+    {
+        const uint8_t* au = af + G.ou;
+        const uint8_t* bu = bf + G.ou;
+        const uint8_t* av = af + G.ov;
+        const uint8_t* bv = bf + G.ov;
+        const int ux = (cw + 7) >> 3, units = ux * ((ch + DS_STRIP - 1) / DS_STRIP);
+        for (int u = blockIdx.x * 256 + tid; u < units; u += gridDim.x * 256) {
+            const int sr = u / ux, x0 = (u - sr * ux) * 8, y0 = sr * DS_STRIP, y1 = imin(y0 + DS_STRIP, ch);
+            const int n = imin(8, cw - x0);
+#pragma unroll 1
+            for (int y = y0; y < y1; ++y) {
+                const size_t o = (size_t)y * G.pc + x0;
+                int du[8], dv[8], x[8], dR, bR;
+                diff_row<ESZ>(au, bu, o, n, false, du, x, dR, bR);
+                diff_row<ESZ>(av, bv, o, n, false, dv, x, dR, bR);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    su += du[k];
+                    su2 += (long long)du[k] * du[k];
+                    sv += dv[k];
+                    sv2 += (long long)dv[k] * dv[k];
+                }
+            }
+        }
+    }
+    // the words of dst[t] in their order; the counts are not sums of the lanes
+    long long v[SN_DIFF_STATS] = {0, s1, s2, 0, sx, 0, sy, st, ne, s2e, 0, su, su2, sv, sv2, 0};
+#pragma unroll
+    for (int i = 0; i < SN_DIFF_STATS; ++i) {
+        if (i == 0 || i == 3 || i == 5 || i == 10 || i == 15) continue;
+        v[i] = wave_sum_ll(v[i]);
+    }
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < SN_DIFF_STATS; ++i) part[tid >> 6][i] = v[i];
+    }
+    __syncthreads();
+    if (tid < SN_DIFF_STATS) {
+        long long tot = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+        if (blockIdx.x == 0) {
+            if (tid == 0) tot = (long long)h * w;
+            if (tid == 3) tot = (long long)h * (w - 1);
+            if (tid == 5) tot = (long long)(h - 1) * w;
+            if (tid == 10) tot = (long long)ch * cw;
+        }
+        if (tot) atomicAdd(&dst[(size_t)t * SN_DIFF_STATS + tid], (unsigned long long)tot);
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -603,6 +753,26 @@ int sn_yuv_rowcol_sums(const uint8_t* src, const sn_yuv_fmt* fmt, uint32_t* rows
     if (hipMemsetAsync(cols, 0, (size_t)T * W * sizeof(uint32_t), s) != hipSuccess) return sn_check_launch();
     const dim3 block(64, 4), grid((W + 511) / 512, (H + 4 * ROWCOL_STRIP - 1) / (4 * ROWCOL_STRIP), T);
     with_esz(fmt, [&](auto esz) { hipLaunchKernelGGL((yuv_rowcol_kernel<esz()>), grid, block, 0, s, src, rows, cols, H, W, fb); });
+    return sn_check_launch();
+}
+
+int sn_yuv_diff_stats(const uint8_t* a, const uint8_t* b, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, int edge, int64_t* dst, int T, int H, int W,
+                      void* stream) {
+    sn_clear_error();
+    if (!valid_payloads(a, fmt, T, H, W) || !b || !aligned_payload(fmt, b) || !dst || ((uintptr_t)dst & 7) || edge < 0) return SN_EINVAL;
+    YuvGeo G;
+    if (!make_geo(fmt, H, W, rect, &G)) return SN_EINVAL;
+    const bool sub = fmt->chroma != SN_YUV_444;
+    const int ch = sub ? (G.h + 1) / 2 : G.h, cw = sub ? (G.w + 1) / 2 : G.w;      // the picture's chroma planes (a legal rectangle shares no chroma sample)
+    const long long units = (long long)((G.w + 7) / 8) * ((G.h + DS_STRIP - 1) / DS_STRIP);      // the chroma planes have no more
+    if (units > 0x7fffffffLL - 1024 * 256) return SN_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(dst, 0, (size_t)T * SN_DIFF_STATS * sizeof(int64_t), s) != hipSuccess) return sn_check_launch();      // dst is overwritten, not added to
+    const long long wgs = (units + 255) / 256;                             // one unit (64 pixels) per lane: a 720p frame is 57 workgroups
+    const dim3 block(256), grid(wgs < 1024 ? (int)wgs : 1024, T);
+    with_esz(fmt, [&](auto esz) {
+        hipLaunchKernelGGL((yuv_diff_stats_kernel<esz()>), grid, block, 0, s, a, b, (unsigned long long*)dst, G, ch, cw, edge, T);
+    });
     return sn_check_launch();
 }
 

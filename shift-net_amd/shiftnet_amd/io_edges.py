@@ -15,6 +15,8 @@ the statistics of the same payloads' luma (csrc/sn_yuv_stats.hip), each for one 
                temporal noise estimate (shiftnet_amd/noise.py);
 ``noise_map_level``: payloads + the 16 knots of such a function -> the denoisers' noise plane;
 ``rowcol_sums_yuv``: uint32 sums of the luma codes of every row and of every column, for the letterbox rule (shiftnet_amd/picture.py);
+``diff_stats_yuv``: int64 sums of the difference of two sets of payloads, what came in and what was written, for the method-noise report
+               (shiftnet_amd/report.py);
 ``rect=(x0, y0, w, h)``, where a function takes it (all but ``thumb_yuv`` and ``rowcol_sums_yuv``), restricts it to that picture of the stream, with
                the result of the cropped stream;
 ``egress_u8``  == the per-frame ``clamp(0,1) * 255`` -> skimage PSNR(data_range=255) against the uint8 ground truth
@@ -312,3 +314,24 @@ def rowcol_sums_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, o
         L.check(L.load().sn_yuv_rowcol_sums(payload_u8.data_ptr(), fmt, rows.data_ptr(), cols.data_ptr(), T, H, W,
                                             torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_rowcol_sums")
     return rows, cols
+
+
+def diff_stats_yuv(ref: torch.Tensor, out: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, rect=None, edge: int = 0,
+                   out_sums: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ref (what came in) and out (what was written): [T, frame_bytes] uint8 on a HIP device each, the same format and size; they may be the same
+    tensor -> int64 [T, 16]: per payload the exact sums of d = out - ref that include/shiftnet_hip.h lists under sn_yuv_diff_stats (the counts; the sums
+    of d and d^2 of the luma; of its products with the right, the lower and the next payload's sample; the count and the sum of d^2 of the pixels whose
+    gradient in ``out`` is at least ``edge`` codes; the sums of d and d^2 of both chroma planes).  ``rect=(x0, y0, w, h)``: the sums of that picture of
+    the stream.  ``out_sums``: a tensor of that shape to overwrite.  report.frame_measures turns a row into numbers."""
+    T, dev = _payload(ref, fmt, H, W)
+    assert _payload(out, fmt, H, W) == (T, dev)
+    edge = int(edge)
+    if edge < 0:
+        raise ValueError(f"edge must be >= 0, got {edge!r}")
+    y = out_sums if out_sums is not None else torch.empty((T, L.SN_DIFF_STATS), dtype=torch.int64, device=dev)
+    assert tuple(y.shape) == (T, L.SN_DIFF_STATS) and y.dtype == torch.int64 and y.is_contiguous() and y.device == dev
+    r = None if rect is None else _rect(rect, fmt, H, W)
+    with torch.cuda.device(dev):
+        L.check(L.load().sn_yuv_diff_stats(ref.data_ptr(), out.data_ptr(), fmt, r, edge, y.data_ptr(), T, H, W,
+                                           torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_diff_stats")
+    return y

@@ -1,0 +1,189 @@
+"""Method noise of a run of the video restorer: numbers about what it changed, per written frame (numpy only, no torch).
+
+The classical test of a denoiser is its method noise, input minus output.  If only noise left the picture, that difference is white in space,
+independent from frame to frame, no stronger on edges than on flat areas, and as strong as the noise was.  If detail left with it, the difference is
+correlated: with its neighbours, with the next frame (static texture is the same in both) and with the edges of the picture.
+
+The sums are what ``sn_yuv_diff_stats`` (csrc/sn_yuv_stats.hip) writes per frame for d = written - input of the luma and of both chroma planes:
+``SUMS`` names its 16 integers.  From one row, in float64 on exact integers (so the device's sums and a host restatement give the same floats):
+
+  m = S1 / N;  var = S2 / N - m^2                       luma code units of the format written; the numerator N S2 - S1^2 is formed in integers
+  mean_y = m / c;  rms_y = sqrt(S2 / N) / c             c = 2^(bits - 8): in 8-bit code units
+  removed_sigma = sqrt(max(var, 0)) / (g s)             g, s of noise.py (``luma_gain``, ``code_scale``): the sigma of i.i.d. noise on 8-bit R'G'B' with
+                                                        this much luma variance -- the unit of the restorer's ``sigma``
+  rho_x = (Sx / Nx - m^2) / var;  rho_y likewise        the correlation of d with its right and its lower neighbour
+  edge_share = Ne / N;  edge_ratio = (S2e / Ne) / ((S2 - S2e) / (N - Ne))        the mean of d^2 on the edge pixels over that on the others
+  mean_u, rms_u, mean_v, rms_v                          as mean_y and rms_y, of the chroma planes
+  rho_t = (St / N - m_t m_t1) / sqrt(var_t var_t1)      the correlation with the next frame's d (``pair_rho``)
+
+A measure whose denominator is zero is nan.  A noise-only removal reads rho_x ~ rho_y ~ rho_t ~ 0, edge_ratio ~ 1 and removed_sigma ~ the sigma
+the window was restored with.  ``removed_sigma`` is not corrected for rounding: the output's rounding to codes adds 1/12 code^2 to var, a TPDF dither
+adds its own noise (about 1/4 code^2), and with an ``amount`` below 1 only that share of the correction was written.  **The interpretation is
+unvalidated on real footage**: the deblur variants change edges by design; the edge threshold is a guess; at 4:2:0 the luma noise of real footage
+need not be white to begin with.
+
+``format_report`` / ``parse_report`` are the file of one line per written frame.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass, fields
+from typing import Dict, Iterable, List, Optional, Sequence
+
+import numpy as np
+
+from .noise import code_scale, luma_gain
+
+SUMS = ("N", "S1", "S2", "Nx", "Sx", "Ny", "Sy", "St", "Ne", "S2e", "Nc", "Su", "Su2", "Sv", "Sv2", "zero")      # the 16 words of sn_yuv_diff_stats
+NAN = float("nan")
+
+
+def _same(a, b) -> bool:
+    return a == b or (isinstance(a, float) and isinstance(b, float) and math.isnan(a) and math.isnan(b))
+
+
+@dataclass(eq=False)
+class FrameReport:
+    """One written frame: where it was (``frame`` in the stream, ``window`` in the order restored), the sigma its window was restored with (None: a
+    deblur variant) and the measures of the module's docstring.  Equality takes nan for equal to nan: two reports of the same sums are equal."""
+    frame: int = 0
+    window: int = 0
+    sigma: Optional[float] = None
+    m: float = NAN
+    var: float = NAN
+    removed_sigma: float = NAN
+    mean_y: float = NAN
+    rms_y: float = NAN
+    rho_x: float = NAN
+    rho_y: float = NAN
+    edge_share: float = NAN
+    edge_ratio: float = NAN
+    mean_u: float = NAN
+    rms_u: float = NAN
+    mean_v: float = NAN
+    rms_v: float = NAN
+    rho_t: float = NAN
+
+    def __eq__(self, other) -> bool:
+        if not isinstance(other, FrameReport):
+            return NotImplemented
+        return all(_same(getattr(self, f.name), getattr(other, f.name)) for f in fields(self))
+
+    __hash__ = None
+
+
+COLUMNS = tuple(f.name for f in fields(FrameReport))
+MEASURES = COLUMNS[3:]                                        # every float column
+
+
+def _ratio(num: int, den: int) -> float:
+    """num / den of two integers, correctly rounded; nan for den == 0."""
+    return num / den if den else NAN
+
+
+def _ints(sums) -> List[int]:
+    s = [int(v) for v in np.asarray(sums).reshape(-1)]
+    if len(s) != len(SUMS):
+        raise ValueError(f"a row of sn_yuv_diff_stats has {len(SUMS)} words, got {len(s)}")
+    return s
+
+
+def frame_measures(sums, bits: int, matrix: int, range_: int) -> FrameReport:
+    """One row of ``sn_yuv_diff_stats`` (the format written: ``bits``, ``matrix``, ``range_``) -> a FrameReport with frame 0, window 0, no sigma and
+    no rho_t.  ``removed_sigma`` is uncorrected: the output's rounding adds 1/12 code^2 to the variance and a TPDF dither its own noise."""
+    N, S1, S2, Nx, Sx, Ny, Sy, _, Ne, S2e, Nc, Su, Su2, Sv, Sv2, _ = _ints(sums)
+    c = float(1 << (bits - 8))
+    r = FrameReport()
+    r.m, r.var = _ratio(S1, N), _ratio(N * S2 - S1 * S1, N * N)
+    r.mean_y, r.rms_y = r.m / c, math.sqrt(_ratio(S2, N)) / c if N else NAN
+    r.removed_sigma = math.sqrt(max(r.var, 0.0)) / (luma_gain(matrix) * code_scale(bits, range_)) if N else NAN
+    vnum = N * S2 - S1 * S1                                   # var = vnum / N^2, cov_x = (Sx N^2 - S1^2 Nx) / (Nx N^2): rho_x = that / var
+    r.rho_x = _ratio(Sx * N * N - S1 * S1 * Nx, Nx * vnum)
+    r.rho_y = _ratio(Sy * N * N - S1 * S1 * Ny, Ny * vnum)
+    r.edge_share = _ratio(Ne, N)
+    r.edge_ratio = _ratio(S2e * (N - Ne), Ne * (S2 - S2e))
+    r.mean_u, r.mean_v = _ratio(Su, Nc) / c, _ratio(Sv, Nc) / c
+    r.rms_u, r.rms_v = (math.sqrt(_ratio(Su2, Nc)) / c, math.sqrt(_ratio(Sv2, Nc)) / c) if Nc else (NAN, NAN)
+    return r
+
+
+def pair_rho(sums_t, sums_t1) -> float:
+    """The correlation of a frame's d with the next frame's: both rows of one launch, so that ``sums_t`` holds St.  nan when there is no next frame
+    (None), the two are of different pictures, or either has no variance."""
+    if sums_t is None or sums_t1 is None:
+        return NAN
+    a, b = _ints(sums_t), _ints(sums_t1)
+    N = a[0]
+    if N == 0 or b[0] != N:
+        return NAN
+    va, vb = N * a[2] - a[1] * a[1], N * b[2] - b[1] * b[1]   # N^2 var of each
+    if va <= 0 or vb <= 0:
+        return NAN
+    return (a[7] * N - a[1] * b[1]) / math.sqrt(va * vb)      # (St / N - m_t m_t1) / sqrt(var_t var_t1), the N^2 cancelled
+
+
+def frames_report(frame_sums: Sequence, windows: Sequence[int], sigmas: Sequence[Optional[float]], bits: int, matrix: int, range_: int
+                  ) -> List[FrameReport]:
+    """The report of a run: ``frame_sums[i]`` is the row of written frame i, ``windows[i]`` the window it was restored in and ``sigmas[i]`` that
+    window's sigma (None: none).  rho_t of a frame is ``pair_rho`` with the next frame where that one lies in the same window -- its St was summed
+    in the same launch -- and nan elsewhere."""
+    out = []
+    n = len(frame_sums)
+    for i in range(n):
+        r = frame_measures(frame_sums[i], bits, matrix, range_)
+        r.frame, r.window, r.sigma = i, int(windows[i]), (None if sigmas[i] is None else float(sigmas[i]))
+        r.rho_t = pair_rho(frame_sums[i], frame_sums[i + 1]) if i + 1 < n and windows[i + 1] == windows[i] else NAN
+        out.append(r)
+    return out
+
+
+def summarize(frames: Iterable[FrameReport]) -> Dict[str, float]:
+    """The median of every measure over the frames that have one (nan where none has)."""
+    frames = list(frames)
+    out = {}
+    for name in MEASURES:
+        v = [getattr(f, name) for f in frames]
+        v = [x for x in v if not math.isnan(x)]
+        out[name] = float(np.median(v)) if v else NAN
+    return out
+
+
+def summary_line(summary: Dict[str, float]) -> str:
+    """The medians a reader looks at first, for a log."""
+    return ", ".join(f"{k} {summary[k]:.3f}" for k in ("removed_sigma", "rho_x", "rho_y", "rho_t", "edge_ratio", "edge_share"))
+
+
+def _word(v) -> str:
+    if v is None:
+        return "-"
+    return repr(float(v)) if isinstance(v, float) else str(int(v))     # repr of a float reads back to the same float; nan reads back as nan
+
+
+def format_report(frames: Iterable[FrameReport], how: str = "") -> str:
+    """The report file: '#' header lines that name the columns, one line per written frame (sigma '-' where the window had none), and the medians of
+    ``summarize`` as the last line, '# median'.  Floats are written so that ``parse_report`` reads back equal reports."""
+    frames = list(frames)
+    med = summarize(frames)
+    lines = ["# method noise: written minus input, one line per written frame" + (f" ({how})" if how else ""),
+             "# m, var: luma codes of the format written; sigma, removed_sigma: 8-bit R'G'B' codes; mean_*, rms_*: 8-bit codes; rho_t: to the next frame",
+             "# " + " ".join(COLUMNS)]
+    lines += [" ".join(_word(getattr(f, c)) for c in COLUMNS) for f in frames]
+    lines.append("# median - - - " + " ".join(_word(med[c]) for c in MEASURES))
+    return "\n".join(lines) + "\n"
+
+
+def parse_report(text: str) -> List[FrameReport]:
+    """The frames of a report file ('#' lines are comments, the medians among them: ``summarize`` makes them again)."""
+    out = []
+    for ln, line in enumerate(text.splitlines(), 1):
+        body = line.split("#", 1)[0].split()
+        if not body:
+            continue
+        if len(body) != len(COLUMNS):
+            raise ValueError(f"line {ln}: {len(COLUMNS)} columns expected, got {len(body)}")
+        try:
+            vals = [int(body[0]), int(body[1]), None if body[2] == "-" else float(body[2])] + [float(w) for w in body[3:]]
+        except ValueError:
+            raise ValueError(f"line {ln}: not a report line: {line!r}") from None
+        out.append(FrameReport(*vals))
+    return out

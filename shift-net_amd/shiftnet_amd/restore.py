@@ -38,6 +38,11 @@ Amount and the removed view (``amount``, ``view``; both off by default): ``amoun
 result's, separately for luma and chroma -- the fallback when the restoration is too strong; ``view="removed"`` writes input minus result around
 mid-grey, to see whether detail leaves with the noise.  Both happen in the egress, in the code domain, from the payloads the window has uploaded
 anyway (``sn_egress_yuv_mix``): amount 0 is the input byte for byte.  The blend is linear in the codes, not perceptual.
+
+Method-noise report (``report``, off by default): numbers about what the run changed, per written frame -- whether input minus output is white in
+space, independent from frame to frame, no stronger on edges than elsewhere, and as strong as the sigma the window was restored with.  Exact integer
+sums of the two sets of payloads the window holds on the device anyway once the egress has run (``sn_yuv_diff_stats``), float64 on the host
+(shiftnet_amd/report.py).  It changes no byte written.  What the numbers mean on real footage nobody has validated.
 """
 from __future__ import annotations
 
@@ -50,8 +55,8 @@ import numpy as np
 
 from .restore_cli import amount_arg, main, make_parser, picture_arg, sigma_arg  # noqa: F401 -- the command line (restore_cli.py), reached through this module
 from .windows import (DITHERS, FUTURE, PAST, PerWindow, _Frames, _SceneFrames, _Thread, amount_form, noise_model_form, pad_multiple,  # noqa: F401
-                      padded_size, picture_form, plan_output, plan_scene_windows, plan_windows, reflect_index, scene_cuts_form, sigma_estimator_form,
-                      sigma_form, window_indices)
+                      padded_size, picture_form, plan_output, plan_scene_windows, plan_windows, reflect_index, report_form, scene_cuts_form,
+                      sigma_estimator_form, sigma_form, window_indices)
 
 VARIANTS = {"deblur": "gshift_deblur1", "deblur_small": "gshift_deblur2", "denoise": "gshift_denoise1", "denoise_small": "gshift_denoise2"}
 
@@ -100,7 +105,8 @@ class _Slot:
         self.used = False                                         # in this restore(): a window has gone through the slot
         self.noise = self.bands = self.sums = None                # _Stat: the window's histograms, band histograms, row and column sums
         self.pairs = self.pair_bands = None                       # _Stat: the histograms and band histograms of the window's frame pairs
-        self.dev_ref = None                                       # a mix with another format out: the window's input payloads in the format written
+        self.dev_ref = None                                       # a mix or a report with another format out: the window's input payloads in the format written
+        self.report = None                                        # _Stat: the sums of written minus input of the window's own frames
 
 
 class _Run:
@@ -117,7 +123,11 @@ class _Run:
         self.window_sigma_spatial: List = []                      # sigma_estimator other than "spatial": the two estimates before the rule and the clamp
         self.window_sigma_temporal: List = []
         self.window_pair_sigma: List = []
-        self.launches = {"noise": 0, "nlf": 0, "nlf_map": 0, "picture": 0, "thumb": 0, "noise_pairs": 0, "nlf_pairs": 0}
+        self.launches = {"noise": 0, "nlf": 0, "nlf_map": 0, "picture": 0, "thumb": 0, "noise_pairs": 0, "nlf_pairs": 0, "report": 0}
+        self.frame_sums: List = []                                # report: the 16 sums of every frame handed out, the window it came from, that window's sigma
+        self.frame_window: List[int] = []
+        self.frame_sigma: List = []
+        self.collected = 0                                        # windows handed out
         self.src = None                                           # the frame source
 
 
@@ -251,12 +261,26 @@ class VideoRestorer:
     pair, which the median over the pairs takes.  ``stats`` then also has ``sigma_estimator``, ``window_sigma_spatial`` and ``window_sigma_temporal`` (the
     two estimates of every window before the rule and the clamp; None where no pair has one), ``window_pair_sigma`` (per window, one entry per pair, None
     allowed), ``noise_pairs_launches`` and, with ``"level"``, ``nlf_pairs_launches``; ``window_sigma``, ``window_frame_sigma`` and ``window_nlf`` keep their
-    meaning: what the window was restored with, the per-frame spatial values, the curve used."""
+    meaning: what the window was restored with, the per-frame spatial values, the curve used.
+    report: False -- today's launches, bytes and stats keys; True -- behind every window's egress one more launch (``sn_yuv_diff_stats``, main stream)
+    sums d = written - input over the window's own frames: the payloads written against the input frames in the format written -- the payloads read, or
+    with ``out_format`` the input converted as ``amount`` defines it (``egress(out format, ingest_float32(in format, frame))``, undithered) -- inside the
+    window's rectangle under ``picture``.  The sums are exact integers, the same with ``pipeline`` on and off, and no byte written changes.
+    ``stats["frame_sums"]`` is one list of 16 ints per written frame (report.SUMS), ``stats["frame_report"]`` one report.FrameReport per frame: the
+    luma difference's mean, rms and ``removed_sigma`` (its standard deviation as the sigma of i.i.d. noise on 8-bit R'G'B', the unit of ``sigma``), its
+    correlation with the right and the lower neighbour (``rho_x``, ``rho_y``) and with the next frame's difference (``rho_t``; nan where the next frame
+    lies in another window), the share of edge pixels and the mean of d^2 on them over that elsewhere (``edge_ratio``), the chroma planes' mean and rms;
+    ``stats["report_summary"]`` their medians, ``stats["report_launches"]`` the launches.  A pixel is an edge where the written luma's gradient,
+    |right - here| + |below - here|, is at least ``report_edge`` 8-bit codes (finite, >= 0; **the default of 16 is a guess nobody has tuned**).  The
+    report describes the stream that was written: with ``amount`` the blended one, with ``dither`` the dither is part of d; ``view="removed"`` with
+    ``report=True`` is a ValueError.  A noise-only removal reads rho_x ~ rho_y ~ rho_t ~ 0, edge_ratio ~ 1, removed_sigma ~ sigma.  **Unvalidated on real
+    footage**: the deblur variants change edges by design, and at 4:2:0 the luma noise of real footage need not be white to begin with."""
 
     def __init__(self, net, one_len: int, sigma=None, pipeline: bool = True, scene_cuts=None,
                  cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0),
                  picture=None, bar_level: float = 1.0, out_format=None, dither=None, dither_seed: int = 0, noise_model=None,
-                 amount=None, view=None, removed_gain: float = 1.0, sigma_estimator: str = "spatial") -> None:
+                 amount=None, view=None, removed_gain: float = 1.0, sigma_estimator: str = "spatial", report: bool = False,
+                 report_edge: float = 16.0) -> None:
         import torch
         from .lib import YuvFmt
         from .noise import check_clamp
@@ -265,6 +289,7 @@ class VideoRestorer:
         self.out_format = out_format
         # the mix of the last egress (None: the code path without any of it), the amounts and the view as stats reports them
         self.mix, self.amount, self.view = amount_form(amount, view, removed_gain)
+        self.report, self.report_edge = report_form(report, report_edge, self.view)      # False: the code path without any of it
         self.net, self.one_len, self.pipeline = net, int(one_len), bool(pipeline)
         if self.one_len < 1:
             raise ValueError("one_len must be >= 1")
@@ -325,7 +350,8 @@ class VideoRestorer:
         self.slots = [_Slot(torch, dev, self.dtype, tin, tout, self.fb, self.ofb, self.hp * self.wp) for _ in range(2)]
         # a picture in another format than was read: the window's whole frames as float32 on their way from one format to the other (main stream only)
         # ... and a mix in another format than was read: the same conversion gives the input side of the mix, one buffer of payloads per slot
-        ref = self.convert and self.mix is not None
+        # ... and so does a report: the input side of its difference
+        ref = self.convert and (self.mix is not None or self.report)
         self.conv32 = torch.empty(tout * 3 * h * w, dtype=torch.float32, device=dev) if self.convert and (self.picture_mode != "full" or ref) else None
         for s in self.slots:
             s.dev_ref = torch.empty((tout, self.ofb), dtype=torch.uint8, device=dev) if ref else None
@@ -347,6 +373,10 @@ class VideoRestorer:
                     s.pair_bands = _Stat(torch, dev, "nlf_pairs", tin - 1, [(NLF_BANDS, nlf_bins(fmt.bits))])
             if self.picture_mode == "auto":
                 s.sums = _Stat(torch, dev, "picture", tin, [(h,), (w,)])
+            if self.report:                                       # one row per frame the window writes
+                from .lib import SN_DIFF_STATS
+                s.report = _Stat(torch, dev, "report", tout, [(SN_DIFF_STATS,)], torch.int64)
+        self.report_code_edge = int(round(self.report_edge * (1 << (ofmt.bits - 8))))      # in codes of the format written
 
     def _size(self, rect) -> Tuple[int, int, int, int]:
         """(h, w, padded h, padded w) of what a window with picture ``rect`` feeds the network."""
@@ -459,7 +489,7 @@ class VideoRestorer:
 
     def _run(self, slot: _Slot, t: int, main) -> int:
         """Forward + egress on the main stream, copy back on the output stream."""
-        from .io_edges import egress_yuv, ingest_yuv, noise_map_level
+        from .io_edges import diff_stats_yuv, egress_yuv, ingest_yuv, noise_map_level
         torch, run = self.torch, self.run
         n = t - PAST - FUTURE
         sigma = self._window_sigma(slot, t) if self.V.denoise else None
@@ -491,13 +521,14 @@ class VideoRestorer:
             run.timers.append((e0, e1))
             own = slot.dev_in[PAST:PAST + n]                     # the window's own n frames (not the reflected ones around them), still on the device
             outside = rect is not None                           # the samples outside the picture have to be put into dev_out first
-            if self.convert and (outside or self.mix is not None):
+            keep = self.mix is not None or self.report           # the input in the format written is read again after dev_out has been written
+            if self.convert and (outside or keep):
                 # ... in the format written: the whole frames converted by the two edges, float32 between them, rounded to nearest.  Straight into
-                # dev_out without a mix; with one into the slot's reference buffer, because the mix reads one while it writes the other
+                # dev_out without a mix or a report; with one into the slot's reference buffer, because they read one while the other is (has been) written
                 full = self.conv32[:n * 3 * self.h * self.w].view(1, n, 3, self.h, self.w)
                 ingest_yuv(own, self.fmt, self.h, self.w, self.h, self.w, torch.float32, out=full)
-                own = egress_yuv(full[0], self.ofmt, self.h, self.w, dst=(slot.dev_out if self.mix is None else slot.dev_ref)[:n])
-                outside = outside and self.mix is not None
+                own = egress_yuv(full[0], self.ofmt, self.h, self.w, dst=(slot.dev_ref if keep else slot.dev_out)[:n])
+                outside = outside and keep
             if outside:
                 # everything outside the picture leaves as it came in (as converted, in another format): the egress below writes the inside only
                 slot.dev_out[:n].copy_(own, non_blocking=True)
@@ -506,6 +537,11 @@ class VideoRestorer:
                 egress_yuv(out, self.ofmt, self.h, self.w, dst=slot.dev_out[:n], rect=rect, dither=dither)
             else:
                 egress_yuv(out, self.ofmt, self.h, self.w, dst=slot.dev_out[:n], rect=rect, dither=dither, mix=self.mix, ref=own)
+            if self.report:
+                # written minus input, both still on the device; the sums are read where the window's frames are handed out (_collect)
+                written = slot.dev_out[:n]
+                slot.report.launch(n, run, lambda sums: diff_stats_yuv(own, written, self.ofmt, self.h, self.w, rect=rect, edge=self.report_code_edge,
+                                                                       out_sums=sums))
             slot.ev_done.record(main)
         with torch.cuda.stream(self.s_out):
             self.s_out.wait_event(slot.ev_done)
@@ -516,6 +552,13 @@ class VideoRestorer:
 
     def _collect(self, slot: _Slot, n: int) -> List[np.ndarray]:
         slot.ev_d2h.synchronize()
+        run = self.run
+        if self.report:                                          # windows are handed out in the order they ran: window_sigma has this one's entry
+            sums, = slot.report.wait(n)
+            run.frame_sums += [[int(v) for v in row] for row in sums]
+            run.frame_window += [run.collected] * n
+            run.frame_sigma += [run.window_sigma[run.collected] if self.V.denoise else None] * n
+        run.collected += 1
         return list(slot.pin_out[:n].numpy().copy())
 
     def _finish_stats(self) -> None:
@@ -543,6 +586,12 @@ class VideoRestorer:
                 stats["noise_pairs_launches"] = run.launches["noise_pairs"]
                 if self.nlf_mode == "level":
                     stats["nlf_pairs_launches"] = run.launches["nlf_pairs"]
+        if self.report:
+            from .report import frames_report, summarize
+            stats["frame_sums"] = [list(r) for r in run.frame_sums]
+            stats["frame_report"] = frames_report(run.frame_sums, run.frame_window, run.frame_sigma, self.ofmt.bits, self.ofmt.matrix, self.ofmt.range)
+            stats["report_summary"] = summarize(stats["frame_report"])
+            stats["report_launches"] = run.launches["report"]
         src = run.src
         if self.scene_cuts is not None:                          # its thread has ended: the stream has been read to its end
             stats["cuts"] = list(src.cuts)

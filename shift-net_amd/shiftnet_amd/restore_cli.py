@@ -40,6 +40,18 @@ def amount_arg(word: str):
     return vals[0] if len(vals) == 1 else vals
 
 
+def report_edge_arg(word: str) -> float:
+    """--report_edge: a finite number >= 0."""
+    import math
+    try:
+        v = float(word)
+    except ValueError:
+        v = math.nan
+    if not (math.isfinite(v) and v >= 0.0):
+        raise argparse.ArgumentTypeError(f"a finite number >= 0, got {word!r}")
+    return v
+
+
 def _modes():
     from .y4m import MODES
     return MODES
@@ -97,6 +109,14 @@ def make_parser() -> argparse.ArgumentParser:
                     help="removed: write what the restoration took out instead of the result, input minus result around mid-grey (see --removed_gain); "
                          "not together with an --amount other than 1; default restored")
     ap.add_argument("--removed_gain", type=float, default=1.0, metavar="G", help="removed: the difference is multiplied by G (finite, >= 0) to make it visible")
+    ap.add_argument("--report", default=None, metavar="FILE",
+                    help="measure what the run changed and write one line per written frame: written minus input as noise level (removed_sigma, to be read "
+                         "beside --sigma_out), its correlation with the right, lower and next-frame neighbour (rho_x, rho_y, rho_t: about 0 if only noise "
+                         "left) and its energy on edges over that elsewhere (edge_ratio: about 1 if only noise left); medians in the last line and in the "
+                         "log; changes no byte written; the interpretation is unvalidated on real footage; not together with --view removed")
+    ap.add_argument("--report_edge", type=report_edge_arg, default=16.0, metavar="E",
+                    help="report: a pixel is an edge where the written luma's gradient |right - here| + |below - here| reaches E 8-bit codes (finite, >= 0; "
+                         "the default is a guess nobody has tuned)")
     ap.add_argument("--cuts_out", default=None, metavar="FILE", help="write the scene starts that were used, in the format --scene_cuts FILE reads")
     ap.add_argument("input", metavar="IN", help="Y4M file, or - for stdin")
     ap.add_argument("output", metavar="OUT", help="Y4M file, or - for stdout")
@@ -138,7 +158,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     from . import noise, picture as pic, scenes
     from .io_edges import yuv_fmt
     from .restore import VideoRestorer, load_net
-    from .windows import amount_form
+    from . import report as rep
+    from .windows import amount_form, report_form
     from .y4m import Y4MReader, Y4MWriter, output_header
     ap = make_parser()
     a = ap.parse_args(argv)
@@ -149,6 +170,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         amount_form(a.amount, view, a.removed_gain)
     except ValueError as e:
         ap.error(f"--amount / --view / --removed_gain: {e}")
+    try:
+        report_form(a.report is not None, a.report_edge, view)
+    except ValueError as e:
+        ap.error(f"--report / --report_edge / --view: {e}")
     if "denoise" in a.variant and a.sigma is None:
         ap.error("--sigma is required by the denoise variants")
     if a.sigma_estimator != "spatial" and a.sigma != "auto":      # before the file of a --sigma FILE is opened
@@ -199,7 +224,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         vr = VideoRestorer(net, a.one_len, sigma=sigma, pipeline=not a.no_pipeline, scene_cuts=cuts, cut_threshold=a.cut_threshold,
                            cut_ratio=a.cut_ratio, sigma_clamp=a.sigma_clamp, picture=picture, bar_level=a.bar_level, out_format=a.out_format,
                            dither=None if a.dither == "none" else a.dither, dither_seed=a.dither_seed, noise_model=noise_model,
-                           amount=a.amount, view=view, removed_gain=a.removed_gain, sigma_estimator=a.sigma_estimator)
+                           amount=a.amount, view=view, removed_gain=a.removed_gain, sigma_estimator=a.sigma_estimator,
+                           report=a.report is not None, report_edge=a.report_edge)
         if a.out_format is not None or a.dither != "none":
             log(f"output: C{a.out_format or hd.chroma}{'' if a.out_format else ' (as the input)'}, dither {a.dither}"
                 f"{' seed %d' % a.dither_seed if a.dither != 'none' else ''}")
@@ -240,6 +266,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         if ws:
             log(f"sigma ({sigma_how}{', ' + a.sigma_estimator if a.sigma_estimator != 'spatial' else ''}{', clamped to [%g, %g]' % tuple(a.sigma_clamp) if sigma_how == 'auto' else ''}): "
                 f"min {min(ws):.2f} / median {float(np.median(ws)):.2f} / max {max(ws):.2f} over {len(ws)} window{'' if len(ws) == 1 else 's'}")
+        if a.report is not None:
+            fr = vr.stats["frame_report"]
+            _write_out(a.report, _text_writer(rep.format_report), fr, f"edge {a.report_edge:g}")
+            log(f"report (written minus input, medians over {len(fr)} frame{'' if len(fr) == 1 else 's'}, unvalidated on real footage): "
+                f"{rep.summary_line(vr.stats['report_summary'])}")
     finally:
         if fin is not sys.stdin.buffer:
             fin.close()

@@ -182,6 +182,24 @@ def amount_form(amount, view=None, removed_gain=1.0):
     return ("removed", gain, gain), pair, view
 
 
+def report_form(report=False, report_edge=16.0, view=None):
+    """-> (whether the method-noise report is made, its edge threshold in 8-bit code units).  ``report``: False or True; ``report_edge``: finite and
+    >= 0; ``view="removed"`` with the report is refused: the report describes the stream that was written, and that view writes the difference itself."""
+    import math
+    if not isinstance(report, (bool, np.bool_)):
+        raise ValueError(f"report must be False or True, got {report!r}")
+    try:
+        edge = math.nan if isinstance(report_edge, (bool, str)) else float(report_edge)
+    except (TypeError, ValueError):
+        edge = math.nan
+    if not (math.isfinite(edge) and edge >= 0.0):
+        raise ValueError(f"report_edge must be a finite number >= 0 (8-bit code units), got {report_edge!r}")
+    if report and view is not None:
+        raise ValueError(f"report=True measures input minus the stream written, and view={view!r} writes that difference instead of the restored "
+                         "frames: use one or the other")
+    return bool(report), edge
+
+
 def picture_form(picture):
     """None -> ("full", None); "auto" -> ("auto", None); four numbers -> ("fixed", the tuple); anything whose elements are sequences or None ->
     ("list", the list).  The rectangles are judged where the stream is known (picture.check_pictures)."""

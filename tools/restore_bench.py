@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15, 3.16, 3.17, 3.19 and 3.20 (run on the MI355X from the repository root).
+"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15, 3.16, 3.17, 3.19, 3.20 and 3.21 (run on the MI355X from the repository root).
 
   kernels : time per pixel of sn_ingest_yuv / sn_egress_yuv / sn_yuv_thumb / sn_yuv_noise_hist (4:2:0 8 bit, 720p x 20 frames; the noise
             histogram on the same frames with noise of sigma 10 as well) beside sn_ingest_u8 / sn_egress_u8 on the same
@@ -26,6 +26,10 @@
             sn_yuv_noise_hist and sn_ingest_yuv on the same payloads (4:2:0 8 bit, 720p x 20 frames, a blurred clip and the same with noise of sigma 10),
             interleaved as in the kernels part; since 3.20 also sn_yuv_noise_hist_pairs and sn_yuv_noise_hist_pairs_bands.  --mode forward: steady-state wall time per 720p window of the pipelined denoiser (as the sigma part)
             with sigma="auto" alone and with noise_model="level" on top, runs of the two alternating in one process, the first two windows left out.
+  report  : the method-noise report (3.21).  --mode kernels: time per launch of sn_yuv_diff_stats (4:2:0 8 bit, 720p x 16 frames: a noisy clip against its
+            clean twin, edge 16) beside sn_egress_yuv from float32 and sn_yuv_noise_hist_pairs on the same frames, interleaved as in the kernels part.
+            --mode forward: steady-state wall time per 720p window of the pipelined denoiser (as the sigma part, sigma=10.0) with report=False and with
+            report=True, runs of the two alternating in one process, the first two windows left out.
 Prints one JSON object per part.
 """
 import argparse
@@ -45,7 +49,7 @@ import torch  # noqa: E402
 
 from shiftnet_amd import lib as L  # noqa: E402
 from shiftnet_amd import restore, synth, y4m  # noqa: E402
-from shiftnet_amd.io_edges import (egress_u8, egress_yuv, ingest_u8, ingest_yuv, noise_hist_bands_yuv, noise_hist_pairs_bands_yuv, noise_hist_pairs_yuv,  # noqa: E402
+from shiftnet_amd.io_edges import (diff_stats_yuv, egress_u8, egress_yuv, ingest_u8, ingest_yuv, noise_hist_bands_yuv, noise_hist_pairs_bands_yuv, noise_hist_pairs_yuv,  # noqa: E402
                                    noise_hist_yuv, noise_map_level, rowcol_sums_yuv, thumb_yuv, yuv_fmt)
 
 
@@ -315,6 +319,84 @@ def nlf_forward(a):
                       "runs": a.runs, "window_nlf_first": [round(k, 3) for k in seen["level"][0]], **res}))
 
 
+def report_kernels(a):
+    T, H, W = 16, 720, 1280
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    blur, _ = synth.blurred_clip(4, H, W, seed=1)
+    rgb = ingest_u8(torch.from_numpy(np.concatenate([blur] * 4)).cuda(), torch.float32)[0]
+    clean = egress_yuv(rgb, fmt, H, W)                                               # what was written
+    noisy = egress_yuv((rgb + torch.randn(rgb.shape, device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * (10.0 / 255)).clamp(0, 1), fmt, H, W)
+    dst = torch.empty_like(clean)
+    sums = torch.empty((T, L.SN_DIFF_STATS), dtype=torch.int64, device="cuda")
+    pairs = torch.empty((T - 1, 1021), dtype=torch.uint32, device="cuda")
+    cases = {
+        "egress_yuv_fp32": lambda: egress_yuv(rgb, fmt, H, W, dst=dst),              # the launch the statistic follows: three times the bytes
+        "diff_stats_yuv": lambda: diff_stats_yuv(noisy, clean, fmt, H, W, edge=16, out_sums=sums),
+        "diff_stats_yuv_same": lambda: diff_stats_yuv(clean, clean, fmt, H, W, edge=16, out_sums=sums),      # d = 0 everywhere: the same loads
+        "noise_hist_pairs_yuv": lambda: noise_hist_pairs_yuv(noisy, fmt, H, W, out=pairs),                   # a statistic that reads every luma plane twice
+    }
+    for f in cases.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in cases}
+    for _ in range(a.reps):
+        for k, f in cases.items():                                                   # interleaved: every repetition times every kernel
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.inner):
+                f()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.inner)
+    px = T * H * W
+    res = {k: {"us_per_launch": summary([m * 1e3 for m in v]), "ps_per_pixel": summary([m * 1e9 / px for m in v])} for k, v in ms.items()}
+    print(json.dumps({"part": "report", "mode": "kernels", "frames": T, "size": [H, W], "reps": a.reps, "inner": a.inner,
+                      "note": "diff_stats and the pair histogram include the memset of dst", **res}))
+
+
+def report_forward(a):
+    H, W, one_len, nwin = 720, 1280, 16, a.windows
+    n = one_len * nwin
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    blur, _ = synth.blurred_clip(8, H, W, seed=2)
+    rgb = ingest_u8(torch.from_numpy(blur).cuda(), torch.float32)[0]
+    g = torch.Generator("cuda").manual_seed(1)
+    frames = []
+    for i in range(n):                                                               # fresh noise of sigma 10 on every frame, as the sigma part
+        j = i % 14
+        x = rgb[j if j < 8 else 14 - j][None]
+        frames.append(egress_yuv((x + torch.randn(x.shape, device="cuda", generator=g) * (10.0 / 255)).clamp(0, 1), fmt, H, W)[0].cpu().numpy())
+    net = restore.load_net("denoise_small", "synthetic", "bf16")
+    seen = {}
+
+    def run(rep):
+        vr = restore.VideoRestorer(net, one_len, sigma=10.0, pipeline=True, report=rep)
+        stamps = []
+        t0 = time.perf_counter()
+        for i, p in enumerate(vr.restore(iter(frames), fmt, H, W)):
+            if (i + 1) % one_len == 0:
+                stamps.append(time.perf_counter())
+        total = time.perf_counter() - t0
+        seen[rep] = vr.stats.get("report_summary")
+        gaps = [(b - c) * 1e3 for b, c in zip(stamps[1:], stamps[:-1])]
+        return {"total_s": total, "window_wall_ms": gaps[1:], "window_forward_ms": vr.stats["window_forward_ms"][2:]}
+
+    run(False)                                                                       # warm-up: code objects, engine buffers
+    run(True)
+    runs = {"off": [], "report": []}
+    for _ in range(a.runs):
+        runs["off"].append(run(False))
+        runs["report"].append(run(True))
+    res = {}
+    for k, rs in runs.items():
+        res[k] = {"window_wall_ms": summary([g for r in rs for g in r["window_wall_ms"]]),
+                  "window_wall_ms_per_run": [round(statistics.median(r["window_wall_ms"]), 2) for r in rs],
+                  "window_forward_ms": summary([g for r in rs for g in r["window_forward_ms"]]), "total_s": [round(r["total_s"], 3) for r in rs]}
+    print(json.dumps({"part": "report", "mode": "forward", "variant": "denoise_small", "dtype": "bf16", "one_len": one_len, "windows": nwin, "size": [H, W],
+                      "runs": a.runs, "report_summary": {k: round(v, 4) for k, v in seen[True].items()}, **res}))
+
+
 PICTURE = dict(H=1080, W=1920, rect=(0, 138, 1920, 804))
 
 
@@ -454,7 +536,7 @@ def picture_part(a):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf"])
+    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report"])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--inner", type=int, default=200)
     ap.add_argument("--windows", type=int, default=8)
@@ -465,9 +547,10 @@ if __name__ == "__main__":
     ap.add_argument("--parent_lib", default=None, metavar="SO", help="kernels part and picture part in kernels mode: a shared library built from another commit's "
                     "csrc/sn_yuv.hip alone; its sn_ingest_yuv / sn_egress_yuv are timed beside this build's")
     ap.add_argument("--only_cases", default=None, metavar="WORDS", help="kernels part: time only the cases whose name contains one of these comma-separated words")
-    ap.add_argument("--mode", choices=["forward", "kernels"], default="forward", help="picture and nlf parts: which measurement")
+    ap.add_argument("--mode", choices=["forward", "kernels"], default="forward", help="picture, nlf and report parts: which measurement")
     ap.add_argument("--picture", choices=["auto", "fixed"], default="auto", help="picture part, forward mode: VideoRestorer(picture='auto') or the rectangle itself")
     a = ap.parse_args()
     with torch.no_grad():
         {"kernels": kernels, "pipeline": pipeline, "sigma": sigma, "picture": picture_part,
-         "nlf": nlf_kernels if a.mode == "kernels" else nlf_forward}[a.part](a)
+         "nlf": nlf_kernels if a.mode == "kernels" else nlf_forward,
+         "report": report_kernels if a.mode == "kernels" else report_forward}[a.part](a)
