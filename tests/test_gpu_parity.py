@@ -420,7 +420,8 @@ def test_cab_phase1_fused_kernel(T, h, w, name, p1key, team, engines):
     channel sums, CAB1 and both CAB2 directions -- the role-split kernel with the RepConv on the matrix cores (csrc/sn_phase1r.hip: C = 64 depthwise
     and C = 80 grouped, gshift_deblur1.py:157-165,183-255): maps smaller than the warm-up rows / the pixel region, one strip (w <= 64: the region
     starts AT the image edge), two border strips (61 + 61 = 122 columns exactly, and 123 = three strips), several strips, row chunks that cross
-    strip and frame boundaries, teams of 4 / 2 frames in lock step with a ragged last frame block (T = 5) and one workgroup per walk (team 1)."""
+    strip and frame boundaries, teams of 4 / 2 frames in lock step with a ragged last frame block (T = 5) and one workgroup per walk (team 1).
+    Per element, against a float64 interval reference that models every rounding of the kernel: tests/test_gpu_phase1_edges.py."""
     from shiftnet_amd import lib as L
     eng, sd = engines(name)
     V = O.VARIANTS[name]
