@@ -661,6 +661,41 @@ int sn_yuv_noise_hist_pairs(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_
 int sn_yuv_noise_hist_pairs_bands(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */, uint32_t* dst, int lo, int hi,
                                   int T, int H, int W, void* stream);
 
+/* ---- block motion of frame pairs and the pair statistics along it (new symbols, SN_ABI_VERSION stays 20) ------------------------------------------
+ * The motion-compensated temporal noise estimate of the video restorer (shiftnet_amd/noise.py): the pair statistics above compare a 2 x 2 block with
+ * the block at the same place in the next payload, so content that moves reads as noise.  sn_yuv_block_motion finds one integer translation per
+ * 16 x 16 luma block of every pair and the two _mv entry points take the second payload's block where it points.  src, fmt, rect (NULL: the whole
+ * frame), lo, hi, T >= 2, H, W and stream exactly as sn_yuv_noise_hist_pairs takes them: only the luma plane is read, of fmt only bits decides
+ * anything, samples are taken as stored (a 16-bit word may hold up to 65535), pair p is payloads p and p + 1.  The picture is h x w, the rectangle
+ * or the frame; every grid is anchored at its first sample and all coordinates below count from there.
+ *   hb = h / 2, wb = w / 2: the whole 2 x 2 blocks (i, j).  Block (i, j) is a MATCHING block if i + j is even and a MEASURING block if it is odd.
+ *   Vector block (I, J) holds the 2 x 2 blocks with i / 8 == I and j / 8 == J: 16 x 16 samples, fewer at the right and lower edge.
+ *   nby = ceil(hb / 8), nbx = ceil(wb / 8).  hb == 0 or wb == 0: no vector block; sn_yuv_block_motion writes nothing and the histograms are zero.
+ *   Candidates: (dy, dx) with |dy| <= 7 and |dx| <= 7, 225 in all.  A candidate is ADMISSIBLE for a vector block iff the block's sample extent --
+ *   rows 16 I .. 2 min(8 I + 8, hb) - 1, columns 16 J .. 2 min(8 J + 8, wb) - 1 -- displaced by it lies inside the h x w picture.  Nothing is
+ *   clamped and nothing outside the picture is ever read.  (0, 0) is always admissible.
+ *   SAD(dy, dx) = the sum of |Y_p(y, x) - Y_{p+1}(y + dy, x + dx)| over the four samples of every matching block of the vector block (at most
+ *   128 x 65535: exact in 32 bits).  The vector is the admissible candidate with the smallest SAD; among equal SADs the one with the smallest
+ *   (|dy| + |dx|, dy, dx) in lexicographic order.
+ * sn_yuv_block_motion: mv:[T - 1][nby][nbx][2] int8 holds (dy, dx), sad:[T - 1][nby][nbx] uint32 the winning SAD.  Both are overwritten; nothing outside
+ *   them is written.
+ * sn_yuv_noise_hist_pairs_mv, sn_yuv_noise_hist_pairs_bands_mv: dst, v, S, band, NBP and NBV exactly as sn_yuv_noise_hist_pairs and
+ *   sn_yuv_noise_hist_pairs_bands define them, except that only measuring blocks count, that the four codes a1 b1 / c1 d1 of payload p + 1 are those
+ *   at rows 2 i + dy, 2 i + dy + 1 and columns 2 j + dx, 2 j + dx + 1 with (dy, dx) = mv[p][i / 8][j / 8], and that a block whose displaced position
+ *   does not lie wholly inside the picture does not count.  mv is device memory the entry point cannot validate: the test is made per block in the
+ *   kernel, ANY int8 contents are memory-safe, and with the vectors of sn_yuv_block_motion it never fails.  The eight codes must lie strictly between
+ *   lo and hi, as there; where hi admits stored words above 2^bits - 1, v is saturated to NBP - 1 (the flat histogram) as it is to NBV - 1.  dst is
+ *   OVERWRITTEN; integer sums, exact and the same for every launch geometry and schedule.
+ * (tests/motion_ref.py restates all three in numpy; the kernels equal it word for word.)
+ * SN_EINVAL before anything is launched: everything sn_yuv_noise_hist_pairs_bands refuses (sn_yuv_block_motion takes no lo / hi / dst), a null mv or
+ * sad, sad or dst not 4-byte aligned, and a picture of more than 65535 x 16 rows for sn_yuv_block_motion (nby is a grid dimension). */
+int sn_yuv_block_motion(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */, int8_t* mv, uint32_t* sad,
+                        int T, int H, int W, void* stream);
+int sn_yuv_noise_hist_pairs_mv(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */, const int8_t* mv, uint32_t* dst,
+                               int lo, int hi, int T, int H, int W, void* stream);
+int sn_yuv_noise_hist_pairs_bands_mv(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */, const int8_t* mv,
+                                     uint32_t* dst, int lo, int hi, int T, int H, int W, void* stream);
+
 /* ---- method noise: the statistics of what a run changed (a new symbol, SN_ABI_VERSION stays 20) ---------------------------------------------------
  * The report of the video restorer (shiftnet_amd/report.py): if only noise left the picture, input minus output is white in space, independent from
  * frame to frame, no stronger on edges than on flat areas, and as strong as the noise was.  sn_yuv_diff_stats makes the integer sums those four

@@ -10,6 +10,10 @@
 //                   uint32 (the noise-level function of shiftnet_amd/noise.py is estimated from these on the host); rect or the whole frame;
 //   sn_yuv_noise_hist_pairs, sn_yuv_noise_hist_pairs_bands : the same two statistics of the DIFFERENCE of consecutive payloads, T - 1 pairs:
 //                   [T - 1][4 (2^bits - 1) + 1] and [T - 1][16][NBV] uint32 (the temporal noise estimate of shiftnet_amd/noise.py); rect or the whole frame;
+//   sn_yuv_block_motion : T payloads -> [T - 1][nby][nbx][2] int8 vectors and [T - 1][nby][nbx] uint32 SADs: per 16 x 16 luma block of every pair the
+//                   integer translation within +-7 samples with the smallest sum of absolute differences over HALF of the block's 2 x 2 blocks;
+//                   sn_yuv_noise_hist_pairs_mv, sn_yuv_noise_hist_pairs_bands_mv: the two pair statistics over the OTHER half, the second payload's block
+//                   taken where the vector points (the motion-compensated temporal estimate of shiftnet_amd/noise.py); rect or the whole frame;
 //   sn_noise_map_level : T payloads and the 16 knots of a noise-level function -> [T][1][Hp][Wp] of the module dtype or float32: the function at the
 //                   low-passed luma of every pixel (bilinear between the means of the 8 x 8 blocks): the denoisers' noise plane; rect or the whole frame;
 //   sn_yuv_rowcol_sums : T payloads -> [T][H] and [T][W] uint32 sums of the luma codes of every row and every column (the letterbox rule of
@@ -332,6 +336,185 @@ __global__ __launch_bounds__(256) void yuv_noise_hist_pairs_bands_kernel(const u
                 const int band = (int)((uint32_t)(2 * (S - 8 * lo)) / span);                         // 0 .. 15 (above)
                 if (v < LOW) atomicAdd(&low[(band * LOW + v) * COPIES + cp], 1u);
                 else atomicAdd(&hist[band * NBV + v], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    uint32_t* out = dst + (size_t)pr * HISTW;
+    for (int i = tid; i < HISTW; i += 256) {
+        uint32_t n = hist[i];
+        const int band = i / NBV, v = i - band * NBV;
+        if (v < LOW) {
+            const uint32_t* c = low + (band * LOW + v) * COPIES;
+            const int rot = (i * COPIES) >> 5;                            // as yuv_noise_hist_bands_kernel: lanes whose copies start on one bank begin at different copies
+#pragma unroll 4
+            for (int k = 0; k < COPIES; ++k) n += c[(k + rot) & (COPIES - 1)];
+        }
+        if (n) atomicAdd(&out[i], n);
+    }
+}
+
+// ---- block motion of frame pairs ------------------------------------------------------------------------------------------------------------
+// The vector of a 16 x 16 luma block (a "vector block": 8 x 8 of the 2 x 2 blocks above) of payload p is the (dy, dx), |dy|, |dx| <= MV_R = 7, for which
+// the sum of |Y_p(y, x) - Y_{p+1}(y + dy, x + dx)| over the block's MATCHING 2 x 2 blocks -- (i + j) even, half of them, a checkerboard -- is smallest.
+// The histogram kernels below measure on the other half: pixel noise is independent between the two, so the choice cannot fit the noise it is
+// measured on (include/shiftnet_hip.h states the arithmetic and the tie order; DESIGN.md 3.23 the reason).
+// A workgroup takes MV_RUN = 4 neighbouring vector blocks of one block row of one pair, blockIdx = (run, block row, pair).  It stages their 16 x 64
+// samples of payload p and the 30 x 78 samples of payload p + 1 that their candidates reach (neighbouring blocks share 14 of a block's 30 columns)
+// in LDS as 16-bit words, element-wise loads, consecutive lanes consecutive samples of a row; what lies outside the picture is not read and stays 0
+// in LDS, where no admissible candidate looks.  Then lane c < 225 owns candidate c = (dy + 7) 15 + (dx + 7) for one vector block after the other: 128
+// differences from LDS (the reference sample is one address for the whole wave, a broadcast; the window's addresses are consecutive in dx), the
+// key SAD * 256 + rank with rank the candidate's place in the tie order, 0xFFFFFFFF where the displaced block would leave the picture, and one unsigned
+// minimum over the workgroup: across the wave by cross-lane moves, across the four waves by an LDS atomic.  SAD <= 128 x 65535 < 2^24: the key fits.
+// The rank is computed once per lane by counting the candidates that come before its own.  Ragged blocks at the right and lower edge have fewer 2 x 2
+// blocks and loops that are shorter by that much.  Integer arithmetic throughout: the result does not depend on the geometry or the schedule.
+constexpr int MV_R = 7, MV_D = 2 * MV_R + 1, MV_CAND = MV_D * MV_D, MV_RUN = 4;
+constexpr int MV_WW = 16 * MV_RUN + 2 * MV_R, MV_WH = 16 + 2 * MV_R, MV_RW = 16 * MV_RUN;      // 78 x 30 window, 64 x 16 reference
+
+template <int ESZ>
+__global__ __launch_bounds__(256) void yuv_block_motion_kernel(const uint8_t* __restrict__ src, int8_t* __restrict__ mv, uint32_t* __restrict__ sad, int h,
+                                                             int w, int W, int hb, int wb, int nbx, size_t origin, size_t frame_bytes) {
+    __shared__ uint16_t win[MV_WH * MV_WW];
+    __shared__ uint16_t ref[16 * MV_RW];
+    __shared__ uint32_t best[MV_RUN];
+    __shared__ uint8_t cand_of[MV_CAND];                                  // rank -> candidate
+    const int tid = threadIdx.x, J0 = blockIdx.x * MV_RUN, I = blockIdx.y, pr = blockIdx.z;
+    const int nby = gridDim.y;
+    const uint8_t* y0 = src + (size_t)pr * frame_bytes + origin;          // payload pr; W: the luma row pitch; origin: the byte offset of the picture's first sample
+    const uint8_t* y1 = y0 + frame_bytes;                                 // payload pr + 1 <= T - 1
+    const int Y0 = 16 * I, X0 = 16 * J0;                                  // the run's first sample, < 2 hb and < 2 wb
+    for (int i = tid; i < MV_WH * MV_WW; i += 256) {
+        const int r = i / MV_WW, c = i - r * MV_WW, y = Y0 - MV_R + r, x = X0 - MV_R + c;
+        win[i] = (y >= 0 && y < h && x >= 0 && x < w) ? (uint16_t)ld1<ESZ>(y1, (size_t)y * W + x) : (uint16_t)0;
+    }
+    for (int i = tid; i < 16 * MV_RW; i += 256) {
+        const int r = i / MV_RW, c = i - r * MV_RW, y = Y0 + r, x = X0 + c;
+        ref[i] = (y < 2 * hb && x < 2 * wb) ? (uint16_t)ld1<ESZ>(y0, (size_t)y * W + x) : (uint16_t)0;
+    }
+    if (tid < MV_RUN) best[tid] = 0xFFFFFFFFu;
+    const int dy = tid / MV_D - MV_R, dx = tid % MV_D - MV_R;             // lanes 225 .. 255 own no candidate
+    const bool own = tid < MV_CAND;
+    int rank = 0;
+    if (own) {
+        const int n = (dy < 0 ? -dy : dy) + (dx < 0 ? -dx : dx);
+        for (int c = 0; c < MV_CAND; ++c) {                               // the candidates before this one in the order (|dy| + |dx|, dy, dx)
+            const int ey = c / MV_D - MV_R, ex = c % MV_D - MV_R, m = (ey < 0 ? -ey : ey) + (ex < 0 ? -ex : ex);
+            rank += (m < n || (m == n && (ey < dy || (ey == dy && ex < dx)))) ? 1 : 0;
+        }
+        cand_of[rank] = (uint8_t)tid;
+    }
+    __syncthreads();
+    const int rows = imin(8, hb - 8 * I);                                 // the 2 x 2 block rows of this block row: 1 .. 8
+    const int ye = Y0 + 2 * rows;                                         // the end of its sample extent
+    const int runs = imin(MV_RUN, nbx - J0);
+    for (int b = 0; b < runs; ++b) {
+        const int cols = imin(8, wb - 8 * (J0 + b));                      // 1 .. 8
+        const int xs = X0 + 16 * b, xe = xs + 2 * cols;
+        uint32_t key = 0xFFFFFFFFu;
+        if (own && Y0 + dy >= 0 && ye + dy <= h && xs + dx >= 0 && xe + dx <= w) {
+            uint32_t s = 0;
+            for (int bi = 0; bi < rows; ++bi) {
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    const uint16_t* a = ref + (2 * bi + r) * MV_RW + 16 * b;
+                    const uint16_t* q = win + (2 * bi + r + MV_R + dy) * MV_WW + 16 * b + MV_R + dx;
+                    for (int bj = bi & 1; bj < cols; bj += 2) {           // (bi + bj) even: 8 I and 8 J are even, the parity is that of (i, j)
+                        const int d0 = (int)a[2 * bj] - (int)q[2 * bj], d1 = (int)a[2 * bj + 1] - (int)q[2 * bj + 1];
+                        s += (uint32_t)(d0 < 0 ? -d0 : d0) + (uint32_t)(d1 < 0 ? -d1 : d1);
+                    }
+                }
+            }
+            key = (s << 8) | (uint32_t)rank;
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const uint32_t o = (uint32_t)__shfl_xor((int)key, m, 64);
+            key = o < key ? o : key;
+        }
+        if ((tid & 63) == 0) atomicMin(&best[b], key);
+    }
+    __syncthreads();
+    if (tid < runs) {                                                     // (0, 0) is always admissible: best holds a candidate's key
+        const uint32_t k = best[tid];
+        const int c = cand_of[k & 255u];
+        const size_t o = ((size_t)pr * nby + I) * nbx + J0 + tid;
+        mv[2 * o] = (int8_t)(c / MV_D - MV_R);
+        mv[2 * o + 1] = (int8_t)(c % MV_D - MV_R);
+        sad[o] = k >> 8;
+    }
+}
+
+// ---- noise histograms of frame pairs along the vectors ----------------------------------------------------------------------------------------
+// yuv_noise_hist_pairs_kernel and its band sibling on the MEASURING 2 x 2 blocks, (i + j) odd, with the four codes of payload p + 1 taken at
+// (2 i + dy, 2 j + dx), (dy, dx) the vector of block (i / 8, j / 8).  One kernel for both: NBANDS = 1 is the flat histogram (NBV = NBP bins, 32
+// copies of the bins below LOW), NBANDS = 16 the band histogram, with the constants and the LDS layout of the two kernels above.  The same units
+// and the same walk: a unit's four blocks lie in one vector block (4 divides 8) and two of them measure, blocks 1 and 3 of the unit in an even block
+// row and 0 and 2 in an odd one.  Payload p is loaded as there; the displaced block of payload p + 1 is at no particular alignment and is loaded
+// element-wise, after the test that it lies inside the picture: mv is device memory nobody has validated, and with the test any int8 contents are
+// safe -- a block whose displaced position is not wholly inside the h x w picture does not count, and nothing outside the picture is read.
+template <int ESZ, bool BANDS> struct MvHistK {
+    static constexpr int NBANDS = BANDS ? SN_NLF_BANDS : 1;
+    static constexpr int NBV = BANDS ? PairBandK<ESZ>::NBV : PairK<ESZ>::NB;
+    static constexpr int LOW = BANDS ? PairBandK<ESZ>::LOW : PairK<ESZ>::LOW;
+    static constexpr int COPIES = BANDS ? PairBandK<ESZ>::COPIES : 32;
+    static constexpr int LOWW = NBANDS * LOW * COPIES, HISTW = NBANDS * NBV;
+};
+
+template <int ESZ, bool BANDS>
+__global__ __launch_bounds__(256) void yuv_noise_hist_pairs_mv_kernel(const uint8_t* __restrict__ src, const int8_t* __restrict__ mv,
+                                                                    uint32_t* __restrict__ dst, int lo, int hi, int h, int w, int W, int hb, int wb, int ux,
+                                                                    int nby, int nbx, size_t origin, size_t frame_bytes) {
+    using K = MvHistK<ESZ, BANDS>;
+    constexpr int NBV = K::NBV, LOW = K::LOW, COPIES = K::COPIES, LOWW = K::LOWW, HISTW = K::HISTW;
+    __shared__ uint32_t low[LOWW];
+    __shared__ uint32_t hist[HISTW];
+    const int tid = threadIdx.x, pr = blockIdx.y, cp = tid & (COPIES - 1);
+    for (int i = tid; i < LOWW; i += 256) low[i] = 0;
+    for (int i = tid; i < HISTW; i += 256) hist[i] = 0;
+    __syncthreads();
+    const uint8_t* y0 = src + (size_t)pr * frame_bytes + origin;          // as yuv_noise_hist_pairs_kernel
+    const uint8_t* y1 = y0 + frame_bytes;
+    const int8_t* vec = mv + (size_t)pr * nby * nbx * 2;
+    const int units = ux * hb;
+    const uint32_t span = (uint32_t)(hi - lo);
+    for (int u = blockIdx.x * 256 + tid; u < units; u += gridDim.x * 256) {
+        const int by = u / ux, bx0 = (u - by * ux) * 4;
+        const int nb = imin(4, wb - bx0);
+        const size_t r0 = (size_t)(2 * by) * W + 2 * bx0, r1 = r0 + W;
+        const int8_t* v2 = vec + ((size_t)(by >> 3) * nbx + (bx0 >> 3)) * 2;      // by / 8 < nby and bx0 / 8 < nbx: inside mv whatever it holds
+        const int dy = v2[0], dx = v2[1];
+        int a0[8], b0[8];
+        if (nb == 4) {
+            ldn<ESZ, 8>(y0, r0, a0);
+            ldn<ESZ, 8>(y0, r1, b0);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {                                 // pixels 2 bx0 .. 2 (bx0 + nb) - 1 < 2 wb <= W exist; the others are not read
+                const bool in = k < 2 * nb;
+                a0[k] = in ? ld1<ESZ>(y0, r0 + k) : 0;
+                b0[k] = in ? ld1<ESZ>(y0, r1 + k) : 0;
+            }
+        }
+        const int yd = 2 * by + dy;                                       // the displaced block's first row: rows yd, yd + 1 must lie in 0 .. h - 1
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int xd = 2 * (bx0 + k) + dx;                            // ... and columns xd, xd + 1 in 0 .. w - 1
+            if (k < nb && ((by + k) & 1) && yd >= 0 && yd + 2 <= h && xd >= 0 && xd + 2 <= w) {      // bx0 is even: (by + k) is the parity of (i + j)
+                const size_t o = (size_t)yd * W + xd;
+                const int p0 = a0[2 * k], q0 = a0[2 * k + 1], r0c = b0[2 * k], s0 = b0[2 * k + 1];
+                const int p1 = ld1<ESZ>(y1, o), q1 = ld1<ESZ>(y1, o + 1), r1c = ld1<ESZ>(y1, o + W), s1 = ld1<ESZ>(y1, o + W + 1);
+                const int mn = imin(imin(imin(p0, q0), imin(r0c, s0)), imin(imin(p1, q1), imin(r1c, s1)));
+                const int mx = imax(imax(imax(p0, q0), imax(r0c, s0)), imax(imax(p1, q1), imax(r1c, s1)));
+                if (mn > lo && mx < hi) {
+                    const int d = (p1 - q1 - r1c + s1) - (p0 - q0 - r0c + s0), v = imin(d < 0 ? -d : d, NBV - 1);      // flat: v <= NBP - 1 as it is
+                    int band = 0;
+                    if (BANDS) {
+                        const int S = ((p0 + q0) + (r0c + s0)) + ((p1 + q1) + (r1c + s1));
+                        band = (int)((uint32_t)(2 * (S - 8 * lo)) / span);                               // 0 .. 15 (yuv_noise_hist_pairs_bands_kernel)
+                    }
+                    if (v < LOW) atomicAdd(&low[(band * LOW + v) * COPIES + cp], 1u);
+                    else atomicAdd(&hist[band * NBV + v], 1u);
+                }
             }
         }
     }
@@ -720,6 +903,60 @@ int sn_yuv_noise_hist_pairs(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_
 int sn_yuv_noise_hist_pairs_bands(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint32_t* dst, int lo, int hi, int T, int H, int W,
                                   void* stream) {
     return noise_hist_pairs(true, src, fmt, rect, dst, lo, hi, T, H, W, stream);
+}
+
+// The vectors of the 16 x 16 blocks of every pair: nothing to zero, every word of mv and sad is written by the one workgroup that owns it
+int sn_yuv_block_motion(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, int8_t* mv, uint32_t* sad, int T, int H, int W, void* stream) {
+    sn_clear_error();
+    if (!valid_payloads(src, fmt, T, H, W) || T < 2 || !mv || !sad || ((uintptr_t)sad & 3)) return SN_EINVAL;
+    YuvGeo G;
+    if (!make_geo(fmt, H, W, rect, &G)) return SN_EINVAL;
+    const int hb = G.h / 2, wb = G.w / 2, nby = (hb + 7) / 8, nbx = (wb + 7) / 8;      // the block grid is anchored at the picture's first sample
+    if (nby > 65535) return SN_EINVAL;                                     // a grid dimension
+    if (hb < 1 || wb < 1) return sn_check_launch();                        // no whole block: no vector block, nothing is written
+    const dim3 block(256), grid((nbx + MV_RUN - 1) / MV_RUN, nby, T - 1);
+    hipStream_t s = (hipStream_t)stream;
+    with_esz(fmt, [&](auto esz) {
+        hipLaunchKernelGGL((yuv_block_motion_kernel<esz()>), grid, block, 0, s, src, mv, sad, G.h, G.w, W, hb, wb, nbx, G.oy, G.frame_bytes);
+    });
+    return sn_check_launch();
+}
+
+// The pair histograms along the vectors: noise_hist_pairs with mv, its grid and the picture's size for the kernel's bounds test
+static int noise_hist_pairs_mv(bool bands, const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const int8_t* mv, uint32_t* dst, int lo,
+                               int hi, int T, int H, int W, void* stream) {
+    sn_clear_error();
+    if (!valid_payloads(src, fmt, T, H, W) || T < 2 || !mv || !dst || ((uintptr_t)dst & 3) || lo > hi) return SN_EINVAL;
+    if (lo < -(1 << 24) || hi > (1 << 24)) return SN_EINVAL;               // the band is 32-bit arithmetic: 2 (S - 8 lo) must fit
+    YuvGeo G;
+    if (!make_geo(fmt, H, W, rect, &G)) return SN_EINVAL;
+    int words = 0;
+    with_esz(fmt, [&](auto esz) { words = bands ? MvHistK<esz(), true>::HISTW : MvHistK<esz(), false>::HISTW; });
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(dst, 0, (size_t)(T - 1) * words * sizeof(uint32_t), s) != hipSuccess) return sn_check_launch();      // dst is overwritten, not added to
+    const int hb = G.h / 2, wb = G.w / 2, ux = (wb + 3) / 4, nby = (hb + 7) / 8, nbx = (wb + 7) / 8;
+    if (hb < 1 || wb < 1) return sn_check_launch();                        // no whole block: all-zero histograms
+    const long long units = (long long)ux * hb;
+    if (units > 0x7fffffffLL - 1024 * 256) return SN_EINVAL;
+    const long long per = bands ? 4096 : 2048, wgs = (units + per - 1) / per;      // units per workgroup as noise_hist
+    const dim3 block(256), grid(wgs < 1024 ? (int)wgs : 1024, T - 1);
+    with_esz(fmt, [&](auto esz) {
+        if (bands) hipLaunchKernelGGL((yuv_noise_hist_pairs_mv_kernel<esz(), true>), grid, block, 0, s, src, mv, dst, lo, hi, G.h, G.w, W, hb, wb, ux, nby,
+                                      nbx, G.oy, G.frame_bytes);
+        else hipLaunchKernelGGL((yuv_noise_hist_pairs_mv_kernel<esz(), false>), grid, block, 0, s, src, mv, dst, lo, hi, G.h, G.w, W, hb, wb, ux, nby, nbx,
+                                G.oy, G.frame_bytes);
+    });
+    return sn_check_launch();
+}
+
+int sn_yuv_noise_hist_pairs_mv(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const int8_t* mv, uint32_t* dst, int lo, int hi, int T,
+                               int H, int W, void* stream) {
+    return noise_hist_pairs_mv(false, src, fmt, rect, mv, dst, lo, hi, T, H, W, stream);
+}
+
+int sn_yuv_noise_hist_pairs_bands_mv(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const int8_t* mv, uint32_t* dst, int lo, int hi,
+                                     int T, int H, int W, void* stream) {
+    return noise_hist_pairs_mv(true, src, fmt, rect, mv, dst, lo, hi, T, H, W, stream);
 }
 
 int sn_noise_map_level(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const float* knots, int lo, int hi, void* dst, int dst_dtype,

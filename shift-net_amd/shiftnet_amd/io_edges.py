@@ -13,6 +13,9 @@ the statistics of the same payloads' luma (csrc/sn_yuv_stats.hip), each for one 
                luma code);
 ``noise_hist_pairs_yuv`` / ``noise_hist_pairs_bands_yuv``: the same two statistics of the difference of consecutive payloads, T - 1 pairs, for the
                temporal noise estimate (shiftnet_amd/noise.py);
+``block_motion_yuv``: one integer translation within +-7 samples per 16 x 16 luma block of every pair of consecutive payloads, and
+``noise_hist_pairs_mv_yuv`` / ``noise_hist_pairs_bands_mv_yuv``: the two pair statistics with the second payload's block taken where the vector
+               points, for the motion-compensated temporal estimate (shiftnet_amd/noise.py);
 ``noise_map_level``: payloads + the 16 knots of such a function -> the denoisers' noise plane;
 ``rowcol_sums_yuv``: uint32 sums of the luma codes of every row and of every column, for the letterbox rule (shiftnet_amd/picture.py);
 ``diff_stats_yuv``: int64 sums of the difference of two sets of payloads, what came in and what was written, for the method-noise report
@@ -274,6 +277,68 @@ def noise_hist_pairs_bands_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int
     ``lo``, ``hi``, ``out``, ``rect`` as ``noise_hist_yuv``."""
     from .noise import NLF_BANDS, nlf_bins
     return _hist_pairs("sn_yuv_noise_hist_pairs_bands", (NLF_BANDS, nlf_bins(fmt.bits)), payload_u8, fmt, H, W, lo, hi, out, rect)
+
+
+def block_motion_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, rect=None, out_mv: Optional[torch.Tensor] = None,
+                     out_sad: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """payload_u8: [T, frame_bytes] uint8 on a HIP device, T >= 2 (only the luma plane of each payload is read) -> (int8 [T - 1, nby, nbx, 2], uint32
+    [T - 1, nby, nbx]) with (nby, nbx) = noise.motion_grid(h, w): per pair of consecutive payloads and per 16 x 16 luma block the vector (dy, dx),
+    |dy|, |dx| <= 7, with the smallest sum of absolute differences over the block's matching 2 x 2 blocks ((i + j) even), and that sum
+    (include/shiftnet_hip.h: sn_yuv_block_motion states the admissible candidates and the tie order).  ``rect=(x0, y0, w, h)``: the blocks of that
+    picture of the stream, the grid anchored at (x0, y0): the cropped stream's vectors.  ``out_mv`` / ``out_sad``: tensors of those shapes to overwrite.
+    A picture without a whole 2 x 2 block has empty grids and nothing is launched."""
+    from .noise import motion_grid
+    T, dev = _payload(payload_u8, fmt, H, W)
+    if T < 2:
+        raise ValueError(f"sn_yuv_block_motion: a pair needs two payloads, got {T}")
+    r = None if rect is None else _rect(rect, fmt, H, W)
+    nby, nbx = motion_grid(H if r is None else r.h, W if r is None else r.w)
+    mv = out_mv if out_mv is not None else torch.empty((T - 1, nby, nbx, 2), dtype=torch.int8, device=dev)
+    sad = out_sad if out_sad is not None else torch.empty((T - 1, nby, nbx), dtype=torch.uint32, device=dev)
+    assert tuple(mv.shape) == (T - 1, nby, nbx, 2) and mv.dtype == torch.int8 and mv.is_contiguous() and mv.device == dev
+    assert tuple(sad.shape) == (T - 1, nby, nbx) and sad.dtype == torch.uint32 and sad.is_contiguous() and sad.device == dev
+    if nby * nbx:
+        with torch.cuda.device(dev):
+            L.check(L.load().sn_yuv_block_motion(payload_u8.data_ptr(), fmt, r, mv.data_ptr(), sad.data_ptr(), T, H, W,
+                                                 torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_block_motion")
+    return mv, sad
+
+
+def _hist_pairs_mv(symbol: str, shape, payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, mv: torch.Tensor, lo, hi, out, rect) -> torch.Tensor:
+    """``_hist_pairs`` with the vectors: mv int8 [T - 1, nby, nbx, 2] on the payloads' device.  Its contents are not looked at: the kernel tests every
+    displaced block against the picture."""
+    from .noise import motion_grid
+    T, dev = _payload(payload_u8, fmt, H, W)
+    if T < 2:
+        raise ValueError(f"{symbol}: a pair needs two payloads, got {T}")
+    lo, hi = _clip(fmt, lo, hi)
+    r = None if rect is None else _rect(rect, fmt, H, W)
+    nby, nbx = motion_grid(H if r is None else r.h, W if r is None else r.w)
+    assert tuple(mv.shape) == (T - 1, nby, nbx, 2) and mv.dtype == torch.int8 and mv.is_contiguous() and mv.device == dev
+    y = out if out is not None else torch.empty((T - 1,) + shape, dtype=torch.uint32, device=dev)
+    assert tuple(y.shape) == (T - 1,) + shape and y.dtype == torch.uint32 and y.is_contiguous() and y.device == dev
+    if nby * nbx == 0:                                        # no whole block: no vector to point at, and what the entry point writes then
+        return y.zero_()
+    with torch.cuda.device(dev):
+        L.check(getattr(L.load(), symbol)(payload_u8.data_ptr(), fmt, r, mv.data_ptr(), y.data_ptr(), lo, hi, T, H, W,
+                                          torch.cuda.current_stream(dev).cuda_stream), symbol)
+    return y
+
+
+def noise_hist_pairs_mv_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, mv: torch.Tensor, lo: Optional[int] = None,
+                            hi: Optional[int] = None, out: Optional[torch.Tensor] = None, rect=None) -> torch.Tensor:
+    """``noise_hist_pairs_yuv`` along the vectors ``mv`` of ``block_motion_yuv`` (same payloads, same ``rect``): only the measuring 2 x 2 blocks ((i + j)
+    odd) count, the second payload's four codes are those at (2 i + dy, 2 j + dx) with (dy, dx) the vector of block (i / 8, j / 8), and a block whose
+    displaced position is not wholly inside the picture does not count.  Any int8 contents of ``mv`` are safe."""
+    from .noise import pair_bins
+    return _hist_pairs_mv("sn_yuv_noise_hist_pairs_mv", (pair_bins(fmt.bits),), payload_u8, fmt, H, W, mv, lo, hi, out, rect)
+
+
+def noise_hist_pairs_bands_mv_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, mv: torch.Tensor, lo: Optional[int] = None,
+                                  hi: Optional[int] = None, out: Optional[torch.Tensor] = None, rect=None) -> torch.Tensor:
+    """``noise_hist_pairs_bands_yuv`` along the vectors ``mv``, with the three differences of ``noise_hist_pairs_mv_yuv``."""
+    from .noise import NLF_BANDS, nlf_bins
+    return _hist_pairs_mv("sn_yuv_noise_hist_pairs_bands_mv", (NLF_BANDS, nlf_bins(fmt.bits)), payload_u8, fmt, H, W, mv, lo, hi, out, rect)
 
 
 def noise_map_level(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, Hp: int, Wp: int, knots, dtype: torch.dtype,

@@ -18,6 +18,8 @@ Noise level (``sigma``, denoise variants): a number, a list with one number per 
 histograms of the luma's 2 x 2 Haar HH coefficient, made on the device from the payloads the window has uploaded anyway
 (``sn_yuv_noise_hist``, shiftnet_amd/noise.py).  ``sigma_estimator="temporal"`` / ``"min"`` adds the same statistic of the difference of consecutive
 input frames (``sn_yuv_noise_hist_pairs``), in which texture that does not move cancels, and uses it alone or the lower of the two.
+``sigma_motion="blocks"`` lets that difference follow the picture: one integer vector per 16 x 16 luma block and pair, found on the device
+(``sn_yuv_block_motion``), so that a pan no longer reads as noise.
 
 Noise model (``noise_model``, denoise variants, off by default): sensor noise is signal dependent, the shadows of R'G'B' carry more of it than the
 highlights.  ``"level"`` estimates per window a noise-level function -- sigma against the luma code, 16 knots -- from the same histograms split by
@@ -56,7 +58,7 @@ import numpy as np
 from .restore_cli import amount_arg, main, make_parser, picture_arg, sigma_arg  # noqa: F401 -- the command line (restore_cli.py), reached through this module
 from .windows import (DITHERS, FUTURE, PAST, PerWindow, _Frames, _SceneFrames, _Thread, amount_form, noise_model_form, pad_multiple,  # noqa: F401
                       padded_size, picture_form, plan_output, plan_scene_windows, plan_windows, reflect_index, report_form, scene_cuts_form,
-                      sigma_estimator_form, sigma_form, window_indices)
+                      sigma_estimator_form, sigma_form, sigma_motion_form, window_indices)
 
 VARIANTS = {"deblur": "gshift_deblur1", "deblur_small": "gshift_deblur2", "denoise": "gshift_denoise1", "denoise_small": "gshift_denoise2"}
 
@@ -105,6 +107,8 @@ class _Slot:
         self.used = False                                         # in this restore(): a window has gone through the slot
         self.noise = self.bands = self.sums = None                # _Stat: the window's histograms, band histograms, row and column sums
         self.pairs = self.pair_bands = None                       # _Stat: the histograms and band histograms of the window's frame pairs
+        self.motion = self.motion_sad = None                      # sigma_motion: _Stat of the pairs' block vectors (flat int8), their SADs on the device
+        self.motion_grid = (0, 0)                                 # ... and the vector blocks of the window the slot holds
         self.dev_ref = None                                       # a mix or a report with another format out: the window's input payloads in the format written
         self.report = None                                        # _Stat: the sums of written minus input of the window's own frames
 
@@ -123,7 +127,8 @@ class _Run:
         self.window_sigma_spatial: List = []                      # sigma_estimator other than "spatial": the two estimates before the rule and the clamp
         self.window_sigma_temporal: List = []
         self.window_pair_sigma: List = []
-        self.launches = {"noise": 0, "nlf": 0, "nlf_map": 0, "picture": 0, "thumb": 0, "noise_pairs": 0, "nlf_pairs": 0, "report": 0}
+        self.window_pair_motion: List = []                        # sigma_motion: per window, per pair, noise.motion_summary's triple
+        self.launches = {"noise": 0, "nlf": 0, "nlf_map": 0, "picture": 0, "thumb": 0, "noise_pairs": 0, "nlf_pairs": 0, "report": 0, "motion": 0}
         self.frame_sums: List = []                                # report: the 16 sums of every frame handed out, the window it came from, that window's sigma
         self.frame_window: List[int] = []
         self.frame_sigma: List = []
@@ -262,6 +267,18 @@ class VideoRestorer:
     two estimates of every window before the rule and the clamp; None where no pair has one), ``window_pair_sigma`` (per window, one entry per pair, None
     allowed), ``noise_pairs_launches`` and, with ``"level"``, ``nlf_pairs_launches``; ``window_sigma``, ``window_frame_sigma`` and ``window_nlf`` keep their
     meaning: what the window was restored with, the per-frame spatial values, the curve used.
+    sigma_motion: None -- the pairs compare every 2 x 2 block with the block at the same place in the next frame, today's launches, bytes and stats keys;
+    ``"blocks"`` (needs ``sigma_estimator="temporal"`` or ``"min"``) -- once per window ``sn_yuv_block_motion`` (side stream) finds for every pair and
+    every 16 x 16 luma block the integer translation within +-7 samples with the smallest sum of absolute differences, and
+    ``sn_yuv_noise_hist_pairs_mv`` runs IN PLACE OF the plain pair histogram (with ``noise_model="level"`` ``..._bands_mv`` in place of the plain band
+    one): the next frame's block is taken where the vector points.  The vector is chosen on one half of the 2 x 2 blocks (checkerboard parity even) and
+    the statistic taken from the other half, so that the choice cannot fit the noise it is measured on (noise.py).  The vectors and their SADs live in
+    per-slot device buffers; the vectors come back to the host in pinned memory (137 KB for a 720p window of 20 frames).  **A heuristic, checked on
+    synthetic clips only**: integer-pel translation per block; sub-pixel motion, zoom, rotation, occlusion and changing motion blur still read as noise;
+    temporally correlated noise still reads LOW; on flat content the estimate reads a few per cent HIGH.  With ``picture`` the vectors are those of the
+    window's rectangle; a cut inside a window stays one outlier pair.  ``stats`` then also has ``sigma_motion`` and ``window_pair_motion`` (per window,
+    per pair: the share of blocks with a nonzero vector, the median dy, the median dx), ``noise_launches`` counts the ``sn_yuv_block_motion`` launches
+    beside the spatial histogram's, and ``noise_pairs_launches`` / ``nlf_pairs_launches`` count the ``_mv`` launches.
     report: False -- today's launches, bytes and stats keys; True -- behind every window's egress one more launch (``sn_yuv_diff_stats``, main stream)
     sums d = written - input over the window's own frames: the payloads written against the input frames in the format written -- the payloads read, or
     with ``out_format`` the input converted as ``amount`` defines it (``egress(out format, ingest_float32(in format, frame))``, undithered) -- inside the
@@ -280,7 +297,7 @@ class VideoRestorer:
                  cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0),
                  picture=None, bar_level: float = 1.0, out_format=None, dither=None, dither_seed: int = 0, noise_model=None,
                  amount=None, view=None, removed_gain: float = 1.0, sigma_estimator: str = "spatial", report: bool = False,
-                 report_edge: float = 16.0) -> None:
+                 report_edge: float = 16.0, sigma_motion=None) -> None:
         import torch
         from .lib import YuvFmt
         from .noise import check_clamp
@@ -305,6 +322,7 @@ class VideoRestorer:
             raise ValueError(f"sigma={'auto' if self.sigma_mode == 'auto' else 'a per-window list'!r} is for the denoise variants; {type(net).__name__} "
                              "of a deblur variant takes no noise level")
         self.sigma_estimator = sigma_estimator_form(sigma_estimator, self.sigma_mode)      # "spatial": the code path without any of the rest
+        self.sigma_motion = sigma_motion_form(sigma_motion, self.sigma_estimator)      # None: the code path without any of the rest
         if noise_model is not None and not self.V.denoise:
             raise ValueError(f"noise_model is for the denoise variants; {type(net).__name__} of a deblur variant takes no noise level")
         # None (the code path without any of the rest), "level", "list" (a PerWindow)
@@ -371,6 +389,11 @@ class VideoRestorer:
                 s.pairs = _Stat(torch, dev, "noise_pairs", tin - 1, [(pair_bins(fmt.bits),)])
                 if self.nlf_mode == "level":
                     s.pair_bands = _Stat(torch, dev, "nlf_pairs", tin - 1, [(NLF_BANDS, nlf_bins(fmt.bits))])
+            if self.sigma_motion is not None:                     # the vectors of the largest window's pairs at the full frame's grid, flat: a
+                from .noise import motion_grid                    # window's are a view of the leading elements at the grid of its picture
+                blocks = (tin - 1) * int(np.prod(motion_grid(h, w)))
+                s.motion = _Stat(torch, dev, "motion", 2 * blocks, [()], torch.int8)
+                s.motion_sad = torch.empty(blocks, dtype=torch.uint32, device=dev)
             if self.picture_mode == "auto":
                 s.sums = _Stat(torch, dev, "picture", tin, [(h,), (w,)])
             if self.report:                                       # one row per frame the window writes
@@ -400,7 +423,8 @@ class VideoRestorer:
     def _stage(self, slot: _Slot, frames: Sequence[np.ndarray], t0: int = 0) -> int:
         """Host frames -> pinned slot -> device -> RGB tensors, on the side stream.  Windows are staged in the order they are restored.
         t0: the number of the window's first restored frame in its clip (the dither's frame number)."""
-        from .io_edges import ingest_yuv, noise_hist_bands_yuv, noise_hist_pairs_bands_yuv, noise_hist_pairs_yuv, noise_hist_yuv, rowcol_sums_yuv
+        from .io_edges import (block_motion_yuv, ingest_yuv, noise_hist_bands_yuv, noise_hist_pairs_bands_mv_yuv, noise_hist_pairs_bands_yuv,
+                               noise_hist_pairs_mv_yuv, noise_hist_pairs_yuv, noise_hist_yuv, rowcol_sums_yuv)
         torch, run = self.torch, self.run
         t = len(frames)
         rect = self._window_picture()
@@ -432,13 +456,28 @@ class VideoRestorer:
                 # the histograms of the payloads just uploaded, ahead of the ingest so that they are on the host long before _run asks.  The
                 # pinned twin is free: _run read it on the host before this slot was handed back to the stager
                 slot.noise.launch(t, run, lambda out: noise_hist_yuv(payloads, self.fmt, self.h, self.w, self.noise_lo, self.noise_hi, out=out, rect=rect))
-            if slot.pairs is not None:                           # the statistic of the t - 1 pairs of consecutive payloads (t >= 5: a window has 4 neighbours)
+            mv = None
+            if slot.motion is not None:
+                # the vectors of the t - 1 pairs, once per window and ahead of the histograms that follow them; their copy to the host is for stats alone
+                from .noise import motion_grid
+                gy, gx = slot.motion_grid = motion_grid(*self._size(rect)[:2])
+                blocks = (t - 1) * gy * gx
+                mv = slot.motion.dev[0][:2 * blocks].view(t - 1, gy, gx, 2)
+                sad = slot.motion_sad[:blocks].view(t - 1, gy, gx)
+                slot.motion.launch(2 * blocks, run, lambda out: block_motion_yuv(payloads, self.fmt, self.h, self.w, rect=rect, out_mv=mv, out_sad=sad))
+            if slot.pairs is not None and mv is not None:        # ... in place of the plain pair histogram
+                slot.pairs.launch(t - 1, run, lambda out: noise_hist_pairs_mv_yuv(payloads, self.fmt, self.h, self.w, mv, self.noise_lo, self.noise_hi,
+                                                                                  out=out, rect=rect))
+            elif slot.pairs is not None:                         # the statistic of the t - 1 pairs of consecutive payloads (t >= 5: a window has 4 neighbours)
                 slot.pairs.launch(t - 1, run, lambda out: noise_hist_pairs_yuv(payloads, self.fmt, self.h, self.w, self.noise_lo, self.noise_hi, out=out,
                                                                                rect=rect))
             if self.nlf_mode == "level":                         # the same statistic by brightness band, from the same payloads, behind it
                 slot.bands.launch(t, run, lambda out: noise_hist_bands_yuv(payloads, self.fmt, self.h, self.w, self.noise_lo, self.noise_hi, out=out,
                                                                            rect=rect))
-            if slot.pair_bands is not None:
+            if slot.pair_bands is not None and mv is not None:
+                slot.pair_bands.launch(t - 1, run, lambda out: noise_hist_pairs_bands_mv_yuv(payloads, self.fmt, self.h, self.w, mv, self.noise_lo,
+                                                                                             self.noise_hi, out=out, rect=rect))
+            elif slot.pair_bands is not None:
                 slot.pair_bands.launch(t - 1, run, lambda out: noise_hist_pairs_bands_yuv(payloads, self.fmt, self.h, self.w, self.noise_lo,
                                                                                           self.noise_hi, out=out, rect=rect))
             ingest_yuv(payloads, self.fmt, self.h, self.w, hp, wp, self.dtype, out=x, rect=rect)
@@ -465,6 +504,11 @@ class VideoRestorer:
                 run.window_pair_sigma.append(ps)
                 run.window_sigma_spatial.append(spatial)
                 run.window_sigma_temporal.append(temporal)
+                if slot.motion is not None:
+                    from .noise import motion_summary
+                    gy, gx = slot.motion_grid
+                    flat, = slot.motion.wait(2 * (t - 1) * gy * gx)
+                    run.window_pair_motion.append(motion_summary(flat.reshape(t - 1, gy, gx, 2)))
                 sigma = combine_sigma(spatial, temporal, self.sigma_estimator, self.sigma_clamp)
         else:
             sigma = self.sigma.at(len(run.window_sigma))
@@ -567,7 +611,7 @@ class VideoRestorer:
         stats["window_forward_ms"] = ms
         stats["forward_s"] = sum(ms) / 1e3
         stats["windows"] = len(ms)
-        stats["noise_launches"] = run.launches["noise"]
+        stats["noise_launches"] = run.launches["noise"] + run.launches["motion"]      # "motion" stays 0 without sigma_motion
         if self.nlf_mode is not None:
             stats["window_nlf"] = [list(c) for c in run.window_nlf]
             stats["nlf_launches"], stats["nlf_map_launches"] = run.launches["nlf"], run.launches["nlf_map"]
@@ -586,6 +630,9 @@ class VideoRestorer:
                 stats["noise_pairs_launches"] = run.launches["noise_pairs"]
                 if self.nlf_mode == "level":
                     stats["nlf_pairs_launches"] = run.launches["nlf_pairs"]
+                if self.sigma_motion is not None:
+                    stats["sigma_motion"] = self.sigma_motion
+                    stats["window_pair_motion"] = [list(p) for p in run.window_pair_motion]
         if self.report:
             from .report import frames_report, summarize
             stats["frame_sums"] = [list(r) for r in run.frame_sums]

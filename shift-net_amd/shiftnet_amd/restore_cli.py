@@ -73,6 +73,11 @@ def make_parser() -> argparse.ArgumentParser:
                     help="--sigma auto only: 'temporal' estimates the noise from the difference of consecutive frames, in which texture that does not move "
                          "cancels (temporally correlated noise -- inter-coded or temporally denoised footage -- reads low); 'min' takes the lower of that and "
                          "the spatial estimate; with --noise_model level the curve follows band by band; default spatial: each frame on its own")
+    ap.add_argument("--sigma_motion", choices=["none", "blocks"], default="none",
+                    help="--sigma_estimator temporal / min only: 'blocks' finds one integer vector (within +-7 px) per 16 x 16 luma block and frame pair on the "
+                         "device and lets the temporal estimate follow it, so that a pan does not read as noise (a heuristic, checked on synthetic clips "
+                         "only: sub-pixel motion, zoom and rotation still read as noise, and flat content reads a few per cent high); default none: every "
+                         "block is compared with the block at the same place")
     ap.add_argument("--sigma_out", default=None, metavar="FILE", help="write the sigma that every window was restored with, in the format --sigma FILE reads")
     ap.add_argument("--noise_model", default="flat", metavar="{flat,level,FILE}",
                     help="denoise variants: 'level' (needs --sigma auto) estimates per window the noise level as a function of brightness on the device and "
@@ -178,6 +183,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--sigma is required by the denoise variants")
     if a.sigma_estimator != "spatial" and a.sigma != "auto":      # before the file of a --sigma FILE is opened
         ap.error(f"--sigma_estimator {a.sigma_estimator} needs --sigma auto")
+    if a.sigma_motion != "none" and a.sigma_estimator == "spatial":      # as above: before any file is opened
+        ap.error(f"--sigma_motion {a.sigma_motion} needs --sigma_estimator temporal or min")
     log = lambda s: (sys.stderr.write(s + "\n"), sys.stderr.flush())      # noqa: E731
     sigma, sigma_how = a.sigma, "fixed"
     if isinstance(sigma, str):
@@ -225,7 +232,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                            cut_ratio=a.cut_ratio, sigma_clamp=a.sigma_clamp, picture=picture, bar_level=a.bar_level, out_format=a.out_format,
                            dither=None if a.dither == "none" else a.dither, dither_seed=a.dither_seed, noise_model=noise_model,
                            amount=a.amount, view=view, removed_gain=a.removed_gain, sigma_estimator=a.sigma_estimator,
-                           report=a.report is not None, report_edge=a.report_edge)
+                           report=a.report is not None, report_edge=a.report_edge, sigma_motion=None if a.sigma_motion == "none" else a.sigma_motion)
         if a.out_format is not None or a.dither != "none":
             log(f"output: C{a.out_format or hd.chroma}{'' if a.out_format else ' (as the input)'}, dither {a.dither}"
                 f"{' seed %d' % a.dither_seed if a.dither != 'none' else ''}")
@@ -264,7 +271,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             log(f"noise model ({nlf_how}): knots min {min(min(c) for c in wn):.2f} / max {max(max(c) for c in wn):.2f} over {len(wn)} "
                 f"window{'' if len(wn) == 1 else 's'}")
         if ws:
-            log(f"sigma ({sigma_how}{', ' + a.sigma_estimator if a.sigma_estimator != 'spatial' else ''}{', clamped to [%g, %g]' % tuple(a.sigma_clamp) if sigma_how == 'auto' else ''}): "
+            log(f"sigma ({sigma_how}{', ' + a.sigma_estimator if a.sigma_estimator != 'spatial' else ''}{', motion ' + a.sigma_motion if a.sigma_motion != 'none' else ''}{', clamped to [%g, %g]' % tuple(a.sigma_clamp) if sigma_how == 'auto' else ''}): "
                 f"min {min(ws):.2f} / median {float(np.median(ws)):.2f} / max {max(ws):.2f} over {len(ws)} window{'' if len(ws) == 1 else 's'}")
         if a.report is not None:
             fr = vr.stats["frame_report"]

@@ -149,6 +149,22 @@ def sigma_estimator_form(sigma_estimator, sigma_mode: str = "auto") -> str:
     return word
 
 
+MOTIONS = ("blocks",)
+
+
+def sigma_motion_form(sigma_motion, sigma_estimator: str = "min"):
+    """None | "blocks" -> the same; ValueError for anything else, and for "blocks" with sigma_estimator="spatial": the vectors compensate the frame
+    pairs of the temporal estimate, and the spatial one has no pairs."""
+    if sigma_motion is None:
+        return None
+    if not (isinstance(sigma_motion, str) and sigma_motion in MOTIONS):
+        raise ValueError(f"sigma_motion must be None or 'blocks', got {sigma_motion!r}")
+    if sigma_estimator == "spatial":
+        raise ValueError(f"sigma_motion={sigma_motion!r} compensates the frame pairs of the temporal estimate: it needs sigma_estimator='temporal' or 'min', "
+                         "not 'spatial'")
+    return sigma_motion
+
+
 VIEWS = ("removed",)
 
 

@@ -30,6 +30,10 @@
             clean twin, edge 16) beside sn_egress_yuv from float32 and sn_yuv_noise_hist_pairs on the same frames, interleaved as in the kernels part.
             --mode forward: steady-state wall time per 720p window of the pipelined denoiser (as the sigma part, sigma=10.0) with report=False and with
             report=True, runs of the two alternating in one process, the first two windows left out.
+  motion  : the motion-compensated temporal estimate (3.23).  --mode kernels: time per launch of sn_yuv_block_motion, sn_yuv_noise_hist_pairs_mv and
+            sn_yuv_noise_hist_pairs_bands_mv beside the two plain pair histograms (4:2:0 8 bit, 720p x 20 frames with noise of sigma 10), interleaved as
+            in the kernels part.  --mode forward: steady-state wall time per 720p window of the pipelined denoiser (as the sigma part) with
+            sigma_estimator="min" alone and with sigma_motion="blocks" on top, runs of the two alternating in one process, the first two windows left out.
 Prints one JSON object per part.
 """
 import argparse
@@ -49,7 +53,7 @@ import torch  # noqa: E402
 
 from shiftnet_amd import lib as L  # noqa: E402
 from shiftnet_amd import restore, synth, y4m  # noqa: E402
-from shiftnet_amd.io_edges import (diff_stats_yuv, egress_u8, egress_yuv, ingest_u8, ingest_yuv, noise_hist_bands_yuv, noise_hist_pairs_bands_yuv, noise_hist_pairs_yuv,  # noqa: E402
+from shiftnet_amd.io_edges import (block_motion_yuv, noise_hist_pairs_bands_mv_yuv, noise_hist_pairs_mv_yuv, diff_stats_yuv, egress_u8, egress_yuv, ingest_u8, ingest_yuv, noise_hist_bands_yuv, noise_hist_pairs_bands_yuv, noise_hist_pairs_yuv,  # noqa: E402
                                    noise_hist_yuv, noise_map_level, rowcol_sums_yuv, thumb_yuv, yuv_fmt)
 
 
@@ -319,6 +323,88 @@ def nlf_forward(a):
                       "runs": a.runs, "window_nlf_first": [round(k, 3) for k in seen["level"][0]], **res}))
 
 
+def motion_kernels(a):
+    """3.23: the matcher and the two histograms along its vectors beside the two plain pair histograms, 720p x 20 frames, 8 bit 4:2:0, interleaved."""
+    T, H, W = 20, 720, 1280
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    blur, _ = synth.blurred_clip(4, H, W, seed=1)
+    rgb = ingest_u8(torch.from_numpy(np.concatenate([blur] * 5)).cuda(), torch.float32)[0]
+    pay = egress_yuv((rgb + torch.randn(rgb.shape, device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * (10.0 / 255)).clamp(0, 1), fmt, H, W)
+    pairs = torch.empty((T - 1, 1021), dtype=torch.uint32, device="cuda")
+    pair_bands = torch.empty((T - 1, 16, 128), dtype=torch.uint32, device="cuda")
+    mv, sad = block_motion_yuv(pay, fmt, H, W)
+    cases = {
+        "noise_hist_pairs_yuv": lambda: noise_hist_pairs_yuv(pay, fmt, H, W, out=pairs),
+        "noise_hist_pairs_bands_yuv": lambda: noise_hist_pairs_bands_yuv(pay, fmt, H, W, out=pair_bands),
+        "block_motion_yuv": lambda: block_motion_yuv(pay, fmt, H, W, out_mv=mv, out_sad=sad),
+        "noise_hist_pairs_mv_yuv": lambda: noise_hist_pairs_mv_yuv(pay, fmt, H, W, mv, out=pairs),
+        "noise_hist_pairs_bands_mv_yuv": lambda: noise_hist_pairs_bands_mv_yuv(pay, fmt, H, W, mv, out=pair_bands),
+    }
+    for f in cases.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in cases}
+    for _ in range(a.reps):
+        for k, f in cases.items():                                                   # interleaved: every repetition times every kernel
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.inner):
+                f()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.inner)
+    px = (T - 1) * H * W                                                             # per pixel of a pair
+    res = {k: {"us_per_launch": summary([m * 1e3 for m in v]), "ps_per_pixel": summary([m * 1e9 / px for m in v])} for k, v in ms.items()}
+    nz = float((mv != 0).any(dim=3).float().mean())
+    print(json.dumps({"part": "motion", "mode": "kernels", "frames": T, "size": [H, W], "reps": a.reps, "inner": a.inner, "nonzero_vectors": round(nz, 4), **res}))
+
+
+def motion_forward(a):
+    """3.23: steady-state wall time per 720p window of the pipelined denoiser with sigma_estimator="min", without and with sigma_motion="blocks",
+    alternating (the stream and the pattern of the sigma part)."""
+    H, W, one_len, nwin = 720, 1280, 16, a.windows
+    n = one_len * nwin
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    blur, _ = synth.blurred_clip(8, H, W, seed=2)
+    rgb = ingest_u8(torch.from_numpy(blur).cuda(), torch.float32)[0]
+    g = torch.Generator("cuda").manual_seed(1)
+    frames = []
+    for i in range(n):                                                               # fresh noise of sigma 10 on every frame, as the sigma part
+        j = i % 14
+        x = rgb[j if j < 8 else 14 - j][None]
+        frames.append(egress_yuv((x + torch.randn(x.shape, device="cuda", generator=g) * (10.0 / 255)).clamp(0, 1), fmt, H, W)[0].cpu().numpy())
+    net = restore.load_net("denoise_small", "synthetic", "bf16")
+    seen = {}
+
+    def run(motion):
+        vr = restore.VideoRestorer(net, one_len, sigma="auto", pipeline=True, sigma_estimator="min", sigma_motion=motion)
+        stamps = []
+        t0 = time.perf_counter()
+        for i, p in enumerate(vr.restore(iter(frames), fmt, H, W)):
+            if (i + 1) % one_len == 0:
+                stamps.append(time.perf_counter())
+        total = time.perf_counter() - t0
+        seen[str(motion)] = (vr.stats["window_sigma"], vr.stats["window_sigma_temporal"])
+        gaps = [(b - c) * 1e3 for b, c in zip(stamps[1:], stamps[:-1])]
+        return {"total_s": total, "window_wall_ms": gaps[1:], "window_forward_ms": vr.stats["window_forward_ms"][2:]}
+
+    run(None)                                                                        # warm-up: code objects, engine buffers
+    run("blocks")
+    runs = {"min": [], "min_blocks": []}
+    for _ in range(a.runs):
+        runs["min"].append(run(None))
+        runs["min_blocks"].append(run("blocks"))
+    res = {}
+    for k, rs in runs.items():
+        res[k] = {"window_wall_ms": summary([g for r in rs for g in r["window_wall_ms"]]),
+                  "window_wall_ms_per_run": [round(statistics.median(r["window_wall_ms"]), 2) for r in rs],
+                  "window_forward_ms": summary([g for r in rs for g in r["window_forward_ms"]]), "total_s": [round(r["total_s"], 3) for r in rs]}
+    print(json.dumps({"part": "motion", "mode": "forward", "variant": "denoise_small", "dtype": "bf16", "one_len": one_len, "windows": nwin, "size": [H, W],
+                      "runs": a.runs, "window_sigma_min": [round(s, 3) for s in seen["None"][0]], "window_sigma_min_blocks": [round(s, 3) for s in seen["blocks"][0]],
+                      "window_temporal_min": [round(s, 3) for s in seen["None"][1]], "window_temporal_min_blocks": [round(s, 3) for s in seen["blocks"][1]], **res}))
+
+
 def report_kernels(a):
     T, H, W = 16, 720, 1280
     fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
@@ -536,7 +622,7 @@ def picture_part(a):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report"])
+    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion"])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--inner", type=int, default=200)
     ap.add_argument("--windows", type=int, default=8)
@@ -547,10 +633,11 @@ if __name__ == "__main__":
     ap.add_argument("--parent_lib", default=None, metavar="SO", help="kernels part and picture part in kernels mode: a shared library built from another commit's "
                     "csrc/sn_yuv.hip alone; its sn_ingest_yuv / sn_egress_yuv are timed beside this build's")
     ap.add_argument("--only_cases", default=None, metavar="WORDS", help="kernels part: time only the cases whose name contains one of these comma-separated words")
-    ap.add_argument("--mode", choices=["forward", "kernels"], default="forward", help="picture, nlf and report parts: which measurement")
+    ap.add_argument("--mode", choices=["forward", "kernels"], default="forward", help="picture, nlf, report and motion parts: which measurement")
     ap.add_argument("--picture", choices=["auto", "fixed"], default="auto", help="picture part, forward mode: VideoRestorer(picture='auto') or the rectangle itself")
     a = ap.parse_args()
     with torch.no_grad():
         {"kernels": kernels, "pipeline": pipeline, "sigma": sigma, "picture": picture_part,
          "nlf": nlf_kernels if a.mode == "kernels" else nlf_forward,
-         "report": report_kernels if a.mode == "kernels" else report_forward}[a.part](a)
+         "report": report_kernels if a.mode == "kernels" else report_forward,
+         "motion": motion_kernels if a.mode == "kernels" else motion_forward}[a.part](a)
