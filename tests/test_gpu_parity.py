@@ -942,7 +942,8 @@ def test_denoise_unit_is_reproducible_under_allocator_churn():
 @pytest.mark.parametrize("name,p1key", [("gshift_deblur2", "p1r"), ("gshift_deblur1", "p1r")])
 def test_squeeze_excite_fold_matches_ca_mlp_and_is_reproducible(name, p1key, engines):
     """sn_se_fold: the last workgroup of each frame of the fused phase-1 launch finishes CALayer2 (fixed-order reduction of the partial sums
-    + the MLP).  Against sn_ca_mlp on the very same partial sums (another summation order: 1e-6), bit-identical over repeated launches
+    + the MLP).  Against sn_ca_mlp on the very same partial sums (another summation order: 1e-6; sn_ca_mlp itself is held to float64 in
+    tests/test_gpu_ca_kernels.py), bit-identical over repeated launches
     whichever workgroup arrives last, counters left at zero -- at a production size (6 x 360 x 640: row chunks that cross strips and frames,
     two or three walks per strip and frame) and a small one."""
     from shiftnet_amd import lib as L
