@@ -21,6 +21,8 @@
 //   sn_yuv_diff_stats : two sets of T payloads, what came in and what was written -> [T][16] int64 sums of their difference in all three planes: its
 //                   moments, its products with the right, lower and next-frame neighbour, its energy on the edges of the written picture (the method-noise
 //                   report of shiftnet_amd/report.py is computed from these on the host); rect or the whole frame.
+// The seven sn_yuv_noise_hist* entry points launch the instances of ONE kernel template, yuv_noise_hist_kernel<sample size, kind, bands>, from one
+// host function; every other entry point has a kernel of its own.
 //
 // All but the noise map are integer reductions: sums commute, so the results are the same for every launch geometry and every schedule, and the numpy
 // restatements of tests/ equal them exactly.  The noise map is float32 arithmetic with every product and sum rounded separately (contraction is
@@ -30,11 +32,11 @@
 
 namespace {
 
-// The kernels below repeat two pieces of code on purpose: the 8-sample row load with its tree sum and element-wise edge path (thumbnail, noise map,
-// row/column sums) and the unit walk of the two histogram kernels.  Each was moved into one __forceinline__ function (pointer and by-value results,
-// a functor per block and per unit were tried for the walk) and every formulation changed the instruction stream of the kernels that used it, some
-// their register counts too: the helper is simplified on its own before it is inlined, and the scheduler then sees another order.  A kernel added
-// here should copy the piece it needs; one that changes it should change the copies together.
+// The thumbnail, noise-map and row/column kernels below repeat one piece of code on purpose: the 8-sample row load with its tree sum and element-wise
+// edge path.  It was moved into one __forceinline__ function (pointer and by-value results) and every formulation changed the instruction stream of
+// the kernels that used it, some their register counts too: the helper is simplified on its own before it is inlined, and the scheduler then sees
+// another order.  A kernel that changes that piece should change the copies together.  The noise histograms are the other way round: one kernel body
+// whose variants are template parameters, held to its results, resources and time per launch rather than to an instruction order.
 
 // ---- thumbnail ------------------------------------------------------------------------------------------------------------------
 // A lane owns one 8 x 8 luma block: 8 rows of one 8 B (10 bit: 16 B) load where the address allows it, element-wise on the right edge
@@ -67,123 +69,137 @@ __global__ __launch_bounds__(256) void yuv_thumb_kernel(const uint8_t* __restric
     dst[((size_t)t * hb + by) * wb + bx] = (uint16_t)sum;
 }
 
-// ---- noise histogram ------------------------------------------------------------------------------------------------------------
-// v = |a - b - c + d| of every non-overlapping 2 x 2 luma block (twice its Haar HH coefficient), counted where all four codes lie strictly
-// between lo and hi.  A lane owns four horizontally adjacent blocks (8 x 2 pixels: one 8 B / 16 B load per row where the ADDRESS allows it,
-// element-wise otherwise and where fewer than four blocks are left on the right edge); a workgroup walks units gridDim.x * 256 apart of one
-// frame and keeps that frame's histogram in LDS: bins >= LOW in one array of NB words, bins < LOW -- where nearly all of the mass lies --
-// in 32 copies, copy (lane & 31) at word v * 32 + (lane & 31).  An LDS instruction is served in lane groups 0..31 and 32..63 and a b32
-// access banks by word mod 32, so the 32 lanes of a group hit 32 different banks whatever their v: a wave's add to the low bins never
-// meets a bank conflict or a second lane on its own address.  At the end the copies are summed and the non-zero bins added to dst with
-// one global atomic each.  Integer sums commute: the result is the same for every geometry and every schedule.
-template <int ESZ> struct NoiseK {
-    static constexpr int NB = 2 * ((ESZ == 1 ? 256 : 1024) - 1) + 1;      // 511 / 2047
-    static constexpr int LOW = ESZ == 1 ? 32 : 128;                       // the same range of noise levels at both depths
+// ---- noise histograms ---------------------------------------------------------------------------------------------------------------
+// One kernel for the six noise statistics, at both depths twelve instances.  KIND says what is measured on a non-overlapping 2 x 2 luma block with the
+// codes p q / r s and HH = p - q - r + s (twice its Haar HH coefficient):
+//   HIST_SPATIAL  : v = |HH| of payload blockIdx.y, counted where the four codes lie strictly between lo and hi;
+//   HIST_PAIRS    : v = |HH(payload p + 1) - HH(payload p)| of the same block in both payloads of pair p = blockIdx.y, counted where all EIGHT codes
+//                   lie strictly between lo and hi.  Content that does not move cancels and the noise of both frames stays: v has the variance
+//                   8 s^2 + 2/3 where the spatial statistic has 4 s^2 + 1/3.  The second payload lies frame_bytes further on, which need not be a
+//                   multiple of 16: every load tests its own address and takes the element-wise path on its own;
+//   HIST_PAIRS_MV : the pair statistic on the MEASURING blocks, (i + j) odd, with the four codes of payload p + 1 taken at (2 i + dy, 2 j + dx), (dy, dx)
+//                   the vector that yuv_block_motion_kernel (below) found on the other half of block (i / 8, j / 8).  The displaced block is at no
+//                   particular alignment and is loaded element-wise, after the test that it lies inside the picture: mv is device memory nobody has
+//                   validated, and with the test any int8 contents are safe -- a block whose displaced position is not wholly inside the h x w picture
+//                   does not count, and nothing outside the picture is read.
+// BANDS splits the count by the brightness of the block: band = (4 (S - 4 lo)) / (hi - lo) with S the sum of the four codes, (2 (S - 8 lo)) / (hi - lo)
+// with the sum of the eight; every code is > lo and < hi, so 4 <= S - 4 lo <= 4 (hi - lo) - 4 (8 and 8 (hi - lo) - 8) and the band is 0 .. 15.  v is
+// then saturated to NBV - 1.
+// The walk: a lane owns a unit of four horizontally adjacent blocks (8 x 2 pixels: one 8 B / 16 B load per row where the ADDRESS allows it, element-wise
+// otherwise and where fewer than four blocks are left on the right edge); a workgroup walks units gridDim.x * 256 apart of one frame or pair.  A unit's
+// four blocks lie in one vector block (4 divides 8) and two of them measure: blocks 1 and 3 in an even block row, 0 and 2 in an odd one.
+// The histogram, [NBANDS][NBV] words, lives in LDS: the bins v >= LOW in one plain array, the bins v < LOW -- where nearly all of the mass lies, and
+// neighbouring blocks are mostly of one brightness, so of one band -- in COPIES copies, copy (lane & (COPIES - 1)) at word (band * LOW + v) * COPIES +
+// copy.  An LDS instruction is served in lane groups 0..31 and 32..63 and a b32 access banks by word mod 32, so with 32 copies the 32 lanes of a group
+// hit 32 different banks whatever their bins: a wave's add to the low bins never meets a bank conflict or a second lane on its own address.  With
+// fewer copies neighbouring lanes are on different copies and lanes COPIES apart share one.  At the end the copies are summed, each lane starting at
+// another copy so that the lanes of a group read different banks, and the non-zero bins are added to dst with one global atomic each.  Integer sums
+// commute: the result is the same for every geometry and every schedule.
+// The constants.  NBV: every value of v, 2 (2^bits - 1) + 1 and twice as far for pairs; with bands 128 / 512.  LOW covers the same range of noise
+// levels at both depths and in every form: 32 / 128 bins flat and 16 / 64 by band for the spatial statistic, and 1.5 times that for pairs, whose v is
+// sqrt(2) times as wide at the same noise level.  COPIES is 32, except 8 and 4 for the 10-bit band forms, spatial and pairs, where 32 copies of 16 x
+// 64 (96) bins do not fit beside the 32 KB of the plain array -- at 10 bit v spreads over four times as many bins, so lanes meet on a word less often
+// to begin with.  (DESIGN.md 3.25 has the LDS, registers and time of every instance.)
+enum { HIST_SPATIAL, HIST_PAIRS, HIST_PAIRS_MV };
+
+template <int ESZ, int KIND, bool BANDS> struct HistK {
+    static constexpr bool PAIR = KIND != HIST_SPATIAL;
+    static constexpr int CODES = ESZ == 1 ? 256 : 1024;
+    static constexpr int NBANDS = BANDS ? SN_NLF_BANDS : 1;
+    static constexpr int NBV = BANDS ? CODES / 2 : (PAIR ? 4 : 2) * (CODES - 1) + 1;      // 128 / 512; 511 / 2047, pairs 1021 / 4093
+    static constexpr int LOW = CODES / (BANDS ? 16 : 8) * (PAIR ? 3 : 2) / 2;            // 16 / 64, pairs 24 / 96; 32 / 128, pairs 48 / 192
+    static constexpr int COPIES = BANDS && ESZ == 2 ? (PAIR ? 4 : 8) : 32;
+    static constexpr int LOWW = NBANDS * LOW * COPIES, HISTW = NBANDS * NBV;
+    static constexpr bool ZERO16 = LOWW % 4 == 0 && HISTW % 4 == 0;                      // the band forms: both arrays are zeroed 16 B at a time
 };
 
-template <int ESZ>
-__global__ __launch_bounds__(256) void yuv_noise_hist_kernel(const uint8_t* __restrict__ src, uint32_t* __restrict__ dst, int lo, int hi, int W,
-                                                           int hb, int wb, int ux, size_t origin, size_t frame_bytes) {
-    constexpr int NB = NoiseK<ESZ>::NB, LOW = NoiseK<ESZ>::LOW;
-    __shared__ uint32_t low[LOW * 32];
-    __shared__ uint32_t hist[NB];
-    const int tid = threadIdx.x, t = blockIdx.y, cp = tid & 31;
-    for (int i = tid; i < LOW * 32; i += 256) low[i] = 0;
-    for (int i = tid; i < NB; i += 256) hist[i] = 0;
+// HIST_PAIRS_MV has one argument more, the vectors, their grid and the picture's size; the other kinds have none in its place (the pack is empty),
+// so that their argument list is what the kernels before the template had
+struct HistMvK { const int8_t* mv; int h, w, nby, nbx; };
+
+template <int ESZ, int KIND, bool BANDS, typename... MVK>
+__global__ __launch_bounds__(256) void yuv_noise_hist_kernel(const uint8_t* __restrict__ src, uint32_t* __restrict__ dst, int lo, int hi, int W, int hb,
+                                                           int wb, int ux, size_t origin, size_t frame_bytes, const MVK... mvk) {
+    using K = HistK<ESZ, KIND, BANDS>;
+    constexpr int NBV = K::NBV, LOW = K::LOW, COPIES = K::COPIES, LOWW = K::LOWW, HISTW = K::HISTW;
+    constexpr bool PAIRS = KIND == HIST_PAIRS, MV = KIND == HIST_PAIRS_MV;
+    static_assert(sizeof...(mvk) == (MV ? 1 : 0));
+    [[maybe_unused]] const HistMvK M = [&] { if constexpr (MV) return (mvk, ...); else return HistMvK{}; }();
+    __shared__ __attribute__((aligned(K::ZERO16 ? 16 : 4))) uint32_t low[LOWW];
+    __shared__ __attribute__((aligned(K::ZERO16 ? 16 : 4))) uint32_t hist[HISTW];
+    const int tid = threadIdx.x, t = blockIdx.y, cp = tid & (COPIES - 1);      // t: the frame, or the pair of payloads t and t + 1 <= T - 1
+    if constexpr (K::ZERO16) {
+        for (int i = tid; i < LOWW / 4; i += 256) ((uint4*)low)[i] = make_uint4(0u, 0u, 0u, 0u);
+        for (int i = tid; i < HISTW / 4; i += 256) ((uint4*)hist)[i] = make_uint4(0u, 0u, 0u, 0u);
+    } else {
+        for (int i = tid; i < LOWW; i += 256) low[i] = 0;
+        for (int i = tid; i < HISTW; i += 256) hist[i] = 0;
+    }
     __syncthreads();
-    const uint8_t* yp = src + (size_t)t * frame_bytes + origin;           // W: the luma row pitch; origin: the byte offset of block (0, 0)
+    const uint8_t* y0 = src + (size_t)t * frame_bytes + origin;           // W: the luma row pitch; origin: the byte offset of block (0, 0)
+    const uint8_t* y1 = y0 + frame_bytes;
     const int units = ux * hb;                                            // hb, wb: whole 2 x 2 blocks; ux = ceil(wb / 4) units per block row
-    for (int u = blockIdx.x * 256 + tid; u < units; u += gridDim.x * 256) {
-        const int by = u / ux, bx0 = (u - by * ux) * 4;
-        const int nb = imin(4, wb - bx0);
-        const size_t r0 = (size_t)(2 * by) * W + 2 * bx0, r1 = r0 + W;
-        int a[8], b[8];
-        if (nb == 4) {
-            ldn<ESZ, 8>(yp, r0, a);
-            ldn<ESZ, 8>(yp, r1, b);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {                                 // pixels 2 bx0 .. 2 (bx0 + nb) - 1 < 2 wb <= W exist; the others are not read
-                const bool in = k < 2 * nb;
-                a[k] = in ? ld1<ESZ>(yp, r0 + k) : 0;
-                b[k] = in ? ld1<ESZ>(yp, r1 + k) : 0;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int p = a[2 * k], q = a[2 * k + 1], r = b[2 * k], s = b[2 * k + 1];
-            const int mn = imin(imin(p, q), imin(r, s)), mx = imax(imax(p, q), imax(r, s));
-            if (k < nb && mn > lo && mx < hi) {
-                const int d = p - q - r + s, v = d < 0 ? -d : d;          // 0 .. 2 (2^bits - 1) = NB - 1
-                if (v < LOW) atomicAdd(&low[v * 32 + cp], 1u);
-                else atomicAdd(&hist[v], 1u);
-            }
-        }
-    }
-    __syncthreads();
-    uint32_t* out = dst + (size_t)t * NB;
-    for (int i = tid; i < NB; i += 256) {
-        uint32_t n = hist[i];
-        if (i < LOW) {
-#pragma unroll 8
-            for (int c = 0; c < 32; ++c) n += low[i * 32 + ((c + i) & 31)];   // rotated by the bin: the lanes of a group read 32 different banks
-        }
-        if (n) atomicAdd(&out[i], n);
-    }
-}
-
-// ---- noise histogram by brightness band -------------------------------------------------------------------------------------------------
-// yuv_noise_hist_kernel split by the block's brightness: band = (4 (S - 4 lo)) / (hi - lo) with S = a + b + c + d, 0 .. 15 for every block that
-// counts (each code is > lo and < hi, so 4 <= S - 4 lo <= 4 (hi - lo) - 4), and v saturated to NBV - 1.  The same units, loads and walk; the
-// workgroup's histogram is [16][NBV] words of LDS.  A band is a range of brightness and neighbouring blocks are mostly of one brightness, so a wave's
-// adds still meet in a few (band, v) pairs: the bins v < LOW of every band are kept in COPIES copies, copy (lane & (COPIES - 1)) at word
-// (band * LOW + v) * COPIES + copy.  At 8 bit COPIES = 32 and the 32 lanes of a lane group hit 32 different banks whatever their bins; at 10 bit
-// LOW covers the same range of noise levels (64 bins) and 32 copies of 16 x 64 bins do not fit: 8 copies, neighbouring lanes on different copies, lanes
-// 8 apart share one.  The other bins go to the plain array.  Integer sums commute: the result is the same for every geometry and every schedule.
-template <int ESZ> struct BandK {
-    static constexpr int NBV = ESZ == 1 ? 128 : 512;
-    static constexpr int LOW = ESZ == 1 ? 16 : 64;
-    static constexpr int COPIES = ESZ == 1 ? 32 : 8;
-    static constexpr int LOWW = SN_NLF_BANDS * LOW * COPIES;             // 8192 words at both depths
-    static constexpr int HISTW = SN_NLF_BANDS * NBV;                     // 2048 / 8192 words
-};
-
-template <int ESZ>
-__global__ __launch_bounds__(256) void yuv_noise_hist_bands_kernel(const uint8_t* __restrict__ src, uint32_t* __restrict__ dst, int lo, int hi, int W,
-                                                                 int hb, int wb, int ux, size_t origin, size_t frame_bytes) {
-    constexpr int NBV = BandK<ESZ>::NBV, LOW = BandK<ESZ>::LOW, COPIES = BandK<ESZ>::COPIES, LOWW = BandK<ESZ>::LOWW, HISTW = BandK<ESZ>::HISTW;
-    __shared__ __attribute__((aligned(16))) uint32_t low[LOWW];
-    __shared__ __attribute__((aligned(16))) uint32_t hist[HISTW];
-    const int tid = threadIdx.x, t = blockIdx.y, cp = tid & (COPIES - 1);
-    for (int i = tid; i < LOWW / 4; i += 256) ((uint4*)low)[i] = make_uint4(0u, 0u, 0u, 0u);
-    for (int i = tid; i < HISTW / 4; i += 256) ((uint4*)hist)[i] = make_uint4(0u, 0u, 0u, 0u);
-    __syncthreads();
-    const uint8_t* yp = src + (size_t)t * frame_bytes + origin;           // as yuv_noise_hist_kernel: W is the luma row pitch, origin the byte offset of block (0, 0)
-    const int units = ux * hb;
     const uint32_t span = (uint32_t)(hi - lo);
     for (int u = blockIdx.x * 256 + tid; u < units; u += gridDim.x * 256) {
         const int by = u / ux, bx0 = (u - by * ux) * 4;
         const int nb = imin(4, wb - bx0);
         const size_t r0 = (size_t)(2 * by) * W + 2 * bx0, r1 = r0 + W;
-        int a[8], b[8];
+        [[maybe_unused]] int yd = 0, dx = 0;                              // HIST_PAIRS_MV: the displaced block's first row, and the vector's dx
+        if constexpr (MV) {
+            const int8_t* v2 = M.mv + (((size_t)t * M.nby + (by >> 3)) * M.nbx + (bx0 >> 3)) * 2;      // by / 8 < nby and bx0 / 8 < nbx: inside mv whatever it holds
+            yd = 2 * by + v2[0], dx = v2[1];
+        }
+        int a0[8], b0[8], a1[8], b1[8];
         if (nb == 4) {
-            ldn<ESZ, 8>(yp, r0, a);
-            ldn<ESZ, 8>(yp, r1, b);
+            ldn<ESZ, 8>(y0, r0, a0);
+            ldn<ESZ, 8>(y0, r1, b0);
+            if constexpr (PAIRS) {
+                ldn<ESZ, 8>(y1, r0, a1);
+                ldn<ESZ, 8>(y1, r1, b1);
+            }
         } else {
 #pragma unroll
             for (int k = 0; k < 8; ++k) {                                 // pixels 2 bx0 .. 2 (bx0 + nb) - 1 < 2 wb <= W exist; the others are not read
                 const bool in = k < 2 * nb;
-                a[k] = in ? ld1<ESZ>(yp, r0 + k) : 0;
-                b[k] = in ? ld1<ESZ>(yp, r1 + k) : 0;
+                a0[k] = in ? ld1<ESZ>(y0, r0 + k) : 0;
+                b0[k] = in ? ld1<ESZ>(y0, r1 + k) : 0;
+                if constexpr (PAIRS) {
+                    a1[k] = in ? ld1<ESZ>(y1, r0 + k) : 0;
+                    b1[k] = in ? ld1<ESZ>(y1, r1 + k) : 0;
+                }
             }
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int p = a[2 * k], q = a[2 * k + 1], r = b[2 * k], s = b[2 * k + 1];
-            const int mn = imin(imin(p, q), imin(r, s)), mx = imax(imax(p, q), imax(r, s));
-            if (k < nb && mn > lo && mx < hi) {
-                const int d = p - q - r + s, v = imin(d < 0 ? -d : d, NBV - 1);
-                const int band = (int)((uint32_t)(4 * ((p + q) + (r + s) - 4 * lo)) / span);      // 0 .. 15 (above)
+            const int p0 = a0[2 * k], q0 = a0[2 * k + 1], r0c = b0[2 * k], s0 = b0[2 * k + 1];
+            int p1 = 0, q1 = 0, r1c = 0, s1 = 0;                          // the block of payload t + 1
+            if constexpr (MV) {
+                const int xd = 2 * (bx0 + k) + dx;                        // rows yd, yd + 1 must lie in 0 .. h - 1 and columns xd, xd + 1 in 0 .. w - 1
+                if (!(k < nb && ((by + k) & 1) && yd >= 0 && yd + 2 <= M.h && xd >= 0 && xd + 2 <= M.w)) continue;      // bx0 is even: (by + k) is the parity of
+                                                                          // (i + j); nothing is loaded for a block that does not count
+                const size_t o = (size_t)yd * W + xd;
+                p1 = ld1<ESZ>(y1, o), q1 = ld1<ESZ>(y1, o + 1), r1c = ld1<ESZ>(y1, o + W), s1 = ld1<ESZ>(y1, o + W + 1);
+            } else if constexpr (PAIRS) {
+                p1 = a1[2 * k], q1 = a1[2 * k + 1], r1c = b1[2 * k], s1 = b1[2 * k + 1];
+            }
+            int mn, mx;
+            if constexpr (K::PAIR) {
+                mn = imin(imin(imin(p0, q0), imin(r0c, s0)), imin(imin(p1, q1), imin(r1c, s1)));
+                mx = imax(imax(imax(p0, q0), imax(r0c, s0)), imax(imax(p1, q1), imax(r1c, s1)));
+            } else {
+                mn = imin(imin(p0, q0), imin(r0c, s0)), mx = imax(imax(p0, q0), imax(r0c, s0));
+            }
+            if ((MV || k < nb) && mn > lo && mx < hi) {
+                const int d = K::PAIR ? (p1 - q1 - r1c + s1) - (p0 - q0 - r0c + s0) : p0 - q0 - r0c + s0;
+                // a code of the format gives v <= NBV - 1.  Where hi admits stored 16-bit words above 2^bits - 1 the flat spatial and pair forms index past
+                // hist, as they always did: inside the workgroup's own LDS the count lands on another bin, beyond it the hardware drops the access
+                int v = d < 0 ? -d : d;
+                if constexpr (BANDS || MV) v = imin(v, NBV - 1);
+                int band = 0;
+                if constexpr (BANDS) {                                    // 0 .. 15 (above)
+                    if constexpr (K::PAIR) band = (int)((uint32_t)(2 * (((p0 + q0) + (r0c + s0)) + ((p1 + q1) + (r1c + s1)) - 8 * lo)) / span);
+                    else band = (int)((uint32_t)(4 * ((p0 + q0) + (r0c + s0) - 4 * lo)) / span);
+                }
                 if (v < LOW) atomicAdd(&low[(band * LOW + v) * COPIES + cp], 1u);
                 else atomicAdd(&hist[band * NBV + v], 1u);
             }
@@ -193,161 +209,11 @@ __global__ __launch_bounds__(256) void yuv_noise_hist_bands_kernel(const uint8_t
     uint32_t* out = dst + (size_t)t * HISTW;
     for (int i = tid; i < HISTW; i += 256) {
         uint32_t n = hist[i];
-        const int band = i / NBV, v = i - band * NBV;
+        const int band = BANDS ? i / NBV : 0, v = i - band * NBV;
         if (v < LOW) {
             const uint32_t* c = low + (band * LOW + v) * COPIES;
             const int rot = (i * COPIES) >> 5;                            // consecutive bins start on different copies: the lanes of a group read 32 different banks
 #pragma unroll 8
-            for (int k = 0; k < COPIES; ++k) n += c[(k + rot) & (COPIES - 1)];
-        }
-        if (n) atomicAdd(&out[i], n);
-    }
-}
-
-// ---- noise histograms of frame pairs ----------------------------------------------------------------------------------------------------
-// The temporal siblings of the two kernels above: v = |HH(payload p + 1) - HH(payload p)| with HH = a - b - c + d of the same 2 x 2 block in both
-// payloads, counted where all EIGHT codes lie strictly between lo and hi; blockIdx.y is the pair.  Content that does not move cancels in v and
-// the noise of both frames stays: v has the variance 8 s^2 + 2/3 where the spatial statistic has 4 s^2 + 1/3.  The same units and the same walk
-// (copied, not shared: see the note at the top of this namespace), with four loads per lane instead of two -- the same two rows of both payloads.  The
-// second payload lies frame_bytes further on, which need not be a multiple of 16: every load tests its own address and takes the element-wise path
-// on its own.  The histogram lives in LDS as above.  v is sqrt(2) times as wide as the spatial statistic at the same noise level and reaches twice
-// as far, so NB doubles and LOW is 1.5 times the spatial kernel's (48 / 192 bins: 6 / 24 KB of copies beside the 4 / 16 KB of the plain array): the
-// copies cover the noise levels they cover there.  Integer sums commute: the result is the same for every geometry and every schedule.
-template <int ESZ> struct PairK {
-    static constexpr int NB = 4 * ((ESZ == 1 ? 256 : 1024) - 1) + 1;      // 1021 / 4093
-    static constexpr int LOW = ESZ == 1 ? 48 : 192;                       // 1.5 x NoiseK::LOW >= sqrt(2) x: the same range of noise levels
-};
-
-template <int ESZ>
-__global__ __launch_bounds__(256) void yuv_noise_hist_pairs_kernel(const uint8_t* __restrict__ src, uint32_t* __restrict__ dst, int lo, int hi, int W,
-                                                                 int hb, int wb, int ux, size_t origin, size_t frame_bytes) {
-    constexpr int NB = PairK<ESZ>::NB, LOW = PairK<ESZ>::LOW;
-    __shared__ uint32_t low[LOW * 32];
-    __shared__ uint32_t hist[NB];
-    const int tid = threadIdx.x, pr = blockIdx.y, cp = tid & 31;
-    for (int i = tid; i < LOW * 32; i += 256) low[i] = 0;
-    for (int i = tid; i < NB; i += 256) hist[i] = 0;
-    __syncthreads();
-    const uint8_t* y0 = src + (size_t)pr * frame_bytes + origin;          // payload pr; W: the luma row pitch; origin: the byte offset of block (0, 0)
-    const uint8_t* y1 = y0 + frame_bytes;                                 // payload pr + 1 <= T - 1
-    const int units = ux * hb;                                            // hb, wb: whole 2 x 2 blocks; ux = ceil(wb / 4) units per block row
-    for (int u = blockIdx.x * 256 + tid; u < units; u += gridDim.x * 256) {
-        const int by = u / ux, bx0 = (u - by * ux) * 4;
-        const int nb = imin(4, wb - bx0);
-        const size_t r0 = (size_t)(2 * by) * W + 2 * bx0, r1 = r0 + W;
-        int a0[8], b0[8], a1[8], b1[8];
-        if (nb == 4) {
-            ldn<ESZ, 8>(y0, r0, a0);
-            ldn<ESZ, 8>(y0, r1, b0);
-            ldn<ESZ, 8>(y1, r0, a1);
-            ldn<ESZ, 8>(y1, r1, b1);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {                                 // pixels 2 bx0 .. 2 (bx0 + nb) - 1 < 2 wb <= W exist; the others are not read
-                const bool in = k < 2 * nb;
-                a0[k] = in ? ld1<ESZ>(y0, r0 + k) : 0;
-                b0[k] = in ? ld1<ESZ>(y0, r1 + k) : 0;
-                a1[k] = in ? ld1<ESZ>(y1, r0 + k) : 0;
-                b1[k] = in ? ld1<ESZ>(y1, r1 + k) : 0;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int p0 = a0[2 * k], q0 = a0[2 * k + 1], r0c = b0[2 * k], s0 = b0[2 * k + 1];
-            const int p1 = a1[2 * k], q1 = a1[2 * k + 1], r1c = b1[2 * k], s1 = b1[2 * k + 1];
-            const int mn = imin(imin(imin(p0, q0), imin(r0c, s0)), imin(imin(p1, q1), imin(r1c, s1)));
-            const int mx = imax(imax(imax(p0, q0), imax(r0c, s0)), imax(imax(p1, q1), imax(r1c, s1)));
-            if (k < nb && mn > lo && mx < hi) {
-                const int d = (p1 - q1 - r1c + s1) - (p0 - q0 - r0c + s0), v = d < 0 ? -d : d;      // 0 .. 4 (2^bits - 1) = NB - 1
-                if (v < LOW) atomicAdd(&low[v * 32 + cp], 1u);
-                else atomicAdd(&hist[v], 1u);
-            }
-        }
-    }
-    __syncthreads();
-    uint32_t* out = dst + (size_t)pr * NB;
-    for (int i = tid; i < NB; i += 256) {
-        uint32_t n = hist[i];
-        if (i < LOW) {
-#pragma unroll 8
-            for (int c = 0; c < 32; ++c) n += low[i * 32 + ((c + i) & 31)];   // rotated by the bin: the lanes of a group read 32 different banks
-        }
-        if (n) atomicAdd(&out[i], n);
-    }
-}
-
-// The pair statistic by brightness band: band = (2 (S - 8 lo)) / (hi - lo) with S the sum of the eight codes, 0 .. 15 for every block that counts
-// (8 <= S - 8 lo <= 8 (hi - lo) - 8), v saturated to NBV - 1 with the NBV of the spatial band kernel.  [16][NBV] words of LDS and copies of the bins
-// v < LOW of every band, as there.  LOW is again 1.5 times the spatial kernel's: 24 bins at 8 bit with 32 copies (48 KB + 8 KB); at 10 bit 96 bins
-// cover the same noise levels and leave room for 4 copies (24 KB + 32 KB; 8 copies of 96 bins would need 48 KB + 32 KB), neighbouring lanes on
-// different copies, lanes 4 apart share one -- at 10 bit v spreads over four times as many bins, so lanes meet on a word less often to begin with.
-template <int ESZ> struct PairBandK {
-    static constexpr int NBV = BandK<ESZ>::NBV;                          // 128 / 512
-    static constexpr int LOW = ESZ == 1 ? 24 : 96;
-    static constexpr int COPIES = ESZ == 1 ? 32 : 4;
-    static constexpr int LOWW = SN_NLF_BANDS * LOW * COPIES;             // 12288 / 6144 words
-    static constexpr int HISTW = SN_NLF_BANDS * NBV;                     // 2048 / 8192 words
-};
-
-template <int ESZ>
-__global__ __launch_bounds__(256) void yuv_noise_hist_pairs_bands_kernel(const uint8_t* __restrict__ src, uint32_t* __restrict__ dst, int lo, int hi,
-                                                                       int W, int hb, int wb, int ux, size_t origin, size_t frame_bytes) {
-    constexpr int NBV = PairBandK<ESZ>::NBV, LOW = PairBandK<ESZ>::LOW, COPIES = PairBandK<ESZ>::COPIES, LOWW = PairBandK<ESZ>::LOWW,
-                  HISTW = PairBandK<ESZ>::HISTW;
-    __shared__ __attribute__((aligned(16))) uint32_t low[LOWW];
-    __shared__ __attribute__((aligned(16))) uint32_t hist[HISTW];
-    const int tid = threadIdx.x, pr = blockIdx.y, cp = tid & (COPIES - 1);
-    for (int i = tid; i < LOWW / 4; i += 256) ((uint4*)low)[i] = make_uint4(0u, 0u, 0u, 0u);
-    for (int i = tid; i < HISTW / 4; i += 256) ((uint4*)hist)[i] = make_uint4(0u, 0u, 0u, 0u);
-    __syncthreads();
-    const uint8_t* y0 = src + (size_t)pr * frame_bytes + origin;          // as yuv_noise_hist_pairs_kernel
-    const uint8_t* y1 = y0 + frame_bytes;
-    const int units = ux * hb;
-    const uint32_t span = (uint32_t)(hi - lo);
-    for (int u = blockIdx.x * 256 + tid; u < units; u += gridDim.x * 256) {
-        const int by = u / ux, bx0 = (u - by * ux) * 4;
-        const int nb = imin(4, wb - bx0);
-        const size_t r0 = (size_t)(2 * by) * W + 2 * bx0, r1 = r0 + W;
-        int a0[8], b0[8], a1[8], b1[8];
-        if (nb == 4) {
-            ldn<ESZ, 8>(y0, r0, a0);
-            ldn<ESZ, 8>(y0, r1, b0);
-            ldn<ESZ, 8>(y1, r0, a1);
-            ldn<ESZ, 8>(y1, r1, b1);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {                                 // pixels 2 bx0 .. 2 (bx0 + nb) - 1 < 2 wb <= W exist; the others are not read
-                const bool in = k < 2 * nb;
-                a0[k] = in ? ld1<ESZ>(y0, r0 + k) : 0;
-                b0[k] = in ? ld1<ESZ>(y0, r1 + k) : 0;
-                a1[k] = in ? ld1<ESZ>(y1, r0 + k) : 0;
-                b1[k] = in ? ld1<ESZ>(y1, r1 + k) : 0;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int p0 = a0[2 * k], q0 = a0[2 * k + 1], r0c = b0[2 * k], s0 = b0[2 * k + 1];
-            const int p1 = a1[2 * k], q1 = a1[2 * k + 1], r1c = b1[2 * k], s1 = b1[2 * k + 1];
-            const int mn = imin(imin(imin(p0, q0), imin(r0c, s0)), imin(imin(p1, q1), imin(r1c, s1)));
-            const int mx = imax(imax(imax(p0, q0), imax(r0c, s0)), imax(imax(p1, q1), imax(r1c, s1)));
-            if (k < nb && mn > lo && mx < hi) {
-                const int d = (p1 - q1 - r1c + s1) - (p0 - q0 - r0c + s0), v = imin(d < 0 ? -d : d, NBV - 1);
-                const int S = ((p0 + q0) + (r0c + s0)) + ((p1 + q1) + (r1c + s1));
-                const int band = (int)((uint32_t)(2 * (S - 8 * lo)) / span);                         // 0 .. 15 (above)
-                if (v < LOW) atomicAdd(&low[(band * LOW + v) * COPIES + cp], 1u);
-                else atomicAdd(&hist[band * NBV + v], 1u);
-            }
-        }
-    }
-    __syncthreads();
-    uint32_t* out = dst + (size_t)pr * HISTW;
-    for (int i = tid; i < HISTW; i += 256) {
-        uint32_t n = hist[i];
-        const int band = i / NBV, v = i - band * NBV;
-        if (v < LOW) {
-            const uint32_t* c = low + (band * LOW + v) * COPIES;
-            const int rot = (i * COPIES) >> 5;                            // as yuv_noise_hist_bands_kernel: lanes whose copies start on one bank begin at different copies
-#pragma unroll 4
             for (int k = 0; k < COPIES; ++k) n += c[(k + rot) & (COPIES - 1)];
         }
         if (n) atomicAdd(&out[i], n);
@@ -441,95 +307,6 @@ __global__ __launch_bounds__(256) void yuv_block_motion_kernel(const uint8_t* __
         mv[2 * o] = (int8_t)(c / MV_D - MV_R);
         mv[2 * o + 1] = (int8_t)(c % MV_D - MV_R);
         sad[o] = k >> 8;
-    }
-}
-
-// ---- noise histograms of frame pairs along the vectors ----------------------------------------------------------------------------------------
-// yuv_noise_hist_pairs_kernel and its band sibling on the MEASURING 2 x 2 blocks, (i + j) odd, with the four codes of payload p + 1 taken at
-// (2 i + dy, 2 j + dx), (dy, dx) the vector of block (i / 8, j / 8).  One kernel for both: NBANDS = 1 is the flat histogram (NBV = NBP bins, 32
-// copies of the bins below LOW), NBANDS = 16 the band histogram, with the constants and the LDS layout of the two kernels above.  The same units
-// and the same walk: a unit's four blocks lie in one vector block (4 divides 8) and two of them measure, blocks 1 and 3 of the unit in an even block
-// row and 0 and 2 in an odd one.  Payload p is loaded as there; the displaced block of payload p + 1 is at no particular alignment and is loaded
-// element-wise, after the test that it lies inside the picture: mv is device memory nobody has validated, and with the test any int8 contents are
-// safe -- a block whose displaced position is not wholly inside the h x w picture does not count, and nothing outside the picture is read.
-template <int ESZ, bool BANDS> struct MvHistK {
-    static constexpr int NBANDS = BANDS ? SN_NLF_BANDS : 1;
-    static constexpr int NBV = BANDS ? PairBandK<ESZ>::NBV : PairK<ESZ>::NB;
-    static constexpr int LOW = BANDS ? PairBandK<ESZ>::LOW : PairK<ESZ>::LOW;
-    static constexpr int COPIES = BANDS ? PairBandK<ESZ>::COPIES : 32;
-    static constexpr int LOWW = NBANDS * LOW * COPIES, HISTW = NBANDS * NBV;
-};
-
-template <int ESZ, bool BANDS>
-__global__ __launch_bounds__(256) void yuv_noise_hist_pairs_mv_kernel(const uint8_t* __restrict__ src, const int8_t* __restrict__ mv,
-                                                                    uint32_t* __restrict__ dst, int lo, int hi, int h, int w, int W, int hb, int wb, int ux,
-                                                                    int nby, int nbx, size_t origin, size_t frame_bytes) {
-    using K = MvHistK<ESZ, BANDS>;
-    constexpr int NBV = K::NBV, LOW = K::LOW, COPIES = K::COPIES, LOWW = K::LOWW, HISTW = K::HISTW;
-    __shared__ uint32_t low[LOWW];
-    __shared__ uint32_t hist[HISTW];
-    const int tid = threadIdx.x, pr = blockIdx.y, cp = tid & (COPIES - 1);
-    for (int i = tid; i < LOWW; i += 256) low[i] = 0;
-    for (int i = tid; i < HISTW; i += 256) hist[i] = 0;
-    __syncthreads();
-    const uint8_t* y0 = src + (size_t)pr * frame_bytes + origin;          // as yuv_noise_hist_pairs_kernel
-    const uint8_t* y1 = y0 + frame_bytes;
-    const int8_t* vec = mv + (size_t)pr * nby * nbx * 2;
-    const int units = ux * hb;
-    const uint32_t span = (uint32_t)(hi - lo);
-    for (int u = blockIdx.x * 256 + tid; u < units; u += gridDim.x * 256) {
-        const int by = u / ux, bx0 = (u - by * ux) * 4;
-        const int nb = imin(4, wb - bx0);
-        const size_t r0 = (size_t)(2 * by) * W + 2 * bx0, r1 = r0 + W;
-        const int8_t* v2 = vec + ((size_t)(by >> 3) * nbx + (bx0 >> 3)) * 2;      // by / 8 < nby and bx0 / 8 < nbx: inside mv whatever it holds
-        const int dy = v2[0], dx = v2[1];
-        int a0[8], b0[8];
-        if (nb == 4) {
-            ldn<ESZ, 8>(y0, r0, a0);
-            ldn<ESZ, 8>(y0, r1, b0);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {                                 // pixels 2 bx0 .. 2 (bx0 + nb) - 1 < 2 wb <= W exist; the others are not read
-                const bool in = k < 2 * nb;
-                a0[k] = in ? ld1<ESZ>(y0, r0 + k) : 0;
-                b0[k] = in ? ld1<ESZ>(y0, r1 + k) : 0;
-            }
-        }
-        const int yd = 2 * by + dy;                                       // the displaced block's first row: rows yd, yd + 1 must lie in 0 .. h - 1
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int xd = 2 * (bx0 + k) + dx;                            // ... and columns xd, xd + 1 in 0 .. w - 1
-            if (k < nb && ((by + k) & 1) && yd >= 0 && yd + 2 <= h && xd >= 0 && xd + 2 <= w) {      // bx0 is even: (by + k) is the parity of (i + j)
-                const size_t o = (size_t)yd * W + xd;
-                const int p0 = a0[2 * k], q0 = a0[2 * k + 1], r0c = b0[2 * k], s0 = b0[2 * k + 1];
-                const int p1 = ld1<ESZ>(y1, o), q1 = ld1<ESZ>(y1, o + 1), r1c = ld1<ESZ>(y1, o + W), s1 = ld1<ESZ>(y1, o + W + 1);
-                const int mn = imin(imin(imin(p0, q0), imin(r0c, s0)), imin(imin(p1, q1), imin(r1c, s1)));
-                const int mx = imax(imax(imax(p0, q0), imax(r0c, s0)), imax(imax(p1, q1), imax(r1c, s1)));
-                if (mn > lo && mx < hi) {
-                    const int d = (p1 - q1 - r1c + s1) - (p0 - q0 - r0c + s0), v = imin(d < 0 ? -d : d, NBV - 1);      // flat: v <= NBP - 1 as it is
-                    int band = 0;
-                    if (BANDS) {
-                        const int S = ((p0 + q0) + (r0c + s0)) + ((p1 + q1) + (r1c + s1));
-                        band = (int)((uint32_t)(2 * (S - 8 * lo)) / span);                               // 0 .. 15 (yuv_noise_hist_pairs_bands_kernel)
-                    }
-                    if (v < LOW) atomicAdd(&low[(band * LOW + v) * COPIES + cp], 1u);
-                    else atomicAdd(&hist[band * NBV + v], 1u);
-                }
-            }
-        }
-    }
-    __syncthreads();
-    uint32_t* out = dst + (size_t)pr * HISTW;
-    for (int i = tid; i < HISTW; i += 256) {
-        uint32_t n = hist[i];
-        const int band = i / NBV, v = i - band * NBV;
-        if (v < LOW) {
-            const uint32_t* c = low + (band * LOW + v) * COPIES;
-            const int rot = (i * COPIES) >> 5;                            // as yuv_noise_hist_bands_kernel: lanes whose copies start on one bank begin at different copies
-#pragma unroll 4
-            for (int k = 0; k < COPIES; ++k) n += c[(k + rot) & (COPIES - 1)];
-        }
-        if (n) atomicAdd(&out[i], n);
     }
 }
 
@@ -814,6 +591,41 @@ __global__ __launch_bounds__(256) void yuv_diff_stats_kernel(const uint8_t* a, c
 }
 }  // namespace
 
+// The seven histogram entry points: one kernel instance each way.  T payloads are T frames or T - 1 pairs; mv is looked at by the vector forms alone
+template <int KIND, bool BANDS>
+static int noise_hist(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const int8_t* mv, uint32_t* dst, int lo, int hi, int T, int H, int W,
+                      void* stream) {
+    constexpr bool PAIR = KIND != HIST_SPATIAL, MV = KIND == HIST_PAIRS_MV;
+    sn_clear_error();
+    if (!valid_payloads(src, fmt, T, H, W) || !dst || ((uintptr_t)dst & 3) || lo > hi) return SN_EINVAL;
+    if ((PAIR && T < 2) || (MV && !mv)) return SN_EINVAL;                  // T - 1 <= 65534 pairs: a grid dimension
+    if ((BANDS || PAIR) && (lo < -(1 << 24) || hi > (1 << 24))) return SN_EINVAL;      // the band is 32-bit arithmetic: 4 (S - 4 lo), 2 (S - 8 lo) must fit
+    YuvGeo G;
+    if (!make_geo(fmt, H, W, rect, &G)) return SN_EINVAL;
+    const int n = PAIR ? T - 1 : T;
+    int words = 0;
+    with_esz(fmt, [&](auto esz) { words = HistK<esz(), KIND, BANDS>::HISTW; });
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(dst, 0, (size_t)n * words * sizeof(uint32_t), s) != hipSuccess) return sn_check_launch();      // dst is overwritten, not added to
+    const int hb = G.h / 2, wb = G.w / 2, ux = (wb + 3) / 4;               // the block grid is anchored at the picture's first sample
+    if (hb < 1 || wb < 1) return sn_check_launch();                        // no whole block: all-zero histograms
+    const long long units = (long long)ux * hb;
+    if (units > 0x7fffffffLL - 1024 * 256) return SN_EINVAL;
+    // 8 units (32 blocks) per lane, with bands 16: the zeroing, the sum of the copies and the flush (bands: of 40 to 64 KB of LDS) are paid once per
+    // 8192 / 16384 blocks, and a 720p frame is 29 / 15 workgroups
+    const long long per = BANDS ? 4096 : 2048, wgs = (units + per - 1) / per;
+    const dim3 block(256), grid(wgs < 1024 ? (int)wgs : 1024, n);
+    with_esz(fmt, [&](auto esz) {
+        if constexpr (MV) {
+            const HistMvK M = {mv, G.h, G.w, (hb + 7) / 8, (wb + 7) / 8};      // the vector blocks: 8 x 8 of the 2 x 2 blocks
+            hipLaunchKernelGGL((yuv_noise_hist_kernel<esz(), KIND, BANDS, HistMvK>), grid, block, 0, s, src, dst, lo, hi, W, hb, wb, ux, G.oy, G.frame_bytes, M);
+        } else {
+            hipLaunchKernelGGL((yuv_noise_hist_kernel<esz(), KIND, BANDS>), grid, block, 0, s, src, dst, lo, hi, W, hb, wb, ux, G.oy, G.frame_bytes);
+        }
+    });
+    return sn_check_launch();
+}
+
 extern "C" {
 
 int sn_yuv_thumb(const uint8_t* src, const sn_yuv_fmt* fmt, uint16_t* dst, int T, int H, int W, void* stream) {
@@ -828,81 +640,39 @@ int sn_yuv_thumb(const uint8_t* src, const sn_yuv_fmt* fmt, uint16_t* dst, int T
     return sn_check_launch();
 }
 
-// The histogram entry points: they differ in the kernel, in the words per frame of dst and in the units (of four 2 x 2 blocks) a workgroup walks
-static int noise_hist(bool bands, const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint32_t* dst, int lo, int hi, int T, int H, int W,
-                      void* stream) {
-    sn_clear_error();
-    if (!valid_payloads(src, fmt, T, H, W) || !dst || ((uintptr_t)dst & 3) || lo > hi) return SN_EINVAL;
-    if (bands && (lo < -(1 << 24) || hi > (1 << 24))) return SN_EINVAL;    // the band is 32-bit arithmetic: 4 (S - 4 lo) must fit
-    YuvGeo G;
-    if (!make_geo(fmt, H, W, rect, &G)) return SN_EINVAL;
-    int words = 0;
-    with_esz(fmt, [&](auto esz) { words = bands ? BandK<esz()>::HISTW : NoiseK<esz()>::NB; });
-    hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(dst, 0, (size_t)T * words * sizeof(uint32_t), s) != hipSuccess) return sn_check_launch();      // dst is overwritten, not added to
-    const int hb = G.h / 2, wb = G.w / 2, ux = (wb + 3) / 4;               // the block grid is anchored at the picture's first sample
-    if (hb < 1 || wb < 1) return sn_check_launch();                        // no whole block: all-zero histograms
-    const long long units = (long long)ux * hb;
-    if (units > 0x7fffffffLL - 1024 * 256) return SN_EINVAL;
-    // 8 units (32 blocks) per lane, with bands 16: the zeroing, the sum of the copies and the flush (bands: of 40 / 64 KB of LDS) are paid once per
-    // 8192 / 16384 blocks, and a 720p frame is 29 / 15 workgroups
-    const long long per = bands ? 4096 : 2048, wgs = (units + per - 1) / per;
-    const dim3 block(256), grid(wgs < 1024 ? (int)wgs : 1024, T);
-    with_esz(fmt, [&](auto esz) {
-        if (bands) hipLaunchKernelGGL((yuv_noise_hist_bands_kernel<esz()>), grid, block, 0, s, src, dst, lo, hi, W, hb, wb, ux, G.oy, G.frame_bytes);
-        else hipLaunchKernelGGL((yuv_noise_hist_kernel<esz()>), grid, block, 0, s, src, dst, lo, hi, W, hb, wb, ux, G.oy, G.frame_bytes);
-    });
-    return sn_check_launch();
-}
-
 int sn_yuv_noise_hist(const uint8_t* src, const sn_yuv_fmt* fmt, uint32_t* dst, int lo, int hi, int T, int H, int W, void* stream) {
-    return noise_hist(false, src, fmt, nullptr, dst, lo, hi, T, H, W, stream);
+    return noise_hist<HIST_SPATIAL, false>(src, fmt, nullptr, nullptr, dst, lo, hi, T, H, W, stream);
 }
 
 int sn_yuv_noise_hist_rect(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint32_t* dst, int lo, int hi, int T, int H, int W,
                            void* stream) {
     if (!rect) { sn_clear_error(); return SN_EINVAL; }
-    return noise_hist(false, src, fmt, rect, dst, lo, hi, T, H, W, stream);
+    return noise_hist<HIST_SPATIAL, false>(src, fmt, rect, nullptr, dst, lo, hi, T, H, W, stream);
 }
 
 int sn_yuv_noise_hist_bands(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint32_t* dst, int lo, int hi, int T, int H, int W,
                             void* stream) {
-    return noise_hist(true, src, fmt, rect, dst, lo, hi, T, H, W, stream);
-}
-
-// The pair histograms: T payloads are T - 1 pairs, blockIdx.y is the pair; the rest is noise_hist's
-static int noise_hist_pairs(bool bands, const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint32_t* dst, int lo, int hi, int T, int H,
-                            int W, void* stream) {
-    sn_clear_error();
-    if (!valid_payloads(src, fmt, T, H, W) || T < 2 || !dst || ((uintptr_t)dst & 3) || lo > hi) return SN_EINVAL;     // T - 1 <= 65534 pairs: a grid dimension
-    if (lo < -(1 << 24) || hi > (1 << 24)) return SN_EINVAL;               // the band is 32-bit arithmetic: 2 (S - 8 lo) must fit
-    YuvGeo G;
-    if (!make_geo(fmt, H, W, rect, &G)) return SN_EINVAL;
-    int words = 0;
-    with_esz(fmt, [&](auto esz) { words = bands ? PairBandK<esz()>::HISTW : PairK<esz()>::NB; });
-    hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(dst, 0, (size_t)(T - 1) * words * sizeof(uint32_t), s) != hipSuccess) return sn_check_launch();      // dst is overwritten, not added to
-    const int hb = G.h / 2, wb = G.w / 2, ux = (wb + 3) / 4;               // the block grid is anchored at the picture's first sample
-    if (hb < 1 || wb < 1) return sn_check_launch();                        // no whole block: all-zero histograms
-    const long long units = (long long)ux * hb;
-    if (units > 0x7fffffffLL - 1024 * 256) return SN_EINVAL;
-    const long long per = bands ? 4096 : 2048, wgs = (units + per - 1) / per;      // units per workgroup as noise_hist
-    const dim3 block(256), grid(wgs < 1024 ? (int)wgs : 1024, T - 1);
-    with_esz(fmt, [&](auto esz) {
-        if (bands) hipLaunchKernelGGL((yuv_noise_hist_pairs_bands_kernel<esz()>), grid, block, 0, s, src, dst, lo, hi, W, hb, wb, ux, G.oy, G.frame_bytes);
-        else hipLaunchKernelGGL((yuv_noise_hist_pairs_kernel<esz()>), grid, block, 0, s, src, dst, lo, hi, W, hb, wb, ux, G.oy, G.frame_bytes);
-    });
-    return sn_check_launch();
+    return noise_hist<HIST_SPATIAL, true>(src, fmt, rect, nullptr, dst, lo, hi, T, H, W, stream);
 }
 
 int sn_yuv_noise_hist_pairs(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint32_t* dst, int lo, int hi, int T, int H, int W,
                             void* stream) {
-    return noise_hist_pairs(false, src, fmt, rect, dst, lo, hi, T, H, W, stream);
+    return noise_hist<HIST_PAIRS, false>(src, fmt, rect, nullptr, dst, lo, hi, T, H, W, stream);
 }
 
 int sn_yuv_noise_hist_pairs_bands(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, uint32_t* dst, int lo, int hi, int T, int H, int W,
                                   void* stream) {
-    return noise_hist_pairs(true, src, fmt, rect, dst, lo, hi, T, H, W, stream);
+    return noise_hist<HIST_PAIRS, true>(src, fmt, rect, nullptr, dst, lo, hi, T, H, W, stream);
+}
+
+int sn_yuv_noise_hist_pairs_mv(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const int8_t* mv, uint32_t* dst, int lo, int hi, int T,
+                               int H, int W, void* stream) {
+    return noise_hist<HIST_PAIRS_MV, false>(src, fmt, rect, mv, dst, lo, hi, T, H, W, stream);
+}
+
+int sn_yuv_noise_hist_pairs_bands_mv(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const int8_t* mv, uint32_t* dst, int lo, int hi,
+                                     int T, int H, int W, void* stream) {
+    return noise_hist<HIST_PAIRS_MV, true>(src, fmt, rect, mv, dst, lo, hi, T, H, W, stream);
 }
 
 // The vectors of the 16 x 16 blocks of every pair: nothing to zero, every word of mv and sad is written by the one workgroup that owns it
@@ -920,43 +690,6 @@ int sn_yuv_block_motion(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_
         hipLaunchKernelGGL((yuv_block_motion_kernel<esz()>), grid, block, 0, s, src, mv, sad, G.h, G.w, W, hb, wb, nbx, G.oy, G.frame_bytes);
     });
     return sn_check_launch();
-}
-
-// The pair histograms along the vectors: noise_hist_pairs with mv, its grid and the picture's size for the kernel's bounds test
-static int noise_hist_pairs_mv(bool bands, const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const int8_t* mv, uint32_t* dst, int lo,
-                               int hi, int T, int H, int W, void* stream) {
-    sn_clear_error();
-    if (!valid_payloads(src, fmt, T, H, W) || T < 2 || !mv || !dst || ((uintptr_t)dst & 3) || lo > hi) return SN_EINVAL;
-    if (lo < -(1 << 24) || hi > (1 << 24)) return SN_EINVAL;               // the band is 32-bit arithmetic: 2 (S - 8 lo) must fit
-    YuvGeo G;
-    if (!make_geo(fmt, H, W, rect, &G)) return SN_EINVAL;
-    int words = 0;
-    with_esz(fmt, [&](auto esz) { words = bands ? MvHistK<esz(), true>::HISTW : MvHistK<esz(), false>::HISTW; });
-    hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(dst, 0, (size_t)(T - 1) * words * sizeof(uint32_t), s) != hipSuccess) return sn_check_launch();      // dst is overwritten, not added to
-    const int hb = G.h / 2, wb = G.w / 2, ux = (wb + 3) / 4, nby = (hb + 7) / 8, nbx = (wb + 7) / 8;
-    if (hb < 1 || wb < 1) return sn_check_launch();                        // no whole block: all-zero histograms
-    const long long units = (long long)ux * hb;
-    if (units > 0x7fffffffLL - 1024 * 256) return SN_EINVAL;
-    const long long per = bands ? 4096 : 2048, wgs = (units + per - 1) / per;      // units per workgroup as noise_hist
-    const dim3 block(256), grid(wgs < 1024 ? (int)wgs : 1024, T - 1);
-    with_esz(fmt, [&](auto esz) {
-        if (bands) hipLaunchKernelGGL((yuv_noise_hist_pairs_mv_kernel<esz(), true>), grid, block, 0, s, src, mv, dst, lo, hi, G.h, G.w, W, hb, wb, ux, nby,
-                                      nbx, G.oy, G.frame_bytes);
-        else hipLaunchKernelGGL((yuv_noise_hist_pairs_mv_kernel<esz(), false>), grid, block, 0, s, src, mv, dst, lo, hi, G.h, G.w, W, hb, wb, ux, nby, nbx,
-                                G.oy, G.frame_bytes);
-    });
-    return sn_check_launch();
-}
-
-int sn_yuv_noise_hist_pairs_mv(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const int8_t* mv, uint32_t* dst, int lo, int hi, int T,
-                               int H, int W, void* stream) {
-    return noise_hist_pairs_mv(false, src, fmt, rect, mv, dst, lo, hi, T, H, W, stream);
-}
-
-int sn_yuv_noise_hist_pairs_bands_mv(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const int8_t* mv, uint32_t* dst, int lo, int hi,
-                                     int T, int H, int W, void* stream) {
-    return noise_hist_pairs_mv(true, src, fmt, rect, mv, dst, lo, hi, T, H, W, stream);
 }
 
 int sn_noise_map_level(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const float* knots, int lo, int hi, void* dst, int dst_dtype,

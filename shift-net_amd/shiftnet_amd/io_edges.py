@@ -208,6 +208,32 @@ def thumb_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, out: Op
     return y
 
 
+def _noise_hist(symbol: str, shape, payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lo, hi, out, rect, pairs: bool = False,
+                vectors: bool = False, mv=None) -> torch.Tensor:
+    """What the six histogram functions share: T payloads -> uint32 [T, *shape] from ``symbol``; with ``pairs`` T >= 2 payloads -> [T - 1, *shape];
+    with ``vectors`` the entry point takes ``mv`` as well, int8 [T - 1, nby, nbx, 2] on the payloads' device.  Its contents are not looked at: the
+    kernel tests every displaced block against the picture."""
+    T, dev = _payload(payload_u8, fmt, H, W)
+    if pairs and T < 2:
+        raise ValueError(f"{symbol}: a pair needs two payloads, got {T}")
+    n = T - 1 if pairs else T
+    lo, hi = _clip(fmt, lo, hi)
+    r = None if rect is None else _rect(rect, fmt, H, W)
+    y = out if out is not None else torch.empty((n,) + shape, dtype=torch.uint32, device=dev)
+    assert tuple(y.shape) == (n,) + shape and y.dtype == torch.uint32 and y.is_contiguous() and y.device == dev
+    args = [payload_u8.data_ptr(), fmt] + ([] if symbol == "sn_yuv_noise_hist" else [r])      # the one entry point without a rectangle
+    if vectors:
+        from .noise import motion_grid
+        nby, nbx = motion_grid(H if r is None else r.h, W if r is None else r.w)
+        assert tuple(mv.shape) == (n, nby, nbx, 2) and mv.dtype == torch.int8 and mv.is_contiguous() and mv.device == dev
+        if nby * nbx == 0:                                    # no whole block: no vector to point at, and what the entry point writes then
+            return y.zero_()
+        args.append(mv.data_ptr())
+    with torch.cuda.device(dev):
+        L.check(getattr(L.load(), symbol)(*args, y.data_ptr(), lo, hi, T, H, W, torch.cuda.current_stream(dev).cuda_stream), symbol)
+    return y
+
+
 def noise_hist_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lo: Optional[int] = None, hi: Optional[int] = None,
                    out: Optional[torch.Tensor] = None, rect=None) -> torch.Tensor:
     """payload_u8: [T, frame_bytes] uint8 on a HIP device (only the luma plane of each payload is read) -> uint32 [T, 2 (2^bits - 1) + 1]:
@@ -215,18 +241,7 @@ def noise_hist_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lo
     ``hi`` (default: the format's black and white codes, noise.clip_codes).  ``out``: a tensor of that shape to overwrite.
     ``rect=(x0, y0, w, h)``: the blocks of that picture of the stream alone, the block grid anchored at (x0, y0): the cropped stream's histograms."""
     from .noise import nbins
-    T, nb = _payload(payload_u8, fmt, H, W)[0], nbins(fmt.bits)
-    lo, hi = _clip(fmt, lo, hi)
-    y = out if out is not None else torch.empty((T, nb), dtype=torch.uint32, device=payload_u8.device)
-    assert tuple(y.shape) == (T, nb) and y.dtype == torch.uint32 and y.is_contiguous() and y.device == payload_u8.device
-    r = None if rect is None else _rect(rect, fmt, H, W)
-    with torch.cuda.device(payload_u8.device):
-        st = torch.cuda.current_stream(payload_u8.device).cuda_stream
-        if r is None:
-            L.check(L.load().sn_yuv_noise_hist(payload_u8.data_ptr(), fmt, y.data_ptr(), lo, hi, T, H, W, st), "sn_yuv_noise_hist")
-        else:
-            L.check(L.load().sn_yuv_noise_hist_rect(payload_u8.data_ptr(), fmt, r, y.data_ptr(), lo, hi, T, H, W, st), "sn_yuv_noise_hist_rect")
-    return y
+    return _noise_hist("sn_yuv_noise_hist" if rect is None else "sn_yuv_noise_hist_rect", (nbins(fmt.bits),), payload_u8, fmt, H, W, lo, hi, out, rect)
 
 
 def noise_hist_bands_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lo: Optional[int] = None, hi: Optional[int] = None,
@@ -235,30 +250,7 @@ def noise_hist_bands_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: i
     ``noise_hist_yuv``'s counts split by the block's brightness, band = (16 (S - 4 lo)) / (4 (hi - lo)) for the block's sum S, and v saturated to
     NBV - 1 (the last bin means "at least NBV - 1").  ``lo``, ``hi``, ``out``, ``rect`` as there."""
     from .noise import NLF_BANDS, nlf_bins
-    T, nbv = _payload(payload_u8, fmt, H, W)[0], nlf_bins(fmt.bits)
-    lo, hi = _clip(fmt, lo, hi)
-    y = out if out is not None else torch.empty((T, NLF_BANDS, nbv), dtype=torch.uint32, device=payload_u8.device)
-    assert tuple(y.shape) == (T, NLF_BANDS, nbv) and y.dtype == torch.uint32 and y.is_contiguous() and y.device == payload_u8.device
-    r = None if rect is None else _rect(rect, fmt, H, W)
-    with torch.cuda.device(payload_u8.device):
-        L.check(L.load().sn_yuv_noise_hist_bands(payload_u8.data_ptr(), fmt, r, y.data_ptr(), lo, hi, T, H, W,
-                                                 torch.cuda.current_stream(payload_u8.device).cuda_stream), "sn_yuv_noise_hist_bands")
-    return y
-
-
-def _hist_pairs(symbol: str, shape, payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lo, hi, out, rect) -> torch.Tensor:
-    """What the two pair histograms share: T >= 2 payloads -> uint32 [T - 1, *shape] from ``symbol``."""
-    T = _payload(payload_u8, fmt, H, W)[0]
-    if T < 2:
-        raise ValueError(f"{symbol}: a pair needs two payloads, got {T}")
-    lo, hi = _clip(fmt, lo, hi)
-    y = out if out is not None else torch.empty((T - 1,) + shape, dtype=torch.uint32, device=payload_u8.device)
-    assert tuple(y.shape) == (T - 1,) + shape and y.dtype == torch.uint32 and y.is_contiguous() and y.device == payload_u8.device
-    r = None if rect is None else _rect(rect, fmt, H, W)
-    with torch.cuda.device(payload_u8.device):
-        L.check(getattr(L.load(), symbol)(payload_u8.data_ptr(), fmt, r, y.data_ptr(), lo, hi, T, H, W,
-                                          torch.cuda.current_stream(payload_u8.device).cuda_stream), symbol)
-    return y
+    return _noise_hist("sn_yuv_noise_hist_bands", (NLF_BANDS, nlf_bins(fmt.bits)), payload_u8, fmt, H, W, lo, hi, out, rect)
 
 
 def noise_hist_pairs_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lo: Optional[int] = None, hi: Optional[int] = None,
@@ -267,7 +259,7 @@ def noise_hist_pairs_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: i
     per pair of consecutive payloads the counts of v = |HH(p + 1) - HH(p)|, HH = a - b - c + d of the same 2 x 2 luma block in both, over the blocks
     whose eight codes lie strictly between ``lo`` and ``hi``.  ``lo``, ``hi``, ``out``, ``rect`` as ``noise_hist_yuv``."""
     from .noise import pair_bins
-    return _hist_pairs("sn_yuv_noise_hist_pairs", (pair_bins(fmt.bits),), payload_u8, fmt, H, W, lo, hi, out, rect)
+    return _noise_hist("sn_yuv_noise_hist_pairs", (pair_bins(fmt.bits),), payload_u8, fmt, H, W, lo, hi, out, rect, pairs=True)
 
 
 def noise_hist_pairs_bands_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lo: Optional[int] = None, hi: Optional[int] = None,
@@ -276,7 +268,7 @@ def noise_hist_pairs_bands_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int
     the brightness of the block in both payloads, band = (2 (S - 8 lo)) / (hi - lo) for the sum S of the eight codes, and v saturated to NBV - 1.
     ``lo``, ``hi``, ``out``, ``rect`` as ``noise_hist_yuv``."""
     from .noise import NLF_BANDS, nlf_bins
-    return _hist_pairs("sn_yuv_noise_hist_pairs_bands", (NLF_BANDS, nlf_bins(fmt.bits)), payload_u8, fmt, H, W, lo, hi, out, rect)
+    return _noise_hist("sn_yuv_noise_hist_pairs_bands", (NLF_BANDS, nlf_bins(fmt.bits)), payload_u8, fmt, H, W, lo, hi, out, rect, pairs=True)
 
 
 def block_motion_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, rect=None, out_mv: Optional[torch.Tensor] = None,
@@ -304,41 +296,20 @@ def block_motion_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, 
     return mv, sad
 
 
-def _hist_pairs_mv(symbol: str, shape, payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, mv: torch.Tensor, lo, hi, out, rect) -> torch.Tensor:
-    """``_hist_pairs`` with the vectors: mv int8 [T - 1, nby, nbx, 2] on the payloads' device.  Its contents are not looked at: the kernel tests every
-    displaced block against the picture."""
-    from .noise import motion_grid
-    T, dev = _payload(payload_u8, fmt, H, W)
-    if T < 2:
-        raise ValueError(f"{symbol}: a pair needs two payloads, got {T}")
-    lo, hi = _clip(fmt, lo, hi)
-    r = None if rect is None else _rect(rect, fmt, H, W)
-    nby, nbx = motion_grid(H if r is None else r.h, W if r is None else r.w)
-    assert tuple(mv.shape) == (T - 1, nby, nbx, 2) and mv.dtype == torch.int8 and mv.is_contiguous() and mv.device == dev
-    y = out if out is not None else torch.empty((T - 1,) + shape, dtype=torch.uint32, device=dev)
-    assert tuple(y.shape) == (T - 1,) + shape and y.dtype == torch.uint32 and y.is_contiguous() and y.device == dev
-    if nby * nbx == 0:                                        # no whole block: no vector to point at, and what the entry point writes then
-        return y.zero_()
-    with torch.cuda.device(dev):
-        L.check(getattr(L.load(), symbol)(payload_u8.data_ptr(), fmt, r, mv.data_ptr(), y.data_ptr(), lo, hi, T, H, W,
-                                          torch.cuda.current_stream(dev).cuda_stream), symbol)
-    return y
-
-
 def noise_hist_pairs_mv_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, mv: torch.Tensor, lo: Optional[int] = None,
                             hi: Optional[int] = None, out: Optional[torch.Tensor] = None, rect=None) -> torch.Tensor:
     """``noise_hist_pairs_yuv`` along the vectors ``mv`` of ``block_motion_yuv`` (same payloads, same ``rect``): only the measuring 2 x 2 blocks ((i + j)
     odd) count, the second payload's four codes are those at (2 i + dy, 2 j + dx) with (dy, dx) the vector of block (i / 8, j / 8), and a block whose
     displaced position is not wholly inside the picture does not count.  Any int8 contents of ``mv`` are safe."""
     from .noise import pair_bins
-    return _hist_pairs_mv("sn_yuv_noise_hist_pairs_mv", (pair_bins(fmt.bits),), payload_u8, fmt, H, W, mv, lo, hi, out, rect)
+    return _noise_hist("sn_yuv_noise_hist_pairs_mv", (pair_bins(fmt.bits),), payload_u8, fmt, H, W, lo, hi, out, rect, pairs=True, vectors=True, mv=mv)
 
 
 def noise_hist_pairs_bands_mv_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, mv: torch.Tensor, lo: Optional[int] = None,
                                   hi: Optional[int] = None, out: Optional[torch.Tensor] = None, rect=None) -> torch.Tensor:
     """``noise_hist_pairs_bands_yuv`` along the vectors ``mv``, with the three differences of ``noise_hist_pairs_mv_yuv``."""
     from .noise import NLF_BANDS, nlf_bins
-    return _hist_pairs_mv("sn_yuv_noise_hist_pairs_bands_mv", (NLF_BANDS, nlf_bins(fmt.bits)), payload_u8, fmt, H, W, mv, lo, hi, out, rect)
+    return _noise_hist("sn_yuv_noise_hist_pairs_bands_mv", (NLF_BANDS, nlf_bins(fmt.bits)), payload_u8, fmt, H, W, lo, hi, out, rect, pairs=True, vectors=True, mv=mv)
 
 
 def noise_map_level(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, Hp: int, Wp: int, knots, dtype: torch.dtype,

@@ -176,8 +176,9 @@ def test_block_motion_and_the_histograms_of_a_rectangle_are_the_cropped_streams(
 @pytest.mark.parametrize("fmt", [F8, F8_420, F10], ids=["8bit444", "8bit420", "10bit420"])
 def test_mv_histograms_with_the_matchers_vectors_equal_the_restatement_exactly(fmt):
     ranges = [N.clip_codes(fmt), (-1, 1 << 16)]                                  # the format's codes; every stored word (v saturates at NBP - 1 then)
-    for H, W in SIZES + [(1, 5)]:
-        for T in (2, 4):
+    # (200, 340): 100 block rows x 43 units = 4300 units, three workgroups per pair for the flat histogram (2048 units each) and two for the band one (4096)
+    for (H, W), Ts in [(s, (2, 4)) for s in SIZES + [(1, 5)]] + [((200, 340), (2,))]:
+        for T in Ts:
             p = payloads(fmt, T, H, W, "texture", seed=T + 3)
             src = on_device(p)
             mv_dev, _ = block_motion_yuv(src, yuv_fmt(*fmt), H, W)

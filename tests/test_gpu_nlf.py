@@ -68,6 +68,7 @@ HIST_CASES = {
     "v >= NBV, 10 bit": (F420_10, 34, 66, 1, None, "random", (-1, 1024)),
     "smaller than one block": (F420_8, 1, 9, 2, None, "random", None),
     "two workgroups per frame": (F420_8, 200, 340, 2, None, "ramp", None),                   # 100 block rows x 43 units = 4300 > the 4096 of a workgroup
+    "two workgroups per frame, 10 bit": (F420_10, 200, 340, 2, None, "ramp", None),         # the same for the 10-bit instance, with its 8 copies
 }
 
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15, 3.16, 3.17, 3.19, 3.20 and 3.21 (run on the MI355X from the repository root).
+"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15, 3.16, 3.17, 3.19, 3.20, 3.21, 3.23 and 3.25 (run on the MI355X from the repository root).
 
   kernels : time per pixel of sn_ingest_yuv / sn_egress_yuv / sn_yuv_thumb / sn_yuv_noise_hist (4:2:0 8 bit, 720p x 20 frames; the noise
             histogram on the same frames with noise of sigma 10 as well) beside sn_ingest_u8 / sn_egress_u8 on the same
@@ -34,6 +34,8 @@
             sn_yuv_noise_hist_pairs_bands_mv beside the two plain pair histograms (4:2:0 8 bit, 720p x 20 frames with noise of sigma 10), interleaved as
             in the kernels part.  --mode forward: steady-state wall time per 720p window of the pipelined denoiser (as the sigma part) with
             sigma_estimator="min" alone and with sigma_motion="blocks" on top, runs of the two alternating in one process, the first two windows left out.
+            Since 3.25, --mode kernels of the nlf and motion parts with --parent_lib SO: the seven noise-histogram entry points of this build and, twice, of
+            another build through one ctypes argument list, at 8 bit and 10 bit 4:2:0, with this build's median against the other's third quartile.
 Prints one JSON object per part.
 """
 import argparse
@@ -234,13 +236,48 @@ def sigma(a):
                       "window_sigma_auto": [round(s, 3) for s in seen["auto"]], "window_sigma_auto_min": [round(s, 3) for s in seen["min"]], **res}))
 
 
+def hist_ab_cases(parent_lib, symbols, tag, pay, fmt, H, W, mv=None):
+    """The noise-histogram entry points ``symbols`` of this build and of ANOTHER build (--parent_lib: the parent commit's whole csrc compiled into a shared
+    library of its own), called through ctypes with one argument list on the same tensors, so that the builds are timed interleaved in one process
+    (3.25).  The other build appears twice, as parentA_ and parentB_, with this build between them: the spread between two copies of identical code
+    is the run's own noise, and what a case owes to its place after another kernel falls on one copy of either side."""
+    if not parent_lib:
+        return {}
+    import ctypes as C
+    from shiftnet_amd.noise import clip_codes
+    plib, T = C.CDLL(os.path.abspath(parent_lib)), pay.shape[0]
+    lo, hi = clip_codes(fmt.bits, fmt.range)
+    dst = torch.empty(T * 16 * 512, dtype=torch.uint32, device="cuda")              # room for the largest of the histograms
+    cases = {}
+    for sym in symbols:
+        rect = [] if sym == "sn_yuv_noise_hist" else [L.YuvRect(0, 0, W, H) if sym.endswith("_rect") else None]
+        args = [pay.data_ptr(), fmt] + rect + ([mv.data_ptr()] if sym.endswith("_mv") else []) + [dst.data_ptr(), lo, hi, T, H, W]
+        for who, lib in (("parentA", plib), ("new", L.load()), ("parentB", plib)):
+            fn = getattr(lib, sym)
+            fn.argtypes = getattr(L.load(), sym).argtypes
+            cases[f"{who}_{sym[len('sn_yuv_'):]}{tag}"] = lambda fn=fn, args=args, sym=sym, keep=(pay, mv, dst): L.check(
+                fn(*args, torch.cuda.current_stream().cuda_stream), sym)
+    return cases
+
+
+def hist_ab_verdict(ms):
+    """Per case of ``hist_ab_cases``: this build's median against the larger third quartile of the two copies of the other build, same run."""
+    out = {}
+    for k, v in ms.items():
+        if k.startswith("new_"):
+            q3 = max(statistics.quantiles(ms[w + k[4:]], n=4, method="inclusive")[2] for w in ("parentA_", "parentB_"))
+            out[k[4:]] = {"new_median_us": statistics.median(v) * 1e3, "parent_q3_us": q3 * 1e3, "ok": statistics.median(v) <= q3}
+    return out
+
+
 def nlf_kernels(a):
     T, H, W = 20, 720, 1280
     fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
     blur, _ = synth.blurred_clip(4, H, W, seed=1)
     rgb = ingest_u8(torch.from_numpy(np.concatenate([blur] * 5)).cuda(), torch.float32)[0]
     pay = egress_yuv(rgb, fmt, H, W)
-    pay_noisy = egress_yuv((rgb + torch.randn(rgb.shape, device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * (10.0 / 255)).clamp(0, 1), fmt, H, W)
+    noisy = (rgb + torch.randn(rgb.shape, device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * (10.0 / 255)).clamp(0, 1)
+    pay_noisy = egress_yuv(noisy, fmt, H, W)
     x_bf = torch.empty((1, T, 3, H, W), dtype=torch.bfloat16, device="cuda")
     nm = torch.empty((1, T, 1, H, W), dtype=torch.bfloat16, device="cuda")
     hists = torch.empty((T, 511), dtype=torch.uint32, device="cuda")
@@ -261,6 +298,11 @@ def nlf_kernels(a):
         "noise_map_level_bf16": lambda: noise_map_level(pay, fmt, H, W, H, W, knots, torch.bfloat16, out=nm),
         "noise_map_level_bf16_sigma10": lambda: noise_map_level(pay_noisy, fmt, H, W, H, W, knots, torch.bfloat16, out=nm),
     }
+    fmt10 = yuv_fmt(10, L.SN_YUV_420_LEFT, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    syms = ["sn_yuv_noise_hist", "sn_yuv_noise_hist_rect", "sn_yuv_noise_hist_bands", "sn_yuv_noise_hist_pairs", "sn_yuv_noise_hist_pairs_bands"]
+    for tag, p, f in (("", pay, fmt), ("_sigma10", pay_noisy, fmt), ("_420p10", egress_yuv(rgb, fmt10, H, W), fmt10),
+                      ("_420p10_sigma10", egress_yuv(noisy, fmt10, H, W), fmt10)):
+        cases.update(hist_ab_cases(a.parent_lib, syms, tag, p, f, H, W))
     for f in cases.values():
         for _ in range(3):
             f()
@@ -277,7 +319,7 @@ def nlf_kernels(a):
             ms[k].append(e0.elapsed_time(e1) / a.inner)
     px = T * H * W
     res = {k: {"us_per_launch": summary([m * 1e3 for m in v]), "ps_per_pixel": summary([m * 1e9 / px for m in v])} for k, v in ms.items()}
-    print(json.dumps({"part": "nlf", "mode": "kernels", "frames": T, "size": [H, W], "reps": a.reps, "inner": a.inner, **res}))
+    print(json.dumps({"part": "nlf", "mode": "kernels", "frames": T, "size": [H, W], "reps": a.reps, "inner": a.inner, "new_vs_parent": hist_ab_verdict(ms), **res}))
 
 
 def nlf_forward(a):
@@ -329,7 +371,8 @@ def motion_kernels(a):
     fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
     blur, _ = synth.blurred_clip(4, H, W, seed=1)
     rgb = ingest_u8(torch.from_numpy(np.concatenate([blur] * 5)).cuda(), torch.float32)[0]
-    pay = egress_yuv((rgb + torch.randn(rgb.shape, device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * (10.0 / 255)).clamp(0, 1), fmt, H, W)
+    noisy = (rgb + torch.randn(rgb.shape, device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * (10.0 / 255)).clamp(0, 1)
+    pay = egress_yuv(noisy, fmt, H, W)
     pairs = torch.empty((T - 1, 1021), dtype=torch.uint32, device="cuda")
     pair_bands = torch.empty((T - 1, 16, 128), dtype=torch.uint32, device="cuda")
     mv, sad = block_motion_yuv(pay, fmt, H, W)
@@ -340,6 +383,11 @@ def motion_kernels(a):
         "noise_hist_pairs_mv_yuv": lambda: noise_hist_pairs_mv_yuv(pay, fmt, H, W, mv, out=pairs),
         "noise_hist_pairs_bands_mv_yuv": lambda: noise_hist_pairs_bands_mv_yuv(pay, fmt, H, W, mv, out=pair_bands),
     }
+    fmt10 = yuv_fmt(10, L.SN_YUV_420_LEFT, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    pay10 = egress_yuv(noisy, fmt10, H, W)
+    syms = ["sn_yuv_noise_hist_pairs", "sn_yuv_noise_hist_pairs_bands", "sn_yuv_noise_hist_pairs_mv", "sn_yuv_noise_hist_pairs_bands_mv"]
+    for tag, p, f in (("", pay, fmt), ("_420p10", pay10, fmt10)):
+        cases.update(hist_ab_cases(a.parent_lib, syms, tag, p, f, H, W, mv=mv if f is fmt else block_motion_yuv(p, f, H, W)[0]))
     for f in cases.values():
         for _ in range(3):
             f()
@@ -357,7 +405,7 @@ def motion_kernels(a):
     px = (T - 1) * H * W                                                             # per pixel of a pair
     res = {k: {"us_per_launch": summary([m * 1e3 for m in v]), "ps_per_pixel": summary([m * 1e9 / px for m in v])} for k, v in ms.items()}
     nz = float((mv != 0).any(dim=3).float().mean())
-    print(json.dumps({"part": "motion", "mode": "kernels", "frames": T, "size": [H, W], "reps": a.reps, "inner": a.inner, "nonzero_vectors": round(nz, 4), **res}))
+    print(json.dumps({"part": "motion", "mode": "kernels", "frames": T, "size": [H, W], "reps": a.reps, "inner": a.inner, "nonzero_vectors": round(nz, 4), "new_vs_parent": hist_ab_verdict(ms), **res}))
 
 
 def motion_forward(a):
@@ -631,7 +679,8 @@ if __name__ == "__main__":
     ap.add_argument("--scene_cuts", choices=["off", "auto", "listed"], default="off", help="pipeline part: VideoRestorer(scene_cuts=...)")
     ap.add_argument("--cut_every", type=int, default=0, help="pipeline part: a cut every N frames in the stream (0: none)")
     ap.add_argument("--parent_lib", default=None, metavar="SO", help="kernels part and picture part in kernels mode: a shared library built from another commit's "
-                    "csrc/sn_yuv.hip alone; its sn_ingest_yuv / sn_egress_yuv are timed beside this build's")
+                    "csrc/sn_yuv.hip alone; its sn_ingest_yuv / sn_egress_yuv are timed beside this build's.  nlf and motion parts in kernels mode: a library "
+                    "built from another commit's whole csrc; its seven noise-histogram entry points are timed beside this build's, at 8 and 10 bit")
     ap.add_argument("--only_cases", default=None, metavar="WORDS", help="kernels part: time only the cases whose name contains one of these comma-separated words")
     ap.add_argument("--mode", choices=["forward", "kernels"], default="forward", help="picture, nlf, report and motion parts: which measurement")
     ap.add_argument("--picture", choices=["auto", "fixed"], default="auto", help="picture part, forward mode: VideoRestorer(picture='auto') or the rectangle itself")
