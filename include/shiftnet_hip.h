@@ -724,6 +724,36 @@ int sn_yuv_noise_hist_pairs_bands_mv(const uint8_t* src, const sn_yuv_fmt* fmt, 
 int sn_yuv_diff_stats(const uint8_t* a, const uint8_t* b, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */,
                       int edge, int64_t* dst /* [T][SN_DIFF_STATS] */, int T, int H, int W, void* stream);
 
+/* ---- method noise along block motion vectors (a new symbol, SN_ABI_VERSION stays 20) ---------------------------------------------------------------
+ * Word 7 of sn_yuv_diff_stats compares a payload's difference with the next payload's AT THE SAME PLACE: removed detail that moves with the picture
+ * reads as uncorrelated, which is what a noise-only removal reads.  sn_yuv_diff_stats_mv takes the next payload's samples where the vectors of
+ * sn_yuv_block_motion point.  a, b, fmt, rect (NULL: the whole frame), H, W and stream exactly as sn_yuv_diff_stats takes them, T >= 2; mv:[T - 1][nby][nbx][2]
+ * int8 laid out as sn_yuv_block_motion writes it for the same picture (the written payloads b, by the restorer's use).  Only the luma planes are read,
+ * samples are taken as stored (a 16-bit word may hold up to 65535), pair p is payloads p and p + 1.  The picture is h x w, the rectangle or the frame;
+ * the block grid is anchored at its first sample and the coordinates below count from there.
+ *   hb = h / 2, wb = w / 2: the whole 2 x 2 blocks (i, j).  Block (i, j) is a MEASURING block iff i + j is odd (sn_yuv_block_motion chose its vector on
+ *   the other half, so the choice cannot fit what is measured here), and its vector is (dy, dx) = mv[p][i / 8][j / 8].
+ *   A measuring block COUNTS iff rows 2 i + dy, 2 i + dy + 1 and columns 2 j + dx, 2 j + dx + 1 lie inside the picture: the rule of
+ *   sn_yuv_noise_hist_pairs_mv.  mv is device memory the entry point cannot validate: the test is made per block in the kernel, so ANY int8 contents are
+ *   memory-safe.  Nothing is clamped and nothing outside the picture is read.
+ *   For each of the four samples (y, x) of a counting block:
+ *     d0 = b_p(y, x) - a_p(y, x),  d1 = b_{p+1}(y + dy, x + dx) - a_{p+1}(y + dy, x + dx),  g = b_{p+1}(y + dy, x + dx) - b_p(y, x).
+ * dst[p] holds SN_DIFF_STATS_MV = 8 signed 64-bit integers:
+ *   0           Nm = the samples counted (4 per counting block)
+ *   1, 2        sum d0, sum d0^2
+ *   3, 4        sum d1, sum d1^2
+ *   5           sum d0 d1
+ *   6           sum g^2 (how well the vectors fit the written picture)
+ *   7           Nv = the counted samples whose vector is not (0, 0)
+ * dst:[T - 1][8] int64 is OVERWRITTEN, never added to; nothing outside those words is written.  Integer sums accumulated in 64 bit: exact, and the same
+ * for every launch geometry and schedule.  a == b is legal.  hb == 0 or wb == 0: all zeros.
+ * (tests/diff_stats_mv_ref.py restates it in numpy; the kernel equals it word for word.)
+ * SN_EINVAL before anything is launched: everything sn_yuv_diff_stats refuses (it takes no edge); T < 2; a null mv; dst not 8-byte aligned; a picture
+ * whose ceil(w / 8) x ceil(h / 8) units exceed the bound sn_yuv_diff_stats checks. */
+#define SN_DIFF_STATS_MV 8
+int sn_yuv_diff_stats_mv(const uint8_t* a, const uint8_t* b, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */,
+                         const int8_t* mv, int64_t* dst /* [T - 1][SN_DIFF_STATS_MV] */, int T, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,10 @@
 //                   shiftnet_amd/picture.py is evaluated on these on the host);
 //   sn_yuv_diff_stats : two sets of T payloads, what came in and what was written -> [T][16] int64 sums of their difference in all three planes: its
 //                   moments, its products with the right, lower and next-frame neighbour, its energy on the edges of the written picture (the method-noise
-//                   report of shiftnet_amd/report.py is computed from these on the host); rect or the whole frame.
+//                   report of shiftnet_amd/report.py is computed from these on the host); rect or the whole frame;
+//   sn_yuv_diff_stats_mv : the same two sets of T payloads and the vectors of sn_yuv_block_motion -> [T - 1][8] int64 sums over the measuring blocks of
+//                   every pair: the moments of the luma difference in both payloads and their product along the vectors (the report's motion-compensated
+//                   temporal correlation); rect or the whole frame.
 // The seven sn_yuv_noise_hist* entry points launch the instances of ONE kernel template, yuv_noise_hist_kernel<sample size, kind, bands>, from one
 // host function; every other entry point has a kernel of its own.
 //
@@ -589,6 +592,109 @@ __global__ __launch_bounds__(256) void yuv_diff_stats_kernel(const uint8_t* a, c
         if (tot) atomicAdd(&dst[(size_t)t * SN_DIFF_STATS + tid], (unsigned long long)tot);
     }
 }
+
+// ---- method noise along block motion vectors ------------------------------------------------------------------------------------------------
+// The temporal product of yuv_diff_stats_kernel compares d = b - a of a payload with the next payload's d at the same place: removed detail that moves
+// with the picture reads as uncorrelated.  Here the next payload's samples are taken where the vector of yuv_block_motion_kernel points, on the
+// MEASURING 2 x 2 blocks, (i + j) odd -- the vector was chosen on the other half, so the choice cannot fit what is measured -- and the eight sums
+// include/shiftnet_hip.h lists (sn_yuv_diff_stats_mv) are made of d0 = d_p(y, x), d1 = d_{p+1}(y + dy, x + dx) and g = b_{p+1}(y + dy, x + dx) - b_p(y, x).
+// blockIdx.y is the pair.  A lane owns a unit of 8 x 8 luma samples anchored at multiples of 8: 4 x 4 blocks of one vector block (4 divides 8), so one
+// vector per unit, and two blocks of every block row measure: 1 and 3 in an even block row, 0 and 2 in an odd one.  Per sample row one 8 B / 16 B load
+// of a and of b of payload p where the ADDRESS allows it, element-wise otherwise and where fewer than four blocks are left on the right edge.  The
+// displaced row of payload p + 1 is at no particular alignment: where all of its 8 samples lie inside the picture and both addresses allow it (a zero
+// vector in an aligned stream: static footage) it is one wide load per plane, otherwise the 4 samples of the two measuring blocks are loaded
+// element-wise, each block after the test that its displaced position lies wholly inside the picture.  mv is device memory nobody has validated: with
+// that test any int8 contents are safe, a block that fails it does not count and nothing outside the picture is read.  Neighbouring lanes own
+// neighbouring units of a unit row; a workgroup walks units gridDim.x * 256 apart.  Accumulators, reduction and the one 64-bit vector atomic per
+// workgroup and non-zero word are those of yuv_diff_stats_kernel; here the two counts are sums of the lanes too.  Integer sums commute: the result is
+// the same for every geometry and every schedule.
+template <int ESZ>
+__global__ __launch_bounds__(256) void yuv_diff_stats_mv_kernel(const uint8_t* a, const uint8_t* b, const int8_t* __restrict__ mv, unsigned long long* dst,
+                                                              const YuvGeo G, int hb, int wb, int nby, int nbx) {
+    __shared__ long long part[4][SN_DIFF_STATS_MV];
+    const int tid = threadIdx.x, p = blockIdx.y;                          // pair p: payloads p and p + 1 <= T - 1
+    const int h = G.h, w = G.w;
+    const uint8_t* a0 = a + (size_t)p * G.frame_bytes + G.oy;
+    const uint8_t* b0 = b + (size_t)p * G.frame_bytes + G.oy;
+    const uint8_t* a1 = a0 + G.frame_bytes;
+    const uint8_t* b1 = b0 + G.frame_bytes;
+    const int ux = (wb + 3) >> 2, units = ux * ((hb + 3) >> 2);           // hb, wb: whole 2 x 2 blocks; a unit is 4 x 4 of them
+    int nm = 0, nv = 0;
+    long long s0 = 0, s00 = 0, s1 = 0, s11 = 0, s01 = 0, sgg = 0;
+    for (int u = blockIdx.x * 256 + tid; u < units; u += gridDim.x * 256) {
+        const int uy = u / ux, uxi = u - uy * ux, x0 = uxi * 8, y0 = uy * 8;
+        const int nb = imin(4, wb - 4 * uxi), rows = 2 * imin(4, hb - 4 * uy);      // blocks per block row 1 .. 4, sample rows 2 .. 8
+        const int8_t* v2 = mv + (((size_t)p * nby + (uy >> 1)) * nbx + (uxi >> 1)) * 2;      // uy / 2 < nby and uxi / 2 < nbx: inside mv whatever it holds
+        const int dy = v2[0], dx = v2[1];
+        const int moved = (dy | dx) != 0 ? 1 : 0;
+        const int xd0 = x0 + dx;                                          // the displaced unit's first column
+        const bool xin = nb == 4 && xd0 >= 0 && xd0 + 8 <= w;             // all 8 samples of a displaced row lie in the picture's columns
+#pragma unroll 1
+        for (int r = 0; r < rows; ++r) {
+            const int odd = (r >> 1) & 1;                                 // 4 uy and 4 uxi are even: the measuring blocks of this row are bj = 1 - odd, 3 - odd
+            const int yd = y0 + (r & ~1) + dy;                            // the displaced block row's first sample row: rows yd, yd + 1 must lie in 0 .. h - 1
+            if (yd < 0 || yd + 2 > h) continue;                           // no block of this row counts: nothing is loaded
+            const size_t o = (size_t)(y0 + r) * G.py + x0;
+            int av[8], bv[8];
+            if (nb == 4) {
+                ldn<ESZ, 8>(a0, o, av);
+                ldn<ESZ, 8>(b0, o, bv);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {                             // samples x0 .. x0 + 2 nb - 1 < 2 wb <= w exist; the others are not read
+                    const bool in = k < 2 * nb;
+                    av[k] = in ? ld1<ESZ>(a0, o + k) : 0;
+                    bv[k] = in ? ld1<ESZ>(b0, o + k) : 0;
+                }
+            }
+            const long long od = (long long)(yd + (r & 1)) * G.py + xd0;   // element offset of the displaced row's first sample; xd0 may be negative
+            const bool wide = xin && ((((uintptr_t)a1 + (uintptr_t)(od * ESZ)) | ((uintptr_t)b1 + (uintptr_t)(od * ESZ))) & (8 * ESZ - 1)) == 0;
+            int aw[8], bw[8];
+            if (wide) {
+                ldn<ESZ, 8>(a1, (size_t)od, aw);
+                ldn<ESZ, 8>(b1, (size_t)od, bw);
+            }
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                const int bj = 1 - odd + 2 * m, xd = xd0 + 2 * bj;        // columns xd, xd + 1 must lie in 0 .. w - 1
+                if (!(bj < nb && xd >= 0 && xd + 2 <= w)) continue;
+                nm += 2;
+                nv += 2 * moved;
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const int ap = odd ? av[4 * m + s] : av[4 * m + 2 + s], bp = odd ? bv[4 * m + s] : bv[4 * m + 2 + s];
+                    int an, bn;
+                    if (wide) {
+                        an = odd ? aw[4 * m + s] : aw[4 * m + 2 + s];
+                        bn = odd ? bw[4 * m + s] : bw[4 * m + 2 + s];
+                    } else {
+                        an = ld1<ESZ>(a1, (size_t)(od + 2 * bj + s));
+                        bn = ld1<ESZ>(b1, (size_t)(od + 2 * bj + s));
+                    }
+                    const int d0 = bp - ap, d1 = bn - an, g = bn - bp;
+                    s0 += d0;
+                    s00 += (long long)d0 * d0;
+                    s1 += d1;
+                    s11 += (long long)d1 * d1;
+                    s01 += (long long)d0 * d1;
+                    sgg += (long long)g * g;
+                }
+            }
+        }
+    }
+    long long v[SN_DIFF_STATS_MV] = {nm, s0, s00, s1, s11, s01, sgg, nv};   // the words of dst[p] in their order
+#pragma unroll
+    for (int i = 0; i < SN_DIFF_STATS_MV; ++i) v[i] = wave_sum_ll(v[i]);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < SN_DIFF_STATS_MV; ++i) part[tid >> 6][i] = v[i];
+    }
+    __syncthreads();
+    if (tid < SN_DIFF_STATS_MV) {
+        const long long tot = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+        if (tot) atomicAdd(&dst[(size_t)p * SN_DIFF_STATS_MV + tid], (unsigned long long)tot);
+    }
+}
 }  // namespace
 
 // The seven histogram entry points: one kernel instance each way.  T payloads are T frames or T - 1 pairs; mv is looked at by the vector forms alone
@@ -742,6 +848,27 @@ int sn_yuv_diff_stats(const uint8_t* a, const uint8_t* b, const sn_yuv_fmt* fmt,
     const dim3 block(256), grid(wgs < 1024 ? (int)wgs : 1024, T);
     with_esz(fmt, [&](auto esz) {
         hipLaunchKernelGGL((yuv_diff_stats_kernel<esz()>), grid, block, 0, s, a, b, (unsigned long long*)dst, G, ch, cw, edge, T);
+    });
+    return sn_check_launch();
+}
+
+int sn_yuv_diff_stats_mv(const uint8_t* a, const uint8_t* b, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect, const int8_t* mv, int64_t* dst, int T, int H, int W,
+                         void* stream) {
+    sn_clear_error();
+    if (!valid_payloads(a, fmt, T, H, W) || !b || !aligned_payload(fmt, b) || !dst || ((uintptr_t)dst & 7) || T < 2 || !mv) return SN_EINVAL;
+    YuvGeo G;
+    if (!make_geo(fmt, H, W, rect, &G)) return SN_EINVAL;
+    const long long bound = (long long)((G.w + 7) / 8) * ((G.h + DS_STRIP - 1) / DS_STRIP);      // the bound of sn_yuv_diff_stats; the units here are no more
+    if (bound > 0x7fffffffLL - 1024 * 256) return SN_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(dst, 0, (size_t)(T - 1) * SN_DIFF_STATS_MV * sizeof(int64_t), s) != hipSuccess) return sn_check_launch();      // dst is overwritten, not added to
+    const int hb = G.h / 2, wb = G.w / 2;                                  // the block grid is anchored at the picture's first sample
+    if (hb < 1 || wb < 1) return sn_check_launch();                        // no whole block: all zeros
+    const long long units = (long long)((wb + 3) / 4) * ((hb + 3) / 4);
+    const long long wgs = (units + 255) / 256;                             // one unit (64 pixels) per lane: a 720p frame is 57 workgroups
+    const dim3 block(256), grid(wgs < 1024 ? (int)wgs : 1024, T - 1);
+    with_esz(fmt, [&](auto esz) {
+        hipLaunchKernelGGL((yuv_diff_stats_mv_kernel<esz()>), grid, block, 0, s, a, b, mv, (unsigned long long*)dst, G, hb, wb, (hb + 7) / 8, (wb + 7) / 8);
     });
     return sn_check_launch();
 }

@@ -20,6 +20,8 @@ the statistics of the same payloads' luma (csrc/sn_yuv_stats.hip), each for one 
 ``rowcol_sums_yuv``: uint32 sums of the luma codes of every row and of every column, for the letterbox rule (shiftnet_amd/picture.py);
 ``diff_stats_yuv``: int64 sums of the difference of two sets of payloads, what came in and what was written, for the method-noise report
                (shiftnet_amd/report.py);
+``diff_stats_mv_yuv``: int64 sums of that difference in consecutive payloads along the vectors of ``block_motion_yuv``, for the report's motion-compensated
+               temporal correlation;
 ``rect=(x0, y0, w, h)``, where a function takes it (all but ``thumb_yuv`` and ``rowcol_sums_yuv``), restricts it to that picture of the stream, with
                the result of the cropped stream;
 ``egress_u8``  == the per-frame ``clamp(0,1) * 255`` -> skimage PSNR(data_range=255) against the uint8 ground truth
@@ -370,4 +372,31 @@ def diff_stats_yuv(ref: torch.Tensor, out: torch.Tensor, fmt: "L.YuvFmt", H: int
     with torch.cuda.device(dev):
         L.check(L.load().sn_yuv_diff_stats(ref.data_ptr(), out.data_ptr(), fmt, r, edge, y.data_ptr(), T, H, W,
                                            torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_diff_stats")
+    return y
+
+
+def diff_stats_mv_yuv(ref: torch.Tensor, out: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, mv: torch.Tensor, rect=None,
+                      out_sums: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ref (what came in) and out (what was written): [T, frame_bytes] uint8 on a HIP device each, T >= 2, the same format and size; ``mv``: int8
+    [T - 1, nby, nbx, 2] as ``block_motion_yuv`` makes it for the same picture (of ``out``, by the restorer's use) -> int64 [T - 1, 8]: per pair of
+    consecutive payloads the exact sums that include/shiftnet_hip.h lists under sn_yuv_diff_stats_mv, over the measuring 2 x 2 luma blocks ((i + j) odd)
+    whose displaced position lies wholly inside the picture: their samples; the sums of d = out - ref and d^2 in the first payload and, where the vector
+    points, in the second; the sum of their product; the sum of the squared difference of ``out`` along the vector; the samples whose vector is not
+    (0, 0).  Any int8 contents of ``mv`` are safe.  ``rect=(x0, y0, w, h)``: the sums of that picture of the stream.  ``out_sums``: a tensor of that
+    shape to overwrite.  report.pair_measures_mv turns a row into numbers."""
+    from .noise import motion_grid
+    T, dev = _payload(ref, fmt, H, W)
+    assert _payload(out, fmt, H, W) == (T, dev)
+    if T < 2:
+        raise ValueError(f"sn_yuv_diff_stats_mv: a pair needs two payloads, got {T}")
+    r = None if rect is None else _rect(rect, fmt, H, W)
+    nby, nbx = motion_grid(H if r is None else r.h, W if r is None else r.w)
+    assert tuple(mv.shape) == (T - 1, nby, nbx, 2) and mv.dtype == torch.int8 and mv.is_contiguous() and mv.device == dev
+    y = out_sums if out_sums is not None else torch.empty((T - 1, L.SN_DIFF_STATS_MV), dtype=torch.int64, device=dev)
+    assert tuple(y.shape) == (T - 1, L.SN_DIFF_STATS_MV) and y.dtype == torch.int64 and y.is_contiguous() and y.device == dev
+    if nby * nbx == 0:                                        # no whole block: no vector to point at, and what the entry point writes then
+        return y.zero_()
+    with torch.cuda.device(dev):
+        L.check(L.load().sn_yuv_diff_stats_mv(ref.data_ptr(), out.data_ptr(), fmt, r, mv.data_ptr(), y.data_ptr(), T, H, W,
+                                              torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_diff_stats_mv")
     return y

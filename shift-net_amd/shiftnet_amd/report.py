@@ -22,19 +22,34 @@ adds its own noise (about 1/4 code^2), and with an ``amount`` below 1 only that 
 unvalidated on real footage**: the deblur variants change edges by design; the edge threshold is a guess; at 4:2:0 the luma noise of real footage
 need not be white to begin with.
 
-``format_report`` / ``parse_report`` are the file of one line per written frame.
+Along block motion (``report_motion="blocks"`` of the restorer): rho_t compares a frame's d with the next frame's AT THE SAME PLACE, so removed detail that
+moves with the picture reads rho_t ~ 0 -- what a noise-only removal reads.  ``sn_yuv_diff_stats_mv`` sums d of the pair along the vectors that
+``sn_yuv_block_motion`` finds on the WRITTEN frames, on the half of the 2 x 2 blocks the vectors were not chosen on: ``SUMS_MV`` names its 8 integers, and
+``pair_measures_mv`` makes of one row
+
+  rho_t_mv = (Nm S01 - S0 S1) / sqrt((Nm S00 - S0^2) (Nm S11 - S1^2))      the correlation of d with the next frame's d where the vector points
+  mv_match_rms = sqrt(Sgg / Nm) / c                     how well the vectors fit the written picture, in 8-bit code units
+  mv_moved = Nv / Nm                                    the share of the counted samples whose vector is not (0, 0)
+  mv_counted = Nm / (h w)                               the share of the picture's samples that were counted (at most about one half)
+
+Its limits: integer-pel vectors within +-7 samples, one per 16 x 16 block; half of the samples; a block at the border whose true vector points outside
+the picture has another vector or none, so a pan reads well below 1 even where everything removed was detail; pairs across window boundaries have no
+value; zoom, rotation and occlusion still read as uncorrelated.  No threshold, no verdict, and as unvalidated on real footage as the rest.
+
+``format_report`` / ``parse_report`` / ``parse_report_motion`` are the file of one line per written frame.
 """
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass, fields
-from typing import Dict, Iterable, List, Optional, Sequence
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from .noise import code_scale, luma_gain
 
 SUMS = ("N", "S1", "S2", "Nx", "Sx", "Ny", "Sy", "St", "Ne", "S2e", "Nc", "Su", "Su2", "Sv", "Sv2", "zero")      # the 16 words of sn_yuv_diff_stats
+SUMS_MV = ("Nm", "S0", "S00", "S1", "S11", "S01", "Sgg", "Nv")                  # the 8 words of sn_yuv_diff_stats_mv
 NAN = float("nan")
 
 
@@ -137,6 +152,69 @@ def frames_report(frame_sums: Sequence, windows: Sequence[int], sigmas: Sequence
     return out
 
 
+@dataclass(eq=False)
+class MotionReport:
+    """The motion part of one written frame's report: the measures of ``pair_measures_mv`` for the pair (frame, frame + 1) where both lie in one
+    window, nan elsewhere -- exactly where ``rho_t`` has a value.  Equality takes nan for equal to nan."""
+    rho_t_mv: float = NAN
+    mv_match_rms: float = NAN
+    mv_moved: float = NAN
+    mv_counted: float = NAN
+
+    def __eq__(self, other) -> bool:
+        if not isinstance(other, MotionReport):
+            return NotImplemented
+        return all(_same(getattr(self, f.name), getattr(other, f.name)) for f in fields(self))
+
+    __hash__ = None
+
+
+COLUMNS_MV = tuple(f.name for f in fields(MotionReport))
+
+
+def pair_measures_mv(sums, bits: int, h: int, w: int) -> MotionReport:
+    """One row of ``sn_yuv_diff_stats_mv`` (the format written has ``bits``; the picture is h x w) -> the four measures, float64 expressions of the exact
+    integers.  None (no pair) -> all nan.  rho_t_mv is nan if nothing was counted or either frame's d has no variance on the counted samples; the
+    other three are nan if nothing was counted (mv_counted: 0.0 then, nan only for an empty picture)."""
+    if sums is None:
+        return MotionReport()
+    s = [int(v) for v in np.asarray(sums).reshape(-1)]
+    if len(s) != len(SUMS_MV):
+        raise ValueError(f"a row of sn_yuv_diff_stats_mv has {len(SUMS_MV)} words, got {len(s)}")
+    Nm, S0, S00, S1, S11, S01, Sgg, Nv = s
+    r = MotionReport()
+    r.mv_counted = _ratio(Nm, int(h) * int(w))
+    if Nm == 0:
+        return r
+    v0, v1 = Nm * S00 - S0 * S0, Nm * S11 - S1 * S1             # Nm^2 var of each
+    if v0 > 0 and v1 > 0:
+        r.rho_t_mv = (Nm * S01 - S0 * S1) / math.sqrt(v0 * v1)
+    r.mv_match_rms = math.sqrt(Sgg / Nm) / float(1 << (bits - 8))
+    r.mv_moved = Nv / Nm
+    return r
+
+
+def frames_report_motion(pair_sums: Sequence, bits: int, sizes: Sequence[Tuple[int, int]]) -> List[MotionReport]:
+    """The motion part of a run's report: ``pair_sums[i]`` is the row of the pair (written frame i, i + 1), or None where the two lie in different
+    windows or i is the last frame; ``sizes[i]`` the (h, w) of the picture frame i's window was restored in."""
+    return [pair_measures_mv(s, bits, *sizes[i]) for i, s in enumerate(pair_sums)]
+
+
+def summarize_motion(motion: Iterable[MotionReport]) -> Dict[str, float]:
+    """The median of every motion measure over the frames that have one (nan where none has)."""
+    motion = list(motion)
+    out = {}
+    for name in COLUMNS_MV:
+        v = [x for x in (getattr(m, name) for m in motion) if not math.isnan(x)]
+        out[name] = float(np.median(v)) if v else NAN
+    return out
+
+
+def summary_line_motion(summary: Dict[str, float]) -> str:
+    """The four motion medians, for a log."""
+    return ", ".join(f"{k} {summary[k]:.3f}" for k in COLUMNS_MV)
+
+
 def summarize(frames: Iterable[FrameReport]) -> Dict[str, float]:
     """The median of every measure over the frames that have one (nan where none has)."""
     frames = list(frames)
@@ -159,31 +237,56 @@ def _word(v) -> str:
     return repr(float(v)) if isinstance(v, float) else str(int(v))     # repr of a float reads back to the same float; nan reads back as nan
 
 
-def format_report(frames: Iterable[FrameReport], how: str = "") -> str:
+def format_report(frames: Iterable[FrameReport], how: str = "", motion: Optional[Iterable[MotionReport]] = None) -> str:
     """The report file: '#' header lines that name the columns, one line per written frame (sigma '-' where the window had none), and the medians of
-    ``summarize`` as the last line, '# median'.  Floats are written so that ``parse_report`` reads back equal reports."""
+    ``summarize`` as the last line, '# median'.  Floats are written so that ``parse_report`` reads back equal reports.  ``motion``: one MotionReport
+    per frame; every line, the median line and the '#' column line then gain its four columns (``parse_report_motion`` reads them back).  Without it
+    the text is what it was before there was a motion part."""
     frames = list(frames)
     med = summarize(frames)
     lines = ["# method noise: written minus input, one line per written frame" + (f" ({how})" if how else ""),
-             "# m, var: luma codes of the format written; sigma, removed_sigma: 8-bit R'G'B' codes; mean_*, rms_*: 8-bit codes; rho_t: to the next frame",
-             "# " + " ".join(COLUMNS)]
-    lines += [" ".join(_word(getattr(f, c)) for c in COLUMNS) for f in frames]
-    lines.append("# median - - - " + " ".join(_word(med[c]) for c in MEASURES))
+             "# m, var: luma codes of the format written; sigma, removed_sigma: 8-bit R'G'B' codes; mean_*, rms_*: 8-bit codes; rho_t: to the next frame"]
+    if motion is None:
+        lines.append("# " + " ".join(COLUMNS))
+        lines += [" ".join(_word(getattr(f, c)) for c in COLUMNS) for f in frames]
+        lines.append("# median - - - " + " ".join(_word(med[c]) for c in MEASURES))
+        return "\n".join(lines) + "\n"
+    motion = list(motion)
+    if len(motion) != len(frames):
+        raise ValueError(f"{len(frames)} frames and {len(motion)} motion reports")
+    mmed = summarize_motion(motion)
+    lines.append("# rho_t_mv: to the next frame along block motion vectors of the written picture (measuring blocks only); mv_match_rms: 8-bit codes; "
+                 "mv_moved, mv_counted: shares")
+    lines.append("# " + " ".join(COLUMNS + COLUMNS_MV))
+    lines += [" ".join([_word(getattr(f, c)) for c in COLUMNS] + [_word(getattr(m, c)) for c in COLUMNS_MV]) for f, m in zip(frames, motion)]
+    lines.append("# median - - - " + " ".join([_word(med[c]) for c in MEASURES] + [_word(mmed[c]) for c in COLUMNS_MV]))
     return "\n".join(lines) + "\n"
 
 
-def parse_report(text: str) -> List[FrameReport]:
-    """The frames of a report file ('#' lines are comments, the medians among them: ``summarize`` makes them again)."""
+def _parse(text: str):
+    """(FrameReport, MotionReport or None) of every line of a report file; a line has the columns of a frame, or those and the four of its motion
+    part ('#' lines are comments, the medians among them: ``summarize`` makes them again)."""
     out = []
+    widths = (len(COLUMNS), len(COLUMNS) + len(COLUMNS_MV))
     for ln, line in enumerate(text.splitlines(), 1):
         body = line.split("#", 1)[0].split()
         if not body:
             continue
-        if len(body) != len(COLUMNS):
-            raise ValueError(f"line {ln}: {len(COLUMNS)} columns expected, got {len(body)}")
+        if len(body) not in widths:
+            raise ValueError(f"line {ln}: {widths[0]} or {widths[1]} columns expected, got {len(body)}")
         try:
             vals = [int(body[0]), int(body[1]), None if body[2] == "-" else float(body[2])] + [float(w) for w in body[3:]]
         except ValueError:
             raise ValueError(f"line {ln}: not a report line: {line!r}") from None
-        out.append(FrameReport(*vals))
+        out.append((FrameReport(*vals[:widths[0]]), MotionReport(*vals[widths[0]:]) if len(body) == widths[1] else None))
     return out
+
+
+def parse_report(text: str) -> List[FrameReport]:
+    """The frames of a report file, with or without a motion part."""
+    return [f for f, _ in _parse(text)]
+
+
+def parse_report_motion(text: str) -> List[Optional[MotionReport]]:
+    """The motion part of every line of a report file; None for a line without one."""
+    return [m for _, m in _parse(text)]

@@ -44,7 +44,9 @@ anyway (``sn_egress_yuv_mix``): amount 0 is the input byte for byte.  The blend 
 Method-noise report (``report``, off by default): numbers about what the run changed, per written frame -- whether input minus output is white in
 space, independent from frame to frame, no stronger on edges than elsewhere, and as strong as the sigma the window was restored with.  Exact integer
 sums of the two sets of payloads the window holds on the device anyway once the egress has run (``sn_yuv_diff_stats``), float64 on the host
-(shiftnet_amd/report.py).  It changes no byte written.  What the numbers mean on real footage nobody has validated.
+(shiftnet_amd/report.py).  It changes no byte written.  What the numbers mean on real footage nobody has validated.  ``report_motion="blocks"`` adds the
+temporal correlation of that difference along the motion of the written picture (``sn_yuv_block_motion`` on the frames written, then
+``sn_yuv_diff_stats_mv``): removed detail that moves with a pan reads as uncorrelated at the same place, and as correlated along its vector.
 """
 from __future__ import annotations
 
@@ -57,7 +59,7 @@ import numpy as np
 
 from .restore_cli import amount_arg, main, make_parser, picture_arg, sigma_arg  # noqa: F401 -- the command line (restore_cli.py), reached through this module
 from .windows import (DITHERS, FUTURE, PAST, PerWindow, _Frames, _SceneFrames, _Thread, amount_form, noise_model_form, pad_multiple,  # noqa: F401
-                      padded_size, picture_form, plan_output, plan_scene_windows, plan_windows, reflect_index, report_form, scene_cuts_form,
+                      padded_size, picture_form, plan_output, plan_scene_windows, plan_windows, reflect_index, report_form, report_motion_form, scene_cuts_form,
                       sigma_estimator_form, sigma_form, sigma_motion_form, window_indices)
 
 VARIANTS = {"deblur": "gshift_deblur1", "deblur_small": "gshift_deblur2", "denoise": "gshift_denoise1", "denoise_small": "gshift_denoise2"}
@@ -111,6 +113,8 @@ class _Slot:
         self.motion_grid = (0, 0)                                 # ... and the vector blocks of the window the slot holds
         self.dev_ref = None                                       # a mix or a report with another format out: the window's input payloads in the format written
         self.report = None                                        # _Stat: the sums of written minus input of the window's own frames
+        self.report_mv = None                                     # report_motion: _Stat of the sums of the window's written pairs along their vectors
+        self.report_vec = self.report_sad = None                  # ... the vectors (flat int8) and SADs of those pairs: they stay on the device
 
 
 class _Run:
@@ -128,10 +132,13 @@ class _Run:
         self.window_sigma_temporal: List = []
         self.window_pair_sigma: List = []
         self.window_pair_motion: List = []                        # sigma_motion: per window, per pair, noise.motion_summary's triple
-        self.launches = {"noise": 0, "nlf": 0, "nlf_map": 0, "picture": 0, "thumb": 0, "noise_pairs": 0, "nlf_pairs": 0, "report": 0, "motion": 0}
+        self.launches = {"noise": 0, "nlf": 0, "nlf_map": 0, "picture": 0, "thumb": 0, "noise_pairs": 0, "nlf_pairs": 0, "report": 0, "motion": 0,
+                         "report_motion": 0, "report_mv": 0}      # report_motion: the block matcher on the written frames, the sums along its vectors
         self.frame_sums: List = []                                # report: the 16 sums of every frame handed out, the window it came from, that window's sigma
         self.frame_window: List[int] = []
         self.frame_sigma: List = []
+        self.pair_sums_mv: List = []                              # report_motion: the 8 sums of the pair (frame, frame + 1) of every frame handed out, or None
+        self.frame_size: List = []                                # ... and the (h, w) of the picture its window was restored in
         self.collected = 0                                        # windows handed out
         self.src = None                                           # the frame source
 
@@ -291,13 +298,25 @@ class VideoRestorer:
     |right - here| + |below - here|, is at least ``report_edge`` 8-bit codes (finite, >= 0; **the default of 16 is a guess nobody has tuned**).  The
     report describes the stream that was written: with ``amount`` the blended one, with ``dither`` the dither is part of d; ``view="removed"`` with
     ``report=True`` is a ValueError.  A noise-only removal reads rho_x ~ rho_y ~ rho_t ~ 0, edge_ratio ~ 1, removed_sigma ~ sigma.  **Unvalidated on real
-    footage**: the deblur variants change edges by design, and at 4:2:0 the luma noise of real footage need not be white to begin with."""
+    footage**: the deblur variants change edges by design, and at 4:2:0 the luma noise of real footage need not be white to begin with.
+    report_motion: None -- today's launches, bytes, stats keys and report; ``"blocks"`` (needs ``report=True``) -- ``rho_t`` compares a frame's d with the
+    next frame's at the same place, so removed detail that moves with the picture reads as uncorrelated, exactly as noise does.  Behind the report's
+    launch, for every window that writes at least two frames, ``sn_yuv_block_motion`` finds the vectors of the WRITTEN frames' pairs (the clean picture,
+    as for the edge rule) and ``sn_yuv_diff_stats_mv`` sums d of both frames of a pair along them, on the half of the 2 x 2 blocks the vectors were not
+    chosen on (two more launches on the main stream; the vectors stay on the device).  ``stats`` then also has ``report_motion``, ``pair_sums_mv`` (per
+    written frame the 8 ints of report.SUMS_MV for the pair with the next frame, None where that one lies in another window),
+    ``frame_report_motion`` (one report.MotionReport per frame: ``rho_t_mv``, the rms of the written picture's difference along the vectors, the share
+    of counted samples that moved, the share of the picture counted), ``report_motion_summary`` (their medians) and ``report_motion_launches``.
+    ``frame_report``, ``frame_sums`` and every byte written stay what they are without it.  It is independent of ``sigma_motion``, whose vectors are
+    those of the input frames as fed.  **Limits**: integer-pel vectors within +-7 samples per 16 x 16 block; half of the samples; blocks at the border
+    whose true vector leaves the picture read low (the synthetic pans of the tests read 0.6 to 0.9 where everything removed was detail); pairs across windows have no value;
+    zoom, rotation and occlusion still read as uncorrelated; no threshold and no verdict; unvalidated on real footage."""
 
     def __init__(self, net, one_len: int, sigma=None, pipeline: bool = True, scene_cuts=None,
                  cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0),
                  picture=None, bar_level: float = 1.0, out_format=None, dither=None, dither_seed: int = 0, noise_model=None,
                  amount=None, view=None, removed_gain: float = 1.0, sigma_estimator: str = "spatial", report: bool = False,
-                 report_edge: float = 16.0, sigma_motion=None) -> None:
+                 report_edge: float = 16.0, sigma_motion=None, report_motion=None) -> None:
         import torch
         from .lib import YuvFmt
         from .noise import check_clamp
@@ -307,6 +326,7 @@ class VideoRestorer:
         # the mix of the last egress (None: the code path without any of it), the amounts and the view as stats reports them
         self.mix, self.amount, self.view = amount_form(amount, view, removed_gain)
         self.report, self.report_edge = report_form(report, report_edge, self.view)      # False: the code path without any of it
+        self.report_motion = report_motion_form(report_motion, self.report)      # None: the code path without any of it
         self.net, self.one_len, self.pipeline = net, int(one_len), bool(pipeline)
         if self.one_len < 1:
             raise ValueError("one_len must be >= 1")
@@ -399,6 +419,13 @@ class VideoRestorer:
             if self.report:                                       # one row per frame the window writes
                 from .lib import SN_DIFF_STATS
                 s.report = _Stat(torch, dev, "report", tout, [(SN_DIFF_STATS,)], torch.int64)
+            if self.report_motion is not None:                    # one row per pair of frames the window writes; the vectors of the largest window's
+                from .lib import SN_DIFF_STATS_MV                 # pairs at the full frame's grid, flat, as sigma_motion keeps its own
+                from .noise import motion_grid
+                blocks = max((tout - 1) * int(np.prod(motion_grid(h, w))), 1)
+                s.report_mv = _Stat(torch, dev, "report_mv", max(tout - 1, 1), [(SN_DIFF_STATS_MV,)], torch.int64)
+                s.report_vec = torch.empty(2 * blocks, dtype=torch.int8, device=dev)
+                s.report_sad = torch.empty(blocks, dtype=torch.uint32, device=dev)
         self.report_code_edge = int(round(self.report_edge * (1 << (ofmt.bits - 8))))      # in codes of the format written
 
     def _size(self, rect) -> Tuple[int, int, int, int]:
@@ -533,7 +560,7 @@ class VideoRestorer:
 
     def _run(self, slot: _Slot, t: int, main) -> int:
         """Forward + egress on the main stream, copy back on the output stream."""
-        from .io_edges import diff_stats_yuv, egress_yuv, ingest_yuv, noise_map_level
+        from .io_edges import block_motion_yuv, diff_stats_mv_yuv, diff_stats_yuv, egress_yuv, ingest_yuv, noise_map_level
         torch, run = self.torch, self.run
         n = t - PAST - FUTURE
         sigma = self._window_sigma(slot, t) if self.V.denoise else None
@@ -586,6 +613,15 @@ class VideoRestorer:
                 written = slot.dev_out[:n]
                 slot.report.launch(n, run, lambda sums: diff_stats_yuv(own, written, self.ofmt, self.h, self.w, rect=rect, edge=self.report_code_edge,
                                                                        out_sums=sums))
+                if slot.report_mv is not None and n >= 2:
+                    # the vectors of the n - 1 pairs of the frames written (the clean picture), then d of both frames of every pair along them
+                    from .noise import motion_grid
+                    gy, gx = motion_grid(*self._size(rect)[:2])
+                    blocks = (n - 1) * gy * gx
+                    mv = slot.report_vec[:2 * blocks].view(n - 1, gy, gx, 2)
+                    block_motion_yuv(written, self.ofmt, self.h, self.w, rect=rect, out_mv=mv, out_sad=slot.report_sad[:blocks].view(n - 1, gy, gx))
+                    run.launches["report_motion"] += 1
+                    slot.report_mv.launch(n - 1, run, lambda sums: diff_stats_mv_yuv(own, written, self.ofmt, self.h, self.w, mv, rect=rect, out_sums=sums))
             slot.ev_done.record(main)
         with torch.cuda.stream(self.s_out):
             self.s_out.wait_event(slot.ev_done)
@@ -602,6 +638,10 @@ class VideoRestorer:
             run.frame_sums += [[int(v) for v in row] for row in sums]
             run.frame_window += [run.collected] * n
             run.frame_sigma += [run.window_sigma[run.collected] if self.V.denoise else None] * n
+            if slot.report_mv is not None:                       # frame i carries the pair (i, i + 1); a window's last frame has none
+                pairs = [[int(v) for v in row] for row in slot.report_mv.wait(n - 1)[0]] if n >= 2 else []
+                run.pair_sums_mv += pairs + [None]
+                run.frame_size += [self._size(run.window_picture[run.collected])[:2]] * n
         run.collected += 1
         return list(slot.pin_out[:n].numpy().copy())
 
@@ -639,6 +679,13 @@ class VideoRestorer:
             stats["frame_report"] = frames_report(run.frame_sums, run.frame_window, run.frame_sigma, self.ofmt.bits, self.ofmt.matrix, self.ofmt.range)
             stats["report_summary"] = summarize(stats["frame_report"])
             stats["report_launches"] = run.launches["report"]
+        if self.report_motion is not None:
+            from .report import frames_report_motion, summarize_motion
+            stats["report_motion"] = self.report_motion
+            stats["pair_sums_mv"] = [None if r is None else list(r) for r in run.pair_sums_mv]
+            stats["frame_report_motion"] = frames_report_motion(run.pair_sums_mv, self.ofmt.bits, run.frame_size)
+            stats["report_motion_summary"] = summarize_motion(stats["frame_report_motion"])
+            stats["report_motion_launches"] = run.launches["report_motion"] + run.launches["report_mv"]
         src = run.src
         if self.scene_cuts is not None:                          # its thread has ended: the stream has been read to its end
             stats["cuts"] = list(src.cuts)

@@ -216,6 +216,21 @@ def report_form(report=False, report_edge=16.0, view=None):
     return bool(report), edge
 
 
+REPORT_MOTIONS = ("blocks",)
+
+
+def report_motion_form(report_motion=None, report=False):
+    """None | "blocks" -> the same; ValueError for anything else, and for "blocks" without ``report=True``: the vectors compensate the report's temporal
+    correlation, and without the report there is nothing to compensate."""
+    if report_motion is None:
+        return None
+    if not (isinstance(report_motion, str) and report_motion in REPORT_MOTIONS):
+        raise ValueError(f"report_motion must be None or 'blocks', got {report_motion!r}")
+    if not (isinstance(report, (bool, np.bool_)) and report):
+        raise ValueError(f"report_motion={report_motion!r} follows the picture in the report's temporal correlation: it needs report=True")
+    return report_motion
+
+
 def picture_form(picture):
     """None -> ("full", None); "auto" -> ("auto", None); four numbers -> ("fixed", the tuple); anything whose elements are sequences or None ->
     ("list", the list).  The rectangles are judged where the stream is known (picture.check_pictures)."""

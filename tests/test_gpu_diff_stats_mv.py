@@ -1,0 +1,357 @@
+"""-m gpu: ``sn_yuv_diff_stats_mv`` against its numpy restatement (tests/diff_stats_mv_ref.py) word for word -- the sums are integers, so every
+comparison is ``==`` -- for the matcher's vectors and for any int8 contents of ``mv``, and the video restorer with ``report_motion="blocks"``: the bytes
+and the report of ``report=True`` alone, the sums of the restatement on the payloads that went in and came out, window by window, along the vectors of
+tests/motion_ref.py on the written payloads, and the host function of shiftnet_amd/report.py on those sums."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import diff_stats_mv_ref as DM
+import motion_ref as M
+import scene_ref as S
+import yuv_ref as R
+from shiftnet_amd import lib as L
+from shiftnet_amd import report, restore, y4m
+from shiftnet_amd.io_edges import block_motion_yuv, diff_stats_mv_yuv, yuv_fmt
+from test_gpu_noise import FRAMES, H, ONE_LEN, W, noisy_clip, same
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FORMATS = [R.Fmt(bits, chroma, R.BT709, R.LIMITED) for bits in (8, 10) for chroma in (R.C444, R.C420_CENTER)]
+IDS = [f"{f.bits}bit-{('444', '420c')[f.chroma]}" for f in FORMATS]
+GARBAGE = -0x5A5A5A5A5A5A5A5B                                  # what dst holds before a call
+WORDS = 8
+
+
+# ---- the kernel ---------------------------------------------------------------------------------------------------------------------------
+def _pair(fmt, T, h, w, seed, wild=True):
+    """(a, b) uint8 [T, frame_bytes]: b a ramp with steps and noise seen through a window that moves by (2, -3) samples per frame, so that the matcher
+    finds non-zero vectors; a = b plus other noise, both clipped to the codes of the format; at 10 bit with ``wild`` a few words of both hold anything
+    up to 65535 (samples are taken as stored).  The chroma planes hold anything: they are not read."""
+    rng = np.random.default_rng(seed)
+    top = (1 << fmt.bits) - 1
+    n = R.frame_bytes(fmt, h, w) // (1 if fmt.bits == 8 else 2)
+    y, x = np.mgrid[0:h + 40, 0:w + 40]
+    canvas = top * (0.2 + 0.5 * ((x // 5) * 5 + y) / (h + w + 78)) + rng.normal(0.0, 0.04 * top, y.shape) + 0.2 * top * ((y // 7) & 1)
+    canvas = np.clip(np.rint(canvas), 0, top).astype(np.int64)
+    b = rng.integers(0, top + 1, (T, n))
+    for t in range(T):
+        y0, x0 = 20 - 2 * t, 20 + 3 * t
+        b[t, :h * w] = canvas[y0:y0 + h, x0:x0 + w].reshape(-1)
+    a = np.clip(b + np.rint(rng.normal(0.0, 0.03 * top, b.shape)).astype(np.int64), 0, top)
+    if fmt.bits == 10 and wild:
+        for p in (a, b):
+            k = rng.integers(0, p.size, max(p.size // 50, 1))
+            p.reshape(-1)[k] = rng.integers(1024, 65536, k.size)
+        a[0, 0], b[0, 0] = 65535, 0
+    as_bytes = (lambda p: p.astype(np.uint8)) if fmt.bits == 8 else (lambda p: p.astype("<u2").view(np.uint8).reshape(T, -1))
+    return as_bytes(a), as_bytes(b)
+
+
+def _at(p, off):
+    """The payloads on the device, their first byte ``off`` bytes past a 16-byte boundary."""
+    T, fb = p.shape
+    buf = torch.zeros(T * fb + 32, dtype=torch.uint8, device="cuda")
+    base = (-buf.data_ptr()) % 16 + off
+    dev = buf[base:base + T * fb].view(T, fb)
+    dev.copy_(torch.from_numpy(p))
+    assert dev.data_ptr() % 16 == off
+    return dev
+
+
+def _guarded(P):
+    """dst as garbage between guard words -> (the whole buffer, the [P, 8] view inside)."""
+    g = torch.full((P * WORDS + 16,), GARBAGE, dtype=torch.int64, device="cuda")
+    return g, g[8:8 + P * WORDS].view(P, WORDS)
+
+
+def _vectors(db, f, h, w, T, seed):
+    """name -> int8 [T - 1, nby, nbx, 2] on the host: the matcher's for the written payloads, and contents no matcher writes."""
+    grid = (T - 1,) + M.grid(h, w) + (2,)
+    rng = np.random.default_rng(seed)
+    return {"matcher": block_motion_yuv(db, f, h, w)[0].cpu().numpy(), "zero": np.zeros(grid, np.int8), "+7": np.full(grid, 7, np.int8),
+            "-7": np.full(grid, -7, np.int8), "any int8": rng.integers(-128, 128, grid).astype(np.int8)}
+
+
+SHAPES = [(1, 1), (1, 9), (2, 2), (3, 3), (16, 16), (17, 33), (37, 53), (64, 64), (66, 130)]
+
+
+@pytest.mark.parametrize("fmt", FORMATS, ids=IDS)
+def test_diff_stats_mv_equals_the_numpy_restatement_exactly_overwrites_and_writes_nothing_else(fmt):
+    f = yuv_fmt(*fmt)
+    offsets = (0, 1, 3) if fmt.bits == 8 else (0, 2)
+    moved = counted = 0
+    for (h, w), T in [(s, t) for s in SHAPES for t in (2, 3, 5)] + [((256, 512), 2)]:
+        a, b = _pair(fmt, T, h, w, seed=h * 1000 + w + T)
+        vectors = _vectors(_at(b, 0), f, h, w, T, seed=h + w + T)
+        want = {k: DM.diff_stats_mv_ref(a, b, v, fmt, h, w) for k, v in vectors.items()}
+        assert (want["zero"][:, 0] == 4 * ((h // 2) * (w // 2) // 2)).all() and (want["zero"][:, 7] == 0).all()
+        assert (want["+7"][:, 7] == want["+7"][:, 0]).all() and (want["matcher"][:, 0] == want["zero"][:, 0]).all()      # the matcher's vectors push nothing out
+        moved += int(want["matcher"][:, 7].sum())
+        counted += int(want["any int8"][:, 0].sum())
+        for off in (offsets if (h, w) != (256, 512) else offsets[:2]):
+            da, db = _at(a, off), _at(b, off)
+            for name, v in vectors.items():
+                mv = torch.from_numpy(v).cuda()
+                g, out = _guarded(T - 1)
+                got = diff_stats_mv_yuv(da, db, f, h, w, mv, out_sums=out)
+                assert got.shape == (T - 1, WORDS) and got.dtype == torch.int64
+                assert np.array_equal(got.cpu().numpy(), want[name]), (fmt, h, w, T, off, name)
+                if name == "matcher":
+                    diff_stats_mv_yuv(da, db, f, h, w, mv, out_sums=out)            # a second call into what is now there: the same words
+                    assert np.array_equal(out.cpu().numpy(), want[name]), (fmt, h, w, T, off, "second call")
+                    ends = g.cpu().numpy()
+                    assert (ends[:8] == GARBAGE).all() and (ends[8 + (T - 1) * WORDS:] == GARBAGE).all()
+    assert moved > 0 and counted > 0                                                  # the matcher did find motion; random vectors leave blocks inside
+    got = diff_stats_mv_yuv(da, db, f, h, w, torch.from_numpy(vectors["matcher"]).cuda())      # allocating form
+    assert np.array_equal(got.cpu().numpy(), want["matcher"])
+
+
+@pytest.mark.parametrize("fmt", FORMATS, ids=IDS)
+def test_a_rectangle_gives_the_sums_of_the_cropped_stream(fmt):
+    f = yuv_fmt(*fmt)
+    h, w, T = 37, 53, 2
+    a, b = _pair(fmt, T, h, w, seed=5)
+    rng = np.random.default_rng(6)
+    for off in ((0, 1, 3) if fmt.bits == 8 else (0, 2)):
+        da, db = _at(a, off), _at(b, off)
+        # even origin and size; odd w and h that reach the far edge; two rows; the one pixel in the far corner (its origin is even: legal at 4:2:0 too)
+        for rect in [(4, 6, 20, 12), (10, 8, w - 10, h - 8), (0, 0, 8, 2), (w - 1, h - 1, 1, 1)]:
+            grid = (T - 1,) + M.grid(rect[3], rect[2]) + (2,)
+            matcher = block_motion_yuv(db, f, h, w, rect=rect)[0]
+            assert np.array_equal(matcher.cpu().numpy(), M.block_motion_ref(b, fmt, h, w, rect=rect)[0])
+            for v in (matcher.cpu().numpy(), np.zeros(grid, np.int8), rng.integers(-128, 128, grid).astype(np.int8)):
+                want = DM.diff_stats_mv_ref(a, b, v, fmt, h, w, rect=rect)
+                crop = [np.stack([M.F.luma_of(p, fmt, h, w, rect) for p in x]) for x in (a, b)]      # the cropped stream's luma, the grid anchored at the rectangle
+                assert list(want[0]) == DM.sums_of_pair(crop[0][0], crop[1][0], crop[0][1], crop[1][1], v[0])
+                g, out = _guarded(T - 1)
+                got = diff_stats_mv_yuv(da, db, f, h, w, torch.from_numpy(v).cuda(), rect=rect, out_sums=out)
+                assert np.array_equal(got.cpu().numpy(), want), (fmt, rect, off)
+                ends = g.cpu().numpy()
+                assert (ends[:8] == GARBAGE).all() and (ends[8 + (T - 1) * WORDS:] == GARBAGE).all()
+        zero = torch.zeros((T - 1,) + M.grid(h, w) + (2,), dtype=torch.int8, device="cuda")
+        whole = DM.diff_stats_mv_ref(a, b, zero.cpu().numpy(), fmt, h, w)
+        assert np.array_equal(diff_stats_mv_yuv(da, db, f, h, w, zero, rect=(0, 0, w, h)).cpu().numpy(), whole)
+        assert np.array_equal(diff_stats_mv_yuv(da, db, f, h, w, zero).cpu().numpy(), whole)
+
+
+@pytest.mark.parametrize("bits", [8, 10])
+def test_extremes_are_exact_where_a_32_bit_partial_sum_is_not(bits):
+    fmt = R.Fmt(bits, R.C420_CENTER, R.BT709, R.FULL)
+    f = yuv_fmt(*fmt)
+    top = (1 << bits) - 1
+    for h, w, T, code in [(66, 130, 2, top), (256, 512, 2, 0xFFFF if bits == 10 else top)]:
+        fb = R.frame_bytes(fmt, h, w)
+        a = np.zeros((T, fb), np.uint8)
+        b = np.full((T, fb // 2), code, "<u2").view(np.uint8).reshape(T, fb) if bits == 10 else np.full((T, fb), code, np.uint8)
+        grid = (T - 1,) + M.grid(h, w) + (2,)
+        zero, far = np.zeros(grid, np.int8), np.full(grid, 7, np.int8)
+        n, c2 = 4 * ((h // 2) * (w // 2) // 2), code * code
+        want = DM.diff_stats_mv_ref(a, b, zero, fmt, h, w)
+        assert list(want[0]) == [n, n * code, n * c2, n * code, n * c2, n * c2, 0, 0]
+        assert code != 0xFFFF or n * c2 > 2 ** 47                                     # far beyond 32 bit: one lane's 32 samples already are
+        da, db = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+        dz, df = torch.from_numpy(zero).cuda(), torch.from_numpy(far).cuda()
+        assert np.array_equal(diff_stats_mv_yuv(da, db, f, h, w, dz).cpu().numpy(), want)
+        assert np.array_equal(diff_stats_mv_yuv(db, da, f, h, w, df).cpu().numpy(), DM.diff_stats_mv_ref(b, a, far, fmt, h, w))      # d = -code: negative sums
+        mixed = np.concatenate([a[:1], b[1:]])                                        # the written picture jumps from 0 to the top code: g^2 is the largest there is
+        assert np.array_equal(diff_stats_mv_yuv(da, torch.from_numpy(mixed).cuda(), f, h, w, dz).cpu().numpy(),
+                              DM.diff_stats_mv_ref(a, mixed, zero, fmt, h, w))
+        got = diff_stats_mv_yuv(db, db, f, h, w, dz).cpu().numpy()                    # the same tensor twice
+        assert [list(r) for r in got] == [[n, 0, 0, 0, 0, 0, 0, 0]] * (T - 1)
+
+
+def test_bad_arguments_return_einval_and_leave_dst_untouched():
+    lib = L.load()
+    f420, f10 = yuv_fmt(8, L.SN_YUV_420_CENTER, 0, 0), yuv_fmt(10, L.SN_YUV_444, 0, 0)
+    h, w = 16, 24
+    pay = 3 * h * w * 2                                                               # the largest payload used: 10 bit 4:4:4
+    buf = torch.zeros(4 * pay + 96, dtype=torch.uint8, device="cuda")
+    vec = torch.zeros(64, dtype=torch.int8, device="cuda")                            # the grid of 16 x 24 is 1 x 2: 4 bytes per pair
+    g, out = _guarded(2)
+    s = torch.cuda.current_stream().cuda_stream
+    a, b, d, m = buf.data_ptr(), buf.data_ptr() + 2 * pay + 32, out.data_ptr(), vec.data_ptr()
+    call = lib.sn_yuv_diff_stats_mv
+    rect = L.YuvRect
+    bad = [
+        (None, b, f420, None, m, d, 2, h, w), (a, None, f420, None, m, d, 2, h, w), (a, b, f420, None, m, None, 2, h, w),            # null a, b, dst
+        (a, b, None, None, m, d, 2, h, w),                                                                                          # null fmt
+        (a, b, f420, None, None, d, 2, h, w),                                                                                       # null mv
+        (a, b, yuv_fmt(12, 0, 0, 0), None, m, d, 2, h, w), (a, b, yuv_fmt(8, 3, 0, 0), None, m, d, 2, h, w),                        # bits 12, chroma code
+        (a + 1, b, f10, None, m, d, 2, h, w), (a, b + 1, f10, None, m, d, 2, h, w),                                                 # 10 bit at an odd address
+        (a, b, f420, rect(8, 8, 24, 8), m, d, 2, h, w), (a, b, f420, rect(0, 0, 8, 17), m, d, 2, h, w),                             # a rect off the frame
+        (a, b, f420, rect(0, 0, 0, 8), m, d, 2, h, w),
+        (a, b, f420, rect(1, 0, 8, 8), m, d, 2, h, w), (a, b, f420, rect(0, 1, 8, 8), m, d, 2, h, w),                               # an odd origin at 4:2:0
+        (a, b, f420, rect(0, 0, 7, 8), m, d, 2, h, w),                                                                              # an odd width inside
+        (a, b, f420, None, m, d, 1, h, w), (a, b, f420, None, m, d, 0, h, w), (a, b, f420, None, m, d, -1, h, w),                   # T: a pair needs two
+        (a, b, f420, None, m, d, 65536, h, w),
+        (a, b, f420, None, m, d, 2, 0, w), (a, b, f420, None, m, d, 2, h, 0),                                                       # H, W
+        (a, b, f420, None, m, d + 4, 2, h, w),                                                                                      # dst is int64
+        (a, b, f420, None, m, d, 2, 400000, 400000),                                                                                # 50000 x 50000 units: beyond the bound
+    ]
+    for args in bad:
+        assert call(*args, s) == -22, args
+    torch.cuda.synchronize()
+    assert (g.cpu().numpy() == GARBAGE).all()
+    assert call(a + 1, b + 3, f420, rect(2, 2, 8, 8), m, d, 3, h, w, s) == 0            # 8-bit payloads may lie anywhere; a legal rect; two pairs
+    torch.cuda.synchronize()
+    ends = g.cpu().numpy()
+    assert (ends[:8] == GARBAGE).all() and (ends[8 + 16:] == GARBAGE).all()
+    assert [list(r) for r in ends[8:24].reshape(2, 8)] == [[32, 0, 0, 0, 0, 0, 0, 0]] * 2      # zeros minus zeros: 8 of the 16 blocks measure
+    assert call(a, b, f10, rect(1, 1, 7, 7), m, d, 2, h, w, s) == 0                      # 4:4:4 takes any rectangle; 3 x 3 blocks, 4 of them measure
+    torch.cuda.synchronize()
+    assert list(g.cpu().numpy()[8:16]) == [16, 0, 0, 0, 0, 0, 0, 0]
+    with pytest.raises(ValueError, match="two payloads"):
+        diff_stats_mv_yuv(buf[:pay // 4].view(1, -1), buf[:pay // 4].view(1, -1), f420, h, w, vec[:0].view(0, 1, 2, 2))
+
+
+# ---- the restorer -------------------------------------------------------------------------------------------------------------------------
+SIGMA = 10.0
+RECT = (8, 6, 64, 48)
+NEW_KEYS = ("report_motion", "pair_sums_mv", "frame_report_motion", "report_motion_summary", "report_motion_launches")
+
+
+@pytest.fixture(scope="module")
+def clip():
+    return restore.load_net("denoise_small", "synthetic", "bf16"), noisy_clip()
+
+
+def run(net, pay, **kw):
+    vr = restore.VideoRestorer(net, ONE_LEN, sigma=SIGMA, **kw)
+    out = list(vr.restore(iter(pay), yuv_fmt(*S.FMT420), H, W))
+    return out, vr.stats, vr
+
+
+def windows_of(cuts=()):
+    """(first frame, frames) of every window, in the order restored."""
+    plan = restore.plan_scene_windows(FRAMES, ONE_LEN, cuts) if cuts else restore.plan_windows(FRAMES, ONE_LEN)
+    return [(lo, n) for lo, n, _ in plan]
+
+
+def host_pairs(ref, out, fmt, cuts=(), rect=None):
+    """What the restorer must report: per written frame the restatement's row of the pair with the next frame, along the vectors of the written
+    payloads, one launch per window that writes two frames or more; None for a window's last frame."""
+    ref, out = np.stack(ref), np.stack(out)
+    rows = []
+    for lo, n in windows_of(cuts):
+        if n >= 2:
+            mv, _ = M.block_motion_ref(out[lo:lo + n], fmt, H, W, rect=rect)
+            rows += [[int(v) for v in r] for r in DM.diff_stats_mv_ref(ref[lo:lo + n], out[lo:lo + n], mv, fmt, H, W, rect=rect)]
+        rows.append(None)
+    return rows
+
+
+def check_motion(stats, vr, ref, out, fmt, cuts=(), rect=None):
+    rows = host_pairs(ref, out, fmt, cuts, rect)
+    assert len(rows) == FRAMES and stats["pair_sums_mv"] == rows and stats["report_motion"] == "blocks"
+    h, w = (H, W) if rect is None else (rect[3], rect[2])
+    want = [report.pair_measures_mv(r, fmt.bits, h, w) for r in rows]
+    assert stats["frame_report_motion"] == want
+    assert list(stats["report_motion_summary"]) == list(report.COLUMNS_MV)
+    assert all(report._same(stats["report_motion_summary"][k], v) for k, v in report.summarize_motion(want).items())
+    pairs = sum(1 for _, n in windows_of(cuts) if n >= 2)
+    assert stats["report_motion_launches"] == 2 * pairs and vr.run.launches["report_motion"] == pairs == vr.run.launches["report_mv"]
+    assert stats["report_launches"] == len(windows_of(cuts))
+    last = {lo + n - 1 for lo, n in windows_of(cuts)}
+    for f, m in zip(stats["frame_report"], stats["frame_report_motion"]):             # a value exactly where rho_t has one
+        assert np.isnan(m.rho_t_mv) == (f.frame in last) == np.isnan(f.rho_t) and np.isnan(m.mv_counted) == (f.frame in last)
+    assert all(0.0 < m.mv_counted <= 0.5 for m in want if not np.isnan(m.mv_counted))
+
+
+@pytest.fixture(scope="module")
+def plain(clip):
+    """The run every other is compared with: the report without the option.  And the run with it."""
+    net, pay = clip
+    off, stats_off, vr_off = run(net, pay, report=True)
+    assert not any(k in stats_off for k in NEW_KEYS)
+    assert vr_off.run.launches["report_motion"] == 0 and vr_off.run.launches["report_mv"] == 0
+    assert all(s.report_mv is None and s.report_vec is None and s.report_sad is None for s in vr_off.slots)
+    on, stats_on, vr_on = run(net, pay, report=True, report_motion="blocks")
+    return off, stats_off, on, stats_on, vr_on
+
+
+def test_the_option_changes_no_byte_and_no_report_and_equals_the_restatement_pipelined_and_not(clip, plain):
+    net, pay = clip
+    off, stats_off, on, stats, vr = plain
+    assert len(off) == FRAMES and same(on, off) and not same(off, pay)
+    assert windows_of() == [(0, 5), (5, 5), (10, 5), (15, 5), (20, 5), (25, 1)]       # a one-frame tail window: no pair, no launch
+    for k in ("frame_sums", "frame_report", "report_launches", "noise_launches", "window_sigma"):
+        assert stats[k] == stats_off[k], k
+    assert all(report._same(stats["report_summary"][k], v) for k, v in stats_off["report_summary"].items())
+    assert set(stats) - set(stats_off) == set(NEW_KEYS)
+    check_motion(stats, vr, pay, on, S.FMT420)
+    assert stats["report_motion_launches"] == 10 and stats["pair_sums_mv"][25] is None and stats["pair_sums_mv"][24] is None
+    serial, stats2, vr2 = run(net, pay, report=True, report_motion="blocks", pipeline=False)
+    assert same(serial, off) and stats2["pair_sums_mv"] == stats["pair_sums_mv"] and stats2["frame_report_motion"] == stats["frame_report_motion"]
+    assert stats2["frame_report"] == stats["frame_report"] and stats2["report_motion_launches"] == 10
+
+
+def test_the_motion_report_of_a_picture_is_over_its_rectangle(clip):
+    net, pay = clip
+    on, stats, vr = run(net, pay, picture=RECT, report=True, report_motion="blocks")
+    check_motion(stats, vr, pay, on, S.FMT420, rect=RECT)
+    assert all(r is None or r[0] == 4 * ((RECT[2] // 2) * (RECT[3] // 2) // 2) for r in stats["pair_sums_mv"])
+
+
+def test_the_motion_report_with_scene_cuts_follows_the_windows_of_the_scenes(clip):
+    net, pay = clip
+    cuts = [7, 12]
+    on, stats, vr = run(net, pay, scene_cuts=cuts, report=True, report_motion="blocks")
+    assert windows_of(cuts) == [(0, 5), (5, 2), (7, 5), (12, 5), (17, 5), (22, 4)]
+    check_motion(stats, vr, pay, on, S.FMT420, cuts=cuts)
+    assert stats["report_motion_launches"] == 12
+
+
+def test_another_output_format_is_compared_with_the_converted_input(clip):
+    net, pay = clip
+    tag = "444p10"
+    ofmt = R.Fmt(10, R.C444, S.FMT420.matrix, S.FMT420.range)
+    conv, _, _ = run(net, pay, out_format=tag, amount=0.0)                            # amount 0 returns the converted input byte for byte
+    on, stats, vr = run(net, pay, out_format=tag, report=True, report_motion="blocks")
+    assert len(on[0]) == R.frame_bytes(ofmt, H, W)
+    check_motion(stats, vr, conv, on, ofmt)
+
+
+def test_the_deblur_variant_reports_along_motion_too():
+    net, pay = restore.load_net("deblur_small", "synthetic", "bf16"), noisy_clip()
+    vr = restore.VideoRestorer(net, ONE_LEN, report=True, report_motion="blocks")
+    on = list(vr.restore(iter(pay), yuv_fmt(*S.FMT420), H, W))
+    off = list(restore.VideoRestorer(net, ONE_LEN, report=True).restore(iter(pay), yuv_fmt(*S.FMT420), H, W))
+    assert same(on, off)
+    check_motion(vr.stats, vr, pay, on, S.FMT420)
+
+
+def test_argument_errors_of_the_restorer(clip):
+    net, _ = clip
+    with pytest.raises(ValueError, match="needs report=True"):
+        restore.VideoRestorer(net, ONE_LEN, sigma=SIGMA, report_motion="blocks")
+    with pytest.raises(ValueError, match="report_motion must be"):
+        restore.VideoRestorer(net, ONE_LEN, sigma=SIGMA, report=True, report_motion="pixels")
+    assert restore.VideoRestorer(net, ONE_LEN, sigma=SIGMA, report=True).report_motion is None
+
+
+# ---- the command line -------------------------------------------------------------------------------------------------------------------------
+def test_restore_video_cli_writes_the_motion_columns_of_the_api(clip, plain, tmp_path):
+    _, pay = clip
+    off, _, _, stats, _ = plain
+    hd = y4m.Y4MHeader(width=W, height=H, fps="24:1", aspect="1:1", chroma="420jpeg", extensions=["COLORRANGE=LIMITED"])
+    src, dst, rep = tmp_path / "in.y4m", tmp_path / "out.y4m", tmp_path / "r.txt"
+    with open(src, "wb") as fh:
+        wr = y4m.Y4MWriter(fh, hd)
+        for p in pay:
+            wr.write(p)
+    cmd = [sys.executable, os.path.join(ROOT, "inference", "restore_video.py"), "--variant", "denoise_small", "--checkpoint", "synthetic",
+           "--dtype", "bf16", "--one_len", str(ONE_LEN), "--sigma", str(SIGMA), "--report", str(rep), "--report_motion", "blocks", str(src), str(dst)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "done: 26 frames" in r.stderr and "report along block motion" in r.stderr and "rho_t_mv" in r.stderr
+    text = rep.read_text()
+    assert report.parse_report(text) == stats["frame_report"] and report.parse_report_motion(text) == stats["frame_report_motion"]
+    assert text.splitlines()[-1].startswith("# median ") and "rho_t_mv" in text
+    with open(dst, "rb") as fh:
+        assert same(list(y4m.Y4MReader(fh)), off)

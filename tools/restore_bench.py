@@ -27,9 +27,10 @@
             interleaved as in the kernels part; since 3.20 also sn_yuv_noise_hist_pairs and sn_yuv_noise_hist_pairs_bands.  --mode forward: steady-state wall time per 720p window of the pipelined denoiser (as the sigma part)
             with sigma="auto" alone and with noise_model="level" on top, runs of the two alternating in one process, the first two windows left out.
   report  : the method-noise report (3.21).  --mode kernels: time per launch of sn_yuv_diff_stats (4:2:0 8 bit, 720p x 16 frames: a noisy clip against its
-            clean twin, edge 16) beside sn_egress_yuv from float32 and sn_yuv_noise_hist_pairs on the same frames, interleaved as in the kernels part.
-            --mode forward: steady-state wall time per 720p window of the pipelined denoiser (as the sigma part, sigma=10.0) with report=False and with
-            report=True, runs of the two alternating in one process, the first two windows left out.
+            clean twin, edge 16) beside sn_egress_yuv from float32 and sn_yuv_noise_hist_pairs on the same frames, interleaved as in the kernels part;
+            since 3.26 also sn_yuv_diff_stats_mv with the matcher's vectors and with all-zero vectors, and sn_yuv_block_motion on the written payloads.
+            --mode forward: steady-state wall time per 720p window of the pipelined denoiser (as the sigma part, sigma=10.0) with report=False, with
+            report=True and with report_motion="blocks" on top, runs of the three alternating in one process, the first two windows left out.
   motion  : the motion-compensated temporal estimate (3.23).  --mode kernels: time per launch of sn_yuv_block_motion, sn_yuv_noise_hist_pairs_mv and
             sn_yuv_noise_hist_pairs_bands_mv beside the two plain pair histograms (4:2:0 8 bit, 720p x 20 frames with noise of sigma 10), interleaved as
             in the kernels part.  --mode forward: steady-state wall time per 720p window of the pipelined denoiser (as the sigma part) with
@@ -55,7 +56,7 @@ import torch  # noqa: E402
 
 from shiftnet_amd import lib as L  # noqa: E402
 from shiftnet_amd import restore, synth, y4m  # noqa: E402
-from shiftnet_amd.io_edges import (block_motion_yuv, noise_hist_pairs_bands_mv_yuv, noise_hist_pairs_mv_yuv, diff_stats_yuv, egress_u8, egress_yuv, ingest_u8, ingest_yuv, noise_hist_bands_yuv, noise_hist_pairs_bands_yuv, noise_hist_pairs_yuv,  # noqa: E402
+from shiftnet_amd.io_edges import (block_motion_yuv, noise_hist_pairs_bands_mv_yuv, noise_hist_pairs_mv_yuv, diff_stats_mv_yuv, diff_stats_yuv, egress_u8, egress_yuv, ingest_u8, ingest_yuv, noise_hist_bands_yuv, noise_hist_pairs_bands_yuv, noise_hist_pairs_yuv,  # noqa: E402
                                    noise_hist_yuv, noise_map_level, rowcol_sums_yuv, thumb_yuv, yuv_fmt)
 
 
@@ -463,11 +464,17 @@ def report_kernels(a):
     dst = torch.empty_like(clean)
     sums = torch.empty((T, L.SN_DIFF_STATS), dtype=torch.int64, device="cuda")
     pairs = torch.empty((T - 1, 1021), dtype=torch.uint32, device="cuda")
+    sums_mv = torch.empty((T - 1, L.SN_DIFF_STATS_MV), dtype=torch.int64, device="cuda")
+    mv, sad = block_motion_yuv(clean, fmt, H, W)                                     # the vectors of the written payloads, as the restorer takes them
+    mv0 = torch.zeros_like(mv)
     cases = {
         "egress_yuv_fp32": lambda: egress_yuv(rgb, fmt, H, W, dst=dst),              # the launch the statistic follows: three times the bytes
         "diff_stats_yuv": lambda: diff_stats_yuv(noisy, clean, fmt, H, W, edge=16, out_sums=sums),
         "diff_stats_yuv_same": lambda: diff_stats_yuv(clean, clean, fmt, H, W, edge=16, out_sums=sums),      # d = 0 everywhere: the same loads
         "noise_hist_pairs_yuv": lambda: noise_hist_pairs_yuv(noisy, fmt, H, W, out=pairs),                   # a statistic that reads every luma plane twice
+        "diff_stats_mv_yuv": lambda: diff_stats_mv_yuv(noisy, clean, fmt, H, W, mv, out_sums=sums_mv),      # report_motion: along the matcher's vectors
+        "diff_stats_mv_yuv_zero": lambda: diff_stats_mv_yuv(noisy, clean, fmt, H, W, mv0, out_sums=sums_mv),      # all-zero vectors: the displaced rows are aligned
+        "block_motion_yuv": lambda: block_motion_yuv(clean, fmt, H, W, out_mv=mv, out_sad=sad),              # ... and the matcher that precedes it
     }
     for f in cases.values():
         for _ in range(3):
@@ -486,7 +493,8 @@ def report_kernels(a):
     px = T * H * W
     res = {k: {"us_per_launch": summary([m * 1e3 for m in v]), "ps_per_pixel": summary([m * 1e9 / px for m in v])} for k, v in ms.items()}
     print(json.dumps({"part": "report", "mode": "kernels", "frames": T, "size": [H, W], "reps": a.reps, "inner": a.inner,
-                      "note": "diff_stats and the pair histogram include the memset of dst", **res}))
+                      "note": "diff_stats, diff_stats_mv and the pair histogram include the memset of dst",
+                      "mv_nonzero_share": round(float((mv != 0).any(dim=-1).float().mean()), 4), **res}))
 
 
 def report_forward(a):
@@ -505,7 +513,7 @@ def report_forward(a):
     seen = {}
 
     def run(rep):
-        vr = restore.VideoRestorer(net, one_len, sigma=10.0, pipeline=True, report=rep)
+        vr = restore.VideoRestorer(net, one_len, sigma=10.0, pipeline=True, report=bool(rep), report_motion="blocks" if rep == "motion" else None)
         stamps = []
         t0 = time.perf_counter()
         for i, p in enumerate(vr.restore(iter(frames), fmt, H, W)):
@@ -518,10 +526,12 @@ def report_forward(a):
 
     run(False)                                                                       # warm-up: code objects, engine buffers
     run(True)
-    runs = {"off": [], "report": []}
+    run("motion")
+    runs = {"off": [], "report": [], "report_motion": []}
     for _ in range(a.runs):
         runs["off"].append(run(False))
         runs["report"].append(run(True))
+        runs["report_motion"].append(run("motion"))
     res = {}
     for k, rs in runs.items():
         res[k] = {"window_wall_ms": summary([g for r in rs for g in r["window_wall_ms"]]),
