@@ -241,7 +241,7 @@ int sn_gsts_shiftconv_mfma_opt(const sn_unit_src* s, const int8_t* offs, const u
  * operand, prep.pk_f16_words of the [9][2C] table with the identity folded into the centre tap).
  * g1_blocked = 0: g1 natural NHWC [T][h][w][C] (sn_grp5_gemm_gate);
  * g1_blocked = 2 (C = 64 only): channel-planar [T][h][C][sn_planar_pitch(w)], zeros in the pad columns (sn_dw5m_gemm_gate).
- * pool: NULL or [T][sn_lngate_blocks][C]. */
+ * pool: NULL or [T][sn_lngate_blocks][C].  T, h or w below 1 is SN_EINVAL like every other bad operand: nothing is launched. */
 int sn_ln_gemm_gate(const sn_unit_src* s, const void* hw, const void* wfrag, const float* bias, const uint32_t* wdw,
                     void* g1, float* pool, int g1_blocked, void* stream);
 int sn_lngate_blocks(int h, int w);

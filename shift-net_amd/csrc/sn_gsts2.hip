@@ -459,7 +459,7 @@ int sn_lngate_blocks(int h, int w) { return (SN_K12_TH * 32 / 64) * ((h + SN_K12
 int sn_ln_gemm_gate(const sn_unit_src* s, const void* hw, const void* wfrag, const float* bias, const uint32_t* wdw,
                     void* g1, float* pool, int g1_blocked, void* stream) {
     sn_clear_error();
-    if (!s || !s->x || (s->C != 64 && s->C != 80) || s->mode < 0 || s->mode > 2 || !wfrag || !bias || !wdw || !g1 ||
+    if (!s || !s->x || (s->C != 64 && s->C != 80) || s->T < 1 || s->h < 1 || s->w < 1 || s->mode < 0 || s->mode > 2 || !wfrag || !bias || !wdw || !g1 ||
         (s->mode != 0 && !hw) || (g1_blocked && s->C != 64) || (g1_blocked != 0 && g1_blocked != 2) || (s->wrap == 2 && s->mode != 0 && !s->halo))
         return SN_EINVAL;
     UnitK2 u; u.x = (const bf16_t*)s->x; u.halo = (const bf16_t*)s->halo; u.T = s->T; u.h = s->h; u.w = s->w; u.C = s->C; u.mode = s->mode; u.wrap = s->wrap; u.clip = sn_clip_len(s->T, s->clip);

@@ -595,7 +595,8 @@ def _sibling_engine(eng, **attrs):
 def test_gsts_pieces_bf16_chain(name, engines):
     """The chain the range guard falls back to (SN_PHASE1=0: sn_ln_gemm_gate + sn_dw5m_gemm_gate / sn_grp5_gemm_gate, g1 in bf16 through HBM,
     sn_ca_mlp between the phases) for all four variants: CAB2 both directions, CAB1, a unit, a whole Encoder_shift_block, ragged sizes --
-    the same checks and tolerances as the fused default."""
+    the same checks and tolerances as the fused default.  Element by element, inside float64 intervals per kernel:
+    tests/test_gpu_chain_edges.py."""
     eng, sd = engines(name)
     chain = _sibling_engine(eng, phase1="0")
     assert not chain._fused_phase1(4)
