@@ -3,10 +3,10 @@
 Why it exists
   * upstream runs the "+" denoiser in float32 (inference/test_denoise.py:83-85: ``.half()`` is commented out), so a
     float32 module must compute in float32, not in bf16 behind a cast;
-  * it is the validation build of the engine: ``Engine32`` inherits the whole control flow of ``engine.Engine``
-    (stage 0 / 1 / 2, TFR_UNet, shift blocks, unit directions, frame trimming) and replaces only the leaf operators, so
-    agreement with the CPU oracle to fp32 round-off (tests: <= 1e-4 of the tensor scale) pins that control flow and the
-    weight bookkeeping independently of bf16 rounding noise.
+  * it is the validation build of the engine: ``Engine32`` runs the control flow of ``network.Network`` (stage 0 / 1 / 2,
+    TFR_UNet, shift blocks, unit directions, frame trimming) that ``engine.Engine`` runs too, on leaf operators of its own and
+    none of the bf16 engine's, so agreement with the CPU oracle to fp32 round-off (tests: <= 1e-4 of the tensor scale) pins that
+    control flow and the weight bookkeeping independently of bf16 rounding noise.
 
 Every activation is NHWC fp32 ``[T, H, W, C]`` with C the logical channel count; weights are the checkpoint's fp32 values
 (transposed, and for the split-precision convs also as bf16 hi / lo fragments).  Two operator chains compute the same network:
@@ -19,34 +19,27 @@ Every activation is NHWC fp32 ``[T, H, W, C]`` with C the logical channel count;
 """
 from __future__ import annotations
 
-import os
-
 import ctypes as C
+import os
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
 from . import lib as L
 from . import prep
-from .engine import Act, Engine, Plan, _dtype_code, host_f32_copy
-from .spec import Variant, shift_table
+from .network import Act, Network, _dtype_code
+from .plan import PlanBase
+from .spec import Variant
 
 
-class Plan32(Plan):
+class Plan32(PlanBase):
     """fp32 weights on the device in natural (checkpoint) order; convs are looked up by the same names as in ``Plan``."""
 
     def __init__(self, V: Variant, sd: Dict[str, torch.Tensor], device: torch.device) -> None:
-        self.V = V
-        self.device = device
-        self.sd = host_f32_copy(sd)
+        super().__init__(V, sd, device)
         self.dsd = {k: v.to(device) for k, v in self.sd.items()}
-        self.convs: Dict[str, Dict[str, object]] = {}
-        self.cas: Dict[str, Dict[str, object]] = {}
-        self.units: Dict[str, Dict[str, object]] = {}
         self._wt: Dict[str, torch.Tensor] = {}
         self._ws: Dict[str, torch.Tensor] = {}
-        self.offs = prep.shift_offsets_i8(shift_table(V.c1)).to(device)
-        self._build()
 
     def add_conv(self, name: str, key: str, cins: Sequence[int], shuffle: bool = False) -> None:      # shuffle: the bf16 plan's row order (unused here)
         self.convs[name] = {"key": key, "cins": list(cins)}
@@ -77,7 +70,6 @@ class Plan32(Plan):
             self._wt[key] = self.dsd[key].permute(2, 3, 1, 0).contiguous()
         return self._wt[key]
 
-
     def rep_merged(self, rp: str, identity: bool) -> str:
         """RepConv's parallel branches as ONE 5x5 kernel: conv_1 (5x5) + conv_2 (3x3, zero-padded) [+ the identity at the centre tap]
         (gshift_deblur1.py:143-157 computes the three terms separately and adds the results; merging the WEIGHTS in fp32 changes each output by a
@@ -102,17 +94,9 @@ class Plan32(Plan):
         return self._ws[key]
 
 
-class Engine32(Engine):
-    def __init__(self, plan: Plan32) -> None:
-        super().__init__(plan, torch.float32)
-        self.graph_auto = False            # hipGraph replay stays opt-in (SN_GRAPH=1) for the fp32 engine: measured on the bf16 engine only
-        self.schedule = "unit"             # the frame wavefront (Engine.shift_chain) is built on the bf16 engine's frame-range launches
-        self.range_guard = False           # no half-precision intermediates: nothing to guard (and no sn_se_fold / sn_ca_mlp flag operand is passed)
-
+class Engine32(Network):
     act_dtype = torch.float32
-    fused_cab_tail = False
-    k4_fuse = "0"                      # sn_cab2_phase2_cab1_phase1 is a bf16 kernel: the fp32 unit keeps its own launches
-    skip_up_lowres = False             # SkipUpSample stays "bilinear x2 in the 1x1's loader" here (sn_upsample2_add is a bf16 pass)
+    k4_fuse = "0"                      # a constant, not a switch: the fp32 unit has one launch sequence (tests/test_host_k4_fuse.py reads it)
     # Dense k = 1 / 3 and grouped-by-8 k = 5 convs with their operands split into bf16 hi + lo parts (three bf16 MFMAs per k-step instead of
     # eight fp32 ones; ~2^-16 per product, fp32 accumulation).  False: exact fp32 products everywhere (v_mfma_f32_16x16x4_f32), about half as
     # fast -- SN_FP32_EXACT=1, `--fp32_exact` on the CLIs and bench.py.  Both are within 1e-4 of the reference (tests/test_gpu_fp32.py runs both).
@@ -125,7 +109,7 @@ class Engine32(Engine):
         """Non-conv launches carry their own minimal HBM bytes for bench.py's per-kernel table (convs: the ("conv32", ...) record of _conv32)."""
         if fn not in self._CONV_FNS:
             self._meta = ("ew32", float(alg_bytes))
-        super()._call(fn, label, *args)
+        Network._call(self, fn, label, *args)
 
     def _conv32(self, wkey: str, bkey: Optional[str], ins: Sequence[torch.Tensor], cins: Sequence[int], *, k: int, stride: int = 1,
                 pad: Optional[int] = None, groups: int = 1, prelu: Optional[float] = None, res: Optional[torch.Tensor] = None,
@@ -224,8 +208,10 @@ class Engine32(Engine):
 
     def cab(self, pre: str, x: Act, extra: Optional[Act] = None) -> Act:
         T, h, w, c = x.dims
-        if not self.cab_closed_form or h < 2 or w < 2 or x.t.stride(2) != c:
-            return super().cab(pre, x, extra)
+        if not self.cab_closed_form or h < 2 or w < 2 or x.t.stride(2) != c:      # one kernel per reference module
+            r = self.conv(pre + "body.0", [x], prelu=self.P.scalar(pre + "body.1.weight"))
+            r, pool, npix = self.conv(pre + "body.2", [r], pool=True)
+            return self.scale_residual(r, x, self.ca_mlp(pre + "CA", pool, npix), extra)
         q = self.P.cas[pre + "CA"]
         cpad = max(16, prep.ceil8(c))
         if self.fuse_ops and self.split_bf16 and c % 4 == 0:      # the sums of mid come out of conv1's epilogue (no pass of sn32_chan_sum over mid)
@@ -290,10 +276,6 @@ class Engine32(Engine):
             s = self._unit_src(x, mode, wrap=wrap, halo=halo, t0=t0, nt=nt)
             self._call("sn32_gsts_gather", "sn32_temporal_roll", C.byref(s), None, y.data_ptr(), None, self._stream())
         return Act(y, c)
-
-    def _ca(self, name: str, g: torch.Tensor) -> torch.Tensor:
-        T, h, w, _ = g.shape
-        return self.ca_mlp(name, self._chan_sum(g), h * w)
 
     def naf(self, pre: str, x: Act, mode: int) -> Act:
         self._unit = tuple(x.dims) + (mode,)

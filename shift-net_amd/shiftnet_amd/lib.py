@@ -72,6 +72,18 @@ class ConvDesc(C.Structure):
 
 SN_CONV_TILE_KERNEL = 1
 
+
+def conv_flags(wgs: int = 0, stream_all: bool = False, res_regs: bool = False, depth: int = 0, dbg: int = 0, s2_small: bool = False) -> int:
+    """The measurement fields of sn_conv_desc.flags, above bit 0 (SN_CONV_TILE_KERNEL).  Bits 4-7 wgs: persistent workgroups per CU of the streaming
+    kernel (0: the library's choice); 8 stream_all: the streaming kernel also where the library prefers the tile kernel; 9 res_regs: its residual
+    operand through registers, not LDS; 10-11 depth: 1 / 2 = three / four tiles of prefetch (16 channels); 12-14 dbg (wrong results): 1 no DMA,
+    2 no B reads / MFMAs, 4 no stores; 15 s2_small: stride-2 convs on 4 x 16 tiles whatever their width.  A value that does not fit its field would
+    overwrite the neighbouring ones: ValueError."""
+    if not (0 <= wgs < 16 and 0 <= depth < 4 and 0 <= dbg < 8):
+        raise ValueError(f"sn_conv_desc.flags: wgs={wgs} (0..15), depth={depth} (0..3) or dbg={dbg} (0..7) does not fit its field")
+    return (wgs << 4) | (bool(stream_all) << 8) | (bool(res_regs) << 9) | (depth << 10) | (dbg << 12) | (bool(s2_small) << 15)
+
+
 # sn_conv2d_route: SN_CONV_ROUTE(kernel, mt, a, d, mode, rl) of include/shiftnet_hip.h
 SN_CONV_K_GENERIC, SN_CONV_K_FAST, SN_CONV_K_STATS, SN_CONV_K_STREAM = 1, 2, 3, 4
 CONV_KERNEL_NAMES = {SN_CONV_K_GENERIC: "conv_mfma", SN_CONV_K_FAST: "conv3_fast", SN_CONV_K_STATS: "conv3_fast_stats", SN_CONV_K_STREAM: "conv3p"}
