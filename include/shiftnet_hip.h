@@ -754,6 +754,24 @@ int sn_yuv_diff_stats(const uint8_t* a, const uint8_t* b, const sn_yuv_fmt* fmt,
 int sn_yuv_diff_stats_mv(const uint8_t* a, const uint8_t* b, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */,
                          const int8_t* mv, int64_t* dst /* [T - 1][SN_DIFF_STATS_MV] */, int T, int H, int W, void* stream);
 
+/* ---- the blend of a tiled window (csrc/sn_tile.hip; a new symbol, SN_ABI_VERSION stays 20) --------------------------------------------------------
+ * The video restorer can run the network on overlapping tiles of a window's frames instead of on whole frames (VideoRestorer(tile=...)); each tile's
+ * float32 result is added into one float32 canvas with feather weights that are separable: a tile's weight at (y, x) is wy[y] * wx[x].
+ *   tile:[T][C][th][tw] f32, canvas:[T][C][Hc][Wc] f32, wy:[th] f32, wx:[tw] f32, all contiguous device memory; (y0, x0) is the tile's first sample
+ *   in a plane of the canvas.  For every t < T, c < C, y < th, x < tw:
+ *     w  = wy[y] * wx[x]                                        (one float32 product, rounded)
+ *     canvas[t][c][y0 + y][x0 + x] = canvas[t][c][y0 + y][x0 + x] + w * tile[t][c][y][x]      (one product, rounded; one sum, rounded)
+ * Three float32 operations, each rounded to nearest even on its own: no FMA, and the same bits for every launch geometry and for the 16-byte and the
+ * element-wise path of the kernel (it moves 4 consecutive samples as one float4 where the addresses of both tensors allow, which it tests itself:
+ * x0, tw and Wc are arbitrary).  The canvas is ADDED to, never overwritten: the caller zeroes it before a window's first tile.  Nothing outside the
+ * th x tw rectangle of each plane is read or written.  Launches on one stream are ordered, so overlapping tiles accumulated one after the other
+ * never race; there are no atomics.  The weights are not looked at: any float32 contents are legal.
+ * (tests/tile_ref.py restates it in numpy; the kernel equals it bit for bit.)
+ * SN_EINVAL before anything is launched: a null pointer; a pointer that is not 4-byte aligned; T, C, th, tw, Hc or Wc < 1; y0 < 0, x0 < 0,
+ * y0 + th > Hc or x0 + tw > Wc; T * C > 65535 (the grid's z). */
+int sn_tile_accumulate(const float* tile, float* canvas, const float* wy, const float* wx, int T, int C, int th, int tw, int Hc, int Wc,
+                       int y0, int x0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,8 @@ the statistics of the same payloads' luma (csrc/sn_yuv_stats.hip), each for one 
                (shiftnet_amd/report.py);
 ``diff_stats_mv_yuv``: int64 sums of that difference in consecutive payloads along the vectors of ``block_motion_yuv``, for the report's motion-compensated
                temporal correlation;
+``tile_accumulate``: one tile's float32 result added into the window's float32 canvas with its feather weights (csrc/sn_tile.hip), for the tiled
+               restorer (``VideoRestorer(tile=...)``);
 ``rect=(x0, y0, w, h)``, where a function takes it (all but ``thumb_yuv`` and ``rowcol_sums_yuv``), restricts it to that picture of the stream, with
                the result of the cropped stream;
 ``egress_u8``  == the per-frame ``clamp(0,1) * 255`` -> skimage PSNR(data_range=255) against the uint8 ground truth
@@ -400,3 +402,27 @@ def diff_stats_mv_yuv(ref: torch.Tensor, out: torch.Tensor, fmt: "L.YuvFmt", H: 
         L.check(L.load().sn_yuv_diff_stats_mv(ref.data_ptr(), out.data_ptr(), fmt, r, mv.data_ptr(), y.data_ptr(), T, H, W,
                                               torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_diff_stats_mv")
     return y
+
+
+def tile_accumulate(tile: torch.Tensor, canvas: torch.Tensor, wy: torch.Tensor, wx: torch.Tensor, y0: int, x0: int) -> torch.Tensor:
+    """tile: [T, C, th, tw] float32 on a HIP device, the result of one tile's forward; canvas: [T, C, Hc, Wc] float32 on the same device; wy: [th] and
+    wx: [tw] float32, the tile's feather weights per axis (windows.plan_tiles) -> ``canvas``, whose th x tw rectangle at (y0, x0) of every plane has
+    become ``canvas + (wy[y] * wx[x]) * tile``, every product and sum rounded to float32 on its own (include/shiftnet_hip.h: sn_tile_accumulate).
+    Nothing else of the canvas is touched; it is added to, so the caller zeroes it before a window's first tile.  All four tensors contiguous."""
+    for name, a, nd in (("tile", tile, 4), ("canvas", canvas, 4), ("wy", wy, 1), ("wx", wx, 1)):
+        if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.float32 and a.dim() == nd and a.is_contiguous() and a.device == tile.device):
+            raise ValueError(f"tile_accumulate: {name} must be a contiguous float32 tensor of {nd} dimensions on the tile's HIP device")
+    T, C, th, tw = tile.shape
+    Hc, Wc = canvas.shape[2], canvas.shape[3]
+    y0, x0 = int(y0), int(x0)
+    if tuple(canvas.shape[:2]) != (T, C) or tuple(wy.shape) != (th,) or tuple(wx.shape) != (tw,):
+        raise ValueError(f"tile_accumulate: tile {tuple(tile.shape)} goes with canvas [{T}, {C}, Hc, Wc], wy [{th}] and wx [{tw}], got "
+                         f"{tuple(canvas.shape)}, {tuple(wy.shape)}, {tuple(wx.shape)}")
+    if min(T, C, th, tw) < 1 or T * C > 65535:
+        raise ValueError(f"tile_accumulate: need T, C, th, tw >= 1 and T * C <= 65535, got tile {tuple(tile.shape)}")
+    if y0 < 0 or x0 < 0 or y0 + th > Hc or x0 + tw > Wc:
+        raise ValueError(f"tile_accumulate: the {th} x {tw} tile at (y0, x0) = ({y0}, {x0}) does not lie inside the {Hc} x {Wc} canvas")
+    with torch.cuda.device(tile.device):
+        L.check(L.load().sn_tile_accumulate(tile.data_ptr(), canvas.data_ptr(), wy.data_ptr(), wx.data_ptr(), T, C, th, tw, Hc, Wc, y0, x0,
+                                            torch.cuda.current_stream(tile.device).cuda_stream), "sn_tile_accumulate")
+    return canvas

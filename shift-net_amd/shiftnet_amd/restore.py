@@ -47,6 +47,13 @@ sums of the two sets of payloads the window holds on the device anyway once the 
 (shiftnet_amd/report.py).  It changes no byte written.  What the numbers mean on real footage nobody has validated.  ``report_motion="blocks"`` adds the
 temporal correlation of that difference along the motion of the written picture (``sn_yuv_block_motion`` on the frames written, then
 ``sn_yuv_diff_stats_mv``): removed detail that moves with a pan reads as uncorrelated at the same place, and as correlated along its vector.
+
+Tiles (``tile``, ``tile_overlap``; off by default): the network's activations grow with the pixels of the frames it is given, and a large frame does
+not fit the device at any useful window length.  With a tile size the forward -- and only the forward -- runs on overlapping rectangles of the
+window's frames, one after the other, and their float32 results are added into one float32 canvas with feather weights (``sn_tile_accumulate``,
+csrc/sn_tile.hip; the plan is windows.plan_tiles); everything before and after still works on the whole picture.  **A tiled result is not the
+full-frame result**: every channel-attention layer pools over the map it is given, so it sees the tile, and the receptive field is cut at tile edges.
+The feather turns a mismatch into a gradient instead of an edge; it does not remove it.
 """
 from __future__ import annotations
 
@@ -57,10 +64,10 @@ from typing import Iterable, Iterator, List, Sequence, Tuple
 
 import numpy as np
 
-from .restore_cli import amount_arg, main, make_parser, picture_arg, sigma_arg  # noqa: F401 -- the command line (restore_cli.py), reached through this module
-from .windows import (DITHERS, FUTURE, PAST, PerWindow, _Frames, _SceneFrames, _Thread, amount_form, noise_model_form, pad_multiple,  # noqa: F401
+from .restore_cli import amount_arg, main, make_parser, picture_arg, sigma_arg, tile_arg  # noqa: F401 -- the command line (restore_cli.py), reached through this module
+from .windows import (DEFAULT_TILE_OVERLAP, DITHERS, FUTURE, PAST, PerWindow, _Frames, _SceneFrames, _Thread, amount_form, noise_model_form, pad_multiple,  # noqa: F401
                       padded_size, picture_form, plan_output, plan_scene_windows, plan_windows, reflect_index, report_form, report_motion_form, scene_cuts_form,
-                      sigma_estimator_form, sigma_form, sigma_motion_form, window_indices)
+                      sigma_estimator_form, sigma_form, sigma_motion_form, tile_form, plan_tiles, window_indices)
 
 VARIANTS = {"deblur": "gshift_deblur1", "deblur_small": "gshift_deblur2", "denoise": "gshift_denoise1", "denoise_small": "gshift_denoise2"}
 
@@ -133,7 +140,9 @@ class _Run:
         self.window_pair_sigma: List = []
         self.window_pair_motion: List = []                        # sigma_motion: per window, per pair, noise.motion_summary's triple
         self.launches = {"noise": 0, "nlf": 0, "nlf_map": 0, "picture": 0, "thumb": 0, "noise_pairs": 0, "nlf_pairs": 0, "report": 0, "motion": 0,
-                         "report_motion": 0, "report_mv": 0}      # report_motion: the block matcher on the written frames, the sums along its vectors
+                         "report_motion": 0, "report_mv": 0,      # report_motion: the block matcher on the written frames, the sums along its vectors
+                         "tile": 0}                               # tile: the sn_tile_accumulate launches
+        self.window_tiles: List = []                              # tile: per window, the (y0, x0, th, tw) of its tiles in the order they ran
         self.frame_sums: List = []                                # report: the 16 sums of every frame handed out, the window it came from, that window's sigma
         self.frame_window: List[int] = []
         self.frame_sigma: List = []
@@ -310,13 +319,36 @@ class VideoRestorer:
     ``frame_report``, ``frame_sums`` and every byte written stay what they are without it.  It is independent of ``sigma_motion``, whose vectors are
     those of the input frames as fed.  **Limits**: integer-pel vectors within +-7 samples per 16 x 16 block; half of the samples; blocks at the border
     whose true vector leaves the picture read low (the synthetic pans of the tests read 0.6 to 0.9 where everything removed was detail); pairs across windows have no value;
-    zoom, rotation and occlusion still read as uncorrelated; no threshold and no verdict; unvalidated on real footage."""
+    zoom, rotation and occlusion still read as uncorrelated; no threshold and no verdict; unvalidated on real footage.
+    tile: None -- the network is given whole frames, today's launches, bytes and stats keys; ``(th, tw)`` or an int ``n`` (``(n, n)``) -- the forward of
+    every window runs on overlapping th x tw rectangles of the window's padded frames instead, one after the other in row-major order, each on the
+    contiguous crop of the input tensors (and of the noise plane under ``noise_model``; a flat sigma is broadcast to the tile's shape), and
+    ``sn_tile_accumulate`` adds each float32 result into one float32 canvas of the whole picture with feather weights; the egress, the mix and the
+    report read the canvas as they read the network's result without tiles.  Ingest, the statistics, the noise plane and the egress still see the whole
+    picture -- the frame, or the window's rectangle under ``picture`` -- so chroma is upsampled from its true neighbours and ``sigma="auto"`` still
+    estimates on the whole frame.  Both sides are multiples of the network's padding multiple (4, or 8 for the "+" variants) and at least twice it.
+    ``tile_overlap`` (an int, ``0 <= tile_overlap <= min(th, tw) // 2``): consecutive tiles overlap by at least that many samples.  The plan is
+    windows.plan_tiles: per axis of length L, tiles of side S at ``min(k (S - overlap), L - S)`` -- all of one size, the last at the far edge -- and a
+    side that is not shorter than the picture gives one tile; where two tiles overlap their results cross-fade linearly, a sample that one tile covers has
+    weight exactly 1, and there is no ramp at the picture's own edges.  A window whose plan is one tile takes the path, the launches and the bytes of
+    ``tile=None``.  With ``picture`` and ``out_format`` together, the input side of ``amount``'s blend and of the report is, inside the rectangle of a
+    window that ran tiled, the rectangle converted as the cropped stream's frames are (two more launches, ``sn_ingest_yuv_rect`` and
+    ``sn_egress_yuv_rect``), so that a tiled window equals the tiled cropped stream inside its rectangle byte for byte and sum for sum; without tiles it
+    stays the whole frame converted, as ``amount`` describes it, which differs within 2 samples of the rectangle's edges where 4:2:0 chroma is
+    upsampled from the bars.  The tiles of a window share one range-guard check and are run once more if it tripped.  **A tiled result is not the full-frame
+    result**: every CALayer pools over the map it is given, so it sees the tile, and the receptive field is cut at tile edges; the feather turns a
+    mismatch into a gradient instead of an edge, it does not remove it.  **The default overlap of 32 is taken from upstream's quadrants, which crop 17 to
+    32 samples per side; nobody has tuned it, and no trained checkpoint ships, so nobody has looked at a seam on real footage.**  Tiles of one window run
+    one at a time (not as one ``forward_clips`` batch), have one size, and do not cut the window in time.  ``stats`` then also has ``tile`` (th, tw),
+    ``tile_overlap``, ``window_tiles`` (per window the list of (y0, x0, th, tw) in the order run) and ``tile_launches`` (the ``sn_tile_accumulate``
+    launches)."""
 
     def __init__(self, net, one_len: int, sigma=None, pipeline: bool = True, scene_cuts=None,
                  cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0),
                  picture=None, bar_level: float = 1.0, out_format=None, dither=None, dither_seed: int = 0, noise_model=None,
                  amount=None, view=None, removed_gain: float = 1.0, sigma_estimator: str = "spatial", report: bool = False,
-                 report_edge: float = 16.0, sigma_motion=None, report_motion=None) -> None:
+                 report_edge: float = 16.0, sigma_motion=None, report_motion=None, tile=None,
+                 tile_overlap: int = DEFAULT_TILE_OVERLAP) -> None:
         import torch
         from .lib import YuvFmt
         from .noise import check_clamp
@@ -333,6 +365,8 @@ class VideoRestorer:
         self.cuts_mode, self.scene_cuts = scene_cuts_form(scene_cuts)          # "off", "auto", "list"
         self.cut_threshold, self.cut_ratio = float(cut_threshold), float(cut_ratio)
         self.V = net.V
+        self.tile = tile_form(tile, tile_overlap, self.V.topo)    # None (the code path without any of it) or (th, tw, overlap)
+        self._tile_plans = {}                                     # (hp, wp) -> (the plan, its weight tables on the device)
         if self.V.denoise and sigma is None:
             raise ValueError("sigma is required by the denoise variants (the noise level of the footage, in 8-bit code values)")
         self.sigma_clamp = check_clamp(sigma_clamp)
@@ -427,6 +461,9 @@ class VideoRestorer:
                 s.report_vec = torch.empty(2 * blocks, dtype=torch.int8, device=dev)
                 s.report_sad = torch.empty(blocks, dtype=torch.uint32, device=dev)
         self.report_code_edge = int(round(self.report_edge * (1 << (ofmt.bits - 8))))      # in codes of the format written
+        # tiles: the float32 canvas the tiles' results are added into, flat and sized for the full frame as the slots' tensors are.  One for the restorer
+        # (main stream only): the egress of a window has consumed it before the next window's forward runs
+        self.canvas = torch.empty(tout * 3 * self.hp * self.wp, dtype=torch.float32, device=dev) if self.tile is not None else None
 
     def _size(self, rect) -> Tuple[int, int, int, int]:
         """(h, w, padded h, padded w) of what a window with picture ``rect`` feeds the network."""
@@ -558,6 +595,48 @@ class VideoRestorer:
         run.window_nlf.append(curve)
         return curve
 
+    def _tile_plan(self, hp: int, wp: int):
+        """(windows.plan_tiles for a padded picture of hp x wp, its weight tables [n_y][th] and [n_x][tw] on the device), made once per size."""
+        key = (int(hp), int(wp))
+        if key not in self._tile_plans:
+            th, tw, overlap = self.tile
+            plan = plan_tiles(key[0], key[1], th, tw, overlap)
+            to_dev = lambda a: self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)      # noqa: E731
+            self._tile_plans[key] = (plan, to_dev(plan.wy), to_dev(plan.wx))
+        return self._tile_plans[key]
+
+    def _forward_tiles(self, x, x32, nm, sigma, t: int):
+        """The forward of one window tile by tile (current stream): x [1, t, 3, hp, wp], x32 its float32 twin or None, nm the per-pixel noise plane
+        [1, t, 1, hp, wp] or None (then ``sigma`` is broadcast where the network takes a noise level) -> the float32 canvas [t - 4, 3, hp, wp]."""
+        from .io_edges import tile_accumulate
+        torch = self.torch
+        hp, wp = x.shape[3], x.shape[4]
+        plan, wy, wx = self._tile_plan(hp, wp)
+        n = t - PAST - FUTURE
+        canvas = self.canvas[:n * 3 * hp * wp].view(n, 3, hp, wp)
+        th, tw = plan.th, plan.tw
+        flat = None
+        if nm is None and self.V.denoise:
+            flat = torch.full((1, 1, 1, 1, 1), sigma / 255.0, dtype=self.dtype, device=self.dev).expand(1, t, 1, th, tw)
+        for _ in range(2):      # one range-guard check for the window's tiles (no device sync between them); a tripped guard moved the module to the
+            canvas.zero_()      # two-kernel chain: run them once more, into a canvas that starts at zero again
+            with self.net.guard_scope() as gs:
+                for i, y0 in enumerate(plan.ys):
+                    for j, x0 in enumerate(plan.xs):
+                        crop = (slice(None), slice(None), slice(None), slice(y0, y0 + th), slice(x0, x0 + tw))
+                        kw = {"shortcut": x32[crop].contiguous()} if x32 is not None else {}
+                        if nm is not None:
+                            o = self.net.forward_fp32_out(x[crop].contiguous(), nm[crop].contiguous(), **kw)
+                        elif flat is not None:
+                            o = self.net.forward_fp32_out(x[crop].contiguous(), flat, **kw)
+                        else:
+                            o = self.net.forward_fp32_out(x[crop].contiguous(), **kw)
+                        tile_accumulate(o, canvas, wy[i], wx[j], y0, x0)
+                        self.run.launches["tile"] += 1
+            if not gs.tripped:
+                break
+        return canvas
+
     def _run(self, slot: _Slot, t: int, main) -> int:
         """Forward + egress on the main stream, copy back on the output stream."""
         from .io_edges import block_motion_yuv, diff_stats_mv_yuv, diff_stats_yuv, egress_yuv, ingest_yuv, noise_map_level
@@ -577,11 +656,19 @@ class VideoRestorer:
             kw = {}
             if x32 is not None:
                 kw["shortcut"] = x32
+            plan = self._tile_plan(x.shape[3], x.shape[4])[0] if self.tile is not None else None
+            if plan is not None:
+                run.window_tiles.append(list(plan.tiles))
+            nm = None
             if curve is not None:
                 # the plane from the payloads the ingest read (ev_ready lies behind their upload; they stay until ev_done); the knots are a kernel argument
                 nm = noise_map_level(slot.dev_in[:t], self.fmt, self.h, self.w, x.shape[3], x.shape[4], [c / 255.0 for c in curve], self.dtype,
                                      self.noise_lo, self.noise_hi, rect=rect)
                 run.launches["nlf_map"] += 1
+            tiled = plan is not None and not plan.single
+            if tiled:
+                out = self._forward_tiles(x, x32, nm, sigma, t)
+            elif curve is not None:
                 out = self.net.forward_fp32_out(x, nm, **kw)
             elif self.V.denoise:
                 nm = torch.full((1, 1, 1, 1, 1), sigma / 255.0, dtype=self.dtype, device=self.dev).expand(1, t, 1, x.shape[3], x.shape[4])
@@ -598,7 +685,14 @@ class VideoRestorer:
                 # dev_out without a mix or a report; with one into the slot's reference buffer, because they read one while the other is (has been) written
                 full = self.conv32[:n * 3 * self.h * self.w].view(1, n, 3, self.h, self.w)
                 ingest_yuv(own, self.fmt, self.h, self.w, self.h, self.w, torch.float32, out=full)
-                own = egress_yuv(full[0], self.ofmt, self.h, self.w, dst=(slot.dev_ref if keep else slot.dev_out)[:n])
+                read, own = own, egress_yuv(full[0], self.ofmt, self.h, self.w, dst=(slot.dev_ref if keep else slot.dev_out)[:n])
+                if tiled and keep and rect is not None:
+                    # a tiled window's mix and report take the rectangle as the whole picture, as everything else of it does: inside the rectangle their
+                    # input side is the rectangle converted as the cropped stream's frames are -- chroma from the rectangle's own clamped neighbours, not from
+                    # the bars'.  The float32 buffer is free again: the egress that read it lies ahead on this stream
+                    part = self.conv32[:n * 3 * rect[3] * rect[2]].view(1, n, 3, rect[3], rect[2])
+                    ingest_yuv(read, self.fmt, self.h, self.w, rect[3], rect[2], torch.float32, out=part, rect=rect)
+                    egress_yuv(part[0], self.ofmt, self.h, self.w, dst=own, rect=rect)
                 outside = outside and keep
             if outside:
                 # everything outside the picture leaves as it came in (as converted, in another format): the egress below writes the inside only
@@ -657,6 +751,10 @@ class VideoRestorer:
             stats["nlf_launches"], stats["nlf_map_launches"] = run.launches["nlf"], run.launches["nlf_map"]
         stats["window_picture"] = list(run.window_picture)
         stats["picture_launches"] = run.launches["picture"]
+        if self.tile is not None:
+            stats["tile"], stats["tile_overlap"] = self.tile[:2], self.tile[2]
+            stats["window_tiles"] = [list(w) for w in run.window_tiles]
+            stats["tile_launches"] = run.launches["tile"]
         if self.picture_mode == "auto":
             stats["picture_wait_ms"] = list(run.picture_wait_ms)
         if self.V.denoise:

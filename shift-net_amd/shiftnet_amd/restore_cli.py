@@ -52,6 +52,15 @@ def report_edge_arg(word: str) -> float:
     return v
 
 
+def tile_arg(word: str):
+    """--tile: N -> the int (N x N tiles); HxW -> (H, W)."""
+    parts = word.lower().split("x")
+    if len(parts) not in (1, 2) or not all(p.isdigit() for p in parts):
+        raise argparse.ArgumentTypeError(f"N or HxW in samples, got {word!r}")
+    vals = tuple(int(p) for p in parts)
+    return vals[0] if len(vals) == 1 else vals
+
+
 def _modes():
     from .y4m import MODES
     return MODES
@@ -128,6 +137,16 @@ def make_parser() -> argparse.ArgumentParser:
                          "that moves with a pan reads rho_t about 0 as noise does; also how well the vectors fit (mv_match_rms), the share that moved and "
                          "the share counted; blocks at the border of a pan read low, zoom and rotation still read as uncorrelated; unvalidated on real "
                          "footage; default none: the report as it is without")
+    ap.add_argument("--tile", type=tile_arg, default=None, metavar="{N,HxW}",
+                    help="for frames whose activations do not fit the device: run the network on overlapping tiles of H x W samples (N: N x N) of every "
+                         "window, one after the other, and blend their results with feather weights on the device; both sides multiples of 4 (8 for "
+                         "the deblur / denoise variants without _small) and at least twice that; everything but the forward still sees the whole "
+                         "picture.  A TILED RESULT IS NOT THE FULL-FRAME RESULT: every channel-attention layer pools over the tile it is given and the "
+                         "receptive field is cut at tile edges; the feather turns a mismatch into a gradient instead of an edge, it does not remove it; "
+                         "nobody has looked at a seam on real footage; default: whole frames")
+    ap.add_argument("--tile_overlap", type=int, default=None, metavar="V",
+                    help="--tile only: consecutive tiles overlap by at least V samples, 0 <= V <= half the tile's shorter side; default 32, taken from "
+                         "upstream's quadrants (which crop 17 to 32 samples per side) and never tuned")
     ap.add_argument("--cuts_out", default=None, metavar="FILE", help="write the scene starts that were used, in the format --scene_cuts FILE reads")
     ap.add_argument("input", metavar="IN", help="Y4M file, or - for stdin")
     ap.add_argument("output", metavar="OUT", help="Y4M file, or - for stdout")
@@ -170,7 +189,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     from .io_edges import yuv_fmt
     from .restore import VideoRestorer, load_net
     from . import report as rep
-    from .windows import amount_form, report_form, report_motion_form
+    from .spec import VARIANTS as SPECS
+    from .restore import VARIANTS
+    from .windows import DEFAULT_TILE_OVERLAP, amount_form, report_form, report_motion_form, tile_form
     from .y4m import Y4MReader, Y4MWriter, output_header
     ap = make_parser()
     a = ap.parse_args(argv)
@@ -189,6 +210,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         report_motion = report_motion_form(None if a.report_motion == "none" else a.report_motion, a.report is not None)
     except ValueError:
         ap.error(f"--report_motion {a.report_motion} needs --report")
+    if a.tile is None and a.tile_overlap is not None:             # as above: before any file is opened
+        ap.error("--tile_overlap needs --tile")
+    tile_overlap = DEFAULT_TILE_OVERLAP if a.tile_overlap is None else a.tile_overlap
+    try:
+        tile_form(a.tile, tile_overlap, SPECS[VARIANTS[a.variant]].topo)
+    except ValueError as e:
+        ap.error(f"--tile / --tile_overlap: {e}")
     if "denoise" in a.variant and a.sigma is None:
         ap.error("--sigma is required by the denoise variants")
     if a.sigma_estimator != "spatial" and a.sigma != "auto":      # before the file of a --sigma FILE is opened
@@ -243,7 +271,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                            dither=None if a.dither == "none" else a.dither, dither_seed=a.dither_seed, noise_model=noise_model,
                            amount=a.amount, view=view, removed_gain=a.removed_gain, sigma_estimator=a.sigma_estimator,
                            report=a.report is not None, report_edge=a.report_edge, sigma_motion=None if a.sigma_motion == "none" else a.sigma_motion,
-                           report_motion=report_motion)
+                           report_motion=report_motion, tile=a.tile, tile_overlap=tile_overlap)
+        if vr.tile is not None:
+            log("tile: %d x %d, overlap %d (a tiled result is not the full-frame result: channel attention sees the tile)" % vr.tile)
         if a.out_format is not None or a.dither != "none":
             log(f"output: C{a.out_format or hd.chroma}{'' if a.out_format else ' (as the input)'}, dither {a.dither}"
                 f"{' seed %d' % a.dither_seed if a.dither != 'none' else ''}")
@@ -268,6 +298,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         log(f"done: {n} frames in {dt:.2f} s, {n / dt if dt > 0 else 0.0:.2f} frames/s end to end, "
             f"{n / fwd if fwd > 0 else 0.0:.2f} frames/s forward only, {len(used) + 1} scene{'s' if used else ''}"
             f"{'' if cuts is None else (' (cuts found)' if cuts == 'auto' else ' (cuts listed)')}")
+        if vr.tile is not None:
+            wt = vr.stats["window_tiles"]
+            log(f"tiles: {min(len(w) for w in wt) if wt else 0} to {max(len(w) for w in wt) if wt else 0} per window, "
+                f"{vr.stats['tile_launches']} blended over {len(wt)} window{'' if len(wt) == 1 else 's'}")
         wp = vr.stats.get("window_picture", [])
         _write_out(a.picture_out, pic.write_pictures, wp, picture_how)
         if picture is not None:

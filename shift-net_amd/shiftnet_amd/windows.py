@@ -85,6 +85,92 @@ def padded_size(h: int, w: int, topo: str) -> Tuple[int, int]:
     return (h + m - 1) // m * m, (w + m - 1) // m * m
 
 
+# ---- tiles: a window's frames cut into overlapping rectangles of one size, and the weights that blend their results ------------------
+DEFAULT_TILE_OVERLAP = 32      # upstream's four quadrants crop 17 to 32 samples per side (cli.quadrant_forward); nobody has tuned it
+
+
+def tile_axis(length: int, side: int, overlap: int) -> Tuple[List[int], np.ndarray]:
+    """One axis of plan_tiles: (the origins of the tiles, their weights as float64 [n][min(side, length)]).
+
+    ``side >= length``: one tile [0, length) of weight 1.  Otherwise ``step = side - overlap``, ``n = ceil((length - side) / step) + 1`` tiles at
+    ``o_k = min(k * step, length - side)``: all of one size, the last at the far edge, consecutive ones overlapping by at least ``overlap``.
+    The weight of tile k at position p is ``t_k(p) / sum_j t_j(p)`` over the tiles j that cover p, with
+    ``t_k(p) = min(p - o_k + 1 if k > 0, o_k + side - p if k < n - 1)``: a ramp towards every edge the tile shares with a neighbour and none at the
+    picture's own edges; a lone tile has weight 1.  Where one tile covers p the weight is exactly 1.0, where two tiles face each other with their
+    ramps the cross-fade is linear, and where the shifted last tile overlaps its neighbour by more than half a side the weights are still positive
+    and still sum to 1."""
+    if length < 1 or side < 1 or not (0 <= overlap < side):
+        raise ValueError(f"tile_axis: need length >= 1, side >= 1 and 0 <= overlap < side, got {length}, {side}, {overlap}")
+    if side >= length:
+        return [0], np.ones((1, length), dtype=np.float64)
+    step = side - overlap
+    n = -(-(length - side) // step) + 1
+    origins = [min(k * step, length - side) for k in range(n)]
+    t = np.zeros((n, length), dtype=np.float64)
+    for k, o in enumerate(origins):
+        p = np.arange(o, o + side, dtype=np.float64)
+        ramp = np.full(side, np.inf)
+        if k > 0:
+            ramp = np.minimum(ramp, p - o + 1)
+        if k < n - 1:
+            ramp = np.minimum(ramp, o + side - p)
+        t[k, o:o + side] = ramp                                   # n >= 2 here: every tile has a neighbour, so no inf stays
+    total = t.sum(axis=0)
+    return origins, np.stack([t[k, o:o + side] / total[o:o + side] for k, o in enumerate(origins)])
+
+
+class TilePlan:
+    """plan_tiles' result: the tile's size (th, tw) as run -- clipped to the picture --, the origins ``ys`` and ``xs`` per axis, the float32 weight
+    tables ``wy`` [len(ys)][th] and ``wx`` [len(xs)][tw] (computed in float64, rounded once), and ``tiles``: (y0, x0, th, tw) in row-major order,
+    the order they are run and accumulated in.  The weight of tile (i, j) at (y, x) is ``wy[i][y] * wx[j][x]``."""
+
+    def __init__(self, hp: int, wp: int, th: int, tw: int, overlap: int) -> None:
+        self.ys, wy = tile_axis(hp, th, overlap)
+        self.xs, wx = tile_axis(wp, tw, overlap)
+        self.wy, self.wx = wy.astype(np.float32), wx.astype(np.float32)
+        self.th, self.tw = self.wy.shape[1], self.wx.shape[1]
+        self.tiles = [(y0, x0, self.th, self.tw) for y0 in self.ys for x0 in self.xs]
+
+    @property
+    def single(self) -> bool:
+        """One tile that is the whole picture: nothing to blend."""
+        return len(self.tiles) == 1
+
+
+def plan_tiles(hp: int, wp: int, th: int, tw: int, overlap: int) -> TilePlan:
+    """The tiles of an hp x wp picture (the padded size the network is fed) for tiles of th x tw that overlap by at least ``overlap`` samples: per
+    axis ``tile_axis``.  Pure: the same plan for every window of one size."""
+    return TilePlan(int(hp), int(wp), int(th), int(tw), int(overlap))
+
+
+def tile_form(tile, tile_overlap=DEFAULT_TILE_OVERLAP, topo: str = "small"):
+    """-> None (no tiles: the code path without any of it) or (th, tw, overlap).  ``tile``: None, an int n (n x n) or (th, tw); both sides multiples
+    of ``pad_multiple(topo)`` and at least twice it (the network takes no map one pixel high at its coarsest level); ``tile_overlap``: an int with
+    ``0 <= overlap <= min(th, tw) // 2``, judged even where ``tile`` is None.  ValueError for anything else."""
+    def integer(v) -> bool:
+        return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if not integer(tile_overlap) or tile_overlap < 0:
+        raise ValueError(f"tile_overlap must be an integer >= 0, got {tile_overlap!r}")
+    if tile is None:
+        return None
+    m = pad_multiple(topo)
+    if integer(tile):
+        pair = (int(tile), int(tile))
+    else:
+        try:
+            pair = () if isinstance(tile, (str, bytes)) else tuple(tile)
+        except TypeError:
+            pair = ()
+        if len(pair) != 2 or not all(integer(v) for v in pair):
+            raise ValueError(f"tile must be None, an integer n (n x n) or (th, tw), got {tile!r}")
+        pair = (int(pair[0]), int(pair[1]))
+    if not all(v >= 2 * m and v % m == 0 for v in pair):
+        raise ValueError(f"tile: both sides must be multiples of {m} and at least {2 * m} for this network, got {tile!r}")
+    if tile_overlap > min(pair) // 2:
+        raise ValueError(f"tile_overlap must be at most half the tile's shorter side ({min(pair) // 2}), got {tile_overlap!r}")
+    return pair[0], pair[1], int(tile_overlap)
+
+
 # ---- per-window options: one value for the stream, or a list with one entry per window ---------------------------------------------
 class PerWindow:
     """An option of the restorer that is one value for the stream (``listed=False``) or a list with one entry per window in the order the

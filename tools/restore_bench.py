@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15, 3.16, 3.17, 3.19, 3.20, 3.21, 3.23 and 3.25 (run on the MI355X from the repository root).
+"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15, 3.16, 3.17, 3.19, 3.20, 3.21, 3.23, 3.25 and 3.29 (run on the MI355X from the repository root).
 
   kernels : time per pixel of sn_ingest_yuv / sn_egress_yuv / sn_yuv_thumb / sn_yuv_noise_hist (4:2:0 8 bit, 720p x 20 frames; the noise
             histogram on the same frames with noise of sigma 10 as well) beside sn_ingest_u8 / sn_egress_u8 on the same
@@ -37,6 +37,12 @@
             sigma_estimator="min" alone and with sigma_motion="blocks" on top, runs of the two alternating in one process, the first two windows left out.
             Since 3.25, --mode kernels of the nlf and motion parts with --parent_lib SO: the seven noise-histogram entry points of this build and, twice, of
             another build through one ctypes argument list, at 8 bit and 10 bit 4:2:0, with this build's median against the other's third quartile.
+  tiles   : the tiled restorer (3.29).  --mode forward: steady-state forward time per window and frames/s of the restorer (Shift-Net-s, one_len 16, bf16,
+            --size HxW, default 720x1280) for every --tile form given (``full``, ``N`` or ``HxW``; repeat the option) at --tile_overlap, runs of the forms
+            alternating in one process, the first window of every run left out, and beside the times ``torch.cuda.max_memory_allocated()`` of every run
+            (the allocator's cache emptied and the peak reset before it; the engine keeps the buffers of the sizes it has seen, so the peak of a form is
+            clean only in a process that runs that form alone: give one --tile).  --mode quality: max and rms of |tiled - full| of the written samples
+            (10 bit 4:4:4 out, in 8-bit code units) at --size (default 256x384) with 2 x 2 tiles for overlaps 0, 16, 32 and 64.
 Prints one JSON object per part.
 """
 import argparse
@@ -541,6 +547,97 @@ def report_forward(a):
                       "runs": a.runs, "report_summary": {k: round(v, 4) for k, v in seen[True].items()}, **res}))
 
 
+def _tile_word(word):
+    return None if word == "full" else restore.tile_arg(word)
+
+
+def _stream(H, W, n, fmt, n_src=4):
+    """n payloads of H x W on the host: the blurred synthetic clip, its n_src frames walked back and forth so that consecutive frames are neighbours."""
+    blur, _ = synth.blurred_clip(n_src, H, W, seed=2)
+    pay = egress_yuv(ingest_u8(torch.from_numpy(blur).cuda(), torch.float32)[0], fmt, H, W).cpu().numpy()
+    period = 2 * n_src - 2
+    return [pay[j if j < n_src else period - j] for j in (i % period for i in range(n))]
+
+
+def tiles_forward(a):
+    H, W = (int(v) for v in (a.size or "720x1280").split("x"))
+    one_len, nwin = 16, a.windows
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    frames = _stream(H, W, one_len * nwin, fmt)
+    net = restore.load_net(a.variant, "synthetic", "bf16")
+    kw = {"sigma": 10.0} if "denoise" in a.variant else {}
+    forms = a.tile or ["full"]
+    plans = {}
+
+    def run(word):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        vr = restore.VideoRestorer(net, one_len, pipeline=True, tile=_tile_word(word), tile_overlap=a.tile_overlap, **kw)
+        t0 = time.perf_counter()
+        for _ in vr.restore(iter(frames), fmt, H, W):
+            pass
+        total = time.perf_counter() - t0
+        torch.cuda.synchronize()
+        plans[word] = vr.stats.get("window_tiles", [None])[0]
+        return {"total_s": total, "window_forward_ms": vr.stats["window_forward_ms"][1:], "peak_bytes": torch.cuda.max_memory_allocated()}
+
+    runs = {w: [] for w in forms}
+    for _ in range(a.runs):
+        for w in forms:                                                              # alternating: every round runs every form
+            runs[w].append(run(w))
+    res = {}
+    for w, rs in runs.items():
+        fwd = [g for r in rs for g in r["window_forward_ms"]]
+        res[w] = {"window_forward_ms": summary(fwd), "window_forward_ms_per_run": [round(statistics.median(r["window_forward_ms"]), 2) for r in rs],
+                  "frames_per_s_forward": {k: round(one_len * 1e3 / v, 3) for k, v in (("median", statistics.median(fwd)), ("slowest", max(fwd)), ("fastest", min(fwd)))},
+                  "frames_per_s_end_to_end": [round(one_len * nwin / r["total_s"], 2) for r in rs],
+                  "peak_allocated_gb": [round(r["peak_bytes"] / 1e9, 3) for r in rs],
+                  "tiles": None if plans[w] is None else {"count": len(plans[w]), "first": [list(t) for t in plans[w][:2]],
+                                                           "pixels_over_picture": round(sum(t[2] * t[3] for t in plans[w]) / (H * W), 4)}}
+    print(json.dumps({"part": "tiles", "mode": "forward", "variant": a.variant, "dtype": "bf16", "one_len": one_len, "windows": nwin, "size": [H, W],
+                      "tile_overlap": a.tile_overlap, "runs": a.runs, "forms_in_this_process": forms, **res}))
+
+
+def tiles_quality(a):
+    """|tiled - full| of the written samples at a small size, 2 x 2 tiles, by overlap.  Synthetic weights: how the blend behaves, not how a trained
+    network's seams look."""
+    H, W = (int(v) for v in (a.size or "256x384").split("x"))
+    one_len = 4
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    frames = _stream(H, W, 2 * one_len, fmt)
+    net = restore.load_net(a.variant, "synthetic", "bf16")
+    kw = {"sigma": 10.0} if "denoise" in a.variant else {}
+
+    def run(tile, overlap):
+        vr = restore.VideoRestorer(net, one_len, out_format="444p10", tile=tile, tile_overlap=overlap, **kw)
+        out = np.stack(list(vr.restore(iter(frames), fmt, H, W))).view("<u2").astype(np.float64) / 4.0      # 10-bit codes in 8-bit code units
+        return out.reshape(len(frames), 3, H, W), vr.stats.get("window_tiles", [None])[0]
+
+    full, _ = run(None, 32)
+    res = {}
+    for v in (0, 16, 32, 64):
+        up = lambda n: -(-n // 4) * 4      # noqa: E731
+        tile = (up((H + v + 1) // 2), up((W + v + 1) // 2))                          # the smallest 2 x 2 tiles that overlap by at least v
+        got, tiles = run(tile, v)
+        d = np.abs(got - full)
+        band = np.zeros((H, W), dtype=bool)                                          # within 16 samples of where a tile ends inside the picture
+        for y0, x0, th, tw in tiles:
+            for e in (y0, y0 + th):
+                if 0 < e < H:
+                    band[max(e - 16, 0):e + 16, :] = True
+            for e in (x0, x0 + tw):
+                if 0 < e < W:
+                    band[:, max(e - 16, 0):e + 16] = True
+        res[f"overlap_{v}"] = {"tile": list(tile), "tiles": [list(t) for t in tiles],
+                               "luma_max": round(float(d[:, 0].max()), 3), "luma_rms": round(float(np.sqrt((d[:, 0] ** 2).mean())), 4),
+                               "all_planes_max": round(float(d.max()), 3), "all_planes_rms": round(float(np.sqrt((d ** 2).mean())), 4),
+                               "luma_rms_near_tile_edges": round(float(np.sqrt((d[:, 0][:, band] ** 2).mean())), 4),
+                               "luma_rms_elsewhere": round(float(np.sqrt((d[:, 0][:, ~band] ** 2).mean())), 4)}
+    print(json.dumps({"part": "tiles", "mode": "quality", "variant": a.variant, "dtype": "bf16", "size": [H, W], "frames": len(frames), "unit": "8-bit codes of Y'CbCr, "
+                      "measured on 10 bit 4:4:4 output", "note": "synthetic weights: how the blend behaves, not how a trained network's seams look", **res}))
+
+
 PICTURE = dict(H=1080, W=1920, rect=(0, 138, 1920, 804))
 
 
@@ -680,7 +777,7 @@ def picture_part(a):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion"])
+    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion", "tiles"])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--inner", type=int, default=200)
     ap.add_argument("--windows", type=int, default=8)
@@ -692,11 +789,17 @@ if __name__ == "__main__":
                     "csrc/sn_yuv.hip alone; its sn_ingest_yuv / sn_egress_yuv are timed beside this build's.  nlf and motion parts in kernels mode: a library "
                     "built from another commit's whole csrc; its seven noise-histogram entry points are timed beside this build's, at 8 and 10 bit")
     ap.add_argument("--only_cases", default=None, metavar="WORDS", help="kernels part: time only the cases whose name contains one of these comma-separated words")
-    ap.add_argument("--mode", choices=["forward", "kernels"], default="forward", help="picture, nlf, report and motion parts: which measurement")
+    ap.add_argument("--mode", choices=["forward", "kernels", "quality"], default="forward", help="picture, nlf, report, motion and tiles parts: which measurement "
+                    "(quality: the tiles part alone)")
     ap.add_argument("--picture", choices=["auto", "fixed"], default="auto", help="picture part, forward mode: VideoRestorer(picture='auto') or the rectangle itself")
+    ap.add_argument("--tile", action="append", default=None, metavar="{full,N,HxW}", help="tiles part, forward mode: a form to run (repeat for several, which then alternate)")
+    ap.add_argument("--tile_overlap", type=int, default=32, help="tiles part, forward mode: VideoRestorer(tile_overlap=...)")
+    ap.add_argument("--size", default=None, metavar="HxW", help="tiles part: the stream's size (default 720x1280 forward, 256x384 quality)")
+    ap.add_argument("--variant", choices=list(restore.VARIANTS), default="deblur_small", help="tiles part: the network")
     a = ap.parse_args()
     with torch.no_grad():
         {"kernels": kernels, "pipeline": pipeline, "sigma": sigma, "picture": picture_part,
          "nlf": nlf_kernels if a.mode == "kernels" else nlf_forward,
          "report": report_kernels if a.mode == "kernels" else report_forward,
-         "motion": motion_kernels if a.mode == "kernels" else motion_forward}[a.part](a)
+         "motion": motion_kernels if a.mode == "kernels" else motion_forward,
+         "tiles": tiles_quality if a.mode == "quality" else tiles_forward}[a.part](a)
