@@ -14,17 +14,6 @@ are clips of their own: windows restart at every scene start and reflect about t
 those of restoring every scene as a separate video.  The cuts are listed by the caller or found from luma thumbnails made on the device
 (``sn_yuv_thumb``, shiftnet_amd/scenes.py).
 
-Noise level (``sigma``, denoise variants): a number, a list with one number per window, or ``"auto"``: a blind estimate per window from
-histograms of the luma's 2 x 2 Haar HH coefficient, made on the device from the payloads the window has uploaded anyway
-(``sn_yuv_noise_hist``, shiftnet_amd/noise.py).  ``sigma_estimator="temporal"`` / ``"min"`` adds the same statistic of the difference of consecutive
-input frames (``sn_yuv_noise_hist_pairs``), in which texture that does not move cancels, and uses it alone or the lower of the two.
-``sigma_motion="blocks"`` lets that difference follow the picture: one integer vector per 16 x 16 luma block and pair, found on the device
-(``sn_yuv_block_motion``), so that a pan no longer reads as noise.
-
-Noise model (``noise_model``, denoise variants, off by default): sensor noise is signal dependent, the shadows of R'G'B' carry more of it than the
-highlights.  ``"level"`` estimates per window a noise-level function -- sigma against the luma code, 16 knots -- from the same histograms split by
-brightness (``sn_yuv_noise_hist_bands``) and writes the network's noise plane per pixel from it (``sn_noise_map_level``), in place of one level everywhere.
-
 Active picture (``picture``, off by default): a letterboxed or pillarboxed stream is restored inside its picture rectangle only -- there the bytes
 are those of restoring the cropped stream, and the bars leave as they came in.  The rectangle is given by the caller, for the stream or per window,
 or found per window from the sums of the luma's rows and columns, made on the device from the payloads the window has uploaded anyway
@@ -41,19 +30,8 @@ result's, separately for luma and chroma -- the fallback when the restoration is
 mid-grey, to see whether detail leaves with the noise.  Both happen in the egress, in the code domain, from the payloads the window has uploaded
 anyway (``sn_egress_yuv_mix``): amount 0 is the input byte for byte.  The blend is linear in the codes, not perceptual.
 
-Method-noise report (``report``, off by default): numbers about what the run changed, per written frame -- whether input minus output is white in
-space, independent from frame to frame, no stronger on edges than elsewhere, and as strong as the sigma the window was restored with.  Exact integer
-sums of the two sets of payloads the window holds on the device anyway once the egress has run (``sn_yuv_diff_stats``), float64 on the host
-(shiftnet_amd/report.py).  It changes no byte written.  What the numbers mean on real footage nobody has validated.  ``report_motion="blocks"`` adds the
-temporal correlation of that difference along the motion of the written picture (``sn_yuv_block_motion`` on the frames written, then
-``sn_yuv_diff_stats_mv``): removed detail that moves with a pan reads as uncorrelated at the same place, and as correlated along its vector.
-
-Tiles (``tile``, ``tile_overlap``; off by default): the network's activations grow with the pixels of the frames it is given, and a large frame does
-not fit the device at any useful window length.  With a tile size the forward -- and only the forward -- runs on overlapping rectangles of the
-window's frames, one after the other, and their float32 results are added into one float32 canvas with feather weights (``sn_tile_accumulate``,
-csrc/sn_tile.hip; the plan is windows.plan_tiles); everything before and after still works on the whole picture.  **A tiled result is not the
-full-frame result**: every channel-attention layer pools over the map it is given, so it sees the tile, and the receptive field is cut at tile edges.
-The feather turns a mismatch into a gradient instead of an edge; it does not remove it.
+Noise level (``sigma``, ``noise_model``; denoise variants), method-noise report (``report``) and tiles (``tile``): each is a part of its own, described at
+its class in shiftnet_amd/restore_parts.py (``NoiseLevel``, ``Report``, ``Tiles``); the restorer holds each or None and calls it by name.
 """
 from __future__ import annotations
 
@@ -65,6 +43,7 @@ from typing import Iterable, Iterator, List, Sequence, Tuple
 import numpy as np
 
 from .restore_cli import amount_arg, main, make_parser, picture_arg, sigma_arg, tile_arg  # noqa: F401 -- the command line (restore_cli.py), reached through this module
+from .restore_parts import NoiseLevel, Report, Tiles, _Stat
 from .windows import (DEFAULT_TILE_OVERLAP, DITHERS, FUTURE, PAST, PerWindow, _Frames, _SceneFrames, _Thread, amount_form, noise_model_form, pad_multiple,  # noqa: F401
                       padded_size, picture_form, plan_output, plan_scene_windows, plan_windows, reflect_index, report_form, report_motion_form, scene_cuts_form,
                       sigma_estimator_form, sigma_form, sigma_motion_form, tile_form, plan_tiles, window_indices)
@@ -72,35 +51,10 @@ from .windows import (DEFAULT_TILE_OVERLAP, DITHERS, FUTURE, PAST, PerWindow, _F
 VARIANTS = {"deblur": "gshift_deblur1", "deblur_small": "gshift_deblur2", "denoise": "gshift_denoise1", "denoise_small": "gshift_denoise2"}
 
 
-# ---- the pieces of the restorer: a per-window statistic, a slot, the state of one run ---------------------------------------------------
-class _Stat:
-    """A statistic of the payloads a window has uploaded, made on the device and read on the host: the device tensor or tensors (``rows`` leading
-    rows each, for the largest window), their pinned twins and the event behind the copies.  ``launch`` and ``wait`` may be on different threads;
-    the waiting one waits for that event -- the launching stream's own work, never the device and never the stream the forward runs on."""
-
-    def __init__(self, torch, dev, name: str, rows: int, shapes, dtype=None) -> None:
-        dtype = torch.uint32 if dtype is None else dtype
-        self.name = name                                         # of its launch counter in _Run.launches
-        self.dev = [torch.empty((rows,) + tuple(s), dtype=dtype, device=dev) for s in shapes]
-        self.pin = [torch.empty((rows,) + tuple(s), dtype=dtype).pin_memory() for s in shapes]
-        self.event = torch.cuda.Event()
-
-    def launch(self, t: int, run: "_Run", kernel) -> None:
-        """``kernel(the first t rows of every device tensor)`` on the current stream, their copies to the host behind it, the event behind those."""
-        kernel(*(d[:t] for d in self.dev))
-        for p, d in zip(self.pin, self.dev):
-            p[:t].copy_(d[:t], non_blocking=True)
-        self.event.record()
-        run.launches[self.name] += 1
-
-    def wait(self, t: int) -> List[np.ndarray]:
-        self.event.synchronize()
-        return [p[:t].numpy() for p in self.pin]
-
-
+# ---- the pieces of the restorer: a slot, the state of one run (a per-window statistic, _Stat, lives in restore_parts.py) -----------------
 class _Slot:
     """Everything one of the two double-buffer slots owns: staging and device buffers sized for the largest window, the events that order the
-    streams about them, what the stager notes for the window the slot holds, and the window's statistics (None where the mode needs none)."""
+    streams about them, what the stager notes for the window the slot holds, and one state object per part that keeps any (None where it keeps none)."""
 
     def __init__(self, torch, dev, dtype, tin: int, tout: int, fb: int, ofb: int, pixels: int) -> None:
         self.pin_in = torch.empty((tin, fb), dtype=torch.uint8).pin_memory()
@@ -114,14 +68,9 @@ class _Slot:
         self.rect = None                                          # the picture of the window the slot holds (None: the full frame)
         self.t0 = 0                                               # the frame number, in its clip, of the first frame that window restores
         self.used = False                                         # in this restore(): a window has gone through the slot
-        self.noise = self.bands = self.sums = None                # _Stat: the window's histograms, band histograms, row and column sums
-        self.pairs = self.pair_bands = None                       # _Stat: the histograms and band histograms of the window's frame pairs
-        self.motion = self.motion_sad = None                      # sigma_motion: _Stat of the pairs' block vectors (flat int8), their SADs on the device
-        self.motion_grid = (0, 0)                                 # ... and the vector blocks of the window the slot holds
+        self.sums = None                                          # picture="auto": _Stat of the window's row and column sums
+        self.noise = self.report = None                           # what the parts NoiseLevel and Report keep per slot (restore_parts.py)
         self.dev_ref = None                                       # a mix or a report with another format out: the window's input payloads in the format written
-        self.report = None                                        # _Stat: the sums of written minus input of the window's own frames
-        self.report_mv = None                                     # report_motion: _Stat of the sums of the window's written pairs along their vectors
-        self.report_vec = self.report_sad = None                  # ... the vectors (flat int8) and SADs of those pairs: they stay on the device
 
 
 class _Run:
@@ -141,7 +90,7 @@ class _Run:
         self.window_pair_motion: List = []                        # sigma_motion: per window, per pair, noise.motion_summary's triple
         self.launches = {"noise": 0, "nlf": 0, "nlf_map": 0, "picture": 0, "thumb": 0, "noise_pairs": 0, "nlf_pairs": 0, "report": 0, "motion": 0,
                          "report_motion": 0, "report_mv": 0,      # report_motion: the block matcher on the written frames, the sums along its vectors
-                         "tile": 0}                               # tile: the sn_tile_accumulate launches
+                         "tile": 0}                               # tile: the tiles added into the canvas
         self.window_tiles: List = []                              # tile: per window, the (y0, x0, th, tw) of its tiles in the order they ran
         self.frame_sums: List = []                                # report: the 16 sums of every frame handed out, the window it came from, that window's sigma
         self.frame_window: List[int] = []
@@ -366,7 +315,6 @@ class VideoRestorer:
         self.cut_threshold, self.cut_ratio = float(cut_threshold), float(cut_ratio)
         self.V = net.V
         self.tile = tile_form(tile, tile_overlap, self.V.topo)    # None (the code path without any of it) or (th, tw, overlap)
-        self._tile_plans = {}                                     # (hp, wp) -> (the plan, its weight tables on the device)
         if self.V.denoise and sigma is None:
             raise ValueError("sigma is required by the denoise variants (the noise level of the footage, in 8-bit code values)")
         self.sigma_clamp = check_clamp(sigma_clamp)
@@ -392,6 +340,11 @@ class VideoRestorer:
         self.dev, self.dtype = p.device, p.dtype
         if self.dev.type != "cuda":
             raise ValueError("VideoRestorer needs the module on a HIP device")
+        # the parts (restore_parts.py), each None where its feature is off: they are given what was parsed above
+        self.noise = NoiseLevel(self.sigma_mode, self.sigma, self.sigma_estimator, self.sigma_motion, self.nlf_mode, self.nlf,
+                                self.sigma_clamp) if self.V.denoise else None
+        self.report_part = Report(self.report_edge, self.report_motion, self.V.denoise) if self.report else None
+        self.tiles = Tiles(torch, net, self.dev, self.tile) if self.tile is not None else None
         self._shape = None
         self._reset()
 
@@ -428,42 +381,15 @@ class VideoRestorer:
         for s in self.slots:
             s.dev_ref = torch.empty((tout, self.ofb), dtype=torch.uint8, device=dev) if ref else None
         self.s_in, self.s_out = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
-        if self.sigma_mode == "auto" or self.nlf_mode is not None:
-            from .noise import clip_codes
-            self.noise_lo, self.noise_hi = clip_codes(fmt.bits, fmt.range)
-        for s in self.slots:                                      # per slot: the window's statistics on the device and in pinned memory
-            if self.sigma_mode == "auto":
-                from .noise import nbins
-                s.noise = _Stat(torch, dev, "noise", tin, [(nbins(fmt.bits),)])
-            if self.nlf_mode == "level":
-                from .noise import NLF_BANDS, nlf_bins
-                s.bands = _Stat(torch, dev, "nlf", tin, [(NLF_BANDS, nlf_bins(fmt.bits))])
-            if self.sigma_estimator != "spatial":                 # tin frames are tin - 1 pairs
-                from .noise import NLF_BANDS, nlf_bins, pair_bins
-                s.pairs = _Stat(torch, dev, "noise_pairs", tin - 1, [(pair_bins(fmt.bits),)])
-                if self.nlf_mode == "level":
-                    s.pair_bands = _Stat(torch, dev, "nlf_pairs", tin - 1, [(NLF_BANDS, nlf_bins(fmt.bits))])
-            if self.sigma_motion is not None:                     # the vectors of the largest window's pairs at the full frame's grid, flat: a
-                from .noise import motion_grid                    # window's are a view of the leading elements at the grid of its picture
-                blocks = (tin - 1) * int(np.prod(motion_grid(h, w)))
-                s.motion = _Stat(torch, dev, "motion", 2 * blocks, [()], torch.int8)
-                s.motion_sad = torch.empty(blocks, dtype=torch.uint32, device=dev)
-            if self.picture_mode == "auto":
+        if self.picture_mode == "auto":
+            for s in self.slots:
                 s.sums = _Stat(torch, dev, "picture", tin, [(h,), (w,)])
-            if self.report:                                       # one row per frame the window writes
-                from .lib import SN_DIFF_STATS
-                s.report = _Stat(torch, dev, "report", tout, [(SN_DIFF_STATS,)], torch.int64)
-            if self.report_motion is not None:                    # one row per pair of frames the window writes; the vectors of the largest window's
-                from .lib import SN_DIFF_STATS_MV                 # pairs at the full frame's grid, flat, as sigma_motion keeps its own
-                from .noise import motion_grid
-                blocks = max((tout - 1) * int(np.prod(motion_grid(h, w))), 1)
-                s.report_mv = _Stat(torch, dev, "report_mv", max(tout - 1, 1), [(SN_DIFF_STATS_MV,)], torch.int64)
-                s.report_vec = torch.empty(2 * blocks, dtype=torch.int8, device=dev)
-                s.report_sad = torch.empty(blocks, dtype=torch.uint32, device=dev)
-        self.report_code_edge = int(round(self.report_edge * (1 << (ofmt.bits - 8))))      # in codes of the format written
-        # tiles: the float32 canvas the tiles' results are added into, flat and sized for the full frame as the slots' tensors are.  One for the restorer
-        # (main stream only): the egress of a window has consumed it before the next window's forward runs
-        self.canvas = torch.empty(tout * 3 * self.hp * self.wp, dtype=torch.float32, device=dev) if self.tile is not None else None
+        if self.noise is not None:
+            self.noise.prepare(torch, dev, self.dtype, fmt, h, w, tin, self.slots)
+        if self.report_part is not None:
+            self.report_part.prepare(torch, dev, ofmt, h, w, tout, self.slots)
+        if self.tiles is not None:
+            self.tiles.prepare(tout, self.hp, self.wp)
 
     def _size(self, rect) -> Tuple[int, int, int, int]:
         """(h, w, padded h, padded w) of what a window with picture ``rect`` feeds the network."""
@@ -487,8 +413,7 @@ class VideoRestorer:
     def _stage(self, slot: _Slot, frames: Sequence[np.ndarray], t0: int = 0) -> int:
         """Host frames -> pinned slot -> device -> RGB tensors, on the side stream.  Windows are staged in the order they are restored.
         t0: the number of the window's first restored frame in its clip (the dither's frame number)."""
-        from .io_edges import (block_motion_yuv, ingest_yuv, noise_hist_bands_yuv, noise_hist_pairs_bands_mv_yuv, noise_hist_pairs_bands_yuv,
-                               noise_hist_pairs_mv_yuv, noise_hist_pairs_yuv, noise_hist_yuv, rowcol_sums_yuv)
+        from .io_edges import ingest_yuv, rowcol_sums_yuv
         torch, run = self.torch, self.run
         t = len(frames)
         rect = self._window_picture()
@@ -516,134 +441,51 @@ class VideoRestorer:
             slot.rect = rect
             x, x32 = self._views(slot, t, rect)
             hp, wp = x.shape[3], x.shape[4]
-            if self.sigma_mode == "auto":
-                # the histograms of the payloads just uploaded, ahead of the ingest so that they are on the host long before _run asks.  The
-                # pinned twin is free: _run read it on the host before this slot was handed back to the stager
-                slot.noise.launch(t, run, lambda out: noise_hist_yuv(payloads, self.fmt, self.h, self.w, self.noise_lo, self.noise_hi, out=out, rect=rect))
-            mv = None
-            if slot.motion is not None:
-                # the vectors of the t - 1 pairs, once per window and ahead of the histograms that follow them; their copy to the host is for stats alone
-                from .noise import motion_grid
-                gy, gx = slot.motion_grid = motion_grid(*self._size(rect)[:2])
-                blocks = (t - 1) * gy * gx
-                mv = slot.motion.dev[0][:2 * blocks].view(t - 1, gy, gx, 2)
-                sad = slot.motion_sad[:blocks].view(t - 1, gy, gx)
-                slot.motion.launch(2 * blocks, run, lambda out: block_motion_yuv(payloads, self.fmt, self.h, self.w, rect=rect, out_mv=mv, out_sad=sad))
-            if slot.pairs is not None and mv is not None:        # ... in place of the plain pair histogram
-                slot.pairs.launch(t - 1, run, lambda out: noise_hist_pairs_mv_yuv(payloads, self.fmt, self.h, self.w, mv, self.noise_lo, self.noise_hi,
-                                                                                  out=out, rect=rect))
-            elif slot.pairs is not None:                         # the statistic of the t - 1 pairs of consecutive payloads (t >= 5: a window has 4 neighbours)
-                slot.pairs.launch(t - 1, run, lambda out: noise_hist_pairs_yuv(payloads, self.fmt, self.h, self.w, self.noise_lo, self.noise_hi, out=out,
-                                                                               rect=rect))
-            if self.nlf_mode == "level":                         # the same statistic by brightness band, from the same payloads, behind it
-                slot.bands.launch(t, run, lambda out: noise_hist_bands_yuv(payloads, self.fmt, self.h, self.w, self.noise_lo, self.noise_hi, out=out,
-                                                                           rect=rect))
-            if slot.pair_bands is not None and mv is not None:
-                slot.pair_bands.launch(t - 1, run, lambda out: noise_hist_pairs_bands_mv_yuv(payloads, self.fmt, self.h, self.w, mv, self.noise_lo,
-                                                                                             self.noise_hi, out=out, rect=rect))
-            elif slot.pair_bands is not None:
-                slot.pair_bands.launch(t - 1, run, lambda out: noise_hist_pairs_bands_yuv(payloads, self.fmt, self.h, self.w, self.noise_lo,
-                                                                                          self.noise_hi, out=out, rect=rect))
+            if self.noise is not None:
+                self.noise.stage(slot.noise, payloads, rect, run)
             ingest_yuv(payloads, self.fmt, self.h, self.w, hp, wp, self.dtype, out=x, rect=rect)
             if x32 is not None:
                 ingest_yuv(payloads, self.fmt, self.h, self.w, hp, wp, torch.float32, out=x32, rect=rect)
             slot.ev_ready.record(self.s_in)
         return t
 
-    def _window_sigma(self, slot: _Slot, t: int) -> float:
-        """The noise level of the window about to run (denoise variants); windows run in the order they are handed out."""
-        run = self.run
-        if self.sigma_mode == "auto":
-            from .noise import frame_sigma, window_sigma
-            hist, = slot.noise.wait(t)
-            per = [frame_sigma(hist[i], self.fmt.bits, self.fmt.matrix, self.fmt.range) for i in range(t)]
-            run.window_frame_sigma.append(per)
-            if self.sigma_estimator == "spatial":
-                sigma = window_sigma(per, self.sigma_clamp)
-            else:
-                from .noise import combine_sigma, frames_median, pair_sigma, window_sigma_temporal
-                pairs, = slot.pairs.wait(t - 1)
-                ps = [pair_sigma(pairs[i], self.fmt.bits, self.fmt.matrix, self.fmt.range) for i in range(t - 1)]
-                spatial, temporal = frames_median(per), window_sigma_temporal(ps)
-                run.window_pair_sigma.append(ps)
-                run.window_sigma_spatial.append(spatial)
-                run.window_sigma_temporal.append(temporal)
-                if slot.motion is not None:
-                    from .noise import motion_summary
-                    gy, gx = slot.motion_grid
-                    flat, = slot.motion.wait(2 * (t - 1) * gy * gx)
-                    run.window_pair_motion.append(motion_summary(flat.reshape(t - 1, gy, gx, 2)))
-                sigma = combine_sigma(spatial, temporal, self.sigma_estimator, self.sigma_clamp)
-        else:
-            sigma = self.sigma.at(len(run.window_sigma))
-        run.window_sigma.append(sigma)
-        return sigma
+    def _forward(self, x, x32, nm, crop=None):
+        """The one call of the network: x [1, t, 3, hp, wp], x32 its float32 twin or None, nm the noise plane [1, t, 1, hp, wp] or None (the deblur
+        variants take none) -> float32 [t - 4, 3, hp, wp].  crop: a tile's index into those tensors; the network is given contiguous crops, and of a flat
+        noise level its stride-0 expansion cut to the tile's shape, which copies nothing."""
+        if crop is not None:
+            x, x32 = x[crop].contiguous(), (x32[crop].contiguous() if x32 is not None else None)
+            if nm is not None:
+                nm = nm[crop] if self.noise.flat else nm[crop].contiguous()
+        args = (x,) if nm is None else (x, nm)
+        return self.net.forward_fp32_out(*args, **({"shortcut": x32} if x32 is not None else {}))
 
-    def _window_curve(self, slot: _Slot, t: int) -> List[float]:
-        """The noise-level function of the window about to run (noise_model): 16 knots, sigma of 8-bit R'G'B'."""
-        run = self.run
-        if self.nlf_mode == "level":
-            from .noise import window_curve, window_curve_pairs
-            bands, = slot.bands.wait(t)
-            if self.sigma_estimator == "spatial":
-                curve = window_curve(bands, self.fmt.bits, self.fmt.matrix, self.fmt.range, self.sigma_clamp)
-            else:
-                pair_bands, = slot.pair_bands.wait(t - 1)
-                curve = window_curve_pairs(bands, pair_bands, self.fmt.bits, self.fmt.matrix, self.fmt.range, self.sigma_estimator, self.sigma_clamp)
-        else:
-            curve = list(self.nlf.at(len(run.window_nlf)))
-        run.window_nlf.append(curve)
-        return curve
-
-    def _tile_plan(self, hp: int, wp: int):
-        """(windows.plan_tiles for a padded picture of hp x wp, its weight tables [n_y][th] and [n_x][tw] on the device), made once per size."""
-        key = (int(hp), int(wp))
-        if key not in self._tile_plans:
-            th, tw, overlap = self.tile
-            plan = plan_tiles(key[0], key[1], th, tw, overlap)
-            to_dev = lambda a: self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)      # noqa: E731
-            self._tile_plans[key] = (plan, to_dev(plan.wy), to_dev(plan.wx))
-        return self._tile_plans[key]
-
-    def _forward_tiles(self, x, x32, nm, sigma, t: int):
-        """The forward of one window tile by tile (current stream): x [1, t, 3, hp, wp], x32 its float32 twin or None, nm the per-pixel noise plane
-        [1, t, 1, hp, wp] or None (then ``sigma`` is broadcast where the network takes a noise level) -> the float32 canvas [t - 4, 3, hp, wp]."""
-        from .io_edges import tile_accumulate
-        torch = self.torch
-        hp, wp = x.shape[3], x.shape[4]
-        plan, wy, wx = self._tile_plan(hp, wp)
-        n = t - PAST - FUTURE
-        canvas = self.canvas[:n * 3 * hp * wp].view(n, 3, hp, wp)
-        th, tw = plan.th, plan.tw
-        flat = None
-        if nm is None and self.V.denoise:
-            flat = torch.full((1, 1, 1, 1, 1), sigma / 255.0, dtype=self.dtype, device=self.dev).expand(1, t, 1, th, tw)
-        for _ in range(2):      # one range-guard check for the window's tiles (no device sync between them); a tripped guard moved the module to the
-            canvas.zero_()      # two-kernel chain: run them once more, into a canvas that starts at zero again
-            with self.net.guard_scope() as gs:
-                for i, y0 in enumerate(plan.ys):
-                    for j, x0 in enumerate(plan.xs):
-                        crop = (slice(None), slice(None), slice(None), slice(y0, y0 + th), slice(x0, x0 + tw))
-                        kw = {"shortcut": x32[crop].contiguous()} if x32 is not None else {}
-                        if nm is not None:
-                            o = self.net.forward_fp32_out(x[crop].contiguous(), nm[crop].contiguous(), **kw)
-                        elif flat is not None:
-                            o = self.net.forward_fp32_out(x[crop].contiguous(), flat, **kw)
-                        else:
-                            o = self.net.forward_fp32_out(x[crop].contiguous(), **kw)
-                        tile_accumulate(o, canvas, wy[i], wx[j], y0, x0)
-                        self.run.launches["tile"] += 1
-            if not gs.tripped:
-                break
-        return canvas
+    def _input_as_written(self, slot: _Slot, n: int, rect, tiled: bool):
+        """The window's own n input frames (not the reflected ones around them) in the format written, on the device: the payloads read, or with another
+        format out the whole frames converted by the two edges, float32 between them, rounded to nearest -- into the slot's reference buffer where a mix or
+        a report reads them again after dev_out has been written, straight into dev_out where only the samples outside a picture are wanted (main stream)."""
+        from .io_edges import egress_yuv, ingest_yuv
+        read = slot.dev_in[PAST:PAST + n]
+        if not self.convert or (slot.dev_ref is None and rect is None):      # as read; or nothing asks
+            return read
+        full = self.conv32[:n * 3 * self.h * self.w].view(1, n, 3, self.h, self.w)
+        ingest_yuv(read, self.fmt, self.h, self.w, self.h, self.w, self.torch.float32, out=full)
+        own = egress_yuv(full[0], self.ofmt, self.h, self.w, dst=(slot.dev_out if slot.dev_ref is None else slot.dev_ref)[:n])
+        if tiled and slot.dev_ref is not None and rect is not None:
+            # a tiled window's mix and report take the rectangle as the whole picture, as everything else of it does: inside the rectangle their
+            # input side is the rectangle converted as the cropped stream's frames are -- chroma from the rectangle's own clamped neighbours, not from
+            # the bars'.  The float32 buffer is free again: the egress that read it lies ahead on this stream
+            part = self.conv32[:n * 3 * rect[3] * rect[2]].view(1, n, 3, rect[3], rect[2])
+            ingest_yuv(read, self.fmt, self.h, self.w, rect[3], rect[2], self.torch.float32, out=part, rect=rect)
+            egress_yuv(part[0], self.ofmt, self.h, self.w, dst=own, rect=rect)
+        return own
 
     def _run(self, slot: _Slot, t: int, main) -> int:
         """Forward + egress on the main stream, copy back on the output stream."""
-        from .io_edges import block_motion_yuv, diff_stats_mv_yuv, diff_stats_yuv, egress_yuv, ingest_yuv, noise_map_level
+        from .io_edges import egress_yuv
         torch, run = self.torch, self.run
         n = t - PAST - FUTURE
-        sigma = self._window_sigma(slot, t) if self.V.denoise else None
-        curve = self._window_curve(slot, t) if self.nlf_mode is not None else None
+        level = self.noise.level(slot.noise, t, run) if self.noise is not None else None
         rect = slot.rect
         run.window_picture.append(rect)
         with torch.cuda.stream(main), torch.no_grad():
@@ -653,69 +495,25 @@ class VideoRestorer:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(main)
             x, x32 = self._views(slot, t, rect)
-            kw = {}
-            if x32 is not None:
-                kw["shortcut"] = x32
-            plan = self._tile_plan(x.shape[3], x.shape[4])[0] if self.tile is not None else None
-            if plan is not None:
-                run.window_tiles.append(list(plan.tiles))
-            nm = None
-            if curve is not None:
-                # the plane from the payloads the ingest read (ev_ready lies behind their upload; they stay until ev_done); the knots are a kernel argument
-                nm = noise_map_level(slot.dev_in[:t], self.fmt, self.h, self.w, x.shape[3], x.shape[4], [c / 255.0 for c in curve], self.dtype,
-                                     self.noise_lo, self.noise_hi, rect=rect)
-                run.launches["nlf_map"] += 1
-            tiled = plan is not None and not plan.single
-            if tiled:
-                out = self._forward_tiles(x, x32, nm, sigma, t)
-            elif curve is not None:
-                out = self.net.forward_fp32_out(x, nm, **kw)
-            elif self.V.denoise:
-                nm = torch.full((1, 1, 1, 1, 1), sigma / 255.0, dtype=self.dtype, device=self.dev).expand(1, t, 1, x.shape[3], x.shape[4])
-                out = self.net.forward_fp32_out(x, nm, **kw)
-            else:
-                out = self.net.forward_fp32_out(x, **kw)
+            hp, wp = x.shape[3], x.shape[4]
+            # the plane from the payloads the ingest read (ev_ready lies behind their upload; they stay until ev_done)
+            nm = self.noise.plane(slot.dev_in[:t], rect, hp, wp, level, run) if self.noise is not None else None
+            out = self.tiles.forward(lambda crop: self._forward(x, x32, nm, crop), n, hp, wp, run) if self.tiles is not None else None
+            tiled = out is not None                              # a window whose plan is one tile takes the path of tile=None
+            if not tiled:
+                out = self._forward(x, x32, nm)
             e1.record(main)
             run.timers.append((e0, e1))
-            own = slot.dev_in[PAST:PAST + n]                     # the window's own n frames (not the reflected ones around them), still on the device
-            outside = rect is not None                           # the samples outside the picture have to be put into dev_out first
-            keep = self.mix is not None or self.report           # the input in the format written is read again after dev_out has been written
-            if self.convert and (outside or keep):
-                # ... in the format written: the whole frames converted by the two edges, float32 between them, rounded to nearest.  Straight into
-                # dev_out without a mix or a report; with one into the slot's reference buffer, because they read one while the other is (has been) written
-                full = self.conv32[:n * 3 * self.h * self.w].view(1, n, 3, self.h, self.w)
-                ingest_yuv(own, self.fmt, self.h, self.w, self.h, self.w, torch.float32, out=full)
-                read, own = own, egress_yuv(full[0], self.ofmt, self.h, self.w, dst=(slot.dev_ref if keep else slot.dev_out)[:n])
-                if tiled and keep and rect is not None:
-                    # a tiled window's mix and report take the rectangle as the whole picture, as everything else of it does: inside the rectangle their
-                    # input side is the rectangle converted as the cropped stream's frames are -- chroma from the rectangle's own clamped neighbours, not from
-                    # the bars'.  The float32 buffer is free again: the egress that read it lies ahead on this stream
-                    part = self.conv32[:n * 3 * rect[3] * rect[2]].view(1, n, 3, rect[3], rect[2])
-                    ingest_yuv(read, self.fmt, self.h, self.w, rect[3], rect[2], torch.float32, out=part, rect=rect)
-                    egress_yuv(part[0], self.ofmt, self.h, self.w, dst=own, rect=rect)
-                outside = outside and keep
-            if outside:
-                # everything outside the picture leaves as it came in (as converted, in another format): the egress below writes the inside only
-                slot.dev_out[:n].copy_(own, non_blocking=True)
+            own = self._input_as_written(slot, n, rect, tiled)
+            written = slot.dev_out[:n]
+            if rect is not None and (slot.dev_ref is not None or not self.convert):
+                # everything outside the picture leaves as it came in (as converted, in another format; converted frames that nothing reads again are
+                # in dev_out already): the egress below writes the inside only
+                written.copy_(own, non_blocking=True)
             dither = None if self.dither is None else (self.dither_seed, slot.t0)
-            if self.mix is None:
-                egress_yuv(out, self.ofmt, self.h, self.w, dst=slot.dev_out[:n], rect=rect, dither=dither)
-            else:
-                egress_yuv(out, self.ofmt, self.h, self.w, dst=slot.dev_out[:n], rect=rect, dither=dither, mix=self.mix, ref=own)
-            if self.report:
-                # written minus input, both still on the device; the sums are read where the window's frames are handed out (_collect)
-                written = slot.dev_out[:n]
-                slot.report.launch(n, run, lambda sums: diff_stats_yuv(own, written, self.ofmt, self.h, self.w, rect=rect, edge=self.report_code_edge,
-                                                                       out_sums=sums))
-                if slot.report_mv is not None and n >= 2:
-                    # the vectors of the n - 1 pairs of the frames written (the clean picture), then d of both frames of every pair along them
-                    from .noise import motion_grid
-                    gy, gx = motion_grid(*self._size(rect)[:2])
-                    blocks = (n - 1) * gy * gx
-                    mv = slot.report_vec[:2 * blocks].view(n - 1, gy, gx, 2)
-                    block_motion_yuv(written, self.ofmt, self.h, self.w, rect=rect, out_mv=mv, out_sad=slot.report_sad[:blocks].view(n - 1, gy, gx))
-                    run.launches["report_motion"] += 1
-                    slot.report_mv.launch(n - 1, run, lambda sums: diff_stats_mv_yuv(own, written, self.ofmt, self.h, self.w, mv, rect=rect, out_sums=sums))
+            egress_yuv(out, self.ofmt, self.h, self.w, dst=written, rect=rect, dither=dither, mix=self.mix, ref=own if self.mix is not None else None)
+            if self.report_part is not None:
+                self.report_part.launch(slot.report, own, written, rect, run)
             slot.ev_done.record(main)
         with torch.cuda.stream(self.s_out):
             self.s_out.wait_event(slot.ev_done)
@@ -727,15 +525,8 @@ class VideoRestorer:
     def _collect(self, slot: _Slot, n: int) -> List[np.ndarray]:
         slot.ev_d2h.synchronize()
         run = self.run
-        if self.report:                                          # windows are handed out in the order they ran: window_sigma has this one's entry
-            sums, = slot.report.wait(n)
-            run.frame_sums += [[int(v) for v in row] for row in sums]
-            run.frame_window += [run.collected] * n
-            run.frame_sigma += [run.window_sigma[run.collected] if self.V.denoise else None] * n
-            if slot.report_mv is not None:                       # frame i carries the pair (i, i + 1); a window's last frame has none
-                pairs = [[int(v) for v in row] for row in slot.report_mv.wait(n - 1)[0]] if n >= 2 else []
-                run.pair_sums_mv += pairs + [None]
-                run.frame_size += [self._size(run.window_picture[run.collected])[:2]] * n
+        if self.report_part is not None:
+            self.report_part.collect(slot.report, n, run)
         run.collected += 1
         return list(slot.pin_out[:n].numpy().copy())
 
@@ -745,45 +536,14 @@ class VideoRestorer:
         stats["window_forward_ms"] = ms
         stats["forward_s"] = sum(ms) / 1e3
         stats["windows"] = len(ms)
-        stats["noise_launches"] = run.launches["noise"] + run.launches["motion"]      # "motion" stays 0 without sigma_motion
-        if self.nlf_mode is not None:
-            stats["window_nlf"] = [list(c) for c in run.window_nlf]
-            stats["nlf_launches"], stats["nlf_map_launches"] = run.launches["nlf"], run.launches["nlf_map"]
+        stats["noise_launches"] = 0                              # the deblur variants estimate nothing; NoiseLevel.finish counts its own
         stats["window_picture"] = list(run.window_picture)
         stats["picture_launches"] = run.launches["picture"]
-        if self.tile is not None:
-            stats["tile"], stats["tile_overlap"] = self.tile[:2], self.tile[2]
-            stats["window_tiles"] = [list(w) for w in run.window_tiles]
-            stats["tile_launches"] = run.launches["tile"]
         if self.picture_mode == "auto":
             stats["picture_wait_ms"] = list(run.picture_wait_ms)
-        if self.V.denoise:
-            stats["window_sigma"] = list(run.window_sigma)
-            if self.sigma_mode == "auto":
-                stats["window_frame_sigma"] = [list(p) for p in run.window_frame_sigma]
-            if self.sigma_estimator != "spatial":
-                stats["sigma_estimator"] = self.sigma_estimator
-                stats["window_sigma_spatial"], stats["window_sigma_temporal"] = list(run.window_sigma_spatial), list(run.window_sigma_temporal)
-                stats["window_pair_sigma"] = [list(p) for p in run.window_pair_sigma]
-                stats["noise_pairs_launches"] = run.launches["noise_pairs"]
-                if self.nlf_mode == "level":
-                    stats["nlf_pairs_launches"] = run.launches["nlf_pairs"]
-                if self.sigma_motion is not None:
-                    stats["sigma_motion"] = self.sigma_motion
-                    stats["window_pair_motion"] = [list(p) for p in run.window_pair_motion]
-        if self.report:
-            from .report import frames_report, summarize
-            stats["frame_sums"] = [list(r) for r in run.frame_sums]
-            stats["frame_report"] = frames_report(run.frame_sums, run.frame_window, run.frame_sigma, self.ofmt.bits, self.ofmt.matrix, self.ofmt.range)
-            stats["report_summary"] = summarize(stats["frame_report"])
-            stats["report_launches"] = run.launches["report"]
-        if self.report_motion is not None:
-            from .report import frames_report_motion, summarize_motion
-            stats["report_motion"] = self.report_motion
-            stats["pair_sums_mv"] = [None if r is None else list(r) for r in run.pair_sums_mv]
-            stats["frame_report_motion"] = frames_report_motion(run.pair_sums_mv, self.ofmt.bits, run.frame_size)
-            stats["report_motion_summary"] = summarize_motion(stats["frame_report_motion"])
-            stats["report_motion_launches"] = run.launches["report_motion"] + run.launches["report_mv"]
+        for part in (self.noise, self.report_part, self.tiles):
+            if part is not None:
+                part.finish(run, stats)
         src = run.src
         if self.scene_cuts is not None:                          # its thread has ended: the stream has been read to its end
             stats["cuts"] = list(src.cuts)

@@ -1,0 +1,330 @@
+"""The optional features of the video restorer (shiftnet_amd/restore.py), one class each: ``NoiseLevel`` (what a window's noise level is and how it is
+obtained), ``Report`` (the method-noise report) and ``Tiles`` (the forward in overlapping tiles).  A part owns everything of its feature -- its state per
+slot on the device and in pinned memory, its launches, its host arithmetic and its keys of ``stats`` -- and writes into the one record of a
+``restore()`` (``restore._Run``) that ``VideoRestorer`` hands it; ``VideoRestorer`` holds each part or None and calls it by name.  The parts are given
+parsed values (windows.py's ``*_form`` functions) and validate nothing.  ``_Stat`` and ``_Vectors`` are what they share."""
+from __future__ import annotations
+
+from typing import List, Tuple
+
+import numpy as np
+
+from .noise import (NLF_BANDS, clip_codes, combine_sigma, frame_sigma, frames_median, motion_grid, motion_summary, nbins, nlf_bins, pair_bins, pair_sigma,
+                    window_curve, window_curve_pairs, window_sigma, window_sigma_temporal)
+from .report import frames_report, frames_report_motion, summarize, summarize_motion
+from .windows import plan_tiles
+
+
+class _Stat:
+    """A statistic of the payloads a window has uploaded, made on the device and read on the host: the device tensor or tensors (``rows`` leading
+    rows each, for the largest window), their pinned twins and the event behind the copies.  ``launch`` and ``wait`` may be on different threads;
+    the waiting one waits for that event -- the launching stream's own work, never the device and never the stream the forward runs on."""
+
+    def __init__(self, torch, dev, name: str, rows: int, shapes, dtype=None) -> None:
+        dtype = torch.uint32 if dtype is None else dtype
+        self.name = name                                         # of its launch counter in _Run.launches
+        self.dev = [torch.empty((rows,) + tuple(s), dtype=dtype, device=dev) for s in shapes]
+        self.pin = [torch.empty((rows,) + tuple(s), dtype=dtype).pin_memory() for s in shapes]
+        self.event = torch.cuda.Event()
+
+    def launch(self, t: int, run: "_Run", kernel) -> None:
+        """``kernel(the first t rows of every device tensor)`` on the current stream, their copies to the host behind it, the event behind those."""
+        kernel(*(d[:t] for d in self.dev))
+        for p, d in zip(self.pin, self.dev):
+            p[:t].copy_(d[:t], non_blocking=True)
+        self.event.record()
+        run.launches[self.name] += 1
+
+    def wait(self, t: int) -> List[np.ndarray]:
+        self.event.synchronize()
+        return [p[:t].numpy() for p in self.pin]
+
+
+def _picture_size(rect, h: int, w: int) -> Tuple[int, int]:
+    """(h, w) of a window's picture: the rectangle's, or the frame's."""
+    return (h, w) if rect is None else (rect[3], rect[2])
+
+
+class _Vectors:
+    """The block vectors (``sn_yuv_block_motion``) of the largest window's ``pairs`` pairs at the full frame's grid, flat: int8 vectors and uint32 SADs
+    on the device.  A window's are views of the leading elements at the grid of its picture.  ``stat``: the name of a ``_Stat`` that brings the
+    vectors to the host as well (None: they stay on the device)."""
+
+    def __init__(self, torch, dev, pairs: int, h: int, w: int, stat=None) -> None:
+        blocks = max(pairs * int(np.prod(motion_grid(h, w))), 1)
+        self.stat = _Stat(torch, dev, stat, 2 * blocks, [()], torch.int8) if stat is not None else None
+        self.mv = self.stat.dev[0] if stat is not None else torch.empty(2 * blocks, dtype=torch.int8, device=dev)
+        self.sad = torch.empty(blocks, dtype=torch.uint32, device=dev)
+
+    def views(self, p: int, h: int, w: int):
+        """(int8 [p, gy, gx, 2], uint32 [p, gy, gx]) for a window of p pairs and a picture of h x w."""
+        gy, gx = motion_grid(h, w)
+        return self.mv[:2 * p * gy * gx].view(p, gy, gx, 2), self.sad[:p * gy * gx].view(p, gy, gx)
+
+
+# ---- the noise level ------------------------------------------------------------------------------------------------------------------
+class _NoiseState:
+    """What a slot holds for ``sigma="auto"``: the ``_Stat``s of the window's histograms (None where the mode needs none) and its vectors."""
+
+    def __init__(self, torch, dev, part: "NoiseLevel", bits: int, h: int, w: int, tin: int) -> None:
+        temporal, level = part.estimator != "spatial", part.nlf_mode == "level"
+        self.hist = _Stat(torch, dev, "noise", tin, [(nbins(bits),)])
+        self.bands = _Stat(torch, dev, "nlf", tin, [(NLF_BANDS, nlf_bins(bits))]) if level else None
+        self.pairs = _Stat(torch, dev, "noise_pairs", tin - 1, [(pair_bins(bits),)]) if temporal else None      # tin frames are tin - 1 pairs
+        self.pair_bands = _Stat(torch, dev, "nlf_pairs", tin - 1, [(NLF_BANDS, nlf_bins(bits))]) if temporal and level else None
+        self.vectors = _Vectors(torch, dev, tin - 1, h, w, stat="motion") if part.motion is not None else None
+        self.grid = (0, 0)                                       # the vector blocks of the window the slot holds
+
+
+class NoiseLevel:
+    """What a window's noise level is and how it is obtained (the denoise variants; every ``sigma`` mode).
+
+    Noise level (``sigma``): a number, a list with one number per window, or ``"auto"``: a blind estimate per window from
+    histograms of the luma's 2 x 2 Haar HH coefficient, made on the device from the payloads the window has uploaded anyway
+    (``sn_yuv_noise_hist``, shiftnet_amd/noise.py).  ``sigma_estimator="temporal"`` / ``"min"`` adds the same statistic of the difference of consecutive
+    input frames (``sn_yuv_noise_hist_pairs``), in which texture that does not move cancels, and uses it alone or the lower of the two.
+    ``sigma_motion="blocks"`` lets that difference follow the picture: one integer vector per 16 x 16 luma block and pair, found on the device
+    (``sn_yuv_block_motion``), so that a pan no longer reads as noise.
+
+    Noise model (``noise_model``, off by default): sensor noise is signal dependent, the shadows of R'G'B' carry more of it than the
+    highlights.  ``"level"`` estimates per window a noise-level function -- sigma against the luma code, 16 knots -- from the same histograms split by
+    brightness (``sn_yuv_noise_hist_bands``) and writes the network's noise plane per pixel from it (``sn_noise_map_level``), in place of one level everywhere.
+
+    ``stage`` runs on the side stream, ``level`` on the thread that runs the forward (it waits for the events of ``stage``'s copies), ``plane`` on
+    the main stream.  ``flat``: the plane is one number everywhere, a stride-0 expansion of one element."""
+
+    def __init__(self, sigma_mode: str, sigma, estimator: str = "spatial", motion=None, nlf_mode=None, nlf=None, clamp=(0.0, 50.0)) -> None:
+        self.sigma_mode, self.sigma, self.estimator, self.motion, self.nlf_mode, self.nlf, self.clamp = sigma_mode, sigma, estimator, motion, nlf_mode, nlf, clamp
+        self.flat = nlf_mode is None
+        if estimator != "spatial":                               # the statistic of the pairs: at the same place, or along the window's vectors
+            from . import io_edges as E
+            self.pair_hist = E.noise_hist_pairs_yuv if motion is None else E.noise_hist_pairs_mv_yuv
+            self.pair_band_hist = E.noise_hist_pairs_bands_yuv if motion is None else E.noise_hist_pairs_bands_mv_yuv
+
+    def prepare(self, torch, dev, dtype, fmt, h: int, w: int, tin: int, slots) -> None:
+        """Per stream shape: the clip codes, and per slot the statistics of the largest window (``slot.noise``; None unless ``sigma="auto"``)."""
+        self.torch, self.dev, self.dtype, self.fmt, self.h, self.w = torch, dev, dtype, fmt, h, w
+        self.lo, self.hi = clip_codes(fmt.bits, fmt.range)
+        self.codes = (fmt.bits, fmt.matrix, fmt.range)           # what the host arithmetic of noise.py asks of the format
+        for s in slots:
+            s.noise = _NoiseState(torch, dev, self, fmt.bits, h, w, tin) if self.sigma_mode == "auto" else None
+
+    def stage(self, st, payloads, rect, run) -> None:
+        """The histograms of the payloads just uploaded (current stream: the side stream), ahead of the ingest so that they are on the host long before
+        ``level`` asks.  The pinned twins are free: ``level`` read them on the host before the slot was handed back to the stager."""
+        if st is None:
+            return
+        from .io_edges import block_motion_yuv, noise_hist_bands_yuv, noise_hist_yuv
+        t = payloads.shape[0]
+        head, kw = (payloads, self.fmt, self.h, self.w), dict(lo=self.lo, hi=self.hi, rect=rect)
+        st.hist.launch(t, run, lambda out: noise_hist_yuv(*head, out=out, **kw))
+        along = head
+        if st.vectors is not None:
+            # the vectors of the t - 1 pairs, once per window and ahead of the histograms that follow them; their copy to the host is for stats alone
+            size = _picture_size(rect, self.h, self.w)
+            st.grid = motion_grid(*size)
+            mv, sad = st.vectors.views(t - 1, *size)
+            st.vectors.stat.launch(mv.numel(), run, lambda out: block_motion_yuv(*head, rect=rect, out_mv=mv, out_sad=sad))
+            along = head + (mv,)
+        if st.pairs is not None:                                 # the statistic of the t - 1 pairs of consecutive payloads (t >= 5: a window has 4 neighbours)
+            st.pairs.launch(t - 1, run, lambda out: self.pair_hist(*along, out=out, **kw))
+        if st.bands is not None:                                 # the same statistic by brightness band, from the same payloads, behind it
+            st.bands.launch(t, run, lambda out: noise_hist_bands_yuv(*head, out=out, **kw))
+        if st.pair_bands is not None:
+            st.pair_bands.launch(t - 1, run, lambda out: self.pair_band_hist(*along, out=out, **kw))
+
+    def level(self, st, t: int, run):
+        """(sigma, curve) of the window about to run: the noise level in 8-bit codes, and the noise-level function (16 knots, sigma of 8-bit R'G'B';
+        None without ``noise_model``).  Windows run in the order they are handed out.  What the window used is recorded only after it was obtained."""
+        if self.sigma_mode == "auto":
+            hist, = st.hist.wait(t)
+            per = [frame_sigma(hist[i], *self.codes) for i in range(t)]
+            run.window_frame_sigma.append(per)
+            if self.estimator == "spatial":
+                sigma = window_sigma(per, self.clamp)
+            else:
+                pairs, = st.pairs.wait(t - 1)
+                ps = [pair_sigma(pairs[i], *self.codes) for i in range(t - 1)]
+                spatial, temporal = frames_median(per), window_sigma_temporal(ps)
+                run.window_pair_sigma.append(ps)
+                run.window_sigma_spatial.append(spatial)
+                run.window_sigma_temporal.append(temporal)
+                if st.vectors is not None:
+                    gy, gx = st.grid
+                    flat, = st.vectors.stat.wait(2 * (t - 1) * gy * gx)
+                    run.window_pair_motion.append(motion_summary(flat.reshape(t - 1, gy, gx, 2)))
+                sigma = combine_sigma(spatial, temporal, self.estimator, self.clamp)
+        else:
+            sigma = self.sigma.at(len(run.window_sigma))
+        run.window_sigma.append(sigma)
+        if self.nlf_mode is None:
+            return sigma, None
+        if self.nlf_mode == "level":
+            bands, = st.bands.wait(t)
+            if self.estimator == "spatial":
+                curve = window_curve(bands, *self.codes, self.clamp)
+            else:
+                pair_bands, = st.pair_bands.wait(t - 1)
+                curve = window_curve_pairs(bands, pair_bands, *self.codes, self.estimator, self.clamp)
+        else:
+            curve = list(self.nlf.at(len(run.window_nlf)))
+        run.window_nlf.append(curve)
+        return sigma, curve
+
+    def plane(self, payloads, rect, hp: int, wp: int, level, run):
+        """What the network is given as its second argument (current stream: the main stream), [1, t, 1, hp, wp]: the plane of the window's curve from
+        the payloads the ingest read -- the knots are a kernel argument -- or ``sigma / 255`` everywhere."""
+        sigma, curve = level
+        t = payloads.shape[0]
+        if curve is None:
+            return self.torch.full((1, 1, 1, 1, 1), sigma / 255.0, dtype=self.dtype, device=self.dev).expand(1, t, 1, hp, wp)
+        from .io_edges import noise_map_level
+        nm = noise_map_level(payloads, self.fmt, self.h, self.w, hp, wp, [c / 255.0 for c in curve], self.dtype, self.lo, self.hi, rect=rect)
+        run.launches["nlf_map"] += 1
+        return nm
+
+    def finish(self, run, stats) -> None:
+        stats["noise_launches"] = run.launches["noise"] + run.launches["motion"]      # "motion" stays 0 without sigma_motion
+        if self.nlf_mode is not None:
+            stats["window_nlf"] = [list(c) for c in run.window_nlf]
+            stats["nlf_launches"], stats["nlf_map_launches"] = run.launches["nlf"], run.launches["nlf_map"]
+        stats["window_sigma"] = list(run.window_sigma)
+        if self.sigma_mode == "auto":
+            stats["window_frame_sigma"] = [list(p) for p in run.window_frame_sigma]
+        if self.estimator != "spatial":
+            stats["sigma_estimator"] = self.estimator
+            stats["window_sigma_spatial"], stats["window_sigma_temporal"] = list(run.window_sigma_spatial), list(run.window_sigma_temporal)
+            stats["window_pair_sigma"] = [list(p) for p in run.window_pair_sigma]
+            stats["noise_pairs_launches"] = run.launches["noise_pairs"]
+            if self.nlf_mode == "level":
+                stats["nlf_pairs_launches"] = run.launches["nlf_pairs"]
+            if self.motion is not None:
+                stats["sigma_motion"] = self.motion
+                stats["window_pair_motion"] = [list(p) for p in run.window_pair_motion]
+
+
+# ---- the method-noise report ------------------------------------------------------------------------------------------------------------
+class _ReportState:
+    """What a slot holds for the report: the ``_Stat`` of the sums of written minus input of the window's own frames (one row per frame the window
+    writes) and, under ``report_motion``, that of the sums of the written pairs along their vectors (one row per pair) and those vectors."""
+
+    def __init__(self, torch, dev, motion, h: int, w: int, tout: int) -> None:
+        from .lib import SN_DIFF_STATS, SN_DIFF_STATS_MV
+        self.sums = _Stat(torch, dev, "report", tout, [(SN_DIFF_STATS,)], torch.int64)
+        self.pair_sums = _Stat(torch, dev, "report_mv", max(tout - 1, 1), [(SN_DIFF_STATS_MV,)], torch.int64) if motion is not None else None
+        self.vectors = _Vectors(torch, dev, tout - 1, h, w) if motion is not None else None
+
+
+class Report:
+    """Method-noise report (``report``, off by default): numbers about what the run changed, per written frame -- whether input minus output is white in
+    space, independent from frame to frame, no stronger on edges than elsewhere, and as strong as the sigma the window was restored with.  Exact integer
+    sums of the two sets of payloads the window holds on the device anyway once the egress has run (``sn_yuv_diff_stats``), float64 on the host
+    (shiftnet_amd/report.py).  It changes no byte written.  What the numbers mean on real footage nobody has validated.  ``report_motion="blocks"`` adds the
+    temporal correlation of that difference along the motion of the written picture (``sn_yuv_block_motion`` on the frames written, then
+    ``sn_yuv_diff_stats_mv``): removed detail that moves with a pan reads as uncorrelated at the same place, and as correlated along its vector.
+
+    ``launch`` runs on the main stream behind the egress, ``collect`` on the thread that hands the window's frames out."""
+
+    def __init__(self, edge: float, motion, denoise: bool) -> None:
+        self.edge, self.motion, self.denoise = edge, motion, denoise
+
+    def prepare(self, torch, dev, ofmt, h: int, w: int, tout: int, slots) -> None:
+        """Per stream shape: the format written, the edge rule in its codes, and per slot the sums of the largest window (``slot.report``)."""
+        self.ofmt, self.h, self.w = ofmt, h, w
+        self.code_edge = int(round(self.edge * (1 << (ofmt.bits - 8))))
+        for s in slots:
+            s.report = _ReportState(torch, dev, self.motion, h, w, tout)
+
+    def launch(self, st, own, written, rect, run) -> None:
+        """Written minus input, the window's own n frames of both still on the device (current stream: the main stream); ``collect`` reads the sums."""
+        from .io_edges import block_motion_yuv, diff_stats_mv_yuv, diff_stats_yuv
+        n = written.shape[0]
+        head = (own, written, self.ofmt, self.h, self.w)
+        st.sums.launch(n, run, lambda sums: diff_stats_yuv(*head, rect=rect, edge=self.code_edge, out_sums=sums))
+        if st.pair_sums is not None and n >= 2:
+            # the vectors of the n - 1 pairs of the frames written (the clean picture), then d of both frames of every pair along them
+            mv, sad = st.vectors.views(n - 1, *_picture_size(rect, self.h, self.w))
+            block_motion_yuv(written, self.ofmt, self.h, self.w, rect=rect, out_mv=mv, out_sad=sad)
+            run.launches["report_motion"] += 1
+            st.pair_sums.launch(n - 1, run, lambda sums: diff_stats_mv_yuv(*head, mv, rect=rect, out_sums=sums))
+
+    def collect(self, st, n: int, run) -> None:
+        """The sums of the window being handed out.  Windows are handed out in the order they ran: ``run.window_sigma`` and ``run.window_picture`` have
+        this one's entry at ``run.collected``."""
+        sums, = st.sums.wait(n)
+        run.frame_sums += [[int(v) for v in row] for row in sums]
+        run.frame_window += [run.collected] * n
+        run.frame_sigma += [run.window_sigma[run.collected] if self.denoise else None] * n
+        if st.pair_sums is not None:                             # frame i carries the pair (i, i + 1); a window's last frame has none
+            pairs = [[int(v) for v in row] for row in st.pair_sums.wait(n - 1)[0]] if n >= 2 else []
+            run.pair_sums_mv += pairs + [None]
+            run.frame_size += [_picture_size(run.window_picture[run.collected], self.h, self.w)] * n
+
+    def finish(self, run, stats) -> None:
+        bits = self.ofmt.bits
+        stats["frame_sums"] = [list(r) for r in run.frame_sums]
+        stats["frame_report"] = frames_report(run.frame_sums, run.frame_window, run.frame_sigma, bits, self.ofmt.matrix, self.ofmt.range)
+        stats["report_summary"] = summarize(stats["frame_report"])
+        stats["report_launches"] = run.launches["report"]
+        if self.motion is not None:
+            stats["report_motion"] = self.motion
+            stats["pair_sums_mv"] = [None if r is None else list(r) for r in run.pair_sums_mv]
+            stats["frame_report_motion"] = frames_report_motion(run.pair_sums_mv, bits, run.frame_size)
+            stats["report_motion_summary"] = summarize_motion(stats["frame_report_motion"])
+            stats["report_motion_launches"] = run.launches["report_motion"] + run.launches["report_mv"]
+
+
+# ---- tiles ----------------------------------------------------------------------------------------------------------------------------
+class Tiles:
+    """Tiles (``tile``, ``tile_overlap``; off by default): the network's activations grow with the pixels of the frames it is given, and a large frame does
+    not fit the device at any useful window length.  With a tile size the forward -- and only the forward -- runs on overlapping rectangles of the
+    window's frames, one after the other, and their float32 results are added into one float32 canvas with feather weights (``sn_tile_accumulate``,
+    csrc/sn_tile.hip; the plan is windows.plan_tiles); everything before and after still works on the whole picture.  **A tiled result is not the
+    full-frame result**: every channel-attention layer pools over the map it is given, so it sees the tile, and the receptive field is cut at tile edges.
+    The feather turns a mismatch into a gradient instead of an edge; it does not remove it."""
+
+    def __init__(self, torch, net, dev, tile) -> None:
+        self.torch, self.net, self.dev, self.tile = torch, net, dev, tile      # tile: (th, tw, overlap)
+        self.plans = {}                                          # (hp, wp) -> (the plan, its weight tables on the device)
+        self.canvas = None
+
+    def prepare(self, tout: int, hp: int, wp: int) -> None:
+        """Per stream shape: the float32 canvas the tiles' results are added into, flat and sized for the full frame as the slots' tensors are.  One for
+        the restorer (main stream only): the egress of a window has consumed it before the next window's forward runs."""
+        self.canvas = self.torch.empty(tout * 3 * hp * wp, dtype=self.torch.float32, device=self.dev)
+
+    def plan(self, hp: int, wp: int):
+        """(windows.plan_tiles for a padded picture of hp x wp, its weight tables [n_y][th] and [n_x][tw] on the device), made once per size."""
+        key = (int(hp), int(wp))
+        if key not in self.plans:
+            plan = plan_tiles(key[0], key[1], *self.tile)
+            to_dev = lambda a: self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)      # noqa: E731
+            self.plans[key] = (plan, to_dev(plan.wy), to_dev(plan.wx))
+        return self.plans[key]
+
+    def forward(self, forward, n: int, hp: int, wp: int, run):
+        """The forward of one window tile by tile (current stream): ``forward(crop)`` is the network's float32 result [n, 3, th, tw] on the crop
+        (a 5-d index) of the window's tensors -> the float32 canvas [n, 3, hp, wp]; None where the window's plan is one tile, which takes the path of
+        ``tile=None``."""
+        from .io_edges import tile_accumulate
+        plan, wy, wx = self.plan(hp, wp)
+        run.window_tiles.append(list(plan.tiles))
+        if plan.single:
+            return None
+        canvas = self.canvas[:n * 3 * hp * wp].view(n, 3, hp, wp)
+        for _ in range(2):      # one range-guard check for the window's tiles (no device sync between them); a tripped guard moved the module to the
+            canvas.zero_()      # two-kernel chain: run them once more, into a canvas that starts at zero again
+            with self.net.guard_scope() as gs:
+                for i, y0 in enumerate(plan.ys):
+                    for j, x0 in enumerate(plan.xs):
+                        crop = (slice(None), slice(None), slice(None), slice(y0, y0 + plan.th), slice(x0, x0 + plan.tw))
+                        tile_accumulate(forward(crop), canvas, wy[i], wx[j], y0, x0)
+                        run.launches["tile"] += 1
+            if not gs.tripped:
+                break
+        return canvas
+
+    def finish(self, run, stats) -> None:
+        stats["tile"], stats["tile_overlap"] = self.tile[:2], self.tile[2]
+        stats["window_tiles"] = [list(w) for w in run.window_tiles]
+        stats["tile_launches"] = run.launches["tile"]

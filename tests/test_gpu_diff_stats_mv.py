@@ -270,7 +270,7 @@ def plain(clip):
     off, stats_off, vr_off = run(net, pay, report=True)
     assert not any(k in stats_off for k in NEW_KEYS)
     assert vr_off.run.launches["report_motion"] == 0 and vr_off.run.launches["report_mv"] == 0
-    assert all(s.report_mv is None and s.report_vec is None and s.report_sad is None for s in vr_off.slots)
+    assert all(s.report.pair_sums is None and s.report.vectors is None for s in vr_off.slots)
     on, stats_on, vr_on = run(net, pay, report=True, report_motion="blocks")
     return off, stats_off, on, stats_on, vr_on
 

@@ -371,11 +371,11 @@ def test_without_the_option_everything_is_todays(net, clip):
     assert stats["noise_launches"] == stats["noise_pairs_launches"] == 3 and "sigma_motion" not in stats and "window_pair_motion" not in stats
     vr = restore.VideoRestorer(net, ONE_LEN, sigma="auto", sigma_estimator="min")
     list(vr.restore(iter(clip[:6]), yuv_fmt(*FMT), H, W))
-    assert vr.run.launches["motion"] == 0 and all(s.motion is None and s.motion_sad is None for s in vr.slots)      # today's slots
+    assert vr.run.launches["motion"] == 0 and all(s.noise.vectors is None for s in vr.slots)      # today's slots
     vr = restore.VideoRestorer(net, ONE_LEN, sigma="auto", sigma_estimator="min", sigma_motion="blocks")
     list(vr.restore(iter(clip[:6]), yuv_fmt(*FMT), H, W))
     gy, gx = noise.motion_grid(H, W)
-    assert vr.run.launches["motion"] == 2 and all(s.motion.dev[0].numel() == 8 * gy * gx * 2 and s.motion_sad.numel() == 8 * gy * gx for s in vr.slots)
+    assert vr.run.launches["motion"] == 2 and all(s.noise.vectors.mv.numel() == 8 * gy * gx * 2 and s.noise.vectors.sad.numel() == 8 * gy * gx for s in vr.slots)
 
 
 # ---- the command line ----------------------------------------------------------------------------------------------------------------------

@@ -304,7 +304,7 @@ def test_a_second_restore_on_the_same_object_and_the_spatial_default(net, clip, 
     assert not any("pair" in k or "estimator" in k or k in ("window_sigma_spatial", "window_sigma_temporal") for k in stats)
     vr = restore.VideoRestorer(net, ONE_LEN, sigma="auto")
     list(vr.restore(iter(clip[:6]), yuv_fmt(*FMT), H, W))
-    assert vr.run.launches["noise_pairs"] == 0 and vr.run.launches["nlf_pairs"] == 0 and all(s.pairs is None and s.pair_bands is None for s in vr.slots)
+    assert vr.run.launches["noise_pairs"] == 0 and vr.run.launches["nlf_pairs"] == 0 and all(s.noise.pairs is None and s.noise.pair_bands is None for s in vr.slots)
     fixed, fstats = run(net, clip[:6], sigma=10.0, sigma_estimator="spatial")                 # with a number "spatial" is today's call
     assert fstats["noise_launches"] == 0 and "sigma_estimator" not in fstats
 

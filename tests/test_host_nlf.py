@@ -12,7 +12,7 @@ import pytest
 import nlf_ref as F
 import noise_ref as N
 import yuv_ref as R
-from shiftnet_amd import noise, restore
+from shiftnet_amd import noise, restore, restore_parts
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -184,12 +184,11 @@ def test_per_window_list_of_curves_running_short_names_the_window():
     assert mode == "list" and isinstance(nlf, restore.PerWindow) and nlf.at(0) == a and nlf.at(1) == b
     with pytest.raises(ValueError, match="noise_model lists 2 windows, window 2 has no entry"):
         nlf.at(2)
-    vr = restore.VideoRestorer.__new__(restore.VideoRestorer)                               # the restorer's record of what every window used
-    vr.nlf_mode, vr.nlf, vr.run = mode, nlf, restore._Run()
-    assert vr._window_curve(None, 9) == a and vr._window_curve(None, 9) == b
+    part, run = restore_parts.NoiseLevel(*restore.sigma_form(10.0), nlf_mode=mode, nlf=nlf), restore._Run()      # the restorer's record of what every window used
+    assert part.level(None, 9, run) == (10.0, a) and part.level(None, 9, run) == (10.0, b)
     with pytest.raises(ValueError, match="window 2"):
-        vr._window_curve(None, 9)
-    assert vr.run.window_nlf == [a, b]
+        part.level(None, 9, run)
+    assert run.window_nlf == [a, b]
 
 
 def test_parser_takes_flat_level_or_a_file():

@@ -12,7 +12,7 @@ import pytest
 
 import noise_ref as N
 import yuv_ref as R
-from shiftnet_amd import noise, restore
+from shiftnet_amd import noise, restore, restore_parts
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -142,12 +142,11 @@ def test_per_window_list_running_short_names_the_window():
     with pytest.raises(ValueError, match="sigma lists 2 windows, window 2 has no entry"):
         sigma.at(2)
     assert restore.sigma_form(10)[1].at(0) == restore.sigma_form(10)[1].at(99) == 10.0            # one value for the stream never runs out
-    vr = restore.VideoRestorer.__new__(restore.VideoRestorer)                                     # the restorer's record of what every window used
-    vr.sigma_mode, vr.sigma, vr.run = mode, sigma, restore._Run()
-    assert vr._window_sigma(None, 9) == 10.0 and vr._window_sigma(None, 9) == 12.5
+    part, run = restore_parts.NoiseLevel(mode, sigma), restore._Run()                             # the restorer's record of what every window used
+    assert part.level(None, 9, run) == (10.0, None) and part.level(None, 9, run) == (12.5, None)
     with pytest.raises(ValueError, match="window 2"):
-        vr._window_sigma(None, 9)
-    assert vr.run.window_sigma == [10.0, 12.5]
+        part.level(None, 9, run)
+    assert run.window_sigma == [10.0, 12.5]
 
 
 def test_sigma_list_format_round_trip_and_refusals():
