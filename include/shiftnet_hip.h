@@ -772,6 +772,41 @@ int sn_yuv_diff_stats_mv(const uint8_t* a, const uint8_t* b, const sn_yuv_fmt* f
 int sn_tile_accumulate(const float* tile, float* canvas, const float* wy, const float* wx, int T, int C, int th, int tw, int Hc, int Wc,
                        int y0, int x0, void* stream);
 
+/* ---- the data movement of the self-ensemble (csrc/sn_geo.hip; new symbols, SN_ABI_VERSION stays 20) ------------------------------------------------
+ * The video restorer and GShiftNet.forward_ensemble_fp32_out can run the network on mirrored, transposed and time-reversed copies of a window
+ * (shiftnet_amd/ensemble.py); each float32 result is mapped back and added into one float32 canvas, which the last launch divides by the number of
+ * members.  A window then costs M forwards, M the number of members.  The transposed members have another input signature (H and W swapped), so the
+ * engine keeps a plan -- and, where forwards are replayed from captured graphs, a graph -- of its own for them.  NOBODY HAS MEASURED WHAT THE ENSEMBLE GAINS
+ * ON THIS NETWORK: the +0.05 to +0.2 dB quoted for image super-resolution is a figure from the literature for other networks, not a property of
+ * Shift-Net, and no trained checkpoint ships here.  The four inference/test_*.py harnesses, where a PSNR against ground truth could be measured once
+ * somebody has a checkpoint, do not take the option yet; GShiftNet.forward_ensemble_fp32_out is there for it.
+ *   op: any OR of the four bits, 0 .. 15.  H and W are the sides of src / canvas, both [T][C][H][W]; dst / member is [T][C][H'][W'] with
+ *   (H', W') = (W, H) if SN_GEO_TRANSPOSE is set and (H, W) otherwise.  All contiguous device memory.
+ * One index map defines both kernels.  For a sample (t', c, y', x') of the transformed tensor (dst / member):
+ *     (u, v) = (y', x');   SN_GEO_FLIP_Y: u = H' - 1 - u;   SN_GEO_FLIP_X: v = W' - 1 - v;
+ *     (y, x) = (v, u) with SN_GEO_TRANSPOSE, else (u, v);   t = T - 1 - t' with SN_GEO_REVERSE_T, else t'
+ *   sn_geo_transform :  dst[t'][c][y'][x'] = src[t][c][y][x] -- pure data movement of esz-byte elements, esz = 2 (bf16 and fp16 alike) or 4
+ *   sn_geo_accumulate:  a = init ? member[t'][c][y'][x'] : canvas[t][c][y][x] + member[t'][c][y'][x']     (one float32 sum, rounded)
+ *                       canvas[t][c][y][x] = a * scale                                                    (one float32 product, rounded)
+ *     No FMA; with init != 0 the canvas is not read, so whatever it held -- NaN included -- does not reach the result.
+ * The map is a bijection, so every sample of the tensor written is written exactly once; nothing outside the two tensors is read or written.  The
+ * inverse of an op with the transpose bit is the op with its two flip bits swapped (5 and 6 are each other's inverses, 4 and 7 their own); without
+ * it every op is its own inverse.  So sn_geo_accumulate(member = sn_geo_transform(a, op), op, init = 1, scale = 1) gives a back.
+ * Without SN_GEO_TRANSPOSE a thread moves 16 bytes of a row where both addresses are 16-byte aligned (it tests the addresses itself; the mirrored
+ * chunk of SN_GEO_FLIP_X is aligned only when W * esz is a multiple of 16) and goes element by element otherwise; with it a workgroup moves a
+ * 64 x 64 tile through LDS so that reads and writes both run along rows.  Every path gives the same bits.  No atomics: the launches of a window
+ * run one after the other on one stream.  T * C is NOT limited by the grid: the kernels loop over the planes beyond 65535.
+ * (tests/geo_ref.py restates both in numpy; the kernels equal it bit for bit.)
+ * SN_EINVAL before anything is launched: a null pointer; a pointer that is not esz-byte aligned (4 for sn_geo_accumulate); esz not 2 or 4; op outside
+ * 0 .. 15; T, C, H or W < 1; T * C * H * W * esz beyond 2^63 - 1 (the kernels index with 64 bits); a scale that is not finite; src / dst
+ * (member / canvas) byte ranges that overlap. */
+#define SN_GEO_FLIP_X 1      /* mirror the columns */
+#define SN_GEO_FLIP_Y 2      /* mirror the rows */
+#define SN_GEO_TRANSPOSE 4   /* swap rows and columns (applied before the flips) */
+#define SN_GEO_REVERSE_T 8   /* frame t' is frame T - 1 - t' */
+int sn_geo_transform(const void* src, void* dst, int esz, int op, int T, int C, int H, int W, void* stream);
+int sn_geo_accumulate(const float* member, float* canvas, int op, int init, float scale, int T, int C, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,8 @@ Contract mirrored:
   * ``forward(x[, noise_map], k1=None, k2=None, k3=None)``: ``x:[B,T,3,H,W]`` in the parameters' dtype, only
     ``x[0]`` is used, returns ``[T-P-F, 3, H, W]``; ``T <= P+F`` gives an empty tensor;
   * ``load_state_dict(torch.load(p)['params'])`` strict: keys/shapes/aliases come from ``spec.param_table``.
-Beyond the upstream API: ``forward_clips(x[, noise_map])`` / ``forward_clips_fp32_out`` restore all B clips of ``x`` in one set of launches.
+Beyond the upstream API: ``forward_clips(x[, noise_map])`` / ``forward_clips_fp32_out`` restore all B clips of ``x`` in one set of launches;
+``forward_ensemble_fp32_out`` averages the results on mirrored, transposed and time-reversed copies of the window (shiftnet_amd/ensemble.py).
 There is no CPU path: calling ``forward`` without a HIP device and the built library raises.
 """
 from __future__ import annotations
@@ -148,6 +149,30 @@ class GShiftNetBase(nn.Module):
         Not part of the upstream API."""
         return self._run_clips(x, noise_map, torch.float32, shortcut)
 
+    def forward_ensemble_fp32_out(self, x, noise_map=None, shortcut=None, ensemble=8, time=False):
+        """Test-time self-ensemble (shiftnet_amd/ensemble.py): ``x:[1,T,3,H,W]`` -> ``[T-P-F, 3, H, W]`` float32, the mean of ``forward_fp32_out`` over
+        ``ensemble`` (None, 1, 2, 4 or 8) mirrored / transposed copies of the window and, with ``time``, as many again reversed in time, each result
+        mapped back: the sequential float32 sum in the order of ``ensemble.members(ensemble, time)``, divided by their number M.  **M forwards**; the
+        transposed members have another input signature, so the engine keeps a plan of its own for them.  ``noise_map``: a number, a stride-0
+        expansion, or a plane ``[1,T,1,H,W]``, which is transformed with the frames.  ``ensemble in (None, 1)`` without ``time`` IS
+        ``forward_fp32_out``: the same launches.  **Nobody has measured what this gains on Shift-Net**; the figures quoted for self-ensembles are from
+        the literature for other networks.  Not part of the upstream API; not available on a temporally split module."""
+        return self._run_ensemble(x, noise_map, shortcut, ensemble, time)
+
+    def _run_ensemble(self, x, noise_map, shortcut, ensemble, time):
+        from .ensemble import Buffers, forward_ensemble, members
+        ops = members(ensemble, bool(time))
+        if len(ops) == 1:
+            return self._run(x, noise_map, torch.float32, shortcut)
+        if getattr(self, "_split", None) is not None:
+            raise ValueError("forward_ensemble_fp32_out cannot be combined with a temporal split (set_temporal_split)")
+        dt = next(self.parameters()).dtype
+        if isinstance(x, torch.Tensor) and x.dtype != dt:
+            raise RuntimeError(f"Input type ({x.dtype}) and weight type ({dt}) should be the same")
+        if getattr(self, "_ensemble_buffers", None) is None:
+            self._ensemble_buffers = Buffers()                  # reused from call to call: a shape that has been seen allocates only the result
+        return forward_ensemble(self, x, noise_map, shortcut, ops, buffers=self._ensemble_buffers)
+
     def _run_clips(self, x, noise_map, out_dtype, shortcut):
         if not isinstance(x, torch.Tensor) or x.dim() != 5:
             raise ValueError(f"forward_clips expects x:[B,T,C,H,W], got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
@@ -193,6 +218,9 @@ def _make(variant: str):
 
             def forward_clips_fp32_out(self, x, shortcut=None):
                 return self._run_clips(x, None, torch.float32, shortcut)
+
+            def forward_ensemble_fp32_out(self, x, shortcut=None, ensemble=8, time=False):
+                return self._run_ensemble(x, None, shortcut, ensemble, time)
 
     GShiftNet.variant = variant
     GShiftNet.__qualname__ = "GShiftNet"

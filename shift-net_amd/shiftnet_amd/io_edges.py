@@ -24,6 +24,8 @@ the statistics of the same payloads' luma (csrc/sn_yuv_stats.hip), each for one 
                temporal correlation;
 ``tile_accumulate``: one tile's float32 result added into the window's float32 canvas with its feather weights (csrc/sn_tile.hip), for the tiled
                restorer (``VideoRestorer(tile=...)``);
+``geo_transform`` / ``geo_accumulate``: a tensor mirrored, transposed and reversed in time, and a float32 result mapped back and added into a float32
+               canvas (csrc/sn_geo.hip), for the self-ensemble (shiftnet_amd/ensemble.py);
 ``rect=(x0, y0, w, h)``, where a function takes it (all but ``thumb_yuv`` and ``rowcol_sums_yuv``), restricts it to that picture of the stream, with
                the result of the cropped stream;
 ``egress_u8``  == the per-frame ``clamp(0,1) * 255`` -> skimage PSNR(data_range=255) against the uint8 ground truth
@@ -425,4 +427,53 @@ def tile_accumulate(tile: torch.Tensor, canvas: torch.Tensor, wy: torch.Tensor, 
     with torch.cuda.device(tile.device):
         L.check(L.load().sn_tile_accumulate(tile.data_ptr(), canvas.data_ptr(), wy.data_ptr(), wx.data_ptr(), T, C, th, tw, Hc, Wc, y0, x0,
                                             torch.cuda.current_stream(tile.device).cuda_stream), "sn_tile_accumulate")
+    return canvas
+
+
+def geo_out_shape(shape, op: int) -> Tuple[int, int, int, int]:
+    """The shape of ``geo_transform(a, op)`` for ``a`` of ``shape`` [T, C, H, W]: the two sides swapped under ``SN_GEO_TRANSPOSE``."""
+    T, C, H, W = (int(v) for v in shape)
+    return (T, C, W, H) if op & L.SN_GEO_TRANSPOSE else (T, C, H, W)
+
+
+def _geo_args(what: str, a: torch.Tensor, b: torch.Tensor, op: int):
+    """a: the plain tensor [T, C, H, W], b: the transformed one; both contiguous, of one dtype, on one HIP device."""
+    if not (isinstance(op, int) and not isinstance(op, bool) and 0 <= op <= 15):
+        raise ValueError(f"{what}: op must be an int of the four SN_GEO_* bits, 0 .. 15, got {op!r}")
+    for t in (a, b):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 4 and t.is_contiguous() and t.device == a.device and t.dtype == a.dtype):
+            raise ValueError(f"{what}: both tensors must be contiguous, of 4 dimensions, of one dtype and on one HIP device")
+    if min(a.shape) < 1 or tuple(b.shape) != geo_out_shape(a.shape, op):
+        raise ValueError(f"{what}: op {op} takes {tuple(a.shape)} to {geo_out_shape(a.shape, op)} (no empty side), got {tuple(b.shape)}")
+    return tuple(int(v) for v in a.shape)
+
+
+def geo_transform(src: torch.Tensor, op: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src: [T, C, H, W] on a HIP device, contiguous, of a 2- or 4-byte dtype -> the tensor mirrored (``SN_GEO_FLIP_X`` columns, ``SN_GEO_FLIP_Y`` rows),
+    transposed (``SN_GEO_TRANSPOSE``, before the flips: [T, C, W, H]) and reversed in time (``SN_GEO_REVERSE_T``) as ``op`` says (include/shiftnet_hip.h:
+    sn_geo_transform).  Pure data movement.  ``out``: where to write it (contiguous, of the result's shape and src's dtype, not overlapping src)."""
+    if isinstance(src, torch.Tensor) and src.dim() == 4 and out is None:
+        out = torch.empty(geo_out_shape(src.shape, op), dtype=src.dtype, device=src.device)
+    T, C, H, W = _geo_args("geo_transform", src, out, op)
+    if src.element_size() not in (2, 4):
+        raise ValueError(f"geo_transform: elements of 2 or 4 bytes, got {src.dtype}")
+    with torch.cuda.device(src.device):
+        L.check(L.load().sn_geo_transform(src.data_ptr(), out.data_ptr(), src.element_size(), op, T, C, H, W,
+                                          torch.cuda.current_stream(src.device).cuda_stream), "sn_geo_transform")
+    return out
+
+
+def geo_accumulate(member: torch.Tensor, canvas: torch.Tensor, op: int, init: bool, scale: float = 1.0) -> torch.Tensor:
+    """member: float32, ``geo_out_shape(canvas.shape, op)``, a result computed on ``geo_transform(., op)`` of the input; canvas: [T, C, H, W] float32 ->
+    ``canvas``, every sample of which has become ``(canvas + member mapped back) * scale`` -- or ``member mapped back * scale`` with ``init``, which
+    does not read the canvas -- the sum and the product each rounded to float32 on its own (include/shiftnet_hip.h: sn_geo_accumulate)."""
+    T, C, H, W = _geo_args("geo_accumulate", canvas, member, op)
+    if canvas.dtype != torch.float32:
+        raise ValueError(f"geo_accumulate: float32 tensors, got {canvas.dtype}")
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError(f"geo_accumulate: scale must be finite, got {scale!r}")
+    with torch.cuda.device(canvas.device):
+        L.check(L.load().sn_geo_accumulate(member.data_ptr(), canvas.data_ptr(), op, 1 if init else 0, scale, T, C, H, W,
+                                           torch.cuda.current_stream(canvas.device).cuda_stream), "sn_geo_accumulate")
     return canvas

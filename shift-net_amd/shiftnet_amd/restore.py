@@ -30,8 +30,9 @@ result's, separately for luma and chroma -- the fallback when the restoration is
 mid-grey, to see whether detail leaves with the noise.  Both happen in the egress, in the code domain, from the payloads the window has uploaded
 anyway (``sn_egress_yuv_mix``): amount 0 is the input byte for byte.  The blend is linear in the codes, not perceptual.
 
-Noise level (``sigma``, ``noise_model``; denoise variants), method-noise report (``report``) and tiles (``tile``): each is a part of its own, described at
-its class in shiftnet_amd/restore_parts.py (``NoiseLevel``, ``Report``, ``Tiles``); the restorer holds each or None and calls it by name.
+Noise level (``sigma``, ``noise_model``; denoise variants), method-noise report (``report``), tiles (``tile``) and the self-ensemble (``ensemble``): each
+is a part of its own, described at its class in shiftnet_amd/restore_parts.py (``NoiseLevel``, ``Report``, ``Tiles``, ``Ensemble``); the restorer holds
+each or None and calls it by name.
 """
 from __future__ import annotations
 
@@ -43,10 +44,10 @@ from typing import Iterable, Iterator, List, Sequence, Tuple
 import numpy as np
 
 from .restore_cli import amount_arg, main, make_parser, picture_arg, sigma_arg, tile_arg  # noqa: F401 -- the command line (restore_cli.py), reached through this module
-from .restore_parts import NoiseLevel, Report, Tiles, _Stat
+from .restore_parts import Ensemble, NoiseLevel, Report, Tiles, _Stat
 from .windows import (DEFAULT_TILE_OVERLAP, DITHERS, FUTURE, PAST, PerWindow, _Frames, _SceneFrames, _Thread, amount_form, noise_model_form, pad_multiple,  # noqa: F401
                       padded_size, picture_form, plan_output, plan_scene_windows, plan_windows, reflect_index, report_form, report_motion_form, scene_cuts_form,
-                      sigma_estimator_form, sigma_form, sigma_motion_form, tile_form, plan_tiles, window_indices)
+                      sigma_estimator_form, sigma_form, sigma_motion_form, tile_form, plan_tiles, window_indices, ensemble_form)
 
 VARIANTS = {"deblur": "gshift_deblur1", "deblur_small": "gshift_deblur2", "denoise": "gshift_denoise1", "denoise_small": "gshift_denoise2"}
 
@@ -90,7 +91,8 @@ class _Run:
         self.window_pair_motion: List = []                        # sigma_motion: per window, per pair, noise.motion_summary's triple
         self.launches = {"noise": 0, "nlf": 0, "nlf_map": 0, "picture": 0, "thumb": 0, "noise_pairs": 0, "nlf_pairs": 0, "report": 0, "motion": 0,
                          "report_motion": 0, "report_mv": 0,      # report_motion: the block matcher on the written frames, the sums along its vectors
-                         "tile": 0}                               # tile: the tiles added into the canvas
+                         "tile": 0,                               # tile: the tiles added into the canvas
+                         "geo_transform": 0, "geo_accumulate": 0} # ensemble: the members' inputs made, their results added into the canvas
         self.window_tiles: List = []                              # tile: per window, the (y0, x0, th, tw) of its tiles in the order they ran
         self.frame_sums: List = []                                # report: the 16 sums of every frame handed out, the window it came from, that window's sigma
         self.frame_window: List[int] = []
@@ -290,14 +292,32 @@ class VideoRestorer:
     32 samples per side; nobody has tuned it, and no trained checkpoint ships, so nobody has looked at a seam on real footage.**  Tiles of one window run
     one at a time (not as one ``forward_clips`` batch), have one size, and do not cut the window in time.  ``stats`` then also has ``tile`` (th, tw),
     ``tile_overlap``, ``window_tiles`` (per window the list of (y0, x0, th, tw) in the order run) and ``tile_launches`` (the ``sn_tile_accumulate``
-    launches)."""
+    launches).
+    ensemble: None or 1 -- one forward per window, today's launches, bytes, buffers and stats keys; 2, 4 or 8 -- a test-time self-ensemble
+    (shiftnet_amd/ensemble.py): the forward of every window runs on that many copies of the window's tensors -- the window itself, its columns
+    mirrored, its rows mirrored and both, and at 8 the transposes of those four -- every float32 result is mapped back, and their mean is what the egress,
+    the mix and the report read.  ``ensemble_time=True`` doubles the members: the same copies of the window reversed in time (a legal window, because
+    it has as many past as future frames).  The network is not equivariant under any of these -- its grouped spatial shifts point in fixed directions
+    and its temporal shift tells past from future -- so every member gives another answer.  **A window costs M forwards**, M the number of members (2
+    to 16).  The copies are made by ``sn_geo_transform`` into buffers that are reused (the frames, their float32 twin and, under
+    ``noise_model``, the noise plane, which is transformed with the frames; a flat sigma is the same for every member and copies nothing);
+    ``sn_geo_accumulate`` adds each result into one float32 canvas and the last launch multiplies by 1 / M, which is exact: the result is the sequential
+    float32 sum in the order of ``stats["ensemble_members"]``, divided by M -- ``net.forward_ensemble_fp32_out`` on the window, bit for bit.  The
+    transposed members have another input signature, hp and wp swapped, so the engine keeps a plan of its own for them, and the first window pays
+    for building it.  The members of a window share one range-guard check and are run once more if it tripped.  ``ensemble`` or ``ensemble_time`` together
+    with ``tile`` is a ValueError: the tiles of a transposed member need a rule for their own sides.  **Nobody has measured what the ensemble gains on this
+    network**: the +0.05 to +0.2 dB quoted for image super-resolution is a figure from the literature for other networks, not a property of Shift-Net,
+    and no trained checkpoint ships here.  The ``inference/test_*.py`` harnesses, where a PSNR against ground truth could be measured once somebody
+    has a checkpoint, do not take the option yet; ``GShiftNet.forward_ensemble_fp32_out`` is there for it.  ``stats`` then also has ``ensemble``,
+    ``ensemble_time``, ``ensemble_members`` (the ops in the order run: bit 1 mirrors the columns, 2 the rows, 4 transposes, 8 reverses time) and
+    ``ensemble_launches`` (``{"transform": the sn_geo_transform launches, "accumulate": the sn_geo_accumulate launches}``)."""
 
     def __init__(self, net, one_len: int, sigma=None, pipeline: bool = True, scene_cuts=None,
                  cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0),
                  picture=None, bar_level: float = 1.0, out_format=None, dither=None, dither_seed: int = 0, noise_model=None,
                  amount=None, view=None, removed_gain: float = 1.0, sigma_estimator: str = "spatial", report: bool = False,
                  report_edge: float = 16.0, sigma_motion=None, report_motion=None, tile=None,
-                 tile_overlap: int = DEFAULT_TILE_OVERLAP) -> None:
+                 tile_overlap: int = DEFAULT_TILE_OVERLAP, ensemble=None, ensemble_time: bool = False) -> None:
         import torch
         from .lib import YuvFmt
         from .noise import check_clamp
@@ -315,6 +335,7 @@ class VideoRestorer:
         self.cut_threshold, self.cut_ratio = float(cut_threshold), float(cut_ratio)
         self.V = net.V
         self.tile = tile_form(tile, tile_overlap, self.V.topo)    # None (the code path without any of it) or (th, tw, overlap)
+        self.ensemble = ensemble_form(ensemble, ensemble_time, self.tile)      # None (the code path without any of it) or (ensemble, time, the ops)
         if self.V.denoise and sigma is None:
             raise ValueError("sigma is required by the denoise variants (the noise level of the footage, in 8-bit code values)")
         self.sigma_clamp = check_clamp(sigma_clamp)
@@ -345,6 +366,8 @@ class VideoRestorer:
                                 self.sigma_clamp) if self.V.denoise else None
         self.report_part = Report(self.report_edge, self.report_motion, self.V.denoise) if self.report else None
         self.tiles = Tiles(torch, net, self.dev, self.tile) if self.tile is not None else None
+        self.ensemble_part = Ensemble(torch, net, self.dev, self.dtype, self.ensemble,
+                                      plane=self.noise is not None and not self.noise.flat) if self.ensemble is not None else None
         self._shape = None
         self._reset()
 
@@ -390,6 +413,8 @@ class VideoRestorer:
             self.report_part.prepare(torch, dev, ofmt, h, w, tout, self.slots)
         if self.tiles is not None:
             self.tiles.prepare(tout, self.hp, self.wp)
+        if self.ensemble_part is not None:
+            self.ensemble_part.prepare(tin, tout, self.hp, self.wp)
 
     def _size(self, rect) -> Tuple[int, int, int, int]:
         """(h, w, padded h, padded w) of what a window with picture ``rect`` feeds the network."""
@@ -500,7 +525,9 @@ class VideoRestorer:
             nm = self.noise.plane(slot.dev_in[:t], rect, hp, wp, level, run) if self.noise is not None else None
             out = self.tiles.forward(lambda crop: self._forward(x, x32, nm, crop), n, hp, wp, run) if self.tiles is not None else None
             tiled = out is not None                              # a window whose plan is one tile takes the path of tile=None
-            if not tiled:
+            if self.ensemble_part is not None:                   # never with tiles: the members' mean in place of the one forward
+                out = self.ensemble_part.forward(x, x32, nm, n, hp, wp, run)
+            elif not tiled:
                 out = self._forward(x, x32, nm)
             e1.record(main)
             run.timers.append((e0, e1))
@@ -541,7 +568,7 @@ class VideoRestorer:
         stats["picture_launches"] = run.launches["picture"]
         if self.picture_mode == "auto":
             stats["picture_wait_ms"] = list(run.picture_wait_ms)
-        for part in (self.noise, self.report_part, self.tiles):
+        for part in (self.noise, self.report_part, self.tiles, self.ensemble_part):
             if part is not None:
                 part.finish(run, stats)
         src = run.src

@@ -147,6 +147,14 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--tile_overlap", type=int, default=None, metavar="V",
                     help="--tile only: consecutive tiles overlap by at least V samples, 0 <= V <= half the tile's shorter side; default 32, taken from "
                          "upstream's quadrants (which crop 17 to 32 samples per side) and never tuned")
+    ap.add_argument("--ensemble", type=int, choices=(1, 2, 4, 8), default=1,
+                    help="test-time self-ensemble: run the network on that many copies of every window -- the window, its columns mirrored, its rows "
+                         "mirrored and both, at 8 also their transposes -- map every result back and write their mean.  A WINDOW COSTS THAT MANY "
+                         "FORWARDS.  The transposed copies have another input signature: the engine builds a plan of its own for them in the first "
+                         "window.  NOBODY HAS MEASURED WHAT THIS GAINS ON SHIFT-NET: the +0.05 to +0.2 dB quoted for image super-resolution is a figure "
+                         "from the literature for other networks, and no trained checkpoint ships here.  Not with --tile; default 1: one forward")
+    ap.add_argument("--ensemble_time", action="store_true",
+                    help="double the members of --ensemble: the same copies of the window reversed in time (twice the forwards again)")
     ap.add_argument("--cuts_out", default=None, metavar="FILE", help="write the scene starts that were used, in the format --scene_cuts FILE reads")
     ap.add_argument("input", metavar="IN", help="Y4M file, or - for stdin")
     ap.add_argument("output", metavar="OUT", help="Y4M file, or - for stdout")
@@ -191,7 +199,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     from . import report as rep
     from .spec import VARIANTS as SPECS
     from .restore import VARIANTS
-    from .windows import DEFAULT_TILE_OVERLAP, amount_form, report_form, report_motion_form, tile_form
+    from .windows import DEFAULT_TILE_OVERLAP, amount_form, ensemble_form, report_form, report_motion_form, tile_form
     from .y4m import Y4MReader, Y4MWriter, output_header
     ap = make_parser()
     a = ap.parse_args(argv)
@@ -214,9 +222,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--tile_overlap needs --tile")
     tile_overlap = DEFAULT_TILE_OVERLAP if a.tile_overlap is None else a.tile_overlap
     try:
-        tile_form(a.tile, tile_overlap, SPECS[VARIANTS[a.variant]].topo)
+        tile = tile_form(a.tile, tile_overlap, SPECS[VARIANTS[a.variant]].topo)
     except ValueError as e:
         ap.error(f"--tile / --tile_overlap: {e}")
+    try:
+        ensemble_form(a.ensemble, a.ensemble_time, tile)
+    except ValueError as e:
+        ap.error(f"--ensemble / --ensemble_time: {e}")
     if "denoise" in a.variant and a.sigma is None:
         ap.error("--sigma is required by the denoise variants")
     if a.sigma_estimator != "spatial" and a.sigma != "auto":      # before the file of a --sigma FILE is opened
@@ -271,7 +283,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                            dither=None if a.dither == "none" else a.dither, dither_seed=a.dither_seed, noise_model=noise_model,
                            amount=a.amount, view=view, removed_gain=a.removed_gain, sigma_estimator=a.sigma_estimator,
                            report=a.report is not None, report_edge=a.report_edge, sigma_motion=None if a.sigma_motion == "none" else a.sigma_motion,
-                           report_motion=report_motion, tile=a.tile, tile_overlap=tile_overlap)
+                           report_motion=report_motion, tile=a.tile, tile_overlap=tile_overlap, ensemble=a.ensemble,
+                           ensemble_time=a.ensemble_time)
+        if vr.ensemble is not None:
+            log(f"ensemble: {len(vr.ensemble[2])} forwards per window (ops {vr.ensemble[2]}); what it gains on this network nobody has measured")
         if vr.tile is not None:
             log("tile: %d x %d, overlap %d (a tiled result is not the full-frame result: channel attention sees the tile)" % vr.tile)
         if a.out_format is not None or a.dither != "none":

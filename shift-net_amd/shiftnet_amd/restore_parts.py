@@ -1,5 +1,6 @@
 """The optional features of the video restorer (shiftnet_amd/restore.py), one class each: ``NoiseLevel`` (what a window's noise level is and how it is
-obtained), ``Report`` (the method-noise report) and ``Tiles`` (the forward in overlapping tiles).  A part owns everything of its feature -- its state per
+obtained), ``Report`` (the method-noise report), ``Tiles`` (the forward in overlapping tiles) and ``Ensemble`` (the forward on mirrored, transposed
+and time-reversed copies).  A part owns everything of its feature -- its state per
 slot on the device and in pinned memory, its launches, its host arithmetic and its keys of ``stats`` -- and writes into the one record of a
 ``restore()`` (``restore._Run``) that ``VideoRestorer`` hands it; ``VideoRestorer`` holds each part or None and calls it by name.  The parts are given
 parsed values (windows.py's ``*_form`` functions) and validate nothing.  ``_Stat`` and ``_Vectors`` are what they share."""
@@ -328,3 +329,41 @@ class Tiles:
         stats["tile"], stats["tile_overlap"] = self.tile[:2], self.tile[2]
         stats["window_tiles"] = [list(w) for w in run.window_tiles]
         stats["tile_launches"] = run.launches["tile"]
+
+
+# ---- the self-ensemble ----------------------------------------------------------------------------------------------------------------
+class Ensemble:
+    """Self-ensemble (``ensemble``, ``ensemble_time``; off by default): the forward -- and only the forward -- of every window runs on M copies of the
+    window's tensors, mirrored, transposed and reversed in time (shiftnet_amd/ensemble.py); every float32 result is mapped back and added into one
+    float32 canvas, which the last launch divides by M (``sn_geo_transform``, ``sn_geo_accumulate``; csrc/sn_geo.hip).  Everything before and after
+    works as without it.  **A window costs M forwards.  Nobody has measured what the ensemble gains on this network.**"""
+
+    def __init__(self, torch, net, dev, dtype, form, plane: bool) -> None:
+        from .ensemble import Buffers
+        self.torch, self.net, self.dev, self.dtype = torch, net, dev, dtype
+        self.ensemble, self.time, self.members = form            # windows.ensemble_form's
+        self.plane = plane                                       # the noise level is a plane (noise_model): it is transformed with the frames
+        self.buffers = Buffers()
+        self.canvas = None
+
+    def prepare(self, tin: int, tout: int, hp: int, wp: int) -> None:
+        """Per stream shape: the members' input buffers and the float32 canvas, flat and sized for the full frame as the slots' tensors are (a
+        ``picture`` only makes the views smaller, at the same addresses).  One set for the restorer (main stream only)."""
+        torch, px = self.torch, hp * wp
+        self.buffers.reserve(torch, "x", tin * 3 * px, self.dtype, self.dev)
+        if self.dtype != torch.float32:
+            self.buffers.reserve(torch, "shortcut", tin * 3 * px, torch.float32, self.dev)
+        if self.plane:
+            self.buffers.reserve(torch, "plane", tin * px, self.dtype, self.dev)
+        self.canvas = torch.empty(tout * 3 * px, dtype=torch.float32, device=self.dev)
+
+    def forward(self, x, x32, nm, n: int, hp: int, wp: int, run):
+        """The forward of one window member by member (current stream): x [1, t, 3, hp, wp], x32 its float32 twin or None, nm the noise plane or
+        level or None -> the float32 canvas [n, 3, hp, wp]."""
+        from .ensemble import forward_ensemble
+        canvas = self.canvas[:n * 3 * hp * wp].view(n, 3, hp, wp)
+        return forward_ensemble(self.net, x, nm, x32, self.members, out=canvas, buffers=self.buffers, counts=run.launches)
+
+    def finish(self, run, stats) -> None:
+        stats["ensemble"], stats["ensemble_time"], stats["ensemble_members"] = self.ensemble, self.time, list(self.members)
+        stats["ensemble_launches"] = {"transform": run.launches["geo_transform"], "accumulate": run.launches["geo_accumulate"]}

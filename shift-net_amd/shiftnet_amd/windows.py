@@ -317,6 +317,24 @@ def report_motion_form(report_motion=None, report=False):
     return report_motion
 
 
+def ensemble_form(ensemble=None, ensemble_time=False, tile=None):
+    """-> None (no ensemble: the code path without any of it) or (ensemble, time, the members' ops in the order they run).  ``ensemble``: None, 1, 2, 4
+    or 8 (ensemble.members); ``ensemble_time``: a bool.  One member -- None or 1 without time -- is no ensemble.  ``tile``: the restorer's parsed tile;
+    an ensemble together with tiles is a ValueError (a tile of a transposed member needs a rule for its own sides: a follow-up).  ValueError for
+    anything else."""
+    from .ensemble import members
+    if not isinstance(ensemble_time, (bool, np.bool_)):
+        raise ValueError(f"ensemble_time must be a bool, got {ensemble_time!r}")
+    if isinstance(ensemble, np.integer):
+        ensemble = int(ensemble)
+    ops = members(ensemble, bool(ensemble_time))
+    if len(ops) == 1:
+        return None
+    if tile is not None:
+        raise ValueError("ensemble / ensemble_time cannot be combined with tile: the tiles of a transposed member need a rule of their own")
+    return (1 if ensemble is None else ensemble), bool(ensemble_time), ops
+
+
 def picture_form(picture):
     """None -> ("full", None); "auto" -> ("auto", None); four numbers -> ("fixed", the tuple); anything whose elements are sequences or None ->
     ("list", the list).  The rectangles are judged where the stream is known (picture.check_pictures)."""
