@@ -807,6 +807,28 @@ int sn_tile_accumulate(const float* tile, float* canvas, const float* wy, const 
 int sn_geo_transform(const void* src, void* dst, int esz, int op, int T, int C, int H, int W, void* stream);
 int sn_geo_accumulate(const float* member, float* canvas, int op, int init, float scale, int T, int C, int H, int W, void* stream);
 
+/* ---- the cross-fade of overlapping windows (csrc/sn_time.hip; a new symbol, SN_ABI_VERSION stays 20) ------------------------------------------------
+ * The video restorer can let consecutive windows of a scene overlap by V frames (VideoRestorer(window_overlap=V)); the V shared frames then have two
+ * float32 answers, the older window's last V frames and the newer window's first V, which are cross-faded with a linear ramp in time.
+ *   prev, cur:[V][C][Hp][Wp] f32, w_prev, w_cur:[V] f32, sq: NULL or [V][C] u64, all contiguous device memory; h x w is the picture inside the padded
+ *   Hp x Wp plane.  prev is read only, cur is updated in place.  For every j < V, c < C, y < Hp, x < Wp:
+ *     cur[j][c][y][x] = (w_prev[j] * prev[j][c][y][x]) + (w_cur[j] * cur[j][c][y][x])      (two products and one sum, each rounded)
+ * Three float32 operations, each rounded to nearest even on its own: no FMA, and the same bits for every launch geometry and for the 16-byte and the
+ * element-wise path of the kernel (it moves 4 consecutive samples as one float4 where the addresses in both tensors allow, which it tests itself:
+ * Hp and Wp are arbitrary).  The weights are not looked at: any float32 contents are legal.
+ * With sq the kernel also measures how far the two answers are apart, from the values BEFORE the blend and over the picture only (y < h and x < w):
+ *     d = prev - cur                                            (one float32 difference, rounded)
+ *     q = rint(min(max(d, -8), 8) * 65536)                      (round half to even; an integer, |q| <= 2^19; a NaN d counts as -8)
+ *     sq[j][c] += q * q                                         (unsigned 64-bit integers)
+ * sq is ADDED to, never overwritten: the caller zeroes it.  Integer sums are exact and do not depend on the launch geometry; a workgroup adds its sum
+ * with one 64-bit vector atomic.  h * w <= 2^25 keeps a plane's sum below 2^63.  A difference beyond +-8 counts as 8: the clamp bounds the sum, and
+ * the restorer's values are pictures in [0, 1] give or take an overshoot.  With sq == NULL an instantiation without any of the statistic runs.
+ * (tests/time_ref.py restates both in numpy and Python integers; the kernel equals them bit for bit.)
+ * SN_EINVAL before anything is launched: a null prev, cur, w_prev or w_cur; one of them not 4-byte aligned, or sq not 8-byte aligned; V, C, Hp or
+ * Wp < 1; h outside 1 .. Hp or w outside 1 .. Wp; V * C > 65535 (the grid's z); with sq, h * w > 2^25. */
+int sn_time_crossfade(const float* prev, float* cur, const float* w_prev, const float* w_cur, unsigned long long* sq /* NULL: no statistic */,
+                      int V, int C, int Hp, int Wp, int h, int w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,8 @@ the statistics of the same payloads' luma (csrc/sn_yuv_stats.hip), each for one 
                restorer (``VideoRestorer(tile=...)``);
 ``geo_transform`` / ``geo_accumulate``: a tensor mirrored, transposed and reversed in time, and a float32 result mapped back and added into a float32
                canvas (csrc/sn_geo.hip), for the self-ensemble (shiftnet_amd/ensemble.py);
+``time_crossfade``: the frames two overlapping windows share, cross-faded in place, and the exact sum of squares of the two answers' difference
+               (csrc/sn_time.hip), for ``VideoRestorer(window_overlap=...)``;
 ``rect=(x0, y0, w, h)``, where a function takes it (all but ``thumb_yuv`` and ``rowcol_sums_yuv``), restricts it to that picture of the stream, with
                the result of the cropped stream;
 ``egress_u8``  == the per-frame ``clamp(0,1) * 255`` -> skimage PSNR(data_range=255) against the uint8 ground truth
@@ -428,6 +430,34 @@ def tile_accumulate(tile: torch.Tensor, canvas: torch.Tensor, wy: torch.Tensor, 
         L.check(L.load().sn_tile_accumulate(tile.data_ptr(), canvas.data_ptr(), wy.data_ptr(), wx.data_ptr(), T, C, th, tw, Hc, Wc, y0, x0,
                                             torch.cuda.current_stream(tile.device).cuda_stream), "sn_tile_accumulate")
     return canvas
+
+
+def time_crossfade(prev: torch.Tensor, cur: torch.Tensor, w_prev: torch.Tensor, w_cur: torch.Tensor, h: int, w: int,
+                   sq: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """prev: [V, C, Hp, Wp] float32 on a HIP device, the last V frames of the older window's result; cur: the same shape, the first V frames of the
+    newer window's; w_prev, w_cur: [V] float32, the weights per shared frame (windows.overlap_weights) -> ``cur``, every sample of which has become
+    ``(w_prev[j] * prev) + (w_cur[j] * cur)``, the two products and the sum rounded to float32 on their own (include/shiftnet_hip.h:
+    sn_time_crossfade).  ``prev`` is not written.  ``sq``: None, or [V, C] int64 that the kernel ADDS to (the caller zeroes it): per plane the sum over
+    the h x w picture of ``rint(clamp(prev - cur, +-8) * 65536) ** 2``, taken before the blend.  All tensors contiguous."""
+    for name, a, nd in (("prev", prev, 4), ("cur", cur, 4), ("w_prev", w_prev, 1), ("w_cur", w_cur, 1)):
+        if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.float32 and a.dim() == nd and a.is_contiguous() and a.device == cur.device):
+            raise ValueError(f"time_crossfade: {name} must be a contiguous float32 tensor of {nd} dimensions on cur's HIP device")
+    V, C, Hp, Wp = cur.shape
+    h, w = int(h), int(w)
+    if tuple(prev.shape) != (V, C, Hp, Wp) or tuple(w_prev.shape) != (V,) or tuple(w_cur.shape) != (V,):
+        raise ValueError(f"time_crossfade: cur {tuple(cur.shape)} goes with prev of its shape and weights [{V}], got {tuple(prev.shape)}, "
+                         f"{tuple(w_prev.shape)}, {tuple(w_cur.shape)}")
+    if min(V, C, Hp, Wp) < 1 or V * C > 65535 or not (1 <= h <= Hp and 1 <= w <= Wp):
+        raise ValueError(f"time_crossfade: need V, C, Hp, Wp >= 1, V * C <= 65535 and a picture inside the plane, got cur {tuple(cur.shape)}, h {h}, w {w}")
+    if sq is not None:
+        if not (isinstance(sq, torch.Tensor) and sq.dtype == torch.int64 and tuple(sq.shape) == (V, C) and sq.is_contiguous() and sq.device == cur.device):
+            raise ValueError(f"time_crossfade: sq must be a contiguous int64 tensor [{V}, {C}] on cur's HIP device")
+        if h * w > 1 << 25:
+            raise ValueError(f"time_crossfade: the statistic takes pictures of at most 2^25 samples, got {h} x {w}")
+    with torch.cuda.device(cur.device):
+        L.check(L.load().sn_time_crossfade(prev.data_ptr(), cur.data_ptr(), w_prev.data_ptr(), w_cur.data_ptr(), None if sq is None else sq.data_ptr(),
+                                           V, C, Hp, Wp, h, w, torch.cuda.current_stream(cur.device).cuda_stream), "sn_time_crossfade")
+    return cur
 
 
 def geo_out_shape(shape, op: int) -> Tuple[int, int, int, int]:

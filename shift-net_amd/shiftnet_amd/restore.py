@@ -30,9 +30,9 @@ result's, separately for luma and chroma -- the fallback when the restoration is
 mid-grey, to see whether detail leaves with the noise.  Both happen in the egress, in the code domain, from the payloads the window has uploaded
 anyway (``sn_egress_yuv_mix``): amount 0 is the input byte for byte.  The blend is linear in the codes, not perceptual.
 
-Noise level (``sigma``, ``noise_model``; denoise variants), method-noise report (``report``), tiles (``tile``) and the self-ensemble (``ensemble``): each
-is a part of its own, described at its class in shiftnet_amd/restore_parts.py (``NoiseLevel``, ``Report``, ``Tiles``, ``Ensemble``); the restorer holds
-each or None and calls it by name.
+Noise level (``sigma``, ``noise_model``; denoise variants), method-noise report (``report``), tiles (``tile``), the self-ensemble (``ensemble``) and
+windows that overlap in time (``window_overlap``): each is a part of its own, described at its class in shiftnet_amd/restore_parts.py (``NoiseLevel``,
+``Report``, ``Tiles``, ``Ensemble``, ``Overlap``); the restorer holds each or None and calls it by name.
 """
 from __future__ import annotations
 
@@ -44,10 +44,11 @@ from typing import Iterable, Iterator, List, Sequence, Tuple
 import numpy as np
 
 from .restore_cli import amount_arg, main, make_parser, picture_arg, sigma_arg, tile_arg  # noqa: F401 -- the command line (restore_cli.py), reached through this module
-from .restore_parts import Ensemble, NoiseLevel, Report, Tiles, _Stat
+from .restore_parts import Ensemble, NoiseLevel, Overlap, Report, Tiles, _Stat
 from .windows import (DEFAULT_TILE_OVERLAP, DITHERS, FUTURE, PAST, PerWindow, _Frames, _SceneFrames, _Thread, amount_form, noise_model_form, pad_multiple,  # noqa: F401
                       padded_size, picture_form, plan_output, plan_scene_windows, plan_windows, reflect_index, report_form, report_motion_form, scene_cuts_form,
-                      sigma_estimator_form, sigma_form, sigma_motion_form, tile_form, plan_tiles, window_indices, ensemble_form)
+                      sigma_estimator_form, sigma_form, sigma_motion_form, tile_form, plan_tiles, window_indices, ensemble_form, overlap_weights,
+                      plan_overlap_windows, plan_scene_overlap_windows, window_overlap_form)
 
 VARIANTS = {"deblur": "gshift_deblur1", "deblur_small": "gshift_deblur2", "denoise": "gshift_denoise1", "denoise_small": "gshift_denoise2"}
 
@@ -68,6 +69,8 @@ class _Slot:
         self.ev_h2d, self.ev_ready, self.ev_done, self.ev_d2h = (torch.cuda.Event() for _ in range(4))
         self.rect = None                                          # the picture of the window the slot holds (None: the full frame)
         self.t0 = 0                                               # the frame number, in its clip, of the first frame that window restores
+        self.head, self.written = 0, None                         # window_overlap: frames shared with the predecessor, frames written (None: all)
+        self.seam = self.seam_size = None                         # what the part Overlap keeps per slot (restore_parts.py)
         self.used = False                                         # in this restore(): a window has gone through the slot
         self.sums = None                                          # picture="auto": _Stat of the window's row and column sums
         self.noise = self.report = None                           # what the parts NoiseLevel and Report keep per slot (restore_parts.py)
@@ -92,7 +95,10 @@ class _Run:
         self.launches = {"noise": 0, "nlf": 0, "nlf_map": 0, "picture": 0, "thumb": 0, "noise_pairs": 0, "nlf_pairs": 0, "report": 0, "motion": 0,
                          "report_motion": 0, "report_mv": 0,      # report_motion: the block matcher on the written frames, the sums along its vectors
                          "tile": 0,                               # tile: the tiles added into the canvas
-                         "geo_transform": 0, "geo_accumulate": 0} # ensemble: the members' inputs made, their results added into the canvas
+                         "geo_transform": 0, "geo_accumulate": 0, # ensemble: the members' inputs made, their results added into the canvas
+                         "overlap": 0}                            # window_overlap: the cross-fades of shared frames
+        self.window_written: List[int] = []                       # window_overlap: the frames every window wrote
+        self.seam_rms: List = []                                  # ... and per window None or the rms difference of the two answers on every shared frame
         self.window_tiles: List = []                              # tile: per window, the (y0, x0, th, tw) of its tiles in the order they ran
         self.frame_sums: List = []                                # report: the 16 sums of every frame handed out, the window it came from, that window's sigma
         self.frame_window: List[int] = []
@@ -310,14 +316,32 @@ class VideoRestorer:
     and no trained checkpoint ships here.  The ``inference/test_*.py`` harnesses, where a PSNR against ground truth could be measured once somebody
     has a checkpoint, do not take the option yet; ``GShiftNet.forward_ensemble_fp32_out`` is there for it.  ``stats`` then also has ``ensemble``,
     ``ensemble_time``, ``ensemble_members`` (the ops in the order run: bit 1 mirrors the columns, 2 the rows, 4 transposes, 8 reverses time) and
-    ``ensemble_launches`` (``{"transform": the sn_geo_transform launches, "accumulate": the sn_geo_accumulate launches}``)."""
+    ``ensemble_launches`` (``{"transform": the sn_geo_transform launches, "accumulate": the sn_geo_accumulate launches}``).
+    window_overlap: 0 -- window k + 1 starts where window k ends, today's launches, bytes and stats keys; V, an integer with ``2 * V <= one_len`` --
+    consecutive windows of a scene share V frames (windows.plan_scene_overlap_windows): the window after [lo, hi) starts at hi - V unless the scene ends
+    at hi, and never reaches across a scene start.  Every window still runs on its own, with 2 input frames of context on each side; a window with a
+    successor writes all but its last V frames and keeps those, float32, in one carry buffer on the device; the successor's first V frames are
+    cross-faded with them in place before its egress (``sn_time_crossfade``, csrc/sn_time.hip; one launch per seam on the main stream): on shared frame
+    j = 0 .. V - 1 the newer window weighs ``(j + 1) / (V + 1)`` and the older ``(V - j) / (V + 1)`` (windows.overlap_weights, the ramp of two tiles
+    that overlap by V).  Every frame is still written once and in order, and the bytes are the same with ``pipeline`` on and off.  The per-window
+    options and statistics stay per window -- ``sigma`` / ``noise_model`` / ``picture`` lists, ``stats["window_*"]`` -- there are simply more windows, and
+    a list written with one overlap reproduces the bytes when read back with the same overlap; the dither's frame number is that of the window's first
+    written frame, so dithered bytes do not depend on the windowing of frames one window covers; the report's ``rho_t`` stays nan across windows.  Two
+    windows whose ``picture`` rectangles differ have results of different shapes: their shared frames are the later window's alone.  The same launch
+    sums the squared difference of the two answers before the blend, exactly (integers; clamped to +-8 per sample): ``stats["seam_rms"]`` has per window
+    None (no predecessor in its scene, or another rectangle) or V numbers, the rms difference in 8-bit R'G'B' code units on each shared frame, oldest
+    first -- how far a window's edge is from the next window's interior, on any footage with any weights.  ``stats["window_overlap"]`` is V,
+    ``stats["window_written"]`` the frames every window wrote, ``stats["overlap_launches"]`` the launches.  **A window still costs one forward, and
+    there are one_len / (one_len - V) times as many.  The cross-fade blends two different answers -- restored with different sigmas, possibly -- so a
+    mismatch becomes a ramp over V frames and is not removed.  Nobody has looked at a seam of a trained network: no checkpoint ships, and ``seam_rms`` on
+    synthetic weights says nothing about one; it is there so that somebody with a checkpoint can find out.**"""
 
     def __init__(self, net, one_len: int, sigma=None, pipeline: bool = True, scene_cuts=None,
                  cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0),
                  picture=None, bar_level: float = 1.0, out_format=None, dither=None, dither_seed: int = 0, noise_model=None,
                  amount=None, view=None, removed_gain: float = 1.0, sigma_estimator: str = "spatial", report: bool = False,
                  report_edge: float = 16.0, sigma_motion=None, report_motion=None, tile=None,
-                 tile_overlap: int = DEFAULT_TILE_OVERLAP, ensemble=None, ensemble_time: bool = False) -> None:
+                 tile_overlap: int = DEFAULT_TILE_OVERLAP, ensemble=None, ensemble_time: bool = False, window_overlap: int = 0) -> None:
         import torch
         from .lib import YuvFmt
         from .noise import check_clamp
@@ -331,6 +355,7 @@ class VideoRestorer:
         self.net, self.one_len, self.pipeline = net, int(one_len), bool(pipeline)
         if self.one_len < 1:
             raise ValueError("one_len must be >= 1")
+        self.window_overlap = window_overlap_form(window_overlap, self.one_len)      # 0: the code path without any of it
         self.cuts_mode, self.scene_cuts = scene_cuts_form(scene_cuts)          # "off", "auto", "list"
         self.cut_threshold, self.cut_ratio = float(cut_threshold), float(cut_ratio)
         self.V = net.V
@@ -368,6 +393,7 @@ class VideoRestorer:
         self.tiles = Tiles(torch, net, self.dev, self.tile) if self.tile is not None else None
         self.ensemble_part = Ensemble(torch, net, self.dev, self.dtype, self.ensemble,
                                       plane=self.noise is not None and not self.noise.flat) if self.ensemble is not None else None
+        self.overlap = Overlap(torch, self.dev, self.window_overlap) if self.window_overlap else None
         self._shape = None
         self._reset()
 
@@ -415,6 +441,8 @@ class VideoRestorer:
             self.tiles.prepare(tout, self.hp, self.wp)
         if self.ensemble_part is not None:
             self.ensemble_part.prepare(tin, tout, self.hp, self.wp)
+        if self.overlap is not None:
+            self.overlap.prepare(self.hp, self.wp, self.slots)
 
     def _size(self, rect) -> Tuple[int, int, int, int]:
         """(h, w, padded h, padded w) of what a window with picture ``rect`` feeds the network."""
@@ -435,14 +463,15 @@ class VideoRestorer:
         return rect
 
     # -- the steps of one window; the slot is slots[k % 2] -------------------------------------------------------------------------
-    def _stage(self, slot: _Slot, frames: Sequence[np.ndarray], t0: int = 0) -> int:
+    def _stage(self, slot: _Slot, frames: Sequence[np.ndarray], t0: int = 0, head: int = 0, written=None) -> int:
         """Host frames -> pinned slot -> device -> RGB tensors, on the side stream.  Windows are staged in the order they are restored.
-        t0: the number of the window's first restored frame in its clip (the dither's frame number)."""
+        t0: the number of the window's first restored frame in its clip (the dither's frame number).  head, written: under ``window_overlap`` the frames
+        the window shares with its predecessor and the frames it writes (None: all it restores)."""
         from .io_edges import ingest_yuv, rowcol_sums_yuv
         torch, run = self.torch, self.run
         t = len(frames)
         rect = self._window_picture()
-        slot.t0 = t0
+        slot.t0, slot.head, slot.written = t0, head, written
         if slot.used:
             slot.ev_h2d.synchronize()                            # the copy that last read this pinned slot has finished
         pin = slot.pin_in.numpy()
@@ -506,7 +535,7 @@ class VideoRestorer:
         return own
 
     def _run(self, slot: _Slot, t: int, main) -> int:
-        """Forward + egress on the main stream, copy back on the output stream."""
+        """Forward + egress on the main stream, copy back on the output stream -> the frames the window wrote."""
         from .io_edges import egress_yuv
         torch, run = self.torch, self.run
         n = t - PAST - FUTURE
@@ -531,6 +560,12 @@ class VideoRestorer:
                 out = self._forward(x, x32, nm)
             e1.record(main)
             run.timers.append((e0, e1))
+            if self.overlap is not None:
+                # the shared frames cross-faded with the predecessor's, the window's own tail kept for the successor; from here on the window is the
+                # frames it writes
+                self.overlap.step(slot, out, slot.head, slot.written, rect, self._size(rect), run)
+                n = slot.written
+                out = out[:n]
             own = self._input_as_written(slot, n, rect, tiled)
             written = slot.dev_out[:n]
             if rect is not None and (slot.dev_ref is not None or not self.convert):
@@ -554,6 +589,8 @@ class VideoRestorer:
         run = self.run
         if self.report_part is not None:
             self.report_part.collect(slot.report, n, run)
+        if self.overlap is not None:
+            self.overlap.collect(slot, run)
         run.collected += 1
         return list(slot.pin_out[:n].numpy().copy())
 
@@ -568,7 +605,7 @@ class VideoRestorer:
         stats["picture_launches"] = run.launches["picture"]
         if self.picture_mode == "auto":
             stats["picture_wait_ms"] = list(run.picture_wait_ms)
-        for part in (self.noise, self.report_part, self.tiles, self.ensemble_part):
+        for part in (self.noise, self.report_part, self.tiles, self.ensemble_part, self.overlap):
             if part is not None:
                 part.finish(run, stats)
         src = run.src
@@ -599,6 +636,8 @@ class VideoRestorer:
         self._reset()
         for slot in self.slots:
             slot.used = False
+        if self.overlap is not None:
+            self.overlap.reset()
         self.stats["out_format"], self.stats["dither"], self.stats["dither_seed"] = (self.out_format if self.convert else None), self.dither, self.dither_seed
         self.stats["amount"], self.stats["view"] = self.amount, self.view
         main = torch.cuda.current_stream(self.dev)
@@ -611,14 +650,16 @@ class VideoRestorer:
                 yield f
 
         def windows():
-            """(the slot, the frames, their first restored frame's number in its clip) of every window, in the order they are restored."""
-            for k, win, clip_lo in self._source(checked(frames)).windows(self.one_len):
-                yield self.slots[k % 2], win, clip_lo
+            """(the slot, the frames, their first restored frame's number in its clip, the frames shared with the predecessor, the frames written) of
+            every window, in the order they are restored."""
+            src = self._source(checked(frames))
+            for k, win, clip_lo in src.windows(self.one_len, self.window_overlap):
+                yield self.slots[k % 2], win, clip_lo, src.head, src.written
 
         if not self.pipeline:
             with torch.cuda.device(self.dev):
-                for slot, win, clip_lo in windows():
-                    n = self._run(slot, self._stage(slot, win, clip_lo), main)
+                for slot, win, *marks in windows():
+                    n = self._run(slot, self._stage(slot, win, *marks), main)
                     for p in self._collect(slot, n):
                         self.stats["frames"] += 1
                         yield p
@@ -641,8 +682,8 @@ class VideoRestorer:
 
         def stage_loop(put):
             with torch.cuda.device(self.dev):
-                for slot, win, clip_lo in windows():
-                    if not acquire(in_free[slot]) or not put((slot, self._stage(slot, win, clip_lo))):
+                for slot, win, *marks in windows():
+                    if not acquire(in_free[slot]) or not put((slot, self._stage(slot, win, *marks))):
                         return
 
         stager = _Thread(stage_loop, depth=1)

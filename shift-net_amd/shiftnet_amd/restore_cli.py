@@ -155,6 +155,14 @@ def make_parser() -> argparse.ArgumentParser:
                          "from the literature for other networks, and no trained checkpoint ships here.  Not with --tile; default 1: one forward")
     ap.add_argument("--ensemble_time", action="store_true",
                     help="double the members of --ensemble: the same copies of the window reversed in time (twice the forwards again)")
+    ap.add_argument("--window_overlap", type=int, default=0, metavar="V",
+                    help="consecutive windows of a scene share V frames, 0 <= V <= one_len / 2, and the two answers for a shared frame are cross-faded on "
+                         "the device with a linear ramp in time, against a step at every window boundary.  A WINDOW STILL COSTS ONE FORWARD AND THERE ARE "
+                         "one_len / (one_len - V) TIMES AS MANY.  The cross-fade blends two different answers: a mismatch becomes a ramp over V frames, it "
+                         "is not removed; nobody has looked at a seam of a trained network; default 0: window k + 1 starts where window k ends")
+    ap.add_argument("--seams_out", default=None, metavar="FILE",
+                    help="--window_overlap: write one line per window, '-' or the V rms differences (8-bit R'G'B' code units, oldest shared frame first) "
+                         "between the previous window's answer for the shared frames and this window's, measured before the cross-fade")
     ap.add_argument("--cuts_out", default=None, metavar="FILE", help="write the scene starts that were used, in the format --scene_cuts FILE reads")
     ap.add_argument("input", metavar="IN", help="Y4M file, or - for stdin")
     ap.add_argument("output", metavar="OUT", help="Y4M file, or - for stdout")
@@ -199,7 +207,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     from . import report as rep
     from .spec import VARIANTS as SPECS
     from .restore import VARIANTS
-    from .windows import DEFAULT_TILE_OVERLAP, amount_form, ensemble_form, report_form, report_motion_form, tile_form
+    from .windows import DEFAULT_TILE_OVERLAP, amount_form, ensemble_form, format_seams, report_form, report_motion_form, tile_form, window_overlap_form
     from .y4m import Y4MReader, Y4MWriter, output_header
     ap = make_parser()
     a = ap.parse_args(argv)
@@ -229,6 +237,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ensemble_form(a.ensemble, a.ensemble_time, tile)
     except ValueError as e:
         ap.error(f"--ensemble / --ensemble_time: {e}")
+    try:
+        window_overlap_form(a.window_overlap, a.one_len)
+    except ValueError as e:
+        ap.error(f"--window_overlap: {e}")
     if "denoise" in a.variant and a.sigma is None:
         ap.error("--sigma is required by the denoise variants")
     if a.sigma_estimator != "spatial" and a.sigma != "auto":      # before the file of a --sigma FILE is opened
@@ -284,9 +296,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                            amount=a.amount, view=view, removed_gain=a.removed_gain, sigma_estimator=a.sigma_estimator,
                            report=a.report is not None, report_edge=a.report_edge, sigma_motion=None if a.sigma_motion == "none" else a.sigma_motion,
                            report_motion=report_motion, tile=a.tile, tile_overlap=tile_overlap, ensemble=a.ensemble,
-                           ensemble_time=a.ensemble_time)
+                           ensemble_time=a.ensemble_time, window_overlap=a.window_overlap)
         if vr.ensemble is not None:
             log(f"ensemble: {len(vr.ensemble[2])} forwards per window (ops {vr.ensemble[2]}); what it gains on this network nobody has measured")
+        if vr.window_overlap:
+            log(f"window overlap: {vr.window_overlap} of {a.one_len} frames shared and cross-faded, {a.one_len / (a.one_len - vr.window_overlap):.2f} times the windows "
+                "(a mismatch becomes a ramp, it is not removed)")
         if vr.tile is not None:
             log("tile: %d x %d, overlap %d (a tiled result is not the full-frame result: channel attention sees the tile)" % vr.tile)
         if a.out_format is not None or a.dither != "none":
@@ -317,6 +332,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             wt = vr.stats["window_tiles"]
             log(f"tiles: {min(len(w) for w in wt) if wt else 0} to {max(len(w) for w in wt) if wt else 0} per window, "
                 f"{vr.stats['tile_launches']} blended over {len(wt)} window{'' if len(wt) == 1 else 's'}")
+        seams = vr.stats.get("seam_rms", [None] * vr.stats["windows"])
+        _write_out(a.seams_out, _text_writer(format_seams), seams)
+        if vr.window_overlap:
+            flat = [v for s in seams if s is not None for v in s]
+            log(f"seams: {sum(s is not None for s in seams)} cross-faded over {len(seams)} window{'' if len(seams) == 1 else 's'}"
+                f"{', median difference of the two answers %.3f 8-bit codes rms' % float(np.median(flat)) if flat else ''} "
+                "(says nothing about a trained network unless the checkpoint is one)")
         wp = vr.stats.get("window_picture", [])
         _write_out(a.picture_out, pic.write_pictures, wp, picture_how)
         if picture is not None:

@@ -1,6 +1,6 @@
 """The optional features of the video restorer (shiftnet_amd/restore.py), one class each: ``NoiseLevel`` (what a window's noise level is and how it is
-obtained), ``Report`` (the method-noise report), ``Tiles`` (the forward in overlapping tiles) and ``Ensemble`` (the forward on mirrored, transposed
-and time-reversed copies).  A part owns everything of its feature -- its state per
+obtained), ``Report`` (the method-noise report), ``Tiles`` (the forward in overlapping tiles), ``Ensemble`` (the forward on mirrored, transposed
+and time-reversed copies) and ``Overlap`` (windows that overlap in time, their shared frames cross-faded).  A part owns everything of its feature -- its state per
 slot on the device and in pinned memory, its launches, its host arithmetic and its keys of ``stats`` -- and writes into the one record of a
 ``restore()`` (``restore._Run``) that ``VideoRestorer`` hands it; ``VideoRestorer`` holds each part or None and calls it by name.  The parts are given
 parsed values (windows.py's ``*_form`` functions) and validate nothing.  ``_Stat`` and ``_Vectors`` are what they share."""
@@ -13,7 +13,7 @@ import numpy as np
 from .noise import (NLF_BANDS, clip_codes, combine_sigma, frame_sigma, frames_median, motion_grid, motion_summary, nbins, nlf_bins, pair_bins, pair_sigma,
                     window_curve, window_curve_pairs, window_sigma, window_sigma_temporal)
 from .report import frames_report, frames_report_motion, summarize, summarize_motion
-from .windows import plan_tiles
+from .windows import overlap_weights, plan_tiles
 
 
 class _Stat:
@@ -367,3 +367,78 @@ class Ensemble:
     def finish(self, run, stats) -> None:
         stats["ensemble"], stats["ensemble_time"], stats["ensemble_members"] = self.ensemble, self.time, list(self.members)
         stats["ensemble_launches"] = {"transform": run.launches["geo_transform"], "accumulate": run.launches["geo_accumulate"]}
+
+
+# ---- windows that overlap in time -------------------------------------------------------------------------------------------------------
+class Overlap:
+    """Windows that overlap in time (``window_overlap`` = V; off by default): every window runs through the network on its own, and the network restores
+    a window's last frames with less temporal context than the first frames of the next window, and each window with its own sigma, noise curve and
+    channel-attention pools -- the result can step at every window boundary.  With V > 0 consecutive windows of a scene share V frames (the plan is
+    windows.plan_scene_overlap_windows); the older window's float32 answer for them is kept in one carry buffer and the newer window's is cross-faded
+    with it, a linear ramp in time (``sn_time_crossfade``, csrc/sn_time.hip; windows.overlap_weights).  The same launch sums, exactly, the squared
+    difference of the two answers before the blend: ``seam_rms``, how far a window's edge is from the next window's interior.  **A window still costs one
+    forward, and there are one_len / (one_len - V) times as many.  The cross-fade blends two different answers: a mismatch becomes a ramp over V
+    frames, it is not removed.**
+
+    ``step`` runs on the main stream behind the forward, ``collect`` on the thread that hands the window's frames out.  One carry for the restorer: the
+    forward, the cross-fade and the egress of all windows run on the main stream, in window order."""
+
+    NONE = object()                                              # the carry holds no window's tail
+
+    def __init__(self, torch, dev, overlap: int) -> None:
+        self.torch, self.dev, self.V = torch, dev, overlap
+        w_prev, w_cur = overlap_weights(overlap)
+        self.w_prev, self.w_cur = torch.from_numpy(w_prev).to(dev), torch.from_numpy(w_cur).to(dev)
+        self.carry = None
+        self.held = self.NONE                                    # the picture rectangle (None: the full frame) of the window whose tail the carry holds
+
+    def prepare(self, hp: int, wp: int, slots) -> None:
+        """Per stream shape: the carry, flat and sized for the full frame as the slots' tensors are, and per slot the sums of a seam (``slot.seam``)."""
+        self.carry = self.torch.empty(self.V * 3 * hp * wp, dtype=self.torch.float32, device=self.dev)
+        for s in slots:
+            s.seam = _Stat(self.torch, self.dev, "overlap", self.V, [(3,)], self.torch.int64)
+            s.seam_size = None
+
+    def reset(self) -> None:
+        self.held = self.NONE
+
+    def step(self, slot, out, head: int, written: int, rect, size, run) -> None:
+        """The window's float32 result ``out`` [n, 3, hp, wp] (current stream: the main stream): its first ``head`` frames cross-faded in place with the
+        predecessor's last, where the carry holds them at the same picture rectangle -- with another rectangle the shapes differ, the shared frames stay
+        this window's alone and the seam has no statistic --, then its own last V frames into the carry if it writes only ``written`` < n of them."""
+        from .io_edges import time_crossfade
+        V, n = self.V, out.shape[0]
+        h, w, hp, wp = size
+        carry = self.carry[:V * 3 * hp * wp].view(V, 3, hp, wp)
+        slot.seam_size = None
+        if head and self.held is not self.NONE and self.held == rect:
+            slot.seam.launch(V, run, lambda sq: time_crossfade(carry, out[:V], self.w_prev, self.w_cur, h, w, sq=sq.zero_()))
+            slot.seam_size = (h, w)
+        if written < n:
+            carry.copy_(out[n - V:])
+            self.held = rect
+        else:
+            self.held = self.NONE
+        run.window_written.append(written)
+
+    def collect(self, slot, run) -> None:
+        """The seam of the window being handed out: None, or per shared frame, oldest first, the rms difference of the two answers in 8-bit R'G'B' code
+        units, ``255 * sqrt(sum over the planes of sq / (2^32 * 3 * h * w))``."""
+        if slot.seam_size is None:
+            run.seam_rms.append(None)
+            return
+        h, w = slot.seam_size
+        sq, = slot.seam.wait(self.V)
+        run.seam_rms.append([seam_rms([int(v) for v in row], h, w) for row in sq])
+
+    def finish(self, run, stats) -> None:
+        stats["window_overlap"] = self.V
+        stats["window_written"] = list(run.window_written)
+        stats["seam_rms"] = [None if s is None else list(s) for s in run.seam_rms]
+        stats["overlap_launches"] = run.launches["overlap"]
+
+
+def seam_rms(sq, h: int, w: int) -> float:
+    """The sums of ``sn_time_crossfade`` of one shared frame's planes -> the rms difference in 8-bit code units (the sums are of (d * 65536)^2)."""
+    import math
+    return 255.0 * math.sqrt(sum(sq) / (2.0 ** 32 * len(sq) * h * w))

@@ -53,6 +53,76 @@ def plan_scene_windows(n: int, one_len: int, cuts: Iterable[int], past: int = PA
     return plan
 
 
+# ---- windows that overlap in time: consecutive windows of a scene share V frames, which are cross-faded --------------------------------------
+def window_overlap_form(window_overlap, one_len: int) -> int:
+    """-> V, the frames consecutive windows of a scene share: an integer with ``0 <= V`` and ``2 * V <= one_len``, so that a frame is covered by at most
+    two windows.  0 is no overlap: the code path without any of it.  ValueError for anything else."""
+    v = window_overlap
+    if not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)) or v < 0:
+        raise ValueError(f"window_overlap must be an integer >= 0, got {window_overlap!r}")
+    if 2 * int(v) > int(one_len):
+        raise ValueError(f"window_overlap must be at most half of one_len ({int(one_len) // 2}), got {window_overlap!r}")
+    return int(v)
+
+
+def overlap_weights(overlap: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(the older window's weights, the newer window's) on the V shared frames, in time order, float32 [V] each: ``(V - j) / (V + 1)`` and
+    ``(j + 1) / (V + 1)`` for j = 0 .. V - 1, computed in float64 and rounded once.  This is the ramp of ``tile_axis``: two tiles of side L that overlap
+    by V, ``tile_axis(2 * L - V, L, V)``, have exactly these weights on the overlap."""
+    j = np.arange(int(overlap), dtype=np.float64)
+    return ((overlap - j) / (overlap + 1.0)).astype(np.float32), ((j + 1.0) / (overlap + 1.0)).astype(np.float32)
+
+
+def plan_overlap_windows(n: int, one_len: int, overlap: int = 0, past: int = PAST, future: int = FUTURE) -> List[Tuple[int, int, List[int], int, int]]:
+    """The windows of a clip of n frames when consecutive windows share ``overlap`` = V frames: per window (first restored frame ``lo``, number restored
+    ``cnt``, the input frame indices, ``head``, ``written``).  Window 0 restores [0, min(one_len, n)); a window that restores [lo, hi) with hi < n is
+    followed by one that starts at hi - V; a window with hi == n is the last.  The indices are ``reflect_index`` over lo - past .. hi + future - 1, as
+    ``plan_windows``'s.  ``head``: how many of the window's first frames the predecessor has restored as well and are cross-faded with its answer
+    (``overlap_weights``): 0 for window 0, V after it.  ``written``: the window writes its first ``written`` frames, [lo, lo + written): all ``cnt`` if it
+    is the last, else ``cnt - V`` -- its last V frames wait for the successor.  So every frame is written exactly once and in order, at most two windows
+    cover a frame, and a window after the first has at least V + 1 frames.  With V = 0 the first three fields are ``plan_windows``'s."""
+    if n < 1 or one_len < 1:
+        raise ValueError(f"plan_overlap_windows: need n >= 1 and one_len >= 1, got {n}, {one_len}")
+    overlap = window_overlap_form(overlap, one_len)
+    plan, lo = [], 0
+    while True:
+        hi = min(lo + one_len, n)
+        last = hi == n
+        plan.append((lo, hi - lo, [reflect_index(i, n) for i in range(lo - past, hi + future)], overlap if plan else 0, hi - lo - (0 if last else overlap)))
+        if last:
+            return plan
+        lo = hi - overlap
+
+
+def plan_scene_overlap_windows(n: int, one_len: int, cuts: Iterable[int], overlap: int = 0, past: int = PAST,
+                               future: int = FUTURE) -> List[Tuple[int, int, List[int], int, int]]:
+    """plan_overlap_windows of every scene on its own, indices shifted to the stream's, as ``plan_scene_windows`` does for ``plan_windows``: the overlap
+    never crosses a scene start, every scene begins with a window that has no predecessor."""
+    if n < 1 or one_len < 1:
+        raise ValueError(f"plan_scene_overlap_windows: need n >= 1 and one_len >= 1, got {n}, {one_len}")
+    starts = [0] + [c for c in check_cuts(cuts) if c < n]
+    plan = []
+    for a, b in zip(starts, starts[1:] + [n]):
+        plan += [(a + lo, cnt, [a + i for i in idx], head, written) for lo, cnt, idx, head, written in plan_overlap_windows(b - a, one_len, overlap, past, future)]
+    return plan
+
+
+def format_seams(seams) -> str:
+    """``stats["seam_rms"]`` as text, one line per window: ``-`` (no seam) or the V numbers, written so that ``parse_seams`` gives them back exactly."""
+    return "# rms difference of the two answers on every shared frame, 8-bit code units, oldest first; one line per window, - : no seam\n" + \
+        "".join(("-" if s is None else " ".join(repr(float(v)) for v in s)) + "\n" for s in seams)
+
+
+def parse_seams(text: str):
+    """The inverse of ``format_seams``: per window None or the list of floats ('#' comments)."""
+    out = []
+    for line in text.splitlines():
+        line = line.split("#", 1)[0].strip()
+        if line:
+            out.append(None if line == "-" else [float(v) for v in line.split()])
+    return out
+
+
 DITHERS = ("tpdf",)
 
 
@@ -358,7 +428,11 @@ class _SceneFrames:
 
     The window that restores [lo, lo + L) of a scene that started at a reads frames lo - 2 .. lo + L + 1 unless the scene ends before: it
     depends on the decisions for lo + 1 .. lo + L + 1, so it is handed out once frame lo + L + 1 + lookahead has been read or the stream has
-    ended.  Frames before max(a, lo - 2) of the next window are dropped: at most L + 4 + lookahead + 1 are held."""
+    ended.  Frames before max(a, lo - 2) of the next window are dropped: at most L + 4 + lookahead + 1 are held.
+
+    ``overlap`` = V > 0 hands out plan_scene_overlap_windows' instead: the window after [lo, hi) starts at hi - V unless the scene ended at hi.  While
+    the scene's end is not known it lies beyond the window's last input frame, so that window is not the scene's last.  ``head`` and ``written`` are
+    those of the window handed out last; the next window reaches back to hi - V - 2, so V more frames are held."""
 
     def __init__(self, it: Iterable[np.ndarray], decider) -> None:
         self.it = iter(it)
@@ -373,6 +447,8 @@ class _SceneFrames:
         self.k = 0
         self.cuts: List[int] = []         # the scene starts used
         self.clip_lo = 0                  # the first restored frame of the window handed out last, counted from the first frame of its clip: the scene
+        self.head = 0                     # ... how many of its first frames are shared with its predecessor (0, or the overlap)
+        self.written = 0                  # ... and how many of its frames, from the first on, it writes
 
     def _fill(self, upto: int) -> None:
         while self.n is None and self.base + len(self.buf) <= upto:
@@ -388,7 +464,7 @@ class _SceneFrames:
             self.decider.finish()
             self.finished = True
 
-    def window(self, k: int, one_len: int) -> Optional[Tuple[int, int, List[np.ndarray]]]:
+    def window(self, k: int, one_len: int, overlap: int = 0) -> Optional[Tuple[int, int, List[np.ndarray]]]:
         """The frames of the k-th window of the stream (k counts up from 0 across the scenes), or None past the end."""
         assert k == self.k, "windows are handed out in order"
         lo, a = self.lo, self.a
@@ -404,7 +480,10 @@ class _SceneFrames:
         hi = min(lo + one_len, b)
         frames = [self.buf[a + reflect_index(i - a, b - a) - self.base] for i in range(lo - PAST, hi + FUTURE)]
         self.k += 1
-        self.lo = hi
+        ended = hi == b                                                       # the scene ends with this window (a stand-in b lies beyond hi)
+        self.head = overlap if lo > a else 0
+        self.written = hi - lo - (0 if ended else overlap)
+        self.lo = hi if ended else hi - overlap
         self.clip_lo = lo - a
         if cut is not None and hi == cut:
             self.a = cut
@@ -415,11 +494,11 @@ class _SceneFrames:
             self.base += drop
         return lo, hi - lo, frames
 
-    def windows(self, one_len: int) -> Iterator[Tuple[int, List[np.ndarray], int]]:
+    def windows(self, one_len: int, overlap: int = 0) -> Iterator[Tuple[int, List[np.ndarray], int]]:
         """(k, the frames of window k, its clip_lo) of every window of the stream, in order."""
         k = 0
         while True:
-            win = self.window(k, one_len)
+            win = self.window(k, one_len, overlap)
             if win is None:
                 return
             yield k, win[2], self.clip_lo

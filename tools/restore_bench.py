@@ -43,6 +43,11 @@
             (the allocator's cache emptied and the peak reset before it; the engine keeps the buffers of the sizes it has seen, so the peak of a form is
             clean only in a process that runs that form alone: give one --tile).  --mode quality: max and rms of |tiled - full| of the written samples
             (10 bit 4:4:4 out, in 8-bit code units) at --size (default 256x384) with 2 x 2 tiles for overlaps 0, 16, 32 and 64.
+  overlap : windows that overlap in time (3.31).  --mode forward: steady-state forward time per window and frames/s end to end of the restorer (Shift-Net-s,
+            one_len 16, bf16, 720p, --windows times 16 frames) for every --overlap V given (repeat the option), runs of the forms alternating in one
+            process, the first window of every run left out.  --mode kernels: ``sn_time_crossfade`` on V = 4 frames of 720p, with and without the
+            statistic, beside a plain device copy of one such tensor, interleaved; bytes per second at 12 bytes per sample (8 for the copy); each also
+            ``_cold``: on six sets of tensors taken in turn, more than the Infinity Cache holds.
 Prints one JSON object per part.
 """
 import argparse
@@ -641,6 +646,79 @@ def tiles_quality(a):
 PICTURE = dict(H=1080, W=1920, rect=(0, 138, 1920, 804))
 
 
+def overlap_forward(a):
+    H, W, one_len, nwin = 720, 1280, 16, a.windows
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    frames = _stream(H, W, one_len * nwin, fmt)
+    net = restore.load_net("deblur_small", "synthetic", "bf16")
+    forms = a.overlap or [0]
+
+    def run(v):
+        torch.cuda.synchronize()
+        vr = restore.VideoRestorer(net, one_len, pipeline=True, window_overlap=v)
+        t0 = time.perf_counter()
+        for _ in vr.restore(iter(frames), fmt, H, W):
+            pass
+        total = time.perf_counter() - t0
+        torch.cuda.synchronize()
+        seams = [x for s in vr.stats.get("seam_rms", []) if s is not None for x in s]
+        return {"total_s": total, "window_forward_ms": vr.stats["window_forward_ms"][1:], "windows": vr.stats["windows"],
+                "seam_rms_median": statistics.median(seams) if seams else None}
+
+    runs = {v: [] for v in forms}
+    for _ in range(a.runs):
+        for v in forms:                                                              # alternating: every round runs every form
+            runs[v].append(run(v))
+    res = {}
+    for v, rs in runs.items():
+        fwd = [g for r in rs for g in r["window_forward_ms"]]
+        res[f"V={v}"] = {"window_forward_ms": summary(fwd), "windows": rs[0]["windows"], "total_s": [round(r["total_s"], 3) for r in rs],
+                         "frames_per_s_end_to_end": [round(one_len * nwin / r["total_s"], 2) for r in rs],
+                         "windows_over_no_overlap": round(rs[0]["windows"] / nwin, 4), "seam_rms_median_synthetic_weights": rs[0]["seam_rms_median"]}
+    print(json.dumps({"part": "overlap", "mode": "forward", "variant": "deblur_small", "dtype": "bf16", "one_len": one_len, "frames": one_len * nwin,
+                      "size": [H, W], "runs": a.runs, **res}))
+
+
+def overlap_kernels(a):
+    from shiftnet_amd.io_edges import time_crossfade
+    from shiftnet_amd.windows import overlap_weights
+    V, C, H, W = 4, 3, 720, 1280
+    g = torch.Generator("cuda").manual_seed(0)
+    prev = torch.rand((V, C, H, W), device="cuda", generator=g)
+    cur = torch.rand((V, C, H, W), device="cuda", generator=g)
+    spare = torch.empty_like(cur)
+    wp, wc = (torch.from_numpy(w).cuda() for w in overlap_weights(V))
+    sq = torch.zeros((V, C), dtype=torch.int64, device="cuda")
+    # the same three on six sets of tensors taken in turn, 800 MB in all: more than the 256 MB Infinity Cache holds, so every launch reads HBM
+    import itertools
+    sets = itertools.cycle([(torch.rand((V, C, H, W), device="cuda", generator=g), torch.rand((V, C, H, W), device="cuda", generator=g)) for _ in range(6)])
+    cases = {"time_crossfade": (12, lambda: time_crossfade(prev, cur, wp, wc, H, W)),
+             "time_crossfade_sq": (12, lambda: time_crossfade(prev, cur, wp, wc, H, W, sq=sq)),
+             "d2d_copy_f32": (8, lambda: spare.copy_(prev, non_blocking=True)),
+             "time_crossfade_cold": (12, lambda: time_crossfade(*next(sets), wp, wc, H, W)),
+             "time_crossfade_sq_cold": (12, lambda: time_crossfade(*next(sets), wp, wc, H, W, sq=sq)),
+             "d2d_copy_f32_cold": (8, lambda: (lambda a, b: b.copy_(a, non_blocking=True))(*next(sets)))}
+    for _, f in cases.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in cases}
+    for _ in range(a.reps):
+        for k, (_, f) in cases.items():                                              # interleaved: every repetition times every case
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.inner):
+                f()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.inner)
+    px = V * C * H * W
+    res = {k: {"us_per_launch": summary([m * 1e3 for m in v]), "tb_per_s_median": round(cases[k][0] * px / (statistics.median(v) * 1e-3) / 1e12, 3)}
+           for k, v in ms.items()}
+    print(json.dumps({"part": "overlap", "mode": "kernels", "shape": [V, C, H, W], "mbytes_moved": {k: round(b * px / 1e6, 1) for k, (b, _) in cases.items()},
+                      "reps": a.reps, "inner": a.inner, **res}))
+
+
 def boxed_1080p(fmt, n_src=8):
     """n_src payloads of a 1920 x 1080 stream on the device: the blurred synthetic clip at 804 rows inside PICTURE['rect'], bars at black (16 / 128)."""
     H, W, (x0, y0, w, h) = PICTURE["H"], PICTURE["W"], PICTURE["rect"]
@@ -777,7 +855,7 @@ def picture_part(a):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion", "tiles"])
+    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion", "tiles", "overlap"])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--inner", type=int, default=200)
     ap.add_argument("--windows", type=int, default=8)
@@ -794,6 +872,7 @@ if __name__ == "__main__":
     ap.add_argument("--picture", choices=["auto", "fixed"], default="auto", help="picture part, forward mode: VideoRestorer(picture='auto') or the rectangle itself")
     ap.add_argument("--tile", action="append", default=None, metavar="{full,N,HxW}", help="tiles part, forward mode: a form to run (repeat for several, which then alternate)")
     ap.add_argument("--tile_overlap", type=int, default=32, help="tiles part, forward mode: VideoRestorer(tile_overlap=...)")
+    ap.add_argument("--overlap", action="append", type=int, default=None, metavar="V", help="overlap part, forward mode: a window_overlap to run (repeat for several, which then alternate)")
     ap.add_argument("--size", default=None, metavar="HxW", help="tiles part: the stream's size (default 720x1280 forward, 256x384 quality)")
     ap.add_argument("--variant", choices=list(restore.VARIANTS), default="deblur_small", help="tiles part: the network")
     a = ap.parse_args()
@@ -802,4 +881,5 @@ if __name__ == "__main__":
          "nlf": nlf_kernels if a.mode == "kernels" else nlf_forward,
          "report": report_kernels if a.mode == "kernels" else report_forward,
          "motion": motion_kernels if a.mode == "kernels" else motion_forward,
-         "tiles": tiles_quality if a.mode == "quality" else tiles_forward}[a.part](a)
+         "tiles": tiles_quality if a.mode == "quality" else tiles_forward,
+         "overlap": overlap_kernels if a.mode == "kernels" else overlap_forward}[a.part](a)
