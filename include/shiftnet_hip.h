@@ -278,6 +278,13 @@ int sn_dw5m_gemm_gate(const void* g1p, const float* ca_in, const void* ttab, con
  * in ONE kernel: u is read once, g2 written once; `a`, g1 and r never reach HBM.  (The denoisers, whose inner CALayer2 needs the global pool of g1,
  * run it twice: sn_phase1_opts.  sn_ln_gemm_gate + sn_dw5m_gemm_gate / sn_grp5_gemm_gate above are the same phase 1 in two kernels with g1 in bf16 in HBM:
  * the engine's fallback for a checkpoint whose activations leave the fp16 range of `a`, g1 and r inside the fused kernel.)
+ * The fused kernel RELIES ON UN-FLUSHED fp16 SUBNORMALS in every fp16 stage (v_cvt_pk_f16_f32 of `a`, the packed fp16 FMAs of RepConv2, the gate product,
+ * the A / B operands of the fp16 MFMAs): the gate's rescaling symmetry (tests/gauge.py) lets a checkpoint hold body[0] rows 2^k times smaller against a
+ * second 1x1 4^k times larger -- the same network -- and g1 = a1 a2 2^-4 is then 4^k of what the synthetic checkpoint gives.  No source sets a denormal
+ * mode; the compiler's default for gfx950 keeps them.  Measured on MI355X (tests/test_gpu_phase1_gauge.py): down to k = -6, where 98 % of g1 is below 2^-14, every
+ * g2 element stays inside a float64 interval that assumes gradual underflow and the error against the exact function stays within 10 % of the base
+ * gauge's; a kernel that flushed would lose one decimal digit at k = -4 and everything at k = -6.  At k = -7 wfrag2 (body[4] times 16) passes 65504:
+ * Plan.add_naf notices at pack time and the engine starts the module on the two-kernel chain, whose second 1x1 is bf16.
  * sn_gsts_cab2_phase1: s->mode 1 / 2, hw = sn_gsts_shiftconv's output; sn_cab1_phase1: s->mode 0.  C = 64 or 80, RepConv depthwise or grouped 8 -> 8 ON THE
  * MATRIX CORES; weights prep.pack_phase1r --
  *     wfrag1  bf16 [C/8][KS1][64][8]: body[0] with the LayerNorm scale folded, wave-paired rows (M-tiles 2q, 2q+1 = channels 16q.. and their gate

@@ -45,6 +45,15 @@ class Engine(Network):
             raise ValueError(f"SN_K4_FUSE={self.k4_fuse!r}: expected 1 (CAB2's phase 2 inside CAB1's phase 1, four launches per unit) or 0 (five launches)")
         if self.cab_fused not in ("0", "p", "p16", "8", "16", "s8", "s16"):
             raise ValueError(f"SN_CAB_FUSED={self.cab_fused!r}: expected 0 (two launches), p / p16 (streaming form) or 8 / 16 / s8 / s16 (tile form)")
+        bad = getattr(plan, "p1r_not_finite", None)
+        if bad is not None and self.phase1 != "0":      # known at pack time: no window is wasted on the range guard, and the message names the weight
+            msg = (f"shiftnet_amd: {bad}: an fp16 operand of the fused phase-1 kernel is not finite for this checkpoint (body.0 rows small against the "
+                   "second 1x1, which the kernel takes times 16 in fp16)")
+            if self.phase1 == "r":
+                raise ValueError(msg + ".  SN_PHASE1=r was asked for explicitly; SN_PHASE1=auto starts the module on the two-kernel chain, float32 has no fp16 operands.")
+            import warnings
+            warnings.warn(msg + ": this module runs phase 1 as the two-kernel chain (SN_PHASE1=0), whose second 1x1 is bf16.")
+            self.phase1 = "0"
 
     act_dtype = torch.bfloat16
 

@@ -120,6 +120,11 @@ class PlanBase:
 class Plan(PlanBase):
     """Device-resident prepared weights of one checkpoint in the bf16 kernels' layouts."""
 
+    # "<block prefix><operand>" of the first fused phase-1 operand (w3, wgrp, wfrag2) whose fp16 packing is not finite, or None.  The gate's rescaling
+    # symmetry lets a checkpoint hold small body.0 rows against a large second 1x1 (times 1 / P1_G1_SCALE in wfrag2); Engine starts such a module on the
+    # two-kernel chain, whose second 1x1 is bf16.
+    p1r_not_finite: Optional[str] = None
+
     def __init__(self, V: Variant, sd: Dict[str, torch.Tensor], device: torch.device) -> None:
         super().__init__(V, sd, device)
         # sn_gsts_shiftconv_mfma reads 16 bytes of a channel-planar LDS row at a displaced column: 8-byte aligned only if every displacement is a multiple
@@ -155,6 +160,9 @@ class Plan(PlanBase):
         g = prep.pack_ln_gemm(sd[f"{pre}body.{i}.weight"], sd[pre + "norm.weight"], sd[pre + "norm.bias"], c); i += 1
         u["w_ln"], u["b_ln"] = self._dev(g["wfrag"]), self._dev(g["bias"])
         w3 = prep.pack_dw3_gate(sd[f"{pre}body.{i}.conv_2.weight"], c); i += 1
+        if not bool(torch.isfinite(w3.to(torch.float16)).all()):
+            raise ValueError(f"shiftnet_amd: {pre}body.1.conv_2.weight is not finite in fp16 (w_dw3_h2, the packed stencil of sn_ln_gemm_gate): neither phase-1 "
+                             "path can run this checkpoint in half precision -- run the module in float32 (net.float(): the fp32 engine has no fp16 operands)")
         u["w_dw3_h2"] = self._dev(prep.pk_f16_words(w3))        # K12: packed-fp16 stencil, [9][C] words = positions (2k, 2k+1)
         i += 1
         if V.denoise:
@@ -167,9 +175,12 @@ class Plan(PlanBase):
         i += 1
         u["w_gate"] = self._dev(prep.pack_gate_gemm(sd[f"{pre}body.{i}.weight"], c))
         # fused phase 1 (sn_gsts_cab2_phase1 / sn_cab1_phase1, csrc/sn_phase1r.hip); the denoisers run it twice (inner CALayer2: sn_phase1_opts)
-        d = {k: self._dev(v) for k, v in prep.pack_phase1r(
+        pk = prep.pack_phase1r(
             sd[f"{pre}body.0.weight"], sd[pre + "norm.weight"], sd[pre + "norm.bias"], sd[f"{pre}body.1.conv_2.weight"],
-            sd[f"{pre}body.{i - 1}.conv_1.weight"], sd[f"{pre}body.{i - 1}.conv_2.weight"], sd[f"{pre}body.{i}.weight"], c).items()}
+            sd[f"{pre}body.{i - 1}.conv_1.weight"], sd[f"{pre}body.{i - 1}.conv_2.weight"], sd[f"{pre}body.{i}.weight"], c)
+        if self.p1r_not_finite is None:
+            self.p1r_not_finite = next((pre + k for k in ("w3", "wgrp", "wfrag2") if not bool(torch.isfinite(pk[k].view(torch.float16)).all())), None)
+        d = {k: self._dev(v) for k, v in pk.items()}
         d["desc"] = L.Phase1Weights(d["wfrag1"].data_ptr(), d["w3"].data_ptr(), d["wgrp"].data_ptr(), d["wfrag2"].data_ptr())   # the tensors stay referenced in d
         u["p1r"] = d
         i += 1

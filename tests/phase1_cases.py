@@ -38,6 +38,15 @@ Stages (Arith: the roundings; reference(): the chain; the kernel's header commen
 fp16 subnormals: wherever an fp16 end is below 2^-14 in magnitude the interval is extended to contain 0, so a consumer that flushes and one that
 does not are both inside.  fp32 results below 2^-100 likewise (exp2 / rcp saturate there).  No modelled fp16 value may exceed 2^15 (asserted).
 
+Two intervals, and which means what.  Arith("interval"), the default and the one every assertion above is about, is the "EITHER" interval: it holds
+for a kernel that keeps fp16 subnormals, for one that flushes them, and for any mixture per stage.  That makes it blind exactly where a checkpoint
+is cold (tests/gauge.py: body.0 rows a few powers of two smaller than the synthetic ones): once a fifth of g1 lies below 2^-14 the extension to 0
+is most of the width, and a kernel that loses two decimal digits by flushing is still inside.  Arith("interval", keep16=True) is the "KEEP16"
+interval: h16 rounds both ends as numpy's fp16 does (gradual underflow, nearest even) and extends nothing, everything else is the same code.  It
+holds only for a kernel EVERY fp16 stage of which keeps subnormals (v_cvt_pk_f16_f32, the packed FMAs, the gate product, the fp16 MFMA operands),
+and stays as narrow at a cold rung as at the base one.  A point emulation that flushes leaves it (the control of tests/test_host_gauge.py); the
+kernel is held inside it by tests/test_gpu_phase1_gauge.py.
+
 Pool rows are per (frame, strip, block of 8 image rows): the interval sum of the un-rounded g2 (sums pass: 16 g1) over the row's own pixels,
 widened by n u sum |.| for the fp32 summation of n terms.
 
@@ -141,11 +150,14 @@ def rbf(x):
 class Arith:
     """The roundings and widenings of one run.  kind "interval": both ends rounded, accumulation terms widen; "point": lo == hi throughout, every
     accumulation term n u M is replaced by share * n u M (share in [-1, 1]: a number, or None for random per element), fp16 subnormals kept or
-    flushed to zero (flush); "exact": nothing is rounded or widened."""
+    flushed to zero (flush); "exact": nothing is rounded or widened.  keep16 (interval): fp16 subnormals are taken as KEPT -- the ends are rounded and
+    not extended to 0 (module docstring: the two intervals)."""
 
-    def __init__(self, kind: str = "interval", rng: Optional[np.random.Generator] = None, share: Optional[float] = None, flush: bool = False):
+    def __init__(self, kind: str = "interval", rng: Optional[np.random.Generator] = None, share: Optional[float] = None, flush: bool = False,
+                 keep16: bool = False):
         assert kind in ("interval", "point", "exact")
-        self.kind, self.rng, self.share, self.flush = kind, rng, share, flush
+        assert not keep16 or kind == "interval"
+        self.kind, self.rng, self.share, self.flush, self.keep16 = kind, rng, share, flush, keep16
         self.max16 = 0.0
 
     def bf(self, lo, hi):
@@ -158,8 +170,9 @@ class Arith:
         if self.kind == "interval":
             if lo.size:
                 self.max16 = max(self.max16, float(np.abs(lo).max()), float(np.abs(hi).max()))      # inf and NaN fail reference()'s assertion too
-            lo = np.where(np.abs(lo) < SUB16, np.minimum(lo, 0.0), lo)
-            hi = np.where(np.abs(hi) < SUB16, np.maximum(hi, 0.0), hi)
+            if not self.keep16:
+                lo = np.where(np.abs(lo) < SUB16, np.minimum(lo, 0.0), lo)
+                hi = np.where(np.abs(hi) < SUB16, np.maximum(hi, 0.0), hi)
         elif self.flush:
             lo = np.where(np.abs(lo) < SUB16, 0.0, lo)
             hi = lo
@@ -527,11 +540,11 @@ def reference(c: P1Case, ops, ar: Optional[Arith] = None, fw=None, fault: Option
     return out
 
 
-def stage_intervals(c: P1Case, t: int, y: int, x: int, ops=None) -> Dict[str, Tuple[np.ndarray, np.ndarray]]:
+def stage_intervals(c: P1Case, t: int, y: int, x: int, ops=None, keep16: bool = False) -> Dict[str, Tuple[np.ndarray, np.ndarray]]:
     """The debug aid: the interval of every stage at pixel (y, x) of absolute frame t -- which stage did a failing element leave?  `a`, F and b hold
-    the gate partners of channel ch at ch and C + ch.  No kernel runs."""
+    the gate partners of channel ch at ch and C + ch.  keep16: the intervals that take fp16 subnormals as kept.  No kernel runs."""
     ops = ops or operands(c)
-    st = frame_stages(c, ops, folded(ops), Arith("interval"), t)
+    st = frame_stages(c, ops, folded(ops), Arith("interval", keep16=keep16), t)
     return {k: (st[k][0][y, x], st[k][1][y, x]) for k in STAGES}
 
 

@@ -85,8 +85,9 @@ class Dev:
         return torch.full((n.value // 2,), NAN, dtype=torch.float16, device=DEV)      # NaN: a row the second pass reads but the first did not write would show
 
 
-def inside(c, ops, rec, tag, what, got, lo, hi):
-    """every element written and inside its interval; the record gets the share at an interval end, or the worst element and its stages"""
+def inside(c, ops, rec, tag, what, got, lo, hi, keep16=False):
+    """every element written and inside its interval; the record gets the share at an interval end, or the worst element and its stages (keep16: the
+    stages' intervals that take fp16 subnormals as kept, for tests/test_gpu_phase1_gauge.py)"""
     got = got.double().cpu().numpy()
     assert got.shape == lo.shape, (c.id, tag, what, got.shape, lo.shape)
     out = PC.outside(got, lo, hi)
@@ -100,7 +101,7 @@ def inside(c, ops, rec, tag, what, got, lo, hi):
         r[what]["worst"] = dict(index=[int(k) for k in i], got=float(got[i]), lo=float(lo[i]), hi=float(hi[i]), excess_over_peak=float(ex[i] / peak))
         if what == "g2":
             t, y, x = c.frames.start + i[0], i[1], i[2]
-            r[what]["worst"]["stages"] = {k: [v[0].tolist(), v[1].tolist()] for k, v in PC.stage_intervals(c, t, y, x, ops).items()}
+            r[what]["worst"]["stages"] = {k: [v[0].tolist(), v[1].tolist()] for k, v in PC.stage_intervals(c, t, y, x, ops, keep16).items()}
         REPORT.append(dict(rec))
         raise AssertionError(f"{c.id}:{tag}: {int(out.sum())} of {out.size} {what} elements outside their interval ({int(np.isnan(got).sum())} not written); "
                              f"worst {r[what]['worst']['index']}: got {got[i]:.9g}, interval [{lo[i]:.9g}, {hi[i]:.9g}]")
