@@ -836,6 +836,41 @@ int sn_geo_accumulate(const float* member, float* canvas, int op, int init, floa
 int sn_time_crossfade(const float* prev, float* cur, const float* w_prev, const float* w_cur, unsigned long long* sq /* NULL: no statistic */,
                       int V, int C, int Hp, int Wp, int h, int w, void* stream);
 
+/* ---- no-reference quality: the per-pixel part of NIQE (csrc/sn_niqe.hip; a new symbol, SN_ABI_VERSION stays 20) ------------------------------------
+ * NIQE (Mittal, Soundararajan, Bovik 2013) scores a picture by the distance of the statistics of its 96 x 96 blocks, at two scales, from those of
+ * pristine natural images.  Per block and scale it fits five asymmetric generalised Gaussians: to the locally normalised luma and to its products with
+ * four neighbours.  Each fit needs five sums of its map; sn_yuv_niqe_sums makes those sums, shiftnet_amd/niqe.py does the rest on the host in float64.
+ *   src: T payloads as sn_ingest_yuv takes them; only the luma plane is read, and of fmt only bits and range decide anything.  rect (NULL: the whole
+ *   frame) as sn_ingest_yuv_rect takes it: the picture is its h x w luma samples and everything below is what the cropped stream would give.
+ *   win7: 7 float32 taps g[0..6] in device memory, the separable factor of the model's 7 x 7 window.  dst:[T][2][nbh][nbw][SN_NIQE_MAPS][SN_NIQE_SUMS]
+ *   doubles, nbh = h / 96, nbw = w / 96 (integer division); only the top-left 96 nbh x 96 nbw samples of the picture count and are read.
+ * Sample value, float32:  limited range v = code * 2^-(bits - 8) (exact);  full range v = 16 + code * k, k = (float)(219.0 / (2^bits - 1)), product and
+ *   sum rounded separately: both on the 16 .. 235 scale of an 8-bit limited-range Y'.
+ * Scale 1: I = v, hs x ws = 96 nbh x 96 nbw.  Scale 2: I(y, x) = 0.25 * ((v(2y, 2x) + v(2y, 2x+1)) + (v(2y+1, 2x) + v(2y+1, 2x+1))), hs x ws half of that.
+ * Per scale, float32, every product and sum rounded on its own (no FMA); a 7-tap sum adds its products p0 .. p6 from the outside in,
+ * (((p0 + p6) + (p1 + p5)) + (p2 + p4)) + p3, in which order the float32 taps of NIQE's window add up to exactly 1 and a flat area gets n = 0 exactly;
+ * cy / cx clamp to 0 .. hs - 1 / 0 .. ws - 1 (the replication is at the crop of that scale, not at the frame):
+ *     r1(y, x) = sum_i g[i] * I(y, cx(x + i - 3))              r2(y, x) = sum_i g[i] * (I * I)(y, cx(x + i - 3))
+ *     mu(y, x) = sum_j g[j] * r1(cy(y + j - 3), x)             m2(y, x) = sum_j g[j] * r2(cy(y + j - 3), x)
+ *     n = (I - mu) / (sqrt(|m2 - mu * mu|) + 1)                (correctly rounded square root and division)
+ * Per block of side B = 96 / scale, block (by, bx) being rows by B .. by B + B - 1 and columns bx B .. of that scale, with (y, x) inside the block:
+ *     map 0: m = n(y, x);   maps 1..4: m = n(y, x) * n((y - dy) mod B, (x - dx) mod B), (dy, dx) = (0, 1), (1, 0), (1, 1), (1, -1)   (one float32 product;
+ *     the wrap is inside the block).
+ * dst[t][scale - 1][by][bx][map] holds five doubles; m is converted to double and everything after that is float64:
+ *     [0] the count of m < 0   [1] the sum of m^2 over m < 0   [2] the count of m > 0   [3] the sum of m^2 over m > 0   [4] the sum of |m|
+ * One workgroup owns one (frame, scale, block), adds in one fixed order and writes its 25 doubles with plain stores; there are no atomics.  The
+ * result does not depend on the launch geometry or the schedule, and a second launch gives the same bits.  Only dst is written, every word of it.
+ * (tests/niqe_ref.py restates the sums in float64; the counts differ from it only where a float32 m and its float64 twin lie on both sides of zero.)
+ * SN_EINVAL before anything is launched: a null src, fmt, win7 or dst; bits not 8 or 10 or an unknown chroma code; a rectangle sn_ingest_yuv_rect
+ * refuses; T outside 1 .. 65535; H or W < 1; no whole block (nbh * nbw == 0); dst not 8-byte or win7 not 4-byte aligned; src at an odd address at
+ * 10 bit. */
+#define SN_NIQE_BLOCK 96
+#define SN_NIQE_MAPS 5
+#define SN_NIQE_SUMS 5
+int sn_yuv_niqe_sums(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */,
+                     const float* win7 /* device, 7 taps */, double* dst /* [T][2][nbh][nbw][5][5] */,
+                     int T, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

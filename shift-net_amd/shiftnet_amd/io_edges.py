@@ -22,6 +22,8 @@ the statistics of the same payloads' luma (csrc/sn_yuv_stats.hip), each for one 
                (shiftnet_amd/report.py);
 ``diff_stats_mv_yuv``: int64 sums of that difference in consecutive payloads along the vectors of ``block_motion_yuv``, for the report's motion-compensated
                temporal correlation;
+``niqe_sums_yuv``: float64 sums of the locally normalised luma and of its neighbour products per 96 x 96 block at two scales (csrc/sn_niqe.hip), for the
+               no-reference quality score of the report (shiftnet_amd/niqe.py);
 ``tile_accumulate``: one tile's float32 result added into the window's float32 canvas with its feather weights (csrc/sn_tile.hip), for the tiled
                restorer (``VideoRestorer(tile=...)``);
 ``geo_transform`` / ``geo_accumulate``: a tensor mirrored, transposed and reversed in time, and a float32 result mapped back and added into a float32
@@ -405,6 +407,29 @@ def diff_stats_mv_yuv(ref: torch.Tensor, out: torch.Tensor, fmt: "L.YuvFmt", H: 
     with torch.cuda.device(dev):
         L.check(L.load().sn_yuv_diff_stats_mv(ref.data_ptr(), out.data_ptr(), fmt, r, mv.data_ptr(), y.data_ptr(), T, H, W,
                                               torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_diff_stats_mv")
+    return y
+
+
+def niqe_sums_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, win7_dev: torch.Tensor, rect=None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """payload_u8: [T, frame_bytes] uint8 on a HIP device (only the luma plane of each payload is read); ``win7_dev``: the 7 float32 taps of NIQE's
+    window on the same device (niqe.load_params) -> float64 [T, 2, nbh, nbw, 5, 5]: per payload, scale (1, 2) and 96 x 96 block of the picture's top-left
+    96 nbh x 96 nbw samples, for the normalised luma and its four neighbour products the five sums include/shiftnet_hip.h lists under sn_yuv_niqe_sums
+    (the count and the sum of squares of the negative and of the positive values, the sum of the magnitudes).  ``rect=(x0, y0, w, h)``: the sums of
+    that picture of the stream.  ``out``: a tensor of that shape to overwrite.  A picture without a whole block is refused (ValueError): the caller
+    decides what no number means.  niqe.block_features and niqe.score turn the sums into the score, on the host."""
+    T, dev = _payload(payload_u8, fmt, H, W)
+    r = None if rect is None else _rect(rect, fmt, H, W)
+    nbh, nbw = (H if r is None else r.h) // L.SN_NIQE_BLOCK, (W if r is None else r.w) // L.SN_NIQE_BLOCK
+    if nbh * nbw == 0:
+        raise ValueError(f"sn_yuv_niqe_sums: the picture holds no whole {L.SN_NIQE_BLOCK} x {L.SN_NIQE_BLOCK} block")
+    assert win7_dev.dtype == torch.float32 and tuple(win7_dev.shape) == (7,) and win7_dev.is_contiguous() and win7_dev.device == dev
+    shape = (T, 2, nbh, nbw, L.SN_NIQE_MAPS, L.SN_NIQE_SUMS)
+    y = out if out is not None else torch.empty(shape, dtype=torch.float64, device=dev)
+    assert tuple(y.shape) == shape and y.dtype == torch.float64 and y.is_contiguous() and y.device == dev
+    with torch.cuda.device(dev):
+        L.check(L.load().sn_yuv_niqe_sums(payload_u8.data_ptr(), fmt, r, win7_dev.data_ptr(), y.data_ptr(), T, H, W,
+                                          torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_niqe_sums")
     return y
 
 

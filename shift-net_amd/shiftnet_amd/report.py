@@ -170,6 +170,7 @@ class MotionReport:
 
 
 COLUMNS_MV = tuple(f.name for f in fields(MotionReport))
+COLUMNS_Q = ("niqe_in", "niqe_out")                           # report_quality="niqe": the score of the input and of the written frame (shiftnet_amd/niqe.py)
 
 
 def pair_measures_mv(sums, bits: int, h: int, w: int) -> MotionReport:
@@ -237,37 +238,71 @@ def _word(v) -> str:
     return repr(float(v)) if isinstance(v, float) else str(int(v))     # repr of a float reads back to the same float; nan reads back as nan
 
 
-def format_report(frames: Iterable[FrameReport], how: str = "", motion: Optional[Iterable[MotionReport]] = None) -> str:
+def summarize_quality(pairs: Iterable) -> Dict[str, float]:
+    """The medians of the (niqe_in, niqe_out) pairs of the written frames, each over the frames that have a number (nan where none has)."""
+    pairs = list(pairs)
+    out = {}
+    for i, name in enumerate(COLUMNS_Q):
+        v = [float(p[i]) for p in pairs if not math.isnan(p[i])]
+        out[name] = float(np.median(v)) if v else NAN
+    return out
+
+
+def summary_line_quality(summary: Dict[str, float]) -> str:
+    """Both medians, for a log."""
+    return ", ".join(f"{k} {summary[k]:.3f}" for k in COLUMNS_Q)
+
+
+def format_report(frames: Iterable[FrameReport], how: str = "", motion: Optional[Iterable[MotionReport]] = None, quality: Optional[Iterable] = None) -> str:
     """The report file: '#' header lines that name the columns, one line per written frame (sigma '-' where the window had none), and the medians of
     ``summarize`` as the last line, '# median'.  Floats are written so that ``parse_report`` reads back equal reports.  ``motion``: one MotionReport
-    per frame; every line, the median line and the '#' column line then gain its four columns (``parse_report_motion`` reads them back).  Without it
-    the text is what it was before there was a motion part."""
+    per frame; every line, the median line and the '#' column line then gain its four columns (``parse_report_motion`` reads them back).  ``quality``:
+    one (niqe_in, niqe_out) per frame; they gain those two columns, last (``parse_report_quality``).  Without either the text is what it was before
+    there was such a part."""
     frames = list(frames)
     med = summarize(frames)
     lines = ["# method noise: written minus input, one line per written frame" + (f" ({how})" if how else ""),
              "# m, var: luma codes of the format written; sigma, removed_sigma: 8-bit R'G'B' codes; mean_*, rms_*: 8-bit codes; rho_t: to the next frame"]
-    if motion is None:
-        lines.append("# " + " ".join(COLUMNS))
-        lines += [" ".join(_word(getattr(f, c)) for c in COLUMNS) for f in frames]
-        lines.append("# median - - - " + " ".join(_word(med[c]) for c in MEASURES))
-        return "\n".join(lines) + "\n"
-    motion = list(motion)
-    if len(motion) != len(frames):
-        raise ValueError(f"{len(frames)} frames and {len(motion)} motion reports")
-    mmed = summarize_motion(motion)
-    lines.append("# rho_t_mv: to the next frame along block motion vectors of the written picture (measuring blocks only); mv_match_rms: 8-bit codes; "
-                 "mv_moved, mv_counted: shares")
-    lines.append("# " + " ".join(COLUMNS + COLUMNS_MV))
-    lines += [" ".join([_word(getattr(f, c)) for c in COLUMNS] + [_word(getattr(m, c)) for c in COLUMNS_MV]) for f, m in zip(frames, motion)]
-    lines.append("# median - - - " + " ".join([_word(med[c]) for c in MEASURES] + [_word(mmed[c]) for c in COLUMNS_MV]))
+    cols = list(COLUMNS)
+    rows = [[_word(getattr(f, c)) for c in COLUMNS] for f in frames]
+    meds = [_word(med[c]) for c in MEASURES]
+    if motion is not None:
+        motion = list(motion)
+        if len(motion) != len(frames):
+            raise ValueError(f"{len(frames)} frames and {len(motion)} motion reports")
+        mmed = summarize_motion(motion)
+        lines.append("# rho_t_mv: to the next frame along block motion vectors of the written picture (measuring blocks only); mv_match_rms: 8-bit codes; "
+                     "mv_moved, mv_counted: shares")
+        cols += COLUMNS_MV
+        for r, m in zip(rows, motion):
+            r += [_word(getattr(m, c)) for c in COLUMNS_MV]
+        meds += [_word(mmed[c]) for c in COLUMNS_MV]
+    if quality is not None:
+        quality = [(float(a), float(b)) for a, b in quality]
+        if len(quality) != len(frames):
+            raise ValueError(f"{len(frames)} frames and {len(quality)} quality pairs")
+        qmed = summarize_quality(quality)
+        lines.append("# niqe_in, niqe_out: NIQE of the luma of the input and of the written frame (no reference; lower is nearer to natural pictures; nan: "
+                     "fewer than two 96 x 96 blocks could be fitted)")
+        cols += COLUMNS_Q
+        for r, q in zip(rows, quality):
+            r += [_word(q[0]), _word(q[1])]
+        meds += [_word(qmed[c]) for c in COLUMNS_Q]
+    lines.append("# " + " ".join(cols))
+    lines += [" ".join(r) for r in rows]
+    lines.append("# median - - - " + " ".join(meds))
     return "\n".join(lines) + "\n"
 
 
 def _parse(text: str):
-    """(FrameReport, MotionReport or None) of every line of a report file; a line has the columns of a frame, or those and the four of its motion
-    part ('#' lines are comments, the medians among them: ``summarize`` makes them again)."""
+    """(FrameReport, MotionReport or None, (niqe_in, niqe_out) or None) of every line of a report file; a line has the columns of a frame, or those and the four of its motion
+    part ('#' lines are comments, the medians among them: ``summarize`` makes them again).  Where the '#' line that names the columns ends in
+    ``niqe_in niqe_out`` every line has those two columns more, last; a file without them is read as it always was."""
     out = []
-    widths = (len(COLUMNS), len(COLUMNS) + len(COLUMNS_MV))
+    nf, nm, nq = len(COLUMNS), len(COLUMNS_MV), len(COLUMNS_Q)
+    named = [line.split()[1:] for line in text.splitlines() if line.startswith("# " + COLUMNS[0] + " ")]
+    q = nq if any(tuple(n[-nq:]) == COLUMNS_Q for n in named) else 0
+    widths = (nf + q, nf + nm + q)
     for ln, line in enumerate(text.splitlines(), 1):
         body = line.split("#", 1)[0].split()
         if not body:
@@ -278,15 +313,21 @@ def _parse(text: str):
             vals = [int(body[0]), int(body[1]), None if body[2] == "-" else float(body[2])] + [float(w) for w in body[3:]]
         except ValueError:
             raise ValueError(f"line {ln}: not a report line: {line!r}") from None
-        out.append((FrameReport(*vals[:widths[0]]), MotionReport(*vals[widths[0]:]) if len(body) == widths[1] else None))
+        rest = vals[nf:len(vals) - q]
+        out.append((FrameReport(*vals[:nf]), MotionReport(*rest) if rest else None, tuple(vals[-q:]) if q else None))
     return out
 
 
 def parse_report(text: str) -> List[FrameReport]:
     """The frames of a report file, with or without a motion part."""
-    return [f for f, _ in _parse(text)]
+    return [f for f, _, _ in _parse(text)]
 
 
 def parse_report_motion(text: str) -> List[Optional[MotionReport]]:
     """The motion part of every line of a report file; None for a line without one."""
-    return [m for _, m in _parse(text)]
+    return [m for _, m, _ in _parse(text)]
+
+
+def parse_report_quality(text: str) -> List[Optional[tuple]]:
+    """The (niqe_in, niqe_out) of every line of a report file; None for a line without them."""
+    return [q for _, _, q in _parse(text)]

@@ -46,7 +46,7 @@ import numpy as np
 from .restore_cli import amount_arg, main, make_parser, picture_arg, sigma_arg, tile_arg  # noqa: F401 -- the command line (restore_cli.py), reached through this module
 from .restore_parts import Ensemble, NoiseLevel, Overlap, Report, Tiles, _Stat
 from .windows import (DEFAULT_TILE_OVERLAP, DITHERS, FUTURE, PAST, PerWindow, _Frames, _SceneFrames, _Thread, amount_form, noise_model_form, pad_multiple,  # noqa: F401
-                      padded_size, picture_form, plan_output, plan_scene_windows, plan_windows, reflect_index, report_form, report_motion_form, scene_cuts_form,
+                      padded_size, picture_form, plan_output, plan_scene_windows, plan_windows, quality_form, reflect_index, report_form, report_motion_form, scene_cuts_form,
                       sigma_estimator_form, sigma_form, sigma_motion_form, tile_form, plan_tiles, window_indices, ensemble_form, overlap_weights,
                       plan_overlap_windows, plan_scene_overlap_windows, window_overlap_form)
 
@@ -94,6 +94,7 @@ class _Run:
         self.window_pair_motion: List = []                        # sigma_motion: per window, per pair, noise.motion_summary's triple
         self.launches = {"noise": 0, "nlf": 0, "nlf_map": 0, "picture": 0, "thumb": 0, "noise_pairs": 0, "nlf_pairs": 0, "report": 0, "motion": 0,
                          "report_motion": 0, "report_mv": 0,      # report_motion: the block matcher on the written frames, the sums along its vectors
+                         "report_quality": 0,                     # report_quality: the NIQE sums of the input and of the written frames
                          "tile": 0,                               # tile: the tiles added into the canvas
                          "geo_transform": 0, "geo_accumulate": 0, # ensemble: the members' inputs made, their results added into the canvas
                          "overlap": 0}                            # window_overlap: the cross-fades of shared frames
@@ -105,6 +106,7 @@ class _Run:
         self.frame_sigma: List = []
         self.pair_sums_mv: List = []                              # report_motion: the 8 sums of the pair (frame, frame + 1) of every frame handed out, or None
         self.frame_size: List = []                                # ... and the (h, w) of the picture its window was restored in
+        self.frame_niqe: List = []                                # report_quality: (niqe_in, niqe_out) of every frame handed out
         self.collected = 0                                        # windows handed out
         self.src = None                                           # the frame source
 
@@ -277,6 +279,16 @@ class VideoRestorer:
     those of the input frames as fed.  **Limits**: integer-pel vectors within +-7 samples per 16 x 16 block; half of the samples; blocks at the border
     whose true vector leaves the picture read low (the synthetic pans of the tests read 0.6 to 0.9 where everything removed was detail); pairs across windows have no value;
     zoom, rotation and occlusion still read as uncorrelated; no threshold and no verdict; unvalidated on real footage.
+    report_quality: None -- today's launches, bytes, stats keys and report; ``"niqe"`` (needs ``report=True``) -- the report says what changed, not how the
+    pictures look.  NIQE is a no-reference score: the distance of the statistics of a picture's 96 x 96 luma blocks, at two scales, from those of pristine
+    natural images (shiftnet_amd/niqe.py; lower is nearer).  Behind the report's launch two more (``sn_yuv_niqe_sums``, main stream) make the per-pixel
+    sums of the window's input frames and of the frames written for them, in the format written and on the same rectangle; the fit and the distance
+    are float64 on the thread that hands the frames out.  ``stats["frame_niqe"]`` is one ``(niqe_in, niqe_out)`` per written frame (nan for a picture
+    with fewer than two whole blocks), ``stats["report_quality_summary"]`` their medians ignoring nan, ``stats["report_quality_launches"]`` the
+    launches.  ``niqe_params``: the pristine model's .npz (None: tests/golden/niqe_pris_params.npz of the checkout; a missing file is a ValueError
+    that names the option).  The model was fitted on natural stills, on the Y of BT.601 R'G'B'; the stream's own luma is fed, whatever its matrix.
+    Denoising can move the score either way -- over-smoothing is not natural either.  No threshold, no verdict, nothing fed back; **unvalidated on
+    real footage**, and on synthetic weights it says nothing about the network.  No byte written changes.
     tile: None -- the network is given whole frames, today's launches, bytes and stats keys; ``(th, tw)`` or an int ``n`` (``(n, n)``) -- the forward of
     every window runs on overlapping th x tw rectangles of the window's padded frames instead, one after the other in row-major order, each on the
     contiguous crop of the input tensors (and of the noise plane under ``noise_model``; a flat sigma is broadcast to the tile's shape), and
@@ -341,7 +353,8 @@ class VideoRestorer:
                  picture=None, bar_level: float = 1.0, out_format=None, dither=None, dither_seed: int = 0, noise_model=None,
                  amount=None, view=None, removed_gain: float = 1.0, sigma_estimator: str = "spatial", report: bool = False,
                  report_edge: float = 16.0, sigma_motion=None, report_motion=None, tile=None,
-                 tile_overlap: int = DEFAULT_TILE_OVERLAP, ensemble=None, ensemble_time: bool = False, window_overlap: int = 0) -> None:
+                 tile_overlap: int = DEFAULT_TILE_OVERLAP, ensemble=None, ensemble_time: bool = False, window_overlap: int = 0,
+                 report_quality=None, niqe_params=None) -> None:
         import torch
         from .lib import YuvFmt
         from .noise import check_clamp
@@ -352,6 +365,7 @@ class VideoRestorer:
         self.mix, self.amount, self.view = amount_form(amount, view, removed_gain)
         self.report, self.report_edge = report_form(report, report_edge, self.view)      # False: the code path without any of it
         self.report_motion = report_motion_form(report_motion, self.report)      # None: the code path without any of it
+        self.report_quality = quality_form(report_quality, niqe_params, self.report)      # None: the code path without any of it; or the pristine model
         self.net, self.one_len, self.pipeline = net, int(one_len), bool(pipeline)
         if self.one_len < 1:
             raise ValueError("one_len must be >= 1")
@@ -389,7 +403,7 @@ class VideoRestorer:
         # the parts (restore_parts.py), each None where its feature is off: they are given what was parsed above
         self.noise = NoiseLevel(self.sigma_mode, self.sigma, self.sigma_estimator, self.sigma_motion, self.nlf_mode, self.nlf,
                                 self.sigma_clamp) if self.V.denoise else None
-        self.report_part = Report(self.report_edge, self.report_motion, self.V.denoise) if self.report else None
+        self.report_part = Report(self.report_edge, self.report_motion, self.V.denoise, self.report_quality) if self.report else None
         self.tiles = Tiles(torch, net, self.dev, self.tile) if self.tile is not None else None
         self.ensemble_part = Ensemble(torch, net, self.dev, self.dtype, self.ensemble,
                                       plane=self.noise is not None and not self.noise.flat) if self.ensemble is not None else None

@@ -137,6 +137,14 @@ def make_parser() -> argparse.ArgumentParser:
                          "that moves with a pan reads rho_t about 0 as noise does; also how well the vectors fit (mv_match_rms), the share that moved and "
                          "the share counted; blocks at the border of a pan read low, zoom and rotation still read as uncorrelated; unvalidated on real "
                          "footage; default none: the report as it is without")
+    ap.add_argument("--report_quality", choices=["none", "niqe"], default="none",
+                    help="--report only: 'niqe' adds two columns about the pictures themselves, NIQE (a no-reference score, lower is nearer to natural "
+                         "pictures) of the luma of every input frame and of the frame written for it (niqe_in, niqe_out); sums on the device, the fit on "
+                         "the host; nan below two 96 x 96 blocks; the model was fitted to natural stills and BT.601 luma, the stream's own luma is fed; "
+                         "denoising can move it either way; no threshold, no verdict, unvalidated on real footage; default none: the report as it is without")
+    ap.add_argument("--niqe_params", default=None, metavar="FILE",
+                    help="--report_quality niqe: the pristine model (an .npz with mu_pris_param, cov_pris_param, gaussian_window); default: "
+                         "tests/golden/niqe_pris_params.npz of the checkout")
     ap.add_argument("--tile", type=tile_arg, default=None, metavar="{N,HxW}",
                     help="for frames whose activations do not fit the device: run the network on overlapping tiles of H x W samples (N: N x N) of every "
                          "window, one after the other, and blend their results with feather weights on the device; both sides multiples of 4 (8 for "
@@ -207,7 +215,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     from . import report as rep
     from .spec import VARIANTS as SPECS
     from .restore import VARIANTS
-    from .windows import DEFAULT_TILE_OVERLAP, amount_form, ensemble_form, format_seams, report_form, report_motion_form, tile_form, window_overlap_form
+    from .windows import DEFAULT_TILE_OVERLAP, amount_form, ensemble_form, format_seams, quality_form, report_form, report_motion_form, tile_form, window_overlap_form
     from .y4m import Y4MReader, Y4MWriter, output_header
     ap = make_parser()
     a = ap.parse_args(argv)
@@ -226,6 +234,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         report_motion = report_motion_form(None if a.report_motion == "none" else a.report_motion, a.report is not None)
     except ValueError:
         ap.error(f"--report_motion {a.report_motion} needs --report")
+    report_quality = None if a.report_quality == "none" else a.report_quality
+    try:                                                          # as above; the model is read here and again by the restorer
+        quality_form(report_quality, a.niqe_params, a.report is not None)
+    except ValueError as e:
+        ap.error(f"--report_quality / --niqe_params: {str(e).replace('report=True', '--report')}")
     if a.tile is None and a.tile_overlap is not None:             # as above: before any file is opened
         ap.error("--tile_overlap needs --tile")
     tile_overlap = DEFAULT_TILE_OVERLAP if a.tile_overlap is None else a.tile_overlap
@@ -296,7 +309,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                            amount=a.amount, view=view, removed_gain=a.removed_gain, sigma_estimator=a.sigma_estimator,
                            report=a.report is not None, report_edge=a.report_edge, sigma_motion=None if a.sigma_motion == "none" else a.sigma_motion,
                            report_motion=report_motion, tile=a.tile, tile_overlap=tile_overlap, ensemble=a.ensemble,
-                           ensemble_time=a.ensemble_time, window_overlap=a.window_overlap)
+                           ensemble_time=a.ensemble_time, window_overlap=a.window_overlap, report_quality=report_quality, niqe_params=a.niqe_params)
         if vr.ensemble is not None:
             log(f"ensemble: {len(vr.ensemble[2])} forwards per window (ops {vr.ensemble[2]}); what it gains on this network nobody has measured")
         if vr.window_overlap:
@@ -357,12 +370,15 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 f"min {min(ws):.2f} / median {float(np.median(ws)):.2f} / max {max(ws):.2f} over {len(ws)} window{'' if len(ws) == 1 else 's'}")
         if a.report is not None:
             fr = vr.stats["frame_report"]
-            _write_out(a.report, _text_writer(rep.format_report), fr, f"edge {a.report_edge:g}", vr.stats.get("frame_report_motion"))
+            _write_out(a.report, _text_writer(rep.format_report), fr, f"edge {a.report_edge:g}", vr.stats.get("frame_report_motion"), vr.stats.get("frame_niqe"))
             log(f"report (written minus input, medians over {len(fr)} frame{'' if len(fr) == 1 else 's'}, unvalidated on real footage): "
                 f"{rep.summary_line(vr.stats['report_summary'])}")
             if report_motion is not None:
                 log(f"report along block motion (medians over the pairs inside a window, unvalidated on real footage): "
                     f"{rep.summary_line_motion(vr.stats['report_motion_summary'])}")
+            if report_quality is not None:
+                log(f"quality (NIQE of the luma, medians over the frames with a score; no verdict, unvalidated on real footage): "
+                    f"{rep.summary_line_quality(vr.stats['report_quality_summary'])}")
     finally:
         if fin is not sys.stdin.buffer:
             fin.close()

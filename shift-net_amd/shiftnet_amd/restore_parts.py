@@ -12,7 +12,7 @@ import numpy as np
 
 from .noise import (NLF_BANDS, clip_codes, combine_sigma, frame_sigma, frames_median, motion_grid, motion_summary, nbins, nlf_bins, pair_bins, pair_sigma,
                     window_curve, window_curve_pairs, window_sigma, window_sigma_temporal)
-from .report import frames_report, frames_report_motion, summarize, summarize_motion
+from .report import frames_report, frames_report_motion, summarize, summarize_motion, summarize_quality
 from .windows import overlap_weights, plan_tiles
 
 
@@ -205,15 +205,27 @@ class NoiseLevel:
 
 
 # ---- the method-noise report ------------------------------------------------------------------------------------------------------------
+def _niqe_shape(h: int, w: int) -> Tuple[int, ...]:
+    """What ``sn_yuv_niqe_sums`` writes per frame of a picture of h x w luma samples: (2 scales, nbh, nbw whole 96 x 96 blocks, 5 maps, 5 sums)."""
+    from .lib import SN_NIQE_BLOCK, SN_NIQE_MAPS, SN_NIQE_SUMS
+    return (2, h // SN_NIQE_BLOCK, w // SN_NIQE_BLOCK, SN_NIQE_MAPS, SN_NIQE_SUMS)
+
+
 class _ReportState:
     """What a slot holds for the report: the ``_Stat`` of the sums of written minus input of the window's own frames (one row per frame the window
-    writes) and, under ``report_motion``, that of the sums of the written pairs along their vectors (one row per pair) and those vectors."""
+    writes), under ``report_motion`` that of the sums of the written pairs along their vectors (one row per pair) and those vectors, and under
+    ``report_quality`` those of the NIQE sums of the input and of the written frames."""
 
-    def __init__(self, torch, dev, motion, h: int, w: int, tout: int) -> None:
+    def __init__(self, torch, dev, motion, quality, h: int, w: int, tout: int) -> None:
         from .lib import SN_DIFF_STATS, SN_DIFF_STATS_MV
         self.sums = _Stat(torch, dev, "report", tout, [(SN_DIFF_STATS,)], torch.int64)
         self.pair_sums = _Stat(torch, dev, "report_mv", max(tout - 1, 1), [(SN_DIFF_STATS_MV,)], torch.int64) if motion is not None else None
         self.vectors = _Vectors(torch, dev, tout - 1, h, w) if motion is not None else None
+        # report_quality: the NIQE sums of the window's input and written frames, flat and sized for the full frame's blocks; a window's are views of
+        # the leading elements at the grid of its picture (one _Stat each: each is one launch)
+        words = max(tout * int(np.prod(_niqe_shape(h, w))), 1)
+        self.niqe_in = _Stat(torch, dev, "report_quality", words, [()], torch.float64) if quality is not None else None
+        self.niqe_out = _Stat(torch, dev, "report_quality", words, [()], torch.float64) if quality is not None else None
 
 
 class Report:
@@ -224,17 +236,24 @@ class Report:
     temporal correlation of that difference along the motion of the written picture (``sn_yuv_block_motion`` on the frames written, then
     ``sn_yuv_diff_stats_mv``): removed detail that moves with a pan reads as uncorrelated at the same place, and as correlated along its vector.
 
+    ``report_quality="niqe"`` adds a number about the pictures themselves, which the difference cannot give: NIQE (shiftnet_amd/niqe.py) of the luma of every
+    input frame and of the frame written for it, in the format written.  Two more launches behind the report's own (``sn_yuv_niqe_sums`` on ``own`` and
+    on ``written``, the same rectangle); the fit of the blocks and the distance are float64 on the host, in ``collect``.  A picture with fewer than two
+    whole 96 x 96 blocks has no score: nan.  No threshold and no verdict; unvalidated on real footage.
+
     ``launch`` runs on the main stream behind the egress, ``collect`` on the thread that hands the window's frames out."""
 
-    def __init__(self, edge: float, motion, denoise: bool) -> None:
-        self.edge, self.motion, self.denoise = edge, motion, denoise
+    def __init__(self, edge: float, motion, denoise: bool, quality=None) -> None:
+        self.edge, self.motion, self.denoise, self.quality = edge, motion, denoise, quality      # quality: None or niqe.load_params' (mu, cov, win7)
 
     def prepare(self, torch, dev, ofmt, h: int, w: int, tout: int, slots) -> None:
         """Per stream shape: the format written, the edge rule in its codes, and per slot the sums of the largest window (``slot.report``)."""
         self.ofmt, self.h, self.w = ofmt, h, w
         self.code_edge = int(round(self.edge * (1 << (ofmt.bits - 8))))
+        if self.quality is not None:                             # the window's taps, float32 on the device
+            self.win7 = torch.from_numpy(np.ascontiguousarray(self.quality[2], dtype=np.float32)).to(dev)
         for s in slots:
-            s.report = _ReportState(torch, dev, self.motion, h, w, tout)
+            s.report = _ReportState(torch, dev, self.motion, self.quality, h, w, tout)
 
     def launch(self, st, own, written, rect, run) -> None:
         """Written minus input, the window's own n frames of both still on the device (current stream: the main stream); ``collect`` reads the sums."""
@@ -248,6 +267,13 @@ class Report:
             block_motion_yuv(written, self.ofmt, self.h, self.w, rect=rect, out_mv=mv, out_sad=sad)
             run.launches["report_motion"] += 1
             st.pair_sums.launch(n - 1, run, lambda sums: diff_stats_mv_yuv(*head, mv, rect=rect, out_sums=sums))
+        if self.quality is not None:
+            from .io_edges import niqe_sums_yuv
+            shape = (n,) + _niqe_shape(*_picture_size(rect, self.h, self.w))
+            if shape[2] * shape[3]:                              # a picture without a whole block: nothing to launch, and no score
+                for stat, payloads in ((st.niqe_in, own), (st.niqe_out, written)):
+                    stat.launch(int(np.prod(shape)), run,
+                                lambda flat, p=payloads: niqe_sums_yuv(p, self.ofmt, self.h, self.w, self.win7, rect=rect, out=flat.view(shape)))
 
     def collect(self, st, n: int, run) -> None:
         """The sums of the window being handed out.  Windows are handed out in the order they ran: ``run.window_sigma`` and ``run.window_picture`` have
@@ -260,6 +286,14 @@ class Report:
             pairs = [[int(v) for v in row] for row in st.pair_sums.wait(n - 1)[0]] if n >= 2 else []
             run.pair_sums_mv += pairs + [None]
             run.frame_size += [_picture_size(run.window_picture[run.collected], self.h, self.w)] * n
+        if self.quality is not None:
+            from .niqe import frame_score
+            shape = (n,) + _niqe_shape(*_picture_size(run.window_picture[run.collected], self.h, self.w))
+            if shape[2] * shape[3]:
+                a, b = (stat.wait(int(np.prod(shape)))[0].reshape(shape) for stat in (st.niqe_in, st.niqe_out))
+                run.frame_niqe += [(frame_score(a[i], *self.quality[:2]), frame_score(b[i], *self.quality[:2])) for i in range(n)]
+            else:
+                run.frame_niqe += [(float("nan"), float("nan"))] * n
 
     def finish(self, run, stats) -> None:
         bits = self.ofmt.bits
@@ -273,6 +307,11 @@ class Report:
             stats["frame_report_motion"] = frames_report_motion(run.pair_sums_mv, bits, run.frame_size)
             stats["report_motion_summary"] = summarize_motion(stats["frame_report_motion"])
             stats["report_motion_launches"] = run.launches["report_motion"] + run.launches["report_mv"]
+        if self.quality is not None:
+            stats["report_quality"] = "niqe"
+            stats["frame_niqe"] = list(run.frame_niqe)
+            stats["report_quality_summary"] = summarize_quality(run.frame_niqe)
+            stats["report_quality_launches"] = run.launches["report_quality"]
 
 
 # ---- tiles ----------------------------------------------------------------------------------------------------------------------------

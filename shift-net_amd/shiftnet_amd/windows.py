@@ -387,6 +387,32 @@ def report_motion_form(report_motion=None, report=False):
     return report_motion
 
 
+REPORT_QUALITIES = ("niqe",)
+
+
+def quality_form(report_quality=None, niqe_params=None, report=False):
+    """-> None (no quality score: the code path without any of it) or (mu[36], cov[36, 36], win7[7]), the pristine model of niqe.load_params read from
+    ``niqe_params`` (None: tests/golden/niqe_pris_params.npz of the checkout).  ``report_quality``: None | "niqe".  ValueError for anything else, for
+    "niqe" without ``report=True`` (the score is two more columns of the report), for ``niqe_params`` without "niqe", and for a model file that is
+    missing or is not one -- that message names the option."""
+    if report_quality is None:
+        if niqe_params is not None:
+            raise ValueError(f"niqe_params={niqe_params!r} is the model of report_quality='niqe': it needs that option")
+        return None
+    if not (isinstance(report_quality, str) and report_quality in REPORT_QUALITIES):
+        raise ValueError(f"report_quality must be None or 'niqe', got {report_quality!r}")
+    if not (isinstance(report, (bool, np.bool_)) and report):
+        raise ValueError(f"report_quality={report_quality!r} adds the score of the input and of the written frame to the report: it needs report=True")
+    import zipfile
+    from . import niqe
+    path = niqe.default_params_path() if niqe_params is None else niqe_params
+    try:
+        return niqe.load_params(path)
+    except (OSError, KeyError, ValueError, zipfile.BadZipFile) as e:
+        raise ValueError(f"niqe_params: the pristine model of report_quality='niqe' could not be read from {path!r} ({e}); "
+                         "name the file with niqe_params= / --niqe_params") from None
+
+
 def ensemble_form(ensemble=None, ensemble_time=False, tile=None):
     """-> None (no ensemble: the code path without any of it) or (ensemble, time, the members' ops in the order they run).  ``ensemble``: None, 1, 2, 4
     or 8 (ensemble.members); ``ensemble_time``: a bool.  One member -- None or 1 without time -- is no ensemble.  ``tile``: the restorer's parsed tile;

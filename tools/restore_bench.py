@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15, 3.16, 3.17, 3.19, 3.20, 3.21, 3.23, 3.25 and 3.29 (run on the MI355X from the repository root).
+"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15, 3.16, 3.17, 3.19, 3.20, 3.21, 3.23, 3.25, 3.29 and 3.33 (run on the MI355X from the repository root).
 
   kernels : time per pixel of sn_ingest_yuv / sn_egress_yuv / sn_yuv_thumb / sn_yuv_noise_hist (4:2:0 8 bit, 720p x 20 frames; the noise
             histogram on the same frames with noise of sigma 10 as well) beside sn_ingest_u8 / sn_egress_u8 on the same
@@ -48,6 +48,11 @@
             process, the first window of every run left out.  --mode kernels: ``sn_time_crossfade`` on V = 4 frames of 720p, with and without the
             statistic, beside a plain device copy of one such tensor, interleaved; bytes per second at 12 bytes per sample (8 for the copy); each also
             ``_cold``: on six sets of tensors taken in turn, more than the Infinity Cache holds.
+  quality : the no-reference score of the report (3.33).  --mode kernels: time per launch of ``sn_yuv_niqe_sums`` (4:2:0 8 bit, 720p x 16 frames with noise
+            of sigma 10) beside a plain device copy of the same frames' luma planes -- the kernel reads every luma plane once per scale -- and beside
+            sn_yuv_diff_stats on the same frames, interleaved as in the kernels part; and the host's milliseconds per frame for the fit and the
+            distance (niqe.frame_score on those sums).  --mode forward: steady-state wall time per 720p window of the pipelined denoiser (as the report
+            part) with report=True alone and with report_quality="niqe" on top, runs of the two alternating in one process, the first two windows left out.
 Prints one JSON object per part.
 """
 import argparse
@@ -552,6 +557,95 @@ def report_forward(a):
                       "runs": a.runs, "report_summary": {k: round(v, 4) for k, v in seen[True].items()}, **res}))
 
 
+def quality_kernels(a):
+    from shiftnet_amd import niqe
+    from shiftnet_amd.io_edges import niqe_sums_yuv
+    T, H, W = 16, 720, 1280
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    blur, _ = synth.blurred_clip(4, H, W, seed=1)
+    rgb = ingest_u8(torch.from_numpy(np.concatenate([blur] * 4)).cuda(), torch.float32)[0]
+    clean = egress_yuv(rgb, fmt, H, W)
+    noisy = egress_yuv((rgb + torch.randn(rgb.shape, device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * (10.0 / 255)).clamp(0, 1), fmt, H, W)
+    mu, cov, win7 = niqe.load_params(niqe.default_params_path())
+    taps = torch.from_numpy(win7.astype(np.float32)).cuda()
+    sums = niqe_sums_yuv(noisy, fmt, H, W, taps)
+    dsums = torch.empty((T, L.SN_DIFF_STATS), dtype=torch.int64, device="cuda")
+    luma = torch.empty((T, H * W), dtype=torch.uint8, device="cuda")
+    cases = {
+        "niqe_sums_yuv": lambda: niqe_sums_yuv(noisy, fmt, H, W, taps, out=sums),
+        "copy_luma": lambda: luma.copy_(noisy[:, :H * W]),                            # the bytes the kernel reads, once, and as many written
+        "diff_stats_yuv": lambda: diff_stats_yuv(noisy, clean, fmt, H, W, edge=16, out_sums=dsums),      # the report's own launch
+    }
+    for f in cases.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in cases}
+    for _ in range(a.reps):
+        for k, f in cases.items():                                                   # interleaved: every repetition times every kernel
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.inner):
+                f()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.inner)
+    host = sums.cpu().numpy()
+    host_ms, scores = [], []
+    for _ in range(3):
+        for t in range(T):
+            t0 = time.perf_counter()
+            scores.append(niqe.frame_score(host[t], mu, cov))
+            host_ms.append((time.perf_counter() - t0) * 1e3)
+    px = T * H * W
+    res = {k: {"us_per_launch": summary([m * 1e3 for m in v]), "us_per_frame": summary([m * 1e3 / T for m in v]),
+               "ps_per_pixel": summary([m * 1e9 / px for m in v])} for k, v in ms.items()}
+    print(json.dumps({"part": "quality", "mode": "kernels", "frames": T, "size": [H, W], "blocks": list(sums.shape[2:4]), "reps": a.reps, "inner": a.inner,
+                      "host_ms_per_frame": summary(host_ms[T:]), "niqe_of_the_noisy_frames": summary(scores[:T]), **res}))
+
+
+def quality_forward(a):
+    H, W, one_len, nwin = 720, 1280, 16, a.windows
+    n = one_len * nwin
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    blur, _ = synth.blurred_clip(8, H, W, seed=2)
+    rgb = ingest_u8(torch.from_numpy(blur).cuda(), torch.float32)[0]
+    g = torch.Generator("cuda").manual_seed(1)
+    frames = []
+    for i in range(n):                                                               # fresh noise of sigma 10 on every frame, as the report part
+        j = i % 14
+        x = rgb[j if j < 8 else 14 - j][None]
+        frames.append(egress_yuv((x + torch.randn(x.shape, device="cuda", generator=g) * (10.0 / 255)).clamp(0, 1), fmt, H, W)[0].cpu().numpy())
+    net = restore.load_net("denoise_small", "synthetic", "bf16")
+    seen = {}
+
+    def run(quality):
+        vr = restore.VideoRestorer(net, one_len, sigma=10.0, pipeline=True, report=True, report_quality=quality)
+        stamps = []
+        t0 = time.perf_counter()
+        for i, p in enumerate(vr.restore(iter(frames), fmt, H, W)):
+            if (i + 1) % one_len == 0:
+                stamps.append(time.perf_counter())
+        total = time.perf_counter() - t0
+        seen[quality] = vr.stats.get("report_quality_summary")
+        gaps = [(b - c) * 1e3 for b, c in zip(stamps[1:], stamps[:-1])]
+        return {"total_s": total, "window_wall_ms": gaps[1:], "window_forward_ms": vr.stats["window_forward_ms"][2:]}
+
+    run(None)                                                                        # warm-up: code objects, engine buffers
+    run("niqe")
+    runs = {"report": [], "report_quality": []}
+    for _ in range(a.runs):
+        runs["report"].append(run(None))
+        runs["report_quality"].append(run("niqe"))
+    res = {}
+    for k, rs in runs.items():
+        res[k] = {"window_wall_ms": summary([g for r in rs for g in r["window_wall_ms"]]),
+                  "window_wall_ms_per_run": [round(statistics.median(r["window_wall_ms"]), 2) for r in rs],
+                  "window_forward_ms": summary([g for r in rs for g in r["window_forward_ms"]]), "total_s": [round(r["total_s"], 3) for r in rs]}
+    print(json.dumps({"part": "quality", "mode": "forward", "variant": "denoise_small", "dtype": "bf16", "one_len": one_len, "windows": nwin, "size": [H, W],
+                      "runs": a.runs, "report_quality_summary": {k: round(v, 4) for k, v in seen["niqe"].items()}, **res}))
+
+
 def _tile_word(word):
     return None if word == "full" else restore.tile_arg(word)
 
@@ -855,7 +949,7 @@ def picture_part(a):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion", "tiles", "overlap"])
+    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion", "tiles", "overlap", "quality"])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--inner", type=int, default=200)
     ap.add_argument("--windows", type=int, default=8)
@@ -867,7 +961,7 @@ if __name__ == "__main__":
                     "csrc/sn_yuv.hip alone; its sn_ingest_yuv / sn_egress_yuv are timed beside this build's.  nlf and motion parts in kernels mode: a library "
                     "built from another commit's whole csrc; its seven noise-histogram entry points are timed beside this build's, at 8 and 10 bit")
     ap.add_argument("--only_cases", default=None, metavar="WORDS", help="kernels part: time only the cases whose name contains one of these comma-separated words")
-    ap.add_argument("--mode", choices=["forward", "kernels", "quality"], default="forward", help="picture, nlf, report, motion and tiles parts: which measurement "
+    ap.add_argument("--mode", choices=["forward", "kernels", "quality"], default="forward", help="picture, nlf, report, motion, tiles, overlap and quality parts: which measurement "
                     "(quality: the tiles part alone)")
     ap.add_argument("--picture", choices=["auto", "fixed"], default="auto", help="picture part, forward mode: VideoRestorer(picture='auto') or the rectangle itself")
     ap.add_argument("--tile", action="append", default=None, metavar="{full,N,HxW}", help="tiles part, forward mode: a form to run (repeat for several, which then alternate)")
@@ -882,4 +976,5 @@ if __name__ == "__main__":
          "report": report_kernels if a.mode == "kernels" else report_forward,
          "motion": motion_kernels if a.mode == "kernels" else motion_forward,
          "tiles": tiles_quality if a.mode == "quality" else tiles_forward,
-         "overlap": overlap_kernels if a.mode == "kernels" else overlap_forward}[a.part](a)
+         "overlap": overlap_kernels if a.mode == "kernels" else overlap_forward,
+         "quality": quality_kernels if a.mode == "kernels" else quality_forward}[a.part](a)
