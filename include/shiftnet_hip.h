@@ -871,6 +871,40 @@ int sn_yuv_niqe_sums(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rec
                      const float* win7 /* device, 7 taps */, double* dst /* [T][2][nbh][nbw][5][5] */,
                      int T, int H, int W, void* stream);
 
+/* ---- full-reference quality: the per-pixel part of SSIM (csrc/sn_ssim.hip; a new symbol, SN_ABI_VERSION stays 20) -----------------------------------
+ * The video restorer can compare what it read and what it wrote with a ground-truth stream (VideoRestorer.restore(..., gt=...)): PSNR of all three
+ * planes comes from the exact sums of sn_yuv_diff_stats with a set to the truth, and SSIM of the luma from sn_yuv_ssim_sums; shiftnet_amd/fullref.py
+ * does the rest on the host in float64.  The definition is the Y-channel SSIM of the evaluation harnesses (upstream's _ssim_cly): an 11 x 11 Gaussian
+ * window, the border replicated, every position counted.  sn_ssim_u8 above is the harness CLI's volume SSIM over interleaved 8-bit RGB: another formula
+ * on another layout.
+ *   a, b, fmt, rect (NULL: the whole frame), H, W and stream exactly as sn_yuv_diff_stats takes them.  Only the luma planes are read and samples are
+ *   taken as stored (a 16-bit word may hold up to 65535).  The picture is h x w, the rectangle or the frame; coordinates below count from its first
+ *   sample, and cy / cx clamp to 0 .. h - 1 / 0 .. w - 1: the border is replicated at the edge of the picture, not of the frame, so a rectangle gives
+ *   what the cropped stream gives.
+ * Constants: g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)) / sum_j exp(-(j - 5)^2 / (2 * 1.5^2)), i = 0 .. 10, computed in float64 on the host and rounded once
+ *   to float32; the window is their outer product.  p = 2^bits - 1, C1 = (0.01 p)^2, C2 = (0.03 p)^2, float64 expressions rounded once to float32;
+ *   mid = 2^(bits - 1).  At 8 bit this is the harnesses' formula on their 0 .. 255 scale; at 10 bit it is the same formula on codes * 255 / 1023,
+ *   because SSIM does not change when the constants scale with the data.
+ * Float32, every product, sum and difference rounded on its own (no FMA); an 11-tap sum adds its products p0 .. p10 from the outside in,
+ *   ((((p0 + p10) + (p1 + p9)) + (p2 + p8)) + (p3 + p7)) + (p4 + p6)) + p5.  With A = a - mid and B = b - mid (exact):
+ *     r_X(y, x) = sum_i g[i] * X(y, cx(x + i - 5))  for the five maps X = A, B, A * A, B * B, A * B  (the product first, then the tap)
+ *     G_X(y, x) = sum_j g[j] * r_X(cy(y + j - 5), x)
+ *     mu_a = G_A + mid,  mu_b = G_B + mid                       (the means of the codes themselves)
+ *     s_aa = G_AA - G_A * G_A,  s_bb = G_BB - G_B * G_B,  s_ab = G_AB - G_A * G_B      (variances do not move with mid; the squares are smaller)
+ *     map  = ((2 * (mu_a * mu_b) + C1) * (2 * s_ab + C2)) / (((mu_a * mu_a + mu_b * mu_b) + C1) * ((s_aa + s_bb) + C2))    (correctly rounded division)
+ * dst[t][i][j] is the float64 sum of map (converted to double) over tile (i, j) of frame t: positions y = SN_SSIM_TILE i .. , x = SN_SSIM_TILE j .. of
+ * the picture, SN_SSIM_TILE each way, the last row and column of tiles partial; nty = ceil(h / SN_SSIM_TILE), ntx = ceil(w / SN_SSIM_TILE).  All h w
+ * positions count; a frame's SSIM is the sum of its tiles over h w.  dst:[T][nty][ntx] doubles is OVERWRITTEN, never added to; nothing outside those
+ * words is written.  One workgroup owns one (frame, tile), adds in one fixed order and writes its double with a plain store; there are no atomics.
+ * The result does not depend on the launch geometry or the schedule, and a second launch gives the same bits.  a == b is legal: numerator and
+ * denominator are then the same float32 expressions, map is exactly 1 everywhere, and every tile's sum is exactly its number of positions.
+ * (tests/ssim_ref.py restates it in float64; the kernel's per-frame SSIM is within 1e-5 of what the harnesses' code gives.)
+ * SN_EINVAL before anything is launched: everything sn_yuv_diff_stats refuses (it takes no edge); dst not 8-byte aligned; a tile grid, nty * ntx,
+ * beyond the bound sn_yuv_diff_stats puts on its units (2^31 - 1 - 2^18). */
+#define SN_SSIM_TILE 32
+int sn_yuv_ssim_sums(const uint8_t* a, const uint8_t* b, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */,
+                     double* dst /* [T][nty][ntx] */, int T, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,8 @@ the statistics of the same payloads' luma (csrc/sn_yuv_stats.hip), each for one 
                temporal correlation;
 ``niqe_sums_yuv``: float64 sums of the locally normalised luma and of its neighbour products per 96 x 96 block at two scales (csrc/sn_niqe.hip), for the
                no-reference quality score of the report (shiftnet_amd/niqe.py);
+``ssim_sums_yuv``: float64 sums of the SSIM map of the luma of two sets of payloads per 32 x 32 tile (csrc/sn_ssim.hip), for the report's comparison with a
+               ground-truth stream (shiftnet_amd/fullref.py);
 ``tile_accumulate``: one tile's float32 result added into the window's float32 canvas with its feather weights (csrc/sn_tile.hip), for the tiled
                restorer (``VideoRestorer(tile=...)``);
 ``geo_transform`` / ``geo_accumulate``: a tensor mirrored, transposed and reversed in time, and a float32 result mapped back and added into a float32
@@ -430,6 +432,29 @@ def niqe_sums_yuv(payload_u8: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, win
     with torch.cuda.device(dev):
         L.check(L.load().sn_yuv_niqe_sums(payload_u8.data_ptr(), fmt, r, win7_dev.data_ptr(), y.data_ptr(), T, H, W,
                                           torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_niqe_sums")
+    return y
+
+
+def ssim_tiles(h: int, w: int) -> tuple:
+    """(nty, ntx): the tiles of ``sn_yuv_ssim_sums`` for a picture of h x w luma samples, the last row and column partial."""
+    return (-(-int(h) // L.SN_SSIM_TILE), -(-int(w) // L.SN_SSIM_TILE))
+
+
+def ssim_sums_yuv(ref: torch.Tensor, out: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, rect=None, out_sums: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ref and out: [T, frame_bytes] uint8 on a HIP device each, the same format and size (only the luma plane of each payload is read); they may be the
+    same tensor -> float64 [T, nty, ntx]: per payload and 32 x 32 tile of the picture the sum of the SSIM map of the two luma planes that
+    include/shiftnet_hip.h states under sn_yuv_ssim_sums (an 11 x 11 Gaussian window, the border replicated at the picture's edge, constants that follow
+    2^bits - 1).  ``rect=(x0, y0, w, h)``: the sums of that picture of the stream.  ``out_sums``: a tensor of that shape to overwrite.
+    fullref.ssim_from_tiles turns a payload's tiles into its SSIM, on the host."""
+    T, dev = _payload(ref, fmt, H, W)
+    assert _payload(out, fmt, H, W) == (T, dev)
+    r = None if rect is None else _rect(rect, fmt, H, W)
+    shape = (T,) + ssim_tiles(H if r is None else r.h, W if r is None else r.w)
+    y = out_sums if out_sums is not None else torch.empty(shape, dtype=torch.float64, device=dev)
+    assert tuple(y.shape) == shape and y.dtype == torch.float64 and y.is_contiguous() and y.device == dev
+    with torch.cuda.device(dev):
+        L.check(L.load().sn_yuv_ssim_sums(ref.data_ptr(), out.data_ptr(), fmt, r, y.data_ptr(), T, H, W,
+                                          torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_ssim_sums")
     return y
 
 

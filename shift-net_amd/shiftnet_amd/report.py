@@ -170,6 +170,7 @@ class MotionReport:
 
 
 COLUMNS_MV = tuple(f.name for f in fields(MotionReport))
+COLUMNS_F = ("psnr_y_in", "psnr_y_out", "psnr_u_in", "psnr_u_out", "psnr_v_in", "psnr_v_out", "ssim_in", "ssim_out")      # gt: fullref.FIELDS, against the truth
 COLUMNS_Q = ("niqe_in", "niqe_out")                           # report_quality="niqe": the score of the input and of the written frame (shiftnet_amd/niqe.py)
 
 
@@ -253,12 +254,14 @@ def summary_line_quality(summary: Dict[str, float]) -> str:
     return ", ".join(f"{k} {summary[k]:.3f}" for k in COLUMNS_Q)
 
 
-def format_report(frames: Iterable[FrameReport], how: str = "", motion: Optional[Iterable[MotionReport]] = None, quality: Optional[Iterable] = None) -> str:
+def format_report(frames: Iterable[FrameReport], how: str = "", motion: Optional[Iterable[MotionReport]] = None, quality: Optional[Iterable] = None,
+                  fullref: Optional[Iterable] = None) -> str:
     """The report file: '#' header lines that name the columns, one line per written frame (sigma '-' where the window had none), and the medians of
     ``summarize`` as the last line, '# median'.  Floats are written so that ``parse_report`` reads back equal reports.  ``motion``: one MotionReport
     per frame; every line, the median line and the '#' column line then gain its four columns (``parse_report_motion`` reads them back).  ``quality``:
-    one (niqe_in, niqe_out) per frame; they gain those two columns, last (``parse_report_quality``).  Without either the text is what it was before
-    there was such a part."""
+    one (niqe_in, niqe_out) per frame; they gain those two columns (``parse_report_quality``).  ``fullref``: one fullref.FullRef per frame (``gt``); they
+    gain its eight columns, after all others (``parse_report_fullref``), ``inf`` where a plane equals the truth's.  Without any of them the text is what
+    it was before there was such a part."""
     frames = list(frames)
     med = summarize(frames)
     lines = ["# method noise: written minus input, one line per written frame" + (f" ({how})" if how else ""),
@@ -288,6 +291,18 @@ def format_report(frames: Iterable[FrameReport], how: str = "", motion: Optional
         for r, q in zip(rows, quality):
             r += [_word(q[0]), _word(q[1])]
         meds += [_word(qmed[c]) for c in COLUMNS_Q]
+    if fullref is not None:
+        from .fullref import summarize_fullref
+        fullref = [tuple(float(v) for v in f) for f in fullref]
+        if len(fullref) != len(frames) or any(len(f) != len(COLUMNS_F) for f in fullref):
+            raise ValueError(f"{len(frames)} frames and {len(fullref)} full-reference rows of {len(COLUMNS_F)} numbers")
+        fmed = summarize_fullref(fullref)["median"]
+        lines.append("# psnr_*_in, psnr_*_out: dB, of the input (as written) and of the written frame against the ground truth, p = 2^bits - 1 (inf: the planes "
+                     "are equal); ssim_in, ssim_out: SSIM of the luma codes, 11 x 11 Gaussian window, replicated border")
+        cols += COLUMNS_F
+        for r, f in zip(rows, fullref):
+            r += [_word(v) for v in f]
+        meds += [_word(fmed[c]) for c in COLUMNS_F]
     lines.append("# " + " ".join(cols))
     lines += [" ".join(r) for r in rows]
     lines.append("# median - - - " + " ".join(meds))
@@ -295,14 +310,16 @@ def format_report(frames: Iterable[FrameReport], how: str = "", motion: Optional
 
 
 def _parse(text: str):
-    """(FrameReport, MotionReport or None, (niqe_in, niqe_out) or None) of every line of a report file; a line has the columns of a frame, or those and the four of its motion
-    part ('#' lines are comments, the medians among them: ``summarize`` makes them again).  Where the '#' line that names the columns ends in
-    ``niqe_in niqe_out`` every line has those two columns more, last; a file without them is read as it always was."""
+    """(FrameReport, MotionReport or None, (niqe_in, niqe_out) or None, the eight numbers of fullref.FullRef or None) of every line of a report file; a
+    line has the columns of a frame, or those and the four of its motion part ('#' lines are comments, the medians among them: ``summarize`` makes them
+    again).  Where the '#' line that names the columns ends in the eight names of COLUMNS_F every line has those columns more, last; where what stands
+    before them (or the line, without them) ends in ``niqe_in niqe_out``, those two more; a file without either is read as it always was."""
     out = []
-    nf, nm, nq = len(COLUMNS), len(COLUMNS_MV), len(COLUMNS_Q)
+    nf, nm, nq, nF = len(COLUMNS), len(COLUMNS_MV), len(COLUMNS_Q), len(COLUMNS_F)
     named = [line.split()[1:] for line in text.splitlines() if line.startswith("# " + COLUMNS[0] + " ")]
-    q = nq if any(tuple(n[-nq:]) == COLUMNS_Q for n in named) else 0
-    widths = (nf + q, nf + nm + q)
+    f = nF if any(tuple(n[-nF:]) == COLUMNS_F for n in named) else 0
+    q = nq if any(tuple(n[len(n) - f - nq:len(n) - f]) == COLUMNS_Q for n in named) else 0
+    widths = (nf + q + f, nf + nm + q + f)
     for ln, line in enumerate(text.splitlines(), 1):
         body = line.split("#", 1)[0].split()
         if not body:
@@ -313,21 +330,29 @@ def _parse(text: str):
             vals = [int(body[0]), int(body[1]), None if body[2] == "-" else float(body[2])] + [float(w) for w in body[3:]]
         except ValueError:
             raise ValueError(f"line {ln}: not a report line: {line!r}") from None
+        full = tuple(vals[len(vals) - f:]) if f else None
+        vals = vals[:len(vals) - f]
         rest = vals[nf:len(vals) - q]
-        out.append((FrameReport(*vals[:nf]), MotionReport(*rest) if rest else None, tuple(vals[-q:]) if q else None))
+        out.append((FrameReport(*vals[:nf]), MotionReport(*rest) if rest else None, tuple(vals[-q:]) if q else None, full))
     return out
 
 
 def parse_report(text: str) -> List[FrameReport]:
     """The frames of a report file, with or without a motion part."""
-    return [f for f, _, _ in _parse(text)]
+    return [f for f, _, _, _ in _parse(text)]
 
 
 def parse_report_motion(text: str) -> List[Optional[MotionReport]]:
     """The motion part of every line of a report file; None for a line without one."""
-    return [m for _, m, _ in _parse(text)]
+    return [m for _, m, _, _ in _parse(text)]
 
 
 def parse_report_quality(text: str) -> List[Optional[tuple]]:
     """The (niqe_in, niqe_out) of every line of a report file; None for a line without them."""
-    return [q for _, _, q in _parse(text)]
+    return [q for _, _, q, _ in _parse(text)]
+
+
+def parse_report_fullref(text: str) -> List[Optional[tuple]]:
+    """The fullref.FullRef of every line of a report file; None for a line without its eight columns."""
+    from .fullref import FullRef
+    return [None if f is None else FullRef(*f) for _, _, _, f in _parse(text)]

@@ -33,6 +33,9 @@ anyway (``sn_egress_yuv_mix``): amount 0 is the input byte for byte.  The blend 
 Noise level (``sigma``, ``noise_model``; denoise variants), method-noise report (``report``), tiles (``tile``), the self-ensemble (``ensemble``) and
 windows that overlap in time (``window_overlap``): each is a part of its own, described at its class in shiftnet_amd/restore_parts.py (``NoiseLevel``,
 ``Report``, ``Tiles``, ``Ensemble``, ``Overlap``); the restorer holds each or None and calls it by name.
+
+Ground truth (``restore(..., gt=...)``, off by default; needs ``report``): a second stream, the clean frames of which the input is a degraded copy, goes
+through the pipeline beside the input, and the report gains PSNR and SSIM of the input and of every frame written against it (shiftnet_amd/fullref.py).
 """
 from __future__ import annotations
 
@@ -75,6 +78,7 @@ class _Slot:
         self.sums = None                                          # picture="auto": _Stat of the window's row and column sums
         self.noise = self.report = None                           # what the parts NoiseLevel and Report keep per slot (restore_parts.py)
         self.dev_ref = None                                       # a mix or a report with another format out: the window's input payloads in the format written
+        self.pin_gt = self.dev_gt = None                          # restore(gt=...): the truth for the frames the window writes, payloads of the format written
 
 
 class _Run:
@@ -95,6 +99,7 @@ class _Run:
         self.launches = {"noise": 0, "nlf": 0, "nlf_map": 0, "picture": 0, "thumb": 0, "noise_pairs": 0, "nlf_pairs": 0, "report": 0, "motion": 0,
                          "report_motion": 0, "report_mv": 0,      # report_motion: the block matcher on the written frames, the sums along its vectors
                          "report_quality": 0,                     # report_quality: the NIQE sums of the input and of the written frames
+                         "fullref": 0,                            # gt: the difference sums and the SSIM sums of input and written frames against the truth
                          "tile": 0,                               # tile: the tiles added into the canvas
                          "geo_transform": 0, "geo_accumulate": 0, # ensemble: the members' inputs made, their results added into the canvas
                          "overlap": 0}                            # window_overlap: the cross-fades of shared frames
@@ -107,6 +112,9 @@ class _Run:
         self.pair_sums_mv: List = []                              # report_motion: the 8 sums of the pair (frame, frame + 1) of every frame handed out, or None
         self.frame_size: List = []                                # ... and the (h, w) of the picture its window was restored in
         self.frame_niqe: List = []                                # report_quality: (niqe_in, niqe_out) of every frame handed out
+        self.gt = None                                            # gt: the iterator over the truth's payloads, and how many the stager has taken
+        self.gt_taken = 0
+        self.frame_fullref: List = []                             # gt: the fullref.FullRef of every frame handed out
         self.collected = 0                                        # windows handed out
         self.src = None                                           # the frame source
 
@@ -289,6 +297,20 @@ class VideoRestorer:
     that names the option).  The model was fitted on natural stills, on the Y of BT.601 R'G'B'; the stream's own luma is fed, whatever its matrix.
     Denoising can move the score either way -- over-smoothing is not natural either.  No threshold, no verdict, nothing fed back; **unvalidated on
     real footage**, and on synthetic weights it says nothing about the network.  No byte written changes.
+    gt (an argument of ``restore()``, not of the constructor; needs ``report=True``, a ValueError naming it otherwise): None -- today's launches, bytes,
+    stats keys and report; an iterable of payloads -- a ground-truth stream, frame i the truth of written frame i, **in the format written**
+    (``out_format`` if given, else the input's) and of the stream's size: the standard experiment of a clean clip, a degraded copy and its restoration
+    compared with the clip, on every frame and under every other option.  The stager takes from ``gt`` exactly the frames its window will write (all
+    it restores, or fewer under ``window_overlap``) and uploads them on the side stream beside the window's input.  Behind the report's launches four
+    more (main stream): ``sn_yuv_diff_stats`` of (truth, input as written) and of (truth, written), edge 0 -- exact sums, PSNR of Y, U and V with
+    p = 2^bits - 1 -- and ``sn_yuv_ssim_sums`` of the same two pairs -- the Y-channel SSIM of the evaluation harnesses on the luma codes, constants
+    following 2^bits - 1 (shiftnet_amd/fullref.py) -- on the same rectangle as the rest of the report under ``picture``.  ``stats["frame_fullref"]`` is
+    one fullref.FullRef per written frame (``psnr_y_in``, ``psnr_y_out``, ... ``ssim_in``, ``ssim_out``: ``_in`` the input against the truth, ``_out``
+    the frame written; ``inf`` where a plane equals the truth's), ``stats["fullref_summary"]`` their means (``inf`` frames left out and counted) and
+    medians, ``stats["fullref_launches"]`` the launches, 4 per window.  A ``gt`` that ends before the frames written do is a ValueError naming ``gt`` and
+    the frame; a payload of another size likewise; payloads beyond the input's last frame are not looked for, so a longer ``gt`` goes unnoticed.
+    **Luma SSIM only; no MS-SSIM, no VMAF; the truth must be frame-aligned by the caller -- no offset is searched; no threshold, no verdict, nothing fed
+    back into ``amount`` or ``sigma``.**  No byte written changes.
     tile: None -- the network is given whole frames, today's launches, bytes and stats keys; ``(th, tw)`` or an int ``n`` (``(n, n)``) -- the forward of
     every window runs on overlapping th x tw rectangles of the window's padded frames instead, one after the other in row-major order, each on the
     contiguous crop of the input tensors (and of the noise plane under ``noise_model``; a flat sigma is broadcast to the tile's shape), and
@@ -491,11 +513,14 @@ class VideoRestorer:
         pin = slot.pin_in.numpy()
         for i, f in enumerate(frames):
             pin[i] = f
+        n_gt = self._take_gt(slot, (t - PAST - FUTURE) if written is None else written)
         with torch.cuda.stream(self.s_in):
             if slot.used:
                 self.s_in.wait_event(slot.ev_done)               # the forward that last read this slot's tensors has finished
             payloads = slot.dev_in[:t]
             payloads.copy_(slot.pin_in[:t], non_blocking=True)
+            if n_gt:                                             # behind the same events as dev_in: ev_h2d frees the pinned twin, ev_ready orders the report's reads
+                slot.dev_gt[:n_gt].copy_(slot.pin_gt[:n_gt], non_blocking=True)
             slot.ev_h2d.record(self.s_in)
             if self.picture_mode == "auto":
                 # the sums of the payloads just uploaded; this thread waits for the event behind their copy to the host -- the side stream's own
@@ -516,6 +541,25 @@ class VideoRestorer:
                 ingest_yuv(payloads, self.fmt, self.h, self.w, hp, wp, torch.float32, out=x32, rect=rect)
             slot.ev_ready.record(self.s_in)
         return t
+
+    def _take_gt(self, slot: _Slot, n: int) -> int:
+        """The truth for the n frames the window being staged will write, from the run's ``gt`` into the slot's pinned buffer -> n (0 without ``gt``).
+        Every frame is written once and in order, so the next n payloads of ``gt`` are theirs; the pinned buffer is free (``_stage`` has waited for ev_h2d)."""
+        run = self.run
+        if run.gt is None:
+            return 0
+        pin = slot.pin_gt.numpy()
+        for i in range(n):
+            try:
+                f = next(run.gt)
+            except StopIteration:
+                raise ValueError(f"gt ended early: it has no payload for frame {run.gt_taken} of the stream written") from None
+            f = np.asarray(f, dtype=np.uint8).reshape(-1)
+            if f.size != self.ofb:
+                raise ValueError(f"gt: frame {run.gt_taken} is a payload of {f.size} bytes, the format written and the size say {self.ofb}")
+            pin[i] = f
+            run.gt_taken += 1
+        return n
 
     def _forward(self, x, x32, nm, crop=None):
         """The one call of the network: x [1, t, 3, hp, wp], x32 its float32 twin or None, nm the noise plane [1, t, 1, hp, wp] or None (the deblur
@@ -589,7 +633,7 @@ class VideoRestorer:
             dither = None if self.dither is None else (self.dither_seed, slot.t0)
             egress_yuv(out, self.ofmt, self.h, self.w, dst=written, rect=rect, dither=dither, mix=self.mix, ref=own if self.mix is not None else None)
             if self.report_part is not None:
-                self.report_part.launch(slot.report, own, written, rect, run)
+                self.report_part.launch(slot.report, own, written, rect, run, gt=slot.dev_gt[:n] if run.gt is not None else None)
             slot.ev_done.record(main)
         with torch.cuda.stream(self.s_out):
             self.s_out.wait_event(slot.ev_done)
@@ -643,11 +687,21 @@ class VideoRestorer:
         return self.run.src
 
     # -- drivers -------------------------------------------------------------------------------------------------------------------
-    def restore(self, frames: Iterable[np.ndarray], fmt, height: int, width: int) -> Iterator[np.ndarray]:
-        """frames: iterable of uint8 payloads (``fmt.frame_bytes(height, width)`` each) -> the restored payloads, in order."""
+    def restore(self, frames: Iterable[np.ndarray], fmt, height: int, width: int, gt=None) -> Iterator[np.ndarray]:
+        """frames: iterable of uint8 payloads (``fmt.frame_bytes(height, width)`` each) -> the restored payloads, in order.  gt: None, or an iterable of
+        ground-truth payloads in the format WRITTEN and of the stream's size, frame i the truth of written frame i (needs ``report=True``; see the class)."""
         torch = self.torch
+        if gt is not None and self.report_part is None:
+            raise ValueError("gt adds PSNR and SSIM against the truth to the report: it needs report=True")
         self._prepare(fmt, height, width)
         self._reset()
+        if gt is not None:
+            self.run.gt = iter(gt)
+            for s in self.slots:                                 # once per stream shape, and only for a run that asks
+                if s.pin_gt is None:
+                    s.pin_gt = torch.empty((self.one_len, self.ofb), dtype=torch.uint8).pin_memory()
+                    s.dev_gt = torch.empty((self.one_len, self.ofb), dtype=torch.uint8, device=self.dev)
+            self.report_part.prepare_gt(torch, self.dev, self.one_len, self.slots)
         for slot in self.slots:
             slot.used = False
         if self.overlap is not None:

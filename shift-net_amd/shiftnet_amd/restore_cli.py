@@ -145,6 +145,13 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--niqe_params", default=None, metavar="FILE",
                     help="--report_quality niqe: the pristine model (an .npz with mu_pris_param, cov_pris_param, gaussian_window); default: "
                          "tests/golden/niqe_pris_params.npz of the checkout")
+    ap.add_argument("--gt", default=None, metavar="FILE",
+                    help="--report only: a ground-truth Y4M of the width, height and C tag of the stream WRITTEN (--out_format if given), frame i the truth "
+                         "of written frame i; adds eight columns, PSNR of Y, U and V and SSIM of the luma of every input frame and of the frame written "
+                         "for it against the truth (psnr_y_in psnr_y_out ... ssim_in ssim_out; peak and SSIM constants follow 2^bits - 1; SSIM is the "
+                         "Y-channel SSIM of the evaluation harnesses: 11 x 11 Gaussian window, replicated border, every frame and every position); sums on "
+                         "the device; LUMA SSIM ONLY, no MS-SSIM or VMAF; the streams must be frame-aligned, no offset is searched; no threshold, no "
+                         "verdict, nothing fed back; changes no byte written; default: the report as it is without")
     ap.add_argument("--tile", type=tile_arg, default=None, metavar="{N,HxW}",
                     help="for frames whose activations do not fit the device: run the network on overlapping tiles of H x W samples (N: N x N) of every "
                          "window, one after the other, and blend their results with feather weights on the device; both sides multiples of 4 (8 for "
@@ -239,6 +246,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         quality_form(report_quality, a.niqe_params, a.report is not None)
     except ValueError as e:
         ap.error(f"--report_quality / --niqe_params: {str(e).replace('report=True', '--report')}")
+    if a.gt is not None and a.report is None:                     # as above: before any file is opened
+        ap.error("--gt adds its columns to the report: it needs --report")
     if a.tile is None and a.tile_overlap is not None:             # as above: before any file is opened
         ap.error("--tile_overlap needs --tile")
     tile_overlap = DEFAULT_TILE_OVERLAP if a.tile_overlap is None else a.tile_overlap
@@ -293,9 +302,22 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         picture, picture_how = _listed(ap, "--picture", picture, pic.read_pictures), "listed"
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
     fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
+    fgt = None
     try:
         rd = Y4MReader(fin)
         hd = rd.header
+        gt = None
+        if a.gt is not None:                                      # judged against the header of the stream written, before the network is loaded
+            try:
+                fgt = open(a.gt, "rb")
+                gt = Y4MReader(fgt)
+            except (OSError, ValueError) as e:
+                ap.error(f"--gt {a.gt}: {e}")
+            want, got = output_header(hd, a.out_format), gt.header
+            if (got.width, got.height) != (want.width, want.height):
+                ap.error(f"--gt {a.gt}: the truth is {got.width}x{got.height}, the stream written is {want.width}x{want.height}")
+            if (got.bits, got.chroma_code) != (want.bits, want.chroma_code):
+                ap.error(f"--gt {a.gt}: the truth is C{got.chroma}, the stream written is C{want.chroma}: the truth must be in the format written")
         matrix = a.matrix or ("bt709" if hd.height >= 720 else "bt601")
         rng = a.range or (hd.color_range if hd.color_range in ("full", "limited") else "limited")
         log(f"input: {hd.width}x{hd.height} C{hd.chroma} F{hd.fps}; matrix {matrix}{'' if a.matrix else ' (default)'}, range {rng}"
@@ -326,7 +348,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         wr = Y4MWriter(fout, output_header(hd, a.out_format))
         t0 = time.perf_counter()
         n = 0
-        for p in vr.restore(rd, fmt, hd.height, hd.width):
+        for p in vr.restore(rd, fmt, hd.height, hd.width, gt=gt):
             wr.write(p)
             n += 1
             if n % max(a.one_len, 1) == 0:
@@ -370,7 +392,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 f"min {min(ws):.2f} / median {float(np.median(ws)):.2f} / max {max(ws):.2f} over {len(ws)} window{'' if len(ws) == 1 else 's'}")
         if a.report is not None:
             fr = vr.stats["frame_report"]
-            _write_out(a.report, _text_writer(rep.format_report), fr, f"edge {a.report_edge:g}", vr.stats.get("frame_report_motion"), vr.stats.get("frame_niqe"))
+            _write_out(a.report, _text_writer(rep.format_report), fr, f"edge {a.report_edge:g}", vr.stats.get("frame_report_motion"), vr.stats.get("frame_niqe"),
+                       vr.stats.get("frame_fullref"))
             log(f"report (written minus input, medians over {len(fr)} frame{'' if len(fr) == 1 else 's'}, unvalidated on real footage): "
                 f"{rep.summary_line(vr.stats['report_summary'])}")
             if report_motion is not None:
@@ -379,9 +402,15 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             if report_quality is not None:
                 log(f"quality (NIQE of the luma, medians over the frames with a score; no verdict, unvalidated on real footage): "
                     f"{rep.summary_line_quality(vr.stats['report_quality_summary'])}")
+            if gt is not None:
+                from .fullref import summary_line_fullref
+                log(f"against the ground truth ({a.gt}; PSNR in dB, SSIM of the luma; _in the input, _out the frames written; no verdict): "
+                    f"{summary_line_fullref(vr.stats['fullref_summary'])}")
     finally:
         if fin is not sys.stdin.buffer:
             fin.close()
         if fout is not sys.stdout.buffer:
             fout.close()
+        if fgt is not None:
+            fgt.close()
     return 0

@@ -226,6 +226,20 @@ class _ReportState:
         words = max(tout * int(np.prod(_niqe_shape(h, w))), 1)
         self.niqe_in = _Stat(torch, dev, "report_quality", words, [()], torch.float64) if quality is not None else None
         self.niqe_out = _Stat(torch, dev, "report_quality", words, [()], torch.float64) if quality is not None else None
+        self.truth = None                                        # restore(gt=...): a _TruthState, made by Report.prepare_gt for a run that asks
+
+
+class _TruthState:
+    """What a slot holds for a report against a ground-truth stream: the ``_Stat``s of the difference sums (one row per written frame) and of the SSIM
+    tile sums (flat and sized for the full frame's tiles; a window's are views of the leading elements at the grid of its picture) of the pairs
+    (truth, input as written) and (truth, written).  One _Stat each: each is one launch."""
+
+    def __init__(self, torch, dev, h: int, w: int, tout: int) -> None:
+        from .io_edges import ssim_tiles
+        from .lib import SN_DIFF_STATS
+        words = tout * int(np.prod(ssim_tiles(h, w)))
+        self.sums = [_Stat(torch, dev, "fullref", tout, [(SN_DIFF_STATS,)], torch.int64) for _ in range(2)]
+        self.ssim = [_Stat(torch, dev, "fullref", words, [()], torch.float64) for _ in range(2)]
 
 
 class Report:
@@ -241,6 +255,11 @@ class Report:
     on ``written``, the same rectangle); the fit of the blocks and the distance are float64 on the host, in ``collect``.  A picture with fewer than two
     whole 96 x 96 blocks has no score: nan.  No threshold and no verdict; unvalidated on real footage.
 
+    ``restore(gt=...)`` compares with a ground-truth stream, which neither of the above can: PSNR of Y, U and V and the luma's SSIM of every input frame
+    and of the frame written for it against the truth's frame, all in the format written (shiftnet_amd/fullref.py).  Four more launches behind the others:
+    ``sn_yuv_diff_stats`` of (truth, ``own``) and (truth, ``written``) with edge 0, whose exact sums give PSNR, and ``sn_yuv_ssim_sums`` of the same two
+    pairs, on the same rectangle.  **Luma SSIM only; the truth must be in the format written and frame-aligned by the caller; no verdict.**
+
     ``launch`` runs on the main stream behind the egress, ``collect`` on the thread that hands the window's frames out."""
 
     def __init__(self, edge: float, motion, denoise: bool, quality=None) -> None:
@@ -255,8 +274,15 @@ class Report:
         for s in slots:
             s.report = _ReportState(torch, dev, self.motion, self.quality, h, w, tout)
 
-    def launch(self, st, own, written, rect, run) -> None:
-        """Written minus input, the window's own n frames of both still on the device (current stream: the main stream); ``collect`` reads the sums."""
+    def prepare_gt(self, torch, dev, tout: int, slots) -> None:
+        """For a run with ``gt``: per slot the sums against the truth of the largest window (``slot.report.truth``), made once per stream shape."""
+        for s in slots:
+            if s.report.truth is None:
+                s.report.truth = _TruthState(torch, dev, self.h, self.w, tout)
+
+    def launch(self, st, own, written, rect, run, gt=None) -> None:
+        """Written minus input, the window's own n frames of both still on the device (current stream: the main stream); ``collect`` reads the sums.
+        gt: None, or the truth's n payloads for the frames written, on the device in the format written."""
         from .io_edges import block_motion_yuv, diff_stats_mv_yuv, diff_stats_yuv
         n = written.shape[0]
         head = (own, written, self.ofmt, self.h, self.w)
@@ -274,6 +300,15 @@ class Report:
                 for stat, payloads in ((st.niqe_in, own), (st.niqe_out, written)):
                     stat.launch(int(np.prod(shape)), run,
                                 lambda flat, p=payloads: niqe_sums_yuv(p, self.ofmt, self.h, self.w, self.win7, rect=rect, out=flat.view(shape)))
+        if gt is not None:
+            # the truth against the input as written and against the frames written: the exact sums PSNR is made of, then the SSIM tile sums
+            from .io_edges import ssim_sums_yuv, ssim_tiles
+            shape = (n,) + ssim_tiles(*_picture_size(rect, self.h, self.w))
+            for k, payloads in enumerate((own, written)):
+                st.truth.sums[k].launch(n, run, lambda sums, p=payloads: diff_stats_yuv(gt, p, self.ofmt, self.h, self.w, rect=rect, edge=0, out_sums=sums))
+            for k, payloads in enumerate((own, written)):
+                st.truth.ssim[k].launch(int(np.prod(shape)), run,
+                                        lambda flat, p=payloads: ssim_sums_yuv(gt, p, self.ofmt, self.h, self.w, rect=rect, out_sums=flat.view(shape)))
 
     def collect(self, st, n: int, run) -> None:
         """The sums of the window being handed out.  Windows are handed out in the order they ran: ``run.window_sigma`` and ``run.window_picture`` have
@@ -294,6 +329,14 @@ class Report:
                 run.frame_niqe += [(frame_score(a[i], *self.quality[:2]), frame_score(b[i], *self.quality[:2])) for i in range(n)]
             else:
                 run.frame_niqe += [(float("nan"), float("nan"))] * n
+        if run.gt is not None:
+            from .fullref import frame_fullref
+            from .io_edges import ssim_tiles
+            h, w = _picture_size(run.window_picture[run.collected], self.h, self.w)
+            shape = (n,) + ssim_tiles(h, w)
+            (si,), (so,) = (stat.wait(n) for stat in st.truth.sums)
+            ti, to = (stat.wait(int(np.prod(shape)))[0].reshape(shape) for stat in st.truth.ssim)
+            run.frame_fullref += [frame_fullref(si[i], so[i], ti[i], to[i], self.ofmt.bits, h, w) for i in range(n)]
 
     def finish(self, run, stats) -> None:
         bits = self.ofmt.bits
@@ -312,6 +355,11 @@ class Report:
             stats["frame_niqe"] = list(run.frame_niqe)
             stats["report_quality_summary"] = summarize_quality(run.frame_niqe)
             stats["report_quality_launches"] = run.launches["report_quality"]
+        if run.gt is not None:
+            from .fullref import summarize_fullref
+            stats["frame_fullref"] = list(run.frame_fullref)
+            stats["fullref_summary"] = summarize_fullref(run.frame_fullref)
+            stats["fullref_launches"] = run.launches["fullref"]
 
 
 # ---- tiles ----------------------------------------------------------------------------------------------------------------------------

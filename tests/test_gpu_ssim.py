@@ -1,0 +1,159 @@
+"""-m gpu: ``sn_yuv_ssim_sums`` on the pairs of tests/ssim_cases.py: the per-frame SSIM made of the kernel's tiles against what the reference
+implementation recorded for those pairs (tests/golden/ssim_cases.npz), the tile sums against the float64 restatement (tests/ssim_ref.py), and the
+equalities that must be exact.
+
+  * The SSIM of a frame is within SSIM_ATOL = 1e-5 absolute of the reference's: a condition, not a measurement -- the project prints SSIM to four
+    decimals and 1e-5 is a tenth of the last one.  (Measured: 1.1e-7, the 3x7 case)
+  * The kernel forms the map in float32 and the restatement in float64, so a tile's sum differs from the restatement's; relative to the tile's number of
+    positions the largest difference measured on these cases is 8.7e-7 (33x65: the corner tile of one position, where nothing averages out; every
+    whole tile is below 3e-7), asserted at TILE_RTOL = 2.6e-6, three times that.
+The test prints every figure before it asserts."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import picture_ref as P
+import ssim_cases as K
+import ssim_ref as SR
+from shiftnet_amd import fullref as F
+from shiftnet_amd import lib as L
+from shiftnet_amd.io_edges import ssim_sums_yuv, yuv_fmt
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SSIM_ATOL = 1e-5
+TILE_RTOL = 2.6e-6
+GARBAGE = -1.2345e300      # what dst holds before a call
+
+
+def size(c):
+    return (c.H, c.W) if c.rect is None else (c.rect[3], c.rect[2])
+
+
+@pytest.fixture(scope="module")
+def results():
+    """case name -> (a and b on the device, the kernel's tile sums, the restatement's), [T, nty, ntx] float64 each: computed once, read by every test."""
+    out = {}
+    for c in K.CASES:
+        a, b = K.payloads(c)
+        da, db = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+        got = ssim_sums_yuv(da, db, yuv_fmt(*c.fmt), c.H, c.W, rect=c.rect).cpu().numpy()
+        out[c.name] = (da, db, got, SR.ssim_sums_ref(a, b, c.fmt, c.H, c.W, c.rect))
+    return out
+
+
+def test_the_ssim_of_the_kernels_tiles_is_the_references_within_a_tenth_of_the_last_decimal_printed(results):
+    with np.load(os.path.join(ROOT, "tests", "golden", "ssim_cases.npz")) as z:
+        recorded = {k: z[k] for k in z.files}
+    worst = 0.0
+    for c in K.CASES:
+        got = results[c.name][2]
+        h, w = size(c)
+        for t in range(len(c.seeds)):
+            want = float(recorded["ssim/" + c.name][t])
+            d = abs(F.ssim_from_tiles(got[t], h, w) - want)
+            print(f"{c.name}[{t}]: reference {want:.9f}, difference {d:.3g}")
+            worst = max(worst, d)
+    print(f"largest difference of an SSIM: {worst:.3g}")
+    assert worst <= SSIM_ATOL
+
+
+def test_tile_sums_equal_the_float64_restatement_within_what_float32_costs(results):
+    worst = 0.0
+    for c in K.CASES:
+        _, _, got, want = results[c.name]
+        assert got.shape == want.shape and got.dtype == np.float64 and np.isfinite(got).all(), c.name
+        rel = float((np.abs(got - want) / SR.tile_counts(*size(c))[None]).max())
+        print(f"{c.name}: largest difference of a tile sum over its positions {rel:.3g}")
+        worst = max(worst, rel)
+    print(f"largest difference of a tile sum relative to its positions: {worst:.3g}")
+    assert worst <= TILE_RTOL
+
+
+def test_equal_payloads_give_every_tile_its_number_of_positions_exactly(results):
+    c = K.BY_NAME["same"]
+    da, db, got, _ = results[c.name]
+    counts = SR.tile_counts(c.H, c.W)
+    assert counts.shape == (2, 3) and counts[1, 2] == 1.0 and np.array_equal(got[0], counts)
+    assert np.array_equal(ssim_sums_yuv(da, da, yuv_fmt(*c.fmt), c.H, c.W).cpu().numpy()[0], counts)      # the same tensor
+    for name in ("70x100-sigma25", "10bit-limited"):                                                      # partial tiles; 10 bit
+        c = K.BY_NAME[name]
+        b = results[name][1]
+        assert np.array_equal(ssim_sums_yuv(b, b.clone(), yuv_fmt(*c.fmt), c.H, c.W).cpu().numpy()[0], SR.tile_counts(c.H, c.W)), name
+
+
+def test_a_rectangle_gives_the_sums_of_the_cropped_stream_exactly(results):
+    for name in ("rect-odd-of-50x70-444", "rect-of-96x128-420"):
+        c = K.BY_NAME[name]
+        got = results[name][2]
+        x0, y0, w, h = c.rect
+        a, b = (torch.from_numpy(P.crop_payloads(p, c.fmt, c.H, c.W, c.rect)).cuda() for p in K.payloads(c))
+        alone = ssim_sums_yuv(a, b, yuv_fmt(*c.fmt), h, w).cpu().numpy()
+        assert got.shape == (1, -(-h // 32), -(-w // 32)) and np.array_equal(got, alone), name
+
+
+def test_every_frame_of_a_launch_equals_the_frame_alone_and_a_second_launch_gives_the_same_doubles(results):
+    c = K.BY_NAME["T3"]
+    da, db, got, _ = results[c.name]
+    f = yuv_fmt(*c.fmt)
+    assert got.shape == (3, 2, 3) and not np.array_equal(got[0], got[1]) and not np.array_equal(got[1], got[2])
+    for t in range(3):
+        assert np.array_equal(ssim_sums_yuv(da[t:t + 1].contiguous(), db[t:t + 1].contiguous(), f, c.H, c.W).cpu().numpy(), got[t:t + 1]), t
+    # into garbage between guard words: every word of dst is overwritten, nothing else is written, and the doubles are those of the first launch
+    n = got.size
+    buf = torch.full((n + 16,), GARBAGE, dtype=torch.float64, device="cuda")
+    out = buf[8:8 + n].view(got.shape)
+    for _ in range(2):
+        assert ssim_sums_yuv(da, db, f, c.H, c.W, out_sums=out) is out
+        assert np.array_equal(out.cpu().numpy(), got)
+    ends = buf.cpu().numpy()
+    assert (ends[:8] == GARBAGE).all() and (ends[8 + n:] == GARBAGE).all()
+
+
+def test_payloads_at_odd_addresses_give_the_same_sums(results):
+    """The wide loads test the address: an 8-bit stream one byte past a 16-byte boundary takes the element-wise path and gives the same doubles."""
+    c = K.BY_NAME["70x100-sigma2"]
+    da, db, got, _ = results[c.name]
+    moved = []
+    for d in (da, db):
+        T, fb = d.shape
+        buf = torch.zeros(T * fb + 32, dtype=torch.uint8, device="cuda")
+        base = (-buf.data_ptr()) % 16 + 1
+        m = buf[base:base + T * fb].view(T, fb)
+        m.copy_(d)
+        assert m.data_ptr() % 16 == 1
+        moved.append(m)
+    assert np.array_equal(ssim_sums_yuv(moved[0], moved[1], yuv_fmt(*c.fmt), c.H, c.W).cpu().numpy(), got)
+    assert np.array_equal(ssim_sums_yuv(moved[0], db, yuv_fmt(*c.fmt), c.H, c.W).cpu().numpy(), got)
+
+
+def test_what_the_entry_point_refuses_it_refuses_before_anything_is_launched(results):
+    """Every refusal on device memory: dst keeps its garbage."""
+    c = K.BY_NAME["10bit-limited"]
+    da, db, got, _ = results[c.name]
+    c8 = K.BY_NAME["8bit-full"]
+    a8, b8 = results[c8.name][:2]
+    lib = L.load()
+    dst = torch.full((got.size + 2,), GARBAGE, dtype=torch.float64, device="cuda")
+    f10, f8 = yuv_fmt(*c.fmt), yuv_fmt(*c8.fmt)
+    R = L.YuvRect
+    a, b, d, H, W = da.data_ptr(), db.data_ptr(), dst.data_ptr(), c.H, c.W
+    big = 2 ** 31 - 1
+    refused = [
+        (None, b, f10, None, d, 1, H, W), (a, None, f10, None, d, 1, H, W), (a, b, None, None, d, 1, H, W), (a, b, f10, None, None, 1, H, W),
+        (a, b, yuv_fmt(12, 0, 0, 0), None, d, 1, H, W), (a, b, yuv_fmt(8, 3, 0, 0), None, d, 1, H, W),
+        (a + 1, b, f10, None, d, 1, H, W), (a, b + 1, f10, None, d, 1, H, W),
+        (a, b, f10, None, d + 4, 1, H, W),
+        (a, b, f10, R(0, 0, 0, 8), d, 1, H, W), (a, b, f10, R(W - 8, 0, 10, 8), d, 1, H, W), (a, b, f10, R(1, 0, 8, 8), d, 1, H, W), (a, b, f10, R(0, 0, 7, 8), d, 1, H, W),
+        (a, b, f10, None, d, 0, H, W), (a, b, f10, None, d, 65536, H, W), (a, b, f10, None, d, 1, 0, W), (a, b, f10, None, d, 1, H, 0),
+        (a8.data_ptr(), b8.data_ptr(), f8, None, d, 1, big, big),
+    ]
+    for args in refused:
+        rect = args[3]
+        assert lib.sn_yuv_ssim_sums(args[0], args[1], args[2], None if rect is None else C.byref(rect), *args[4:], None) == -22, args
+    torch.cuda.synchronize()
+    assert (dst.cpu().numpy() == GARBAGE).all()

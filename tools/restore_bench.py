@@ -53,6 +53,11 @@
             sn_yuv_diff_stats on the same frames, interleaved as in the kernels part; and the host's milliseconds per frame for the fit and the
             distance (niqe.frame_score on those sums).  --mode forward: steady-state wall time per 720p window of the pipelined denoiser (as the report
             part) with report=True alone and with report_quality="niqe" on top, runs of the two alternating in one process, the first two windows left out.
+  fullref : the report's comparison with a ground-truth stream (3.34).  --mode kernels: time per launch of ``sn_yuv_ssim_sums`` (4:2:0 8 bit, 720p x 16
+            frames: a clean clip against its copy with noise of sigma 10) beside a plain device copy of the luma planes of both sets -- the bytes the
+            kernel reads, once -- and beside sn_yuv_diff_stats on the same frames, interleaved as in the kernels part.  --mode forward: steady-state wall
+            time per 720p window of the pipelined denoiser (as the report part) with report=True alone and with gt= on top, runs of the two alternating in
+            one process, the first two windows left out.
 Prints one JSON object per part.
 """
 import argparse
@@ -646,6 +651,89 @@ def quality_forward(a):
                       "runs": a.runs, "report_quality_summary": {k: round(v, 4) for k, v in seen["niqe"].items()}, **res}))
 
 
+def fullref_kernels(a):
+    from shiftnet_amd import fullref
+    from shiftnet_amd.io_edges import ssim_sums_yuv
+    T, H, W = 16, 720, 1280
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    blur, _ = synth.blurred_clip(4, H, W, seed=1)
+    rgb = ingest_u8(torch.from_numpy(np.concatenate([blur] * 4)).cuda(), torch.float32)[0]
+    clean = egress_yuv(rgb, fmt, H, W)
+    noisy = egress_yuv((rgb + torch.randn(rgb.shape, device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * (10.0 / 255)).clamp(0, 1), fmt, H, W)
+    tiles = ssim_sums_yuv(clean, noisy, fmt, H, W)
+    dsums = torch.empty((T, L.SN_DIFF_STATS), dtype=torch.int64, device="cuda")
+    luma = torch.empty((2, T, H * W), dtype=torch.uint8, device="cuda")
+    cases = {
+        "ssim_sums_yuv": lambda: ssim_sums_yuv(clean, noisy, fmt, H, W, out_sums=tiles),
+        "copy_luma_x2": lambda: (luma[0].copy_(clean[:, :H * W]), luma[1].copy_(noisy[:, :H * W])),      # the bytes the kernel reads, once, and as many written
+        "diff_stats_yuv": lambda: diff_stats_yuv(clean, noisy, fmt, H, W, edge=0, out_sums=dsums),       # the other launch of the comparison
+    }
+    for f in cases.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in cases}
+    for _ in range(a.reps):
+        for k, f in cases.items():                                                   # interleaved: every repetition times every kernel
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.inner):
+                f()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.inner)
+    host, rows = tiles.cpu().numpy(), dsums.cpu().numpy()
+    px = T * H * W
+    res = {k: {"us_per_launch": summary([m * 1e3 for m in v]), "us_per_frame": summary([m * 1e3 / T for m in v]),
+               "ps_per_pixel": summary([m * 1e9 / px for m in v])} for k, v in ms.items()}
+    print(json.dumps({"part": "fullref", "mode": "kernels", "frames": T, "size": [H, W], "tiles": list(tiles.shape[1:]), "reps": a.reps, "inner": a.inner,
+                      "ssim_of_the_noisy_frames": summary([fullref.ssim_from_tiles(host[t], H, W) for t in range(T)]),
+                      "psnr_y_of_the_noisy_frames": summary([fullref.psnr_from_sums(rows[t], 8)[0] for t in range(T)]), **res}))
+
+
+def fullref_forward(a):
+    H, W, one_len, nwin = 720, 1280, 16, a.windows
+    n = one_len * nwin
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    blur, _ = synth.blurred_clip(8, H, W, seed=2)
+    rgb = ingest_u8(torch.from_numpy(blur).cuda(), torch.float32)[0]
+    g = torch.Generator("cuda").manual_seed(1)
+    frames, truth = [], []
+    for i in range(n):                                                               # fresh noise of sigma 10 on every frame, as the report part
+        j = i % 14
+        x = rgb[j if j < 8 else 14 - j][None]
+        truth.append(egress_yuv(x, fmt, H, W)[0].cpu().numpy())
+        frames.append(egress_yuv((x + torch.randn(x.shape, device="cuda", generator=g) * (10.0 / 255)).clamp(0, 1), fmt, H, W)[0].cpu().numpy())
+    net = restore.load_net("denoise_small", "synthetic", "bf16")
+    seen = {}
+
+    def run(gt):
+        vr = restore.VideoRestorer(net, one_len, sigma=10.0, pipeline=True, report=True)
+        stamps = []
+        t0 = time.perf_counter()
+        for i, p in enumerate(vr.restore(iter(frames), fmt, H, W, gt=iter(truth) if gt else None)):
+            if (i + 1) % one_len == 0:
+                stamps.append(time.perf_counter())
+        total = time.perf_counter() - t0
+        seen[gt] = vr.stats.get("fullref_summary")
+        gaps = [(b - c) * 1e3 for b, c in zip(stamps[1:], stamps[:-1])]
+        return {"total_s": total, "window_wall_ms": gaps[1:], "window_forward_ms": vr.stats["window_forward_ms"][2:]}
+
+    run(False)                                                                       # warm-up: code objects, engine buffers
+    run(True)
+    runs = {"report": [], "report_gt": []}
+    for _ in range(a.runs):
+        runs["report"].append(run(False))
+        runs["report_gt"].append(run(True))
+    res = {}
+    for k, rs in runs.items():
+        res[k] = {"window_wall_ms": summary([g for r in rs for g in r["window_wall_ms"]]),
+                  "window_wall_ms_per_run": [round(statistics.median(r["window_wall_ms"]), 2) for r in rs],
+                  "window_forward_ms": summary([g for r in rs for g in r["window_forward_ms"]]), "total_s": [round(r["total_s"], 3) for r in rs]}
+    print(json.dumps({"part": "fullref", "mode": "forward", "variant": "denoise_small", "dtype": "bf16", "one_len": one_len, "windows": nwin, "size": [H, W],
+                      "runs": a.runs, "fullref_means": {k: round(v, 4) for k, v in seen[True]["mean"].items()}, **res}))
+
+
 def _tile_word(word):
     return None if word == "full" else restore.tile_arg(word)
 
@@ -949,7 +1037,7 @@ def picture_part(a):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion", "tiles", "overlap", "quality"])
+    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion", "tiles", "overlap", "quality", "fullref"])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--inner", type=int, default=200)
     ap.add_argument("--windows", type=int, default=8)
@@ -961,7 +1049,7 @@ if __name__ == "__main__":
                     "csrc/sn_yuv.hip alone; its sn_ingest_yuv / sn_egress_yuv are timed beside this build's.  nlf and motion parts in kernels mode: a library "
                     "built from another commit's whole csrc; its seven noise-histogram entry points are timed beside this build's, at 8 and 10 bit")
     ap.add_argument("--only_cases", default=None, metavar="WORDS", help="kernels part: time only the cases whose name contains one of these comma-separated words")
-    ap.add_argument("--mode", choices=["forward", "kernels", "quality"], default="forward", help="picture, nlf, report, motion, tiles, overlap and quality parts: which measurement "
+    ap.add_argument("--mode", choices=["forward", "kernels", "quality"], default="forward", help="picture, nlf, report, motion, tiles, overlap, quality and fullref parts: which measurement "
                     "(quality: the tiles part alone)")
     ap.add_argument("--picture", choices=["auto", "fixed"], default="auto", help="picture part, forward mode: VideoRestorer(picture='auto') or the rectangle itself")
     ap.add_argument("--tile", action="append", default=None, metavar="{full,N,HxW}", help="tiles part, forward mode: a form to run (repeat for several, which then alternate)")
@@ -977,4 +1065,5 @@ if __name__ == "__main__":
          "motion": motion_kernels if a.mode == "kernels" else motion_forward,
          "tiles": tiles_quality if a.mode == "quality" else tiles_forward,
          "overlap": overlap_kernels if a.mode == "kernels" else overlap_forward,
-         "quality": quality_kernels if a.mode == "kernels" else quality_forward}[a.part](a)
+         "quality": quality_kernels if a.mode == "kernels" else quality_forward,
+         "fullref": fullref_kernels if a.mode == "kernels" else fullref_forward}[a.part](a)
