@@ -455,7 +455,12 @@ int sn_egress_blocks(void);
 int sn_egress_u8(const void* out, int out_dtype, const uint8_t* gt, uint8_t* img, float* sse, int T, int H, int W, void* stream);
 /* The CLIs' own SSIM (inference/test_deblur.py:25-49: Gaussian statistics, sd 1.5, over the (C,H,W) volume of clamp(out,0,1) and
  * gt / 255, scipy 'reflect' boundaries on all three axes): scratch:[T][15][H][W] f32 workspace, partial:[T][sn_ssim_blocks()]
- * f32 sums of the SSIM map; SSIM of frame t = sum(partial[t]) / (3 H W). */
+ * f32 sums of the SSIM map; SSIM of frame t = sum(partial[t]) / (3 H W).
+ * Arithmetic: scipy's and numpy's, rounding for rounding -- the five statistics a, b, a a, b b, a b in float32; the filter one axis after the
+ * other in scipy's order C, H, W, each a float64 sum of float64 taps rounded once to float32 (scratch holds the planes after C and H); the map
+ * in float32 with every operation rounded on its own (no FMA); the map summed in float64 per workgroup and rounded once into partial.  Only the
+ * order of the sums inside float64 and of the final mean differs from the CLI's ssim_calculate: within 2e-5 of it on any content, near-flat
+ * frames far from mid-grey included (measured: 2e-7).  Every word of partial is written; nothing outside scratch and partial is. */
 int sn_ssim_blocks(void);
 int sn_ssim_u8(const void* out, int out_dtype, const uint8_t* gt, float* scratch, float* partial, int T, int H, int W, void* stream);
 
@@ -881,24 +886,24 @@ int sn_yuv_niqe_sums(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rec
  *   taken as stored (a 16-bit word may hold up to 65535).  The picture is h x w, the rectangle or the frame; coordinates below count from its first
  *   sample, and cy / cx clamp to 0 .. h - 1 / 0 .. w - 1: the border is replicated at the edge of the picture, not of the frame, so a rectangle gives
  *   what the cropped stream gives.
- * Constants: g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)) / sum_j exp(-(j - 5)^2 / (2 * 1.5^2)), i = 0 .. 10, computed in float64 on the host and rounded once
- *   to float32; the window is their outer product.  p = 2^bits - 1, C1 = (0.01 p)^2, C2 = (0.03 p)^2, float64 expressions rounded once to float32;
- *   mid = 2^(bits - 1).  At 8 bit this is the harnesses' formula on their 0 .. 255 scale; at 10 bit it is the same formula on codes * 255 / 1023,
- *   because SSIM does not change when the constants scale with the data.
- * Float32, every product, sum and difference rounded on its own (no FMA); an 11-tap sum adds its products p0 .. p10 from the outside in,
- *   ((((p0 + p10) + (p1 + p9)) + (p2 + p8)) + (p3 + p7)) + (p4 + p6)) + p5.  With A = a - mid and B = b - mid (exact):
- *     r_X(y, x) = sum_i g[i] * X(y, cx(x + i - 5))  for the five maps X = A, B, A * A, B * B, A * B  (the product first, then the tap)
+ * Constants: g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)) / sum_j exp(-(j - 5)^2 / (2 * 1.5^2)), i = 0 .. 10, float64, computed on the host; the window is their
+ *   outer product.  p = 2^bits - 1, C1 = (0.01 p)^2, C2 = (0.03 p)^2, float64.  At 8 bit this is the harnesses' formula on their 0 .. 255 scale; at
+ *   10 bit it is the same formula on codes * 255 / 1023, because SSIM does not change when the constants scale with the data.
+ * Float64 from the codes on (a product of two codes is exact), every product, sum and difference rounded on its own (no FMA); an 11-tap sum adds its
+ *   products p0 .. p10 from the outside in, ((((p0 + p10) + (p1 + p9)) + (p2 + p8)) + (p3 + p7)) + (p4 + p6)) + p5:
+ *     r_X(y, x) = sum_i g[i] * X(y, cx(x + i - 5))  for the five maps X = a, b, a * a, b * b, a * b  (the product first, then the tap)
  *     G_X(y, x) = sum_j g[j] * r_X(cy(y + j - 5), x)
- *     mu_a = G_A + mid,  mu_b = G_B + mid                       (the means of the codes themselves)
- *     s_aa = G_AA - G_A * G_A,  s_bb = G_BB - G_B * G_B,  s_ab = G_AB - G_A * G_B      (variances do not move with mid; the squares are smaller)
- *     map  = ((2 * (mu_a * mu_b) + C1) * (2 * s_ab + C2)) / (((mu_a * mu_a + mu_b * mu_b) + C1) * ((s_aa + s_bb) + C2))    (correctly rounded division)
- * dst[t][i][j] is the float64 sum of map (converted to double) over tile (i, j) of frame t: positions y = SN_SSIM_TILE i .. , x = SN_SSIM_TILE j .. of
+ *     s_aa = G_aa - G_a * G_a,  s_bb = G_bb - G_b * G_b,  s_ab = G_ab - G_a * G_b
+ *     map  = ((2 * (G_a * G_b) + C1) * (2 * s_ab + C2)) / (((G_a * G_a + G_b * G_b) + C1) * ((s_aa + s_bb) + C2))
+ *   (Until the near-flat pairs of tests/ssim_cases.py this was float32 on codes minus mid-grey: the variances of a flat area far from mid-grey lost
+ *   their digits, a frame of code 2 came out 2e-5 from the reference and a tile 6e-5.)
+ * dst[t][i][j] is the float64 sum of map over tile (i, j) of frame t: positions y = SN_SSIM_TILE i .. , x = SN_SSIM_TILE j .. of
  * the picture, SN_SSIM_TILE each way, the last row and column of tiles partial; nty = ceil(h / SN_SSIM_TILE), ntx = ceil(w / SN_SSIM_TILE).  All h w
  * positions count; a frame's SSIM is the sum of its tiles over h w.  dst:[T][nty][ntx] doubles is OVERWRITTEN, never added to; nothing outside those
  * words is written.  One workgroup owns one (frame, tile), adds in one fixed order and writes its double with a plain store; there are no atomics.
  * The result does not depend on the launch geometry or the schedule, and a second launch gives the same bits.  a == b is legal: numerator and
- * denominator are then the same float32 expressions, map is exactly 1 everywhere, and every tile's sum is exactly its number of positions.
- * (tests/ssim_ref.py restates it in float64; the kernel's per-frame SSIM is within 1e-5 of what the harnesses' code gives.)
+ * denominator are then the same float64 expressions, map is exactly 1 everywhere, and every tile's sum is exactly its number of positions.
+ * (tests/ssim_ref.py restates it with numpy; the kernel's per-frame SSIM is within 1e-5 of what the harnesses' code gives, on near-flat pictures too.)
  * SN_EINVAL before anything is launched: everything sn_yuv_diff_stats refuses (it takes no edge); dst not 8-byte aligned; a tile grid, nty * ntx,
  * beyond the bound sn_yuv_diff_stats puts on its units (2^31 - 1 - 2^18). */
 #define SN_SSIM_TILE 32

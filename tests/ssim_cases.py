@@ -4,7 +4,12 @@ reference implementation on exactly these and records its answers in tests/golde
 A pair is a truth ``a`` -- texture (two sinusoids and a chirp), a blocky random field and a checker, in all three planes -- and a degraded copy ``b``: the
 truth with a little less contrast and lifted blacks (so that "noise 0" is not "the same picture") plus seeded Gaussian noise, as codes of the case's
 format.  The shapes are the smallest at which the kernel can still go wrong: both borders inside one window, one tile exactly, one position beyond a
-tile both ways, partial tiles, rectangles at odd and even offsets, three different frames in one launch."""
+tile both ways, partial tiles, rectangles at odd and even offsets, three different frames in one launch.
+
+A case with ``level`` set is a near-flat pair instead, far from mid-grey or at it: all three planes of the truth are that one code, and the degraded copy is the
+code plus seeded Gaussian noise of ``sigma`` codes OF THE CASE'S FORMAT, rounded and clipped to the format's range (0 .. 2^bits - 1).  There the variances are
+tiny against the squares they are the difference of, and they are divided by something close to C2: sky, walls, night, bars -- what a denoiser outputs.  A
+tuple of levels gives every frame its own."""
 from __future__ import annotations
 
 from collections import namedtuple
@@ -14,9 +19,13 @@ import numpy as np
 import picture_ref as P
 import yuv_ref as R
 
-Case = namedtuple("Case", "name fmt H W rect seeds sigma same")      # rect: (x0, y0, w, h) or None; seeds: one per frame; sigma: noise in 8-bit codes; same: b is a
+# rect: (x0, y0, w, h) or None; seeds: one per frame; sigma: noise in 8-bit codes (in the format's codes with ``level``); same: b is a;
+# level: None, or the one code of a near-flat truth (a tuple: one per frame)
+Case = namedtuple("Case", "name fmt H W rect seeds sigma same level", defaults=(None,))
 _L8 = R.Fmt(8, R.C444, R.BT709, R.LIMITED)
 _L8_420 = R.Fmt(8, R.C420_CENTER, R.BT709, R.LIMITED)
+_F8 = R.Fmt(8, R.C444, R.BT601, R.FULL)
+_L10 = R.Fmt(10, R.C420_LEFT, R.BT709, R.LIMITED)
 CASES = [
     Case("3x7", _L8, 3, 7, None, (31,), 5.0, False),                                         # both borders replicate inside one window
     Case("7x3", _L8, 7, 3, None, (32,), 5.0, False),
@@ -32,7 +41,16 @@ CASES = [
     Case("rect-of-96x128-420", _L8_420, 96, 128, (10, 8, 100, 70), (42,), 5.0, False),
     Case("T3", _L8_420, 40, 72, None, (43, 44, 45), 5.0, False),                             # three different pairs: the payload stride
     Case("same", _L8, 33, 65, None, (46,), 5.0, True),                                       # a == b: SSIM 1, PSNR inf
+    # near-flat pairs (appended: the rows above keep their seeds and their recorded answers)
+    Case("flat235-s1", _L8, 70, 100, None, (47,), 1.0, False, 235),                          # limited-range white
+    Case("flat235-s2", _L8, 70, 100, None, (48,), 2.0, False, 235),
+    Case("flat16-s1", _L8, 70, 100, None, (49,), 1.0, False, 16),                            # limited-range black
+    Case("flat250-s1-full", _F8, 70, 100, None, (50,), 1.0, False, 250),
+    Case("flat2-s1-full", _F8, 70, 100, None, (51,), 1.0, False, 2),                         # the noise clips at code 0
+    Case("flat940-s4-10bit", _L10, 70, 100, None, (52,), 4.0, False, 940),
+    Case("flat-T3", _L8, 33, 65, None, (53, 54, 55), 1.0, False, (235, 128, 16)),            # bright, mid-grey and dark in one launch: the payload stride
 ]
+FLAT = tuple(c.name for c in CASES if c.level is not None)
 BY_NAME = {c.name: c for c in CASES}
 
 
@@ -58,6 +76,12 @@ def frame_pair(case: Case, seed: int):
     rng = np.random.default_rng(seed)
     ch, cw = R.chroma_shape(case.fmt, case.H, case.W)
     a, b = [], []
+    if case.level is not None:
+        level = case.level[case.seeds.index(seed)] if isinstance(case.level, tuple) else case.level
+        for h, w in ((case.H, case.W), (ch, cw), (ch, cw)):
+            a.append(np.full((h, w), level, np.int64))
+            b.append(np.clip(np.rint(level + rng.normal(0, 1, (h, w)) * case.sigma), 0, (1 << case.fmt.bits) - 1).astype(np.int64))
+        return tuple(a), tuple(b)
     for i, (h, w) in enumerate(((case.H, case.W), (ch, cw), (ch, cw))):
         v = _plane(h, w, rng, (37, 23, 29)[i], (17, 13, 19)[i])
         noise = rng.normal(0, 1, (h, w)) * (case.sigma / 255.0)

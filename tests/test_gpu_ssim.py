@@ -3,10 +3,13 @@ implementation recorded for those pairs (tests/golden/ssim_cases.npz), the tile 
 equalities that must be exact.
 
   * The SSIM of a frame is within SSIM_ATOL = 1e-5 absolute of the reference's: a condition, not a measurement -- the project prints SSIM to four
-    decimals and 1e-5 is a tenth of the last one.  (Measured: 1.1e-7, the 3x7 case)
-  * The kernel forms the map in float32 and the restatement in float64, so a tile's sum differs from the restatement's; relative to the tile's number of
-    positions the largest difference measured on these cases is 8.7e-7 (33x65: the corner tile of one position, where nothing averages out; every
-    whole tile is below 3e-7), asserted at TILE_RTOL = 2.6e-6, three times that.
+    decimals and 1e-5 is a tenth of the last one.  (Measured: 4.8e-13)
+  * A tile's sum against the restatement's, relative to the tile's number of positions: TILE_RTOL = 2.6e-6 on the textured pairs, three times the
+    8.7e-7 measured on them while the kernel formed the map in float32 (33x65: the corner tile of one position, where nothing averages out), and
+    TILE_ATOL_FLAT = 1e-5, the stated condition, on the near-flat pairs (``Case.level``), for which a figure measured at mid-grey is no bound.
+    The float32 kernel, on codes minus mid-grey, read 1.99e-5 per frame (code 2, one code of noise: beyond SSIM_ATOL) and 6.1e-5 per tile (the
+    corner tile of flat-T3) there, and at most 8.7e-7 elsewhere.  The kernel is float64 from the codes on now and differs from the restatement in
+    the order of its sums only: 6.2e-14 per tile on the textured pairs, 7.4e-13 on the near-flat ones.
 The test prints every figure before it asserts."""
 import ctypes as C
 import os
@@ -27,6 +30,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SSIM_ATOL = 1e-5
 TILE_RTOL = 2.6e-6
+TILE_ATOL_FLAT = 1e-5      # the near-flat pairs (Case.level): the stated condition per position; TILE_RTOL was measured at mid-grey and is no bound elsewhere
 GARBAGE = -1.2345e300      # what dst holds before a call
 
 
@@ -63,15 +67,18 @@ def test_the_ssim_of_the_kernels_tiles_is_the_references_within_a_tenth_of_the_l
 
 
 def test_tile_sums_equal_the_float64_restatement_within_what_float32_costs(results):
-    worst = 0.0
+    worst = worst_flat = 0.0
     for c in K.CASES:
         _, _, got, want = results[c.name]
         assert got.shape == want.shape and got.dtype == np.float64 and np.isfinite(got).all(), c.name
         rel = float((np.abs(got - want) / SR.tile_counts(*size(c))[None]).max())
         print(f"{c.name}: largest difference of a tile sum over its positions {rel:.3g}")
-        worst = max(worst, rel)
-    print(f"largest difference of a tile sum relative to its positions: {worst:.3g}")
-    assert worst <= TILE_RTOL
+        if c.level is not None:
+            worst_flat = max(worst_flat, rel)
+        else:
+            worst = max(worst, rel)
+    print(f"largest difference of a tile sum relative to its positions: {worst:.3g}; on the near-flat pairs: {worst_flat:.3g}")
+    assert worst <= TILE_RTOL and worst_flat <= TILE_ATOL_FLAT
 
 
 def test_equal_payloads_give_every_tile_its_number_of_positions_exactly(results):

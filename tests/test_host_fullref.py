@@ -5,7 +5,8 @@ report file's eight columns, the new symbol, and the refusals of the C entry poi
 
 Tolerances, measured here against the fixture (DESIGN.md 3.34 has the table).  Restatement and reference are both float64 and differ in the order of
 their sums only (separable filter and tile sums here, one 11 x 11 correlation and one mean there):
-  * SSIM: largest relative difference 6.3e-14 (3x7), asserted at SSIM_RTOL = 6.3e-13, ten times that;
+  * SSIM: largest relative difference 6.3e-14 (3x7) on the textured pairs, asserted at SSIM_RTOL = 6.3e-13, ten times that; the near-flat pairs
+    (``Case.level``) are held to the same figure and read 4.0e-13 at most (code 250, one code of noise: G(a a) - G(a)^2 cancels twelve digits);
   * PSNR: largest relative difference 3.3e-16, asserted at PSNR_RTOL = 3.3e-15, ten times that -- the sums are exact integers, what is left is a logarithm."""
 import ctypes as C
 import math
