@@ -847,25 +847,34 @@ int sn_time_crossfade(const float* prev, float* cur, const float* w_prev, const 
  * four neighbours.  Each fit needs five sums of its map; sn_yuv_niqe_sums makes those sums, shiftnet_amd/niqe.py does the rest on the host in float64.
  *   src: T payloads as sn_ingest_yuv takes them; only the luma plane is read, and of fmt only bits and range decide anything.  rect (NULL: the whole
  *   frame) as sn_ingest_yuv_rect takes it: the picture is its h x w luma samples and everything below is what the cropped stream would give.
- *   win7: 7 float32 taps g[0..6] in device memory, the separable factor of the model's 7 x 7 window.  dst:[T][2][nbh][nbw][SN_NIQE_MAPS][SN_NIQE_SUMS]
+ *   win7: 7 float32 taps win7[0..6] in device memory, the separable factor of the model's 7 x 7 window.  dst:[T][2][nbh][nbw][SN_NIQE_MAPS][SN_NIQE_SUMS]
  *   doubles, nbh = h / 96, nbw = w / 96 (integer division); only the top-left 96 nbh x 96 nbw samples of the picture count and are read.
- * Sample value, float32:  limited range v = code * 2^-(bits - 8) (exact);  full range v = 16 + code * k, k = (float)(219.0 / (2^bits - 1)), product and
- *   sum rounded separately: both on the 16 .. 235 scale of an 8-bit limited-range Y'.
- * Scale 1: I = v, hs x ws = 96 nbh x 96 nbw.  Scale 2: I(y, x) = 0.25 * ((v(2y, 2x) + v(2y, 2x+1)) + (v(2y+1, 2x) + v(2y+1, 2x+1))), hs x ws half of that.
- * Per scale, float32, every product and sum rounded on its own (no FMA); a 7-tap sum adds its products p0 .. p6 from the outside in,
- * (((p0 + p6) + (p1 + p5)) + (p2 + p4)) + p3, in which order the float32 taps of NIQE's window add up to exactly 1 and a flat area gets n = 0 exactly;
- * cy / cx clamp to 0 .. hs - 1 / 0 .. ws - 1 (the replication is at the crop of that scale, not at the frame):
- *     r1(y, x) = sum_i g[i] * I(y, cx(x + i - 3))              r2(y, x) = sum_i g[i] * (I * I)(y, cx(x + i - 3))
- *     mu(y, x) = sum_j g[j] * r1(cy(y + j - 3), x)             m2(y, x) = sum_j g[j] * r2(cy(y + j - 3), x)
- *     n = (I - mu) / (sqrt(|m2 - mu * mu|) + 1)                (correctly rounded square root and division)
- * Per block of side B = 96 / scale, block (by, bx) being rows by B .. by B + B - 1 and columns bx B .. of that scale, with (y, x) inside the block:
- *     map 0: m = n(y, x);   maps 1..4: m = n(y, x) * n((y - dy) mod B, (x - dx) mod B), (dy, dx) = (0, 1), (1, 0), (1, 1), (1, -1)   (one float32 product;
+ * Everything is float64, every product and sum rounded on its own (no FMA), square root and division correctly rounded.
+ * Sample value:  limited range v = code * 2^-(bits - 8);  full range v = 16 + code * k, k = (double)(float)(219.0 / (2^bits - 1)): both on the 16 .. 235
+ *   scale of an 8-bit limited-range Y', and both exact (a 10-bit code times a 24-bit constant).
+ * Scale 1: I = v, hs x ws = 96 nbh x 96 nbw.  Scale 2: I(y, x) = 0.25 * ((v(2y, 2x) + v(2y, 2x+1)) + (v(2y+1, 2x) + v(2y+1, 2x+1))), hs x ws half of that
+ *   (exact).
+ * Taps: a 7-tap sum adds its terms p0 .. p6 from the outside in, sum7(p) = (((p0 + p6) + (p1 + p5)) + (p2 + p4)) + p3.  w[i] = (double)win7[i],
+ *   g[i] = w[i] / sum7(w): the float32 taps over their own sum, which add up to 1 to an ulp whatever their roundings added up to.
+ *   (Taps that add up to 0 give NaNs; nothing checks device memory.)
+ * Per scale and per block of side B = 96 / scale, block (by, bx) being rows by B .. by B + B - 1 and columns bx B .. of that scale: the filters run on
+ * the deviations from the block's own first sample, J = I - p with p = I(by B, bx B) (exact), for the block's samples and for the 3 samples around it
+ * that belong to its neighbours alike; n and the variance do not change under that shift, and a flat area has J = 0, every product and sum 0 and
+ * n = 0 / (0 + 1) = 0 exactly, at every code.  cy / cx clamp to 0 .. hs - 1 / 0 .. ws - 1 (the replication is at the crop of that scale, not at the
+ * frame), (y, x) inside the block:
+ *     r1(y, x) = sum7_i g[i] * J(y, cx(x + i - 3))             r2(y, x) = sum7_i g[i] * (J * J)(y, cx(x + i - 3))
+ *     mu(y, x) = sum7_j g[j] * r1(cy(y + j - 3), x)            m2(y, x) = sum7_j g[j] * r2(cy(y + j - 3), x)
+ *     n = (J - mu) / (sqrt(|m2 - mu * mu|) + 1)                kept as a double
+ *     map 0: m = n(y, x);   maps 1..4: m = n(y, x) * n((y - dy) mod B, (x - dx) mod B), (dy, dx) = (0, 1), (1, 0), (1, 1), (1, -1)   (one product;
  *     the wrap is inside the block).
- * dst[t][scale - 1][by][bx][map] holds five doubles; m is converted to double and everything after that is float64:
+ * dst[t][scale - 1][by][bx][map] holds five doubles:
  *     [0] the count of m < 0   [1] the sum of m^2 over m < 0   [2] the count of m > 0   [3] the sum of m^2 over m > 0   [4] the sum of |m|
  * One workgroup owns one (frame, scale, block), adds in one fixed order and writes its 25 doubles with plain stores; there are no atomics.  The
  * result does not depend on the launch geometry or the schedule, and a second launch gives the same bits.  Only dst is written, every word of it.
- * (tests/niqe_ref.py restates the sums in float64; the counts differ from it only where a float32 m and its float64 twin lie on both sides of zero.)
+ * (tests/niqe_ref.py restates this rounding for rounding: the counts are equal and the sums differ by the order in which a block's values are added,
+ * 1e-12 at most.  Against the same formula on the values themselves in long double with unrounded taps the sums are within 3e-8, the rounding of
+ * the taps to float32, on textured and on near-flat frames alike.  Until the kernel computed in float64 on deviations it was float32 on the values,
+ * and lost up to 8e-3 of a sum on near-flat bright frames and left a one-signed residue on flat frames of some codes: DESIGN.md 3.33.)
  * SN_EINVAL before anything is launched: a null src, fmt, win7 or dst; bits not 8 or 10 or an unknown chroma code; a rectangle sn_ingest_yuv_rect
  * refuses; T outside 1 .. 65535; H or W < 1; no whole block (nbh * nbw == 0); dst not 8-byte or win7 not 4-byte aligned; src at an odd address at
  * 10 bit. */

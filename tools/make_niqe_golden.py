@@ -17,7 +17,9 @@ Two of its imports are replaced:
     lets the module import.
 
 What is recorded (float64):
-  score/<case>      : ``niqe()`` on every frame of every case of tests/niqe_cases.py, fed with the luma on the 16 .. 235 scale in float64;
+  score/<case>      : ``niqe()`` on every frame of every case of ``niqe_cases.CASES``, fed with the luma on the 16 .. 235 scale in float64 (the whole
+                      pictures of one code, ``niqe_cases.FLAT_CASES``, are not recorded: upstream fits the residue its own sums leave there, and
+                      the answer says nothing -- DESIGN.md 3.33);
   feature/<block>   : ``compute_feature()`` on every block of ``niqe_cases.feature_blocks()`` (float32 blocks).
 """
 import argparse
