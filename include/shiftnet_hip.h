@@ -919,6 +919,37 @@ int sn_yuv_niqe_sums(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rec
 int sn_yuv_ssim_sums(const uint8_t* a, const uint8_t* b, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* NULL: whole frame */,
                      double* dst /* [T][nty][ntx] */, int T, int H, int W, void* stream);
 
+/* ---- noise added to a clean stream (csrc/sn_degrade.hip; a new symbol and a new struct, SN_ABI_VERSION stays 20) -------------------------------------
+ * The first half of the experiment the ground truth above is for: a degraded copy of a clean stream (VideoRestorer(add_noise=...)), as upstream's
+ * denoise harnesses make one -- in_tensor + normal_(0, sigma) on R'G'B' -- but from payloads to payloads, with no float frame in memory.
+ *   src: T payloads of fmt, H x W, as sn_ingest_yuv takes them; dst: T payloads of the same format and size, whole frames, as sn_egress_yuv writes them.
+ *   Payload t is frame f = noise->t0 + t of the stream.  Per pixel (y, x), every float32 product and sum rounded separately (no FMA):
+ *   1. R, G, B: sn_ingest_yuv's float32 values of the pixel (its constants, its integer chroma upsampling for both 4:2:0 sitings, clamped to [0, 1]);
+ *      they are not rounded to a module dtype.
+ *   2. s: the curve noise->knots -- SN_NLF_BANDS = 16 sigmas in 8-bit R'G'B' code units, knot b at luma code lo + (b + 0.5) (hi - lo) / 16 with lo, hi
+ *      the format's black and white luma codes (16 s, 235 s limited; 0, 2^bits - 1 full) -- at the pixel's own CLEAN luma code Y, with
+ *      sn_noise_map_level's interpolation:  k[b] = knots[b] / 255, a float64 quotient rounded ONCE to float32;
+ *        u = min(max((float(Y) - float(lo)) * sc - 0.5, 0), 15)   with sc = 16 / (hi - lo), a float64 expression rounded ONCE to float32
+ *        i = min(int(floor(u)), 14);  e = u - float(i);  s = k[i] + e * (k[i + 1] - k[i])
+ *      A flat curve gives exactly k[0] at every pixel; a curve written here and one read by sn_noise_map_level mean the same thing.
+ *   3. R' = R + s * g(f, 0, y, x), G' = G + s * g(f, 1, y, x), B' = B + s * g(f, 2, y, x), NOT clamped, with g(f, c, y, x) = gauss[h >> 16] and
+ *        h = the murmur3 finaliser of  (y * 0x9E3779B1) ^ (x * 0x85EBCA77) ^ (f * 0xC2B2AE3D) ^ ((3 + c) * 0x27D4EB2F) ^ seed       (uint32, products wrap)
+ *      exactly as sn_egress_yuv_dither hashes: planes 3 .. 5 of the seed space whose planes 0 .. 2 are the dither's, so the two are independent.
+ *      gauss: 65536 float32 in DEVICE memory that the host makes once (shiftnet_amd/degrade.py: gauss_table): entry k is the standard normal quantile
+ *      at (k + 0.5) / 65536 in float64, divided by the root mean square of the 65536 quantiles, then rounded: mean 0, variance 1, antisymmetric, the
+ *      largest about 4.3.  A lookup and not Box-Muller: the numpy restatement is the kernel bit for bit.
+ *   4. The codes written are sn_egress_yuv's for the frame R', G', B': clamped to [0, 1], the matrix, both 4:2:0 downsampling filters with coordinates
+ *      clamped to the frame (a clamped pixel is the frame's pixel at the clamped place, its noise included), rounding, the legal code range.
+ * The noise is a pure function of (seed, f, c, y, x): the bytes do not depend on the launch geometry, and T frames in one launch are the T launches
+ * with t0, t0 + 1, ...  (tests/degrade_ref.py restates it in numpy; the kernel equals it bit for bit.)  The per-thread layout is sn_egress_yuv's: 8 x 2
+ * pixels, wide loads and stores where the address allows, element-wise with the same arithmetic elsewhere; the left-sited 4:2:0 filter's pixel
+ * x0 - 1 is recomputed by the thread that needs it.  Only dst is written.
+ * SN_EINVAL before anything is launched: everything sn_egress_yuv refuses of fmt, T, H, W and dst, the same of src; a null noise or gauss; gauss not
+ * 4-byte aligned; t0 < 0; a knot that is negative or not finite; byte ranges [src, src + T frame_bytes) and [dst, dst + T frame_bytes) that overlap. */
+typedef struct sn_yuv_degrade_noise { uint32_t seed; int t0; float knots[16]; } sn_yuv_degrade_noise;
+int sn_yuv_degrade(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_degrade_noise* noise, const float* gauss /* device, 65536 */, uint8_t* dst,
+                   int T, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,20 +21,10 @@
 // Both are bandwidth kernels.  A thread owns four horizontally adjacent 2x2 luma blocks (8 x 2 pixels), so that every chroma sample is
 // produced once and the 8 pixels of a row are one 8 / 16 B load and one 16 / 2 x 16 B store where the address is aligned; a thread
 // whose span is not aligned, or touches the frame edge or the padding, takes the element-wise path with the same arithmetic.
-#include "sn_yuv.h"
+#include "sn_yuv_color.h"
 #pragma clang fp contract(off)
 
 namespace {
-
-struct YuvK {
-    // ingest: R = ky*(Y - yoff) + crv*(V - coff), G = (ky*(Y - yoff) + cgu*(U - coff)) + cgv*(V - coff), B = ky*(Y - yoff) + cbu*(U - coff)
-    float ky, crv, cgu, cgv, cbu;
-    // egress: Y' = (kr*R + kg*G) + kb*B, Cb = (B - Y')*cu, Cr = (R - Y')*cv; code = rint(off + scale * value)
-    float kr, kg, kb, cu, cv, ys, yo, cs, co;
-    int yoff, coff, ylo, yhi, clo, chi;
-};
-
-__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
 
 // ---- RGB tensor elements ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float h_lo(uint32_t u) { return __half2float(__ushort_as_half((unsigned short)(u & 0xffffu))); }
@@ -56,38 +46,7 @@ __device__ __forceinline__ void ld8_any(const void* p, int dt, size_t i, bool ve
     }
 }
 
-// ---- ingest -------------------------------------------------------------------------------------------------------------------
-// CH: SN_YUV_444 / SN_YUV_420_CENTER / SN_YUV_420_LEFT.  Chroma reaches the matrix as an integer numerator over DEN (1 / 16 / 8):
-//   centre: (3 * (3 * C[j][i] + C[jn][i]) + (3 * C[j][in] + C[jn][in])) / 16 with (j, i) = (y >> 1, x >> 1) and jn / in the neighbour
-//           on the side of the luma sample (odd: +1, even: -1), clamped to the plane;
-//   left:   v(c) = 3 * C[j][c] + C[jn][c]; even x: 2 * v(i) / 8, odd x: (v(i) + v(min(i + 1, cw - 1))) / 8.
-template <int CH> struct Den { static constexpr int value = CH == SN_YUV_444 ? 1 : (CH == SN_YUV_420_CENTER ? 16 : 8); };
-
-template <int CH> __device__ __forceinline__ void yuv_to_rgb(const YuvK& K, int y, int un, int vn, float* r, float* g, float* b) {
-    constexpr float inv = 1.0f / Den<CH>::value;
-    const float yd = (float)(y - K.yoff);
-    const float ud = mulr((float)(un - Den<CH>::value * K.coff), inv);        // exact: a power of two times an integer < 2^15
-    const float vd = mulr((float)(vn - Den<CH>::value * K.coff), inv);
-    const float yy = mulr(K.ky, yd);
-    *r = clamp01(addr(yy, mulr(K.crv, vd)));
-    *g = clamp01(addr(addr(yy, mulr(K.cgu, ud)), mulr(K.cgv, vd)));
-    *b = clamp01(addr(yy, mulr(K.cbu, ud)));
-}
-
-template <int ESZ, int CH> __device__ __forceinline__ int chroma_num(const uint8_t* p, int pc, int cw, int ch, int ye, int xe) {
-    const int j = ye >> 1, i = xe >> 1;
-    const int jn = imin(imax(j + ((ye & 1) ? 1 : -1), 0), ch - 1);
-    const size_t rj = (size_t)j * pc, rn = (size_t)jn * pc;
-    if (CH == SN_YUV_420_CENTER) {
-        const int in = imin(imax(i + ((xe & 1) ? 1 : -1), 0), cw - 1);
-        return 3 * (3 * ld1<ESZ>(p, rj + i) + ld1<ESZ>(p, rn + i)) + (3 * ld1<ESZ>(p, rj + in) + ld1<ESZ>(p, rn + in));
-    }
-    const int v0 = 3 * ld1<ESZ>(p, rj + i) + ld1<ESZ>(p, rn + i);
-    if (!(xe & 1)) return 2 * v0;
-    const int i1 = imin(i + 1, cw - 1);
-    return v0 + (3 * ld1<ESZ>(p, rj + i1) + ld1<ESZ>(p, rn + i1));
-}
-
+// ---- ingest (the chroma numerators and the matrix: sn_yuv_color.h) ----------------------------------------------------------------------
 template <int ESZ, int CH>
 __global__ __launch_bounds__(256) void ingest_yuv_kernel(const uint8_t* __restrict__ src, void* __restrict__ dst, int dt, const YuvK K,
                                                        const YuvGeo G, int Hp, int Wp, int dst_vec) {
@@ -169,24 +128,17 @@ __global__ __launch_bounds__(256) void ingest_yuv_kernel(const uint8_t* __restri
 }
 
 // ---- egress -------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int quant(float off, float scale, float v, int lo, int hi) {
-    return imin(imax(__float2int_rn(addr(off, mulr(scale, v))), lo), hi);
-}
-
 // The dither of a launch.  DITHER is a template parameter of the kernel: SN_DITHER_NONE carries nothing and every line below that touches a
 // key is dead in it, so the instantiations the entry points without _dither launch are the ones they launched before there was a dither.
 template <int DITHER> struct DitherK { static constexpr int mode = DITHER; };
 template <> struct DitherK<SN_DITHER_TPDF> { static constexpr int mode = SN_DITHER_TPDF; uint32_t seed; uint32_t t0; };
 template <int DITHER> __device__ __forceinline__ uint32_t dither_frame_key(const DitherK<DITHER>&, int) { return 0u; }
 template <> __device__ __forceinline__ uint32_t dither_frame_key<SN_DITHER_TPDF>(const DitherK<SN_DITHER_TPDF>& D, int t) {
-    return ((D.t0 + (uint32_t)t) * 0xC2B2AE3Du) ^ D.seed;
+    return hash_frame_key(D.seed, D.t0 + (uint32_t)t);
 }
-// plane p, row y of the plane: the part of the key that a row of samples shares (uint32 arithmetic wraps)
-__device__ __forceinline__ uint32_t dither_row_key(uint32_t fk, int p, int y) { return fk ^ ((uint32_t)p * 0x27D4EB2Fu) ^ ((uint32_t)y * 0x9E3779B1u); }
-// the sample at column x of that row: the murmur3 finaliser of the key, two 12-bit fields of it summed to a triangle on (-1, 1); exact in float32
+// the sample at column x of that row (the keys and the hash: sn_yuv_color.h): two 12-bit fields of it summed to a triangle on (-1, 1); exact in float32
 __device__ __forceinline__ float dither_tpdf(uint32_t rk, int x) {
-    uint32_t k = rk ^ ((uint32_t)x * 0x85EBCA77u);
-    k ^= k >> 16; k *= 0x85EBCA6Bu; k ^= k >> 13; k *= 0xC2B2AE35u; k ^= k >> 16;
+    const uint32_t k = hash_sample(rk, x);
     return mulr((float)((int)(k & 0xFFFu) + (int)((k >> 12) & 0xFFFu) - 4095), 1.0f / 4096.0f);
 }
 // code = clamp(rint((off + scale * v) + d)); without dither the line above
@@ -314,28 +266,6 @@ __global__ __launch_bounds__(256) void egress_yuv_kernel(const void* __restrict_
             if (nc == 4) stn<ESZ, 4>(pl ? vp : up, o, q); else for (int i = 0; i < nc; ++i) st1<ESZ>(pl ? vp : up, o + i, q[i]);
         }
     }
-}
-
-// constants: float64 expressions rounded once to float32 (tests/yuv_ref.py: constants() evaluates the same expressions)
-bool make_consts(const sn_yuv_fmt* f, YuvK* K) {
-    if (!valid_fmt(f) || f->matrix < 0 || f->matrix > 1 || f->range < 0 || f->range > 1) return false;
-    const double kr = f->matrix == SN_YUV_BT709 ? 0.2126 : 0.299, kb = f->matrix == SN_YUV_BT709 ? 0.0722 : 0.114;
-    const double kg = 1.0 - kr - kb;
-    const int s = 1 << (f->bits - 8), top = (1 << f->bits) - 1;
-    const bool full = f->range == SN_YUV_FULL;
-    const double yo = full ? 0.0 : 16.0 * s, ys = full ? (double)top : 219.0 * s, cs = full ? (double)top : 224.0 * s, co = 128.0 * s;
-    K->ky = (float)(1.0 / ys);
-    K->crv = (float)(2.0 * (1.0 - kr) / cs);
-    K->cgu = (float)(-2.0 * kb * (1.0 - kb) / kg / cs);
-    K->cgv = (float)(-2.0 * kr * (1.0 - kr) / kg / cs);
-    K->cbu = (float)(2.0 * (1.0 - kb) / cs);
-    K->kr = (float)kr; K->kg = (float)kg; K->kb = (float)kb;
-    K->cu = (float)(1.0 / (2.0 * (1.0 - kb)));
-    K->cv = (float)(1.0 / (2.0 * (1.0 - kr)));
-    K->ys = (float)ys; K->yo = (float)yo; K->cs = (float)cs; K->co = (float)co;
-    K->yoff = (int)yo; K->coff = (int)co;
-    K->ylo = full ? 0 : 16 * s; K->yhi = full ? top : 235 * s; K->clo = full ? 0 : 16 * s; K->chi = full ? top : 240 * s;
-    return true;
 }
 
 }  // namespace

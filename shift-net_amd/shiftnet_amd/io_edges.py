@@ -17,6 +17,8 @@ the statistics of the same payloads' luma (csrc/sn_yuv_stats.hip), each for one 
 ``noise_hist_pairs_mv_yuv`` / ``noise_hist_pairs_bands_mv_yuv``: the two pair statistics with the second payload's block taken where the vector
                points, for the motion-compensated temporal estimate (shiftnet_amd/noise.py);
 ``noise_map_level``: payloads + the 16 knots of such a function -> the denoisers' noise plane;
+``degrade_yuv``: clean payloads + the 16 knots of a noise curve -> the payloads with Gaussian noise added to R'G'B' (csrc/sn_degrade.hip), for the
+               restorer's ``add_noise`` stage: the degraded copy that the comparison with a ground truth needs;
 ``rowcol_sums_yuv``: uint32 sums of the luma codes of every row and of every column, for the letterbox rule (shiftnet_amd/picture.py);
 ``diff_stats_yuv``: int64 sums of the difference of two sets of payloads, what came in and what was written, for the method-noise report
                (shiftnet_amd/report.py);
@@ -39,6 +41,7 @@ the statistics of the same payloads' luma (csrc/sn_yuv_stats.hip), each for one 
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from typing import List, Optional, Tuple
 
@@ -205,6 +208,31 @@ def egress_yuv(out: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, dst: Optional
             L.check(L.load().sn_egress_yuv(out.data_ptr(), _CODE[out.dtype], fmt, y.data_ptr(), T, H, W, Hp, Wp, st), "sn_egress_yuv")
         else:
             L.check(L.load().sn_egress_yuv_rect(out.data_ptr(), _CODE[out.dtype], fmt, r, y.data_ptr(), T, H, W, Hp, Wp, st), "sn_egress_yuv_rect")
+    return y
+
+
+def degrade_yuv(src: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, knots, seed: int, t0: int, gauss: torch.Tensor,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src: [T, frame_bytes] uint8 on a HIP device, T clean payloads of H x W, frames t0 .. t0 + T - 1 of their stream -> [T, frame_bytes] uint8, the
+    same frames with Gaussian noise added to R'G'B' between the two colour edges (include/shiftnet_hip.h: sn_yuv_degrade): ``egress(ingest_float32(src) +
+    s * g)``, in one launch and with no float frame in memory.  ``knots``: the 16 sigmas of the noise curve in 8-bit R'G'B' code units, finite and >= 0,
+    knot b at luma code lo + (b + 0.5) (hi - lo) / 16 of the format's black and white codes (noise.knot_codes); s is the curve at the pixel's clean luma
+    code.  ``seed`` (0 .. 2^32 - 1) picks the noise, a hash of the seed, the frame's number in the stream, the channel, the row and the column.
+    ``gauss``: float32 [65536] on the same device, degrade.gauss_table().  ``out``: a [T, frame_bytes] uint8 tensor to fill, another than ``src``."""
+    T, dev = _payload(src, fmt, H, W)
+    kn = [float(k) for k in knots]
+    if len(kn) != L.SN_NLF_BANDS or not all(math.isfinite(k) and k >= 0.0 for k in kn):
+        raise ValueError(f"knots: need {L.SN_NLF_BANDS} finite numbers >= 0, got {knots!r}")
+    seed, t0 = int(seed), int(t0)
+    if not (0 <= seed < 2 ** 32) or not (0 <= t0 <= 2 ** 31 - 1 - T):
+        raise ValueError(f"need 0 <= seed < 2^32 and 0 <= t0 <= 2^31 - 1 - T, got seed {seed!r}, t0 {t0!r}")
+    assert gauss.dtype == torch.float32 and tuple(gauss.shape) == (1 << 16,) and gauss.is_contiguous() and gauss.device == dev
+    y = out if out is not None else torch.empty_like(src)
+    assert _payload(y, fmt, H, W) == (T, dev)
+    noise = L.YuvDegradeNoise(seed, t0, (C.c_float * L.SN_NLF_BANDS)(*kn))
+    with torch.cuda.device(dev):
+        L.check(L.load().sn_yuv_degrade(src.data_ptr(), fmt, noise, gauss.data_ptr(), y.data_ptr(), T, H, W,
+                                        torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_degrade")
     return y
 
 

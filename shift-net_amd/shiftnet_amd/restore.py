@@ -36,6 +36,10 @@ windows that overlap in time (``window_overlap``): each is a part of its own, de
 
 Ground truth (``restore(..., gt=...)``, off by default; needs ``report``): a second stream, the clean frames of which the input is a degraded copy, goes
 through the pipeline beside the input, and the report gains PSNR and SSIM of the input and of every frame written against it (shiftnet_amd/fullref.py).
+
+Added noise (``add_noise``, off by default): the other half of that experiment.  The frames given are the clean stream; a stage in front of everything
+else degrades them on the device (``sn_yuv_degrade``, shiftnet_amd/degrade.py), the degraded payloads are the input of all the rest, and under
+``report`` the clean ones are the truth.
 """
 from __future__ import annotations
 
@@ -102,7 +106,8 @@ class _Run:
                          "fullref": 0,                            # gt: the difference sums and the SSIM sums of input and written frames against the truth
                          "tile": 0,                               # tile: the tiles added into the canvas
                          "geo_transform": 0, "geo_accumulate": 0, # ensemble: the members' inputs made, their results added into the canvas
-                         "overlap": 0}                            # window_overlap: the cross-fades of shared frames
+                         "overlap": 0,                            # window_overlap: the cross-fades of shared frames
+                         "degrade": 0}                            # add_noise: the chunks of the clean stream degraded
         self.window_written: List[int] = []                       # window_overlap: the frames every window wrote
         self.seam_rms: List = []                                  # ... and per window None or the rms difference of the two answers on every shared frame
         self.window_tiles: List = []                              # tile: per window, the (y0, x0, th, tw) of its tiles in the order they ran
@@ -167,6 +172,62 @@ class _DeviceThumbs:
 
     def is_cut(self, t: int) -> bool:
         return self.detector.is_cut(t)
+
+
+# ---- noise added to a clean stream, in front of everything else ----------------------------------------------------------------------
+class _DeviceDegrade:
+    """``add_noise``: the clean stream's payloads -> the degraded stream's, which the rest of restore() takes for its input (sn_yuv_degrade).
+
+    A stage in front of the frame source, in the style of _DeviceThumbs: chunks of up to ``chunk`` host payloads go through a pinned buffer to the device
+    on a stream of the stage's own, one launch degrades the chunk, one copy brings the payloads back into pinned memory, and the calling thread
+    waits for the event recorded behind that copy -- never for the device, and never for the stream the forward runs on.  The noise of a frame is
+    keyed by its index in the STREAM, which only this stage knows: whatever the windows, the scenes and the reflections make of a frame later, it
+    carries the same noise.  ``keep_clean``: the clean payloads queue up as the run's truth (``truth()``), in the order the frames are written."""
+
+    def __init__(self, torch, dev, fmt, h: int, w: int, chunk: int, knots: Sequence[float], seed: int, keep_clean: bool, run: "_Run") -> None:
+        from collections import deque
+        from .degrade import gauss_table
+        self.torch, self.dev, self.fmt, self.h, self.w, self.chunk, self.knots, self.seed, self.run = torch, dev, fmt, h, w, chunk, knots, seed, run
+        fb = fmt.frame_bytes(h, w)
+        self.pin_in, self.pin_out = (torch.empty((chunk, fb), dtype=torch.uint8).pin_memory() for _ in range(2))
+        self.dev_in, self.dev_out = (torch.empty((chunk, fb), dtype=torch.uint8, device=dev) for _ in range(2))
+        self.gauss = torch.from_numpy(gauss_table().copy()).to(dev)
+        self.stream, self.event = torch.cuda.Stream(dev), torch.cuda.Event()
+        self.clean = deque() if keep_clean else None
+
+    def frames(self, it: Iterable[np.ndarray], tap=None) -> Iterator[np.ndarray]:
+        """The degraded payloads of ``it``'s clean ones, in order; ``tap`` is called with each before it is handed on."""
+        from itertools import islice
+        from .io_edges import degrade_yuv
+        torch = self.torch
+        it, f0 = iter(it), 0
+        while True:
+            part = list(islice(it, self.chunk))
+            t = len(part)
+            if not t:
+                return
+            pin = self.pin_in.numpy()
+            for i, f in enumerate(part):
+                pin[i] = f
+            with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+                self.dev_in[:t].copy_(self.pin_in[:t], non_blocking=True)
+                degrade_yuv(self.dev_in[:t], self.fmt, self.h, self.w, self.knots, self.seed, f0, self.gauss, out=self.dev_out[:t])
+                self.pin_out[:t].copy_(self.dev_out[:t], non_blocking=True)
+                self.event.record()
+            self.run.launches["degrade"] += 1
+            self.event.synchronize()
+            if self.clean is not None:
+                self.clean.extend(pin[:t].copy())
+            f0 += t
+            for d in self.pin_out[:t].numpy().copy():
+                if tap is not None:
+                    tap(d)
+                yield d
+
+    def truth(self) -> Iterator[np.ndarray]:
+        """The clean payloads, oldest first: a window's own frames have been read, and so degraded, before the stager asks for their truth."""
+        while True:
+            yield self.clean.popleft()
 
 
 # ---- the restorer -----------------------------------------------------------------------------------------------------------------
@@ -368,7 +429,24 @@ class VideoRestorer:
     ``stats["window_written"]`` the frames every window wrote, ``stats["overlap_launches"]`` the launches.  **A window still costs one forward, and
     there are one_len / (one_len - V) times as many.  The cross-fade blends two different answers -- restored with different sigmas, possibly -- so a
     mismatch becomes a ramp over V frames and is not removed.  Nobody has looked at a seam of a trained network: no checkpoint ships, and ``seam_rms`` on
-    synthetic weights says nothing about one; it is there so that somebody with a checkpoint can find out.**"""
+    synthetic weights says nothing about one; it is there so that somebody with a checkpoint can find out.**
+    add_noise: None -- the frames given are the input, today's launches, bytes and stats keys; a number, or 16 numbers (each finite and >= 0) -- the
+    frames given are a CLEAN stream, and a stage in front of everything else makes the input from them on the device (``sn_yuv_degrade``,
+    csrc/sn_degrade.hip; shiftnet_amd/degrade.py): ``egress(ingest_float32(frame) + s * g)``, Gaussian noise g, i.i.d. per R'G'B' channel and pixel, with
+    sigma s in 8-bit code units -- the number, or the curve of 16 knots (noise.knot_codes, what ``noise_model`` reads) at the pixel's own clean luma
+    code.  Chunks of up to ``one_len`` payloads go to the device on a stream of the stage's own, one launch each, and come back as payloads; the rest
+    of restore() -- the cut detector, the stager, every statistic, ``amount``, ``view`` -- takes the degraded payloads for THE input and is untouched.
+    The noise of a frame is a hash of ``add_noise_seed`` (0 .. 2^32 - 1), the frame's index in the stream, the channel, the row and the column: a frame
+    carries the same noise as a window's own frame, as a neighbour's halo, reflected at a clip's end, and under ``scene_cuts`` and ``window_overlap``.
+    With ``report=True`` the clean payloads are the run's truth by the mechanism of ``gt``: ``stats["frame_fullref"]`` and the report's eight columns
+    appear without a second stream.  ``restore(..., degraded=callable)`` is called with every degraded payload, in order.  ``add_noise`` with ``gt`` is
+    a ValueError, and so is ``add_noise`` with ``report`` and an ``out_format`` that differs from the input's (the truth would have to be converted).
+    ``stats`` then also has ``add_noise`` (the 16 knots), ``add_noise_seed`` and ``degrade_launches``.  **The conversion round trip runs even at sigma
+    0**: at 4:2:0 the degraded stream's chroma has been up- and down-sampled once, ``psnr_u_in`` / ``psnr_v_in`` include that, and sigma 0 is not the
+    input byte for byte.  **The noise is clipped** to [0, 1] and to the legal codes on the way out; **its tails end at about 4.3 sigma** (a table of
+    65536 quantiles); it is added before the chroma subsampling and depends on the clean luma only: what the networks were trained with, not a sensor
+    and a codec.  **Bars are noised too**: ``picture="auto"`` then needs a higher ``bar_level``.  It covers the noise experiment only -- no blur is
+    synthesised for the deblur variants -- and says nothing about the network without a trained checkpoint."""
 
     def __init__(self, net, one_len: int, sigma=None, pipeline: bool = True, scene_cuts=None,
                  cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0),
@@ -376,8 +454,9 @@ class VideoRestorer:
                  amount=None, view=None, removed_gain: float = 1.0, sigma_estimator: str = "spatial", report: bool = False,
                  report_edge: float = 16.0, sigma_motion=None, report_motion=None, tile=None,
                  tile_overlap: int = DEFAULT_TILE_OVERLAP, ensemble=None, ensemble_time: bool = False, window_overlap: int = 0,
-                 report_quality=None, niqe_params=None) -> None:
+                 report_quality=None, niqe_params=None, add_noise=None, add_noise_seed: int = 0) -> None:
         import torch
+        from .degrade import add_noise_form
         from .lib import YuvFmt
         from .noise import check_clamp
         self.torch = torch
@@ -430,6 +509,7 @@ class VideoRestorer:
         self.ensemble_part = Ensemble(torch, net, self.dev, self.dtype, self.ensemble,
                                       plane=self.noise is not None and not self.noise.flat) if self.ensemble is not None else None
         self.overlap = Overlap(torch, self.dev, self.window_overlap) if self.window_overlap else None
+        self.add_noise, self.add_noise_seed = add_noise_form(add_noise, add_noise_seed)      # None: the code path without any of it; or the 16 knots
         self._shape = None
         self._reset()
 
@@ -666,6 +746,8 @@ class VideoRestorer:
         for part in (self.noise, self.report_part, self.tiles, self.ensemble_part, self.overlap):
             if part is not None:
                 part.finish(run, stats)
+        if self.add_noise is not None:
+            stats["add_noise"], stats["add_noise_seed"], stats["degrade_launches"] = list(self.add_noise), self.add_noise_seed, run.launches["degrade"]
         src = run.src
         if self.scene_cuts is not None:                          # its thread has ended: the stream has been read to its end
             stats["cuts"] = list(src.cuts)
@@ -687,14 +769,29 @@ class VideoRestorer:
         return self.run.src
 
     # -- drivers -------------------------------------------------------------------------------------------------------------------
-    def restore(self, frames: Iterable[np.ndarray], fmt, height: int, width: int, gt=None) -> Iterator[np.ndarray]:
+    def restore(self, frames: Iterable[np.ndarray], fmt, height: int, width: int, gt=None, degraded=None) -> Iterator[np.ndarray]:
         """frames: iterable of uint8 payloads (``fmt.frame_bytes(height, width)`` each) -> the restored payloads, in order.  gt: None, or an iterable of
-        ground-truth payloads in the format WRITTEN and of the stream's size, frame i the truth of written frame i (needs ``report=True``; see the class)."""
+        ground-truth payloads in the format WRITTEN and of the stream's size, frame i the truth of written frame i (needs ``report=True``; see the class).
+        degraded: None, or a callable that is given every payload ``add_noise`` makes of ``frames``, in order, on the thread that reads ``frames`` (needs
+        ``add_noise``)."""
         torch = self.torch
         if gt is not None and self.report_part is None:
             raise ValueError("gt adds PSNR and SSIM against the truth to the report: it needs report=True")
+        if gt is not None and self.add_noise is not None:
+            raise ValueError("add_noise makes the clean frames the truth of the report: not together with gt")
+        if degraded is not None and self.add_noise is None:
+            raise ValueError("degraded is given the payloads add_noise makes: it needs add_noise")
         self._prepare(fmt, height, width)
+        if self.add_noise is not None and self.report_part is not None and self.convert:
+            raise ValueError(f"add_noise with report and out_format={self.out_format!r}, another format than the input's: the clean frames, the truth of "
+                             "the report, would have to be converted")
         self._reset()
+        stage = None
+        if self.add_noise is not None:
+            stage = _DeviceDegrade(torch, self.dev, fmt, height, width, self.one_len, self.add_noise, self.add_noise_seed, self.report_part is not None,
+                                   self.run)
+            if self.report_part is not None:
+                gt = stage.truth()
         if gt is not None:
             self.run.gt = iter(gt)
             for s in self.slots:                                 # once per stream shape, and only for a run that asks
@@ -720,7 +817,7 @@ class VideoRestorer:
         def windows():
             """(the slot, the frames, their first restored frame's number in its clip, the frames shared with the predecessor, the frames written) of
             every window, in the order they are restored."""
-            src = self._source(checked(frames))
+            src = self._source(checked(frames) if stage is None else stage.frames(checked(frames), degraded))
             for k, win, clip_lo in src.windows(self.one_len, self.window_overlap):
                 yield self.slots[k % 2], win, clip_lo, src.head, src.written
 

@@ -52,6 +52,15 @@ def report_edge_arg(word: str) -> float:
     return v
 
 
+def add_noise_arg(word: str):
+    """--add_noise: SIGMA or s0,...,s15 -> the 16 knots."""
+    from .degrade import parse_add_noise
+    try:
+        return parse_add_noise(word)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def tile_arg(word: str):
     """--tile: N -> the int (N x N tiles); HxW -> (H, W)."""
     parts = word.lower().split("x")
@@ -152,6 +161,15 @@ def make_parser() -> argparse.ArgumentParser:
                          "Y-channel SSIM of the evaluation harnesses: 11 x 11 Gaussian window, replicated border, every frame and every position); sums on "
                          "the device; LUMA SSIM ONLY, no MS-SSIM or VMAF; the streams must be frame-aligned, no offset is searched; no threshold, no "
                          "verdict, nothing fed back; changes no byte written; default: the report as it is without")
+    ap.add_argument("--add_noise", type=add_noise_arg, default=None, metavar="{SIGMA,s0,...,s15}",
+                    help="IN is a CLEAN stream: add Gaussian noise to it on the device and restore the degraded stream; SIGMA is the standard deviation in "
+                         "8-bit R'G'B' code values, 16 comma-separated values are a curve from black to white (the knots --noise_model FILE reads) taken at "
+                         "the clean pixel's luma; with --report the clean frames are the truth and the report has the columns of --gt (not together with "
+                         "--gt, nor with --report and an --out_format other than the input's).  I.i.d. per R'G'B' channel, added before chroma subsampling: "
+                         "what the networks were trained with, not a sensor and a codec; clipped to the legal codes; tails end at about 4.3 sigma; the "
+                         "colour conversion round trip runs even at 0, so 0 is not the input byte for byte; bars are noised too; default: IN is the input")
+    ap.add_argument("--add_noise_seed", type=int, default=0, metavar="N", help="--add_noise: which noise (0 .. 2^32 - 1); the same seed gives the same bytes")
+    ap.add_argument("--degraded_out", default=None, metavar="FILE", help="--add_noise: write the degraded stream, a Y4M with the input's header")
     ap.add_argument("--tile", type=tile_arg, default=None, metavar="{N,HxW}",
                     help="for frames whose activations do not fit the device: run the network on overlapping tiles of H x W samples (N: N x N) of every "
                          "window, one after the other, and blend their results with feather weights on the device; both sides multiples of 4 (8 for "
@@ -208,6 +226,11 @@ def _listed(ap: argparse.ArgumentParser, flag: str, word: str, read):
         ap.error(f"{flag} {word}: {e}")
 
 
+def _injected(knots) -> str:
+    """The level --add_noise injected, for the log: the number, or the ends of the curve."""
+    return "%g" % knots[0] if min(knots) == max(knots) else "a curve, %g at black .. %g at white" % (knots[0], knots[-1])
+
+
 def _write_out(path: Optional[str], write, *args) -> None:
     """A --*_out option: ``write(path, *args)`` where a path was given."""
     if path is not None:
@@ -248,6 +271,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error(f"--report_quality / --niqe_params: {str(e).replace('report=True', '--report')}")
     if a.gt is not None and a.report is None:                     # as above: before any file is opened
         ap.error("--gt adds its columns to the report: it needs --report")
+    if a.add_noise is not None and a.gt is not None:              # as above: before any file is opened
+        ap.error("--add_noise makes the clean input the truth of the report: not together with --gt")
+    if a.add_noise is None and (a.degraded_out is not None or a.add_noise_seed != 0):
+        ap.error("--add_noise_seed / --degraded_out need --add_noise")
+    if not (0 <= a.add_noise_seed < 2 ** 32):
+        ap.error("--add_noise_seed: an integer in 0 .. 2^32 - 1")
     if a.tile is None and a.tile_overlap is not None:             # as above: before any file is opened
         ap.error("--tile_overlap needs --tile")
     tile_overlap = DEFAULT_TILE_OVERLAP if a.tile_overlap is None else a.tile_overlap
@@ -302,7 +331,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         picture, picture_how = _listed(ap, "--picture", picture, pic.read_pictures), "listed"
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
     fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
-    fgt = None
+    fgt = fdeg = None
     try:
         rd = Y4MReader(fin)
         hd = rd.header
@@ -318,6 +347,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 ap.error(f"--gt {a.gt}: the truth is {got.width}x{got.height}, the stream written is {want.width}x{want.height}")
             if (got.bits, got.chroma_code) != (want.bits, want.chroma_code):
                 ap.error(f"--gt {a.gt}: the truth is C{got.chroma}, the stream written is C{want.chroma}: the truth must be in the format written")
+        if a.add_noise is not None and a.report is not None:      # as above: the clean input is the truth, in the format read
+            want = output_header(hd, a.out_format)
+            if (want.bits, want.chroma_code) != (hd.bits, hd.chroma_code):
+                ap.error(f"--add_noise with --report and --out_format {a.out_format}: the truth is the clean input, C{hd.chroma}, the stream written is "
+                         f"C{want.chroma}; it would have to be converted")
         matrix = a.matrix or ("bt709" if hd.height >= 720 else "bt601")
         rng = a.range or (hd.color_range if hd.color_range in ("full", "limited") else "limited")
         log(f"input: {hd.width}x{hd.height} C{hd.chroma} F{hd.fps}; matrix {matrix}{'' if a.matrix else ' (default)'}, range {rng}"
@@ -331,7 +365,16 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                            amount=a.amount, view=view, removed_gain=a.removed_gain, sigma_estimator=a.sigma_estimator,
                            report=a.report is not None, report_edge=a.report_edge, sigma_motion=None if a.sigma_motion == "none" else a.sigma_motion,
                            report_motion=report_motion, tile=a.tile, tile_overlap=tile_overlap, ensemble=a.ensemble,
-                           ensemble_time=a.ensemble_time, window_overlap=a.window_overlap, report_quality=report_quality, niqe_params=a.niqe_params)
+                           ensemble_time=a.ensemble_time, window_overlap=a.window_overlap, report_quality=report_quality, niqe_params=a.niqe_params,
+                           add_noise=a.add_noise, add_noise_seed=a.add_noise_seed)
+        wdeg = None
+        if a.add_noise is not None:
+            kn = vr.add_noise
+            log(f"added noise: sigma {_injected(kn)} in 8-bit R'G'B' codes, seed "
+                f"{a.add_noise_seed}; IN is the clean stream{', and the truth of the report' if a.report is not None else ''}")
+            if a.degraded_out is not None:
+                fdeg = open(a.degraded_out, "wb")
+                wdeg = Y4MWriter(fdeg, hd)
         if vr.ensemble is not None:
             log(f"ensemble: {len(vr.ensemble[2])} forwards per window (ops {vr.ensemble[2]}); what it gains on this network nobody has measured")
         if vr.window_overlap:
@@ -348,7 +391,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         wr = Y4MWriter(fout, output_header(hd, a.out_format))
         t0 = time.perf_counter()
         n = 0
-        for p in vr.restore(rd, fmt, hd.height, hd.width, gt=gt):
+        for p in vr.restore(rd, fmt, hd.height, hd.width, gt=gt, degraded=None if wdeg is None else wdeg.write):
             wr.write(p)
             n += 1
             if n % max(a.one_len, 1) == 0:
@@ -389,7 +432,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 f"window{'' if len(wn) == 1 else 's'}")
         if ws:
             log(f"sigma ({sigma_how}{', ' + a.sigma_estimator if a.sigma_estimator != 'spatial' else ''}{', motion ' + a.sigma_motion if a.sigma_motion != 'none' else ''}{', clamped to [%g, %g]' % tuple(a.sigma_clamp) if sigma_how == 'auto' else ''}): "
-                f"min {min(ws):.2f} / median {float(np.median(ws)):.2f} / max {max(ws):.2f} over {len(ws)} window{'' if len(ws) == 1 else 's'}")
+                f"min {min(ws):.2f} / median {float(np.median(ws)):.2f} / max {max(ws):.2f} over {len(ws)} window{'' if len(ws) == 1 else 's'}"
+                f"{'; injected ' + _injected(vr.add_noise) if vr.add_noise is not None else ''}")
         if a.report is not None:
             fr = vr.stats["frame_report"]
             _write_out(a.report, _text_writer(rep.format_report), fr, f"edge {a.report_edge:g}", vr.stats.get("frame_report_motion"), vr.stats.get("frame_niqe"),
@@ -402,9 +446,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             if report_quality is not None:
                 log(f"quality (NIQE of the luma, medians over the frames with a score; no verdict, unvalidated on real footage): "
                     f"{rep.summary_line_quality(vr.stats['report_quality_summary'])}")
-            if gt is not None:
+            if gt is not None or a.add_noise is not None:
                 from .fullref import summary_line_fullref
-                log(f"against the ground truth ({a.gt}; PSNR in dB, SSIM of the luma; _in the input, _out the frames written; no verdict): "
+                log(f"against the ground truth ({a.gt or 'the clean input'}; PSNR in dB, SSIM of the luma; _in the input, _out the frames written; no verdict): "
                     f"{summary_line_fullref(vr.stats['fullref_summary'])}")
     finally:
         if fin is not sys.stdin.buffer:
@@ -413,4 +457,6 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             fout.close()
         if fgt is not None:
             fgt.close()
+        if fdeg is not None:
+            fdeg.close()
     return 0

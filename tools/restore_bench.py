@@ -58,6 +58,9 @@
             kernel reads, once -- and beside sn_yuv_diff_stats on the same frames, interleaved as in the kernels part.  --mode forward: steady-state wall
             time per 720p window of the pipelined denoiser (as the report part) with report=True alone and with gt= on top, runs of the two alternating in
             one process, the first two windows left out.
+  degrade : --mode kernels: sn_yuv_degrade on 16 frames of 1280 x 720 at 8-bit 4:2:0 (both sitings) and at 10-bit 4:4:4 beside sn_egress_yuv from float32
+            and a plain device copy of the same payloads, interleaved; microseconds per launch and TB/s of each case's own bytes.  --mode forward: the
+            stream restored with add_noise=10 and report=True against the same stream degraded beforehand and restored with the clean one as gt.
 Prints one JSON object per part.
 """
 import argparse
@@ -734,6 +737,85 @@ def fullref_forward(a):
                       "runs": a.runs, "fullref_means": {k: round(v, 4) for k, v in seen[True]["mean"].items()}, **res}))
 
 
+def degrade_kernels(a):
+    from shiftnet_amd import degrade
+    from shiftnet_amd.io_edges import degrade_yuv
+    T, H, W = 16, 720, 1280
+    blur, _ = synth.blurred_clip(4, H, W, seed=1)
+    rgb = ingest_u8(torch.from_numpy(np.concatenate([blur] * 4)).cuda(), torch.float32)[0]
+    gauss = torch.from_numpy(degrade.gauss_table().copy()).cuda()
+    knots = [10.0] * 16
+    cases, nbytes = {}, {}
+    for tag, f in (("420p8", yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)), ("420p8_left", yuv_fmt(8, L.SN_YUV_420_LEFT, L.SN_YUV_BT709, L.SN_YUV_LIMITED)),
+                   ("444p10", yuv_fmt(10, L.SN_YUV_444, L.SN_YUV_BT709, L.SN_YUV_LIMITED))):
+        clean = egress_yuv(rgb, f, H, W)
+        dst = torch.empty_like(clean)
+        fb = f.frame_bytes(H, W)
+        cases["degrade_yuv_" + tag] = (lambda c=clean, d=dst, f=f: degrade_yuv(c, f, H, W, knots, 1, 0, gauss, out=d))
+        cases["egress_yuv_fp32_" + tag] = (lambda d=dst, f=f: egress_yuv(rgb, f, H, W, dst=d))
+        cases["copy_payloads_" + tag] = (lambda c=clean, d=dst: d.copy_(c, non_blocking=True))
+        nbytes["degrade_yuv_" + tag] = nbytes["copy_payloads_" + tag] = 2 * T * fb                    # the kernel's own bytes: every payload read once, written once
+        nbytes["egress_yuv_fp32_" + tag] = T * (12 * H * W + fb)
+    for f in cases.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in cases}
+    for _ in range(a.reps):
+        for k, f in cases.items():                                                   # interleaved: every repetition times every kernel
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.inner):
+                f()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.inner)
+    res = {k: {"us_per_launch": summary([m * 1e3 for m in v]), "tb_per_s": summary([nbytes[k] / (m * 1e-3) / 1e12 for m in v]), "bytes": nbytes[k]} for k, v in ms.items()}
+    print(json.dumps({"part": "degrade", "mode": "kernels", "frames": T, "size": [H, W], "reps": a.reps, "inner": a.inner, **res}))
+
+
+def degrade_forward(a):
+    """--add_noise 10 --report on a clean stream against the same stream degraded beforehand and run with the clean one as gt: the difference is the stage."""
+    H, W, one_len, nwin = 720, 1280, 16, a.windows
+    n = one_len * nwin
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    blur, _ = synth.blurred_clip(8, H, W, seed=2)
+    rgb = ingest_u8(torch.from_numpy(blur).cuda(), torch.float32)[0]
+    truth = []
+    for i in range(n):
+        j = i % 14
+        truth.append(egress_yuv(rgb[j if j < 8 else 14 - j][None], fmt, H, W)[0].cpu().numpy())
+    net = restore.load_net("denoise_small", "synthetic", "bf16")
+    frames, seen = [], {}
+
+    def run(stage):
+        vr = restore.VideoRestorer(net, one_len, sigma=10.0, pipeline=True, report=True, **({"add_noise": 10.0} if stage else {}))
+        stamps = []
+        t0 = time.perf_counter()
+        more = {"degraded": lambda p: frames.append(p.copy())} if stage and not frames else ({} if stage else {"gt": iter(truth)})
+        for i, p in enumerate(vr.restore(iter(truth if stage else frames), fmt, H, W, **more)):
+            if (i + 1) % one_len == 0:
+                stamps.append(time.perf_counter())
+        total = time.perf_counter() - t0
+        seen[stage] = vr.stats["fullref_summary"]
+        gaps = [(b - c) * 1e3 for b, c in zip(stamps[1:], stamps[:-1])]
+        return {"total_s": total, "window_wall_ms": gaps[1:], "window_forward_ms": vr.stats["window_forward_ms"][2:]}
+
+    run(True)                                                                        # warm-up: code objects, engine buffers; and the degraded stream for the other side
+    run(False)
+    runs = {"pre_degraded_gt": [], "add_noise": []}
+    for _ in range(a.runs):
+        runs["pre_degraded_gt"].append(run(False))
+        runs["add_noise"].append(run(True))
+    res = {}
+    for k, rs in runs.items():
+        res[k] = {"window_wall_ms": summary([g for r in rs for g in r["window_wall_ms"]]),
+                  "window_wall_ms_per_run": [round(statistics.median(r["window_wall_ms"]), 2) for r in rs],
+                  "window_forward_ms": summary([g for r in rs for g in r["window_forward_ms"]]), "total_s": [round(r["total_s"], 3) for r in rs]}
+    print(json.dumps({"part": "degrade", "mode": "forward", "variant": "denoise_small", "dtype": "bf16", "one_len": one_len, "windows": nwin, "size": [H, W],
+                      "runs": a.runs, "same_numbers": seen[True] == seen[False], "fullref_means": {k: round(v, 4) for k, v in seen[True]["mean"].items()}, **res}))
+
+
 def _tile_word(word):
     return None if word == "full" else restore.tile_arg(word)
 
@@ -1037,7 +1119,7 @@ def picture_part(a):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion", "tiles", "overlap", "quality", "fullref"])
+    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion", "tiles", "overlap", "quality", "fullref", "degrade"])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--inner", type=int, default=200)
     ap.add_argument("--windows", type=int, default=8)
@@ -1066,4 +1148,5 @@ if __name__ == "__main__":
          "tiles": tiles_quality if a.mode == "quality" else tiles_forward,
          "overlap": overlap_kernels if a.mode == "kernels" else overlap_forward,
          "quality": quality_kernels if a.mode == "kernels" else quality_forward,
-         "fullref": fullref_kernels if a.mode == "kernels" else fullref_forward}[a.part](a)
+         "fullref": fullref_kernels if a.mode == "kernels" else fullref_forward,
+         "degrade": degrade_kernels if a.mode == "kernels" else degrade_forward}[a.part](a)
