@@ -950,6 +950,41 @@ typedef struct sn_yuv_degrade_noise { uint32_t seed; int t0; float knots[16]; } 
 int sn_yuv_degrade(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_degrade_noise* noise, const float* gauss /* device, 65536 */, uint8_t* dst,
                    int T, int H, int W, void* stream);
 
+/* ---- motion blur of a sharp stream (csrc/sn_blur.hip; a new symbol and a new struct, SN_ABI_VERSION stays 20) ----------------------------------------
+ * The same experiment for the deblurrers (VideoRestorer(add_blur=...)): a blurred copy of a sharp stream, made as the deblur datasets are -- GOPRO and
+ * DVD average consecutive frames of a high-frame-rate stream, GOPRO in linear light through an inverse gamma of 2.2, and keep the sharp centre frame
+ * for the truth -- but from payloads to payloads, with no float frame in memory.
+ *   src: S payloads of fmt, H x W, as sn_ingest_yuv takes them; dst: T payloads of the same format and size, whole frames, as sn_egress_yuv writes them.
+ *   win: n taps, odd, 1 .. SN_BLUR_MAX_TAPS, r = n / 2.  Output t is the mean over j = -r .. r of source payload clamp(c0 + t + j, lo, hi): a clamped
+ *   index counts as often as it occurs, so the ends of a stream or of a scene [lo, hi] are replicated.
+ *   Per pixel (y, x) and channel, every float32 product and sum rounded separately (no FMA), no division, no powf, no exp2f:
+ *   1. Per tap j, R, G, B: sn_ingest_yuv's float32 values of the pixel in that source payload (its constants, its integer chroma upsampling for both
+ *      4:2:0 sitings, clamped to [0, 1]); they are not rounded to a module dtype.
+ *   2. With tables, each of them is decoded into linear light:
+ *        u = R * 4095.0f;  i = min((int)u, 4094);  e = u - (float)i;  v = lin[i] + e * (lin[i + 1] - lin[i])
+ *      Without tables (lin and rinv both NULL: gamma 1), v = R.
+ *   3. acc = v(-r), then acc = acc + v(j) in ascending j; m = acc * inv_n with inv_n = 1.0 / n, a float64 quotient rounded ONCE to float32.
+ *   4. With tables, the mean is encoded: i = the largest index in 0 .. 4094 with lin[i] <= m;
+ *        e = min((m - lin[i]) * rinv[i], 1.0f);  x = ((float)i + e) * k        with k = 1.0 / 4095, a float64 quotient rounded ONCE to float32
+ *      Without tables, x = m.
+ *      lin: 4096 float32 in DEVICE memory, strictly increasing from 0 to 1; rinv: 4095 float32 in DEVICE memory, rinv[i] = 1 / (lin[i + 1] - lin[i]); the
+ *      host makes both once per gamma (shiftnet_amd/degrade.py: gamma_tables: lin[i] = (i / 4095) ** gamma in float64, rounded once).  Tables and not
+ *      powf: the numpy restatement is the kernel bit for bit.  A pure power law, not the sRGB curve.
+ *   5. The codes written are sn_egress_yuv's for the frame x: clamped to [0, 1], the matrix, both 4:2:0 downsampling filters with coordinates clamped
+ *      to the frame, rounding, the legal code range.
+ * The bytes do not depend on the launch geometry, and T outputs in one launch are the T launches of one output with c0, c0 + 1, ...; n = 1 without
+ * tables is egress(ingest(src)).  (tests/blur_ref.py restates it in numpy; the kernel equals it bit for bit.)  The per-thread layout is sn_egress_yuv's:
+ * 8 x 2 pixels, wide loads and stores where the address allows, element-wise with the same arithmetic elsewhere; the left-sited 4:2:0 filter's pixel
+ * x0 - 1 is recomputed by the thread that needs it; blockIdx.z is the output frame; both tables are copied into LDS (32 KB).  Only dst is written.
+ * SN_EINVAL before anything is launched: everything sn_yuv_degrade refuses of fmt, T, H, W, src and dst; S < 1; a null win; n even or outside
+ * 1 .. SN_BLUR_MAX_TAPS; anything but 0 <= lo <= hi < S; c0 < lo or c0 + T - 1 > hi; exactly one of lin / rinv being null; a table that is not 4-byte
+ * aligned; byte ranges [src, src + S frame_bytes) and [dst, dst + T frame_bytes) that overlap.  No index reaches the device unchecked. */
+#define SN_BLUR_MAX_TAPS 15
+typedef struct sn_yuv_blur_window { int n; int c0; int lo; int hi; } sn_yuv_blur_window;
+int sn_yuv_blur(const uint8_t* src, int S, const sn_yuv_fmt* fmt, const sn_yuv_blur_window* win,
+                const float* lin /* device, 4096, or NULL */, const float* rinv /* device, 4095, or NULL */,
+                uint8_t* dst, int T, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,8 @@ the statistics of the same payloads' luma (csrc/sn_yuv_stats.hip), each for one 
 ``noise_map_level``: payloads + the 16 knots of such a function -> the denoisers' noise plane;
 ``degrade_yuv``: clean payloads + the 16 knots of a noise curve -> the payloads with Gaussian noise added to R'G'B' (csrc/sn_degrade.hip), for the
                restorer's ``add_noise`` stage: the degraded copy that the comparison with a ground truth needs;
+``blur_yuv``: sharp payloads -> the means of n consecutive ones on R'G'B', in linear light where gamma tables are given (csrc/sn_blur.hip), for the
+               restorer's ``add_blur`` stage: the same for the deblurrers;
 ``rowcol_sums_yuv``: uint32 sums of the luma codes of every row and of every column, for the letterbox rule (shiftnet_amd/picture.py);
 ``diff_stats_yuv``: int64 sums of the difference of two sets of payloads, what came in and what was written, for the method-noise report
                (shiftnet_amd/report.py);
@@ -233,6 +235,33 @@ def degrade_yuv(src: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, knots, seed:
     with torch.cuda.device(dev):
         L.check(L.load().sn_yuv_degrade(src.data_ptr(), fmt, noise, gauss.data_ptr(), y.data_ptr(), T, H, W,
                                         torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_degrade")
+    return y
+
+
+def blur_yuv(src: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, n: int, c0: int, lo: int, hi: int, tables, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src: [S, frame_bytes] uint8 on a HIP device, S sharp payloads of H x W; out: [T, frame_bytes] uint8 to fill, another than ``src`` (None: T =
+    hi - c0 + 1 fresh payloads) -> output t is the mean of the ``n`` (odd, 1 .. 15) source payloads clamp(c0 + t + j, lo, hi), j = -(n // 2) .. n // 2,
+    taken on R'G'B' between the two colour edges (include/shiftnet_hip.h: sn_yuv_blur), in one launch and with no float frame in memory.  [lo, hi], with
+    0 <= lo <= hi < S, is the scene the outputs c0 .. c0 + T - 1 lie in: its ends are replicated.  ``tables``: None -- the mean of the R'G'B' values as
+    they are (gamma 1); (lin, rinv) -- float32 [4096] and [4095] on the same device, degrade.gamma_tables(g): the mean in linear light."""
+    S, dev = _payload(src, fmt, H, W)
+    n, c0, lo, hi = int(n), int(c0), int(lo), int(hi)
+    if not (1 <= n <= L.SN_BLUR_MAX_TAPS and n % 2 == 1):
+        raise ValueError(f"n: need an odd number of taps, 1 .. {L.SN_BLUR_MAX_TAPS}, got {n!r}")
+    y = out if out is not None else torch.empty((max(hi - c0 + 1, 1), src.shape[1]), dtype=torch.uint8, device=dev)
+    T, ydev = _payload(y, fmt, H, W)
+    assert ydev == dev
+    if not (0 <= lo <= hi < S) or not (lo <= c0 and c0 + T - 1 <= hi):
+        raise ValueError(f"need 0 <= lo <= hi < S and lo <= c0, c0 + T - 1 <= hi, got lo {lo}, hi {hi}, c0 {c0} with S {S}, T {T}")
+    lin = rinv = None
+    if tables is not None:
+        lin, rinv = tables
+        for t, k in ((lin, 4096), (rinv, 4095)):
+            assert t.dtype == torch.float32 and tuple(t.shape) == (k,) and t.is_contiguous() and t.device == dev
+    win = L.YuvBlurWindow(n, c0, lo, hi)
+    with torch.cuda.device(dev):
+        L.check(L.load().sn_yuv_blur(src.data_ptr(), S, fmt, win, None if lin is None else lin.data_ptr(), None if rinv is None else rinv.data_ptr(),
+                                     y.data_ptr(), T, H, W, torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_blur")
     return y
 
 

@@ -26,7 +26,7 @@ SYMBOLS = [          # include/shiftnet_hip.h, production ABI
     "sn_ingest_yuv_rect", "sn_egress_yuv_rect", "sn_yuv_noise_hist_rect", "sn_yuv_rowcol_sums", "sn_egress_yuv_dither",
     "sn_yuv_noise_hist_bands", "sn_noise_map_level", "sn_egress_yuv_mix", "sn_yuv_noise_hist_pairs", "sn_yuv_noise_hist_pairs_bands",
     "sn_yuv_diff_stats", "sn_yuv_diff_stats_mv", "sn_yuv_block_motion", "sn_yuv_noise_hist_pairs_mv", "sn_yuv_noise_hist_pairs_bands_mv",
-    "sn_tile_accumulate", "sn_geo_transform", "sn_geo_accumulate", "sn_time_crossfade", "sn_yuv_niqe_sums", "sn_yuv_ssim_sums", "sn_yuv_degrade",
+    "sn_tile_accumulate", "sn_geo_transform", "sn_geo_accumulate", "sn_time_crossfade", "sn_yuv_niqe_sums", "sn_yuv_ssim_sums", "sn_yuv_degrade", "sn_yuv_blur",
     "sn32_conv2d", "sn32_conv2d_route", "sn32_gsts_gather", "sn32_layernorm", "sn32_gate", "sn32_gate_sum", "sn32_chan_sum", "sn32_scale_residual", "sn32_ingest", "sn32_cab_ca", "sn32_dw_gate", "sn32_conv1x1_gate2", "sn32_gsts_shiftconv", "sn32_conv_csum_tiles",
     "sn_ln_gemm_gate", "sn_lngate_blocks", "sn_grp5_gemm_gate", "sn_grp5_blocks", "sn_gsts_cab2_phase1", "sn_cab1_phase1", "sn_phase1_pool_blocks", "sn_phase1_g1_store_bytes", "sn_p1r_plan", "sn_p1r_strip_begin",
     "sn_cab2_phase2_cab1_phase1", "sn_cab2_phase2_cab1_phase1_supported",
@@ -170,6 +170,7 @@ class YuvRect(C.Structure):
 
 
 SN_DITHER_NONE, SN_DITHER_TPDF = 0, 1
+SN_BLUR_MAX_TAPS = 15 # the longest window of sn_yuv_blur
 SN_NLF_BANDS = 16    # knots of a noise-level function (sn_yuv_noise_hist_bands / sn_noise_map_level)
 SN_DIFF_STATS = 16   # int64 words per payload of sn_yuv_diff_stats
 SN_DIFF_STATS_MV = 8  # int64 words per pair of payloads of sn_yuv_diff_stats_mv
@@ -195,6 +196,11 @@ class YuvDegradeNoise(C.Structure):
     """sn_yuv_degrade_noise: the noise of sn_yuv_degrade; t0 is the stream's frame number of the launch's first payload, knots the sigma curve in 8-bit
     R'G'B' code units."""
     _fields_ = [("seed", C.c_uint32), ("t0", C.c_int), ("knots", C.c_float * SN_NLF_BANDS)]
+
+
+class YuvBlurWindow(C.Structure):
+    """sn_yuv_blur_window: output t of sn_yuv_blur is the mean of the n source payloads clamp(c0 + t + j, lo, hi), j = -(n / 2) .. n / 2."""
+    _fields_ = [("n", C.c_int), ("c0", C.c_int), ("lo", C.c_int), ("hi", C.c_int)]
 
 
 class ShiftNetLibError(RuntimeError):
@@ -292,6 +298,7 @@ def load() -> C.CDLL:
     lib.sn_yuv_niqe_sums.argtypes = [vp, C.POINTER(YuvFmt), C.POINTER(YuvRect), vp, vp, ci, ci, ci, vp]
     lib.sn_yuv_ssim_sums.argtypes = [vp, vp, C.POINTER(YuvFmt), C.POINTER(YuvRect), vp, ci, ci, ci, vp]
     lib.sn_yuv_degrade.argtypes = [vp, C.POINTER(YuvFmt), C.POINTER(YuvDegradeNoise), vp, vp, ci, ci, ci, vp]
+    lib.sn_yuv_blur.argtypes = [vp, ci, C.POINTER(YuvFmt), C.POINTER(YuvBlurWindow), vp, vp, vp, ci, ci, ci, vp]
     ll = C.c_longlong
     lib.sn32_conv2d.argtypes = [C.POINTER(Conv32Desc), vp]
     lib.sn32_conv2d_route.argtypes = [C.POINTER(Conv32Desc)]

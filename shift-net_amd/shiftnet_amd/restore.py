@@ -39,7 +39,8 @@ through the pipeline beside the input, and the report gains PSNR and SSIM of the
 
 Added noise (``add_noise``, off by default): the other half of that experiment.  The frames given are the clean stream; a stage in front of everything
 else degrades them on the device (``sn_yuv_degrade``, shiftnet_amd/degrade.py), the degraded payloads are the input of all the rest, and under
-``report`` the clean ones are the truth.
+``report`` the clean ones are the truth.  Added blur (``add_blur``, off by default) is the same stage for the deblurrers: every frame becomes the mean
+of the frames around it (``sn_yuv_blur``), as the deblur datasets are made.
 """
 from __future__ import annotations
 
@@ -107,7 +108,8 @@ class _Run:
                          "tile": 0,                               # tile: the tiles added into the canvas
                          "geo_transform": 0, "geo_accumulate": 0, # ensemble: the members' inputs made, their results added into the canvas
                          "overlap": 0,                            # window_overlap: the cross-fades of shared frames
-                         "degrade": 0}                            # add_noise: the chunks of the clean stream degraded
+                         "degrade": 0,                            # add_noise: the chunks of the clean stream degraded
+                         "blur": 0}                               # add_blur: the scene segments of the chunks of the sharp stream blurred
         self.window_written: List[int] = []                       # window_overlap: the frames every window wrote
         self.seam_rms: List = []                                  # ... and per window None or the rms difference of the two answers on every shared frame
         self.window_tiles: List = []                              # tile: per window, the (y0, x0, th, tw) of its tiles in the order they ran
@@ -174,60 +176,131 @@ class _DeviceThumbs:
         return self.detector.is_cut(t)
 
 
-# ---- noise added to a clean stream, in front of everything else ----------------------------------------------------------------------
-class _DeviceDegrade:
-    """``add_noise``: the clean stream's payloads -> the degraded stream's, which the rest of restore() takes for its input (sn_yuv_degrade).
+# ---- a degraded copy of a clean stream, made in front of everything else ----------------------------------------------------------------
+class _DeviceStage:
+    """What the stages in front of the frame source share (``add_noise``: _DeviceDegrade, ``add_blur``: _DeviceBlur), in the style of _DeviceThumbs:
+    host payloads go through a pinned buffer to the device on a stream of the stage's own, the stage's launches make up to ``chunk`` payloads of them,
+    one copy brings those back into pinned memory, and the calling thread waits for the event recorded behind that copy -- never for the device, and
+    never for the stream the forward runs on.  ``held``: the source payloads the device buffer has room for.  ``keep_clean``: the clean payloads queue
+    up as the run's truth (``truth()``), in the order the frames are read, which is the order they are written in."""
 
-    A stage in front of the frame source, in the style of _DeviceThumbs: chunks of up to ``chunk`` host payloads go through a pinned buffer to the device
-    on a stream of the stage's own, one launch degrades the chunk, one copy brings the payloads back into pinned memory, and the calling thread
-    waits for the event recorded behind that copy -- never for the device, and never for the stream the forward runs on.  The noise of a frame is
-    keyed by its index in the STREAM, which only this stage knows: whatever the windows, the scenes and the reflections make of a frame later, it
-    carries the same noise.  ``keep_clean``: the clean payloads queue up as the run's truth (``truth()``), in the order the frames are written."""
-
-    def __init__(self, torch, dev, fmt, h: int, w: int, chunk: int, knots: Sequence[float], seed: int, keep_clean: bool, run: "_Run") -> None:
+    def __init__(self, torch, dev, fmt, h: int, w: int, chunk: int, held: int, keep_clean: bool, run: "_Run") -> None:
         from collections import deque
-        from .degrade import gauss_table
-        self.torch, self.dev, self.fmt, self.h, self.w, self.chunk, self.knots, self.seed, self.run = torch, dev, fmt, h, w, chunk, knots, seed, run
+        self.torch, self.dev, self.fmt, self.h, self.w, self.chunk, self.run = torch, dev, fmt, h, w, chunk, run
         fb = fmt.frame_bytes(h, w)
-        self.pin_in, self.pin_out = (torch.empty((chunk, fb), dtype=torch.uint8).pin_memory() for _ in range(2))
-        self.dev_in, self.dev_out = (torch.empty((chunk, fb), dtype=torch.uint8, device=dev) for _ in range(2))
-        self.gauss = torch.from_numpy(gauss_table().copy()).to(dev)
+        self.pin_in, self.pin_out = (torch.empty((k, fb), dtype=torch.uint8).pin_memory() for k in (held, chunk))
+        self.dev_in, self.dev_out = (torch.empty((k, fb), dtype=torch.uint8, device=dev) for k in (held, chunk))
         self.stream, self.event = torch.cuda.Stream(dev), torch.cuda.Event()
         self.clean = deque() if keep_clean else None
+
+    def _chunk(self, part: Sequence[np.ndarray], at: int, launch, tap) -> Iterator[np.ndarray]:
+        """``part``: the host payloads read for this chunk -> dev_in[at : at + len(part)]; ``launch()``, on the stage's stream, leaves t payloads in
+        dev_out and returns t; -> their host copies, in order, ``tap`` called with each before it is handed on."""
+        torch = self.torch
+        k = len(part)
+        pin = self.pin_in.numpy()
+        for i, f in enumerate(part):
+            pin[i] = f
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            if k:
+                self.dev_in[at:at + k].copy_(self.pin_in[:k], non_blocking=True)
+            t = launch()
+            self.pin_out[:t].copy_(self.dev_out[:t], non_blocking=True)
+            self.event.record()
+        self.event.synchronize()
+        if self.clean is not None:
+            self.clean.extend(pin[:k].copy())
+        for d in self.pin_out[:t].numpy().copy():
+            if tap is not None:
+                tap(d)
+            yield d
+
+    def truth(self) -> Iterator[np.ndarray]:
+        """The clean payloads, oldest first: a window's own frames have been read, and so degraded, before the stager asks for their truth."""
+        while True:
+            yield self.clean.popleft()
+
+
+class _DeviceDegrade(_DeviceStage):
+    """``add_noise``: the clean stream's payloads -> the degraded stream's, which the rest of restore() takes for its input (sn_yuv_degrade).
+
+    Chunks of up to ``chunk`` payloads, one launch each.  The noise of a frame is keyed by its index in the STREAM, which only this stage knows:
+    whatever the windows, the scenes and the reflections make of a frame later, it carries the same noise."""
+
+    def __init__(self, torch, dev, fmt, h: int, w: int, chunk: int, knots: Sequence[float], seed: int, keep_clean: bool, run: "_Run") -> None:
+        from .degrade import gauss_table
+        super().__init__(torch, dev, fmt, h, w, chunk, chunk, keep_clean, run)
+        self.knots, self.seed = knots, seed
+        self.gauss = torch.from_numpy(gauss_table().copy()).to(dev)
 
     def frames(self, it: Iterable[np.ndarray], tap=None) -> Iterator[np.ndarray]:
         """The degraded payloads of ``it``'s clean ones, in order; ``tap`` is called with each before it is handed on."""
         from itertools import islice
         from .io_edges import degrade_yuv
-        torch = self.torch
         it, f0 = iter(it), 0
         while True:
             part = list(islice(it, self.chunk))
             t = len(part)
             if not t:
                 return
-            pin = self.pin_in.numpy()
-            for i, f in enumerate(part):
-                pin[i] = f
-            with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
-                self.dev_in[:t].copy_(self.pin_in[:t], non_blocking=True)
-                degrade_yuv(self.dev_in[:t], self.fmt, self.h, self.w, self.knots, self.seed, f0, self.gauss, out=self.dev_out[:t])
-                self.pin_out[:t].copy_(self.dev_out[:t], non_blocking=True)
-                self.event.record()
-            self.run.launches["degrade"] += 1
-            self.event.synchronize()
-            if self.clean is not None:
-                self.clean.extend(pin[:t].copy())
-            f0 += t
-            for d in self.pin_out[:t].numpy().copy():
-                if tap is not None:
-                    tap(d)
-                yield d
 
-    def truth(self) -> Iterator[np.ndarray]:
-        """The clean payloads, oldest first: a window's own frames have been read, and so degraded, before the stager asks for their truth."""
+            def launch() -> int:
+                degrade_yuv(self.dev_in[:t], self.fmt, self.h, self.w, self.knots, self.seed, f0, self.gauss, out=self.dev_out[:t])
+                self.run.launches["degrade"] += 1
+                return t
+
+            yield from self._chunk(part, 0, launch, tap)
+            f0 += t
+
+
+class _DeviceBlur(_DeviceStage):
+    """``add_blur``: the sharp stream's payloads -> the blurred stream's, which the rest of restore() takes for its input (sn_yuv_blur).
+
+    Output f is the mean of the n frames around frame f of the stream, so the stage reads r = n // 2 frames ahead of the chunk it makes, and launches
+    once per scene segment of the chunk (degrade.plan_blur): under a LISTED ``scene_cuts`` the averaging window is clamped to the frame's scene, as it
+    is to the stream's two ends.  **The 2r halo frames are carried on the device**: the device buffer holds chunk + 2r source payloads, and after a
+    chunk's launches the payloads the next chunk's windows reach back to are moved to its front (two device copies of at most 2r payloads); only new
+    frames are uploaded, each once."""
+
+    def __init__(self, torch, dev, fmt, h: int, w: int, chunk: int, n: int, gamma: float, cuts, keep_clean: bool, run: "_Run") -> None:
+        from .degrade import gamma_tables
+        r = n // 2
+        super().__init__(torch, dev, fmt, h, w, chunk, chunk + 2 * r, keep_clean, run)
+        self.n, self.cuts = n, cuts
+        self.tables = None if gamma == 1.0 else tuple(torch.from_numpy(t.copy()).to(dev) for t in gamma_tables(gamma))
+        self.halo = torch.empty((2 * r, fmt.frame_bytes(h, w)), dtype=torch.uint8, device=dev) if r else None
+
+    def frames(self, it: Iterable[np.ndarray], tap=None) -> Iterator[np.ndarray]:
+        """The blurred payloads of ``it``'s sharp ones, in order; ``tap`` is called with each before it is handed on."""
+        from itertools import islice
+        from .degrade import plan_blur
+        from .io_edges import blur_yuv
+        it, r = iter(it), self.n // 2
+        f0, base, held, ended = 0, 0, 0, False                   # the next output; dev_in[:held] are frames base .. base + held - 1 of the stream
         while True:
-            yield self.clean.popleft()
+            want = f0 + self.chunk + r - (base + held)           # up to r frames past the chunk
+            part = [] if ended else list(islice(it, want))
+            ended = ended or len(part) < want
+            S = held + len(part)
+            last = base + S - 1
+            t = min(self.chunk, last - f0 + 1)
+            if t < 1:
+                return
+            keep_from = max(base, f0 + t - r)                    # what the next chunk's windows reach back to
+
+            def launch() -> int:
+                for a, cnt, lo, hi in plan_blur(f0, t, self.n, self.cuts, last, ended):
+                    blur_yuv(self.dev_in[:S], self.fmt, self.h, self.w, self.n, a - base, max(lo, base) - base, min(hi, last) - base, self.tables,
+                             out=self.dev_out[a - f0:a - f0 + cnt])
+                    self.run.launches["blur"] += 1
+                k = last + 1 - keep_from
+                if k > 0 and keep_from > base:                   # through a buffer of its own: the two ranges may overlap
+                    self.halo[:k].copy_(self.dev_in[keep_from - base:S])
+                    self.dev_in[:k].copy_(self.halo[:k])
+                return t
+
+            yield from self._chunk(part, held, launch, tap)
+            f0, base, held = f0 + t, keep_from, max(last + 1 - keep_from, 0)
 
 
 # ---- the restorer -----------------------------------------------------------------------------------------------------------------
@@ -446,7 +519,20 @@ class VideoRestorer:
     input byte for byte.  **The noise is clipped** to [0, 1] and to the legal codes on the way out; **its tails end at about 4.3 sigma** (a table of
     65536 quantiles); it is added before the chroma subsampling and depends on the clean luma only: what the networks were trained with, not a sensor
     and a codec.  **Bars are noised too**: ``picture="auto"`` then needs a higher ``bar_level``.  It covers the noise experiment only -- no blur is
-    synthesised for the deblur variants -- and says nothing about the network without a trained checkpoint."""
+    synthesised by it (``add_blur`` does that) -- and says nothing about the network without a trained checkpoint.
+    add_blur: None -- as above; an odd integer N in 1 .. 15 -- the frames given are a SHARP stream, and the same stage in front of everything else
+    makes the input from them on the device (``sn_yuv_blur``, csrc/sn_blur.hip; shiftnet_amd/degrade.py): frame f of the input is the mean of frames
+    f - N // 2 .. f + N // 2 of the stream, taken on R'G'B' between the two colour edges, in linear light through ``add_blur_gamma`` (finite, in
+    [1, 3], default 2.2, GOPRO's; exactly 1 averages the R'G'B' values as they are, DVD's) -- how the deblur datasets are made, with the sharp centre
+    frame for the truth.  The window is clamped at the stream's two ends, so the first and last frames are replicated.  With a LISTED ``scene_cuts``
+    it is clamped to the frame's scene as well.  **With ``scene_cuts="auto"`` it is not: the cuts are found afterwards, on the blurred stream, and the
+    blur crosses them** -- N // 2 frames on either side of a cut are a mix of two scenes, and the detector sees a cross-fade where the cut was.  The
+    stage reads N // 2 frames ahead, launches once per scene segment of a chunk of ``one_len`` frames, and carries the frames two chunks share on the
+    device.  ``report``, ``degraded`` and the refusals are ``add_noise``'s (not with ``gt``; not with ``report`` and another ``out_format``); and
+    ``add_blur`` with ``add_noise`` is a ValueError: no network here was trained on both.  ``stats`` then also has ``add_blur``, ``add_blur_gamma``
+    and ``blur_launches``.  **The blur is a box over N frames of the stream as it is**: its length in time is N / fps of the input, no frame is
+    dropped, and a stream that was not shot at a high frame rate gets ghosting and not motion blur.  **A pure power law, not the sRGB curve; not a
+    lens and not a rolling shutter.**  **N = 1 still runs the conversion round trip** (see ``add_noise``), and **bars are averaged too**."""
 
     def __init__(self, net, one_len: int, sigma=None, pipeline: bool = True, scene_cuts=None,
                  cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0),
@@ -454,9 +540,10 @@ class VideoRestorer:
                  amount=None, view=None, removed_gain: float = 1.0, sigma_estimator: str = "spatial", report: bool = False,
                  report_edge: float = 16.0, sigma_motion=None, report_motion=None, tile=None,
                  tile_overlap: int = DEFAULT_TILE_OVERLAP, ensemble=None, ensemble_time: bool = False, window_overlap: int = 0,
-                 report_quality=None, niqe_params=None, add_noise=None, add_noise_seed: int = 0) -> None:
+                 report_quality=None, niqe_params=None, add_noise=None, add_noise_seed: int = 0, add_blur=None,
+                 add_blur_gamma: float = 2.2) -> None:
         import torch
-        from .degrade import add_noise_form
+        from .degrade import add_blur_form, add_noise_form
         from .lib import YuvFmt
         from .noise import check_clamp
         self.torch = torch
@@ -510,6 +597,9 @@ class VideoRestorer:
                                       plane=self.noise is not None and not self.noise.flat) if self.ensemble is not None else None
         self.overlap = Overlap(torch, self.dev, self.window_overlap) if self.window_overlap else None
         self.add_noise, self.add_noise_seed = add_noise_form(add_noise, add_noise_seed)      # None: the code path without any of it; or the 16 knots
+        self.add_blur, self.add_blur_gamma = add_blur_form(add_blur, add_blur_gamma)          # None: the code path without any of it; or the taps
+        if self.add_blur is not None and self.add_noise is not None:
+            raise ValueError("add_blur together with add_noise: no network here was trained on both, pick one")
         self._shape = None
         self._reset()
 
@@ -748,6 +838,8 @@ class VideoRestorer:
                 part.finish(run, stats)
         if self.add_noise is not None:
             stats["add_noise"], stats["add_noise_seed"], stats["degrade_launches"] = list(self.add_noise), self.add_noise_seed, run.launches["degrade"]
+        if self.add_blur is not None:
+            stats["add_blur"], stats["add_blur_gamma"], stats["blur_launches"] = self.add_blur, self.add_blur_gamma, run.launches["blur"]
         src = run.src
         if self.scene_cuts is not None:                          # its thread has ended: the stream has been read to its end
             stats["cuts"] = list(src.cuts)
@@ -772,26 +864,30 @@ class VideoRestorer:
     def restore(self, frames: Iterable[np.ndarray], fmt, height: int, width: int, gt=None, degraded=None) -> Iterator[np.ndarray]:
         """frames: iterable of uint8 payloads (``fmt.frame_bytes(height, width)`` each) -> the restored payloads, in order.  gt: None, or an iterable of
         ground-truth payloads in the format WRITTEN and of the stream's size, frame i the truth of written frame i (needs ``report=True``; see the class).
-        degraded: None, or a callable that is given every payload ``add_noise`` makes of ``frames``, in order, on the thread that reads ``frames`` (needs
-        ``add_noise``)."""
+        degraded: None, or a callable that is given every payload ``add_noise`` or ``add_blur`` makes of ``frames``, in order, on the thread that reads
+        ``frames`` (needs one of the two)."""
         torch = self.torch
         if gt is not None and self.report_part is None:
             raise ValueError("gt adds PSNR and SSIM against the truth to the report: it needs report=True")
-        if gt is not None and self.add_noise is not None:
-            raise ValueError("add_noise makes the clean frames the truth of the report: not together with gt")
-        if degraded is not None and self.add_noise is None:
-            raise ValueError("degraded is given the payloads add_noise makes: it needs add_noise")
+        option = "add_noise" if self.add_noise is not None else ("add_blur" if self.add_blur is not None else None)
+        if gt is not None and option is not None:
+            raise ValueError(f"{option} makes the clean frames the truth of the report: not together with gt")
+        if degraded is not None and option is None:
+            raise ValueError("degraded is given the payloads add_noise or add_blur makes: it needs one of them")
         self._prepare(fmt, height, width)
-        if self.add_noise is not None and self.report_part is not None and self.convert:
-            raise ValueError(f"add_noise with report and out_format={self.out_format!r}, another format than the input's: the clean frames, the truth of "
+        if option is not None and self.report_part is not None and self.convert:
+            raise ValueError(f"{option} with report and out_format={self.out_format!r}, another format than the input's: the clean frames, the truth of "
                              "the report, would have to be converted")
         self._reset()
         stage = None
         if self.add_noise is not None:
             stage = _DeviceDegrade(torch, self.dev, fmt, height, width, self.one_len, self.add_noise, self.add_noise_seed, self.report_part is not None,
                                    self.run)
-            if self.report_part is not None:
-                gt = stage.truth()
+        elif self.add_blur is not None:
+            stage = _DeviceBlur(torch, self.dev, fmt, height, width, self.one_len, self.add_blur, self.add_blur_gamma,
+                                self.scene_cuts if self.cuts_mode == "list" else None, self.report_part is not None, self.run)
+        if stage is not None and self.report_part is not None:
+            gt = stage.truth()
         if gt is not None:
             self.run.gt = iter(gt)
             for s in self.slots:                                 # once per stream shape, and only for a run that asks

@@ -61,6 +61,15 @@ def add_noise_arg(word: str):
         raise argparse.ArgumentTypeError(str(e)) from None
 
 
+def add_blur_arg(word: str) -> int:
+    """--add_blur: N -> the odd number of frames averaged."""
+    from .degrade import parse_add_blur
+    try:
+        return parse_add_blur(word)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def tile_arg(word: str):
     """--tile: N -> the int (N x N tiles); HxW -> (H, W)."""
     parts = word.lower().split("x")
@@ -169,7 +178,20 @@ def make_parser() -> argparse.ArgumentParser:
                          "what the networks were trained with, not a sensor and a codec; clipped to the legal codes; tails end at about 4.3 sigma; the "
                          "colour conversion round trip runs even at 0, so 0 is not the input byte for byte; bars are noised too; default: IN is the input")
     ap.add_argument("--add_noise_seed", type=int, default=0, metavar="N", help="--add_noise: which noise (0 .. 2^32 - 1); the same seed gives the same bytes")
-    ap.add_argument("--degraded_out", default=None, metavar="FILE", help="--add_noise: write the degraded stream, a Y4M with the input's header")
+    ap.add_argument("--degraded_out", default=None, metavar="FILE",
+                    help="--add_noise / --add_blur: write the degraded stream, a Y4M with the input's header")
+    ap.add_argument("--add_blur", type=add_blur_arg, default=None, metavar="N",
+                    help="IN is a SHARP stream: blur it on the device and restore the blurred stream, for the deblur variants; every frame becomes the mean "
+                         "of N consecutive frames around it (N odd, 1 .. 15), taken on R'G'B' in linear light (--add_blur_gamma), as the deblur datasets "
+                         "(GOPRO, DVD) are made; the window is clamped at the stream's ends and, with a LISTED --scene_cuts, to the frame's scene; with "
+                         "--scene_cuts auto the cuts are found afterwards on the blurred stream and the blur crosses them; with --report the sharp frames "
+                         "are the truth and the report has the columns of --gt (not together with --gt or --add_noise, nor with --report and an "
+                         "--out_format other than the input's).  A box over N frames of the stream as it is: its length in time is N / fps of the input, "
+                         "no frame is dropped; a pure power law, not the sRGB curve; not a lens and not a rolling shutter; N = 1 still runs the colour "
+                         "conversion round trip, so it is not the input byte for byte; bars are averaged too; default: IN is the input")
+    ap.add_argument("--add_blur_gamma", type=float, default=2.2, metavar="G",
+                    help="--add_blur: the power law between R'G'B' and the linear light the frames are averaged in, 1 .. 3; 1 averages the R'G'B' values "
+                         "as they are (default 2.2)")
     ap.add_argument("--tile", type=tile_arg, default=None, metavar="{N,HxW}",
                     help="for frames whose activations do not fit the device: run the network on overlapping tiles of H x W samples (N: N x N) of every "
                          "window, one after the other, and blend their results with feather weights on the device; both sides multiples of 4 (8 for "
@@ -273,8 +295,16 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--gt adds its columns to the report: it needs --report")
     if a.add_noise is not None and a.gt is not None:              # as above: before any file is opened
         ap.error("--add_noise makes the clean input the truth of the report: not together with --gt")
-    if a.add_noise is None and (a.degraded_out is not None or a.add_noise_seed != 0):
-        ap.error("--add_noise_seed / --degraded_out need --add_noise")
+    if a.add_blur is not None and a.gt is not None:
+        ap.error("--add_blur makes the sharp input the truth of the report: not together with --gt")
+    if a.add_blur is not None and a.add_noise is not None:
+        ap.error("--add_blur together with --add_noise: no network here was trained on both, pick one")
+    if a.add_noise is None and (a.add_noise_seed != 0 or (a.degraded_out is not None and a.add_blur is None)):
+        ap.error("--add_noise_seed / --degraded_out need --add_noise (--degraded_out also goes with --add_blur)")
+    if a.add_blur is None and a.add_blur_gamma != 2.2:
+        ap.error("--add_blur_gamma needs --add_blur")
+    if not (1.0 <= a.add_blur_gamma <= 3.0):
+        ap.error("--add_blur_gamma: a number in 1 .. 3")
     if not (0 <= a.add_noise_seed < 2 ** 32):
         ap.error("--add_noise_seed: an integer in 0 .. 2^32 - 1")
     if a.tile is None and a.tile_overlap is not None:             # as above: before any file is opened
@@ -347,11 +377,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 ap.error(f"--gt {a.gt}: the truth is {got.width}x{got.height}, the stream written is {want.width}x{want.height}")
             if (got.bits, got.chroma_code) != (want.bits, want.chroma_code):
                 ap.error(f"--gt {a.gt}: the truth is C{got.chroma}, the stream written is C{want.chroma}: the truth must be in the format written")
-        if a.add_noise is not None and a.report is not None:      # as above: the clean input is the truth, in the format read
+        if (a.add_noise is not None or a.add_blur is not None) and a.report is not None:      # as above: the clean input is the truth, in the format read
             want = output_header(hd, a.out_format)
             if (want.bits, want.chroma_code) != (hd.bits, hd.chroma_code):
-                ap.error(f"--add_noise with --report and --out_format {a.out_format}: the truth is the clean input, C{hd.chroma}, the stream written is "
-                         f"C{want.chroma}; it would have to be converted")
+                ap.error(f"{'--add_noise' if a.add_noise is not None else '--add_blur'} with --report and --out_format {a.out_format}: the truth is the "
+                         f"clean input, C{hd.chroma}, the stream written is C{want.chroma}; it would have to be converted")
         matrix = a.matrix or ("bt709" if hd.height >= 720 else "bt601")
         rng = a.range or (hd.color_range if hd.color_range in ("full", "limited") else "limited")
         log(f"input: {hd.width}x{hd.height} C{hd.chroma} F{hd.fps}; matrix {matrix}{'' if a.matrix else ' (default)'}, range {rng}"
@@ -366,15 +396,20 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                            report=a.report is not None, report_edge=a.report_edge, sigma_motion=None if a.sigma_motion == "none" else a.sigma_motion,
                            report_motion=report_motion, tile=a.tile, tile_overlap=tile_overlap, ensemble=a.ensemble,
                            ensemble_time=a.ensemble_time, window_overlap=a.window_overlap, report_quality=report_quality, niqe_params=a.niqe_params,
-                           add_noise=a.add_noise, add_noise_seed=a.add_noise_seed)
+                           add_noise=a.add_noise, add_noise_seed=a.add_noise_seed, add_blur=a.add_blur, add_blur_gamma=a.add_blur_gamma)
         wdeg = None
+        if a.add_blur is not None:
+            log(f"added blur: the mean of {a.add_blur} frame{'' if a.add_blur == 1 else 's'} (a box of {a.add_blur} frame times at F{hd.fps}), "
+                f"{'of the RGB values as they are' if a.add_blur_gamma == 1.0 else 'in linear light through gamma %g' % a.add_blur_gamma}; "
+                f"IN is the sharp stream{', and the truth of the report' if a.report is not None else ''}"
+                f"{'; the blur crosses the cuts --scene_cuts auto finds' if a.scene_cuts == 'auto' and a.add_blur > 1 else ''}")
         if a.add_noise is not None:
             kn = vr.add_noise
             log(f"added noise: sigma {_injected(kn)} in 8-bit R'G'B' codes, seed "
                 f"{a.add_noise_seed}; IN is the clean stream{', and the truth of the report' if a.report is not None else ''}")
-            if a.degraded_out is not None:
-                fdeg = open(a.degraded_out, "wb")
-                wdeg = Y4MWriter(fdeg, hd)
+        if a.degraded_out is not None:
+            fdeg = open(a.degraded_out, "wb")
+            wdeg = Y4MWriter(fdeg, hd)
         if vr.ensemble is not None:
             log(f"ensemble: {len(vr.ensemble[2])} forwards per window (ops {vr.ensemble[2]}); what it gains on this network nobody has measured")
         if vr.window_overlap:
@@ -446,7 +481,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             if report_quality is not None:
                 log(f"quality (NIQE of the luma, medians over the frames with a score; no verdict, unvalidated on real footage): "
                     f"{rep.summary_line_quality(vr.stats['report_quality_summary'])}")
-            if gt is not None or a.add_noise is not None:
+            if gt is not None or a.add_noise is not None or a.add_blur is not None:
                 from .fullref import summary_line_fullref
                 log(f"against the ground truth ({a.gt or 'the clean input'}; PSNR in dB, SSIM of the luma; _in the input, _out the frames written; no verdict): "
                     f"{summary_line_fullref(vr.stats['fullref_summary'])}")

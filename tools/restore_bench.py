@@ -59,7 +59,8 @@
             time per 720p window of the pipelined denoiser (as the report part) with report=True alone and with gt= on top, runs of the two alternating in
             one process, the first two windows left out.
   degrade : --mode kernels: sn_yuv_degrade on 16 frames of 1280 x 720 at 8-bit 4:2:0 (both sitings) and at 10-bit 4:4:4 beside sn_egress_yuv from float32
-            and a plain device copy of the same payloads, interleaved; microseconds per launch and TB/s of each case's own bytes.  --mode forward: the
+            and a plain device copy of the same payloads, and sn_yuv_blur at n = 1, 7, 15 with and without gamma tables (16 - 2r outputs from the 16
+            sources), interleaved; microseconds per launch and TB/s of each case's own bytes.  --mode forward: the
             stream restored with add_noise=10 and report=True against the same stream degraded beforehand and restored with the clean one as gt.
 Prints one JSON object per part.
 """
@@ -739,12 +740,13 @@ def fullref_forward(a):
 
 def degrade_kernels(a):
     from shiftnet_amd import degrade
-    from shiftnet_amd.io_edges import degrade_yuv
+    from shiftnet_amd.io_edges import blur_yuv, degrade_yuv
     T, H, W = 16, 720, 1280
     blur, _ = synth.blurred_clip(4, H, W, seed=1)
     rgb = ingest_u8(torch.from_numpy(np.concatenate([blur] * 4)).cuda(), torch.float32)[0]
     gauss = torch.from_numpy(degrade.gauss_table().copy()).cuda()
     knots = [10.0] * 16
+    tables = tuple(torch.from_numpy(t.copy()).cuda() for t in degrade.gamma_tables(2.2))
     cases, nbytes = {}, {}
     for tag, f in (("420p8", yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)), ("420p8_left", yuv_fmt(8, L.SN_YUV_420_LEFT, L.SN_YUV_BT709, L.SN_YUV_LIMITED)),
                    ("444p10", yuv_fmt(10, L.SN_YUV_444, L.SN_YUV_BT709, L.SN_YUV_LIMITED))):
@@ -756,6 +758,12 @@ def degrade_kernels(a):
         cases["copy_payloads_" + tag] = (lambda c=clean, d=dst: d.copy_(c, non_blocking=True))
         nbytes["degrade_yuv_" + tag] = nbytes["copy_payloads_" + tag] = 2 * T * fb                    # the kernel's own bytes: every payload read once, written once
         nbytes["egress_yuv_fp32_" + tag] = T * (12 * H * W + fb)
+        for n in (1, 7, 15):                                                             # the 16 payloads are the sources: T - 2r outputs whose windows clamp nowhere
+            r, to = n // 2, T - 2 * (n // 2)
+            for how, tab in (("gamma", tables), ("plain", None)):
+                k = f"blur_yuv_n{n}_{how}_{tag}"
+                cases[k] = (lambda c=clean, d=dst, f=f, n=n, r=r, to=to, tab=tab: blur_yuv(c, f, H, W, n, r, 0, T - 1, tab, out=d[:to]))
+                nbytes[k] = (T + to) * fb                                                # the unique bytes: T = to + 2r payloads read, to written
     for f in cases.values():
         for _ in range(3):
             f()
