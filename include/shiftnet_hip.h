@@ -985,6 +985,39 @@ int sn_yuv_blur(const uint8_t* src, int S, const sn_yuv_fmt* fmt, const sn_yuv_b
                 const float* lin /* device, 4096, or NULL */, const float* rinv /* device, 4095, or NULL */,
                 uint8_t* dst, int T, int H, int W, void* stream);
 
+/* ---- grain put back on a restored stream (csrc/sn_grain.hip; a new symbol and a new struct, SN_ABI_VERSION stays 20) ---------------------------------
+ * The last step of "denoise, encode, re-grain" (VideoRestorer(grain=...)): a controlled share of fine, spatially correlated Gaussian grain on the codes
+ * that were written, from payloads to payloads.
+ *   src: T payloads of fmt, H x W; dst: T payloads of the same format and size.  rect == NULL: whole frames; else only the rectangle's samples, luma
+ *   and chroma, are read and written, and it is the picture (sn_egress_yuv_rect's rules).  Payload t is frame f = grain->t0 + t of its clip.
+ *   Float32 throughout, every product and sum rounded separately (no FMA); rint is round-to-nearest-even (__float2int_rn).
+ *   White field of plane p (6: Y, 7: Cb, 8: Cr; the dither owns 0 .. 2, sn_yuv_degrade 3 .. 5 of the same seed space):
+ *        g_p(f, y, x) = gauss[h >> 16],  h = the murmur3 finaliser of  (y * 0x9E3779B1) ^ (x * 0x85EBCA77) ^ (f * 0xC2B2AE3D) ^ (p * 0x27D4EB2F) ^ seed
+ *      y, x: the sample's row and column IN ITS OWN PLANE counted from the picture's first sample (the frame's, or the rectangle's as the dither counts
+ *      them).  Any integer is legal: negative coordinates wrap as uint32, so the field has no edge and nothing is clamped.  gauss: sn_yuv_degrade's table.
+ *   Correlated field: a separable 5-tap filter (w2, w1, w0, w1, w2) with taps = {w0, w1, w2}:
+ *        h(y, x) = (((w2 * g(y, x - 2) + w1 * g(y, x - 1)) + w0 * g(y, x)) + w1 * g(y, x + 1)) + w2 * g(y, x + 2)
+ *        c(y, x) = (((w2 * h(y - 2, x) + w1 * h(y - 1, x)) + w0 * h(y, x)) + w1 * h(y + 1, x)) + w2 * h(y + 2, x)
+ *   Level: s(Y), the curve grain->knots -- SN_NLF_BANDS = 16 values ALREADY IN LUMA CODE UNITS OF fmt (the host converts them) -- at a luma code, with
+ *      sn_yuv_degrade's interpolation: u = min(max((float(Y) - float(lo)) * sc - 0.5, 0), 15), sc = 16 / (hi - lo) in float64 rounded once;
+ *      i = min(int(floor(u)), 14); s = k[i] + (u - float(i)) * (k[i + 1] - k[i]).
+ *   Luma:   Y' = clamp(rint(float(Y) + s(Y) * c_6), min(ylo, Y), max(yhi, Y))
+ *   Chroma: C' = clamp(rint(float(C) + (chroma * s(Ym)) * c_p), min(clo, C), max(chi, C)), p = 7, 8; Ym is the luma code READ FROM src: at 4:4:4 the
+ *      same pixel's; at either 4:2:0 siting (Y00 + Y01 + Y10 + Y11 + 2) >> 2 of the sample's 2 x 2 block, coordinates clamped to the picture.  The
+ *      chroma field lives on the chroma plane's own lattice.
+ *   So: all knots 0 returns src byte for byte, illegal codes included; chroma == 0 leaves chroma as it came; taps {1, 0, 0} is white grain.
+ * The grain is a pure function of (seed, f, p, y, x): the bytes do not depend on the launch geometry or the tiling, and T frames in one launch are
+ * the T launches with t0, t0 + 1, ...  (tests/grain_ref.py restates it in numpy, knowing no tiles; the kernel equals it byte for byte.)  A workgroup
+ * owns 256 x 16 luma samples: the white field of the tile plus a halo of 2 is gathered once into LDS, the horizontal pass goes LDS to LDS, the
+ * vertical pass LDS to registers, the chroma tiles follow in the same buffers where chroma != 0.  dst == src (in place) is legal: a thread owns its
+ * 8 x 2 luma samples and their chroma, reads them before it stores, and takes the filter's neighbours from the hash, not from memory.
+ * SN_EINVAL before anything is launched: everything sn_yuv_degrade refuses of fmt, T, H, W, src, dst and gauss; a rectangle sn_egress_yuv_rect
+ * refuses; a null grain; t0 < 0; a knot or chroma that is negative or not finite; a tap that is negative or not finite, w0 <= 0, or
+ * w0^2 + 2 w1^2 + 2 w2^2 further than 1e-3 from 1; byte ranges of src and dst that overlap without being the same. */
+typedef struct sn_yuv_grain_noise { uint32_t seed; int t0; float knots[16]; float chroma; float taps[3]; } sn_yuv_grain_noise;
+int sn_yuv_grain(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* or NULL */, const sn_yuv_grain_noise* grain,
+                 const float* gauss /* device, 65536 */, uint8_t* dst, int T, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,8 @@ the statistics of the same payloads' luma (csrc/sn_yuv_stats.hip), each for one 
                restorer's ``add_noise`` stage: the degraded copy that the comparison with a ground truth needs;
 ``blur_yuv``: sharp payloads -> the means of n consecutive ones on R'G'B', in linear light where gamma tables are given (csrc/sn_blur.hip), for the
                restorer's ``add_blur`` stage: the same for the deblurrers;
+``grain_yuv``: payloads + the 16 knots of a level curve -> the payloads with spatially correlated Gaussian grain added in the code domain, in place if
+               asked (csrc/sn_grain.hip), for the restorer's ``grain`` stage behind the egress;
 ``rowcol_sums_yuv``: uint32 sums of the luma codes of every row and of every column, for the letterbox rule (shiftnet_amd/picture.py);
 ``diff_stats_yuv``: int64 sums of the difference of two sets of payloads, what came in and what was written, for the method-noise report
                (shiftnet_amd/report.py);
@@ -235,6 +237,43 @@ def degrade_yuv(src: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, knots, seed:
     with torch.cuda.device(dev):
         L.check(L.load().sn_yuv_degrade(src.data_ptr(), fmt, noise, gauss.data_ptr(), y.data_ptr(), T, H, W,
                                         torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_degrade")
+    return y
+
+
+def grain_yuv(src: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, knots, taps, chroma: float, seed: int, t0: int, gauss: torch.Tensor, rect=None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src: [T, frame_bytes] uint8 on a HIP device, T payloads of H x W, frames t0 .. t0 + T - 1 of their clip -> [T, frame_bytes] uint8, the same
+    frames with spatially correlated Gaussian grain added in the code domain (include/shiftnet_hip.h: sn_yuv_grain), in one launch.  ``knots``: the 16
+    levels of the grain in 8-bit R'G'B' code units, finite and >= 0 (the sigma of i.i.d. noise on R'G'B' whose luma part the grain equals; converted
+    to luma codes here, grain.luma_knots), knot b at luma code lo + (b + 0.5) (hi - lo) / 16 (noise.knot_codes); the level of a sample is the curve at
+    the luma code read.  ``taps``: (w0, w1, w2) of the separable filter, grain.grain_taps(size).  ``chroma``: the share of the level the chroma planes
+    get, >= 0; 0 leaves them as they came.  ``seed`` (0 .. 2^32 - 1) picks the grain, a hash of the seed, the frame's number, the plane, the row and the
+    column counted from the picture's origin.  ``gauss``: float32 [65536] on the same device, degrade.gauss_table().  ``rect=(x0, y0, w, h)``: only that
+    picture is read and written.  ``out``: a [T, frame_bytes] uint8 tensor to fill -- ``src`` itself for in place, or one that does not overlap it; None
+    is a new tensor (a copy of ``src`` outside a rectangle)."""
+    from .grain import luma_knots
+    T, dev = _payload(src, fmt, H, W)
+    try:
+        kn = luma_knots(knots, fmt)
+    except (TypeError, ValueError):
+        raise ValueError(f"knots: need {L.SN_NLF_BANDS} finite numbers >= 0, got {knots!r}") from None
+    tp = [float(w) for w in taps]
+    if len(tp) != 3 or not all(math.isfinite(w) and w >= 0.0 for w in tp) or not tp[0] > 0.0 or abs(tp[0] ** 2 + 2 * tp[1] ** 2 + 2 * tp[2] ** 2 - 1.0) > 1e-3:
+        raise ValueError(f"taps: need (w0, w1, w2), finite and >= 0, w0 > 0, of unit energy w0^2 + 2 w1^2 + 2 w2^2, got {taps!r}")
+    chroma = float(chroma)
+    if not (math.isfinite(chroma) and chroma >= 0.0):
+        raise ValueError(f"chroma: need a finite share >= 0, got {chroma!r}")
+    seed, t0 = int(seed), int(t0)
+    if not (0 <= seed < 2 ** 32) or not (0 <= t0 <= 2 ** 31 - 1 - T):
+        raise ValueError(f"need 0 <= seed < 2^32 and 0 <= t0 <= 2^31 - 1 - T, got seed {seed!r}, t0 {t0!r}")
+    assert gauss.dtype == torch.float32 and tuple(gauss.shape) == (1 << 16,) and gauss.is_contiguous() and gauss.device == dev
+    r = None if rect is None else _rect(rect, fmt, H, W)
+    y = out if out is not None else (torch.empty_like(src) if r is None else src.clone())
+    assert _payload(y, fmt, H, W) == (T, dev)
+    grain = L.YuvGrainNoise(seed, t0, (C.c_float * L.SN_NLF_BANDS)(*kn), chroma, (C.c_float * 3)(*tp))
+    with torch.cuda.device(dev):
+        L.check(L.load().sn_yuv_grain(src.data_ptr(), fmt, r, grain, gauss.data_ptr(), y.data_ptr(), T, H, W,
+                                      torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_grain")
     return y
 
 

@@ -26,7 +26,7 @@ SYMBOLS = [          # include/shiftnet_hip.h, production ABI
     "sn_ingest_yuv_rect", "sn_egress_yuv_rect", "sn_yuv_noise_hist_rect", "sn_yuv_rowcol_sums", "sn_egress_yuv_dither",
     "sn_yuv_noise_hist_bands", "sn_noise_map_level", "sn_egress_yuv_mix", "sn_yuv_noise_hist_pairs", "sn_yuv_noise_hist_pairs_bands",
     "sn_yuv_diff_stats", "sn_yuv_diff_stats_mv", "sn_yuv_block_motion", "sn_yuv_noise_hist_pairs_mv", "sn_yuv_noise_hist_pairs_bands_mv",
-    "sn_tile_accumulate", "sn_geo_transform", "sn_geo_accumulate", "sn_time_crossfade", "sn_yuv_niqe_sums", "sn_yuv_ssim_sums", "sn_yuv_degrade", "sn_yuv_blur",
+    "sn_tile_accumulate", "sn_geo_transform", "sn_geo_accumulate", "sn_time_crossfade", "sn_yuv_niqe_sums", "sn_yuv_ssim_sums", "sn_yuv_degrade", "sn_yuv_blur", "sn_yuv_grain",
     "sn32_conv2d", "sn32_conv2d_route", "sn32_gsts_gather", "sn32_layernorm", "sn32_gate", "sn32_gate_sum", "sn32_chan_sum", "sn32_scale_residual", "sn32_ingest", "sn32_cab_ca", "sn32_dw_gate", "sn32_conv1x1_gate2", "sn32_gsts_shiftconv", "sn32_conv_csum_tiles",
     "sn_ln_gemm_gate", "sn_lngate_blocks", "sn_grp5_gemm_gate", "sn_grp5_blocks", "sn_gsts_cab2_phase1", "sn_cab1_phase1", "sn_phase1_pool_blocks", "sn_phase1_g1_store_bytes", "sn_p1r_plan", "sn_p1r_strip_begin",
     "sn_cab2_phase2_cab1_phase1", "sn_cab2_phase2_cab1_phase1_supported",
@@ -203,6 +203,12 @@ class YuvBlurWindow(C.Structure):
     _fields_ = [("n", C.c_int), ("c0", C.c_int), ("lo", C.c_int), ("hi", C.c_int)]
 
 
+class YuvGrainNoise(C.Structure):
+    """sn_yuv_grain_noise: the grain of sn_yuv_grain; t0 is the frame number, in its clip, of the launch's first payload, knots the level curve in LUMA
+    code units of the format, chroma the share of it the chroma planes get, taps (w0, w1, w2) of the separable filter (w2, w1, w0, w1, w2)."""
+    _fields_ = [("seed", C.c_uint32), ("t0", C.c_int), ("knots", C.c_float * SN_NLF_BANDS), ("chroma", C.c_float), ("taps", C.c_float * 3)]
+
+
 class ShiftNetLibError(RuntimeError):
     pass
 
@@ -299,6 +305,7 @@ def load() -> C.CDLL:
     lib.sn_yuv_ssim_sums.argtypes = [vp, vp, C.POINTER(YuvFmt), C.POINTER(YuvRect), vp, ci, ci, ci, vp]
     lib.sn_yuv_degrade.argtypes = [vp, C.POINTER(YuvFmt), C.POINTER(YuvDegradeNoise), vp, vp, ci, ci, ci, vp]
     lib.sn_yuv_blur.argtypes = [vp, ci, C.POINTER(YuvFmt), C.POINTER(YuvBlurWindow), vp, vp, vp, ci, ci, ci, vp]
+    lib.sn_yuv_grain.argtypes = [vp, C.POINTER(YuvFmt), C.POINTER(YuvRect), C.POINTER(YuvGrainNoise), vp, vp, ci, ci, ci, vp]
     ll = C.c_longlong
     lib.sn32_conv2d.argtypes = [C.POINTER(Conv32Desc), vp]
     lib.sn32_conv2d_route.argtypes = [C.POINTER(Conv32Desc)]

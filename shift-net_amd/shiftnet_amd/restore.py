@@ -41,6 +41,10 @@ Added noise (``add_noise``, off by default): the other half of that experiment. 
 else degrades them on the device (``sn_yuv_degrade``, shiftnet_amd/degrade.py), the degraded payloads are the input of all the rest, and under
 ``report`` the clean ones are the truth.  Added blur (``add_blur``, off by default) is the same stage for the deblurrers: every frame becomes the mean
 of the frames around it (``sn_yuv_blur``), as the deblur datasets are made.
+
+Grain put back (``grain``, off by default): behind every window's egress, and ahead of the report, a spatially correlated Gaussian field is added to
+the written payloads in place (``sn_yuv_grain``, shiftnet_amd/grain.py; the part ``Grain`` in restore_parts.py), at a level, a curve, or a share of
+what the window was restored with.
 """
 from __future__ import annotations
 
@@ -52,7 +56,7 @@ from typing import Iterable, Iterator, List, Sequence, Tuple
 import numpy as np
 
 from .restore_cli import amount_arg, main, make_parser, picture_arg, sigma_arg, tile_arg  # noqa: F401 -- the command line (restore_cli.py), reached through this module
-from .restore_parts import Ensemble, NoiseLevel, Overlap, Report, Tiles, _Stat
+from .restore_parts import Ensemble, Grain, NoiseLevel, Overlap, Report, Tiles, _Stat
 from .windows import (DEFAULT_TILE_OVERLAP, DITHERS, FUTURE, PAST, PerWindow, _Frames, _SceneFrames, _Thread, amount_form, noise_model_form, pad_multiple,  # noqa: F401
                       padded_size, picture_form, plan_output, plan_scene_windows, plan_windows, quality_form, reflect_index, report_form, report_motion_form, scene_cuts_form,
                       sigma_estimator_form, sigma_form, sigma_motion_form, tile_form, plan_tiles, window_indices, ensemble_form, overlap_weights,
@@ -109,7 +113,9 @@ class _Run:
                          "geo_transform": 0, "geo_accumulate": 0, # ensemble: the members' inputs made, their results added into the canvas
                          "overlap": 0,                            # window_overlap: the cross-fades of shared frames
                          "degrade": 0,                            # add_noise: the chunks of the clean stream degraded
-                         "blur": 0}                               # add_blur: the scene segments of the chunks of the sharp stream blurred
+                         "blur": 0,                               # add_blur: the scene segments of the chunks of the sharp stream blurred
+                         "grain": 0}                              # grain: the windows whose written payloads got grain
+        self.window_grain: List = []                              # grain: the 16 knots (sigma of 8-bit R'G'B') of every window's grain
         self.window_written: List[int] = []                       # window_overlap: the frames every window wrote
         self.seam_rms: List = []                                  # ... and per window None or the rms difference of the two answers on every shared frame
         self.window_tiles: List = []                              # tile: per window, the (y0, x0, th, tw) of its tiles in the order they ran
@@ -532,7 +538,26 @@ class VideoRestorer:
     ``add_blur`` with ``add_noise`` is a ValueError: no network here was trained on both.  ``stats`` then also has ``add_blur``, ``add_blur_gamma``
     and ``blur_launches``.  **The blur is a box over N frames of the stream as it is**: its length in time is N / fps of the input, no frame is
     dropped, and a stream that was not shot at a high frame rate gets ghosting and not motion blur.  **A pure power law, not the sRGB curve; not a
-    lens and not a rolling shutter.**  **N = 1 still runs the conversion round trip** (see ``add_noise``), and **bars are averaged too**."""
+    lens and not a rolling shutter.**  **N = 1 still runs the conversion round trip** (see ``add_noise``), and **bars are averaged too**.
+    grain: None -- nothing is added to what the egress wrote, today's launches, bytes and stats keys; a number G, or 16 numbers (each finite and >= 0)
+    -- behind every window's egress, and ahead of the report, one launch (``sn_yuv_grain``, csrc/sn_grain.hip; main stream) puts grain back on the
+    window's written payloads in place, inside its rectangle under ``picture`` (restore_parts.Grain; shiftnet_amd/grain.py): a Gaussian field times a
+    level, added to the codes and rounded.  The level is in the unit of ``sigma``: the sigma of i.i.d. noise on 8-bit R'G'B' whose LUMA part the grain
+    equals; 16 numbers are a curve (noise.knot_codes) taken at the written luma code.  ``"auto"`` / ``"auto:SHARE"`` (denoise variants; SHARE in
+    [0, 4], default 0.5): SHARE times what the window was restored with -- its sigma as 16 equal knots, or its curve under ``noise_model`` -- whether
+    that was given, listed or estimated.  ``grain_size`` (0 .. 1.2): the standard deviation, in samples, of the 5-tap Gaussian of unit energy the white
+    field is filtered with each way; 0 is white grain.  ``grain_chroma`` (>= 0): the chroma planes get fields of their own at that share of the
+    level (0: chroma stays); ``grain_seed`` (0 .. 2^32 - 1) picks the grain.  The field is a hash of the seed, the plane, the sample's row and column
+    counted from the picture's origin and the dither's frame number, so the bytes are the same with ``pipeline`` on and off, those of restoring every
+    scene as a separate video, and inside a picture those of the cropped stream.  ``report``, ``gt`` and NIQE describe the stream that is written,
+    grain included.  ``grain`` with ``view="removed"`` is a ValueError, and so are ``"auto"`` with a deblur variant and any of the other three without
+    ``grain``.  ``stats`` then also has ``grain`` (the 16 knots, or ``"auto:SHARE"``), ``grain_size``, ``grain_chroma``, ``grain_seed``,
+    ``window_grain`` (the 16 knots of every window, in the unit above) and ``grain_launches``.  **A Gaussian field of a size the user chooses, not a
+    model fitted to the removed noise: no AR fit, no film-grain table for an encoder.**  Its level is a function of the written luma code alone; it is
+    independent from frame to frame; under ``"auto"`` it steps at window boundaries with the estimate; codes are integers, so the grain itself is
+    rounded (variance L^2 + 1/12) and clipped at the legal range; 4:2:0 chroma grain lives at chroma resolution and looks twice the size; the chroma
+    share is a plain factor; ``sigma="auto"`` run on a re-grained stream reads about (1 - rho_1) G for sized grain (grain.lag1; 0.33 G at size 0.8).
+    **Nobody has judged it on real footage.**"""
 
     def __init__(self, net, one_len: int, sigma=None, pipeline: bool = True, scene_cuts=None,
                  cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0),
@@ -541,9 +566,10 @@ class VideoRestorer:
                  report_edge: float = 16.0, sigma_motion=None, report_motion=None, tile=None,
                  tile_overlap: int = DEFAULT_TILE_OVERLAP, ensemble=None, ensemble_time: bool = False, window_overlap: int = 0,
                  report_quality=None, niqe_params=None, add_noise=None, add_noise_seed: int = 0, add_blur=None,
-                 add_blur_gamma: float = 2.2) -> None:
+                 add_blur_gamma: float = 2.2, grain=None, grain_size: float = 0.0, grain_chroma: float = 0.0, grain_seed: int = 0) -> None:
         import torch
         from .degrade import add_blur_form, add_noise_form
+        from .grain import grain_form
         from .lib import YuvFmt
         from .noise import check_clamp
         self.torch = torch
@@ -600,6 +626,13 @@ class VideoRestorer:
         self.add_blur, self.add_blur_gamma = add_blur_form(add_blur, add_blur_gamma)          # None: the code path without any of it; or the taps
         if self.add_blur is not None and self.add_noise is not None:
             raise ValueError("add_blur together with add_noise: no network here was trained on both, pick one")
+        grain_mode, grain_value, *grain_rest = grain_form(grain, grain_size, grain_chroma, grain_seed)      # None: the code path without any of it
+        if grain_mode is not None and self.view is not None:
+            raise ValueError(f"grain together with view={self.view!r}: the view is not the restored stream, there is nothing to put grain back on")
+        if grain_mode == "auto" and not self.V.denoise:
+            raise ValueError(f"grain='auto' is a share of the noise level a window was restored with; {type(net).__name__} of a deblur variant takes none: "
+                             "give grain a number or 16 knots")
+        self.grain_part = Grain(grain_mode, grain_value, *grain_rest) if grain_mode is not None else None
         self._shape = None
         self._reset()
 
@@ -649,6 +682,8 @@ class VideoRestorer:
             self.ensemble_part.prepare(tin, tout, self.hp, self.wp)
         if self.overlap is not None:
             self.overlap.prepare(self.hp, self.wp, self.slots)
+        if self.grain_part is not None:
+            self.grain_part.prepare(torch, dev, ofmt, h, w)
 
     def _size(self, rect) -> Tuple[int, int, int, int]:
         """(h, w, padded h, padded w) of what a window with picture ``rect`` feeds the network."""
@@ -802,6 +837,8 @@ class VideoRestorer:
                 written.copy_(own, non_blocking=True)
             dither = None if self.dither is None else (self.dither_seed, slot.t0)
             egress_yuv(out, self.ofmt, self.h, self.w, dst=written, rect=rect, dither=dither, mix=self.mix, ref=own if self.mix is not None else None)
+            if self.grain_part is not None:                      # in place, ahead of everything that describes the stream written
+                self.grain_part.launch(written, rect, slot.t0, level, run)
             if self.report_part is not None:
                 self.report_part.launch(slot.report, own, written, rect, run, gt=slot.dev_gt[:n] if run.gt is not None else None)
             slot.ev_done.record(main)
@@ -833,7 +870,7 @@ class VideoRestorer:
         stats["picture_launches"] = run.launches["picture"]
         if self.picture_mode == "auto":
             stats["picture_wait_ms"] = list(run.picture_wait_ms)
-        for part in (self.noise, self.report_part, self.tiles, self.ensemble_part, self.overlap):
+        for part in (self.noise, self.report_part, self.tiles, self.ensemble_part, self.overlap, self.grain_part):
             if part is not None:
                 part.finish(run, stats)
         if self.add_noise is not None:

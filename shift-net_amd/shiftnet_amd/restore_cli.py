@@ -70,6 +70,15 @@ def add_blur_arg(word: str) -> int:
         raise argparse.ArgumentTypeError(str(e)) from None
 
 
+def grain_arg(word: str):
+    """--grain: SIGMA or s0,...,s15 -> the 16 knots; auto / auto:SHARE -> ("auto", share)."""
+    from .grain import parse_grain
+    try:
+        return parse_grain(word)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def tile_arg(word: str):
     """--tile: N -> the int (N x N tiles); HxW -> (H, W)."""
     parts = word.lower().split("x")
@@ -192,6 +201,22 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--add_blur_gamma", type=float, default=2.2, metavar="G",
                     help="--add_blur: the power law between R'G'B' and the linear light the frames are averaged in, 1 .. 3; 1 averages the R'G'B' values "
                          "as they are (default 2.2)")
+    ap.add_argument("--grain", type=grain_arg, default=None, metavar="{SIGMA,s0,...,s15,auto,auto:SHARE}",
+                    help="put fine grain back on the stream written, on the device, behind everything else ('denoise, encode, re-grain'): SIGMA is its "
+                         "level in the unit of --sigma, the sigma of i.i.d. noise on 8-bit R'G'B' whose luma part the grain equals; 16 comma-separated "
+                         "values are a curve from black to white taken at the written luma code; 'auto' is SHARE (0 .. 4, default 0.5) times what the "
+                         "window was restored with (the denoise variants).  A Gaussian field of the size --grain_size says, NOT a model fitted to the "
+                         "removed noise: no AR fit, no film-grain table for an encoder; independent from frame to frame; rounded to codes and clipped at "
+                         "the legal range; under auto it steps at window boundaries; --report, --gt and NIQE describe the stream with the grain; nobody "
+                         "has judged it on real footage; not together with --view removed; default: no grain")
+    ap.add_argument("--grain_size", type=float, default=0.0, metavar="S",
+                    help="--grain: the standard deviation, in samples, of the Gaussian the grain is filtered with (5 taps each way, unit energy), "
+                         "0 .. 1.2; 0 is white grain (default); 4:2:0 chroma grain lives at chroma resolution and looks twice the size")
+    ap.add_argument("--grain_chroma", type=float, default=0.0, metavar="C",
+                    help="--grain: the chroma planes get grain of their own at C times the luma's level (a plain factor, >= 0); default 0: chroma stays")
+    ap.add_argument("--grain_seed", type=int, default=0, metavar="N", help="--grain: which grain (0 .. 2^32 - 1); the same seed gives the same bytes")
+    ap.add_argument("--grain_out", default=None, metavar="FILE",
+                    help="--grain: write the curve of every window's grain, 16 levels per line in the format --noise_model FILE reads")
     ap.add_argument("--tile", type=tile_arg, default=None, metavar="{N,HxW}",
                     help="for frames whose activations do not fit the device: run the network on overlapping tiles of H x W samples (N: N x N) of every "
                          "window, one after the other, and blend their results with feather weights on the device; both sides multiples of 4 (8 for "
@@ -262,6 +287,7 @@ def _write_out(path: Optional[str], write, *args) -> None:
 def main(argv: Optional[Sequence[str]] = None) -> int:
     from . import lib as L
     from . import noise, picture as pic, scenes
+    from .grain import grain_form
     from .io_edges import yuv_fmt
     from .restore import VideoRestorer, load_net
     from . import report as rep
@@ -307,6 +333,16 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--add_blur_gamma: a number in 1 .. 3")
     if not (0 <= a.add_noise_seed < 2 ** 32):
         ap.error("--add_noise_seed: an integer in 0 .. 2^32 - 1")
+    if a.grain is None and a.grain_out is not None:               # as above: before any file is opened
+        ap.error("--grain_out needs --grain")
+    try:
+        grain_mode = grain_form(a.grain, a.grain_size, a.grain_chroma, a.grain_seed)[0]
+    except ValueError as e:
+        ap.error(f"--grain / --grain_size / --grain_chroma / --grain_seed: {e}")
+    if grain_mode is not None and view is not None:
+        ap.error(f"--grain together with --view {view}: the view is not the restored stream, there is nothing to put grain back on")
+    if grain_mode == "auto" and "denoise" not in a.variant:
+        ap.error("--grain auto is a share of the noise level the window was restored with: it is for the denoise variants")
     if a.tile is None and a.tile_overlap is not None:             # as above: before any file is opened
         ap.error("--tile_overlap needs --tile")
     tile_overlap = DEFAULT_TILE_OVERLAP if a.tile_overlap is None else a.tile_overlap
@@ -396,7 +432,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                            report=a.report is not None, report_edge=a.report_edge, sigma_motion=None if a.sigma_motion == "none" else a.sigma_motion,
                            report_motion=report_motion, tile=a.tile, tile_overlap=tile_overlap, ensemble=a.ensemble,
                            ensemble_time=a.ensemble_time, window_overlap=a.window_overlap, report_quality=report_quality, niqe_params=a.niqe_params,
-                           add_noise=a.add_noise, add_noise_seed=a.add_noise_seed, add_blur=a.add_blur, add_blur_gamma=a.add_blur_gamma)
+                           add_noise=a.add_noise, add_noise_seed=a.add_noise_seed, add_blur=a.add_blur, add_blur_gamma=a.add_blur_gamma,
+                           grain=a.grain, grain_size=a.grain_size, grain_chroma=a.grain_chroma, grain_seed=a.grain_seed)
         wdeg = None
         if a.add_blur is not None:
             log(f"added blur: the mean of {a.add_blur} frame{'' if a.add_blur == 1 else 's'} (a box of {a.add_blur} frame times at F{hd.fps}), "
@@ -469,6 +506,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             log(f"sigma ({sigma_how}{', ' + a.sigma_estimator if a.sigma_estimator != 'spatial' else ''}{', motion ' + a.sigma_motion if a.sigma_motion != 'none' else ''}{', clamped to [%g, %g]' % tuple(a.sigma_clamp) if sigma_how == 'auto' else ''}): "
                 f"min {min(ws):.2f} / median {float(np.median(ws)):.2f} / max {max(ws):.2f} over {len(ws)} window{'' if len(ws) == 1 else 's'}"
                 f"{'; injected ' + _injected(vr.add_noise) if vr.add_noise is not None else ''}")
+        if vr.grain_part is not None:
+            wg = vr.stats["window_grain"]
+            _write_out(a.grain_out, _text_writer(noise.format_curves), wg, "the grain put back: " + vr.grain_part.how)
+            log(f"grain ({vr.grain_part.how}): size {vr.stats['grain_size']:g}, chroma share {vr.stats['grain_chroma']:g}, seed {vr.stats['grain_seed']}, "
+                f"median level {float(np.median([k for c in wg for k in c])) if wg else 0.0:.2f} in 8-bit R'G'B' codes over {len(wg)} "
+                f"window{'' if len(wg) == 1 else 's'} (a Gaussian field, not a model of the removed noise)")
         if a.report is not None:
             fr = vr.stats["frame_report"]
             _write_out(a.report, _text_writer(rep.format_report), fr, f"edge {a.report_edge:g}", vr.stats.get("frame_report_motion"), vr.stats.get("frame_niqe"),

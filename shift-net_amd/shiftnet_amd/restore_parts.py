@@ -1,6 +1,7 @@
 """The optional features of the video restorer (shiftnet_amd/restore.py), one class each: ``NoiseLevel`` (what a window's noise level is and how it is
 obtained), ``Report`` (the method-noise report), ``Tiles`` (the forward in overlapping tiles), ``Ensemble`` (the forward on mirrored, transposed
-and time-reversed copies) and ``Overlap`` (windows that overlap in time, their shared frames cross-faded).  A part owns everything of its feature -- its state per
+and time-reversed copies), ``Overlap`` (windows that overlap in time, their shared frames cross-faded) and ``Grain`` (grain put back on the payloads
+written).  A part owns everything of its feature -- its state per
 slot on the device and in pinned memory, its launches, its host arithmetic and its keys of ``stats`` -- and writes into the one record of a
 ``restore()`` (``restore._Run``) that ``VideoRestorer`` hands it; ``VideoRestorer`` holds each part or None and calls it by name.  The parts are given
 parsed values (windows.py's ``*_form`` functions) and validate nothing.  ``_Stat`` and ``_Vectors`` are what they share."""
@@ -523,6 +524,58 @@ class Overlap:
         stats["window_written"] = list(run.window_written)
         stats["seam_rms"] = [None if s is None else list(s) for s in run.seam_rms]
         stats["overlap_launches"] = run.launches["overlap"]
+
+
+# ---- grain put back on the stream written ------------------------------------------------------------------------------------------------
+class Grain:
+    """Grain put back (``grain``; off by default): a fully denoised picture looks waxy and bands, and the usual delivery chain is "denoise, encode,
+    re-grain".  Behind every window's egress one launch (``sn_yuv_grain``, csrc/sn_grain.hip; main stream) adds a spatially correlated Gaussian field
+    to the window's written payloads IN PLACE, inside the window's rectangle under ``picture``: luma, and chroma at ``grain_chroma`` times the level.
+    The level is a curve of 16 knots at the written luma code, in the unit of ``sigma`` (the sigma of i.i.d. noise on 8-bit R'G'B' whose luma part
+    the grain equals): the knots given, or under ``"auto"`` the share times what THIS window was restored with -- ``NoiseLevel.level``'s sigma as 16
+    equal knots, or its curve under ``noise_model``.  The field is keyed by the dither's frame number, so the bytes do not depend on how the windows
+    are run.  Everything behind it -- the report, ``gt``, NIQE -- describes the stream with the grain.  **A Gaussian field of a size the user chooses,
+    not a model fitted to the removed noise** (shiftnet_amd/grain.py states the limits).
+
+    ``launch`` runs on the main stream between the egress and the report."""
+
+    def __init__(self, mode: str, value, size: float, chroma: float, seed: int) -> None:
+        from .grain import grain_taps
+        self.mode, self.value, self.size, self.chroma, self.seed = mode, value, size, chroma, seed
+        self.taps = grain_taps(size)
+        if mode == "auto":
+            self.how = "auto:%g" % value
+        else:
+            self.how = "level %g" % value[0] if min(value) == max(value) else "a curve, %g at black .. %g at white" % (value[0], value[-1])
+        self.gauss = None
+
+    def prepare(self, torch, dev, ofmt, h: int, w: int) -> None:
+        """Per stream shape: the format written and, once, the table on the device."""
+        self.ofmt, self.h, self.w = ofmt, h, w
+        if self.gauss is None:
+            from .degrade import gauss_table
+            self.gauss = torch.from_numpy(gauss_table().copy()).to(dev)
+
+    def knots(self, level) -> List[float]:
+        """The 16 knots of the window whose ``NoiseLevel.level`` is ``level``, in 8-bit R'G'B' code units."""
+        if self.mode != "auto":
+            return list(self.value)
+        sigma, curve = level
+        return [self.value * k for k in (curve if curve is not None else [sigma] * NLF_BANDS)]
+
+    def launch(self, written, rect, t0: int, level, run) -> None:
+        """``written``: the window's payloads as the egress left them (current stream: the main stream), grained in place; t0: the dither's frame number."""
+        from .io_edges import grain_yuv
+        knots = self.knots(level)
+        run.window_grain.append(knots)
+        grain_yuv(written, self.ofmt, self.h, self.w, knots, self.taps, self.chroma, self.seed, t0, self.gauss, rect=rect, out=written)
+        run.launches["grain"] += 1
+
+    def finish(self, run, stats) -> None:
+        stats["grain"] = self.how if self.mode == "auto" else list(self.value)
+        stats["grain_size"], stats["grain_chroma"], stats["grain_seed"] = self.size, self.chroma, self.seed
+        stats["window_grain"] = [list(k) for k in run.window_grain]
+        stats["grain_launches"] = run.launches["grain"]
 
 
 def seam_rms(sq, h: int, w: int) -> float:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15, 3.16, 3.17, 3.19, 3.20, 3.21, 3.23, 3.25, 3.29 and 3.33 (run on the MI355X from the repository root).
+"""Measurements behind DESIGN.md 3.11, 3.13, 3.14, 3.15, 3.16, 3.17, 3.19, 3.20, 3.21, 3.23, 3.25, 3.29, 3.33 and 3.38 (run on the MI355X from the repository root).
 
   kernels : time per pixel of sn_ingest_yuv / sn_egress_yuv / sn_yuv_thumb / sn_yuv_noise_hist (4:2:0 8 bit, 720p x 20 frames; the noise
             histogram on the same frames with noise of sigma 10 as well) beside sn_ingest_u8 / sn_egress_u8 on the same
@@ -62,6 +62,10 @@
             and a plain device copy of the same payloads, and sn_yuv_blur at n = 1, 7, 15 with and without gamma tables (16 - 2r outputs from the 16
             sources), interleaved; microseconds per launch and TB/s of each case's own bytes.  --mode forward: the
             stream restored with add_noise=10 and report=True against the same stream degraded beforehand and restored with the clean one as gt.
+  grain   : --mode kernels: sn_yuv_grain on 16 frames of 1280 x 720 at 8-bit 4:2:0, size 0 and 0.8, chroma share 0 and 0.5, out of place and in place,
+            beside a plain device copy of the same payloads and sn_yuv_degrade, interleaved; microseconds per launch and TB/s of each case's own bytes
+            (3.38).  --mode forward: steady-state wall time per 720p window of the pipelined denoiser (as the sigma part, sigma=10.0) without grain and
+            with grain="auto:0.5" at size 0.8 and chroma share 0.5, runs of the two alternating in one process, the first two windows left out.
 Prints one JSON object per part.
 """
 import argparse
@@ -824,6 +828,94 @@ def degrade_forward(a):
                       "runs": a.runs, "same_numbers": seen[True] == seen[False], "fullref_means": {k: round(v, 4) for k, v in seen[True]["mean"].items()}, **res}))
 
 
+def grain_kernels(a):
+    """3.38: sn_yuv_grain on 16 frames of 720p 8-bit 4:2:0 at size 0 and 0.8, chroma share 0 and 0.5, out of place and in place, beside a plain device
+    copy of the same payloads and sn_yuv_degrade (three gathers per pixel), interleaved."""
+    from shiftnet_amd import degrade, grain
+    from shiftnet_amd.io_edges import degrade_yuv, grain_yuv
+    T, H, W = 16, 720, 1280
+    blur, _ = synth.blurred_clip(4, H, W, seed=1)
+    rgb = ingest_u8(torch.from_numpy(np.concatenate([blur] * 4)).cuda(), torch.float32)[0]
+    gauss = torch.from_numpy(degrade.gauss_table().copy()).cuda()
+    knots = [10.0] * 16
+    f = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    clean = egress_yuv(rgb, f, H, W)
+    dst, own = torch.empty_like(clean), clean.clone()
+    fb = f.frame_bytes(H, W)
+    cases = {"copy_payloads": lambda: dst.copy_(clean, non_blocking=True),
+             "degrade_yuv": lambda: degrade_yuv(clean, f, H, W, knots, 1, 0, gauss, out=dst)}
+    nbytes = {"copy_payloads": 2 * T * fb, "degrade_yuv": 2 * T * fb}
+    for size in (0.0, 0.8):
+        taps = grain.grain_taps(size)
+        for chroma in (0.0, 0.5):
+            k = f"grain_yuv_size{size:g}_chroma{chroma:g}"
+            cases[k] = (lambda taps=taps, chroma=chroma: grain_yuv(clean, f, H, W, knots, taps, chroma, 1, 0, gauss, out=dst))
+            nbytes[k] = 2 * T * fb                                                        # every payload read once, written once
+            cases[k + "_in_place"] = (lambda taps=taps, chroma=chroma: grain_yuv(own, f, H, W, knots, taps, chroma, 1, 0, gauss, out=own))
+            nbytes[k + "_in_place"] = 2 * T * (fb if chroma else H * W)                   # share 0 in place: the chroma planes are not touched
+    for fn in cases.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in cases}
+    for _ in range(a.reps):
+        for k, fn in cases.items():                                                  # interleaved: every repetition times every kernel
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.inner):
+                fn()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.inner)
+    res = {k: {"us_per_launch": summary([m * 1e3 for m in v]), "tb_per_s": summary([nbytes[k] / (m * 1e-3) / 1e12 for m in v]), "bytes": nbytes[k]} for k, v in ms.items()}
+    print(json.dumps({"part": "grain", "mode": "kernels", "frames": T, "size": [H, W], "reps": a.reps, "inner": a.inner,
+                      "note": "in place the clip accumulates grain from launch to launch: the codes drift to the legal range's ends, the work per sample stays", **res}))
+
+
+def grain_forward(a):
+    """3.38: steady-state wall and forward time per 720p window of the pipelined denoiser (as the sigma part, sigma=10.0) without grain and with
+    grain="auto:0.5", size 0.8, chroma share 0.5, runs of the two alternating in one process, the first two windows left out."""
+    H, W, one_len, nwin = 720, 1280, 16, a.windows
+    n = one_len * nwin
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    blur, _ = synth.blurred_clip(8, H, W, seed=2)
+    rgb = ingest_u8(torch.from_numpy(blur).cuda(), torch.float32)[0]
+    g = torch.Generator("cuda").manual_seed(1)
+    frames = []
+    for i in range(n):                                                               # fresh noise of sigma 10 on every frame, as the sigma part
+        j = i % 14
+        x = rgb[j if j < 8 else 14 - j][None]
+        frames.append(egress_yuv((x + torch.randn(x.shape, device="cuda", generator=g) * (10.0 / 255)).clamp(0, 1), fmt, H, W)[0].cpu().numpy())
+    net = restore.load_net("denoise_small", "synthetic", "bf16")
+    seen = {}
+
+    def run(on):
+        vr = restore.VideoRestorer(net, one_len, sigma=10.0, pipeline=True, **(dict(grain="auto:0.5", grain_size=0.8, grain_chroma=0.5) if on else {}))
+        stamps = []
+        t0 = time.perf_counter()
+        for i, p in enumerate(vr.restore(iter(frames), fmt, H, W)):
+            if (i + 1) % one_len == 0:
+                stamps.append(time.perf_counter())
+        total = time.perf_counter() - t0
+        seen[on] = vr.stats.get("grain_launches")
+        gaps = [(b - c) * 1e3 for b, c in zip(stamps[1:], stamps[:-1])]
+        return {"total_s": total, "window_wall_ms": gaps[1:], "window_forward_ms": vr.stats["window_forward_ms"][2:]}
+
+    run(False)                                                                       # warm-up: code objects, engine buffers
+    run(True)
+    runs = {"off": [], "grain": []}
+    for _ in range(a.runs):
+        runs["off"].append(run(False))
+        runs["grain"].append(run(True))
+    res = {}
+    for k, rs in runs.items():
+        res[k] = {"window_wall_ms": summary([g for r in rs for g in r["window_wall_ms"]]),
+                  "window_wall_ms_per_run": [round(statistics.median(r["window_wall_ms"]), 2) for r in rs],
+                  "window_forward_ms": summary([g for r in rs for g in r["window_forward_ms"]]), "total_s": [round(r["total_s"], 3) for r in rs]}
+    print(json.dumps({"part": "grain", "mode": "forward", "variant": "denoise_small", "dtype": "bf16", "one_len": one_len, "windows": nwin, "size": [H, W],
+                      "runs": a.runs, "grain_launches": seen[True], **res}))
+
+
 def _tile_word(word):
     return None if word == "full" else restore.tile_arg(word)
 
@@ -1127,7 +1219,7 @@ def picture_part(a):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion", "tiles", "overlap", "quality", "fullref", "degrade"])
+    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion", "tiles", "overlap", "quality", "fullref", "degrade", "grain"])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--inner", type=int, default=200)
     ap.add_argument("--windows", type=int, default=8)
@@ -1139,7 +1231,7 @@ if __name__ == "__main__":
                     "csrc/sn_yuv.hip alone; its sn_ingest_yuv / sn_egress_yuv are timed beside this build's.  nlf and motion parts in kernels mode: a library "
                     "built from another commit's whole csrc; its seven noise-histogram entry points are timed beside this build's, at 8 and 10 bit")
     ap.add_argument("--only_cases", default=None, metavar="WORDS", help="kernels part: time only the cases whose name contains one of these comma-separated words")
-    ap.add_argument("--mode", choices=["forward", "kernels", "quality"], default="forward", help="picture, nlf, report, motion, tiles, overlap, quality and fullref parts: which measurement "
+    ap.add_argument("--mode", choices=["forward", "kernels", "quality"], default="forward", help="picture, nlf, report, motion, tiles, overlap, quality, fullref, degrade and grain parts: which measurement "
                     "(quality: the tiles part alone)")
     ap.add_argument("--picture", choices=["auto", "fixed"], default="auto", help="picture part, forward mode: VideoRestorer(picture='auto') or the rectangle itself")
     ap.add_argument("--tile", action="append", default=None, metavar="{full,N,HxW}", help="tiles part, forward mode: a form to run (repeat for several, which then alternate)")
@@ -1157,4 +1249,5 @@ if __name__ == "__main__":
          "overlap": overlap_kernels if a.mode == "kernels" else overlap_forward,
          "quality": quality_kernels if a.mode == "kernels" else quality_forward,
          "fullref": fullref_kernels if a.mode == "kernels" else fullref_forward,
-         "degrade": degrade_kernels if a.mode == "kernels" else degrade_forward}[a.part](a)
+         "degrade": degrade_kernels if a.mode == "kernels" else degrade_forward,
+         "grain": grain_kernels if a.mode == "kernels" else grain_forward}[a.part](a)
