@@ -1018,6 +1018,36 @@ typedef struct sn_yuv_grain_noise { uint32_t seed; int t0; float knots[16]; floa
 int sn_yuv_grain(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* or NULL */, const sn_yuv_grain_noise* grain,
                  const float* gauss /* device, 65536 */, uint8_t* dst, int T, int H, int W, void* stream);
 
+/* ---- brightness flicker taken out (csrc/sn_deflicker.hip; two new symbols, SN_ABI_VERSION stays 20) ---------------------------------------------------
+ * The two device steps of VideoRestorer(deflicker=R): the luma histogram of every payload, and one tone curve per frame applied to the payloads.  The
+ * rule between them is the host's (shiftnet_amd/deflicker.py; restated by tests/deflicker_ref.py).  No float frame, no colour conversion.
+ *   The rule (host, float64 and exact integers; h_t the histogram of frame t, C_t its running sum, C_t[-1] = 0, the clip [lo, hi), R = 1 .. 15):
+ *        r = min(R, t - lo, hi - 1 - t); for every code c with h_t[c] > 0: a = C_t[c - 1] + C_t[c]; for s = t - r .. t + r: k the smallest code with
+ *        2 C_s[k] >= a and Q_s = ((2k - 1) h_s[k] + a - 2 C_s[k - 1]) / (2 h_s[k]), one division; lutY_t[c] = clamp(floor(median_s Q_s + 0.5), 0, L - 1);
+ *        an absent code takes the value of the nearest present code below it, or of the first present one.
+ *        Chroma: m, m' the mean luma code before and after the table (sum of code * count, one division by N), yo the luma black code,
+ *        k = clamp((m' - yo) / (m - yo), 0.5, 2), k = 1 when m - yo < 1 or lutY is the identity on every present code;
+ *        lutC_t[c] = clamp(floor(co + k (c - co) + 0.5), 0, L - 1), co = 128 * 2^(bits - 8); or the identity.
+ *   L = 2^bits.  A 10-bit payload is 16-bit words and may hold anything: BOTH kernels index with min(code, L - 1) before any use.
+ * sn_yuv_code_hist: src: T payloads of fmt, H x W -> dst[t][c], t < T, c < L, uint32: the number of luma samples of payload t -- of the whole frame
+ *   (rect == NULL) or of the rectangle (sn_egress_yuv_rect's rules) -- whose index min(code, L - 1) is c.  Exact; every frame's bins sum to its sample
+ *   count.  dst is ZEROED BY THE CALL (on the stream, ahead of the kernel), as sn_yuv_noise_hist zeroes its own: it is overwritten, not added to.
+ *   Private histograms in LDS (32 copies at 8 bit, 8 at 10; equal neighbours among a lane's 16 bytes of samples are one add of the run's length, so
+ *   a flat frame costs a sixteenth of the LDS atomics and never two lanes of a group on one word at 8 bit), one global atomic per non-empty bin.
+ * sn_yuv_apply_lut: lut: device, [T][2][L] uint16, 4-byte aligned: per payload the table of the luma plane, then the table of BOTH chroma planes.
+ *   dst[sample] = lut[t][plane ? 1 : 0][min(src[sample], L - 1)] for every sample of the frame, or of the rectangle; the value is stored as the
+ *   format stores a code (8 bit: its low byte; tables hold codes <= L - 1).  Samples outside rect are not touched.  No table is assumed monotone.
+ *   dst == src (in place) is legal: a thread stores only the samples it alone has read.  The tables of a frame go into LDS once per workgroup.
+ * SN_EINVAL before anything is launched, both: a null src / fmt / dst / lut; bits other than 8 and 10, a chroma, matrix or range code out of range;
+ * T outside 1 .. 65535; H or W < 1; at 10 bit an odd address of a payload; dst (histograms) or lut not 4-byte aligned; a rectangle
+ * sn_egress_yuv_rect refuses; more than 2^32 - 1 samples in the picture (histograms); byte ranges of src and dst that overlap without being the same
+ * (tables). */
+int sn_yuv_code_hist(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* or NULL */,
+                     uint32_t* dst /* [T][1 << bits] */, int T, int H, int W, void* stream);
+int sn_yuv_apply_lut(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rect* rect /* or NULL */,
+                     const uint16_t* lut /* device, [T][2][1 << bits]: Y, then Cb and Cr */, uint8_t* dst,
+                     int T, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,9 @@ the statistics of the same payloads' luma (csrc/sn_yuv_stats.hip), each for one 
                restorer's ``add_blur`` stage: the same for the deblurrers;
 ``grain_yuv``: payloads + the 16 knots of a level curve -> the payloads with spatially correlated Gaussian grain added in the code domain, in place if
                asked (csrc/sn_grain.hip), for the restorer's ``grain`` stage behind the egress;
+``code_hist_yuv``: payloads -> the exact histogram of every payload's luma codes, and ``apply_lut_yuv``: payloads + one table for the luma and one for
+               the chroma planes per payload -> the payloads looked up, in place if asked (csrc/sn_deflicker.hip), for the restorer's ``deflicker``
+               stage (the rule between the two is shiftnet_amd/deflicker.py's);
 ``rowcol_sums_yuv``: uint32 sums of the luma codes of every row and of every column, for the letterbox rule (shiftnet_amd/picture.py);
 ``diff_stats_yuv``: int64 sums of the difference of two sets of payloads, what came in and what was written, for the method-noise report
                (shiftnet_amd/report.py);
@@ -274,6 +277,38 @@ def grain_yuv(src: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, knots, taps, c
     with torch.cuda.device(dev):
         L.check(L.load().sn_yuv_grain(src.data_ptr(), fmt, r, grain, gauss.data_ptr(), y.data_ptr(), T, H, W,
                                       torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_grain")
+    return y
+
+
+def code_hist_yuv(src: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, rect=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src: [T, frame_bytes] uint8 on a HIP device, T payloads of H x W -> [T, 2^bits] int32 (the bits of uint32 counts): how many luma samples of
+    every payload have each code, a stored 16-bit word above 2^bits - 1 counted in the last bin (include/shiftnet_hip.h: sn_yuv_code_hist), in one
+    launch.  Exact; every row sums to the sample count.  ``rect=(x0, y0, w, h)``: only that picture is counted.  ``out``: a [T, 2^bits] int32 tensor to
+    fill -- the call zeroes it itself -- instead of a new one."""
+    T, dev = _payload(src, fmt, H, W)
+    r = None if rect is None else _rect(rect, fmt, H, W)
+    codes = 1 << fmt.bits
+    y = out if out is not None else torch.empty((T, codes), dtype=torch.int32, device=dev)
+    assert tuple(y.shape) == (T, codes) and y.dtype == torch.int32 and y.is_contiguous() and y.device == dev
+    with torch.cuda.device(dev):
+        L.check(L.load().sn_yuv_code_hist(src.data_ptr(), fmt, r, y.data_ptr(), T, H, W, torch.cuda.current_stream(dev).cuda_stream), "sn_yuv_code_hist")
+    return y
+
+
+def apply_lut_yuv(src: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lut: torch.Tensor, rect=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src: [T, frame_bytes] uint8 on a HIP device, T payloads of H x W; lut: [T, 2, 2^bits] int16 (the bits of uint16 codes) on the same device, per
+    payload the table of the luma plane and the table of both chroma planes -> [T, frame_bytes] uint8, every code replaced by its table's entry
+    (include/shiftnet_hip.h: sn_yuv_apply_lut), in one launch.  ``rect=(x0, y0, w, h)``: only that picture is read and written.  ``out``: a
+    [T, frame_bytes] uint8 tensor to fill -- ``src`` itself for in place, or one that does not overlap it; None is a new tensor (a copy of ``src``
+    outside a rectangle)."""
+    T, dev = _payload(src, fmt, H, W)
+    assert lut.dtype == torch.int16 and tuple(lut.shape) == (T, 2, 1 << fmt.bits) and lut.is_contiguous() and lut.device == dev
+    r = None if rect is None else _rect(rect, fmt, H, W)
+    y = out if out is not None else (torch.empty_like(src) if r is None else src.clone())
+    assert _payload(y, fmt, H, W) == (T, dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().sn_yuv_apply_lut(src.data_ptr(), fmt, r, lut.data_ptr(), y.data_ptr(), T, H, W, torch.cuda.current_stream(dev).cuda_stream),
+                "sn_yuv_apply_lut")
     return y
 
 

@@ -45,6 +45,9 @@ of the frames around it (``sn_yuv_blur``), as the deblur datasets are made.
 Grain put back (``grain``, off by default): behind every window's egress, and ahead of the report, a spatially correlated Gaussian field is added to
 the written payloads in place (``sn_yuv_grain``, shiftnet_amd/grain.py; the part ``Grain`` in restore_parts.py), at a level, a curve, or a share of
 what the window was restored with.
+Flicker taken out (``deflicker``, off by default): one more stage in front of everything else, in the place of ``add_noise`` and ``add_blur``.  Every
+frame gets one tone curve that matches its luma histogram to the median of its neighbours' (``sn_yuv_code_hist``, the rule of
+shiftnet_amd/deflicker.py on the host, ``sn_yuv_apply_lut``); the deflickered payloads are the input of all the rest.
 """
 from __future__ import annotations
 
@@ -114,7 +117,9 @@ class _Run:
                          "overlap": 0,                            # window_overlap: the cross-fades of shared frames
                          "degrade": 0,                            # add_noise: the chunks of the clean stream degraded
                          "blur": 0,                               # add_blur: the scene segments of the chunks of the sharp stream blurred
-                         "grain": 0}                              # grain: the windows whose written payloads got grain
+                         "grain": 0,                              # grain: the windows whose written payloads got grain
+                         "deflicker": 0}                          # deflicker: the histogram and the table launches of the chunks of the stream
+        self.frame_deflicker: List = []                           # deflicker: (r, mean_in, mean_out, chroma_gain) of every frame, in stream order
         self.window_grain: List = []                              # grain: the 16 knots (sigma of 8-bit R'G'B') of every window's grain
         self.window_written: List[int] = []                       # window_overlap: the frames every window wrote
         self.seam_rms: List = []                                  # ... and per window None or the rms difference of the two answers on every shared frame
@@ -307,6 +312,77 @@ class _DeviceBlur(_DeviceStage):
 
             yield from self._chunk(part, held, launch, tap)
             f0, base, held = f0 + t, keep_from, max(last + 1 - keep_from, 0)
+
+
+class _DeviceDeflicker(_DeviceStage):
+    """``deflicker``: the stream's payloads -> the same payloads under one tone curve per frame, which the rest of restore() takes for its input
+    (sn_yuv_code_hist, the rule of shiftnet_amd/deflicker.py on the host, sn_yuv_apply_lut).  Payloads in, payloads out, the whole frame always.
+
+    Frame f's curve needs the histograms of frames f - R .. f + R, so the stage reads R frames ahead of the chunk it makes, as _DeviceBlur does.  Every
+    frame is uploaded once; the device buffer holds chunk + R payloads and the payloads the next chunk still needs move to its front.  The histograms
+    of the last R frames behind the chunk stay on the host (at most 4 KB per frame come back).  Per chunk: one histogram launch on the new frames,
+    their copy to pinned memory and a wait ON THE STAGE'S OWN STREAM ONLY, the tables of the chunk's frames on the host and their upload, one apply
+    launch.  A closing chunk that reads no new frame has no histogram launch.  Under a LISTED ``scene_cuts`` the window is clamped to the frame's
+    scene (degrade.plan_blur), as it is to the stream's two ends."""
+
+    def __init__(self, torch, dev, fmt, h: int, w: int, chunk: int, R: int, chroma: str, cuts, run: "_Run") -> None:
+        from collections import deque
+        super().__init__(torch, dev, fmt, h, w, chunk, chunk + R, False, run)
+        self.R, self.chroma, self.cuts = R, chroma, cuts
+        codes = 1 << fmt.bits
+        self.pin_hist = torch.empty((chunk + R, codes), dtype=torch.int32).pin_memory()
+        self.dev_hist = torch.empty((chunk + R, codes), dtype=torch.int32, device=dev)
+        self.pin_lut = torch.empty((chunk, 2, codes), dtype=torch.int16).pin_memory()
+        self.dev_lut = torch.empty((chunk, 2, codes), dtype=torch.int16, device=dev)
+        self.halo = torch.empty((R, fmt.frame_bytes(h, w)), dtype=torch.uint8, device=dev)
+        self.hists = deque()                                      # host: the histograms of frames hist0 .. of the stream
+        self.hist0 = 0
+
+    def frames(self, it: Iterable[np.ndarray], tap=None) -> Iterator[np.ndarray]:
+        """The deflickered payloads of ``it``'s, in order; ``tap`` is called with each before it is handed on."""
+        from itertools import islice
+        from .deflicker import tables
+        from .degrade import plan_blur
+        from .io_edges import apply_lut_yuv, code_hist_yuv
+        it, R = iter(it), self.R
+        f0, held, ended = 0, 0, False                             # the next output; dev_in[:held] are frames f0 .. f0 + held - 1 of the stream
+        while True:
+            want = self.chunk + R - held                          # up to R frames past the chunk
+            part = [] if ended else list(islice(it, want))
+            ended = ended or len(part) < want
+            k, S = len(part), held + len(part)
+            last = f0 + S - 1
+            t = min(self.chunk, S)
+            if t < 1:
+                return
+
+            def launch() -> int:
+                if k:
+                    code_hist_yuv(self.dev_in[held:S], self.fmt, self.h, self.w, out=self.dev_hist[:k])
+                    self.pin_hist[:k].copy_(self.dev_hist[:k], non_blocking=True)
+                    self.event.record()
+                    self.event.synchronize()                      # the stage's own stream: never the device, never the stream of the forward
+                    self.hists.extend(self.pin_hist[:k].numpy().view(np.uint32).astype(np.int64))
+                    self.run.launches["deflicker"] += 1
+                H = np.stack(self.hists)                          # frames hist0 .. last
+                lut = self.pin_lut.numpy().view(np.uint16)
+                for a, cnt, lo, hi in plan_blur(f0, t, 2 * R + 1, self.cuts, last, ended):
+                    lo = max(lo, self.hist0)                      # a clip that began further back: R frames behind the chunk are here, no window reaches past them
+                    lut[a - f0:a - f0 + cnt], info = tables(H, lo - self.hist0, hi + 1 - self.hist0, R, self.fmt, self.chroma, a - self.hist0, cnt)
+                    self.run.frame_deflicker.extend(info)
+                self.dev_lut[:t].copy_(self.pin_lut[:t], non_blocking=True)
+                apply_lut_yuv(self.dev_in[:t], self.fmt, self.h, self.w, self.dev_lut[:t], out=self.dev_out[:t])
+                self.run.launches["deflicker"] += 1
+                if S > t:                                         # through a buffer of its own: the two ranges may overlap
+                    self.halo[:S - t].copy_(self.dev_in[t:S])
+                    self.dev_in[:S - t].copy_(self.halo[:S - t])
+                return t
+
+            yield from self._chunk(part, held, launch, tap)
+            f0, held = f0 + t, S - t
+            while self.hist0 < f0 - R:                            # what no later window reaches back to
+                self.hists.popleft()
+                self.hist0 += 1
 
 
 # ---- the restorer -----------------------------------------------------------------------------------------------------------------
@@ -557,7 +633,21 @@ class VideoRestorer:
     independent from frame to frame; under ``"auto"`` it steps at window boundaries with the estimate; codes are integers, so the grain itself is
     rounded (variance L^2 + 1/12) and clipped at the legal range; 4:2:0 chroma grain lives at chroma resolution and looks twice the size; the chroma
     share is a plain factor; ``sigma="auto"`` run on a re-grained stream reads about (1 - rho_1) G for sized grain (grain.lag1; 0.33 G at size 0.8).
-    **Nobody has judged it on real footage.**"""
+    **Nobody has judged it on real footage.**
+    deflicker: None -- the frames given are the input, today's launches, bytes and stats keys; an integer R in 1 .. 15 -- a stage in front of
+    everything else (_DeviceDeflicker; ``sn_yuv_code_hist`` and ``sn_yuv_apply_lut``, csrc/sn_deflicker.hip; a stream of its own) takes brightness
+    flicker out of the payloads, whole frames, no float frame and no colour conversion: every frame gets ONE tone curve that matches its luma
+    histogram to the median of the quantiles of the r = min(R, frames to the clip's start, frames to its end) frames on either side
+    (shiftnet_amd/deflicker.py states the rule and its limits).  The clip is the stream, or the frame's scene under a LISTED ``scene_cuts``; with
+    ``"auto"`` the cuts are found afterwards, on the deflickered stream.  ``deflicker_chroma``: ``"gain"`` scales Cb and Cr about mid-grey by the
+    factor the frame's mean luma above black changed by, clamped to [0.5, 2]; ``"off"`` leaves chroma as it came.  The rest of restore() -- the cut
+    detector, the stager, every statistic, ``amount`` (0 returns the deflickered stream), ``view``, ``report``, ``gt`` -- takes the deflickered
+    payloads for THE input.  ``restore(..., deflickered=callable)`` is called with every one of them, in order.  A static clip leaves byte for byte.
+    ``deflicker`` with ``add_noise`` or ``add_blur`` is a ValueError.  ``stats`` then also has ``deflicker``, ``deflicker_chroma``,
+    ``frame_deflicker`` ((r, mean_in, mean_out, chroma_gain) of every frame) and ``deflicker_launches`` (two per chunk of ``one_len`` frames; one
+    for a closing chunk that reads no new frame).  **One curve per frame: local flicker stays; a real flash is pulled towards its neighbours; luma
+    decides alone; computed on codes, not in linear light; bars are in the histogram; moving content that changes the histogram reads as flicker.
+    Nobody has judged it on real footage.**"""
 
     def __init__(self, net, one_len: int, sigma=None, pipeline: bool = True, scene_cuts=None,
                  cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0),
@@ -566,8 +656,10 @@ class VideoRestorer:
                  report_edge: float = 16.0, sigma_motion=None, report_motion=None, tile=None,
                  tile_overlap: int = DEFAULT_TILE_OVERLAP, ensemble=None, ensemble_time: bool = False, window_overlap: int = 0,
                  report_quality=None, niqe_params=None, add_noise=None, add_noise_seed: int = 0, add_blur=None,
-                 add_blur_gamma: float = 2.2, grain=None, grain_size: float = 0.0, grain_chroma: float = 0.0, grain_seed: int = 0) -> None:
+                 add_blur_gamma: float = 2.2, grain=None, grain_size: float = 0.0, grain_chroma: float = 0.0, grain_seed: int = 0, deflicker=None,
+                 deflicker_chroma: str = "gain") -> None:
         import torch
+        from .deflicker import deflicker_form
         from .degrade import add_blur_form, add_noise_form
         from .grain import grain_form
         from .lib import YuvFmt
@@ -626,6 +718,8 @@ class VideoRestorer:
         self.add_blur, self.add_blur_gamma = add_blur_form(add_blur, add_blur_gamma)          # None: the code path without any of it; or the taps
         if self.add_blur is not None and self.add_noise is not None:
             raise ValueError("add_blur together with add_noise: no network here was trained on both, pick one")
+        # None: the code path without any of it; or R
+        self.deflicker, self.deflicker_chroma = deflicker_form(deflicker, deflicker_chroma, self.add_noise, self.add_blur)
         grain_mode, grain_value, *grain_rest = grain_form(grain, grain_size, grain_chroma, grain_seed)      # None: the code path without any of it
         if grain_mode is not None and self.view is not None:
             raise ValueError(f"grain together with view={self.view!r}: the view is not the restored stream, there is nothing to put grain back on")
@@ -877,6 +971,9 @@ class VideoRestorer:
             stats["add_noise"], stats["add_noise_seed"], stats["degrade_launches"] = list(self.add_noise), self.add_noise_seed, run.launches["degrade"]
         if self.add_blur is not None:
             stats["add_blur"], stats["add_blur_gamma"], stats["blur_launches"] = self.add_blur, self.add_blur_gamma, run.launches["blur"]
+        if self.deflicker is not None:
+            stats["deflicker"], stats["deflicker_chroma"], stats["deflicker_launches"] = self.deflicker, self.deflicker_chroma, run.launches["deflicker"]
+            stats["frame_deflicker"] = [tuple(f) for f in run.frame_deflicker]
         src = run.src
         if self.scene_cuts is not None:                          # its thread has ended: the stream has been read to its end
             stats["cuts"] = list(src.cuts)
@@ -898,11 +995,11 @@ class VideoRestorer:
         return self.run.src
 
     # -- drivers -------------------------------------------------------------------------------------------------------------------
-    def restore(self, frames: Iterable[np.ndarray], fmt, height: int, width: int, gt=None, degraded=None) -> Iterator[np.ndarray]:
+    def restore(self, frames: Iterable[np.ndarray], fmt, height: int, width: int, gt=None, degraded=None, deflickered=None) -> Iterator[np.ndarray]:
         """frames: iterable of uint8 payloads (``fmt.frame_bytes(height, width)`` each) -> the restored payloads, in order.  gt: None, or an iterable of
         ground-truth payloads in the format WRITTEN and of the stream's size, frame i the truth of written frame i (needs ``report=True``; see the class).
         degraded: None, or a callable that is given every payload ``add_noise`` or ``add_blur`` makes of ``frames``, in order, on the thread that reads
-        ``frames`` (needs one of the two)."""
+        ``frames`` (needs one of the two).  deflickered: the same for the payloads ``deflicker`` makes of ``frames`` (needs it)."""
         torch = self.torch
         if gt is not None and self.report_part is None:
             raise ValueError("gt adds PSNR and SSIM against the truth to the report: it needs report=True")
@@ -911,6 +1008,8 @@ class VideoRestorer:
             raise ValueError(f"{option} makes the clean frames the truth of the report: not together with gt")
         if degraded is not None and option is None:
             raise ValueError("degraded is given the payloads add_noise or add_blur makes: it needs one of them")
+        if deflickered is not None and self.deflicker is None:
+            raise ValueError("deflickered is given the payloads deflicker makes: it needs deflicker")
         self._prepare(fmt, height, width)
         if option is not None and self.report_part is not None and self.convert:
             raise ValueError(f"{option} with report and out_format={self.out_format!r}, another format than the input's: the clean frames, the truth of "
@@ -925,6 +1024,10 @@ class VideoRestorer:
                                 self.scene_cuts if self.cuts_mode == "list" else None, self.report_part is not None, self.run)
         if stage is not None and self.report_part is not None:
             gt = stage.truth()
+        if self.deflicker is not None:                           # not a degraded copy: no truth comes of it, and gt stays what the caller gave
+            stage = _DeviceDeflicker(torch, self.dev, fmt, height, width, self.one_len, self.deflicker, self.deflicker_chroma,
+                                     self.scene_cuts if self.cuts_mode == "list" else None, self.run)
+            degraded = deflickered
         if gt is not None:
             self.run.gt = iter(gt)
             for s in self.slots:                                 # once per stream shape, and only for a run that asks

@@ -70,6 +70,15 @@ def add_blur_arg(word: str) -> int:
         raise argparse.ArgumentTypeError(str(e)) from None
 
 
+def deflicker_arg(word: str) -> int:
+    """--deflicker: R, the frames looked at on either side, 1 .. 15."""
+    from .deflicker import parse_deflicker
+    try:
+        return parse_deflicker(word)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def grain_arg(word: str):
     """--grain: SIGMA or s0,...,s15 -> the 16 knots; auto / auto:SHARE -> ("auto", share)."""
     from .grain import parse_grain
@@ -201,6 +210,19 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--add_blur_gamma", type=float, default=2.2, metavar="G",
                     help="--add_blur: the power law between R'G'B' and the linear light the frames are averaged in, 1 .. 3; 1 averages the R'G'B' values "
                          "as they are (default 2.2)")
+    ap.add_argument("--deflicker", type=deflicker_arg, default=None, metavar="R",
+                    help="take brightness flicker out of IN on the device, in front of everything else: every frame gets one tone curve that matches "
+                         "its luma histogram to the median of the histograms of the R frames on either side (1 .. 15), inside its scene under a listed "
+                         "--scene_cuts; payloads to payloads, no colour conversion.  The deflickered stream is THE input of all the rest (--amount 0 "
+                         "returns it, not the file).  One curve per frame: local flicker stays; a real flash is pulled towards its neighbours; moving "
+                         "content that changes the histogram reads as flicker; computed on codes, not in linear light; bars are in the histogram; "
+                         "nobody has judged it on real footage; not together with --add_noise or --add_blur; default: off")
+    ap.add_argument("--deflicker_chroma", choices=["gain", "off"], default="gain",
+                    help="--deflicker: 'gain' scales Cb and Cr about mid-grey by the factor the frame's mean luma above black changed by, clamped to "
+                         "0.5 .. 2 (default); 'off' leaves chroma as it came")
+    ap.add_argument("--deflicker_out", default=None, metavar="FILE",
+                    help="--deflicker: write one line per frame, 'r mean_in mean_out chroma_gain', and a last line with the rms second difference of "
+                         "the frame means before and after")
     ap.add_argument("--grain", type=grain_arg, default=None, metavar="{SIGMA,s0,...,s15,auto,auto:SHARE}",
                     help="put fine grain back on the stream written, on the device, behind everything else ('denoise, encode, re-grain'): SIGMA is its "
                          "level in the unit of --sigma, the sigma of i.i.d. noise on 8-bit R'G'B' whose luma part the grain equals; 16 comma-separated "
@@ -287,6 +309,7 @@ def _write_out(path: Optional[str], write, *args) -> None:
 def main(argv: Optional[Sequence[str]] = None) -> int:
     from . import lib as L
     from . import noise, picture as pic, scenes
+    from .deflicker import deflicker_form, format_deflicker, mean_roughness
     from .grain import grain_form
     from .io_edges import yuv_fmt
     from .restore import VideoRestorer, load_net
@@ -333,6 +356,16 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--add_blur_gamma: a number in 1 .. 3")
     if not (0 <= a.add_noise_seed < 2 ** 32):
         ap.error("--add_noise_seed: an integer in 0 .. 2^32 - 1")
+    if a.deflicker is None and a.deflicker_out is not None:       # as above: before any file is opened
+        ap.error("--deflicker_out needs --deflicker")
+    for flag, other in (("--add_noise", a.add_noise), ("--add_blur", a.add_blur)):
+        if a.deflicker is not None and other is not None:
+            ap.error(f"--deflicker together with {flag}: {flag} makes a degraded copy of a clean stream for an experiment, --deflicker repairs a stream "
+                     "that flickers; pick one")
+    try:
+        deflicker_form(a.deflicker, a.deflicker_chroma)
+    except ValueError as e:
+        ap.error(f"--deflicker / --deflicker_chroma: {e}")
     if a.grain is None and a.grain_out is not None:               # as above: before any file is opened
         ap.error("--grain_out needs --grain")
     try:
@@ -433,8 +466,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                            report_motion=report_motion, tile=a.tile, tile_overlap=tile_overlap, ensemble=a.ensemble,
                            ensemble_time=a.ensemble_time, window_overlap=a.window_overlap, report_quality=report_quality, niqe_params=a.niqe_params,
                            add_noise=a.add_noise, add_noise_seed=a.add_noise_seed, add_blur=a.add_blur, add_blur_gamma=a.add_blur_gamma,
-                           grain=a.grain, grain_size=a.grain_size, grain_chroma=a.grain_chroma, grain_seed=a.grain_seed)
+                           grain=a.grain, grain_size=a.grain_size, grain_chroma=a.grain_chroma, grain_seed=a.grain_seed,
+                           deflicker=a.deflicker, deflicker_chroma=a.deflicker_chroma)
         wdeg = None
+        if a.deflicker is not None:
+            log(f"deflicker: one tone curve per frame from the median of {2 * a.deflicker + 1} luma histograms, chroma {a.deflicker_chroma}; the "
+                f"deflickered stream is the input of all the rest{'; the windows cross the cuts --scene_cuts auto finds' if a.scene_cuts == 'auto' else ''}")
         if a.add_blur is not None:
             log(f"added blur: the mean of {a.add_blur} frame{'' if a.add_blur == 1 else 's'} (a box of {a.add_blur} frame times at F{hd.fps}), "
                 f"{'of the RGB values as they are' if a.add_blur_gamma == 1.0 else 'in linear light through gamma %g' % a.add_blur_gamma}; "
@@ -506,6 +543,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             log(f"sigma ({sigma_how}{', ' + a.sigma_estimator if a.sigma_estimator != 'spatial' else ''}{', motion ' + a.sigma_motion if a.sigma_motion != 'none' else ''}{', clamped to [%g, %g]' % tuple(a.sigma_clamp) if sigma_how == 'auto' else ''}): "
                 f"min {min(ws):.2f} / median {float(np.median(ws)):.2f} / max {max(ws):.2f} over {len(ws)} window{'' if len(ws) == 1 else 's'}"
                 f"{'; injected ' + _injected(vr.add_noise) if vr.add_noise is not None else ''}")
+        if vr.deflicker is not None:
+            fd = vr.stats["frame_deflicker"]
+            _write_out(a.deflicker_out, _text_writer(format_deflicker), fd)
+            log(f"deflicker (R {vr.deflicker}, chroma {vr.deflicker_chroma}): rms second difference of the frame means "
+                f"{mean_roughness([f[1] for f in fd]):.4f} before, {mean_roughness([f[2] for f in fd]):.4f} after, in luma codes over {len(fd)} "
+                f"frame{'' if len(fd) == 1 else 's'} (one curve per frame; unvalidated on real footage)")
         if vr.grain_part is not None:
             wg = vr.stats["window_grain"]
             _write_out(a.grain_out, _text_writer(noise.format_curves), wg, "the grain put back: " + vr.grain_part.how)

@@ -66,6 +66,11 @@
             beside a plain device copy of the same payloads and sn_yuv_degrade, interleaved; microseconds per launch and TB/s of each case's own bytes
             (3.38).  --mode forward: steady-state wall time per 720p window of the pipelined denoiser (as the sigma part, sigma=10.0) without grain and
             with grain="auto:0.5" at size 0.8 and chroma share 0.5, runs of the two alternating in one process, the first two windows left out.
+  deflicker : --mode kernels: sn_yuv_code_hist and sn_yuv_apply_lut on 16 frames of 1280 x 720 at 8-bit and 10-bit 4:2:0, each on a NOISY clip and on a
+            FLAT one (every luma sample one code: the histogram's worst case), beside a plain device copy of the same payloads and sn_yuv_degrade,
+            interleaved; microseconds per launch, TB/s of each case's own bytes and the histogram's flat-to-noisy ratio (3.39).  --mode forward:
+            steady-state wall time per 720p window of the pipelined deblurrer without and with deflicker=3 on a stream whose luma flickers by +-8 %,
+            runs of the two alternating in one process, the first two windows left out.
 Prints one JSON object per part.
 """
 import argparse
@@ -916,6 +921,101 @@ def grain_forward(a):
                       "runs": a.runs, "grain_launches": seen[True], **res}))
 
 
+def deflicker_kernels(a):
+    """3.39: sn_yuv_code_hist and sn_yuv_apply_lut on 16 frames of 720p at 8-bit and 10-bit 4:2:0, on a noisy clip and on a flat one, beside a plain
+    device copy of the same payloads and sn_yuv_degrade, interleaved."""
+    from shiftnet_amd import degrade
+    from shiftnet_amd.io_edges import apply_lut_yuv, code_hist_yuv, degrade_yuv
+    T, H, W = 16, 720, 1280
+    blur, _ = synth.blurred_clip(4, H, W, seed=1)
+    rgb = ingest_u8(torch.from_numpy(np.concatenate([blur] * 4)).cuda(), torch.float32)[0]
+    g = torch.Generator("cuda").manual_seed(1)
+    noisy = (rgb + torch.randn(rgb.shape, device="cuda", generator=g) * (10.0 / 255)).clamp(0, 1)
+    gauss = torch.from_numpy(degrade.gauss_table().copy()).cuda()
+    cases, nbytes = {}, {}
+    for bits in (8, 10):
+        f = yuv_fmt(bits, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+        fb, esz, codes = f.frame_bytes(H, W), 1 if bits == 8 else 2, 1 << bits
+        clips = {"noisy": egress_yuv(noisy, f, H, W), "flat": egress_yuv(torch.full_like(rgb, 0.5), f, H, W)}
+        dst = torch.empty_like(clips["noisy"])
+        hist = torch.empty((T, codes), dtype=torch.int32, device="cuda")
+        lut = torch.from_numpy(np.tile(((np.arange(codes) * 15) // 16 + codes // 32).astype(np.uint16).view(np.int16), (T, 2, 1))).cuda()      # a gain of 15/16 about mid-grey
+        cases[f"copy_payloads_{bits}"] = lambda src=clips["noisy"], dst=dst: dst.copy_(src, non_blocking=True)
+        nbytes[f"copy_payloads_{bits}"] = 2 * T * fb
+        if bits == 8:
+            cases["degrade_yuv_8"] = lambda src=clips["noisy"], dst=dst, f=f: degrade_yuv(src, f, H, W, [10.0] * 16, 1, 0, gauss, out=dst)
+            nbytes["degrade_yuv_8"] = 2 * T * fb
+        for kind, src in clips.items():
+            cases[f"code_hist_{bits}_{kind}"] = lambda src=src, f=f, hist=hist: code_hist_yuv(src, f, H, W, out=hist)
+            nbytes[f"code_hist_{bits}_{kind}"] = T * H * W * esz                             # the luma planes, read once
+            cases[f"apply_lut_{bits}_{kind}"] = lambda src=src, f=f, lut=lut, dst=dst: apply_lut_yuv(src, f, H, W, lut, out=dst)
+            nbytes[f"apply_lut_{bits}_{kind}"] = 2 * T * fb                                  # every payload read once, written once
+    for fn in cases.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in cases}
+    for _ in range(a.reps):
+        for k, fn in cases.items():                                                  # interleaved: every repetition times every kernel
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.inner):
+                fn()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.inner)
+    res = {k: {"us_per_launch": summary([m * 1e3 for m in v]), "tb_per_s": summary([nbytes[k] / (m * 1e-3) / 1e12 for m in v]), "bytes": nbytes[k]} for k, v in ms.items()}
+    ratio = {bits: round(statistics.median(ms[f"code_hist_{bits}_flat"]) / statistics.median(ms[f"code_hist_{bits}_noisy"]), 3) for bits in (8, 10)}
+    print(json.dumps({"part": "deflicker", "mode": "kernels", "frames": T, "size": [H, W], "reps": a.reps, "inner": a.inner,
+                      "note": "code_hist includes the memset of its destination", "hist_flat_to_noisy": ratio, **res}))
+
+
+def deflicker_forward(a):
+    """3.39: steady-state wall and forward time per 720p window of the pipelined deblurrer without and with deflicker=3 on a stream whose luma flickers
+    by +-8 %, runs of the two alternating in one process, the first two windows left out."""
+    H, W, one_len, nwin = 720, 1280, 16, a.windows
+    n = one_len * nwin
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    gains = 1.0 + np.random.default_rng(3).uniform(-0.08, 0.08, n)
+    frames = []
+    for p, gain in zip(_stream(H, W, n, fmt, n_src=8), gains):
+        p = p.copy()
+        p[:H * W] = np.clip(np.floor(16.0 + gain * (p[:H * W].astype(np.float64) - 16.0) + 0.5), 0, 255).astype(np.uint8)
+        frames.append(p)
+    net = restore.load_net("deblur_small", "synthetic", "bf16")
+    seen = {}
+
+    def run(on):
+        vr = restore.VideoRestorer(net, one_len, pipeline=True, **(dict(deflicker=3) if on else {}))
+        stamps = []
+        t0 = time.perf_counter()
+        for i, p in enumerate(vr.restore(iter(frames), fmt, H, W)):
+            if (i + 1) % one_len == 0:
+                stamps.append(time.perf_counter())
+        total = time.perf_counter() - t0
+        seen[on] = vr.stats.get("deflicker_launches")
+        if on:
+            from shiftnet_amd.deflicker import mean_roughness
+            fd = vr.stats["frame_deflicker"]
+            seen["roughness"] = [round(mean_roughness([f[1] for f in fd]), 3), round(mean_roughness([f[2] for f in fd]), 3)]
+        gaps = [(b - c) * 1e3 for b, c in zip(stamps[1:], stamps[:-1])]
+        return {"total_s": total, "window_wall_ms": gaps[1:], "window_forward_ms": vr.stats["window_forward_ms"][2:]}
+
+    run(False)                                                                       # warm-up: code objects, engine buffers
+    run(True)
+    runs = {"off": [], "deflicker": []}
+    for _ in range(a.runs):
+        runs["off"].append(run(False))
+        runs["deflicker"].append(run(True))
+    res = {}
+    for k, rs in runs.items():
+        res[k] = {"window_wall_ms": summary([g for r in rs for g in r["window_wall_ms"]]),
+                  "window_wall_ms_per_run": [round(statistics.median(r["window_wall_ms"]), 2) for r in rs],
+                  "window_forward_ms": summary([g for r in rs for g in r["window_forward_ms"]]), "total_s": [round(r["total_s"], 3) for r in rs]}
+    print(json.dumps({"part": "deflicker", "mode": "forward", "variant": "deblur_small", "dtype": "bf16", "one_len": one_len, "windows": nwin, "size": [H, W],
+                      "runs": a.runs, "deflicker_launches": seen[True], "mean_roughness_before_after": seen["roughness"], **res}))
+
+
 def _tile_word(word):
     return None if word == "full" else restore.tile_arg(word)
 
@@ -1219,7 +1319,7 @@ def picture_part(a):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion", "tiles", "overlap", "quality", "fullref", "degrade", "grain"])
+    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion", "tiles", "overlap", "quality", "fullref", "degrade", "grain", "deflicker"])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--inner", type=int, default=200)
     ap.add_argument("--windows", type=int, default=8)
@@ -1231,7 +1331,7 @@ if __name__ == "__main__":
                     "csrc/sn_yuv.hip alone; its sn_ingest_yuv / sn_egress_yuv are timed beside this build's.  nlf and motion parts in kernels mode: a library "
                     "built from another commit's whole csrc; its seven noise-histogram entry points are timed beside this build's, at 8 and 10 bit")
     ap.add_argument("--only_cases", default=None, metavar="WORDS", help="kernels part: time only the cases whose name contains one of these comma-separated words")
-    ap.add_argument("--mode", choices=["forward", "kernels", "quality"], default="forward", help="picture, nlf, report, motion, tiles, overlap, quality, fullref, degrade and grain parts: which measurement "
+    ap.add_argument("--mode", choices=["forward", "kernels", "quality"], default="forward", help="picture, nlf, report, motion, tiles, overlap, quality, fullref, degrade, grain and deflicker parts: which measurement "
                     "(quality: the tiles part alone)")
     ap.add_argument("--picture", choices=["auto", "fixed"], default="auto", help="picture part, forward mode: VideoRestorer(picture='auto') or the rectangle itself")
     ap.add_argument("--tile", action="append", default=None, metavar="{full,N,HxW}", help="tiles part, forward mode: a form to run (repeat for several, which then alternate)")
@@ -1250,4 +1350,5 @@ if __name__ == "__main__":
          "quality": quality_kernels if a.mode == "kernels" else quality_forward,
          "fullref": fullref_kernels if a.mode == "kernels" else fullref_forward,
          "degrade": degrade_kernels if a.mode == "kernels" else degrade_forward,
-         "grain": grain_kernels if a.mode == "kernels" else grain_forward}[a.part](a)
+         "grain": grain_kernels if a.mode == "kernels" else grain_forward,
+         "deflicker": deflicker_kernels if a.mode == "kernels" else deflicker_forward}[a.part](a)
