@@ -1048,6 +1048,37 @@ int sn_yuv_apply_lut(const uint8_t* src, const sn_yuv_fmt* fmt, const sn_yuv_rec
                      const uint16_t* lut /* device, [T][2][1 << bits]: Y, then Cb and Cr */, uint8_t* dst,
                      int T, int H, int W, void* stream);
 
+/* ---- dirt and blotches taken out (csrc/sn_despot.hip; a new symbol, SN_ABI_VERSION stays 20) -----------------------------------------------------------
+ * The device step of VideoRestorer(despot=T): the spike detection index of the film-restoration literature (Kokaram) along the integer block vectors
+ * of sn_yuv_block_motion, and the repair.  Payloads in, payloads out, the whole frame; no float frame, no colour conversion; fmt->matrix and
+ * fmt->range decide nothing.  Samples are taken as stored (a 16-bit word may hold up to 65535) and all arithmetic is on ints.
+ * src: S payloads of fmt, H x W.  dst[i], i < n, is frame f = f0 + i repaired from the ORIGINAL frames f - 1, f, f + 1 of src, never from a repaired
+ * neighbour.  mv_next, mv_prev: device, [S - 1][nby][nbx][2] int8 (dy, dx) in the layout of sn_yuv_block_motion for the same picture: mv_next[f] is
+ * what it writes for the pair (f, f + 1), mv_prev[f - 1] the vector of frame f's block into frame f - 1 (the matcher run on the time-reversed stack,
+ * flipped back along its first axis).  counts: device, [n][2] uint32, OVERWRITTEN: per frame the core seeds and the luma samples replaced.
+ *   Vectors.  The vector of luma sample (y, x) is that of block (min(y / 16, nby - 1), min(x / 16, nbx - 1)): a last odd row or column, which belongs
+ *        to no block, borrows its neighbour's.  Displaced coordinates are CLAMPED to the plane; with the matcher's vectors the clamp acts on that odd
+ *        row or column only, and with ANY int8 contents it keeps every read inside the payloads.  A picture without a vector block (H < 2 or W < 2)
+ *        has no seeds: dst is a copy and the counts are 0; the vectors are not read.
+ *   Seed.  c = Y_f(y, x), p = Y_{f-1} at the place displaced by the previous vector, n = Y_{f+1} at the place displaced by the next; a = c - p,
+ *        b = c - n; d = min(|a|, |b|) if a and b are both positive or both negative, else 0.  The sample is a SEED iff d > threshold + |p - n|.
+ *   Support.  A seed is a CORE seed iff at least `support` of its eight neighbours are seeds; samples outside the picture are not seeds.
+ *   Grow.  The mask M is the core seeds dilated by the (2 grow + 1) x (2 grow + 1) square, inside the picture.
+ *   Repair.  A luma sample in M becomes (p + n + 1) >> 1; every other luma sample is the source's.  Chroma, chroma == 1 (follow): at 4:4:4 a chroma
+ *        sample is repaired iff its luma sample is in M, with the same vector; at 4:2:0 (either siting) iff any of its up to four luma samples inside
+ *        the picture is in M, with the vector of luma sample (2 cy, 2 cx), both components halved by an arithmetic shift right, the coordinates clamped
+ *        to the chroma plane; the value is (pu + nu + 1) >> 1, likewise for V.  chroma == 0 (off): chroma is the source's.
+ *   One launch: a workgroup owns a 128 x 32 luma tile (8 x 2 vector blocks) and its chroma, makes the seeds of the tile plus a halo of 1 + grow into
+ *   an LDS byte mask, derives the core seeds and M from LDS, and adds its two counts with two global atomics at most.  Integer sums commute.
+ * (tests/despot_ref.py restates the rule with numpy on Python ints; the kernel equals it byte for byte and count for count.)
+ * SN_EINVAL before anything is launched: a null src / fmt / mv_prev / mv_next / dst / counts; bits other than 8 and 10, a chroma, matrix or range
+ * code out of range; S outside 1 .. 65535; H or W < 1; at 10 bit an odd address of src or dst; counts not 4-byte aligned; f0 < 1, n < 1 or
+ * f0 + n > S - 1; threshold < 0, support outside 0 .. 8, grow outside 0 .. 2, chroma other than 0 and 1; byte ranges of dst (n payloads) and src
+ * (S payloads) that overlap, because a frame's neighbours read its original; more than 65535 x 32 rows (a grid dimension). */
+int sn_yuv_despot(const uint8_t* src, const sn_yuv_fmt* fmt, const int8_t* mv_prev, const int8_t* mv_next, uint8_t* dst, uint32_t* counts /* [n][2] */,
+                  int S, int f0, int n, int threshold /* in the format's codes */, int support, int grow, int chroma /* 0 off, 1 follow */,
+                  int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libshiftnet_hip.so")
 SOURCES = ["sn_conv.hip", "sn_conv3p.hip", "sn_cabf.hip", "sn_gsts.hip", "sn_gsts2.hip", "sn_gsts3.hip", "sn_phase1r.hip", "sn_f32.hip", "sn_io.hip", "sn_yuv.hip",
            "sn_yuv_stats.hip", "sn_tile.hip", "sn_geo.hip", "sn_time.hip", "sn_niqe.hip", "sn_ssim.hip", "sn_degrade.hip", "sn_blur.hip", "sn_grain.hip",
-           "sn_deflicker.hip"]
+           "sn_deflicker.hip", "sn_despot.hip"]
 
 
 def needs_build(out: str = OUT) -> bool:

@@ -26,6 +26,8 @@ the statistics of the same payloads' luma (csrc/sn_yuv_stats.hip), each for one 
 ``code_hist_yuv``: payloads -> the exact histogram of every payload's luma codes, and ``apply_lut_yuv``: payloads + one table for the luma and one for
                the chroma planes per payload -> the payloads looked up, in place if asked (csrc/sn_deflicker.hip), for the restorer's ``deflicker``
                stage (the rule between the two is shiftnet_amd/deflicker.py's);
+``despot_vectors``: payloads -> the block vectors of every frame into its previous and into its next frame, and ``despot_yuv``: payloads + those
+               vectors -> the payloads with dirt taken out and two counts per frame (csrc/sn_despot.hip), for the restorer's ``despot`` stage;
 ``rowcol_sums_yuv``: uint32 sums of the luma codes of every row and of every column, for the letterbox rule (shiftnet_amd/picture.py);
 ``diff_stats_yuv``: int64 sums of the difference of two sets of payloads, what came in and what was written, for the method-noise report
                (shiftnet_amd/report.py);
@@ -310,6 +312,45 @@ def apply_lut_yuv(src: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, lut: torch
         L.check(L.load().sn_yuv_apply_lut(src.data_ptr(), fmt, r, lut.data_ptr(), y.data_ptr(), T, H, W, torch.cuda.current_stream(dev).cuda_stream),
                 "sn_yuv_apply_lut")
     return y
+
+
+def despot_vectors(src: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """src: [S, frame_bytes] uint8 on a HIP device, S >= 2 payloads of H x W -> (mv_prev, mv_next), int8 [S - 1, nby, nbx, 2] each, what
+    ``despot_yuv`` takes: mv_next[f] is the vector of every 16 x 16 luma block of frame f into frame f + 1 (``block_motion_yuv`` on the stack), and
+    mv_prev[f - 1] that of frame f into frame f - 1 (``block_motion_yuv`` on the time-reversed stack, flipped back along its first axis).  Two
+    launches; none for a picture without a vector block."""
+    mv_next, _ = block_motion_yuv(src, fmt, H, W)
+    mv_rev, _ = block_motion_yuv(src.flip(0), fmt, H, W)
+    return mv_rev.flip(0).contiguous(), mv_next
+
+
+def despot_yuv(src: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, mv_prev: torch.Tensor, mv_next: torch.Tensor, f0: int, n: int, threshold: int,
+               support: int, grow: int, chroma: str, out: Optional[torch.Tensor] = None,
+               out_counts: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """src: [S, frame_bytes] uint8 on a HIP device, S payloads of H x W; mv_prev, mv_next: int8 [S - 1, nby, nbx, 2] on the same device, as
+    ``despot_vectors`` makes them (ANY int8 contents are memory-safe) -> ([n, frame_bytes] uint8: frames f0 .. f0 + n - 1 with dirt taken out, each
+    repaired from the ORIGINAL frames f - 1, f, f + 1 of ``src``; [n, 2] int32, the bits of uint32 counts: the core seeds and the luma samples
+    replaced of each), in one launch (include/shiftnet_hip.h: sn_yuv_despot states the rule).  1 <= f0 and f0 + n <= S - 1.  ``threshold``: T in
+    8-BIT codes, multiplied here by 2^(bits - 8); ``support``: K in 0 .. 8; ``grow``: G in 0 .. 2; ``chroma``: "follow" or "off".  ``out``: a
+    [n, frame_bytes] uint8 tensor to fill that does not overlap ``src``; ``out_counts``: a [n, 2] int32 tensor to overwrite."""
+    from .noise import motion_grid
+    S, dev = _payload(src, fmt, H, W)
+    nby, nbx = motion_grid(H, W)
+    for mv in (mv_prev, mv_next):
+        assert mv.dtype == torch.int8 and tuple(mv.shape) == (S - 1, nby, nbx, 2) and mv.is_contiguous() and mv.device == dev
+    if chroma not in ("follow", "off"):
+        raise ValueError(f"sn_yuv_despot: chroma is 'follow' or 'off', got {chroma!r}")
+    y = out if out is not None else torch.empty((n, src.shape[1]), dtype=torch.uint8, device=dev)
+    assert _payload(y, fmt, H, W) == (n, dev)
+    c = out_counts if out_counts is not None else torch.empty((n, 2), dtype=torch.int32, device=dev)
+    assert tuple(c.shape) == (n, 2) and c.dtype == torch.int32 and c.is_contiguous() and c.device == dev
+    # an empty grid has no storage to point at: the entry point reads no vector then, and wants no null pointer
+    mp, mn = (mv.data_ptr() if mv.numel() else src.data_ptr() for mv in (mv_prev, mv_next))
+    with torch.cuda.device(dev):
+        L.check(L.load().sn_yuv_despot(src.data_ptr(), fmt, mp, mn, y.data_ptr(), c.data_ptr(), S, int(f0), int(n), int(threshold) << (fmt.bits - 8),
+                                       int(support), int(grow), 1 if chroma == "follow" else 0, H, W, torch.cuda.current_stream(dev).cuda_stream),
+                "sn_yuv_despot")
+    return y, c
 
 
 def blur_yuv(src: torch.Tensor, fmt: "L.YuvFmt", H: int, W: int, n: int, c0: int, lo: int, hi: int, tables, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -27,7 +27,7 @@ SYMBOLS = [          # include/shiftnet_hip.h, production ABI
     "sn_yuv_noise_hist_bands", "sn_noise_map_level", "sn_egress_yuv_mix", "sn_yuv_noise_hist_pairs", "sn_yuv_noise_hist_pairs_bands",
     "sn_yuv_diff_stats", "sn_yuv_diff_stats_mv", "sn_yuv_block_motion", "sn_yuv_noise_hist_pairs_mv", "sn_yuv_noise_hist_pairs_bands_mv",
     "sn_tile_accumulate", "sn_geo_transform", "sn_geo_accumulate", "sn_time_crossfade", "sn_yuv_niqe_sums", "sn_yuv_ssim_sums", "sn_yuv_degrade", "sn_yuv_blur", "sn_yuv_grain",
-    "sn_yuv_code_hist", "sn_yuv_apply_lut",
+    "sn_yuv_code_hist", "sn_yuv_apply_lut", "sn_yuv_despot",
     "sn32_conv2d", "sn32_conv2d_route", "sn32_gsts_gather", "sn32_layernorm", "sn32_gate", "sn32_gate_sum", "sn32_chan_sum", "sn32_scale_residual", "sn32_ingest", "sn32_cab_ca", "sn32_dw_gate", "sn32_conv1x1_gate2", "sn32_gsts_shiftconv", "sn32_conv_csum_tiles",
     "sn_ln_gemm_gate", "sn_lngate_blocks", "sn_grp5_gemm_gate", "sn_grp5_blocks", "sn_gsts_cab2_phase1", "sn_cab1_phase1", "sn_phase1_pool_blocks", "sn_phase1_g1_store_bytes", "sn_p1r_plan", "sn_p1r_strip_begin",
     "sn_cab2_phase2_cab1_phase1", "sn_cab2_phase2_cab1_phase1_supported",
@@ -309,6 +309,7 @@ def load() -> C.CDLL:
     lib.sn_yuv_grain.argtypes = [vp, C.POINTER(YuvFmt), C.POINTER(YuvRect), C.POINTER(YuvGrainNoise), vp, vp, ci, ci, ci, vp]
     lib.sn_yuv_code_hist.argtypes = [vp, C.POINTER(YuvFmt), C.POINTER(YuvRect), vp, ci, ci, ci, vp]
     lib.sn_yuv_apply_lut.argtypes = [vp, C.POINTER(YuvFmt), C.POINTER(YuvRect), vp, vp, ci, ci, ci, vp]
+    lib.sn_yuv_despot.argtypes = [vp, C.POINTER(YuvFmt), vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]
     ll = C.c_longlong
     lib.sn32_conv2d.argtypes = [C.POINTER(Conv32Desc), vp]
     lib.sn32_conv2d_route.argtypes = [C.POINTER(Conv32Desc)]

@@ -48,6 +48,9 @@ what the window was restored with.
 Flicker taken out (``deflicker``, off by default): one more stage in front of everything else, in the place of ``add_noise`` and ``add_blur``.  Every
 frame gets one tone curve that matches its luma histogram to the median of its neighbours' (``sn_yuv_code_hist``, the rule of
 shiftnet_amd/deflicker.py on the host, ``sn_yuv_apply_lut``); the deflickered payloads are the input of all the rest.
+Dirt taken out (``despot``, off by default): a stage in the same place, behind ``deflicker`` when both are on.  Every frame is repaired from its two
+ORIGINAL neighbours along block vectors (``sn_yuv_block_motion`` both ways in time, ``sn_yuv_despot``; shiftnet_amd/despot.py states the rule); the
+despotted payloads are the input of all the rest.
 """
 from __future__ import annotations
 
@@ -118,7 +121,9 @@ class _Run:
                          "degrade": 0,                            # add_noise: the chunks of the clean stream degraded
                          "blur": 0,                               # add_blur: the scene segments of the chunks of the sharp stream blurred
                          "grain": 0,                              # grain: the windows whose written payloads got grain
-                         "deflicker": 0}                          # deflicker: the histogram and the table launches of the chunks of the stream
+                         "deflicker": 0,                          # deflicker: the histogram and the table launches of the chunks of the stream
+                         "despot": 0}                             # despot: the motion launches of the chunks (two each) and the repair launches
+        self.frame_despot: List = []                              # despot: (seeds, replaced, share, kept) of every frame, in stream order
         self.frame_deflicker: List = []                           # deflicker: (r, mean_in, mean_out, chroma_gain) of every frame, in stream order
         self.window_grain: List = []                              # grain: the 16 knots (sigma of 8-bit R'G'B') of every window's grain
         self.window_written: List[int] = []                       # window_overlap: the frames every window wrote
@@ -385,6 +390,92 @@ class _DeviceDeflicker(_DeviceStage):
                 self.hist0 += 1
 
 
+class _DeviceDespot(_DeviceStage):
+    """``despot``: the stream's payloads -> the same payloads with dirt and blotches taken out, which the rest of restore() takes for its input
+    (sn_yuv_block_motion both ways in time, sn_yuv_despot; shiftnet_amd/despot.py states the rule).  Payloads in, payloads out, the whole frame always.
+
+    Frame f is repaired from the ORIGINAL frames f - 1, f and f + 1, so the stage reads one frame ahead of the chunk it makes, as _DeviceBlur does at
+    three taps: every frame is uploaded once, the device buffer holds chunk + 2 payloads and the payloads the next chunk reaches back to move to its
+    front.  Per chunk, on the stage's own stream: the two motion launches on the payloads held (``despot_vectors``), then one ``sn_yuv_despot`` launch
+    per scene segment of the chunk (degrade.plan_blur): under a LISTED ``scene_cuts`` the frame's neighbours are those of its scene, as they are the
+    stream's.  A clip's first and last frame have one neighbour only: a plain device copy and the record (0, 0, 0.0, False); a segment with nothing
+    but such frames launches nothing, and a chunk with nothing but such segments has no motion launches either.  The counts come back with the
+    payloads, behind the stage's own event; the guard -- a frame whose replaced share exceeds ``max_share`` is handed on as the ORIGINAL -- is a
+    substitution of host bytes the stage still holds, not a second launch."""
+
+    def __init__(self, torch, dev, fmt, h: int, w: int, chunk: int, T: int, K: int, G: int, chroma: str, max_share: float, cuts, run: "_Run") -> None:
+        from collections import deque
+        super().__init__(torch, dev, fmt, h, w, chunk, chunk + 2, False, run)
+        self.T, self.K, self.G, self.chroma, self.max_share, self.cuts = T, K, G, chroma, max_share, cuts
+        self.halo = torch.empty((2, fmt.frame_bytes(h, w)), dtype=torch.uint8, device=dev)
+        self.pin_counts = torch.empty((chunk, 2), dtype=torch.int32).pin_memory()
+        self.dev_counts = torch.empty((chunk, 2), dtype=torch.int32, device=dev)
+        self.host = deque()                                       # host: the source payloads of frames host0 .. of the stream, for the guard
+        self.host0 = 0
+
+    def frames(self, it: Iterable[np.ndarray], tap=None) -> Iterator[np.ndarray]:
+        """The payloads of ``it`` with dirt taken out, in order; ``tap`` is called with each before it is handed on."""
+        from itertools import islice
+        from .degrade import plan_blur
+        from .despot import END_RECORD, frame_record
+        from .io_edges import despot_vectors, despot_yuv
+        from .noise import motion_grid
+        it = iter(it)
+        motion = 2 if all(motion_grid(self.h, self.w)) else 0     # a picture without a vector block: despot_vectors launches nothing
+        f0, base, held, ended = 0, 0, 0, False                    # the next output; dev_in[:held] are frames base .. base + held - 1 of the stream
+        while True:
+            want = f0 + self.chunk + 1 - (base + held)            # one frame past the chunk
+            part = [] if ended else list(islice(it, want))
+            ended = ended or len(part) < want
+            S = held + len(part)
+            last = base + S - 1
+            t = min(self.chunk, last - f0 + 1)
+            if t < 1:
+                return
+            self.host.extend(np.array(f, copy=True) for f in part)
+            keep_from = max(base, f0 + t - 1)                     # what the next chunk's first frame reaches back to
+            inner = [False] * t                                   # the chunk's frames with two neighbours in their clip
+
+            def launch() -> int:
+                vectors = None
+                for a, cnt, lo, hi in plan_blur(f0, t, 3, self.cuts, last, ended):
+                    ia, ib = max(a, lo + 1), min(a + cnt - 1, hi - 1)      # hi is the clip's last frame, or a frame past the chunk
+                    for f in range(a, a + cnt):
+                        if not ia <= f <= ib:
+                            self.dev_out[f - f0].copy_(self.dev_in[f - base])
+                    if ia > ib:
+                        continue
+                    if vectors is None:
+                        vectors = despot_vectors(self.dev_in[:S], self.fmt, self.h, self.w)
+                        self.run.launches["despot"] += motion
+                    despot_yuv(self.dev_in[:S], self.fmt, self.h, self.w, vectors[0], vectors[1], ia - base, ib - ia + 1, self.T, self.K, self.G,
+                               self.chroma, out=self.dev_out[ia - f0:ib + 1 - f0], out_counts=self.dev_counts[ia - f0:ib + 1 - f0])
+                    self.run.launches["despot"] += 1
+                    inner[ia - f0:ib + 1 - f0] = [True] * (ib - ia + 1)
+                self.pin_counts[:t].copy_(self.dev_counts[:t], non_blocking=True)
+                k = last + 1 - keep_from
+                if k > 0 and keep_from > base:                    # through a buffer of its own: the two ranges may overlap
+                    self.halo[:k].copy_(self.dev_in[keep_from - base:S])
+                    self.dev_in[:k].copy_(self.halo[:k])
+                return t
+
+            counts = None
+            for i, d in enumerate(self._chunk(part, held, launch, None)):
+                if counts is None:                                # behind the stage's event: the counts have come back with the payloads
+                    counts = self.pin_counts[:t].numpy().view(np.uint32).copy()
+                rec = frame_record(counts[i, 0], counts[i, 1], self.h * self.w, self.max_share) if inner[i] else END_RECORD
+                if rec[3]:                                        # the guard: the original, from the host
+                    d = self.host[f0 + i - self.host0].copy()
+                self.run.frame_despot.append(rec)
+                if tap is not None:
+                    tap(d)
+                yield d
+            f0, base, held = f0 + t, keep_from, max(last + 1 - keep_from, 0)
+            while self.host0 < f0:                                # the guard never reaches back
+                self.host.popleft()
+                self.host0 += 1
+
+
 # ---- the restorer -----------------------------------------------------------------------------------------------------------------
 class VideoRestorer:
     """``VideoRestorer(net, one_len, sigma=None).restore(frames, fmt, height, width)`` -> iterator of restored payloads, one per input frame.
@@ -647,7 +738,28 @@ class VideoRestorer:
     ``frame_deflicker`` ((r, mean_in, mean_out, chroma_gain) of every frame) and ``deflicker_launches`` (two per chunk of ``one_len`` frames; one
     for a closing chunk that reads no new frame).  **One curve per frame: local flicker stays; a real flash is pulled towards its neighbours; luma
     decides alone; computed on codes, not in linear light; bars are in the histogram; moving content that changes the histogram reads as flicker.
-    Nobody has judged it on real footage.**"""
+    Nobody has judged it on real footage.**
+    despot: None -- the frames given are the input, today's launches, bytes and stats keys; an integer T in 1 .. 255, the threshold in 8-bit codes --
+    a stage in front of everything else (_DeviceDespot; ``sn_yuv_block_motion`` on the stack and on the time-reversed stack, ``sn_yuv_despot``,
+    csrc/sn_despot.hip; a stream of its own) takes dirt, dust, blotches and dropouts out of the payloads -- small regions that are wrong in exactly
+    ONE frame -- whole frames, no float frame and no colour conversion.  Frame f is repaired from the ORIGINAL frames f - 1, f, f + 1 only, never from
+    a repaired neighbour, so the result depends on neither ``one_len``, the windows nor ``pipeline``: a luma sample is a seed iff it differs from both
+    motion-compensated neighbours in the same direction by more than T + |p - n|; a seed with at least ``despot_support`` (K, 0 .. 8, default 2)
+    seeds among its eight neighbours is a core seed; the core seeds grown by ``despot_grow`` (G, 0 .. 2, default 1) samples are replaced by
+    (p + n + 1) >> 1; ``despot_chroma``: ``"follow"`` repairs chroma where its luma is repaired, ``"off"`` leaves it (shiftnet_amd/despot.py states
+    the rule and its limits).  The clip is the stream, or the frame's scene under a LISTED ``scene_cuts``; a clip's first and last frame leave as they
+    came; with ``"auto"`` the cuts are found afterwards, on the despotted stream.  A frame of which more than ``despot_max_share`` (default 0.05)
+    would be replaced -- a flash, a frame under uncorrected flicker, a cut the motion search could not follow -- is handed on as it came and marked
+    kept.  **With ``deflicker`` the stage runs BEHIND it**, each on a stream of its own: uncorrected flicker makes whole frames read as spikes, so
+    flicker goes first.  The rest of restore() -- the cut detector, the stager, every statistic, ``amount``, ``view``, ``report``, ``gt`` -- takes
+    the despotted payloads for THE input.  ``restore(..., despotted=callable)`` is called with every one of them, in order.  A static clip leaves
+    byte for byte.  ``despot`` with ``add_noise`` or ``add_blur`` is a ValueError.  ``stats`` then also has ``despot``, ``despot_support``,
+    ``despot_grow``, ``despot_chroma``, ``despot_max_share``, ``frame_despot`` ((seeds, replaced, share, kept) of every frame) and
+    ``despot_launches`` (per chunk of ``one_len`` frames the two motion launches and one repair launch per scene segment that has a frame with two
+    neighbours).  **One threshold in codes, not scaled to the footage's noise; integer-pel vectors within +-7 px per 16 x 16 block, chosen on a block
+    that contains the dirt; dirt that persists for two frames, line scratches and anything else that stays are not found; small fast objects that
+    are in one place for one frame ARE taken for dirt; the repair is the mean of two neighbours, which is soft; luma alone decides.  Nobody has
+    judged it on real footage.**"""
 
     def __init__(self, net, one_len: int, sigma=None, pipeline: bool = True, scene_cuts=None,
                  cut_threshold: float = 4.0, cut_ratio: float = 2.5, sigma_clamp: Sequence[float] = (0.0, 50.0),
@@ -657,9 +769,11 @@ class VideoRestorer:
                  tile_overlap: int = DEFAULT_TILE_OVERLAP, ensemble=None, ensemble_time: bool = False, window_overlap: int = 0,
                  report_quality=None, niqe_params=None, add_noise=None, add_noise_seed: int = 0, add_blur=None,
                  add_blur_gamma: float = 2.2, grain=None, grain_size: float = 0.0, grain_chroma: float = 0.0, grain_seed: int = 0, deflicker=None,
-                 deflicker_chroma: str = "gain") -> None:
+                 deflicker_chroma: str = "gain", despot=None, despot_support: int = 2, despot_grow: int = 1, despot_chroma: str = "follow",
+                 despot_max_share: float = 0.05) -> None:
         import torch
         from .deflicker import deflicker_form
+        from .despot import despot_form
         from .degrade import add_blur_form, add_noise_form
         from .grain import grain_form
         from .lib import YuvFmt
@@ -720,6 +834,9 @@ class VideoRestorer:
             raise ValueError("add_blur together with add_noise: no network here was trained on both, pick one")
         # None: the code path without any of it; or R
         self.deflicker, self.deflicker_chroma = deflicker_form(deflicker, deflicker_chroma, self.add_noise, self.add_blur)
+        # None: the code path without any of it; or T
+        self.despot, self.despot_support, self.despot_grow, self.despot_chroma, self.despot_max_share = despot_form(
+            despot, despot_support, despot_grow, despot_chroma, despot_max_share, self.add_noise, self.add_blur)
         grain_mode, grain_value, *grain_rest = grain_form(grain, grain_size, grain_chroma, grain_seed)      # None: the code path without any of it
         if grain_mode is not None and self.view is not None:
             raise ValueError(f"grain together with view={self.view!r}: the view is not the restored stream, there is nothing to put grain back on")
@@ -974,6 +1091,10 @@ class VideoRestorer:
         if self.deflicker is not None:
             stats["deflicker"], stats["deflicker_chroma"], stats["deflicker_launches"] = self.deflicker, self.deflicker_chroma, run.launches["deflicker"]
             stats["frame_deflicker"] = [tuple(f) for f in run.frame_deflicker]
+        if self.despot is not None:
+            stats["despot"], stats["despot_support"], stats["despot_grow"] = self.despot, self.despot_support, self.despot_grow
+            stats["despot_chroma"], stats["despot_max_share"], stats["despot_launches"] = self.despot_chroma, self.despot_max_share, run.launches["despot"]
+            stats["frame_despot"] = [tuple(f) for f in run.frame_despot]
         src = run.src
         if self.scene_cuts is not None:                          # its thread has ended: the stream has been read to its end
             stats["cuts"] = list(src.cuts)
@@ -995,11 +1116,13 @@ class VideoRestorer:
         return self.run.src
 
     # -- drivers -------------------------------------------------------------------------------------------------------------------
-    def restore(self, frames: Iterable[np.ndarray], fmt, height: int, width: int, gt=None, degraded=None, deflickered=None) -> Iterator[np.ndarray]:
+    def restore(self, frames: Iterable[np.ndarray], fmt, height: int, width: int, gt=None, degraded=None, deflickered=None,
+                despotted=None) -> Iterator[np.ndarray]:
         """frames: iterable of uint8 payloads (``fmt.frame_bytes(height, width)`` each) -> the restored payloads, in order.  gt: None, or an iterable of
         ground-truth payloads in the format WRITTEN and of the stream's size, frame i the truth of written frame i (needs ``report=True``; see the class).
         degraded: None, or a callable that is given every payload ``add_noise`` or ``add_blur`` makes of ``frames``, in order, on the thread that reads
-        ``frames`` (needs one of the two).  deflickered: the same for the payloads ``deflicker`` makes of ``frames`` (needs it)."""
+        ``frames`` (needs one of the two).  deflickered: the same for the payloads ``deflicker`` makes of ``frames`` (needs it).  despotted: the same for
+        the payloads ``despot`` hands on (needs it): with ``deflicker`` they are made of the deflickered ones."""
         torch = self.torch
         if gt is not None and self.report_part is None:
             raise ValueError("gt adds PSNR and SSIM against the truth to the report: it needs report=True")
@@ -1010,6 +1133,8 @@ class VideoRestorer:
             raise ValueError("degraded is given the payloads add_noise or add_blur makes: it needs one of them")
         if deflickered is not None and self.deflicker is None:
             raise ValueError("deflickered is given the payloads deflicker makes: it needs deflicker")
+        if despotted is not None and self.despot is None:
+            raise ValueError("despotted is given the payloads despot hands on: it needs despot")
         self._prepare(fmt, height, width)
         if option is not None and self.report_part is not None and self.convert:
             raise ValueError(f"{option} with report and out_format={self.out_format!r}, another format than the input's: the clean frames, the truth of "
@@ -1028,6 +1153,10 @@ class VideoRestorer:
             stage = _DeviceDeflicker(torch, self.dev, fmt, height, width, self.one_len, self.deflicker, self.deflicker_chroma,
                                      self.scene_cuts if self.cuts_mode == "list" else None, self.run)
             degraded = deflickered
+        despot_stage = None
+        if self.despot is not None:                              # behind deflicker, each on a stream of its own: flicker reads as spikes, so it goes first
+            despot_stage = _DeviceDespot(torch, self.dev, fmt, height, width, self.one_len, self.despot, self.despot_support, self.despot_grow,
+                                         self.despot_chroma, self.despot_max_share, self.scene_cuts if self.cuts_mode == "list" else None, self.run)
         if gt is not None:
             self.run.gt = iter(gt)
             for s in self.slots:                                 # once per stream shape, and only for a run that asks
@@ -1053,7 +1182,8 @@ class VideoRestorer:
         def windows():
             """(the slot, the frames, their first restored frame's number in its clip, the frames shared with the predecessor, the frames written) of
             every window, in the order they are restored."""
-            src = self._source(checked(frames) if stage is None else stage.frames(checked(frames), degraded))
+            feed = checked(frames) if stage is None else stage.frames(checked(frames), degraded)
+            src = self._source(feed if despot_stage is None else despot_stage.frames(feed, despotted))
             for k, win, clip_lo in src.windows(self.one_len, self.window_overlap):
                 yield self.slots[k % 2], win, clip_lo, src.head, src.written
 

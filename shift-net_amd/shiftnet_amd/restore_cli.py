@@ -79,6 +79,15 @@ def deflicker_arg(word: str) -> int:
         raise argparse.ArgumentTypeError(str(e)) from None
 
 
+def despot_arg(word: str) -> int:
+    """--despot: T, the threshold in 8-bit codes, 1 .. 255."""
+    from .despot import parse_despot
+    try:
+        return parse_despot(word)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def grain_arg(word: str):
     """--grain: SIGMA or s0,...,s15 -> the 16 knots; auto / auto:SHARE -> ("auto", share)."""
     from .grain import parse_grain
@@ -223,6 +232,29 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--deflicker_out", default=None, metavar="FILE",
                     help="--deflicker: write one line per frame, 'r mean_in mean_out chroma_gain', and a last line with the rms second difference of "
                          "the frame means before and after")
+    ap.add_argument("--despot", type=despot_arg, default=None, metavar="T",
+                    help="take dirt, dust, blotches and dropouts -- small regions that are wrong in exactly ONE frame -- out of IN on the device, in "
+                         "front of everything else and behind --deflicker: a luma sample that differs from both motion-compensated neighbours "
+                         "(frames f - 1 and f + 1 along one integer vector per 16 x 16 block) in the same direction by more than T + |p - n| is a "
+                         "seed, T in 8-bit codes (1 .. 255; 24 is a start); seeds with --despot_support seeds around them, grown by --despot_grow, "
+                         "become the mean of the two neighbours; inside its scene under a listed --scene_cuts, whose first and last frame leave as "
+                         "they came; payloads to payloads, no colour conversion.  The despotted stream is THE input of all the rest.  One threshold "
+                         "in codes, not scaled to the footage's noise; dirt that stays for two frames and line scratches are not found; small fast "
+                         "objects that are in one place for one frame ARE taken for dirt; the repair is soft; luma alone decides; nobody has judged "
+                         "it on real footage; not together with --add_noise or --add_blur; default: off")
+    ap.add_argument("--despot_support", type=int, default=2, metavar="K",
+                    help="--despot: a seed counts only with at least K seeds among its eight neighbours, 0 .. 8: dirt comes in blobs, noise in single "
+                         "samples (default 2)")
+    ap.add_argument("--despot_grow", type=int, default=1, metavar="G",
+                    help="--despot: the mask is grown by G samples, 0 .. 2: a blotch has a soft edge that stays under T (default 1)")
+    ap.add_argument("--despot_chroma", choices=["follow", "off"], default="follow",
+                    help="--despot: 'follow' repairs a chroma sample where its luma is repaired (default); 'off' leaves chroma as it came")
+    ap.add_argument("--despot_max_share", type=float, default=0.05, metavar="S",
+                    help="--despot: a frame of which more than this share would be replaced -- a flash, a frame under uncorrected flicker, a cut the "
+                         "motion search could not follow -- is handed on as it came, in (0, 1] (default 0.05)")
+    ap.add_argument("--despot_out", default=None, metavar="FILE",
+                    help="--despot: write one line per frame, 'seeds replaced share kept', and a last line with the median share and the number of "
+                         "frames kept")
     ap.add_argument("--grain", type=grain_arg, default=None, metavar="{SIGMA,s0,...,s15,auto,auto:SHARE}",
                     help="put fine grain back on the stream written, on the device, behind everything else ('denoise, encode, re-grain'): SIGMA is its "
                          "level in the unit of --sigma, the sigma of i.i.d. noise on 8-bit R'G'B' whose luma part the grain equals; 16 comma-separated "
@@ -310,6 +342,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     from . import lib as L
     from . import noise, picture as pic, scenes
     from .deflicker import deflicker_form, format_deflicker, mean_roughness
+    from .despot import despot_form, format_despot, frames_kept, median_share
     from .grain import grain_form
     from .io_edges import yuv_fmt
     from .restore import VideoRestorer, load_net
@@ -366,6 +399,16 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         deflicker_form(a.deflicker, a.deflicker_chroma)
     except ValueError as e:
         ap.error(f"--deflicker / --deflicker_chroma: {e}")
+    if a.despot is None and a.despot_out is not None:             # as above: before any file is opened
+        ap.error("--despot_out needs --despot")
+    for flag, other in (("--add_noise", a.add_noise), ("--add_blur", a.add_blur)):
+        if a.despot is not None and other is not None:
+            ap.error(f"--despot together with {flag}: {flag} makes a degraded copy of a clean stream for an experiment, --despot repairs a stream "
+                     "that carries dirt; pick one")
+    try:
+        despot_form(a.despot, a.despot_support, a.despot_grow, a.despot_chroma, a.despot_max_share)
+    except ValueError as e:
+        ap.error(f"--despot / --despot_support / --despot_grow / --despot_chroma / --despot_max_share: {e}")
     if a.grain is None and a.grain_out is not None:               # as above: before any file is opened
         ap.error("--grain_out needs --grain")
     try:
@@ -467,11 +510,16 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                            ensemble_time=a.ensemble_time, window_overlap=a.window_overlap, report_quality=report_quality, niqe_params=a.niqe_params,
                            add_noise=a.add_noise, add_noise_seed=a.add_noise_seed, add_blur=a.add_blur, add_blur_gamma=a.add_blur_gamma,
                            grain=a.grain, grain_size=a.grain_size, grain_chroma=a.grain_chroma, grain_seed=a.grain_seed,
-                           deflicker=a.deflicker, deflicker_chroma=a.deflicker_chroma)
+                           deflicker=a.deflicker, deflicker_chroma=a.deflicker_chroma, despot=a.despot, despot_support=a.despot_support,
+                           despot_grow=a.despot_grow, despot_chroma=a.despot_chroma, despot_max_share=a.despot_max_share)
         wdeg = None
         if a.deflicker is not None:
             log(f"deflicker: one tone curve per frame from the median of {2 * a.deflicker + 1} luma histograms, chroma {a.deflicker_chroma}; the "
                 f"deflickered stream is the input of all the rest{'; the windows cross the cuts --scene_cuts auto finds' if a.scene_cuts == 'auto' else ''}")
+        if a.despot is not None:
+            log(f"despot: threshold {a.despot} (8-bit codes), support {a.despot_support}, grow {a.despot_grow}, chroma {a.despot_chroma}, at most "
+                f"{a.despot_max_share:g} of a frame; {'behind deflicker; ' if a.deflicker is not None else ''}the despotted stream is the input of "
+                f"all the rest{'; the windows cross the cuts --scene_cuts auto finds' if a.scene_cuts == 'auto' else ''}")
         if a.add_blur is not None:
             log(f"added blur: the mean of {a.add_blur} frame{'' if a.add_blur == 1 else 's'} (a box of {a.add_blur} frame times at F{hd.fps}), "
                 f"{'of the RGB values as they are' if a.add_blur_gamma == 1.0 else 'in linear light through gamma %g' % a.add_blur_gamma}; "
@@ -549,6 +597,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             log(f"deflicker (R {vr.deflicker}, chroma {vr.deflicker_chroma}): rms second difference of the frame means "
                 f"{mean_roughness([f[1] for f in fd]):.4f} before, {mean_roughness([f[2] for f in fd]):.4f} after, in luma codes over {len(fd)} "
                 f"frame{'' if len(fd) == 1 else 's'} (one curve per frame; unvalidated on real footage)")
+        if vr.despot is not None:
+            fd = vr.stats["frame_despot"]
+            _write_out(a.despot_out, _text_writer(format_despot), fd)
+            log(f"despot (T {vr.despot}, K {vr.despot_support}, G {vr.despot_grow}, chroma {vr.despot_chroma}): median share replaced "
+                f"{median_share(fd):.6f}, {frames_kept(fd)} frame{'' if frames_kept(fd) == 1 else 's'} kept as they came, over {len(fd)} "
+                f"frame{'' if len(fd) == 1 else 's'} (one threshold in codes; unvalidated on real footage)")
         if vr.grain_part is not None:
             wg = vr.stats["window_grain"]
             _write_out(a.grain_out, _text_writer(noise.format_curves), wg, "the grain put back: " + vr.grain_part.how)

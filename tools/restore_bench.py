@@ -71,6 +71,10 @@
             interleaved; microseconds per launch, TB/s of each case's own bytes and the histogram's flat-to-noisy ratio (3.39).  --mode forward:
             steady-state wall time per 720p window of the pipelined deblurrer without and with deflicker=3 on a stream whose luma flickers by +-8 %,
             runs of the two alternating in one process, the first two windows left out.
+  despot  : --mode kernels: sn_yuv_despot (chroma follow and off) on the 14 frames of 16 payloads of 1280 x 720 that have two neighbours, and the two
+            sn_yuv_block_motion launches that make its vectors, at 8-bit and 10-bit 4:2:0, beside a plain device copy of the 16 payloads,
+            interleaved; microseconds per call and TB/s of each case's own bytes (3.40).  --mode forward: steady-state wall time per 720p window
+            of the pipelined deblurrer without and with despot=24, runs of the two alternating in one process, the first two windows left out.
 Prints one JSON object per part.
 """
 import argparse
@@ -1016,6 +1020,97 @@ def deflicker_forward(a):
                       "runs": a.runs, "deflicker_launches": seen[True], "mean_roughness_before_after": seen["roughness"], **res}))
 
 
+def despot_kernels(a):
+    """3.40: sn_yuv_despot on the 14 frames of 16 payloads of 720p that have two neighbours, and the two sn_yuv_block_motion launches that make its
+    vectors (on the stack and on the time-reversed stack, as despot_vectors makes them), at 8-bit and 10-bit 4:2:0, beside a plain device copy of
+    the 16 payloads, interleaved."""
+    from shiftnet_amd.io_edges import despot_yuv
+    T, H, W = 16, 720, 1280
+    blur, _ = synth.blurred_clip(4, H, W, seed=1)
+    rgb = ingest_u8(torch.from_numpy(np.concatenate([blur, blur[::-1]] * 2)).cuda(), torch.float32)[0]      # consecutive frames are neighbours
+    g = torch.Generator("cuda").manual_seed(1)
+    noisy = (rgb + torch.randn(rgb.shape, device="cuda", generator=g) * (5.0 / 255)).clamp(0, 1)
+    cases, nbytes, replaced = {}, {}, {}
+    for bits in (8, 10):
+        f = yuv_fmt(bits, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+        fb, esz = f.frame_bytes(H, W), 1 if bits == 8 else 2
+        src = egress_yuv(noisy, f, H, W)
+        rev = src.flip(0).contiguous()
+        dst = torch.empty_like(src)
+        mvn, sad = block_motion_yuv(src, f, H, W)
+        mvr, sadr = block_motion_yuv(rev, f, H, W)
+        mvp = mvr.flip(0).contiguous()
+        counts = torch.empty((T - 2, 2), dtype=torch.int32, device="cuda")
+        cases[f"copy_payloads_{bits}"] = lambda src=src, dst=dst: dst.copy_(src, non_blocking=True)
+        nbytes[f"copy_payloads_{bits}"] = 2 * T * fb
+        cases[f"block_motion_both_ways_{bits}"] = lambda src=src, rev=rev, f=f, mvn=mvn, sad=sad, mvr=mvr, sadr=sadr: (
+            block_motion_yuv(src, f, H, W, out_mv=mvn, out_sad=sad), block_motion_yuv(rev, f, H, W, out_mv=mvr, out_sad=sadr))
+        nbytes[f"block_motion_both_ways_{bits}"] = 2 * T * H * W * esz                       # the luma planes, read once per direction
+        for chroma in ("follow", "off"):
+            cases[f"despot_{bits}_{chroma}"] = lambda src=src, f=f, mvp=mvp, mvn=mvn, dst=dst, counts=counts, chroma=chroma: despot_yuv(
+                src, f, H, W, mvp, mvn, 1, T - 2, 24, 2, 1, chroma, out=dst[:T - 2], out_counts=counts)
+            nbytes[f"despot_{bits}_{chroma}"] = (T - 2) * (2 * fb + 2 * H * W * esz)             # a frame read and written once, two neighbours' luma read
+        despot_yuv(src, f, H, W, mvp, mvn, 1, T - 2, 24, 2, 1, "follow", out=dst[:T - 2], out_counts=counts)
+        replaced[bits] = round(float(counts.cpu().numpy().view(np.uint32)[:, 1].mean()) / (H * W), 6)
+    for fn in cases.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in cases}
+    for _ in range(a.reps):
+        for k, fn in cases.items():                                                  # interleaved: every repetition times every kernel
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.inner):
+                fn()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.inner)
+    res = {k: {"us_per_call": summary([m * 1e3 for m in v]), "tb_per_s": summary([nbytes[k] / (m * 1e-3) / 1e12 for m in v]), "bytes": nbytes[k]} for k, v in ms.items()}
+    print(json.dumps({"part": "despot", "mode": "kernels", "frames": T, "repaired": T - 2, "size": [H, W], "reps": a.reps, "inner": a.inner,
+                      "note": "despot includes the memset of its counts; block_motion_both_ways is two launches", "mean_share_replaced": replaced, **res}))
+
+
+def despot_forward(a):
+    """3.40: steady-state wall and forward time per 720p window of the pipelined deblurrer without and with despot=24, runs of the two alternating in
+    one process, the first two windows left out."""
+    H, W, one_len, nwin = 720, 1280, 16, a.windows
+    n = one_len * nwin
+    fmt = yuv_fmt(8, L.SN_YUV_420_CENTER, L.SN_YUV_BT709, L.SN_YUV_LIMITED)
+    frames = _stream(H, W, n, fmt, n_src=8)
+    net = restore.load_net("deblur_small", "synthetic", "bf16")
+    seen = {}
+
+    def run(on):
+        vr = restore.VideoRestorer(net, one_len, pipeline=True, **(dict(despot=24) if on else {}))
+        stamps = []
+        t0 = time.perf_counter()
+        for i, p in enumerate(vr.restore(iter(frames), fmt, H, W)):
+            if (i + 1) % one_len == 0:
+                stamps.append(time.perf_counter())
+        total = time.perf_counter() - t0
+        seen[on] = vr.stats.get("despot_launches")
+        if on:
+            from shiftnet_amd.despot import frames_kept, median_share
+            seen["share"] = [round(median_share(vr.stats["frame_despot"]), 6), frames_kept(vr.stats["frame_despot"])]
+        gaps = [(b - c) * 1e3 for b, c in zip(stamps[1:], stamps[:-1])]
+        return {"total_s": total, "window_wall_ms": gaps[1:], "window_forward_ms": vr.stats["window_forward_ms"][2:]}
+
+    run(False)                                                                       # warm-up: code objects, engine buffers
+    run(True)
+    runs = {"off": [], "despot": []}
+    for _ in range(a.runs):
+        runs["off"].append(run(False))
+        runs["despot"].append(run(True))
+    res = {}
+    for k, rs in runs.items():
+        res[k] = {"window_wall_ms": summary([g for r in rs for g in r["window_wall_ms"]]),
+                  "window_wall_ms_per_run": [round(statistics.median(r["window_wall_ms"]), 2) for r in rs],
+                  "window_forward_ms": summary([g for r in rs for g in r["window_forward_ms"]]), "total_s": [round(r["total_s"], 3) for r in rs]}
+    print(json.dumps({"part": "despot", "mode": "forward", "variant": "deblur_small", "dtype": "bf16", "one_len": one_len, "windows": nwin, "size": [H, W],
+                      "runs": a.runs, "despot_launches": seen[True], "median_share_and_frames_kept": seen["share"], **res}))
+
+
 def _tile_word(word):
     return None if word == "full" else restore.tile_arg(word)
 
@@ -1319,7 +1414,7 @@ def picture_part(a):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion", "tiles", "overlap", "quality", "fullref", "degrade", "grain", "deflicker"])
+    ap.add_argument("part", choices=["kernels", "pipeline", "sigma", "picture", "nlf", "report", "motion", "tiles", "overlap", "quality", "fullref", "degrade", "grain", "deflicker", "despot"])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--inner", type=int, default=200)
     ap.add_argument("--windows", type=int, default=8)
@@ -1331,7 +1426,7 @@ if __name__ == "__main__":
                     "csrc/sn_yuv.hip alone; its sn_ingest_yuv / sn_egress_yuv are timed beside this build's.  nlf and motion parts in kernels mode: a library "
                     "built from another commit's whole csrc; its seven noise-histogram entry points are timed beside this build's, at 8 and 10 bit")
     ap.add_argument("--only_cases", default=None, metavar="WORDS", help="kernels part: time only the cases whose name contains one of these comma-separated words")
-    ap.add_argument("--mode", choices=["forward", "kernels", "quality"], default="forward", help="picture, nlf, report, motion, tiles, overlap, quality, fullref, degrade, grain and deflicker parts: which measurement "
+    ap.add_argument("--mode", choices=["forward", "kernels", "quality"], default="forward", help="picture, nlf, report, motion, tiles, overlap, quality, fullref, degrade, grain, deflicker and despot parts: which measurement "
                     "(quality: the tiles part alone)")
     ap.add_argument("--picture", choices=["auto", "fixed"], default="auto", help="picture part, forward mode: VideoRestorer(picture='auto') or the rectangle itself")
     ap.add_argument("--tile", action="append", default=None, metavar="{full,N,HxW}", help="tiles part, forward mode: a form to run (repeat for several, which then alternate)")
@@ -1351,4 +1446,5 @@ if __name__ == "__main__":
          "fullref": fullref_kernels if a.mode == "kernels" else fullref_forward,
          "degrade": degrade_kernels if a.mode == "kernels" else degrade_forward,
          "grain": grain_kernels if a.mode == "kernels" else grain_forward,
-         "deflicker": deflicker_kernels if a.mode == "kernels" else deflicker_forward}[a.part](a)
+         "deflicker": deflicker_kernels if a.mode == "kernels" else deflicker_forward,
+         "despot": despot_kernels if a.mode == "kernels" else despot_forward}[a.part](a)
